@@ -15,6 +15,13 @@ per-step collective): "weak" scaling, value = all ranks' frames / max-over-ranks
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and
 `cpu_baseline` objects.  Inputs are resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything
+else the line can carry, each measured after the timed region: the Mimi decode report
+(`mimi`), the live per-kernel timings (`roofline.dominant_kernels`), the `extras` legs (configs
+3 / 4 / 5, long context, the reference-style loop) and the CPU oracle (`cpu_baseline`); without
+it those fields are null.  `--dump-outputs DIR` writes the frame of codes that the last timed
+step produced, (B, 32) as float32, to DIR/codes_last_step.npy (rank 0).
 """
 import argparse
 import ctypes
@@ -499,6 +506,10 @@ def main():
     ap.add_argument("--tiny", action="store_true", help="tiny shapes (plumbing check only; not a valid bench)")
     ap.add_argument("--no-extras", action="store_true", help="skip the config-3 / config-5 / long-context legs (N=1 only)")
     ap.add_argument("--extra-steps", type=int, default=40)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the Mimi report, the per-kernel timings, the extras legs and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the codes of the last timed step to DIR/codes_last_step.npy (float32)")
     args = ap.parse_args()
     if args.cpu_worker:
         cpu_worker(args)
@@ -619,10 +630,15 @@ def main():
     frames, eos = model.read_frames(B)
     assert frames.shape[0] == 1 + args.warmup + args.steps
     assert int((frames < 0).sum()) == 0 and int(frames.max()) < margs.audio_vocab_size
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: one frame of 32 codes per utterance (codes < 2^24: exact in float32)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "codes_last_step.npy"), frames[-1].numpy().astype(np.float32))
 
     # ---- Mimi decode of the generated frames (reported separately, never inside `value`) ----
     mimi = None
-    if not args.tiny and not args.no_mimi:
+    if args.full and not args.tiny and not args.no_mimi:
         from sesameai.mimi import MimiArgs, MimiCodec
         mimi_sd = None
         if multi:                                      # rank 0 seeds the codec's weights too; one more flat broadcast
@@ -716,7 +732,7 @@ def main():
         else:                                 # the pass measured other kernel sources: not this run's traffic
             traffic_src["stale_traffic_bytes_per_frame"] = pj.get("traffic_bytes_per_frame")
             traffic_src["note"] += "; the pass was taken on DIFFERENT kernel sources (digest mismatch), so `traffic` is null"
-    kernels = None if (args.tiny or args.weights != "bf16") else dominant_kernels(model, B, args.temperature, args.topk)
+    kernels = None if (not args.full or args.tiny or args.weights != "bf16") else dominant_kernels(model, B, args.temperature, args.topk)
     paths = model.describe()               # which kernels ran + every CSM_* / MIMI_* switch set (csm_describe): the line says what it measured
     out = {
         "metric": "audio frames/sec", "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
@@ -757,10 +773,10 @@ def main():
             out["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version())
         except Exception:
             out["rccl_version"] = None
-    if not multi and B == 1 and not args.tiny and not args.no_extras and args.weights == "bf16":
+    if args.full and not multi and B == 1 and not args.tiny and not args.no_extras and args.weights == "bf16":
         del model
         out["extras"] = extras_legs(args, margs, sd, dev)
-    elif multi and not args.tiny and not args.no_extras and args.weights == "bf16":
+    elif args.full and multi and not args.tiny and not args.no_extras and args.weights == "bf16":
         # ---- BASELINE config 4: B = 32 per GPU on every rank (batch 32 x N sharded over the N GPUs, no per-step collective);
         #      aggregate = all ranks' frames / the slowest rank's time, like `value`
         del model
@@ -780,7 +796,7 @@ def main():
         # the oracle beside it, on this host's cores, after the timed region.  The other ranks wait for it ASLEEP -- a key in the
         # rendezvous store, polled with sleeps -- not in an RCCL barrier, whose waiters spin on host cores and GPU queues beside the
         # CPU run that is being timed
-        out["cpu_baseline"] = cpu_baseline(args) if not (args.no_cpu_baseline or args.tiny) else None
+        out["cpu_baseline"] = cpu_baseline(args) if args.full and not (args.no_cpu_baseline or args.tiny) else None
         print(json.dumps(out), flush=True)
     if dist is not None:
         store = getattr(dist.distributed_c10d, "_get_default_store", lambda: None)()

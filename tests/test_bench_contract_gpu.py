@@ -33,6 +33,34 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert abs(d["value"] - 1000.0 / d["ms_per_step"]) / d["value"] < 0.02          # B = 1: frames/s == 1 / step time
 
 
+def test_plain_run_prints_the_headline_only_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run (no --full) is the headline alone: the Mimi report, the per-kernel timings, the extras and the CPU baseline stay null.
+    --dump-outputs writes the last timed step's codes as float32; the inputs are seeded, so two runs with the same arguments dump the
+    same array."""
+    import numpy as np
+    from sesameai.models import csm_tiny_args
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tiny", "--steps", "7", "--warmup", "2",
+                            "--ctx-text", "5", "--ctx-frames", "8", "--gen-text", "4", "--dump-outputs", str(out_dir)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, f"stdout must hold exactly one line, got {len(lines)}"
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 1000.0 / d["ms_per_step"]) / d["value"] < 0.02
+        assert d["mimi"] is None and d["cpu_baseline"] is None and d["roofline"]["dominant_kernels"] is None and "extras" not in d
+        a = np.load(out_dir / "codes_last_step.npy")
+        assert a.dtype == np.float32 and a.shape == (1, 32), (a.dtype, a.shape)
+        assert (a == np.round(a)).all() and a.min() >= 0 and a.max() < csm_tiny_args().audio_vocab_size
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1]), "two runs with the same arguments dumped different codes"
+
+
 def test_bench_self_launches_its_ranks_when_no_launcher_is_present():
     """`python bench.py --gpus 2` with no torchrun around it: the GPU-free parent spawns both ranks and relays rank 0's
     line (it used to exit 2).  BENCH_SHARE_GPU0=1 lets the two ranks share the box's one GPU over gloo --
@@ -107,7 +135,7 @@ def test_two_full_size_ranks_carry_the_config4_leg_and_honest_kernel_entries():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["BENCH_SHARE_GPU0"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--extra-steps", "3",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=1500, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     c4 = d["extras"]["config4"]
@@ -145,8 +173,8 @@ def test_single_gpu_line_names_the_kernels_it_timed():
     reference-style host loop, the long-context step, config 5 and config 5 at B = 32."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--extra-steps", "6", "--no-cpu-baseline", "--no-mimi"],
-                       capture_output=True, text=True, timeout=1500)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--extra-steps", "6", "--no-cpu-baseline", "--no-mimi",
+                        "--full"], capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     names = [k["kernel"] for k in d["roofline"]["dominant_kernels"]]
