@@ -38,6 +38,11 @@ Files (all torch.save'd dicts of small tensors):
                     steps at positions S and S + 1 (top-8 logits, codes, margins, the bf16-vs-fp32 gap), bf16 and fp8-dequantised; plus 64
                     CONSECUTIVE teacher-forced steps after a 740-row prompt (positions 740..803: across the one-launch backbone layer's
                     switch from one CU per head to the key range split over 8 CUs at 768).
+  csm1b_norms.pt    CSM-1B checkpoints whose RMSNorm scales are not 1 (oracle.csm_ref.norm_test_weights, seed 1234: `jitter` and
+                    `outlier`), legs A-F of NORMS_LEGS (bf16 / fp8-dequantised, config-2 and config-5 prompts): top-8 logits, codes,
+                    margins and the bf16-vs-fp32 gap per frame; for legs A and E the move of the logits (at the golden's top-8
+                    indices, frame 0) under each scale fault of oracle.csm_ref.NORM_FAULTS that clears 1.5 x the leg's gap.
+                    About 2 minutes on 8 CPU threads.
 """
 from __future__ import annotations
 
@@ -357,6 +362,78 @@ def possweep_golden(shape: C.CsmShape, weights, sizes, consec_s: int, consec_fra
     return out
 
 
+# ---- norm-test checkpoints (RMSNorm scales != 1) ---------------------------------------------------------------------------------------
+NORMS_PROMPTS = dict(cfg2=dict(seed=2025), cfg5=dict(seed=5000, segments=10, ctx_text=30, ctx_frames=100))     # config 2 (S = 190), config 5 (S = 1334)
+NORMS_LEGS = (          # leg, checkpoint, weights, prompt, teacher-forced frames
+    ("A", "jitter", "bf16", "cfg2", 4),
+    ("B", "jitter", "fp8", "cfg2", 4),
+    ("C", "jitter", "bf16", "cfg5", 2),
+    ("D", "jitter", "fp8", "cfg5", 2),
+    ("E", "outlier", "bf16", "cfg2", 4),
+    ("F", "outlier", "fp8", "cfg2", 2),
+)
+NORMS_FAULT_LEGS = ("A", "E")
+NORMS_FAULT_MIN = 1.5   # a stored fault moves the logits by at least this many x its leg's gap
+NORMS_SEED = 1234
+
+
+def norms_prompt(shape: C.CsmShape, name: str):
+    return bench_prompt(shape, **NORMS_PROMPTS[name])
+
+
+@torch.inference_mode()
+def norm_fault_delta(shape: C.CsmShape, weights, gold, tok, msk, fault: str) -> torch.Tensor:
+    """Frame 0, teacher-forced on the golden codes, with a scale fault edited into the weights: max |dlogit| at the golden's top-8
+    indices against the golden's top-8 values -- the statistic the GPU test asserts on."""
+    m = C.OracleModel(shape, C.norm_fault_weights(shape, weights, fault))
+    m.setup_caches(1)
+    tr = C.FrameTrace()
+    m.generate_frame(tok.unsqueeze(0), msk.unsqueeze(0), torch.arange(tok.shape[0]).unsqueeze(0), 1.0, 1, greedy=True,
+                     forced=gold["codes"][0].unsqueeze(0), trace=tr)
+    lg = torch.stack(tr.logits, 0)[:, 0].float()
+    return (torch.gather(lg, 1, gold["top_i"][0].long()) - gold["top_v"][0].float()).abs().max()
+
+
+def norms_golden(shape: C.CsmShape):
+    """Legs A-F (NORMS_LEGS) in frames_golden's layout, and for legs A and E the four scale faults of C.NORM_FAULTS on frame 0.
+    Every fault kept moves the logits by >= NORMS_FAULT_MIN x the leg's gap; the piece permutation must clear it on A or on E."""
+    gold = dict(weight_seed=NORMS_SEED, prompts={k: dict(v) for k, v in NORMS_PROMPTS.items()}, prompt_checksum={}, legs={})
+    prompts = {k: norms_prompt(shape, k) for k in NORMS_PROMPTS}
+    for k, (tok, msk) in prompts.items():
+        gold["prompt_checksum"][k] = torch.stack([tok.sum(), msk.sum(), torch.tensor(tok.shape[0])])
+    for variant in ("jitter", "outlier"):
+        w = C.norm_test_weights(shape, seed=NORMS_SEED, outliers=variant == "outlier")
+        w8 = None
+        for leg, v, dtype, pname, n in NORMS_LEGS:
+            if v != variant:
+                continue
+            t0 = time.time()
+            if dtype == "fp8" and w8 is None:
+                w8 = C.fp8_dequantized(w)
+            wts = w8 if dtype == "fp8" else w
+            tok, msk = prompts[pname]
+            g = frames_golden(shape, wts, (tok, msk), n, keep_full=False, with_fp32=True, quiet=True)
+            del g["prompt_tokens"], g["prompt_mask"]
+            g.update(checkpoint=v, weights=dtype, prompt=pname, rows=tok.shape[0])
+            if dtype == "fp8":
+                g["deq_checksum"] = torch.stack([w8["backbone.layers.3.mlp.w2.weight"].float().abs().sum(),
+                                                 w8["decoder.layers.1.attn.q_proj.weight"].float().abs().sum(), w8["audio_head"].float().abs().sum()])
+            gap = float(g["bf16_vs_fp32_gap"].max())
+            msg = f"  leg {leg} ({v}, {dtype}, S={tok.shape[0]}, {n} frames): gap {gap:.4f}"
+            if leg in NORMS_FAULT_LEGS:
+                faults = {f: norm_fault_delta(shape, wts, g, tok, msk, f) for f in C.NORM_FAULTS}
+                msg += "; faults " + ", ".join(f"{f} {float(d):.3f} ({float(d) / gap:.1f} x)" for f, d in faults.items())
+                g["faults"] = {f: d for f, d in faults.items() if float(d) >= NORMS_FAULT_MIN * gap}
+            print(msg + f"  [{time.time() - t0:.0f}s]", flush=True)
+            gold["legs"][leg] = g
+        del w, w8
+    for leg in NORMS_FAULT_LEGS:
+        kept = gold["legs"][leg]["faults"]
+        assert leg != "A" or all(f in kept for f in C.NORM_FAULTS if f != "bb7_sa_pieces"), f"leg A: a scale fault is within {NORMS_FAULT_MIN} x gap"
+    assert any("bb7_sa_pieces" in gold["legs"][leg]["faults"] for leg in NORMS_FAULT_LEGS), "the piece permutation clears 1.5 x gap on neither leg A nor E"
+    return gold
+
+
 def sampler_cases():
     g = torch.Generator().manual_seed(77)
     V = 2051
@@ -495,6 +572,8 @@ def main():
         gold["fp8"] = possweep_golden(shape, C.fp8_dequantized(w), POSSWEEP_S, CONSEC_S, CONSEC_FRAMES)
         torch.save(gold, os.path.join(OUT, "csm1b_possweep.pt"))
         del w
+    if want("norms"):
+        torch.save(norms_golden(C.csm_1b()), os.path.join(OUT, "csm1b_norms.pt"))
     if a.only == "decisivefinish":          # re-derive the checksums / PCM of existing files without re-running the trajectories
         for fname, shape, full in (("tiny_decisive.pt", C.csm_tiny(), False), ("csm1b_decisive.pt", C.csm_1b(), True)):
             path = os.path.join(OUT, fname)

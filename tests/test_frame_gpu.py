@@ -688,14 +688,18 @@ def test_long_prompt_kernel_keeps_rows_independent_of_row_count():
     assert torch.equal(res[0][1][:, :3], res[1][1])
 
 
-def test_layer0_qkv_table_gives_the_same_bits_as_computing_it(monkeypatch):
+@pytest.mark.parametrize("checkpoint", ["bench", "jitter"])
+def test_layer0_qkv_table_gives_the_same_bits_as_computing_it(monkeypatch, checkpoint):
     """The depth decoder's layer-0 q/k/v of steps >= 2 come from a table precomputed with the production kernel
     (csm_engine.hip build_qkv0_table); CSM_QKV0_TABLE=0 computes them per step.  Same logits, same frames, bit for bit,
-    for B = 1 and B = 2 (the GEMV path)."""
+    for B = 1 and B = 2 (the GEMV path).  The table is the one place decoder layer 0's sa_norm is applied at load time: the
+    `jitter` checkpoint (oracle.csm_ref.norm_test_weights) has scales != 1, so a table built without them, or with another
+    layer's, differs."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
+    from oracle import csm_ref as C
     from sesameai.models import Model, csm_tiny_args, synthetic_state_dict
-    sd = synthetic_state_dict(csm_tiny_args(), seed=1234)
+    sd = synthetic_state_dict(csm_tiny_args(), seed=1234) if checkpoint == "bench" else C.norm_test_weights(C.csm_tiny(), seed=1234)
     g = torch.Generator().manual_seed(3)
     S = 12
     tok = torch.zeros(2, S, 33, dtype=torch.long); msk = torch.zeros(2, S, 33, dtype=torch.bool)
@@ -1259,7 +1263,7 @@ def _same_until_a_near_tie(got, want, margin, noise, what, tie=NEAR_TIE):
     return first
 
 
-def _teacher_forced(m, gold, S, n_frames, noise, what):
+def _teacher_forced(m, gold, S, n_frames, noise, what, tie=NEAR_TIE, max_excused=0.08):
     """depth() on the current backbone state for golden frames 0..n-1, feeding the golden codes back one row at a time."""
     max_diff, mism = 0.0, []
     for f in range(n_frames):
@@ -1276,9 +1280,10 @@ def _teacher_forced(m, gold, S, n_frames, noise, what):
     print(f"{what}: max|dlogit|={max_diff:.4f} (oracle bf16-vs-fp32 gap {noise:.4f}); {len(mism)} of {32 * n_frames} greedy rows excused as near-ties "
           f"({100.0 * len(mism) / (32 * n_frames):.1f} %): {mism}")
     assert max_diff <= noise, what
-    assert len(mism) <= max(0.08 * 32 * n_frames, 3), f"{what}: too many greedy rows differ from the oracle, near-ties or not" 
+    assert len(mism) <= max(max_excused * 32 * n_frames, 3), f"{what}: too many greedy rows differ from the oracle, near-ties or not" 
     for f, cb, margin in mism:
-        _excuse(margin, noise, f"{what}: greedy index differs at frame {f} codebook {cb}")
+        _excuse(margin, noise, f"{what}: greedy index differs at frame {f} codebook {cb}", tie=tie)
+    return max_diff
 
 
 def test_csm1b_config2_prompt_vs_golden(csm1b):
