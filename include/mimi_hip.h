@@ -106,6 +106,29 @@ int mimi_reset_stream(mimi_handle h, void* stream);
  * work buffers: it ends any stateful decode stream.  n_samples <= hop * max_frames.            */
 int mimi_encode(mimi_handle h, const float* wav, long n_samples, long stride_b, int B, int32_t* codes, void* stream);
 
+/* ---- A pool of stateful decode streams decoded TOGETHER (many callers served from one batch of the frame loop) ----
+ * A pool holds n_streams independent streams: per stream the left-context rows of every causal buffer, a per-layer K/V ring of
+ * tr_context + 2 * max_chunk_frames tokens and its own token offset (RoPE position, window start).  A stream runs for any number of
+ * frames: nothing in it grows with its length.  mimi_pool_decode takes a list of DISTINCT stream ids and the same T new frames for each
+ * (1 <= T <= max_chunk_frames) and runs ONE launch chain for all of them: the streams' rows are stacked along the row axis of every
+ * product, and each kernel maps a global row to (stream, local row) from a small device table, so that no tap and no attention window
+ * reaches into a neighbour.  The K-split choice and every element's summation order depend on the product's shape alone -- a stream's PCM
+ * does not depend on which other streams share the call or on its place in the list, and equals, bit for bit, what a single handle's
+ * stateful mimi_decode gives for the same chunk schedule.
+ * codes: element (i,k,t) at codes[i*stride_s + k*stride_k + t*stride_t], i = index in `streams` (a host array); codes >= codebook_size clamp
+ * as in mimi_decode.  pcm: [n][hop*T] fp32 (device).  Each listed stream continues where its last call ended; mimi_pool_reset starts the
+ * listed streams afresh.  Returns 0, or -1 (bad argument: a duplicate id, an id outside [0, n_streams), T > max_chunk_frames, ...) / -2 (HIP
+ * error) with a message in mimi_pool_last_error; a refused call changes nothing.  Drive ONE HIP stream per pool at a time.
+ * The weights are those of the MimiWeights given (device memory the caller keeps alive); a pool can share them with a mimi_handle.       */
+#define MIMI_POOL_MAX_STREAMS 64
+typedef struct MimiStreamPool* mimi_pool;
+int  mimi_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_pool* out);
+void mimi_pool_destroy(mimi_pool p);
+const char* mimi_pool_last_error(mimi_pool p);      /* p == NULL: why mimi_pool_create failed (this thread) */
+int  mimi_pool_reset(mimi_pool p, const int32_t* streams, int n, void* stream);
+int  mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, const int32_t* codes, int T,
+                      long stride_s, long stride_k, long stride_t, void* pcm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

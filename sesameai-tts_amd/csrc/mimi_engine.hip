@@ -57,6 +57,14 @@ struct GemmArgs {
     // partial tile in kpart[ks][T_in][C_out] with write-through stores, and the LAST of a tile's ksplit blocks to arrive adds the
     // partials in ks order and runs the epilogue.  ksplit is a function of (taps, C_in) alone: streaming == whole decode, bit for bit.
     int ksplit; float* kpart; int* kticket;
+    // Stream pool (the SEG instantiation only; MimiStreamPool below): the T_in rows of the launch are the rows of several streams stacked,
+    // seg_T per stream.  Global row g = si * seg_T + tl belongs to the si-th listed stream; its A rows start at segment * seg_x + tl * in_stride,
+    // its output (residual) row is segment * seg_o (seg_r) + tl * phases + p, where segment = the stream's id (seg_tab[si]) for a buffer that
+    // keeps every stream's history in place (bit 0 / 1 / 2 of seg_by_id: x / out / resid) and si for a dense work buffer.  A tap therefore
+    // reaches back into its OWN stream's history rows, never into its neighbour's.  RoPE position and K/V ring slot come from the stream's
+    // token offset seg_tab[MIMI_POOL_MAX_STREAMS + si].
+    int seg_T, seg_x, seg_o, seg_r, seg_by_id, rope_ring;
+    const int* seg_tab;
 };
 
 __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expf(v) - 1.0f; }
@@ -79,7 +87,7 @@ __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expf(v) - 
 // the weights re-tiled into MFMA operand order so that every wave load is one contiguous 1 KB (the K = 2048 linear 24 us against
 // 19.5 row-major: with one 32-row tile these launches sit on 16..64 CUs and are bound by the fp32 matrix pipe -- 128 dependent
 // 64-cycle v_mfma_f32_32x32x2_f32 per wave, two waves per SIMD = 6.8 us -- plus the ~4.7 us of a dependent launch, not by loads).
-template <bool ELU>
+template <bool ELU, bool SEG = false>
 __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
     __shared__ float red[G32_NW][16][64];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -93,7 +101,11 @@ __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
     const int trow = trow_ok ? (t0 + r) : (a.T_in - 1);
     const int nrow = nrow_ok ? (n0 + r) : (a.C_out - 1);
     const int kchunks = a.C_in / 32, iters = a.taps * kchunks;
-    const int arow0 = trow * a.in_stride + a.shift0;
+    int arow0 = trow * a.in_stride + a.shift0;
+    if (SEG) {
+        const int si = trow / a.seg_T, tl = trow - si * a.seg_T;
+        arow0 = ((a.seg_by_id & 1) ? a.seg_tab[si] : si) * a.seg_x + tl * a.in_stride + a.shift0;
+    }
     const float* const wrow = a.w + ((long)p * a.taps * a.C_out + nrow) * a.C_in + h * 16;
     const int it_lo = a.ksplit > 1 ? ks * (iters / a.ksplit) : 0, it_hi = a.ksplit > 1 ? it_lo + iters / a.ksplit : iters;
     for (int it = it_lo + wave; it < it_hi; it += G32_NW) {
@@ -199,35 +211,41 @@ __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
 #pragma unroll
             for (int w = 0; w < G32_NW; ++w) sum += red[w][reg][lane];          // fixed order
         }
-        const long orow = (long)t * a.phases + p;
+        long orow = (long)t * a.phases + p, rrow = orow;
+        int pos = a.rope_offset + t;                                    // token position (RoPE angle)
+        long kvrow = pos;                                               // its row in the K / V cache
+        if (SEG) {
+            const int si = t / a.seg_T, tl = t - si * a.seg_T, sid = a.seg_tab[si];
+            orow = (long)((a.seg_by_id & 2) ? sid : si) * a.seg_o + (long)tl * a.phases + p;
+            rrow = (long)((a.seg_by_id & 4) ? sid : si) * a.seg_r + (long)tl * a.phases + p;
+            if (a.rope_q) { pos = a.seg_tab[MIMI_POOL_MAX_STREAMS + si] + tl; kvrow = (long)sid * a.rope_ring + pos % a.rope_ring; }
+        }
         float v = sum + bias;
         if (a.rope_q) {                                                 // (whole 32-channel tiles: every lane of the half-wave is here)
             const float partner = __shfl_xor(v, 1, 64);
             const int sec = ch / a.rope_d, cc = ch - sec * a.rope_d;
-            if (sec == 2) { a.rope_v[(long)(a.rope_offset + t) * a.rope_d + cc] = v; continue; }
-            const float ang = (float)(a.rope_offset + t) * a.rope_freqs[(cc & 63) >> 1];
+            if (sec == 2) { a.rope_v[kvrow * a.rope_d + cc] = v; continue; }
+            const float ang = (float)pos * a.rope_freqs[(cc & 63) >> 1];
             const float c = cosf(ang), s = sinf(ang);
             const float o = (cc & 1) ? partner * s + v * c : v * c - partner * s;
             if (sec == 0) a.rope_q[(long)t * a.rope_d + cc] = o;
-            else a.rope_k[(long)(a.rope_offset + t) * a.rope_d + cc] = o;
+            else a.rope_k[kvrow * a.rope_d + cc] = o;
             continue;
         }
         if (a.act_out == 1) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
         if (a.col_scale) v = cs * v;
-        if (a.resid) v = a.resid[orow * a.ldr + ch] + v;
+        if (a.resid) v = a.resid[rrow * a.ldr + ch] + v;
         a.out[orow * a.ldo + ch] = v;
     }
 }
 
 // RVQ decode: q_first = emb_0[c0]; q_rest = sum_{k>=1} emb_k[c_k]; out = Wf q_first + Wr q_rest
-__global__ __launch_bounds__(256) void k_rvq(const int* codes, long stride_k, long stride_t, int T, int ncb, int nsem,
-                                             int cbsize, int cbdim, int hidden, const float* books, const float* pf,
-                                             const float* pr, float* out, long ldo) {
-    extern __shared__ float q[];                 // [2][cbdim] sums, then [ncb] clamped codes
-    const int t = blockIdx.x;
+// (one frame: `codes` points at the frame's codebook 0, `out` at the frame's row; shared by k_rvq and the stream pool's k_pool_rvq)
+__device__ __forceinline__ void rvq_frame(float* q, const int* codes, long stride_k, int ncb, int nsem, int cbsize, int cbdim, int hidden,
+                                          const float* books, const float* pf, const float* pr, float* out) {
     int* cidx = reinterpret_cast<int*>(q + 2 * cbdim);
     for (int k = threadIdx.x; k < ncb; k += blockDim.x)                  // the frame's codes once, not once per thread
-        cidx[k] = min(max(codes[k * stride_k + t * stride_t], 0), cbsize - 1);
+        cidx[k] = min(max(codes[k * stride_k], 0), cbsize - 1);
     __syncthreads();
     for (int d = threadIdx.x; d < cbdim; d += blockDim.x) {
         float s1 = 0.f, s2 = 0.f;
@@ -249,13 +267,25 @@ __global__ __launch_bounds__(256) void k_rvq(const int* codes, long stride_k, lo
             a1 = fmaf(pf[(long)d * hidden + c], q[d], a1);
             a2 = fmaf(pr[(long)d * hidden + c], q[cbdim + d], a2);
         }
-        out[(long)t * ldo + c] = a1 + a2;
+        out[c] = a1 + a2;
     }
+}
+
+__global__ __launch_bounds__(256) void k_rvq(const int* codes, long stride_k, long stride_t, int T, int ncb, int nsem,
+                                             int cbsize, int cbdim, int hidden, const float* books, const float* pf,
+                                             const float* pr, float* out, long ldo) {
+    extern __shared__ float q[];                 // [2][cbdim] sums, then [ncb] clamped codes
+    const int t = blockIdx.x;
+    rvq_frame(q, codes + t * stride_t, stride_k, ncb, nsem, cbsize, cbdim, hidden, books, pf, pr, out + (long)t * ldo);
 }
 
 // depthwise ConvTranspose1d k4 s2, causal: out[2t+p][c] = x[t][c] w[p][0][c] + x[t-1][c] w[p][1][c]
 // (+ the K-split tiles' arrival tickets back to zero: they reset themselves, but only in a launch that completes -- the first kernel of every
 //  pass puts them at zero so that an aborted launch cannot leave a tile one arrival ahead; no launch of its own)
+__device__ __forceinline__ float upsample_tap2(const float* xr, long ldx, const float* w, int p, int C, int c) {
+    return xr[c] * w[(p * 2 + 0) * C + c] + xr[c - ldx] * w[(p * 2 + 1) * C + c];
+}
+
 __global__ void k_upsample(const float* x, long ldx, int T, int C, const float* w, float* out, long ldo, int* tickets, int n_tickets) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (tickets != nullptr)
@@ -265,7 +295,7 @@ __global__ void k_upsample(const float* x, long ldx, int T, int C, const float* 
     const long n = i / C;
     const long t = n >> 1;
     const int p = (int)(n & 1);
-    out[n * ldo + c] = x[t * ldx + c] * w[(p * 2 + 0) * C + c] + x[(t - 1) * ldx + c] * w[(p * 2 + 1) * C + c];
+    out[n * ldo + c] = upsample_tap2(x + t * ldx, ldx, w, p, C, c);
 }
 
 // One wave per row; the row is read ONCE into registers (up to 16 values per lane, d <= 1024) with w and b loads in
@@ -300,15 +330,15 @@ __global__ __launch_bounds__(64) void k_layernorm(const float* x, int d, const f
     }
 }
 
-// causal windowed attention, one wave per (query, head); head_dim 64
-__global__ __launch_bounds__(64) void k_mimi_attn(const float* q, const float* kc, const float* vc, int d, int offset,
-                                                  int context, float* out) {
-    __shared__ float pbuf[1024];
-    const int i = blockIdx.x, hh = blockIdx.y, lane = threadIdx.x;
-    const int pi = offset + i;
+// causal windowed attention, one wave per (query, head); head_dim 64.  qr / outr: the query's and the output's 64 floats of this head;
+// pi: the query's token position; kc / vc: the stream's cache at this head.  RING: position p sits in row p % ring (stream pool), and the
+// keys are still walked in chronological order from the window start, so the sums are those of the linear cache.
+template <bool RING>
+__device__ __forceinline__ void attn_row(float* pbuf, const float* qr, const float* kc, const float* vc, int d, int pi, int context, int ring,
+                                         float* outr) {
+    const int lane = threadIdx.x;
     const int lo = max(0, pi - context + 1);
     const int nk = pi - lo + 1;
-    const float* qr = q + (long)i * d + hh * 64;
     float qv[64];
 #pragma unroll
     for (int e = 0; e < 64; e += 4) {
@@ -317,7 +347,7 @@ __global__ __launch_bounds__(64) void k_mimi_attn(const float* q, const float* k
     }
     float mx = -INFINITY;
     for (int j = lane; j < nk; j += 64) {
-        const float* kr = kc + (long)(lo + j) * d + hh * 64;
+        const float* kr = kc + (long)(RING ? (lo + j) % ring : lo + j) * d;
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < 64; e += 4) {
@@ -336,18 +366,28 @@ __global__ __launch_bounds__(64) void k_mimi_attn(const float* q, const float* k
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     __syncthreads();
     float o = 0.f;
-    for (int j = 0; j < nk; ++j) o = fmaf(pbuf[j], vc[(long)(lo + j) * d + hh * 64 + lane], o);
-    out[(long)i * d + hh * 64 + lane] = o / sum;
+    if (RING) {
+        int row = lo % ring;
+        for (int j = 0; j < nk; ++j) { o = fmaf(pbuf[j], vc[(long)row * d + lane], o); if (++row == ring) row = 0; }
+    } else {
+        for (int j = 0; j < nk; ++j) o = fmaf(pbuf[j], vc[(long)(lo + j) * d + lane], o);
+    }
+    outr[lane] = o / sum;
+}
+
+__global__ __launch_bounds__(64) void k_mimi_attn(const float* q, const float* kc, const float* vc, int d, int offset,
+                                                  int context, float* out) {
+    __shared__ float pbuf[1024];
+    const int i = blockIdx.x, hh = blockIdx.y;
+    attn_row<false>(pbuf, q + (long)i * d + hh * 64, kc + hh * 64, vc + hh * 64, d, offset + i, context, 0, out + (long)i * d + hh * 64);
 }
 
 // final Conv1d (taps x C_in -> 1 channel) with ELU on the input; one thread per output sample
-__global__ void k_conv_out(const float* x, long ldx, long T, int C_in, int taps, const float* w /*[taps][1][C_in]*/,
-                           const float* bias, float* pcm) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
+// (xt: the input row of the output sample's own time step; the earlier taps sit in the rows before it)
+__device__ __forceinline__ float conv_out_sample(const float* xt, long ldx, int C_in, int taps, const float* w, const float* bias) {
     float acc = bias ? bias[0] : 0.f;
     for (int j = 0; j < taps; ++j) {
-        const float* xr = x + (t + j - (taps - 1)) * ldx;
+        const float* xr = xt + (j - (taps - 1)) * ldx;
         const float* wr = w + (long)j * C_in;
         for (int c = 0; c < C_in; c += 4) {
             const float4 v = *reinterpret_cast<const float4*>(xr + c);
@@ -356,7 +396,14 @@ __global__ void k_conv_out(const float* x, long ldx, long T, int C_in, int taps,
             acc = fmaf(elu1(v.z), u.z, acc); acc = fmaf(elu1(v.w), u.w, acc);
         }
     }
-    pcm[t] = acc;
+    return acc;
+}
+
+__global__ void k_conv_out(const float* x, long ldx, long T, int C_in, int taps, const float* w /*[taps][1][C_in]*/,
+                           const float* bias, float* pcm) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    pcm[t] = conv_out_sample(x + t * ldx, ldx, C_in, taps, w, bias);
 }
 
 // slide the left-context window of a [hist + T][C] buffer: new hist rows = last hist rows of (old hist ++ new T rows)
@@ -459,17 +506,23 @@ static hipError_t alloc_hbuf(HBuf& b, int hist, long rows, int C) {
 
 extern "C" void csm_warn_unknown_switches(void);     // csm_engine.hip: names under CSM_ / MIMI_ that no switch reads, once per process
 
+// what the kernels assume of a configuration (mimi_create and mimi_pool_create)
+static const char* config_error(const MimiConfig* cfg) {
+    if (cfg->hidden % 32 || cfg->hidden > 1024 || cfg->codebook_dim % 4 || cfg->tr_ffn % 32 || cfg->hidden / cfg->tr_heads != 64)
+        return "mimi_create: hidden%32, hidden<=1024, tr_ffn%32 and head_dim==64 required";
+    if (cfg->n_stages < 1 || cfg->n_stages > MIMI_MAX_STAGES || cfg->tr_layers > MIMI_MAX_TR_LAYERS || cfg->tr_context > 1024)
+        return "mimi_create: too many stages/layers or context > 1024";
+    if (cfg->kernel > MAX_TAPS || cfg->res_kernel > MAX_TAPS) return "mimi_create: kernel too wide";
+    int c = cfg->n_filters << cfg->n_stages;
+    for (int j = 0; j < cfg->n_stages; ++j) { c /= 2; if ((c / 2) % 32) return "mimi_create: SEANet channels must stay multiples of 32"; }
+    return nullptr;
+}
+
 extern "C" int mimi_create(const MimiConfig* cfg, const MimiWeights* w, int max_frames, int reserved, mimi_handle* out) {
     csm_warn_unknown_switches();
     (void)reserved;
     if (!cfg || !w || !out || max_frames < 1) return mfail(nullptr, "mimi_create: null/invalid argument");
-    if (cfg->hidden % 32 || cfg->hidden > 1024 || cfg->codebook_dim % 4 || cfg->tr_ffn % 32 || cfg->hidden / cfg->tr_heads != 64)
-        return mfail(nullptr, "mimi_create: hidden%32, hidden<=1024, tr_ffn%32 and head_dim==64 required");
-    if (cfg->n_stages < 1 || cfg->n_stages > MIMI_MAX_STAGES || cfg->tr_layers > MIMI_MAX_TR_LAYERS || cfg->tr_context > 1024)
-        return mfail(nullptr, "mimi_create: too many stages/layers or context > 1024");
-    if (cfg->kernel > MAX_TAPS || cfg->res_kernel > MAX_TAPS) return mfail(nullptr, "mimi_create: kernel too wide");
-    int c = cfg->n_filters << cfg->n_stages;
-    for (int j = 0; j < cfg->n_stages; ++j) { c /= 2; if ((c / 2) % 32) return mfail(nullptr, "mimi_create: SEANet channels must stay multiples of 32"); }
+    if (const char* bad = config_error(cfg)) return mfail(nullptr, bad);
     MimiDecoder* m = new MimiDecoder();
     m->cfg = *cfg; m->w = *w; m->max_frames = max_frames; m->offset = 0;
     const int d = cfg->hidden;
@@ -548,10 +601,11 @@ extern "C" int mimi_reset_stream(mimi_handle m, void* stream) {
 }
 
 struct RopeOut { float *q, *k, *v; const float* freqs; int offset, d; };
+struct SegArgs { int T, x, o, r, by_id, ring; const int* tab; };       // GemmArgs.seg_*: a product over the stacked rows of a stream pool
 static hipError_t gemm(hipStream_t st, const float* x, long ldx, long T_in, const float* w, const float* bias, int C_in,
                        int C_out, int taps, int phases, const int* shifts, int elu_in, int act_out, const float* col_scale,
                        const float* resid, long ldr, float* out, long ldo, int in_stride = 1, int edge = 0, int row_lo = 0,
-                       int row_hi = 0, const RopeOut* rope = nullptr, const KSplitWs* ksw = nullptr) {
+                       int row_hi = 0, const RopeOut* rope = nullptr, const KSplitWs* ksw = nullptr, const SegArgs* seg = nullptr) {
     GemmArgs a;
     memset(&a, 0, sizeof a);
     if (rope) { a.rope_q = rope->q; a.rope_k = rope->k; a.rope_v = rope->v; a.rope_freqs = rope->freqs; a.rope_offset = rope->offset; a.rope_d = rope->d; }
@@ -571,6 +625,12 @@ static hipError_t gemm(hipStream_t st, const float* x, long ldx, long T_in, cons
             a.ksplit = ksw->ksplit; a.kpart = ksw->part; a.kticket = ksw->ticket;
             grid.z = (unsigned)ksw->ksplit;
         }
+    }
+    if (seg != nullptr) {
+        a.seg_T = seg->T; a.seg_x = seg->x; a.seg_o = seg->o; a.seg_r = seg->r; a.seg_by_id = seg->by_id; a.rope_ring = seg->ring; a.seg_tab = seg->tab;
+        if (elu_in) hipLaunchKernelGGL((k_gemm32<true, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        else hipLaunchKernelGGL((k_gemm32<false, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        return hipGetLastError();
     }
     if (elu_in) hipLaunchKernelGGL(k_gemm32<true>, grid, dim3(64 * G32_NW), 0, st, a);
     else hipLaunchKernelGGL(k_gemm32<false>, grid, dim3(64 * G32_NW), 0, st, a);
@@ -825,4 +885,296 @@ extern "C" int mimi_decode_strided(mimi_handle m, const int32_t* codes, int B, i
 extern "C" int mimi_decode(mimi_handle m, const int32_t* codes, int B, int T, long stride_b, long stride_k, void* pcm,
                            int stateful, void* stream) {
     return mimi_decode_strided(m, codes, B, T, stride_b, stride_k, 1, pcm, stateful, stream);
+}
+
+// ---- stream pool: N stateful streams decoded by one launch chain (include/mimi_hip.h) ------------------------------------------------
+// Buffers that feed a causal op keep EVERY stream's segment in place: stream s owns rows [s * seg, (s + 1) * seg) with seg = hist + the rows
+// of max_chunk_frames, its history in front -- so a call needs no gather and the slide is what it is for one stream.  Work buffers between
+// two such buffers (tok, ln, q, att, ffn, r1) are dense: the listed streams' rows one after the other.  Products between dense buffers are
+// the plain k_gemm32 over n * rows rows; those that touch a segmented buffer, and the q|k|v projection, are its SEG instantiation.
+struct PBuf {
+    float* base = nullptr;
+    int hist = 0, C = 0;
+    long cap = 0;                                   // rows of one stream's chunk at this level
+    int seg() const { return (int)(hist + cap); }   // rows between two streams' segments
+    float* row0() const { return base + (long)hist * C; }       // row 0 of stream 0
+};
+
+struct MimiStreamPool {
+    MimiConfig cfg;
+    MimiWeights w;
+    int n_streams = 0, max_chunk = 0, ring = 0;
+    std::vector<long> offset;                       // tokens each stream has decoded so far
+    PBuf rvq, a0, s0, u[MIMI_MAX_STAGES], xj[MIMI_MAX_STAGES];
+    float* r1[MIMI_MAX_STAGES] = {};
+    float *tok = nullptr, *ln = nullptr, *q = nullptr, *att = nullptr, *ffn = nullptr;
+    float *kc = nullptr, *vc = nullptr;             // [layer][stream][ring][d]
+    int* tab = nullptr;                             // device table of the running call: [i] stream id, [MIMI_POOL_MAX_STREAMS + i] token offset
+    KSplitWs ksw = {nullptr, nullptr, 0, 0, 0, 0};
+    std::string err;
+};
+
+struct PoolIds { int n; int sid[MIMI_POOL_MAX_STREAMS]; int off[MIMI_POOL_MAX_STREAMS]; };
+#define POOL_MAX_REGIONS (3 + 2 * MIMI_MAX_STAGES)
+struct PoolRegions { float* base[POOL_MAX_REGIONS]; int hist[POOL_MAX_REGIONS], C[POOL_MAX_REGIONS], seg[POOL_MAX_REGIONS]; long T[POOL_MAX_REGIONS]; int count; };
+
+// first kernel of a call: the call's streams and offsets into the device table every later kernel reads, the K-split tickets to zero
+__global__ void k_pool_begin(const PoolIds ids, int* tab, int* tickets, int n_tickets) {
+    for (int i = threadIdx.x; i < ids.n; i += blockDim.x) { tab[i] = ids.sid[i]; tab[MIMI_POOL_MAX_STREAMS + i] = ids.off[i]; }
+    for (int j = threadIdx.x; j < n_tickets; j += blockDim.x) tickets[j] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_pool_rvq(const int* codes, long stride_s, long stride_k, long stride_t, int T, int ncb, int nsem,
+                                                  int cbsize, int cbdim, int hidden, const float* books, const float* pf, const float* pr,
+                                                  float* out /*row 0 of stream 0*/, int seg, const int* tab) {
+    extern __shared__ float q[];
+    const int si = blockIdx.x / T, t = blockIdx.x - si * T;
+    rvq_frame(q, codes + si * stride_s + t * stride_t, stride_k, ncb, nsem, cbsize, cbdim, hidden, books, pf, pr,
+              out + ((long)tab[si] * seg + t) * hidden);
+}
+
+__global__ void k_pool_upsample(const float* x /*row 0 of stream 0*/, int seg, const int* tab, int T, int n, int C, const float* w, float* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)n * T * 2 * C) return;
+    const int c = (int)(i % C);
+    const long g = i / C;                           // dense output row
+    const int si = (int)(g / (2 * T)), nl = (int)(g - (long)si * 2 * T);
+    out[g * C + c] = upsample_tap2(x + ((long)tab[si] * seg + (nl >> 1)) * C, (long)C, w, nl & 1, C, c);
+}
+
+__global__ __launch_bounds__(64) void k_pool_attn(const float* q, const float* kc, const float* vc, int d, int T2, int ring, int context,
+                                                  const int* tab, float* out) {
+    __shared__ float pbuf[1024];
+    const int g = blockIdx.x, hh = blockIdx.y;
+    const int si = g / T2, tl = g - si * T2;
+    const long cache = (long)tab[si] * ring * d + hh * 64;
+    attn_row<true>(pbuf, q + (long)g * d + hh * 64, kc + cache, vc + cache, d, tab[MIMI_POOL_MAX_STREAMS + si] + tl, context, ring,
+                   out + (long)g * d + hh * 64);
+}
+
+__global__ void k_pool_conv_out(const float* x /*row 0 of stream 0*/, int seg, const int* tab, long Tj, int n, int C_in, int taps, const float* w,
+                                const float* bias, float* pcm) {
+    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= Tj * n) return;
+    const int si = (int)(g / Tj);
+    const long tl = g - si * Tj;
+    pcm[g] = conv_out_sample(x + ((long)tab[si] * seg + tl) * C_in, (long)C_in, C_in, taps, w, bias);
+}
+
+// k_slide_hist for every segmented buffer (blockIdx.z) of every listed stream (blockIdx.y) in one launch
+__global__ void k_pool_slide(const PoolRegions z, const int* tab) {
+    const int reg = blockIdx.z, c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= z.C[reg]) return;
+    float* base = z.base[reg] + (long)tab[blockIdx.y] * z.seg[reg] * z.C[reg];
+    for (int r = 0; r < z.hist[reg]; ++r) base[(long)r * z.C[reg] + c] = base[((long)r + z.T[reg]) * z.C[reg] + c];    // ascending r: source is always ahead
+}
+
+__global__ void k_pool_zero_hist(const PoolRegions z, const PoolIds ids) {
+    const int reg = blockIdx.z;
+    float* base = z.base[reg] + (long)ids.sid[blockIdx.y] * z.seg[reg] * z.C[reg];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < z.hist[reg] * z.C[reg]; i += gridDim.x * blockDim.x) base[i] = 0.f;
+}
+
+static int pfail(MimiStreamPool* p, const char* msg) {
+    if (p) p->err = msg; else g_mimi_err = msg;
+    return -1;
+}
+
+// the segmented buffers of a pool, with the rows a chunk of T frames adds to each
+static PoolRegions pool_regions(const MimiStreamPool* p, int T) {
+    PoolRegions z;
+    z.count = 0;
+    auto add = [&](const PBuf& b, long rows) {
+        if (!b.hist) return;
+        z.base[z.count] = b.base; z.hist[z.count] = b.hist; z.C[z.count] = b.C; z.seg[z.count] = b.seg(); z.T[z.count] = rows; ++z.count;
+    };
+    long Tj = 2L * T;
+    add(p->rvq, T); add(p->a0, Tj); add(p->s0, Tj);
+    for (int j = 0; j < p->cfg.n_stages; ++j) { Tj *= p->cfg.ratios[j]; add(p->u[j], Tj); add(p->xj[j], Tj); }
+    return z;
+}
+
+static int pool_alloc(MimiStreamPool* p) {
+    const MimiConfig& c = p->cfg;
+    const int d = c.hidden, N = p->n_streams;
+    const long T2 = 2L * p->max_chunk;
+    auto abuf = [&](PBuf& b, int hist, long rows, int C) {
+        b.hist = hist; b.C = C; b.cap = rows;
+        const size_t bytes = (size_t)N * (hist + rows) * C * 4;
+        hipError_t e = hipMalloc((void**)&b.base, bytes);
+        return e != hipSuccess ? e : hipMemset(b.base, 0, bytes);
+    };
+    MCHK(p, abuf(p->rvq, 1, p->max_chunk, d));
+    MCHK(p, abuf(p->a0, c.kernel - 1, T2, d));
+    int C = c.n_filters << c.n_stages;
+    MCHK(p, abuf(p->s0, 1, T2, C));
+    long Tj = T2;
+    for (int j = 0; j < c.n_stages; ++j) {
+        Tj *= c.ratios[j]; C /= 2;
+        MCHK(p, abuf(p->u[j], c.res_kernel - 1, Tj, C));
+        MCHK(p, hipMalloc((void**)&p->r1[j], (size_t)N * Tj * (C / 2) * 4));
+        MCHK(p, abuf(p->xj[j], (j + 1 < c.n_stages) ? 1 : c.last_kernel - 1, Tj, C));
+    }
+    const long M2 = N * T2;                          // rows of a full call at the transformer's rate
+#define A4(ptr, n) MCHK(p, hipMalloc((void**)&(ptr), (size_t)(n) * 4))
+    A4(p->tok, M2 * d); A4(p->ln, M2 * d); A4(p->q, M2 * d); A4(p->att, M2 * d); A4(p->ffn, M2 * c.tr_ffn);
+    const long kv = (long)c.tr_layers * N * p->ring * d;
+    A4(p->kc, kv); A4(p->vc, kv);
+    A4(p->tab, 2 * MIMI_POOL_MAX_STREAMS);
+    {   // K-split workspace as in mimi_create (same switch, same shapes split: the sums are those of a single handle), sized for a full call
+        const char* ev = getenv("MIMI_KSPLIT");
+        const int want = ev ? atoi(ev) : MIMI_KSPLIT;
+        if (want == 2 || want == 4 || want == 8) {
+            const int ccap = c.n_filters << c.n_stages;
+            p->ksw.ksplit = want; p->ksw.cap_rows = M2; p->ksw.cap_cols = ccap > d ? ccap : d;
+            p->ksw.n_tickets = (int)((M2 + 31) / 32) * ((p->ksw.cap_cols + 31) / 32);
+            A4(p->ksw.part, (long)want * p->ksw.cap_rows * p->ksw.cap_cols);
+            A4(p->ksw.ticket, p->ksw.n_tickets);
+            MCHK(p, hipMemset(p->ksw.ticket, 0, (size_t)p->ksw.n_tickets * 4));
+        }
+    }
+#undef A4
+    MCHK(p, hipDeviceSynchronize());
+    return 0;
+}
+
+extern "C" int mimi_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_pool* out) {
+    csm_warn_unknown_switches();
+    if (!cfg || !w || !out) return pfail(nullptr, "mimi_pool_create: null argument");
+    if (n_streams < 1 || n_streams > MIMI_POOL_MAX_STREAMS) return pfail(nullptr, "mimi_pool_create: n_streams must be 1 .. MIMI_POOL_MAX_STREAMS (64)");
+    if (max_chunk_frames < 1 || max_chunk_frames > 64) return pfail(nullptr, "mimi_pool_create: max_chunk_frames must be 1 .. 64");
+    if (const char* bad = config_error(cfg)) return pfail(nullptr, bad);
+    MimiStreamPool* p = new MimiStreamPool();
+    p->cfg = *cfg; p->w = *w; p->n_streams = n_streams; p->max_chunk = max_chunk_frames;
+    p->ring = cfg->tr_context + 2 * max_chunk_frames;        // a call's oldest key (offset - context + 1) and newest (offset + 2T - 1) never share a row
+    p->offset.assign(n_streams, 0);
+    const int rc = pool_alloc(p);
+    if (rc) { g_mimi_err = p->err; mimi_pool_destroy(p); return rc; }
+    *out = p;
+    return 0;
+}
+
+extern "C" void mimi_pool_destroy(mimi_pool p) {
+    if (!p) return;
+    (void)hipFree(p->rvq.base); (void)hipFree(p->a0.base); (void)hipFree(p->s0.base);
+    for (int j = 0; j < MIMI_MAX_STAGES; ++j) { (void)hipFree(p->u[j].base); (void)hipFree(p->xj[j].base); (void)hipFree(p->r1[j]); }
+    void* ps[] = {p->tok, p->ln, p->q, p->att, p->ffn, p->kc, p->vc, p->tab, p->ksw.part, p->ksw.ticket};
+    for (void* x : ps) (void)hipFree(x);
+    delete p;
+}
+
+extern "C" const char* mimi_pool_last_error(mimi_pool p) { return p ? p->err.c_str() : g_mimi_err.c_str(); }
+
+// distinct ids in range -> PoolIds (offsets filled by the caller); nullptr or the reason
+static const char* pool_ids(const MimiStreamPool* p, const int32_t* streams, int n, PoolIds* ids) {
+    if (!streams || n < 1 || n > p->n_streams) return "stream list: need 1 .. n_streams ids";
+    bool seen[MIMI_POOL_MAX_STREAMS] = {};
+    for (int i = 0; i < n; ++i) {
+        if (streams[i] < 0 || streams[i] >= p->n_streams) return "stream id outside [0, n_streams)";
+        if (seen[streams[i]]) return "duplicate stream id in one call";
+        seen[streams[i]] = true;
+        ids->sid[i] = streams[i]; ids->off[i] = 0;
+    }
+    ids->n = n;
+    return nullptr;
+}
+
+extern "C" int mimi_pool_reset(mimi_pool p, const int32_t* streams, int n, void* stream) {
+    if (!p) return pfail(nullptr, "mimi_pool_reset: null pool");
+    PoolIds ids;
+    if (const char* bad = pool_ids(p, streams, n, &ids)) { p->err = std::string("mimi_pool_reset: ") + bad; return -1; }
+    const PoolRegions z = pool_regions(p, 0);
+    // (the rings need no clearing: a window never starts before position 0, and every position is written before it is read)
+    hipLaunchKernelGGL(k_pool_zero_hist, dim3(8, n, z.count), dim3(256), 0, (hipStream_t)stream, z, ids);
+    MCHK(p, hipGetLastError());
+    for (int i = 0; i < n; ++i) p->offset[ids.sid[i]] = 0;
+    return 0;
+}
+
+extern "C" int mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, const int32_t* codes, int T, long stride_s, long stride_k,
+                                long stride_t, void* pcm_out, void* stream) {
+    if (!p) return pfail(nullptr, "mimi_pool_decode: null pool");
+    if (!codes || !pcm_out) return pfail(p, "mimi_pool_decode: null codes or pcm");
+    if (T < 1 || T > p->max_chunk) return pfail(p, "mimi_pool_decode: T must be 1 .. max_chunk_frames given to mimi_pool_create");
+    PoolIds ids;
+    if (const char* bad = pool_ids(p, streams, n, &ids)) { p->err = std::string("mimi_pool_decode: ") + bad; return -1; }
+    for (int i = 0; i < n; ++i) {
+        if (p->offset[ids.sid[i]] + 2L * T > 0x7fffffffL) return pfail(p, "mimi_pool_decode: a stream passed 2^31 tokens; reset it");
+        ids.off[i] = (int)p->offset[ids.sid[i]];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const MimiConfig& c = p->cfg;
+    const int d = c.hidden, zero = 0;
+    const int T2 = 2 * T;
+    const long M2 = (long)n * T2;
+    const int* tab = p->tab;
+    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(256), 0, st, ids, p->tab, p->ksw.ticket, p->ksw.ticket ? p->ksw.n_tickets : 0);
+    // 1. RVQ lookup-sum + output projections -> rvq segments
+    hipLaunchKernelGGL(k_pool_rvq, dim3(n * T, (d + 63) / 64), dim3(256), (size_t)(2 * c.codebook_dim + c.n_codebooks) * 4, st, codes, stride_s,
+                       stride_k, stride_t, T, c.n_codebooks, c.n_semantic, c.codebook_size, c.codebook_dim, d, p->w.codebooks, p->w.proj_first,
+                       p->w.proj_rest, p->rvq.row0(), p->rvq.seg(), tab);
+    // 2. depthwise transposed conv x2 -> tok (dense)
+    hipLaunchKernelGGL(k_pool_upsample, dim3((unsigned)((M2 * d + 255) / 256)), dim3(256), 0, st, p->rvq.row0(), p->rvq.seg(), tab, T, n, d,
+                       p->w.upsample, p->tok);
+    MCHK(p, hipGetLastError());
+    // 3. transformer: every product as in decode_middle, over n * 2T rows
+    for (int l = 0; l < c.tr_layers; ++l) {
+        const MimiTrLayer& L = p->w.tr[l];
+        float* kc = p->kc + (long)l * p->n_streams * p->ring * d;
+        float* vc = p->vc + (long)l * p->n_streams * p->ring * d;
+        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)M2), dim3(64), 0, st, p->tok, d, L.ln1_w, L.ln1_b, c.norm_eps, p->ln);
+        const RopeOut ro = {p->q, kc, vc, p->w.rope_freqs, 0, d};
+        const SegArgs sq = {T2, T2, T2, T2, 0, p->ring, tab};
+        MCHK(p, gemm(st, p->ln, d, M2, L.in_proj, nullptr, d, 3 * d, 1, 1, &zero, 0, 0, nullptr, nullptr, 0, nullptr, 0, 1, 0, 0, 0, &ro, nullptr, &sq));
+        hipLaunchKernelGGL(k_pool_attn, dim3((unsigned)M2, c.tr_heads), dim3(64), 0, st, p->q, kc, vc, d, T2, p->ring, c.tr_context, tab, p->att);
+        MCHK(p, gemm(st, p->att, d, M2, L.out_proj, nullptr, d, d, 1, 1, &zero, 0, 0, L.ls1, p->tok, d, p->tok, d));
+        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)M2), dim3(64), 0, st, p->tok, d, L.ln2_w, L.ln2_b, c.norm_eps, p->ln);
+        MCHK(p, gemm(st, p->ln, d, M2, L.lin1, nullptr, d, c.tr_ffn, 1, 1, &zero, 0, 1, nullptr, nullptr, 0, p->ffn, c.tr_ffn));
+        if (l + 1 < c.tr_layers) {
+            MCHK(p, gemm(st, p->ffn, c.tr_ffn, M2, L.lin2, nullptr, c.tr_ffn, d, 1, 1, &zero, 0, 0, L.ls2, p->tok, d, p->tok, d, 1, 0, 0, 0, nullptr, &p->ksw));
+        } else {                                                        // the last layer writes the streams' a0 segments
+            const SegArgs sa = {T2, T2, p->a0.seg(), T2, 2, 0, tab};
+            MCHK(p, gemm(st, p->ffn, c.tr_ffn, M2, L.lin2, nullptr, c.tr_ffn, d, 1, 1, &zero, 0, 0, L.ls2, p->tok, d, p->a0.row0(), d, 1, 0, 0, 0, nullptr,
+                         &p->ksw, &sa));
+        }
+        MCHK(p, hipGetLastError());
+    }
+    // 4. SEANet decoder
+    int shifts[MAX_TAPS];
+    for (int j = 0; j < c.kernel; ++j) shifts[j] = j - (c.kernel - 1);
+    const MimiConv& ci = p->w.conv_in;
+    {
+        const SegArgs s = {T2, p->a0.seg(), p->s0.seg(), 0, 1 | 2, 0, tab};
+        MCHK(p, gemm(st, p->a0.row0(), d, M2, ci.w, ci.bias, ci.c_in, ci.c_out, ci.taps, 1, shifts, 0, 0, nullptr, nullptr, 0, p->s0.row0(), ci.c_out,
+                     1, 0, 0, 0, nullptr, &p->ksw, &s));
+    }
+    const PBuf* xin = &p->s0;
+    int Tj = T2;                                                        // rows per stream at the current level
+    for (int j = 0; j < c.n_stages; ++j) {
+        const MimiConv &up = p->w.up[j], &r1 = p->w.res1[j], &r2 = p->w.res2[j];
+        const int tshift[2] = {0, -1};
+        const SegArgs su = {Tj, xin->seg(), p->u[j].seg(), 0, 1 | 2, 0, tab};
+        MCHK(p, gemm(st, xin->row0(), xin->C, (long)n * Tj, up.w, up.bias, up.c_in, up.c_out, 2, up.phases, tshift, 1, 0, nullptr, nullptr, 0,
+                     p->u[j].row0(), up.c_out, 1, 0, 0, 0, nullptr, nullptr, &su));
+        Tj *= up.phases;
+        for (int k = 0; k < r1.taps; ++k) shifts[k] = k - (r1.taps - 1);
+        const SegArgs s1 = {Tj, p->u[j].seg(), Tj, 0, 1, 0, tab};
+        MCHK(p, gemm(st, p->u[j].row0(), up.c_out, (long)n * Tj, r1.w, r1.bias, r1.c_in, r1.c_out, r1.taps, 1, shifts, 1, 0, nullptr, nullptr, 0,
+                     p->r1[j], r1.c_out, 1, 0, 0, 0, nullptr, nullptr, &s1));
+        const SegArgs s2 = {Tj, Tj, p->xj[j].seg(), p->u[j].seg(), 2 | 4, 0, tab};
+        MCHK(p, gemm(st, p->r1[j], r1.c_out, (long)n * Tj, r2.w, r2.bias, r2.c_in, r2.c_out, 1, 1, &zero, 1, 0, nullptr, p->u[j].row0(), up.c_out,
+                     p->xj[j].row0(), r2.c_out, 1, 0, 0, 0, nullptr, nullptr, &s2));
+        xin = &p->xj[j];
+    }
+    // 5. output convolution -> pcm [n][hop * T], then every segmented buffer's history slides by the chunk
+    const MimiConv& co = p->w.conv_out;
+    hipLaunchKernelGGL(k_pool_conv_out, dim3((unsigned)(((long)n * Tj + 255) / 256)), dim3(256), 0, st, xin->row0(), xin->seg(), tab, (long)Tj, n, co.c_in,
+                       co.taps, co.w, co.bias, (float*)pcm_out);
+    const PoolRegions z = pool_regions(p, T);
+    int maxC = 0;
+    for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
+    hipLaunchKernelGGL(k_pool_slide, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
+    MCHK(p, hipGetLastError());
+    for (int i = 0; i < n; ++i) p->offset[ids.sid[i]] += T2;
+    return 0;
 }

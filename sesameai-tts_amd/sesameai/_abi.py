@@ -108,6 +108,11 @@ MIMI_SIGNATURES = {
     "mimi_decode_strided": (_i, [_vp, _vp, _i, _i, _l, _l, _l, _vp, _i, _vp]),
     "mimi_reset_stream": (_i, [_vp, _vp]),
     "mimi_encode": (_i, [_vp, _vp, _l, _l, _i, _vp, _vp]),
+    "mimi_pool_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "mimi_pool_destroy": (None, [_vp]),
+    "mimi_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_pool_reset": (_i, [_vp, _vp, _i, _vp]),
+    "mimi_pool_decode": (_i, [_vp, _vp, _i, _vp, _i, _l, _l, _l, _vp, _vp]),
 }
 
 for _name, (_res, _args) in list(SIGNATURES.items()) + list(MIMI_SIGNATURES.items()):

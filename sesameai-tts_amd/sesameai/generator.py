@@ -7,6 +7,7 @@ EOS flag every few frames instead of synchronising on every frame (generator.py:
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import queue
 import struct
@@ -252,6 +253,22 @@ class Generator:
         all prompts or one per prompt), so a long run hands its results out as it
         goes.  There is no limit on the total number of frame steps: the engine's frame history is a ring (include/csm_hip.h,
         csm_read_frames) and every block of ``poll`` steps is read before the next one is launched."""
+        parts: dict = {}
+        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, poll):
+            for i, _slot, frames, last in block or ():
+                parts.setdefault(i, []).append(frames)
+                if last:
+                    got = parts.pop(i)
+                    yield i, (got[0] if len(got) == 1 else torch.cat(got))
+
+    @torch.inference_mode()
+    def _iter_blocks_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
+                                temperature: float, topk: int, poll: Optional[int] = None):
+        """The incremental form of ``iter_codes_continuous`` (same loop, same model calls in the same order): per polled block it
+        yields a list of ``(index of the prompt, batch slot, that utterance's NEW frames [k][32] int32 CPU, last)`` -- ``last`` with
+        the frames that complete the utterance (possibly none); an utterance that is empty before it ever holds a slot has slot -1.
+        In between it yields ``None`` each time a block's frame steps have just been queued and before it waits for them: the
+        moment for a consumer to start work that should run beside those steps (generate_many_stream's Mimi decode)."""
         from collections import deque
         m = self._model
         # one length limit for all, or one per prompt (a request's own max_audio_length_ms)
@@ -272,9 +289,16 @@ class Generator:
         pending = deque(range(len(prompts)))
         slot_idx: List[Optional[int]] = [None] * B
         slot_frames: List[List[torch.Tensor]] = [[] for _ in range(B)]
+        reported: List[int] = [0] * B                                   # frames of the slot's utterance already handed out
         empty = torch.empty(0, 32, dtype=torch.int32)
-        finished: List[Tuple[int, torch.Tensor]] = []
+        finished: List[Tuple[int, int, torch.Tensor, bool]] = []        # this block's events
         m.reset_caches()
+
+        def report(slot: int, upto: int, last: bool) -> None:
+            fs = slot_frames[slot][reported[slot]:upto]
+            if fs or last:
+                finished.append((slot_idx[slot], slot, torch.stack(fs).to(torch.int32) if fs else empty, last))
+            reported[slot] = max(reported[slot], min(upto, len(slot_frames[slot])))
 
         def start(slot: int) -> bool:
             while pending:
@@ -282,17 +306,18 @@ class Generator:
                 t, mk = prompts[i]
                 f0 = m.refill_slot(slot, t, mk, temperature, topk).cpu()
                 if limits[i] <= 0 or bool((f0 == 0).all()):
-                    finished.append((i, empty))                         # EOS in the very first frame: empty utterance (generator.py:296)
+                    finished.append((i, -1, empty, True))               # EOS in the very first frame: empty utterance (generator.py:296)
                     continue
-                slot_idx[slot], slot_frames[slot] = i, [f0]
+                slot_idx[slot], slot_frames[slot], reported[slot] = i, [f0], 0
                 return True
             slot_idx[slot] = None
             return False
 
         for s_ in range(B):
             start(s_)
-        yield from finished
-        finished.clear()
+        if finished:
+            yield finished
+            finished = []
         g = m.num_frames()                                              # next global frame index
         while any(i is not None for i in slot_idx):
             active = [s_ for s_ in range(B) if slot_idx[s_] is not None]
@@ -301,6 +326,7 @@ class Generator:
                 n = min(poll, min(limits[slot_idx[s_]] - len(slot_frames[s_]) for s_ in active))
                 for _ in range(n):
                     m.step(B, temperature, topk)
+                yield None                                              # (the block's steps are queued)
                 fr, eos = m.read_frames(B, g, n)
                 for s_ in active:
                     rows = fr[:, s_]
@@ -311,15 +337,19 @@ class Generator:
                     if len(slot_frames[s_]) >= limits[slot_idx[s_]] and s_ not in done:
                         done.append(s_)
                 g += n
+                for s_ in active:
+                    if s_ not in done:
+                        report(s_, len(slot_frames[s_]), False)
             idle = []
             for s_ in done:
-                finished.append((slot_idx[s_], torch.stack(slot_frames[s_][:limits[slot_idx[s_]]]).to(torch.int32)))
+                report(s_, limits[slot_idx[s_]], True)
                 if not start(s_):
                     idle.append(s_)
             if idle and any(i is not None for i in slot_idx):
                 m.reset_slots(idle)                                      # a retired slot keeps stepping: keep its position away from max_seq
-            yield from finished
-            finished.clear()
+            if finished:
+                yield finished
+                finished = []
 
     def _iter_codes_refilling_beside_the_loop(self, prompts, limits: List[int], temperature: float, topk: int, poll: int, B: int):
         """The continuously refilled batch WITHOUT stalls (round 4): a retired slot's next prompt runs a few backbone layers after
@@ -336,6 +366,8 @@ class Generator:
         slot_idx: List[Optional[int]] = [None] * B          # prompt index generating in the slot
         start_g: List[int] = [0] * B                        # global frame index of its frame 0
         slot_frames: List[List[torch.Tensor]] = [[] for _ in range(B)]
+        reported: List[int] = [0] * B                       # frames of the slot's utterance already handed out
+        empty = torch.empty(0, 32, dtype=torch.int32)
         refilling: Optional[Tuple[int, int, int]] = None    # (slot, prompt index, prompt rows)
         m.reset_caches()
 
@@ -355,7 +387,7 @@ class Generator:
                 # the refill work is the same whenever it is done -- with nobody waiting the steps stay within ~8 % of an undisturbed one
                 per_call = max(1, budget * (1 + len(free)) // max(rows, 1))
                 if m.refill_advance(L if everything else min(per_call, L)):
-                    slot_idx[slot], start_g[slot], slot_frames[slot] = i, m.num_frames(), []
+                    slot_idx[slot], start_g[slot], slot_frames[slot], reported[slot] = i, m.num_frames(), [], 0
                     refilling = None
                 if not everything:
                     return
@@ -371,8 +403,10 @@ class Generator:
             for _ in range(n):
                 m.step(B, temperature, topk)
                 feed(False)
+            yield None                                      # (the block's steps are queued)
             fr, eos = m.read_frames(B, g, n)
             done = []
+            events: List[Tuple[int, int, torch.Tensor, bool]] = []
             for s_ in [s_ for s_ in range(B) if slot_idx[s_] is not None]:      # (a slot may have joined during this block)
                 lo = max(start_g[s_] - g, 0)                # rows of this block that belong to the slot's current utterance
                 if lo >= n:
@@ -382,12 +416,17 @@ class Generator:
                 if ended:
                     rows = rows[: max(e - (g + lo), 0)]
                 slot_frames[s_].extend(rows.unbind(0))
-                if ended or len(slot_frames[s_]) >= limits[slot_idx[s_]]:
+                last = ended or len(slot_frames[s_]) >= limits[slot_idx[s_]]
+                fs = slot_frames[s_][reported[s_]:max(limits[slot_idx[s_]], 0)]
+                reported[s_] += len(fs)
+                if fs or last:
+                    events.append((slot_idx[s_], s_, torch.stack(fs).to(torch.int32) if fs else empty, last))
+                if last:
                     done.append(s_)
             g += n
+            if events:
+                yield events
             for s_ in done:
-                fs = slot_frames[s_][:max(limits[slot_idx[s_]], 0)]
-                yield slot_idx[s_], (torch.stack(fs).to(torch.int32) if fs else torch.empty(0, 32, dtype=torch.int32))
                 slot_idx[s_], slot_frames[s_] = None, []
                 free.append(s_)
             if free and (pending or any(i is not None for i in slot_idx)):
@@ -413,6 +452,105 @@ class Generator:
             if frames.shape[0]:                                       # decoded as each utterance finishes, not at the end
                 out[i] = self._decode_frames(frames.unsqueeze(1))
         return out
+
+    def generate_many_stream(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
+                             temperature: float = 0.7, topk: int = 30
+                             ) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
+        """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
+        the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
+        Each batch slot is one stream of a ``MimiStreamPool`` (reset when a new utterance takes the slot); after every polled block
+        all slots that hold ``_stream_buffer_size`` undecoded frames are decoded by ONE pool call, and finishing utterances flush
+        their remaining 1..9 frames grouped by equal length.  The decode runs on the Mimi side stream and is submitted right after
+        the next block's frame steps have been queued, so the language model never waits for it.  Every request ends with exactly
+        one ``last=True`` chunk, which is empty (0 samples, 0 frames) when no frames remain -- an utterance whose first frame is EOS
+        yields just that.  All other chunks are ``_stream_buffer_size`` frames.
+        The streams are STATEFUL: the chunks of one request, concatenated, are the whole-clip decode of its frames (what
+        ``generate_many`` returns for them).  ``generate_stream`` differs: it keeps the reference's stateless 10-frame chunks."""
+        codec = self._audio_tokenizer
+        if codec is None or not hasattr(codec, "open_streams"):
+            raise RuntimeError("generate_many_stream needs a Mimi codec with stream pools (MimiCodec.open_streams)")
+        max_generation_len = (int(max_audio_length_ms / FRAME_MS) if isinstance(max_audio_length_ms, (int, float))
+                              else [int(x / FRAME_MS) for x in max_audio_length_ms])
+        with torch.inference_mode():
+            prompts = [self._build_prompt(t, sp, ctx) for t, sp, ctx in zip(texts, speakers, contexts)]
+        if not prompts:
+            return
+        size = self._stream_buffer_size
+        B = min(self._max_batch, len(prompts))
+        pools = self.__dict__.setdefault("_stream_pools", {})
+        if (B, size) not in pools:
+            pools[(B, size)] = codec.open_streams(B, max_chunk_frames=size)
+        pool = pools[(B, size)]
+        on_gpu = torch.device(self.device).type == "cuda"
+        if on_gpu and getattr(self, "_mimi_stream", None) is None:
+            self._mimi_stream = torch.cuda.Stream(device=self.device)
+        side = self._mimi_stream if on_gpu else None
+        owner: List[Optional[int]] = [None] * B                     # request whose stream the slot's pool stream carries
+        held: List[List[torch.Tensor]] = [[] for _ in range(B)]     # its frames not decoded yet
+        backlog: List[List[Tuple[int, int, torch.Tensor, bool]]] = []       # polled blocks whose audio is still to be decoded
+        no_pcm = torch.empty(0, dtype=torch.float32, device=self.device)
+        no_frames = torch.empty(0, 32, dtype=torch.int32)
+
+        def deliver(block) -> List[Tuple[int, torch.Tensor, torch.Tensor, bool]]:
+            """One polled block (a slot carries at most one utterance in it) -> its chunks."""
+            out: List[Tuple[int, torch.Tensor, torch.Tensor, bool]] = []
+            fresh: List[int] = []
+            ending: List[int] = []
+            for i, slot, fr, last in block:
+                if slot < 0:
+                    out.append((i, no_pcm, no_frames, True))
+                    continue
+                if owner[slot] != i:
+                    owner[slot], held[slot] = i, []
+                    fresh.append(slot)
+                held[slot].extend(fr.unbind(0))
+                if last:
+                    ending.append(slot)
+            calls: List[Tuple[List[int], int, torch.Tensor, torch.Tensor]] = []
+
+            def decode(slots: List[int], T: int) -> None:
+                frames = torch.stack([torch.stack(held[s_][:T]) for s_ in slots]).to(torch.int32)      # (n, T, 32)
+                for s_ in slots:
+                    del held[s_][:T]
+                calls.append((slots, T, frames, pool.decode(slots, frames.permute(0, 2, 1))))
+
+            with torch.inference_mode(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+                if fresh:
+                    pool.reset(fresh)
+                while True:
+                    full = [s_ for s_ in range(B) if len(held[s_]) >= size]
+                    if not full:
+                        break
+                    decode(full, size)
+                by_len: dict = {}
+                for s_ in ending:
+                    by_len.setdefault(len(held[s_]), []).append(s_)
+                for T in sorted(by_len):
+                    if T:
+                        decode(by_len[T], T)
+            if side is not None:
+                side.synchronize()
+            closed = set()
+            for k, (slots, T, frames, pcm) in enumerate(calls):
+                for j, s_ in enumerate(slots):
+                    last = s_ in ending and not any(s_ in later[0] for later in calls[k + 1:])
+                    if last:
+                        closed.add(s_)
+                    out.append((owner[s_], pcm[j, 0], frames[j], last))
+            for s_ in ending:
+                if s_ not in closed:                                # nothing was left to decode: the closing chunk is empty
+                    out.append((owner[s_], no_pcm, no_frames, True))
+                owner[s_] = None
+            return out
+
+        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size):
+            if block is not None:
+                backlog.append(block)
+                continue
+            while backlog:                                          # the next block's steps are queued: decode beside them
+                yield from deliver(backlog.pop(0))
+        while backlog:
+            yield from deliver(backlog.pop(0))
 
     def _decode_frames(self, frames: torch.Tensor) -> torch.Tensor:
         """frames [n][1][32] -> audio (n*1920,) (reference: _decode_frames, generator.py:111-117)."""

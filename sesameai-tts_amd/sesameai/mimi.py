@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -264,7 +264,7 @@ class MimiCodec:
                 raise ValueError(f"Mimi checkpoint: tensor {name} missing or not of shape {shp}")
         self._keep: List[torch.Tensor] = []
         self._h = C.c_void_p(None)
-        cfg, w = self._build(sd)
+        cfg, w = self._cfg_w = self._build(sd)                   # (kept: open_streams hands the same device weights to a pool)
         with torch.cuda.device(self.device):
             check(lib.mimi_create(C.byref(cfg), C.byref(w), max_frames, 0, C.byref(self._h)), None, mimi=True)
 
@@ -391,9 +391,64 @@ class MimiCodec:
         concatenated output equals ``decode`` of the concatenated codes.  Call reset_stream() first."""
         return self._run(codes, stateful=True)
 
+    def open_streams(self, n: int, max_chunk_frames: int = 10) -> "MimiStreamPool":
+        """A pool of ``n`` stateful decode streams that are decoded together (one launch chain per call, whatever the number
+        of streams in it); shares this codec's device weights.  See ``MimiStreamPool``."""
+        return MimiStreamPool(self, n, max_chunk_frames)
+
     def __del__(self):
         try:
             if self._h:
                 lib.mimi_destroy(self._h)
+        except Exception:
+            pass
+
+
+class MimiStreamPool:
+    """``n`` independent stateful Mimi decode streams (include/mimi_hip.h, mimi_pool_*): stream ``i`` keeps its own conv left
+    contexts, K/V ring and token offset, and runs for any number of frames.  ``decode(ids, codes)`` continues the listed
+    streams by the same ``T <= max_chunk_frames`` frames each; a stream's PCM does not depend on which other streams share the
+    call, and its chunks, concatenated, are ``MimiCodec.decode`` of its concatenated codes.  Streams start reset."""
+
+    def __init__(self, codec: MimiCodec, n: int, max_chunk_frames: int = 10):
+        self.codec = codec                        # keeps the device weights alive
+        self.n_streams, self.max_chunk_frames = int(n), int(max_chunk_frames)
+        self._h = C.c_void_p(None)
+        cfg, w = codec._cfg_w
+        with torch.cuda.device(codec.device):
+            rc = lib.mimi_pool_create(C.byref(cfg), C.byref(w), self.n_streams, self.max_chunk_frames, C.byref(self._h))
+        if rc != 0:
+            raise _abi.CsmError(rc, (lib.mimi_pool_last_error(None) or b"").decode())
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise _abi.CsmError(rc, (lib.mimi_pool_last_error(self._h) or b"").decode())
+
+    @staticmethod
+    def _ids(ids: Sequence[int]):
+        ids = [int(i) for i in ids]
+        return (C.c_int32 * len(ids))(*ids), len(ids)
+
+    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
+        """Start the listed streams (default: all) afresh."""
+        arr, n = self._ids(range(self.n_streams) if ids is None else ids)
+        self._check(lib.mimi_pool_reset(self._h, arr, n, _stream()))
+
+    @torch.inference_mode()
+    def decode(self, ids: Sequence[int], codes: torch.Tensor) -> torch.Tensor:
+        """ids: n distinct stream ids; codes (n,32,T) int, row i for stream ids[i] -> (n,1,hop*T) fp32."""
+        arr, n = self._ids(ids)
+        s = self.codec.args
+        assert codes.dim() == 3 and codes.shape[0] == n and codes.shape[1] == s.num_codebooks, "codes must be (len(ids), 32, T)"
+        T = codes.shape[2]
+        c = codes.to(device=self.codec.device, dtype=torch.int32)
+        pcm = torch.empty(n, 1, s.hop * T, dtype=torch.float32, device=self.codec.device)
+        self._check(lib.mimi_pool_decode(self._h, arr, n, c.data_ptr(), T, c.stride(0), c.stride(1), c.stride(2), pcm.data_ptr(), _stream()))
+        return pcm
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib.mimi_pool_destroy(self._h)
         except Exception:
             pass
