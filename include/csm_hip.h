@@ -83,6 +83,7 @@ typedef struct CsmWeights {
 } CsmWeights;
 
 typedef struct CsmModel* csm_handle;
+typedef struct CsmPrefix* csm_prefix;   /* a K/V snapshot of a prompt prefix (csm_prefix_capture) */
 
 /* Model(config) + setup_caches(max_batch) (models.py:107-130): allocates KV caches
  * [L][B][KV][max_seq][hd] (backbone) / [L][B][KV][n_codebooks][hd] (decoder) and workspaces.
@@ -188,6 +189,32 @@ int csm_refill_supported(csm_handle h, int B);
 int csm_refill_begin(csm_handle h, int slot, const int32_t* tokens, const uint8_t* mask, const int32_t* pos, int S, void* stream);
 int csm_refill_advance(csm_handle h, int max_layers, void* stream);
 
+/* Prefix store: shared voice-prompt K/V for the live batch.  A request is a 900-1,550-row voice prompt followed by a few dozen rows of new
+ * text, and the reference re-runs the whole prompt for every sentence (tts_service.py:191-207).  In prompt mode a row's K/V do not depend on
+ * how many rows share the call, so the backbone K/V rows of a prompt prefix are the same bits in every slot and for every request that starts
+ * with it: they are snapshotted once and copied instead of recomputed; only the rows after the prefix are prefilled, at their true positions
+ * (the `pos` arrays of csm_prefill / csm_prefill_slot / csm_refill_begin start at the prefix length P; a parked slot is held at P + S).
+ *   csm_prefix_capture: snapshots rows [0, rows) of `slot`'s backbone K/V, all layers, into a dense allocation
+ *                       [layer][K|V][kv head][rows][hd] bf16 that the prefix owns.  rows must not exceed the slot's position (the rows must
+ *                       have been written: synchronises the stream to learn it) and must be < max_seq; CSM_E_STATE for the slot whose refill
+ *                       beside the loop is running.
+ *   csm_prefix_apply:   writes the snapshot into rows [0, rows) of each listed slot's caches (host array, n <= max_batch) -- ONE launch for
+ *                       all layers, K and V, all kv heads and all n slots, no host synchronisation.  Positions and every other state of the
+ *                       slots are untouched.  Enqueue it IMMEDIATELY before the csm_refill_begin / csm_prefill_slot / csm_prefill call that
+ *                       runs the suffix, on the same stream: a retired slot keeps stepping from position 0 as a placeholder and a frame step
+ *                       in between would overwrite the first copied rows.  CSM_E_STATE for a slot whose refill is in flight; CSM_E_INVALID
+ *                       for a prefix of another shape (layers / kv heads / head_dim), of another GPU, or with rows >= this handle's max_seq.
+ *   csm_prefix_rows / csm_prefix_bytes: the snapshot's row count / size of its allocation (0 for NULL).
+ *   csm_prefix_read:    downloads the snapshot to host memory (bytes must equal csm_prefix_bytes; synchronises).  For tests.
+ *   csm_prefix_destroy: frees the snapshot.  csm_destroy of the handle it was captured from releases the device memory of the prefixes still
+ *                       alive (they can then only be destroyed); csm_describe reports their number and total bytes.                         */
+int    csm_prefix_capture(csm_handle h, int slot, int rows, csm_prefix* out, void* stream);
+int    csm_prefix_apply(csm_handle h, csm_prefix prefix, const int32_t* slots /*host*/, int n, void* stream);
+int    csm_prefix_rows(csm_prefix prefix);
+size_t csm_prefix_bytes(csm_prefix prefix);
+int    csm_prefix_read(csm_prefix prefix, void* host_buf, size_t bytes, void* stream);
+void   csm_prefix_destroy(csm_prefix prefix);
+
 /* Start-up weight broadcast (SURVEY.md 8b's csm_broadcast_weights; 8e: "one RCCL ncclBroadcast of the packed weight blob at start-up
  * over xGMI ... no per-step collective").  The reference has no counterpart (it is single-GPU: every process downloads its own
  * checkpoint, sesameai/generator.py:330-346); in the replica layout rank `root` holds the weights and every other
@@ -202,7 +229,7 @@ int csm_refill_advance(csm_handle h, int max_layers, void* stream);
 int csm_broadcast_weights(void* dev_blob, size_t bytes, void* rccl_comm, int root, void* stream);
 
 /* What this handle runs, as one line of text: weight stream, the kernels of a batch-1 / batched backbone step, of the depth decoder and of
- * prompts, the frame-graph cache, and every CSM_* / MIMI_* switch set in the environment.  Writes at most n - 1 characters + NUL into buf (may
+ * prompts, the frame-graph cache, the live prefixes of the prefix store (number, total bytes), and every CSM_* / MIMI_* switch set in the environment.  Writes at most n - 1 characters + NUL into buf (may
  * be NULL) and returns the length the whole text needs.  The reference has no counterpart (it has one eager path); bench.py records it with
  * every number it prints (config.paths).                                                                                              */
 int csm_describe(csm_handle h, char* buf, int n);

@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -137,7 +138,16 @@ struct CsmModel {
     uint64_t graph_clock;
     int graph_captures;                 // hipGraphInstantiate calls since csm_create (csm_debug_graph_captures)
     hipStream_t cap_stream;             // capture happens on an internal stream: the caller's may be the legacy NULL stream
+    std::vector<struct CsmPrefix*> prefixes;     // live K/V snapshots captured from this handle (csm_prefix_capture); orphaned by csm_destroy
     std::string err;
+};
+
+// A voice prompt's backbone K/V rows [0, rows) of every layer, dense: [layer][K|V][kv head][rows][hd] bf16 (csm_prefix_capture).
+struct CsmPrefix {
+    CsmModel* owner;                    // the handle it was captured from (nullptr once that handle is destroyed: the snapshot is gone with it)
+    int n_layers, kv_heads, hd, rows, device;
+    bf16_t* data;
+    size_t bytes;
 };
 
 #define HIPCHK(h, x)                                                                         \
@@ -1503,6 +1513,7 @@ extern "C" void csm_destroy(csm_handle m) {
         (void)hipStreamDestroy(m->pf_stream);
     }
     if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
+    for (CsmPrefix* p : m->prefixes) { (void)hipFree(p->data); p->data = nullptr; p->owner = nullptr; }      // (the caller still destroys the objects)
     void* ptrs[] = {m->bb.kc, m->bb.vc, m->dec.kc, m->dec.vc, m->h, m->q, m->att, m->act, m->part, m->attn_ctr, m->dec_in, m->proj_emb, m->slab,
                     m->hdec, m->qd, m->attd, m->actd, m->logits, m->frame, m->cur_tokens, m->cur_mask, m->cur_pos,
                     m->history, m->n_frames, m->eos_at, m->rng, m->frame_save, m->fresh, m->rf_h, m->rf_xn, m->rf_last, m->dec_pos, m->slot_scratch, m->p_state, m->b_state, m->qkv0_tab};
@@ -1873,6 +1884,109 @@ extern "C" int csm_refill_advance(csm_handle m, int max_layers, void* stream) {
 
 extern "C" int csm_refill_supported(csm_handle m, int B) { return m && B >= 1 && refill_beside_ok(m, B) ? 1 : 0; }
 
+// ---------------------------------------------------------------------------------------
+// prefix store: K/V snapshots of prompt prefixes (the reference re-runs the whole 900-1,550-row voice prompt for every sentence,
+// tts_service.py:191-207).  The backbone cache is [L][B][KV][cache_len][hd], so rows [0, rows) of one slot are L * 2 * KV runs of
+// rows * hd contiguous elements; a snapshot keeps the runs back to back.  One launch moves every run of every listed slot: grid =
+// (pieces of a run, run, slot), 16 B per lane, four independent loads in flight per lane before the first store.  The slot list
+// travels in the kernel arguments (max_batch <= 256), so an apply needs neither a host-to-device copy nor a synchronisation.
+// ---------------------------------------------------------------------------------------
+#define PREFIX_VECS_PER_BLOCK (256 * 4)
+struct PrefixSlots { unsigned short s[256]; };
+
+template <bool APPLY>
+__global__ __launch_bounds__(256) void k_prefix_copy(bf16_t* kc, bf16_t* vc, bf16_t* snap, long run_vecs, int kv_heads, long layer_stride,
+                                                     long slot_stride, long head_stride, PrefixSlots sl) {
+    const int run = blockIdx.y, kvh = run % kv_heads, which = (run / kv_heads) & 1, l = run / (2 * kv_heads);
+    const long slot = sl.s[blockIdx.z];
+    uint4* c = (uint4*)((which ? vc : kc) + (long)l * layer_stride + slot * slot_stride + (long)kvh * head_stride);
+    uint4* s = (uint4*)snap + (long)run * run_vecs;
+    const long i0 = (long)blockIdx.x * PREFIX_VECS_PER_BLOCK + threadIdx.x;
+    uint4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long i = i0 + j * 256;
+        if (i < run_vecs) v[j] = APPLY ? s[i] : c[i];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long i = i0 + j * 256;
+        if (i < run_vecs) { if (APPLY) c[i] = v[j]; else s[i] = v[j]; }
+    }
+}
+
+static hipError_t launch_prefix_copy(CsmModel* m, const CsmPrefix* p, const PrefixSlots& sl, int n, bool apply, hipStream_t st) {
+    const Stack& S = m->bb;
+    const long run_vecs = (long)p->rows * p->hd / 8;
+    const long head_stride = (long)S.cache_len * S.hd, slot_stride = (long)S.d.n_kv_heads * head_stride;
+    const dim3 grid((unsigned)((run_vecs + PREFIX_VECS_PER_BLOCK - 1) / PREFIX_VECS_PER_BLOCK), (unsigned)(p->n_layers * 2 * p->kv_heads), (unsigned)n);
+    if (apply) hipLaunchKernelGGL(k_prefix_copy<true>, grid, dim3(256), 0, st, S.kc, S.vc, p->data, run_vecs, p->kv_heads, S.layer_stride, slot_stride, head_stride, sl);
+    else hipLaunchKernelGGL(k_prefix_copy<false>, grid, dim3(256), 0, st, S.kc, S.vc, p->data, run_vecs, p->kv_heads, S.layer_stride, slot_stride, head_stride, sl);
+    return hipGetLastError();
+}
+
+extern "C" int csm_prefix_capture(csm_handle m, int slot, int rows, csm_prefix* out, void* stream) {
+    if (!m || !out) return fail(m, CSM_E_INVALID, "csm_prefix_capture: null argument");
+    if (slot < 0 || slot >= m->max_batch || rows < 1 || rows >= m->cfg.backbone.max_seq) return fail(m, CSM_E_INVALID, "csm_prefix_capture: slot outside the batch or rows outside [1, max_seq)");
+    if (slot == m->rf_slot) return fail(m, CSM_E_STATE, "csm_prefix_capture: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+    hipStream_t st = (hipStream_t)stream;
+    int pos = 0;
+    HIPCHK(m, hipMemcpyAsync(&pos, m->cur_pos + slot, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(m, hipStreamSynchronize(st));
+    if (rows > pos) return fail(m, CSM_E_INVALID, "csm_prefix_capture: rows beyond the slot's position (those rows have not been written)");
+    CsmPrefix* p = new CsmPrefix();
+    p->owner = m; p->n_layers = m->cfg.backbone.n_layers; p->kv_heads = m->cfg.backbone.n_kv_heads; p->hd = m->bb.hd; p->rows = rows; p->device = m->device;
+    p->bytes = (size_t)p->n_layers * 2 * p->kv_heads * rows * p->hd * 2;
+    hipError_t e = hipMalloc((void**)&p->data, p->bytes);
+    if (e == hipSuccess) {
+        PrefixSlots sl; sl.s[0] = (unsigned short)slot;
+        e = launch_prefix_copy(m, p, sl, 1, false, st);
+        if (e != hipSuccess) (void)hipFree(p->data);
+    }
+    if (e != hipSuccess) { delete p; HIPCHK(m, e); }
+    m->prefixes.push_back(p);
+    *out = p;
+    return CSM_OK;
+}
+
+extern "C" int csm_prefix_apply(csm_handle m, csm_prefix p, const int32_t* slots, int n, void* stream) {
+    if (!m || !p || !slots || n < 0 || n > m->max_batch) return fail(m, CSM_E_INVALID, "csm_prefix_apply: bad argument");
+    if (!p->data) return fail(m, CSM_E_INVALID, "csm_prefix_apply: the handle this prefix was captured from has been destroyed");
+    if (p->n_layers != m->cfg.backbone.n_layers || p->kv_heads != m->cfg.backbone.n_kv_heads || p->hd != m->bb.hd || p->device != m->device)
+        return fail(m, CSM_E_INVALID, "csm_prefix_apply: the prefix comes from a handle of another shape (layers / kv heads / head_dim) or another GPU");
+    if (p->rows >= m->cfg.backbone.max_seq) return fail(m, CSM_E_INVALID, "csm_prefix_apply: the prefix has max_seq rows or more");
+    PrefixSlots sl;
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_prefix_apply: slot outside the batch");
+        if (slots[i] == m->rf_slot) return fail(m, CSM_E_STATE, "csm_prefix_apply: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+        sl.s[i] = (unsigned short)slots[i];
+    }
+    if (n == 0) return CSM_OK;
+    HIPCHK(m, launch_prefix_copy(m, p, sl, n, true, (hipStream_t)stream));
+    return CSM_OK;
+}
+
+extern "C" int csm_prefix_rows(csm_prefix p) { return p ? p->rows : 0; }
+extern "C" size_t csm_prefix_bytes(csm_prefix p) { return p ? p->bytes : 0; }
+
+extern "C" int csm_prefix_read(csm_prefix p, void* host_buf, size_t bytes, void* stream) {
+    if (!p || !host_buf || bytes != p->bytes) return fail(p ? p->owner : nullptr, CSM_E_INVALID, "csm_prefix_read: null argument or bytes != csm_prefix_bytes");
+    if (!p->data) return fail(nullptr, CSM_E_INVALID, "csm_prefix_read: the handle this prefix was captured from has been destroyed");
+    HIPCHK(p->owner, hipMemcpyAsync(host_buf, p->data, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(p->owner, hipStreamSynchronize((hipStream_t)stream));
+    return CSM_OK;
+}
+
+extern "C" void csm_prefix_destroy(csm_prefix p) {
+    if (!p) return;
+    if (p->owner) {
+        auto& v = p->owner->prefixes;
+        v.erase(std::remove(v.begin(), v.end(), p), v.end());
+    }
+    if (p->data) (void)hipFree(p->data);
+    delete p;
+}
+
 extern "C" int csm_num_frames(csm_handle m) { return m ? m->host_frames : 0; }
 
 extern "C" int csm_read_frames(csm_handle m, int B, int first, int n, int32_t* host_frames, int32_t* host_eos_at, void* stream) {
@@ -1983,6 +2097,8 @@ extern "C" int csm_describe(csm_handle m, char* buf, int n) {
     snprintf(tmp, sizeof tmp, "; layer0_qkv_table=%d; attn_merge_in_kernel=%d; frame_graphs=LRU of %d (%d captured)", m->qkv0_tab != nullptr, m->attn_ctr != nullptr,
              CSM_FRAME_GRAPHS, m->graph_captures);
     t += tmp;
+    { size_t pb = 0; for (const CsmPrefix* p : m->prefixes) pb += p->bytes;
+      snprintf(tmp, sizeof tmp, "; prefix_store=%d prefixes, %zu bytes", (int)m->prefixes.size(), pb); t += tmp; }
     const std::string sw = set_switches(true);
     t += "; switches=" + (sw.empty() ? std::string("none") : sw);
     if (buf && n > 0) { strncpy(buf, t.c_str(), (size_t)n - 1); buf[n - 1] = 0; }

@@ -78,6 +78,12 @@ SIGNATURES = {
     "csm_refill_supported": (_i, [_vp, _i]),
     "csm_refill_begin": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
     "csm_refill_advance": (_i, [_vp, _i, _vp]),
+    "csm_prefix_capture": (_i, [_vp, _i, _i, C.POINTER(_vp), _vp]),
+    "csm_prefix_apply": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "csm_prefix_rows": (_i, [_vp]),
+    "csm_prefix_bytes": (C.c_size_t, [_vp]),
+    "csm_prefix_read": (_i, [_vp, _vp, C.c_size_t, _vp]),
+    "csm_prefix_destroy": (None, [_vp]),
     "csm_broadcast_weights": (_i, [_vp, C.c_size_t, _vp, _i, _vp]),
     "csm_num_frames": (_i, [_vp]),
     "csm_read_frames": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -18,7 +18,7 @@ from typing import Callable, Generator as PyGenerator, List, Optional, Sequence,
 
 import torch
 
-from .models import Model, ModelArgs, csm_1b_args
+from .models import Model, ModelArgs, csm_1b_args, match_stored_prefix
 
 FRAME_MS = 80                     # generator.py:257
 MAX_SEQ_LEN = 2048                # generator.py:276
@@ -157,6 +157,70 @@ class Generator:
         toks.append(t); masks.append(m)
         return torch.cat(toks, 0).long().to(self.device), torch.cat(masks, 0).bool().to(self.device)
 
+    # -- prefix store: a voice prompt's K/V computed once, copied into any slot ----------------------
+    def _store(self) -> list:
+        """[(tokens (P,33) zeroed where masked, mask (P,33), handle)] of the registered prefixes.  The list lives on the model:
+        ``Model.prefill_prompt`` (B = 1) reads it too, and ``Model.setup_caches`` empties it with the handle the snapshots came from."""
+        st = getattr(self._model, "stored_prefixes", None)
+        if st is None:
+            st = self._model.stored_prefixes = []
+        return st
+
+    def cache_prefix(self, context, mask: Optional[torch.Tensor] = None):
+        """Registers a prompt prefix -- a voice's context ``List[Segment]``, or its rows ``(tokens (P,33), mask (P,33))`` -- with
+        the prefix store: the rows are prefilled once (call it while no generation is running: it resets the caches), their backbone
+        K/V snapshotted (Model.capture_prefix), and every later request whose prompt starts with them -- ``generate``,
+        ``generate_stream``, ``generate_many``, ``generate_many_stream``, ``iter_codes_continuous`` -- copies the snapshot into its
+        slot and prefills only the rows after it.  The results are bit-identical to running the whole prompt (in prompt mode a row's
+        K/V do not depend on the rows that share its call).  Returns the handle (``.rows``, ``.bytes``); ``drop_prefix`` frees it."""
+        if mask is None:
+            toks, masks = zip(*[self._tokenize_segment(seg) for seg in context])
+            tokens, mask = torch.cat(toks, 0), torch.cat(masks, 0)
+        else:
+            tokens = context
+        tokens, mask = tokens.to(self.device).long(), mask.to(self.device).bool()
+        if tokens.dim() != 2 or tokens.shape[0] < 1 or tokens.shape[0] >= MAX_SEQ_LEN:
+            raise ValueError(f"a prefix is (P,33) rows with 1 <= P < {MAX_SEQ_LEN}")
+        m = self._model
+        m.reset_caches()
+        m.prefill_prompt(tokens.unsqueeze(0), mask.unsqueeze(0))
+        handle = m.capture_prefix(0, int(tokens.shape[0]))
+        self._store().append((torch.where(mask, tokens, torch.zeros_like(tokens)), mask, handle))
+        return handle
+
+    def drop_prefix(self, handle) -> None:
+        """Forgets a registered prefix and frees its snapshot."""
+        st = self._store()
+        st[:] = [e for e in st if e[2] is not handle]
+        handle.destroy()
+
+    @property
+    def prefixes(self) -> list:
+        """Handles of the registered prefixes, oldest first."""
+        return [e[2] for e in self._store()]
+
+    def _plan_prefixes(self, prompts) -> List[Tuple[int, object]]:
+        """Per prompt (rows P to copy, handle): the registered prefix with the longest match, (0, None) without one.  Computed for
+        all prompts before the loop starts, so that no comparison's host synchronisation falls between frame steps."""
+        st = self._store()
+        if not st:
+            return [(0, None)] * len(prompts)
+        return [match_stored_prefix(st, t, mk) for t, mk in prompts]
+
+    @staticmethod
+    def _seed_shared(m, slots: Sequence[int], idx: Sequence[int], plan) -> dict:
+        """The initial fill: all slots whose first prompts copy from the same prefix are seeded by ONE apply_prefix call.
+        Returns {slot: handle} of what was copied."""
+        groups: dict = {}
+        for slot, i in zip(slots, idx):
+            if plan[i][1] is not None:
+                groups.setdefault(id(plan[i][1]), (plan[i][1], []))[1].append(slot)
+        seeded = {}
+        for handle, group in groups.values():
+            m.apply_prefix(handle, group)
+            seeded.update({slot: handle for slot in group})
+        return seeded
+
     # -- the frame loop -----------------------------------------------------------------------
     def _frame_blocks(self, prompt_tokens: torch.Tensor, prompt_mask: torch.Tensor, max_generation_len: int,
                       temperature: float, topk: int, poll: int, gate: Optional["_FirstBlockGate"] = None
@@ -283,8 +347,9 @@ class Generator:
         poll = poll or self._eos_poll
         B = min(self._max_batch, len(prompts))
         beside = getattr(m, "supports_refill_beside_the_loop", None)
+        plan = self._plan_prefixes(prompts)
         if beside is not None and beside(B) and getattr(self, "refill_beside_the_loop", True):
-            yield from self._iter_codes_refilling_beside_the_loop(prompts, limits, temperature, topk, poll, B)
+            yield from self._iter_codes_refilling_beside_the_loop(prompts, limits, temperature, topk, poll, B, plan)
             return
         pending = deque(range(len(prompts)))
         slot_idx: List[Optional[int]] = [None] * B
@@ -304,7 +369,13 @@ class Generator:
             while pending:
                 i = pending.popleft()
                 t, mk = prompts[i]
-                f0 = m.refill_slot(slot, t, mk, temperature, topk).cpu()
+                P, handle = plan[i]
+                if handle is None:
+                    f0 = m.refill_slot(slot, t, mk, temperature, topk).cpu()
+                else:                                                   # copy the prefix's K/V, run only the rows after it
+                    if seeded.pop(slot, None) is not handle:
+                        m.apply_prefix(handle, [slot])
+                    f0 = m.refill_slot(slot, t[P:], mk[P:], temperature, topk, start=P).cpu()
                 if limits[i] <= 0 or bool((f0 == 0).all()):
                     finished.append((i, -1, empty, True))               # EOS in the very first frame: empty utterance (generator.py:296)
                     continue
@@ -313,8 +384,10 @@ class Generator:
             slot_idx[slot] = None
             return False
 
+        seeded = self._seed_shared(m, range(B), range(B), plan)
         for s_ in range(B):
             start(s_)
+        seeded.clear()
         if finished:
             yield finished
             finished = []
@@ -351,14 +424,17 @@ class Generator:
                 yield finished
                 finished = []
 
-    def _iter_codes_refilling_beside_the_loop(self, prompts, limits: List[int], temperature: float, topk: int, poll: int, B: int):
+    def _iter_codes_refilling_beside_the_loop(self, prompts, limits: List[int], temperature: float, topk: int, poll: int, B: int, plan=None):
         """The continuously refilled batch WITHOUT stalls (round 4): a retired slot's next prompt runs a few backbone layers after
         each frame step (Model.refill_begin / refill_advance: about ``refill_row_layers`` = 600 prompt-row x layer units per step, i.e.
         3 layers of a 190-row prompt = +8 % of a B = 32 step; measured: bench.py extras.config3.refill_beside_the_loop) while the other slots keep generating, and the new utterance's frame
         0 is sampled by the batch's next frame step -- csm_prefill_slot made the other slots wait ~4 ms for a 190-row prompt and
-        > 8 ms for a 1,334-row one.  Until its prompt is complete a slot's rows are placeholders and are skipped here."""
+        > 8 ms for a 1,334-row one.  Until its prompt is complete a slot's rows are placeholders and are skipped here.
+        A prompt that starts with a registered prefix (``plan``) has the prefix's K/V copied into the slot right before its refill
+        begins, and only the rows after it count against the budget."""
         from collections import deque
         m = self._model
+        plan = plan or [(0, None)] * len(prompts)
         L = getattr(m.bb, "num_layers", 16)
         budget = getattr(self, "refill_row_layers", 600)
         pending = deque(range(len(prompts)))
@@ -380,8 +456,14 @@ class Generator:
                         return
                     slot, i = free.popleft(), pending.popleft()
                     t, mk = prompts[i]
-                    m.refill_begin(slot, t, mk)
-                    refilling = (slot, i, int(t.shape[0]))
+                    P, handle = plan[i]
+                    if handle is None:
+                        m.refill_begin(slot, t, mk)
+                    else:                                   # copy, then begin at once: no frame step may fall between the two
+                        if seeded.pop(slot, None) is not handle:
+                            m.apply_prefix(handle, [slot])
+                        m.refill_begin(slot, t[P:], mk[P:], start=P)
+                    refilling = (slot, i, int(t.shape[0]) - P)
                 slot, i, rows = refilling
                 # the per-step budget grows with the backlog: every slot that waits for a prompt is 1/B of the batch's throughput idle, and
                 # the refill work is the same whenever it is done -- with nobody waiting the steps stay within ~8 % of an undisturbed one
@@ -392,7 +474,9 @@ class Generator:
                 if not everything:
                     return
 
+        seeded = self._seed_shared(m, list(free), list(pending)[:B], plan)
         feed(True)                                          # the initial fill: nothing to protect yet
+        seeded.clear()
         g = m.num_frames()
         while any(i is not None for i in slot_idx) or refilling is not None or (pending and free):
             if not any(i is not None for i in slot_idx):

@@ -336,6 +336,73 @@ def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+class Prefix:
+    """A K/V snapshot of a prompt prefix (include/csm_hip.h csm_prefix_capture): rows [0, rows) of one slot's backbone caches, all
+    layers.  ``Model.apply_prefix`` copies it into any slots; ``destroy()`` (or garbage collection) frees the device memory.  A
+    model's ``setup_caches`` destroys the prefixes captured from it."""
+
+    def __init__(self, model: "Model", ptr: int):
+        self._model, self._p = model, C.c_void_p(ptr)
+        self.rows = int(lib.csm_prefix_rows(self._p))
+        self.bytes = int(lib.csm_prefix_bytes(self._p))
+
+    @property
+    def alive(self) -> bool:
+        return bool(self._p)
+
+    def _ptr(self) -> C.c_void_p:
+        if not self._p:
+            raise ValueError("this prefix has been destroyed")
+        return self._p
+
+    def read(self) -> torch.Tensor:
+        """The snapshot [layers][2 (K, V)][kv heads][rows][head_dim] bf16 on the host (csm_prefix_read; synchronises)."""
+        m = self._model
+        out = torch.empty(m.bb.num_layers, 2, m.bb.num_kv_heads, self.rows, m.bb.head_dim, dtype=torch.bfloat16)
+        with m._on_device():
+            check(lib.csm_prefix_read(self._ptr(), out.data_ptr(), out.numel() * 2, _stream_ptr()), m._h)
+        return out
+
+    def destroy(self) -> None:
+        if self._p:
+            lib.csm_prefix_destroy(self._p)
+            self._p = C.c_void_p(None)
+            self._model._prefixes = [r for r in self._model._prefixes if r() not in (None, self)]
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def common_prefix_rows(t: torch.Tensor, m: torch.Tensor, ot: torch.Tensor, om: torch.Tensor) -> int:
+    """Leading rows on which two prompts (S,33) / (S',33) agree: tokens under the mask and the mask itself, as ``prefill_prompt``
+    compares (tokens already zeroed where the mask is off)."""
+    n = min(t.shape[0], ot.shape[0])
+    if n == 0:
+        return 0
+    same = ((t[:n] == ot[:n]) & (m[:n] == om[:n])).all(dim=1)
+    return int(same.to(torch.int32).cumprod(0).sum().item())
+
+
+def match_stored_prefix(entries, tokens: torch.Tensor, mask: torch.Tensor):
+    """(rows, prefix) over ``entries`` = [(tokens (P,33) zeroed where masked, mask (P,33) bool, prefix handle with ``.rows``), ...]:
+    the entry that agrees with the prompt (S,33) on the most leading rows, capped at S - 1; (0, None) when none agrees on any."""
+    best_rows, best = 0, None
+    if not entries:
+        return best_rows, best
+    mk = mask.to(torch.bool)
+    tk = torch.where(mk, tokens, torch.zeros_like(tokens))
+    for pt, pm, p in entries:
+        if not getattr(p, "alive", True):
+            continue
+        rows = min(common_prefix_rows(tk, mk, pt.to(device=tk.device, dtype=tk.dtype), pm.to(tk.device)), int(p.rows), tokens.shape[0] - 1)
+        if rows > best_rows:
+            best_rows, best = rows, p
+    return best_rows, best
+
+
 class Model:
     """Drop-in for the reference ``Model`` (sesameai/models.py:99-203)."""
 
@@ -385,6 +452,11 @@ class Model:
         self.prefix_reuse = True
         self._kv_prompt: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self.last_prefill_rows = 0
+        # prefix store (include/csm_hip.h csm_prefix_*): snapshots captured from this handle, and the (tokens, mask, Prefix) entries
+        # prefill_prompt may seed slot 0 from (Generator.cache_prefix registers them)
+        self._prefixes: list = []
+        self.stored_prefixes: List[Tuple[torch.Tensor, torch.Tensor, Prefix]] = []
+        self.prefill_rows_total = 0           # prompt rows run by prefill_prompt / refill_slot / refill_begin since construction
 
     # -- reference-compatible construction helpers ------------------------------------------
     @classmethod
@@ -445,6 +517,7 @@ class Model:
     def setup_caches(self, max_batch_size: int) -> None:
         """reference: Model.setup_caches (sesameai/models.py:120-130)."""
         if self._h:
+            self._drop_prefixes()
             lib.csm_destroy(self._h)
             self._h = C.c_void_p(None)
         cfg, w = self._cfg_struct(), self._weights_struct()
@@ -518,9 +591,19 @@ class Model:
     def _require(self) -> None:
         assert self._h, "backbone caches are not enabled"     # reference: models.py:153
 
+    def _drop_prefixes(self) -> None:
+        """The snapshots live in the handle's caches' layout and die with it."""
+        for r in list(self._prefixes):
+            p = r()
+            if p is not None:
+                p.destroy()
+        self._prefixes = []
+        del self.stored_prefixes[:]                              # (the list is shared with the Generator that registered them)
+
     def __del__(self):
         try:
             if self._h:
+                self._drop_prefixes()
                 lib.csm_destroy(self._h)
         except Exception:
             pass
@@ -559,11 +642,49 @@ class Model:
             same = ((t[:, :n] == ot[:, :n]) & (m[:, :n] == om[:, :n])).all(dim=2).all(dim=0)
             start = int(same.to(torch.int32).cumprod(0).sum().item())
             start = min(start, s - 1)                                 # at least the last row runs (it yields last_h)
+        if self.prefix_reuse and b == 1 and self.stored_prefixes:
+            # a stored prefix that matches further than the previous prompt (a service alternating between voices): seed slot 0 from it
+            rows, best = self.match_prefix(t[0], m[0])
+            if best is not None and rows > start:
+                self.apply_prefix(best, [0], rows=rows)
+                start = rows
         pos = torch.arange(start, s, device=self.device, dtype=torch.int32).unsqueeze(0).repeat(b, 1)
         self.prefill(t[:, start:], m[:, start:], pos, _keeps_prompt_prefix=True)
         self._kv_prompt = (t, m)
         self.last_prefill_rows = s - start
+        self.prefill_rows_total += b * (s - start)
         return s - start
+
+    # -- prefix store ---------------------------------------------------------------------------
+    def capture_prefix(self, slot: int, rows: int) -> Prefix:
+        """Snapshots backbone K/V rows [0, rows) of batch slot ``slot`` (csm_prefix_capture); the rows must have been written."""
+        self._require()
+        out = C.c_void_p(None)
+        with self._on_device():
+            check(lib.csm_prefix_capture(self._h, int(slot), int(rows), C.byref(out), _stream_ptr()), self._h)
+        p = Prefix(self, out.value)
+        import weakref
+        self._prefixes.append(weakref.ref(p))
+        return p
+
+    def apply_prefix(self, prefix: Prefix, slots, rows: Optional[int] = None) -> None:
+        """Writes the snapshot into rows [0, prefix.rows) of the listed slots' caches in one launch (csm_prefix_apply).  Call it
+        IMMEDIATELY before the ``refill_slot`` / ``refill_begin`` / ``prefill`` that runs the rows after it: a retired slot keeps
+        stepping from position 0 and a frame step in between would overwrite the first copied rows.  (``rows``: how many of them the
+        caller is going to rely on, for bookkeeping only -- the whole snapshot is copied.)"""
+        self._require()
+        slots = [int(x) for x in slots]
+        arr = (C.c_int32 * max(len(slots), 1))(*slots)
+        with self._on_device():
+            check(lib.csm_prefix_apply(self._h, prefix._ptr(), arr, len(slots), _stream_ptr()), self._h)
+        if 0 in slots:
+            self._kv_prompt = None                               # slot 0's rows are the prefix's now (prefill_prompt re-records its own prompt)
+
+    def match_prefix(self, tokens: torch.Tensor, mask: torch.Tensor) -> Tuple[int, Optional[Prefix]]:
+        """(rows, prefix): the stored prefix that agrees with the prompt (S,33) on the most leading rows, capped at S - 1 so that the
+        last row always runs -- (0, None) when none agrees on any.  A prefix that agrees only partway is used up to that row: the
+        rows of the snapshot beyond it are overwritten by the suffix's own."""
+        return match_stored_prefix(self.stored_prefixes, tokens, mask)
 
     def reset_slots(self, slots) -> None:
         """Position 0 and "no EOS yet" for the listed batch slots; the other slots are untouched (csm_reset_slots)."""
@@ -572,36 +693,41 @@ class Model:
         with self._on_device():
             check(lib.csm_reset_slots(self._h, arr, len(slots), _stream_ptr()), self._h)
 
-    def refill_slot(self, slot: int, tokens: torch.Tensor, tokens_mask: torch.Tensor, temperature: float, topk: int) -> torch.Tensor:
+    def refill_slot(self, slot: int, tokens: torch.Tensor, tokens_mask: torch.Tensor, temperature: float, topk: int, start: int = 0) -> torch.Tensor:
         """A new prompt (S,33) starting at position 0 into batch slot ``slot`` of a live batch: backbone prefill into the slot's
         caches, depth pass, the new utterance's frame 0 staged as the slot's next input.  Returns frame 0 (32,) int32 on the
-        device.  The other slots keep generating undisturbed (bit-identical frames); see include/csm_hip.h csm_prefill_slot."""
+        device.  The other slots keep generating undisturbed (bit-identical frames); see include/csm_hip.h csm_prefill_slot.
+        ``start``: the rows are the prompt's rows [start, start + S); rows [0, start) are already in the slot's caches (apply_prefix)."""
         self._require()
         s = tokens.shape[0]
-        if s >= self.bb.max_seq_len or s > max(self._max_prefill_rows, 2 * self._max_batch):
+        if start < 0 or start + s >= self.bb.max_seq_len or s > max(self._max_prefill_rows, 2 * self._max_batch):
             raise ValueError(f"prompt of {s} rows exceeds the limits (max_seq_len {self.bb.max_seq_len}, max_prefill_rows {self._max_prefill_rows})")
         self._kv_prompt = None                                   # slot 0's cached prompt prefix no longer describes the caches
         t = self._to_dev(tokens, torch.int32)
         m = self._to_dev(tokens_mask, torch.uint8)
-        p = torch.arange(s, device=self.device, dtype=torch.int32)
+        p = torch.arange(start, start + s, device=self.device, dtype=torch.int32)
+        self.last_prefill_rows = s
+        self.prefill_rows_total += s
         out = torch.empty(self.config.audio_num_codebooks, dtype=torch.int32, device=self.device)
         with self._on_device():
             check(lib.csm_prefill_slot(self._h, int(slot), t.data_ptr(), m.data_ptr(), p.data_ptr(), s, 1, float(temperature), int(topk),
                                        out.data_ptr(), _stream_ptr()), self._h)
         return out
 
-    def refill_begin(self, slot: int, tokens: torch.Tensor, tokens_mask: torch.Tensor) -> None:
+    def refill_begin(self, slot: int, tokens: torch.Tensor, tokens_mask: torch.Tensor, start: int = 0) -> None:
         """Starts a refill BESIDE the frame loop (csm_refill_begin): the prompt (S,33) is embedded and the slot parked; its layers run
         a few at a time through ``refill_advance`` between frame steps, so the other slots never wait for a whole prompt.  One
-        refill at a time per model."""
+        refill at a time per model.  ``start``: as for ``refill_slot``."""
         self._require()
         s = tokens.shape[0]
-        if s >= self.bb.max_seq_len or s > max(self._max_prefill_rows, 2 * self._max_batch):
+        if start < 0 or start + s >= self.bb.max_seq_len or s > max(self._max_prefill_rows, 2 * self._max_batch):
             raise ValueError(f"prompt of {s} rows exceeds the limits (max_seq_len {self.bb.max_seq_len}, max_prefill_rows {self._max_prefill_rows})")
         self._kv_prompt = None
         t = self._to_dev(tokens, torch.int32)
         m = self._to_dev(tokens_mask, torch.uint8)
-        p = torch.arange(s, device=self.device, dtype=torch.int32)
+        p = torch.arange(start, start + s, device=self.device, dtype=torch.int32)
+        self.last_prefill_rows = s
+        self.prefill_rows_total += s
         self._refill_keep = (t, m, p)                             # the position array is read by every advance call
         with self._on_device():
             check(lib.csm_refill_begin(self._h, int(slot), t.data_ptr(), m.data_ptr(), p.data_ptr(), s, _stream_ptr()), self._h)
