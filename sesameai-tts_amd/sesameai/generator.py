@@ -7,7 +7,6 @@ EOS flag every few frames instead of synchronising on every frame (generator.py:
 """
 from __future__ import annotations
 
-import contextlib
 import os
 import queue
 import struct
@@ -18,10 +17,16 @@ from typing import Callable, Generator as PyGenerator, List, Optional, Sequence,
 
 import torch
 
-from .models import Model, ModelArgs, csm_1b_args, match_stored_prefix
+from .live_batch import SlotStreams, live_batch
+from .models import Model, ModelArgs, csm_1b_args
 
 FRAME_MS = 80                     # generator.py:257
 MAX_SEQ_LEN = 2048                # generator.py:276
+
+
+def _frames_for(max_audio_length_ms):
+    """A length limit in ms, or one per request, in frames."""
+    return int(max_audio_length_ms / FRAME_MS) if isinstance(max_audio_length_ms, (int, float)) else [int(x / FRAME_MS) for x in max_audio_length_ms]
 
 
 @dataclass
@@ -72,6 +77,10 @@ class _FirstBlockGate:
 
 class Generator:
     """reference: sesameai/generator.py:41-300."""
+    # the live batch's settings, for callers to assign; class-level so that a Generator assembled without __init__ (tests, tools) has them
+    refill_beside_the_loop = True              # refill a few layers per frame step where the model supports it (sesameai/live_batch.py) ...
+    refill_row_layers = 600                    # ... about this many prompt-row x layer units per step
+    _stream_pools: Optional[dict] = None       # {(slots, chunk frames): MimiStreamPool} of generate_many_stream, made on first use and kept
 
     def __init__(self, model: Model, audio_tokenizer=None, text_tokenizer=None, max_batch_size: int = 1):
         self._model = model
@@ -83,7 +92,7 @@ class Generator:
         self.device = model.device
         self._stream_buffer_size = 10          # generator.py:61
         self._eos_poll = 8                     # frames launched between EOS polls
-        self._mimi_stream = None               # side HIP stream for Mimi in generate_stream
+        self._mimi_stream = None               # side HIP stream for Mimi in generate_stream / generate_many_stream (_side_stream)
 
     def warm_up(self, temperature: float = 0.7, topk: int = 30, also=((0.8, 40), (0.9, 50))) -> None:
         """One short synthetic utterance through the streaming path and the whole-utterance path.  Everything a process does once --
@@ -161,10 +170,9 @@ class Generator:
     def _store(self) -> list:
         """[(tokens (P,33) zeroed where masked, mask (P,33), handle)] of the registered prefixes.  The list lives on the model:
         ``Model.prefill_prompt`` (B = 1) reads it too, and ``Model.setup_caches`` empties it with the handle the snapshots came from."""
-        st = getattr(self._model, "stored_prefixes", None)
-        if st is None:
-            st = self._model.stored_prefixes = []
-        return st
+        if not hasattr(self._model, "stored_prefixes"):               # (a scripted model of the host-logic tests)
+            self._model.stored_prefixes = []
+        return self._model.stored_prefixes
 
     def cache_prefix(self, context, mask: Optional[torch.Tensor] = None):
         """Registers a prompt prefix -- a voice's context ``List[Segment]``, or its rows ``(tokens (P,33), mask (P,33))`` -- with
@@ -198,28 +206,6 @@ class Generator:
     def prefixes(self) -> list:
         """Handles of the registered prefixes, oldest first."""
         return [e[2] for e in self._store()]
-
-    def _plan_prefixes(self, prompts) -> List[Tuple[int, object]]:
-        """Per prompt (rows P to copy, handle): the registered prefix with the longest match, (0, None) without one.  Computed for
-        all prompts before the loop starts, so that no comparison's host synchronisation falls between frame steps."""
-        st = self._store()
-        if not st:
-            return [(0, None)] * len(prompts)
-        return [match_stored_prefix(st, t, mk) for t, mk in prompts]
-
-    @staticmethod
-    def _seed_shared(m, slots: Sequence[int], idx: Sequence[int], plan) -> dict:
-        """The initial fill: all slots whose first prompts copy from the same prefix are seeded by ONE apply_prefix call.
-        Returns {slot: handle} of what was copied."""
-        groups: dict = {}
-        for slot, i in zip(slots, idx):
-            if plan[i][1] is not None:
-                groups.setdefault(id(plan[i][1]), (plan[i][1], []))[1].append(slot)
-        seeded = {}
-        for handle, group in groups.values():
-            m.apply_prefix(handle, group)
-            seeded.update({slot: handle for slot in group})
-        return seeded
 
     # -- the frame loop -----------------------------------------------------------------------
     def _frame_blocks(self, prompt_tokens: torch.Tensor, prompt_mask: torch.Tensor, max_generation_len: int,
@@ -332,189 +318,10 @@ class Generator:
         yields a list of ``(index of the prompt, batch slot, that utterance's NEW frames [k][32] int32 CPU, last)`` -- ``last`` with
         the frames that complete the utterance (possibly none); an utterance that is empty before it ever holds a slot has slot -1.
         In between it yields ``None`` each time a block's frame steps have just been queued and before it waits for them: the
-        moment for a consumer to start work that should run beside those steps (generate_many_stream's Mimi decode)."""
-        from collections import deque
-        m = self._model
-        # one length limit for all, or one per prompt (a request's own max_audio_length_ms)
-        limits = [int(max_generation_len)] * len(prompts) if isinstance(max_generation_len, (int, float)) else [int(x) for x in max_generation_len]
-        if len(limits) != len(prompts):
-            raise ValueError("max_generation_len: one value, or one per prompt")
-        for (t, _), lim in zip(prompts, limits):
-            if t.shape[0] >= MAX_SEQ_LEN - lim:
-                raise ValueError(f"Inputs too long, must be below max_seq_len - max_generation_len: {MAX_SEQ_LEN - lim}")
-        if not prompts:
-            return
-        poll = poll or self._eos_poll
-        B = min(self._max_batch, len(prompts))
-        beside = getattr(m, "supports_refill_beside_the_loop", None)
-        plan = self._plan_prefixes(prompts)
-        if beside is not None and beside(B) and getattr(self, "refill_beside_the_loop", True):
-            yield from self._iter_codes_refilling_beside_the_loop(prompts, limits, temperature, topk, poll, B, plan)
-            return
-        pending = deque(range(len(prompts)))
-        slot_idx: List[Optional[int]] = [None] * B
-        slot_frames: List[List[torch.Tensor]] = [[] for _ in range(B)]
-        reported: List[int] = [0] * B                                   # frames of the slot's utterance already handed out
-        empty = torch.empty(0, 32, dtype=torch.int32)
-        finished: List[Tuple[int, int, torch.Tensor, bool]] = []        # this block's events
-        m.reset_caches()
-
-        def report(slot: int, upto: int, last: bool) -> None:
-            fs = slot_frames[slot][reported[slot]:upto]
-            if fs or last:
-                finished.append((slot_idx[slot], slot, torch.stack(fs).to(torch.int32) if fs else empty, last))
-            reported[slot] = max(reported[slot], min(upto, len(slot_frames[slot])))
-
-        def start(slot: int) -> bool:
-            while pending:
-                i = pending.popleft()
-                t, mk = prompts[i]
-                P, handle = plan[i]
-                if handle is None:
-                    f0 = m.refill_slot(slot, t, mk, temperature, topk).cpu()
-                else:                                                   # copy the prefix's K/V, run only the rows after it
-                    if seeded.pop(slot, None) is not handle:
-                        m.apply_prefix(handle, [slot])
-                    f0 = m.refill_slot(slot, t[P:], mk[P:], temperature, topk, start=P).cpu()
-                if limits[i] <= 0 or bool((f0 == 0).all()):
-                    finished.append((i, -1, empty, True))               # EOS in the very first frame: empty utterance (generator.py:296)
-                    continue
-                slot_idx[slot], slot_frames[slot], reported[slot] = i, [f0], 0
-                return True
-            slot_idx[slot] = None
-            return False
-
-        seeded = self._seed_shared(m, range(B), range(B), plan)
-        for s_ in range(B):
-            start(s_)
-        seeded.clear()
-        if finished:
-            yield finished
-            finished = []
-        g = m.num_frames()                                              # next global frame index
-        while any(i is not None for i in slot_idx):
-            active = [s_ for s_ in range(B) if slot_idx[s_] is not None]
-            done = [s_ for s_ in active if len(slot_frames[s_]) >= limits[slot_idx[s_]]]
-            if not done:
-                n = min(poll, min(limits[slot_idx[s_]] - len(slot_frames[s_]) for s_ in active))
-                for _ in range(n):
-                    m.step(B, temperature, topk)
-                yield None                                              # (the block's steps are queued)
-                fr, eos = m.read_frames(B, g, n)
-                for s_ in active:
-                    rows = fr[:, s_]
-                    if int(eos[s_]) >= 0:
-                        rows = rows[: max(int(eos[s_]) - g, 0)]
-                        done.append(s_)
-                    slot_frames[s_].extend(rows.unbind(0))
-                    if len(slot_frames[s_]) >= limits[slot_idx[s_]] and s_ not in done:
-                        done.append(s_)
-                g += n
-                for s_ in active:
-                    if s_ not in done:
-                        report(s_, len(slot_frames[s_]), False)
-            idle = []
-            for s_ in done:
-                report(s_, limits[slot_idx[s_]], True)
-                if not start(s_):
-                    idle.append(s_)
-            if idle and any(i is not None for i in slot_idx):
-                m.reset_slots(idle)                                      # a retired slot keeps stepping: keep its position away from max_seq
-            if finished:
-                yield finished
-                finished = []
-
-    def _iter_codes_refilling_beside_the_loop(self, prompts, limits: List[int], temperature: float, topk: int, poll: int, B: int, plan=None):
-        """The continuously refilled batch WITHOUT stalls (round 4): a retired slot's next prompt runs a few backbone layers after
-        each frame step (Model.refill_begin / refill_advance: about ``refill_row_layers`` = 600 prompt-row x layer units per step, i.e.
-        3 layers of a 190-row prompt = +8 % of a B = 32 step; measured: bench.py extras.config3.refill_beside_the_loop) while the other slots keep generating, and the new utterance's frame
-        0 is sampled by the batch's next frame step -- csm_prefill_slot made the other slots wait ~4 ms for a 190-row prompt and
-        > 8 ms for a 1,334-row one.  Until its prompt is complete a slot's rows are placeholders and are skipped here.
-        A prompt that starts with a registered prefix (``plan``) has the prefix's K/V copied into the slot right before its refill
-        begins, and only the rows after it count against the budget."""
-        from collections import deque
-        m = self._model
-        plan = plan or [(0, None)] * len(prompts)
-        L = getattr(m.bb, "num_layers", 16)
-        budget = getattr(self, "refill_row_layers", 600)
-        pending = deque(range(len(prompts)))
-        free = deque(range(B))
-        slot_idx: List[Optional[int]] = [None] * B          # prompt index generating in the slot
-        start_g: List[int] = [0] * B                        # global frame index of its frame 0
-        slot_frames: List[List[torch.Tensor]] = [[] for _ in range(B)]
-        reported: List[int] = [0] * B                       # frames of the slot's utterance already handed out
-        empty = torch.empty(0, 32, dtype=torch.int32)
-        refilling: Optional[Tuple[int, int, int]] = None    # (slot, prompt index, prompt rows)
-        m.reset_caches()
-
-        def feed(everything: bool) -> None:
-            """One bounded piece of refill work (``everything``: nobody is generating, so run whole prompts)."""
-            nonlocal refilling
-            while True:
-                if refilling is None:
-                    if not (free and pending):
-                        return
-                    slot, i = free.popleft(), pending.popleft()
-                    t, mk = prompts[i]
-                    P, handle = plan[i]
-                    if handle is None:
-                        m.refill_begin(slot, t, mk)
-                    else:                                   # copy, then begin at once: no frame step may fall between the two
-                        if seeded.pop(slot, None) is not handle:
-                            m.apply_prefix(handle, [slot])
-                        m.refill_begin(slot, t[P:], mk[P:], start=P)
-                    refilling = (slot, i, int(t.shape[0]) - P)
-                slot, i, rows = refilling
-                # the per-step budget grows with the backlog: every slot that waits for a prompt is 1/B of the batch's throughput idle, and
-                # the refill work is the same whenever it is done -- with nobody waiting the steps stay within ~8 % of an undisturbed one
-                per_call = max(1, budget * (1 + len(free)) // max(rows, 1))
-                if m.refill_advance(L if everything else min(per_call, L)):
-                    slot_idx[slot], start_g[slot], slot_frames[slot], reported[slot] = i, m.num_frames(), [], 0
-                    refilling = None
-                if not everything:
-                    return
-
-        seeded = self._seed_shared(m, list(free), list(pending)[:B], plan)
-        feed(True)                                          # the initial fill: nothing to protect yet
-        seeded.clear()
-        g = m.num_frames()
-        while any(i is not None for i in slot_idx) or refilling is not None or (pending and free):
-            if not any(i is not None for i in slot_idx):
-                feed(True)                                  # only prompts left: finish them at full speed
-                continue
-            active = [s_ for s_ in range(B) if slot_idx[s_] is not None]
-            n = max(min(poll, min(limits[slot_idx[s_]] - len(slot_frames[s_]) for s_ in active)), 1)
-            for _ in range(n):
-                m.step(B, temperature, topk)
-                feed(False)
-            yield None                                      # (the block's steps are queued)
-            fr, eos = m.read_frames(B, g, n)
-            done = []
-            events: List[Tuple[int, int, torch.Tensor, bool]] = []
-            for s_ in [s_ for s_ in range(B) if slot_idx[s_] is not None]:      # (a slot may have joined during this block)
-                lo = max(start_g[s_] - g, 0)                # rows of this block that belong to the slot's current utterance
-                if lo >= n:
-                    continue                                # (it joined after this block's last step)
-                rows, e = fr[lo:, s_], int(eos[s_])
-                ended = e >= start_g[s_]
-                if ended:
-                    rows = rows[: max(e - (g + lo), 0)]
-                slot_frames[s_].extend(rows.unbind(0))
-                last = ended or len(slot_frames[s_]) >= limits[slot_idx[s_]]
-                fs = slot_frames[s_][reported[s_]:max(limits[slot_idx[s_]], 0)]
-                reported[s_] += len(fs)
-                if fs or last:
-                    events.append((slot_idx[s_], s_, torch.stack(fs).to(torch.int32) if fs else empty, last))
-                if last:
-                    done.append(s_)
-            g += n
-            if events:
-                yield events
-            for s_ in done:
-                slot_idx[s_], slot_frames[s_] = None, []
-                free.append(s_)
-            if free and (pending or any(i is not None for i in slot_idx)):
-                m.reset_slots(list(free))                   # retired slots keep stepping as placeholders: keep their positions away from max_seq
+        moment for a consumer to start work that should run beside those steps (generate_many_stream's Mimi decode).
+        The scheduler is sesameai/live_batch.py; ``refill_beside_the_loop`` / ``refill_row_layers`` choose and tune how slots are refilled."""
+        yield from live_batch(self._model, prompts, max_generation_len, temperature, topk, poll or self._eos_poll, self._max_batch,
+                              self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN)
 
     def generate_codes_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: int,
                                   temperature: float, topk: int, poll: Optional[int] = None) -> List[torch.Tensor]:
@@ -528,8 +335,7 @@ class Generator:
                       temperature: float = 0.7, topk: int = 30) -> List[torch.Tensor]:
         """``generate`` for a list of requests through the continuously refilled batch: one audio tensor per request
         (``max_audio_length_ms``: one value, or one per request)."""
-        max_generation_len = (int(max_audio_length_ms / FRAME_MS) if isinstance(max_audio_length_ms, (int, float))
-                              else [int(x / FRAME_MS) for x in max_audio_length_ms])
+        max_generation_len = _frames_for(max_audio_length_ms)
         prompts = [self._build_prompt(t, sp, ctx) for t, sp, ctx in zip(texts, speakers, contexts)]
         out: List[torch.Tensor] = [torch.tensor([]) for _ in prompts]
         for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk):
@@ -553,88 +359,35 @@ class Generator:
         codec = self._audio_tokenizer
         if codec is None or not hasattr(codec, "open_streams"):
             raise RuntimeError("generate_many_stream needs a Mimi codec with stream pools (MimiCodec.open_streams)")
-        max_generation_len = (int(max_audio_length_ms / FRAME_MS) if isinstance(max_audio_length_ms, (int, float))
-                              else [int(x / FRAME_MS) for x in max_audio_length_ms])
+        max_generation_len = _frames_for(max_audio_length_ms)
         with torch.inference_mode():
             prompts = [self._build_prompt(t, sp, ctx) for t, sp, ctx in zip(texts, speakers, contexts)]
         if not prompts:
             return
         size = self._stream_buffer_size
         B = min(self._max_batch, len(prompts))
-        pools = self.__dict__.setdefault("_stream_pools", {})
-        if (B, size) not in pools:
-            pools[(B, size)] = codec.open_streams(B, max_chunk_frames=size)
-        pool = pools[(B, size)]
-        on_gpu = torch.device(self.device).type == "cuda"
-        if on_gpu and getattr(self, "_mimi_stream", None) is None:
-            self._mimi_stream = torch.cuda.Stream(device=self.device)
-        side = self._mimi_stream if on_gpu else None
-        owner: List[Optional[int]] = [None] * B                     # request whose stream the slot's pool stream carries
-        held: List[List[torch.Tensor]] = [[] for _ in range(B)]     # its frames not decoded yet
-        backlog: List[List[Tuple[int, int, torch.Tensor, bool]]] = []       # polled blocks whose audio is still to be decoded
-        no_pcm = torch.empty(0, dtype=torch.float32, device=self.device)
-        no_frames = torch.empty(0, 32, dtype=torch.int32)
-
-        def deliver(block) -> List[Tuple[int, torch.Tensor, torch.Tensor, bool]]:
-            """One polled block (a slot carries at most one utterance in it) -> its chunks."""
-            out: List[Tuple[int, torch.Tensor, torch.Tensor, bool]] = []
-            fresh: List[int] = []
-            ending: List[int] = []
-            for i, slot, fr, last in block:
-                if slot < 0:
-                    out.append((i, no_pcm, no_frames, True))
-                    continue
-                if owner[slot] != i:
-                    owner[slot], held[slot] = i, []
-                    fresh.append(slot)
-                held[slot].extend(fr.unbind(0))
-                if last:
-                    ending.append(slot)
-            calls: List[Tuple[List[int], int, torch.Tensor, torch.Tensor]] = []
-
-            def decode(slots: List[int], T: int) -> None:
-                frames = torch.stack([torch.stack(held[s_][:T]) for s_ in slots]).to(torch.int32)      # (n, T, 32)
-                for s_ in slots:
-                    del held[s_][:T]
-                calls.append((slots, T, frames, pool.decode(slots, frames.permute(0, 2, 1))))
-
-            with torch.inference_mode(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                if fresh:
-                    pool.reset(fresh)
-                while True:
-                    full = [s_ for s_ in range(B) if len(held[s_]) >= size]
-                    if not full:
-                        break
-                    decode(full, size)
-                by_len: dict = {}
-                for s_ in ending:
-                    by_len.setdefault(len(held[s_]), []).append(s_)
-                for T in sorted(by_len):
-                    if T:
-                        decode(by_len[T], T)
-            if side is not None:
-                side.synchronize()
-            closed = set()
-            for k, (slots, T, frames, pcm) in enumerate(calls):
-                for j, s_ in enumerate(slots):
-                    last = s_ in ending and not any(s_ in later[0] for later in calls[k + 1:])
-                    if last:
-                        closed.add(s_)
-                    out.append((owner[s_], pcm[j, 0], frames[j], last))
-            for s_ in ending:
-                if s_ not in closed:                                # nothing was left to decode: the closing chunk is empty
-                    out.append((owner[s_], no_pcm, no_frames, True))
-                owner[s_] = None
-            return out
-
+        if self._stream_pools is None:
+            self._stream_pools = {}
+        if (B, size) not in self._stream_pools:
+            self._stream_pools[(B, size)] = codec.open_streams(B, max_chunk_frames=size)
+        streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device)
+        backlog: List[list] = []                                    # polled blocks whose audio is still to be decoded
         for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size):
             if block is not None:
                 backlog.append(block)
                 continue
             while backlog:                                          # the next block's steps are queued: decode beside them
-                yield from deliver(backlog.pop(0))
+                yield from streams.chunks(backlog.pop(0))
         while backlog:
-            yield from deliver(backlog.pop(0))
+            yield from streams.chunks(backlog.pop(0))
+
+    def _side_stream(self):
+        """The HIP stream Mimi decodes on beside the frame steps, made on first use; None on a CPU device (the host-logic tests)."""
+        if torch.device(self.device).type != "cuda":
+            return None
+        if self._mimi_stream is None:
+            self._mimi_stream = torch.cuda.Stream(device=self.device)
+        return self._mimi_stream
 
     def _decode_frames(self, frames: torch.Tensor) -> torch.Tensor:
         """frames [n][1][32] -> audio (n*1920,) (reference: _decode_frames, generator.py:111-117)."""
@@ -659,10 +412,7 @@ class Generator:
             tokens, mask = tokens.unsqueeze(0), mask.unsqueeze(0)
         if tokens.shape[1] >= MAX_SEQ_LEN - max_generation_len:
             raise ValueError(f"Inputs too long, must be below max_seq_len - max_generation_len: {MAX_SEQ_LEN - max_generation_len}")
-        on_gpu = torch.device(self.device).type == "cuda"           # (a CPU device only occurs in the host-logic tests)
-        if on_gpu and getattr(self, "_mimi_stream", None) is None:
-            self._mimi_stream = torch.cuda.Stream(device=self.device)
-        side = self._mimi_stream if on_gpu else None
+        side = self._side_stream()
         pending: List[torch.Tensor] = []
         size = self._stream_buffer_size
 

@@ -1,0 +1,249 @@
+"""The continuously refilled batch behind ``Generator.iter_codes_continuous`` / ``generate_many`` / ``generate_many_stream``: ONE slot
+scheduler (``LiveBatch``) with two ways of giving a free slot its next prompt (``_Stalling``, ``_BesideTheLoop``), and the consumer that
+turns its polled blocks into streamed audio (``SlotStreams``).  Host code only; the reference (batch-1) has no counterpart."""
+import contextlib
+from collections import deque
+from dataclasses import dataclass
+from typing import Iterator, List, Optional, Tuple
+
+import torch
+
+from .models import match_stored_prefix
+
+_NO_FRAMES = torch.empty(0, 32, dtype=torch.int32)
+
+
+@dataclass
+class _Utterance:
+    """What a batch slot holds while it generates."""
+    index: int                          # of its prompt
+    limit: int                          # frames
+    first: int                          # global frame index of the first frame it takes from the history: its frame 0, or frame 1 when
+    frames: List[torch.Tensor]          # the refill handed frame 0 over; the frames held so far
+    reported: int = 0                   # how many of them were handed out
+
+
+class LiveBatch:
+    """A batch of ``slots`` slots kept full: every polled block's rows are cut per slot at the utterance's EOS or length limit and handed out
+    as events ``(index of the prompt, batch slot, its NEW frames [k][32] int32 CPU, last)``, finished utterances are retired and their slots
+    refilled while the others keep generating.  How a free slot gets its next prompt is the subclass's business -- ``_feed(everything)``: called
+    after every queued frame step, and with ``everything`` when nobody generates (True: it did something); ``_vacated``, ``_idle``,
+    ``_report_order`` -- the rest happens here, once.  The Philox key of a sampled frame includes the global frame index, so the number of
+    frame steps between any two refill calls is part of the results (tests/test_live_batch_trace.py pins them)."""
+
+    def __init__(self, model, prompts, limits: List[int], temperature: float, topk: int, poll: int, slots: int, store: list):
+        self.m, self.prompts, self.limits, self.sampling, self.poll, self.B = model, prompts, limits, (temperature, topk), poll, slots
+        # per prompt (rows P to copy, handle): the registered prefix with the longest match, (0, None) without one -- all matched before the loop
+        # starts: no comparison's host synchronisation falls between frame steps; and {slot: handle} of the initial fill's shared copies
+        self.plan = [match_stored_prefix(store, t, mk) for t, mk in prompts] if store else [(0, None)] * len(prompts)
+        self.seeded = {slot: handle for slot, (_, handle) in enumerate(self.plan[:slots]) if handle is not None}
+        self.pending = deque(range(len(prompts)))
+        self.free = deque(range(slots))                             # slots waiting for a prompt
+        self.slots: List[Optional[_Utterance]] = [None] * slots
+        self.events: list = []                                      # of the current block
+        self.g = 0                                                  # next global frame index to read
+
+    def run(self) -> Iterator[Optional[list]]:
+        """Per polled block a list of events; ``None`` each time a block's frame steps have just been queued (Generator._iter_blocks_continuous)."""
+        m, B = self.m, self.B
+        m.reset_caches()
+        for handle in {id(h): h for h in self.seeded.values()}.values():    # all slots that start from the same prefix: ONE copy
+            m.apply_prefix(handle, [slot for slot, h in self.seeded.items() if h is handle])
+        self._feed(True)                                            # the initial fill: nothing to protect yet
+        self.seeded.clear()
+        self.g = m.num_frames()
+        while True:
+            if self.events:
+                yield self.events
+                self.events = []
+            active = [u for u in self.slots if u is not None]
+            if not active:
+                if not self._feed(True):                            # only prompts left: finish them at full speed
+                    return
+                continue
+            cuts = [(s, True) for s, u in enumerate(self.slots) if u is not None and u.frames and len(u.frames) >= u.limit]
+            if not cuts:                                            # (else an utterance that came with its frame 0 is complete already: no steps)
+                n = max(min(self.poll, min(u.limit - len(u.frames) for u in active)), 1)
+                for _ in range(n):
+                    m.step(B, *self.sampling)
+                    self._feed(False)
+                yield None                                          # (the block's steps are queued)
+                cuts = self._read(n)
+            for s, last in self._report_order(cuts):
+                u = self.slots[s]
+                fs = u.frames[u.reported:max(u.limit, 0)]           # the event: what is new, up to the limit
+                u.reported += len(fs)
+                if fs or last:
+                    self.events.append((u.index, s, torch.stack(fs).to(torch.int32) if fs else _NO_FRAMES, last))
+                if last:
+                    self.slots[s] = None
+                    self._vacated(s)
+            idle = self._idle([s for s, last in cuts if last])
+            if idle and (self.pending or any(u is not None for u in self.slots)):
+                m.reset_slots(idle)                                 # a retired slot keeps stepping: keep its position away from max_seq
+
+    def _read(self, n: int) -> List[Tuple[int, bool]]:
+        """Reads the block of ``n`` steps and gives every slot its rows, cut at its EOS.  Returns [(slot, whether its utterance is over)]."""
+        fr, eos = self.m.read_frames(self.B, self.g, n)            # waits for the block
+        cuts = []
+        for s, u in enumerate(self.slots):                          # (a slot may have joined during this block)
+            lo = max(u.first - self.g, 0) if u is not None else n   # rows of this block that belong to the slot's current utterance
+            if lo >= n:
+                continue                                            # (nobody there, or it joined after this block's last step)
+            rows, e = fr[lo:, s], int(eos[s])
+            ended = e >= u.first
+            if ended:
+                rows = rows[: max(e - (self.g + lo), 0)]
+            u.frames.extend(rows.unbind(0))
+            cuts.append((s, ended or len(u.frames) >= u.limit))
+        self.g += n
+        return cuts
+
+    def _rows_to_run(self, slot: int, i: int) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+        """(tokens, mask, keywords) for the refill of ``slot`` with prompt ``i``.  A registered prefix's K/V are copied into the slot HERE (unless the
+        initial fill's shared copy put them there) and only the rows after it run: the caller begins at once, no frame step between the two."""
+        (t, mk), (P, handle) = self.prompts[i], self.plan[i]
+        if handle is None:
+            return t, mk, {}
+        if self.seeded.pop(slot, None) is not handle:
+            self.m.apply_prefix(handle, [slot])
+        return t[P:], mk[P:], {"start": P}
+
+    def _report_order(self, cuts: List[Tuple[int, bool]]) -> List[Tuple[int, bool]]:
+        return cuts                                                 # by slot
+
+
+class _Stalling(LiveBatch):
+    """``Model.refill_slot``: the batch waits while the whole prompt runs (~4 ms for 190 rows, > 8 ms for 1,334) and frame 0 comes back at
+    once.  An all-zero frame 0, or a limit <= 0, is an empty utterance (generator.py:296) reported with slot -1; the slot takes the next."""
+
+    def _vacated(self, slot: int) -> None:
+        while self.pending:
+            i = self.pending.popleft()
+            t, mk, kw = self._rows_to_run(slot, i)
+            f0 = self.m.refill_slot(slot, t, mk, *self.sampling, **kw).cpu()
+            if self.limits[i] > 0 and not bool((f0 == 0).all()):
+                self.slots[slot] = _Utterance(i, self.limits[i], self.g, [f0])
+                return
+            self.events.append((i, -1, _NO_FRAMES, True))
+
+    def _feed(self, everything: bool) -> bool:
+        while everything and self.free:     # (the initial fill; a slot that gets nothing there is not rewound)
+            self._vacated(self.free.popleft())
+        return False                        # later every vacated slot is refilled at once: with nobody generating nothing is left
+
+    def _idle(self, vacated: List[int]) -> List[int]:
+        return [s for s in vacated if self.slots[s] is None]        # out of prompts: rewound once
+
+    def _report_order(self, cuts):
+        return sorted(cuts, key=lambda c: c[1])                     # the ending slots last: each is followed by the empty utterances its refill met
+
+
+class _BesideTheLoop(LiveBatch):
+    """WITHOUT stalls: a retired slot's next prompt runs a few backbone layers after each frame step (Model.refill_begin / refill_advance: about
+    ``budget`` = 600 prompt-row x layer units per step, i.e. 3 layers of a 190-row prompt = +8 % of a B = 32 step; measured: bench.py
+    extras.config3.refill_beside_the_loop) while the other slots keep generating, and the new utterance's frame 0 is sampled by the batch's next
+    frame step.  Until then the slot's rows are placeholders and are skipped.  Only the rows after a registered prefix count against the budget."""
+
+    def __init__(self, *args, budget: int):
+        super().__init__(*args)
+        self.budget, self.layers = budget, self.m.bb.num_layers
+        self.refilling: Optional[Tuple[int, int, int]] = None       # (slot, prompt index, prompt rows to run)
+
+    def _feed(self, everything: bool) -> bool:
+        """One bounded piece of refill work (``everything``: nobody is generating, so run whole prompts).  False: there was none."""
+        m, fed = self.m, False
+        while self.refilling is not None or (self.free and self.pending):
+            if self.refilling is None:
+                slot, i = self.free.popleft(), self.pending.popleft()
+                t, mk, kw = self._rows_to_run(slot, i)
+                m.refill_begin(slot, t, mk, **kw)
+                self.refilling = (slot, i, int(t.shape[0]))
+            slot, i, rows = self.refilling
+            # the per-step budget grows with the backlog: every slot that waits for a prompt is 1/B of the batch's throughput idle, and
+            # the refill work is the same whenever it is done -- with nobody waiting the steps stay within ~8 % of an undisturbed one
+            per_call = max(1, self.budget * (1 + len(self.free)) // max(rows, 1))
+            if m.refill_advance(self.layers if everything else min(per_call, self.layers)):
+                self.slots[slot] = _Utterance(i, self.limits[i], m.num_frames(), [])
+                self.refilling = None
+            fed = True
+            if not everything:
+                break
+        return fed
+
+    def _vacated(self, slot: int) -> None:
+        self.free.append(slot)
+
+    def _idle(self, vacated: List[int]) -> List[int]:
+        return list(self.free)                                      # they step as placeholders until a prompt takes them: rewound after every block
+
+
+def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_batch, store, beside_the_loop, refill_row_layers, max_seq_len):
+    """``LiveBatch.run`` over ``prompts`` [(tokens (S_i,33), mask (S_i,33)), ...] with one length limit for all or one per prompt (a
+    request's own max_audio_length_ms), refilling beside the loop where the model's frame steps of this batch size honour it."""
+    limits = [int(max_generation_len)] * len(prompts) if isinstance(max_generation_len, (int, float)) else [int(x) for x in max_generation_len]
+    if len(limits) != len(prompts):
+        raise ValueError("max_generation_len: one value, or one per prompt")
+    for (t, _), lim in zip(prompts, limits):
+        if t.shape[0] >= max_seq_len - lim:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_generation_len: {max_seq_len - lim}")
+    if not prompts:
+        return
+    B = min(max_batch, len(prompts))
+    args = (model, prompts, limits, temperature, topk, poll, B, store)
+    supported = getattr(model, "supports_refill_beside_the_loop", None)         # (a scripted model may lack it)
+    beside = supported is not None and supported(B) and beside_the_loop
+    yield from (_BesideTheLoop(*args, budget=refill_row_layers) if beside else _Stalling(*args)).run()
+
+
+class SlotStreams:
+    """The stream state of ``generate_many_stream``: each batch slot is one stream of a ``MimiStreamPool``; ``owner[slot]`` is the request
+    whose audio the slot's stream carries, ``held[slot]`` its frames not decoded yet.  Decodes run on ``side`` (a HIP stream, or None)."""
+
+    def __init__(self, pool, slots: int, size: int, side, device):
+        self.pool, self.size, self.side = pool, size, side
+        self.owner: List[Optional[int]] = [None] * slots
+        self.held: List[List[torch.Tensor]] = [[] for _ in range(slots)]
+        self.no_pcm = torch.empty(0, dtype=torch.float32, device=device)
+
+    def chunks(self, block: list) -> List[Tuple[int, torch.Tensor, torch.Tensor, bool]]:
+        """One polled block (a slot carries at most one utterance in it) -> its chunks: a stream is reset when a new request takes its slot, all slots that
+        hold ``size`` frames go into ONE pool call, finishing requests flush the rest grouped by length and close with ONE ``last`` chunk, maybe empty."""
+        owner, held, pool = self.owner, self.held, self.pool
+        out: List[Tuple[int, torch.Tensor, torch.Tensor, bool]] = []
+        fresh, ending = [], []                                      # slots a new request took / whose request ends, in this block
+        for i, slot, fr, last in block:
+            if slot < 0:
+                out.append((i, self.no_pcm, _NO_FRAMES, True))
+                continue
+            if owner[slot] != i:
+                owner[slot], held[slot] = i, []
+                fresh.append(slot)
+            held[slot].extend(fr.unbind(0))
+            if last:
+                ending.append(slot)
+        calls: List[Tuple[List[int], torch.Tensor, torch.Tensor]] = []
+
+        def decode(slots: List[int], T: int) -> None:
+            frames = torch.stack([torch.stack(held[s_][:T]) for s_ in slots]).to(torch.int32)      # (n, T, 32)
+            for s_ in slots:
+                del held[s_][:T]
+            calls.append((slots, frames, pool.decode(slots, frames.permute(0, 2, 1))))
+
+        with torch.inference_mode(), (torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext()):
+            if fresh:
+                pool.reset(fresh)
+            while full := [s_ for s_, h in enumerate(held) if len(h) >= self.size]:
+                decode(full, self.size)
+            for T in sorted({len(held[s_]) for s_ in ending} - {0}):
+                decode([s_ for s_ in ending if len(held[s_]) == T], T)
+        if self.side is not None:
+            self.side.synchronize()
+        final = {s_: k for k, (slots, _, _) in enumerate(calls) for s_ in slots}       # the call that holds a slot's newest chunk
+        for k, (slots, frames, pcm) in enumerate(calls):
+            out.extend((owner[s_], pcm[j, 0], frames[j], s_ in ending and final[s_] == k) for j, s_ in enumerate(slots))
+        for s_ in ending:
+            if s_ not in final:                                     # nothing was left to decode: the closing chunk is empty
+                out.append((owner[s_], self.no_pcm, _NO_FRAMES, True))
+            owner[s_] = None
+        return out

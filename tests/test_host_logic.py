@@ -446,7 +446,7 @@ def test_continuous_batching_retires_at_eos_and_refills_the_slot():
 
 
 class _ScriptedSlotsBeside:
-    """Stands in for sesameai.models.Model under Generator._iter_codes_refilling_beside_the_loop (the contract of csm_refill_begin /
+    """Stands in for sesameai.models.Model under the live batch refilling beside the loop (sesameai/live_batch.py, _BesideTheLoop; the contract of csm_refill_begin /
     csm_refill_advance / k_advance's fresh flag, include/csm_hip.h): a prompt needs 16 layers of refill work, handed out a few per call
     between frame steps; until it is complete the slot emits placeholder frames (all 7); the step after completion emits the
     utterance's frame 0 and restarts the slot's EOS word; a retired slot emits placeholders too."""

@@ -1,5 +1,5 @@
 """Host logic of the prefix store (no GPU): scripted models stand in for the frame loop (tests/test_host_logic.py) and record the
-prefix calls.  What is checked is the bookkeeping of Generator.cache_prefix / the two continuous loops: which prefix a prompt is matched
+prefix calls.  What is checked is the bookkeeping of Generator.cache_prefix / the live batch (sesameai/live_batch.py, both refill policies): which prefix a prompt is matched
 with and how far, that the copy sits immediately in front of the refill it belongs to, that only the rows after it are handed to the
 model (at ``start = P``), that the refill budget counts those rows, that the initial fill seeds slots that share a prefix with one
 call -- and that without a registered prefix the model sees exactly the calls it saw before."""
