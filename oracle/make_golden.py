@@ -43,6 +43,12 @@ Files (all torch.save'd dicts of small tensors):
                     margins and the bf16-vs-fp32 gap per frame; for legs A and E the move of the logits (at the golden's top-8
                     indices, frame 0) under each scale fault of oracle.csm_ref.NORM_FAULTS that clears 1.5 x the leg's gap.
                     About 2 minutes on 8 CPU threads.
+  mimi_long.pt      full-size Mimi (seed 4321 weights) at real clip lengths (MIMI_LONG): the oracle's PCM of seeded 126 / 150 / 300 / 1125-frame
+                    clips (every 16th sample + head / tail windows; the codes are a function of the stored seeds), the oracle's codes of a 5 s and a
+                    10.4 s voice prompt, and per clip how far the compared samples move when the oracle's attention window is 249, 251 or unbounded
+                    or its RoPE angle is taken modulo the stream pool's ring (270): each asserted >= 10 x the 2e-5-of-peak bound of the GPU test
+                    wherever the fault touches the clip; for the prompts the frames whose codes change, and the share of frames a 1e-6 nudge of
+                    the latent leaves alone (the inputs do not sit on quantiser ties).  The wall time of every oracle run is stored beside it.
 """
 from __future__ import annotations
 
@@ -434,6 +440,118 @@ def norms_golden(shape: C.CsmShape):
     return gold
 
 
+# ---- full-size Mimi at real clip lengths ----------------------------------------------------------------------------------------------
+MIMI_LONG = dict(
+    weight_seed=4321,
+    decode=((126, 9126), (150, 9150), (300, 9300), (1125, 91125)),              # (frames, code seed): 252 / 300 / 600 / 2250 transformer tokens
+    encode=((1920 * 126 + 777, 7126), (1920 * 260 + 5, 7260)),                  # (samples, wav seed): a 5 s and a 10.4 s voice prompt
+    stride=16, window=2048, last_frames=10,
+    bound=2e-5,                 # of the clip's peak: what tests/test_mimi_long_gpu.py allows between the HIP codec and these vectors
+    fault_factor=10.0,          # an injected fault moves the compared samples by at least this many bounds
+    pool_ring=270,              # tr_context + 2 * max_chunk_frames of open_streams(n, max_chunk_frames=10)
+    tie_nudge=1e-6, tie_unchanged_min=0.97, enc_changed_min=0.10,
+    # graded against the live oracle by the GPU test (no golden): a batch of two prompts, and lengths around one hop
+    encode_b2=(1920 * 40 + 300, 7340), encode_edges=((1919, 7301), (1920, 7302), (1921, 7303), (9600, 7304)),
+    longest_oracle_seconds=9.9)     # M.decode of the 1125-frame clip, 8 CPU threads, measured when the fixture was first generated
+MIMI_LONG_FAULTS = (("ctx249", dict(context=249)), ("ctx251", dict(context=251)), ("nowindow", dict(context=M.NO_WINDOW)),
+                    ("rope_mod_ring", dict(rope_mod=270)))
+
+
+def mimi_long_codes(seed: int, frames: int, rows: int = 1) -> torch.Tensor:
+    return torch.randint(0, 2048, (rows, 32, frames), generator=torch.Generator().manual_seed(seed))
+
+
+def mimi_long_wav(seed: int, samples: int, rows: int = 1) -> torch.Tensor:
+    return torch.randn(rows, 1, samples, generator=torch.Generator().manual_seed(seed)) * 0.3
+
+
+def mimi_long_views(pcm: torch.Tensor):
+    """The samples of a clip (.., hop * T) that the fixture keeps and the GPU test compares: name -> view."""
+    a = MIMI_LONG
+    s16 = pcm[..., ::a["stride"]]
+    return dict(stride16=s16, head=pcm[..., :a["window"]], tail=pcm[..., -a["window"]:],
+                last_stride16=s16[..., -a["last_frames"] * 1920 // a["stride"]:])
+
+
+def mimi_long_fault_applies(fault: str, tokens: int) -> bool:
+    """Does the fault change anything a clip of this many transformer tokens computes?"""
+    kw = dict(MIMI_LONG_FAULTS)[fault]
+    if "rope_mod" in kw:
+        return tokens > kw["rope_mod"]
+    return tokens > 250          # some query's window starts above 0: the last key of a 251-token window / the first of a 250-token one exists
+
+
+def mimi_long_move(got: torch.Tensor, want: torch.Tensor) -> float:
+    """max over the compared views of max|got - want| / the view's peak: the statistic the GPU test bounds per view."""
+    g, w = mimi_long_views(got), mimi_long_views(want)
+    return max(float((g[k] - w[k]).abs().max() / w[k].abs().max()) for k in w)
+
+
+def mimi_long_tie_unchanged(s, w, z: torch.Tensor, codes: torch.Tensor, seed: int) -> float:
+    """Share of frames whose 32 codes all survive a nudge of the latent by tie_nudge x its peak (seeded noise)."""
+    noise = torch.randn(z.shape, generator=torch.Generator().manual_seed(seed + 1))
+    return float((M.quantize(s, w, z + MIMI_LONG["tie_nudge"] * z.abs().max() * noise) == codes).all(dim=1).float().mean())
+
+
+def mimi_long_golden():
+    a = MIMI_LONG
+    s = M.mimi_full()
+    w = M.make_weights(s, seed=a["weight_seed"], encoder=True)
+    need = a["fault_factor"] * a["bound"]
+    gold = dict(weight_seed=a["weight_seed"], bound=a["bound"], fault_factor=a["fault_factor"], pool_ring=a["pool_ring"],
+                stride=a["stride"], window=a["window"], longest_oracle_seconds=a["longest_oracle_seconds"], decode=[], encode=[])
+    for frames, seed in a["decode"]:
+        codes = mimi_long_codes(seed, frames)
+        t0 = time.time()
+        pcm = M.decode(s, w, codes)
+        secs = time.time() - t0
+        v = mimi_long_views(pcm)
+        moves = {}
+        for fault, kw in MIMI_LONG_FAULTS:
+            moves[fault] = mimi_long_move(M.decode(s, w, codes, **kw), pcm) if mimi_long_fault_applies(fault, 2 * frames) else 0.0
+            assert not mimi_long_fault_applies(fault, 2 * frames) or moves[fault] >= need, \
+                f"{frames} frames: the fault {fault} moves the compared samples by {moves[fault]:.3g} of peak < {need:.3g}"
+        print(f"  mimi_long decode {frames} frames: oracle {secs:.1f}s, peak {float(pcm.abs().max()):.3g}, fault moves (of peak) "
+              + ", ".join(f"{k} {x:.3g}" for k, x in moves.items()), flush=True)
+        gold["decode"].append(dict(frames=frames, code_seed=seed, code_checksum=int((codes[0] * torch.arange(1, frames + 1)).sum()),
+                                   pcm_stride16=v["stride16"].clone(), pcm_head=v["head"].clone(), pcm_tail=v["tail"].clone(),
+                                   fault_moves=moves))
+    for samples, seed in a["encode"]:
+        wav = mimi_long_wav(seed, samples)
+        t0 = time.time()
+        z = M.encode_latent(s, w, wav)
+        codes = M.quantize(s, w, z)
+        secs = time.time() - t0
+        T = codes.shape[-1]
+        past = torch.arange(T) >= 125                   # frames whose last token (2t + 1) has a window that starts above 0
+        changed = {}
+        for fault, kw in MIMI_LONG_FAULTS[:3]:
+            diff = (M.encode(s, w, wav, **kw) != codes).any(dim=1)[0]
+            assert not bool(diff[:124].any()), "a window fault reached frames whose windows all start at 0"
+            changed[fault] = int(diff.sum())
+        unchanged = mimi_long_tie_unchanged(s, w, z, codes, seed)
+        assert unchanged >= a["tie_unchanged_min"], f"{samples} samples: only {unchanged:.3f} of the frames survive a {a['tie_nudge']} nudge"
+        print(f"  mimi_long encode {samples} samples ({T} frames, {int(past.sum())} past the window): oracle {secs:.1f}s, frames changed "
+              + ", ".join(f"{k} {x}" for k, x in changed.items()) + f", unchanged under the nudge {unchanged:.3f}", flush=True)
+        gold["encode"].append(dict(samples=samples, wav_seed=seed, wav_checksum=float(wav.double().abs().sum()), codes=codes.to(torch.int16),
+                                   frames_past_window=int(past.sum()), frames_changed=changed, tie_unchanged=unchanged))
+    mimi_long_check_encode_faults(gold["encode"])
+    return gold
+
+
+def mimi_long_check_encode_faults(enc) -> None:
+    """Every window fault changes the codes of >= enc_changed_min of the frames past the window: over the prompts together, and on its
+    own in every prompt that has at least 1 / enc_changed_min such frames (the 5 s prompt has 2: 254 tokens against a window of 250)."""
+    need = MIMI_LONG["enc_changed_min"]
+    for fault, _ in MIMI_LONG_FAULTS[:3]:
+        total, past = sum(e["frames_changed"][fault] for e in enc), sum(e["frames_past_window"] for e in enc)
+        assert total >= need * past, f"the fault {fault} changes {total} of the {past} frames past the window"
+        for e in enc:
+            if e["frames_past_window"] * need >= 1:
+                assert e["frames_changed"][fault] >= need * e["frames_past_window"], \
+                    f"{e['samples']} samples: the fault {fault} changes {e['frames_changed'][fault]} of the {e['frames_past_window']} frames past the window"
+
+
 def sampler_cases():
     g = torch.Generator().manual_seed(77)
     V = 2051
@@ -484,6 +602,8 @@ def main():
                             pcm_tail=whole[..., -4096:].clone(),
                             chunks_stride16=chunks[..., ::16].clone(),
                             rms=whole.pow(2).mean().sqrt()), os.path.join(OUT, f"mimi_{name}.pt"))
+    if want("mimilong"):
+        torch.save(mimi_long_golden(), os.path.join(OUT, "mimi_long.pt"))
     if want("tinydecisive"):
         torch.save(decisive_golden(C.csm_tiny(), 1234, full=False), os.path.join(OUT, "tiny_decisive.pt"))
     if want("decisive"):

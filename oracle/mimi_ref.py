@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -191,26 +191,35 @@ def rvq_decode(s: MimiShape, w: Dict[str, torch.Tensor], codes: torch.Tensor) ->
 
 
 def _rope_interleaved(x: torch.Tensor, pos: torch.Tensor, theta: float) -> torch.Tensor:
-    """x (B,H,T,hd); rotate pairs (2i,2i+1) by pos * theta^(-2i/hd)."""
+    """x (B,H,T,hd); rotate pairs (2i,2i+1) by pos * theta^(-2i/hd).  Angles in x's dtype (fp32 weights: fp32, as ever)."""
     hd = x.shape[-1]
-    freqs = torch.exp(torch.arange(hd // 2, dtype=torch.float32) * (-math.log(theta) * 2 / hd))
-    ang = pos.float()[:, None] * freqs[None, :]                    # (T, hd/2)
+    freqs = torch.exp(torch.arange(hd // 2, dtype=x.dtype) * (-math.log(theta) * 2 / hd))
+    ang = pos.to(x.dtype)[:, None] * freqs[None, :]                # (T, hd/2)
     c, sn = torch.cos(ang), torch.sin(ang)
     xr, xi = x[..., 0::2], x[..., 1::2]
     out = torch.stack([xr * c - xi * sn, xr * sn + xi * c], dim=-1)
     return out.flatten(-2)
 
 
+NO_WINDOW = 1 << 30      # ``context=NO_WINDOW``: every earlier key stays visible
+
+
 def transformer(s: MimiShape, w: Dict[str, torch.Tensor], x: torch.Tensor, offset: int = 0,
-                prefix: str = "transformer") -> torch.Tensor:
+                prefix: str = "transformer", context: Optional[int] = None, rope_mod: Optional[int] = None) -> torch.Tensor:
     """x (B,T,d) -> (B,T,d); causal with context window (key j visible to query i iff
-    0 <= i-j < context)."""
+    0 <= i-j < context).
+
+    ``context`` and ``rope_mod`` are FAULT INJECTION for the tests (defaults: the model): another window length than
+    ``s.tr_context``, and RoPE angles taken from ``pos % rope_mod`` -- what an implementation computes that rotates by
+    its K/V ring slot instead of the token position."""
     B, T, d = x.shape
     H = s.tr_heads
     hd = d // H
     pos = torch.arange(offset, offset + T)
     delta = pos[:, None] - pos[None, :]
-    allowed = (delta >= 0) & (delta < s.tr_context)
+    allowed = (delta >= 0) & (delta < (s.tr_context if context is None else context))
+    if rope_mod is not None:
+        pos = pos % rope_mod
     for i in range(s.tr_layers):
         L = f"{prefix}.{i}"
         h = F.layer_norm(x, (d,), w[f"{L}.norm1.weight"], w[f"{L}.norm1.bias"], s.norm_eps)
@@ -239,11 +248,12 @@ def seanet_decode(s: MimiShape, w: Dict[str, torch.Tensor], x: torch.Tensor) -> 
 
 
 @torch.inference_mode()
-def decode(s: MimiShape, w: Dict[str, torch.Tensor], codes: torch.Tensor) -> torch.Tensor:
-    """codes (B,K,T) -> pcm (B,1,hop*T) fp32."""
+def decode(s: MimiShape, w: Dict[str, torch.Tensor], codes: torch.Tensor, context: Optional[int] = None,
+           rope_mod: Optional[int] = None) -> torch.Tensor:
+    """codes (B,K,T) -> pcm (B,1,hop*T) fp32.  ``context`` / ``rope_mod``: fault injection, see ``transformer``."""
     x = rvq_decode(s, w, codes)
     x = causal_convtr1d(x, w["upsample.convtr.weight"], None, 2, groups=s.hidden)
-    x = transformer(s, w, x.transpose(1, 2)).transpose(1, 2)
+    x = transformer(s, w, x.transpose(1, 2), context=context, rope_mod=rope_mod).transpose(1, 2)
     return seanet_decode(s, w, x)
 
 
@@ -272,8 +282,10 @@ def _strided_causal_conv(x: torch.Tensor, w: torch.Tensor, b, stride: int, pad_m
 
 
 @torch.inference_mode()
-def encode_latent(s: MimiShape, w: Dict[str, torch.Tensor], wav: torch.Tensor) -> torch.Tensor:
-    """wav (B,1,n) -> pre-quantisation embeddings (B, hidden, T), T = ceil(n / hop)."""
+def encode_latent(s: MimiShape, w: Dict[str, torch.Tensor], wav: torch.Tensor, context: Optional[int] = None,
+                  rope_mod: Optional[int] = None) -> torch.Tensor:
+    """wav (B,1,n) -> pre-quantisation embeddings (B, hidden, T), T = ceil(n / hop).  ``context`` / ``rope_mod``: fault
+    injection, see ``transformer``."""
     x = causal_conv1d(wav, w["enc.conv_in.weight"], w["enc.conv_in.bias"])
     for j, r in enumerate(reversed(s.ratios)):
         y = causal_conv1d(F.elu(x), w[f"enc.down.{j}.res.conv1.weight"], w[f"enc.down.{j}.res.conv1.bias"])
@@ -281,7 +293,7 @@ def encode_latent(s: MimiShape, w: Dict[str, torch.Tensor], wav: torch.Tensor) -
         x = x + y
         x = _strided_causal_conv(F.elu(x), w[f"enc.down.{j}.conv.weight"], w[f"enc.down.{j}.conv.bias"], r)
     x = causal_conv1d(F.elu(x), w["enc.conv_out.weight"], w["enc.conv_out.bias"])
-    x = transformer(s, w, x.transpose(1, 2), prefix="enc_transformer").transpose(1, 2)
+    x = transformer(s, w, x.transpose(1, 2), prefix="enc_transformer", context=context, rope_mod=rope_mod).transpose(1, 2)
     return _strided_causal_conv(x, w["downsample.conv.weight"], None, 2, pad_mode="replicate")
 
 
@@ -296,11 +308,8 @@ def _rvq_encode(res: torch.Tensor, books: List[torch.Tensor]) -> List[torch.Tens
 
 
 @torch.inference_mode()
-def encode(s: MimiShape, w: Dict[str, torch.Tensor], wav: torch.Tensor) -> torch.Tensor:
-    """wav (B,1,n) fp32 @ 24 kHz -> codes (B, num_codebooks, ceil(n/1920)) int64.  Split RVQ: the
-    semantic codebook and the acoustic stack both quantise the SAME embeddings, each behind its own
-    1x1 input projection."""
-    z = encode_latent(s, w, wav)
+def quantize(s: MimiShape, w: Dict[str, torch.Tensor], z: torch.Tensor) -> torch.Tensor:
+    """pre-quantisation embeddings (B, hidden, T) -> codes (B, num_codebooks, T) int64: the split RVQ of ``encode``."""
     def emb(k):
         return w[f"rvq.{k}.embedding_sum"] / w[f"rvq.{k}.cluster_usage"].clamp(min=1e-5)[:, None]
     first = F.conv1d(z, w["rvq_first.input_proj.weight"]).transpose(1, 2)
@@ -308,3 +317,12 @@ def encode(s: MimiShape, w: Dict[str, torch.Tensor], wav: torch.Tensor) -> torch
     codes = _rvq_encode(first, [emb(k) for k in range(s.num_semantic)])
     codes += _rvq_encode(rest, [emb(k) for k in range(s.num_semantic, s.num_codebooks)])
     return torch.stack(codes, dim=1)
+
+
+@torch.inference_mode()
+def encode(s: MimiShape, w: Dict[str, torch.Tensor], wav: torch.Tensor, context: Optional[int] = None,
+           rope_mod: Optional[int] = None) -> torch.Tensor:
+    """wav (B,1,n) fp32 @ 24 kHz -> codes (B, num_codebooks, ceil(n/1920)) int64.  Split RVQ: the
+    semantic codebook and the acoustic stack both quantise the SAME embeddings, each behind its own
+    1x1 input projection.  ``context`` / ``rope_mod``: fault injection, see ``transformer``."""
+    return quantize(s, w, encode_latent(s, w, wav, context=context, rope_mod=rope_mod))
