@@ -56,8 +56,10 @@ static __global__ __launch_bounds__(256) void k_embed_sum(const int* tokens /*[M
 //   t = bf16(logit / T); drop t < kth-largest (ties kept); log_softmax; softmax;
 //   argmax(p / Exp(1)) with the first index winning ties.  (Algorithm: see k_sample.)
 // The bf16 rounding points are those of torch-CPU's reduced-precision kernels (verified by
-// probe): the log-softmax keeps its exp-sum and its log in bf16 and subtracts
-// in two bf16 steps; softmax rounds once.  topk == 1 is the deterministic greedy rule
+// probe): the log-softmax keeps its exp-sum and its log in bf16 and rounds
+// (t - max) - log-sum ONCE (an intermediate bf16(t - max) is only exact for logits within a factor
+// of two of the maximum: with a large k or a high temperature it moved probabilities by up to
+// 100 ulp, docs/experiments/sampler_batch_parity.md); softmax rounds once.  topk == 1 is the deterministic greedy rule
 // (lowest index among maxima).  The kth-largest value is found exactly with a two-pass
 // radix select over the 16-bit order-preserving keys (256-bin LDS histograms).
 // Tail: writes the code into frame[b][cb] and the embedding row of the FED code
@@ -272,7 +274,7 @@ __device__ __forceinline__ int sample_body(const uint32_t (&w)[ITERS][4], int V,
                     const float sum = wave_sum(live ? expf(v - mx) : 0.f);
                     const float logsum = round_bf(logf(round_bf(sum)));
                     const float mx2 = round_bf(0.f - logsum);      // log-prob of the max element
-                    const float e3 = live ? expf(round_bf(round_bf(v - mx) - logsum) - mx2) : 0.f;
+                    const float e3 = live ? expf(round_bf((v - mx) - logsum) - mx2) : 0.f;
                     const float s2 = wave_sum(e3);
                     sync.mark(4);
                     sync();                                    // the Exp(1) draws of waves 1..3 are in cand_q
@@ -311,7 +313,7 @@ __device__ __forceinline__ int sample_body(const uint32_t (&w)[ITERS][4], int V,
                 float s2 = 0.f;
                 for (int c = lane; c < n; c += 64) {
                     const float v = sc.cand_t[c];
-                    if (order_key(v) >= kth) s2 += expf(round_bf(round_bf(v - mx) - logsum) - mx2);
+                    if (order_key(v) >= kth) s2 += expf(round_bf((v - mx) - logsum) - mx2);
                 }
                 s2 = wave_sum(s2);
                 sync();
@@ -319,7 +321,7 @@ __device__ __forceinline__ int sample_body(const uint32_t (&w)[ITERS][4], int V,
                     const float v = sc.cand_t[c];
                     if (order_key(v) < kth) continue;
                     const int idx = sc.cand_i[c];
-                    const float p = round_bf(expf(round_bf(round_bf(v - mx) - logsum) - mx2) / s2);
+                    const float p = round_bf(expf(round_bf((v - mx) - logsum) - mx2) / s2);
                     if (!(p > 0.f)) continue;
                     const float q = c < 256 ? sc.cand_q[c] : exp1_draw(idx, noise_row, seed, step, b, codebook);
                     const float r = round_bf(p / q);

@@ -513,16 +513,27 @@ def test_sampler_golden(abi):
         assert (frame[:, :7] == -1).all() and (frame[:, 8:] == -1).all()
 
 
-@pytest.mark.parametrize("V", [2051, 1000, 2056, 2100])
-def test_sampler_random_parameters_vs_oracle(abi, V):
-    """Random (temperature, top-k) pairs, logits on a coarse bf16 grid (many exact ties at the kth value): the HIP
-    sampler must pick the oracle's index given the oracle's Exp(1) noise.  Integer-exact except where one
-    probability sits within a bf16 ulp of the decision (fp32 order of <= k exp-sums), as in the golden cases.
-    V = 2051 / 2056 / 2100: a second 2,048-logit row with 3 / 8 / 52 live logits; V = 1000: one row."""
-    from oracle.csm_ref import sample_topk
-    g = torch.Generator().manual_seed(V)
-    B, ldl = 64, 2560
-    total, agree = 0, 0
+def _masked_rows(B, V, live, g):
+    """rows of which all but `live` logits (at random places) are -inf"""
+    logits = torch.full((B, V), float("-inf"))
+    for b in range(B):
+        at = torch.randperm(V, generator=g)[:live]
+        logits[b, at] = torch.randn(live, generator=g) * 2.0
+    return logits.to(torch.bfloat16)
+
+
+def _sampler_sweep_cases(V, g):
+    """(T, k, logits [64][V] bf16) of test_sampler_random_parameters_vs_oracle: 24 random pairs with T in [0.2, 1.6] and k in
+    [1, 119] or V -- then the parameter ranges those never reach:
+      * k in 120..256 and beyond (k <= 128 bisects thread-PAIR maxima, 129..256 the 256 thread maxima -- kth_largest_key<4> -- and k > 256
+        has no lower bound at all: every element is a candidate, those listed at 256 and later draw their noise inline), each with
+        T in {2.0, 2.5, 4.0, 0.1} (from T = 2 on, more than four neighbouring bf16 logits can round to one t: the candidate margin
+        2 ceil(T) + 2 is what keeps the kth-largest exact; T = 0.1 spreads t over the whole bf16 range).  k must not exceed V (torch.topk
+        of the oracle refuses it), so V = 1000 runs 999 in place of 2050;
+      * rows of which all but 3 / 40 / 300 logits are -inf, with k below and above the live count (above it the kth-largest IS -inf and
+        nothing is removed; the oracle's probabilities stay finite -- asserted -- because every row has a finite maximum);
+      * rows with one logit 40 above the rest (every other probability ~ e^-40: representable in bf16, and it can still win the race)."""
+    B = 64
     for case in range(24):
         T = float(torch.empty(1).uniform_(0.2, 1.6, generator=g))
         k = int(torch.randint(1, 120, (1,), generator=g)) if case else V           # case 0: top-k = V (nothing removed)
@@ -530,7 +541,41 @@ def test_sampler_random_parameters_vs_oracle(abi, V):
         logits = (torch.randn(B, V, generator=g) * scale).to(torch.bfloat16)
         if case % 4 == 1:
             logits = (logits.float() * 4).round().div(4).to(torch.bfloat16)            # quarter-steps: ties everywhere
+        yield T, k, logits
+    if V not in (2051, 1000):
+        return
+    n = 0
+    for T in (2.0, 2.5, 4.0, 0.1):
+        for k in (120, 128, 129, 200, 256, 257, 500, 2050 if V > 2050 else V - 1):
+            logits = (torch.randn(B, V, generator=g) * (0.5, 1.0, 3.0)[n % 3]).to(torch.bfloat16)
+            if n % 4 == 1:
+                logits = (logits.float() * 4).round().div(4).to(torch.bfloat16)
+            n += 1
+            yield T, k, logits
+    for live, ks in ((3, (2, 5, 200)), (40, (30, 50, 129)), (300, (200, 257, 400))):
+        for k, T in zip(ks, (0.8, 1.0, 2.5)):
+            yield T, k, _masked_rows(B, V, live, g)
+    for T, k in ((0.9, 50), (2.0, 200), (1.0, V)):
+        logits = torch.randn(B, V, generator=g)
+        logits[torch.arange(B), torch.randint(0, V, (B,), generator=g)] += 40.0
+        yield T, k, logits.to(torch.bfloat16)
+
+
+@pytest.mark.parametrize("V", [2051, 1000, 2056, 2100])
+def test_sampler_random_parameters_vs_oracle(abi, V):
+    """Random (temperature, top-k) pairs, logits on a coarse bf16 grid (many exact ties at the kth value): the HIP
+    sampler must pick the oracle's index given the oracle's Exp(1) noise.  Integer-exact except where one
+    probability sits within a bf16 ulp of the decision (fp32 order of <= k exp-sums), as in the golden cases.
+    V = 2051 / 2056 / 2100: a second 2,048-logit row with 3 / 8 / 52 live logits; V = 1000: one row.
+    V = 2051 and 1000 go on through the parameter ranges the random pairs never reach (_sampler_sweep_cases)."""
+    from oracle.csm_ref import sample_topk
+    from philox_ref import oracle_ratio
+    g = torch.Generator().manual_seed(V)
+    B, ldl = 64, 2560
+    total, agree = 0, 0
+    for case, (T, k, logits) in enumerate(_sampler_sweep_cases(V, g)):
         noise = torch.empty(B, V).exponential_(1, generator=g).to(torch.bfloat16).clamp_min(1e-30)
+        assert bool(torch.isfinite(oracle_ratio(logits, k, T, noise).float()).all()), f"case {case}: the oracle itself is not finite here"
         want = sample_topk(logits, k, T, q=noise)[:, 0]
         lg = torch.full((B, ldl), 99.0, dtype=torch.bfloat16); lg[:, :V] = logits
         lgd, nd = dev(lg), dev(noise)
@@ -574,3 +619,40 @@ def test_sampler_philox_distribution(abi):
     n = counts.sum()
     sigma = torch.sqrt(p * (1 - p) / n)
     assert ((freq - p).abs() <= 5 * sigma + 0.01).all(), f"freq {freq.tolist()} vs p {p.tolist()}"
+
+
+def test_sampler_philox_draws_equal_the_host_reference(abi):
+    """exp1_draw bit by bit: counter (index, sequence, codebook, step_lo), key (seed_lo, seed_hi ^ step_hi), u = (float32(x) + 0.5) * 2^-32,
+    q = bf16(-log u), against a numpy Philox4x32-10 written from the published algorithm (tests/philox_ref.py; validated against
+    Random123's known-answer vectors -- all-zero, all-ones and digits-of-pi counter / key -- in tests/test_philox_ref.py, not against
+    this kernel).  Rows of V = 2051 EQUAL logits with k = V, T = 1: every probability is the same, so the pick is the first index of
+    the largest bf16(p / q) -- a function of the draws alone, which the oracle's sample_topk predicts from the host's q.  k = V > 256
+    also means the candidates listed from 256 on draw inline on wave 0, the others on waves 1..3: both call sites are covered.
+    8 rows (the sequence word) x codebooks {0, 1, 17, 31} x counters {0, 1, 2^32 + 3} (the step's high word enters the key) x seeds
+    {4242, 0x123456789ABCDEF0} (the seed's high word too).  A pick may differ only where the host's own bf16(p / q) of the two indices
+    are within one ulp (host log vs device logf can differ in the last fp32 bit, i.e. one bf16 ulp of one q); at least 95 % identical,
+    and the reference alone has its two best within an ulp in ~1 % of these rows (test_philox_ref.py bounds it under 5 %)."""
+    from oracle.csm_ref import sample_topk
+    import philox_ref as P
+    V, B, ldl = P.DRAW_V, P.DRAW_ROWS, 2560
+    logits = torch.zeros(B, V, dtype=torch.bfloat16)
+    lg = torch.full((B, ldl), 99.0, dtype=torch.bfloat16); lg[:, :V] = logits
+    lgd = dev(lg)
+    total = agree = ties = 0
+    rows_r = []
+    for seed, counter, cb, noise in P.draw_grid():
+        want = sample_topk(logits, V, 1.0, q=noise)[:, 0]
+        rng = torch.tensor([seed, counter], dtype=torch.int64, device="cuda")
+        frame = torch.full((B, 32), -1, dtype=torch.int32, device="cuda")
+        _ck(abi, abi.lib.csm_op_sample(B, V, ldl, lgd.data_ptr(), 1.0, V, None, rng.data_ptr(), cb, 32, frame.data_ptr(), stream()))
+        torch.cuda.synchronize()
+        got = frame[:, cb].cpu()
+        assert int(got.min()) >= 0 and int(got.max()) < V
+        total += B; agree += int((got == want).sum())
+        ties += _assert_sampler_misses_are_one_ulp_ties(logits, 1.0, V, noise, got, want.cpu(), f"seed {seed:#x} counter {counter} codebook {cb}")
+        rows_r.append(P.oracle_ratio(logits, V, 1.0, noise))
+    share = P.top2_tie_share(torch.cat(rows_r))
+    print(f"philox draws vs host reference: {agree}/{total} picks identical, {ties} excused as <= 1-ulp ties of p/q; "
+          f"oracle-only top-2 tie share of these rows {100 * share:.2f} %")
+    assert share < 0.05, "the rows are too often ties of the reference itself to grade the draws"
+    assert agree / total >= 0.95, f"agreement {agree / total:.3f}"
