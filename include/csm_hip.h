@@ -102,6 +102,32 @@ int csm_reset(csm_handle h, void* stream);
  * (seed ^ salt, refill counter), so neither two refills nor a refill and a frame step ever share a noise stream.            */
 int csm_seed(csm_handle h, uint64_t seed, void* stream);
 
+/* Per-slot sampling table: temperature, top-k and Philox seed of ONE request inside a live batch.  The reference samples every frame with the
+ * caller's scalars (tts_service.py:175 uses 0.9/50, :266 0.8/40) and is batch-1, so two such requests never meet; here they share a batch.
+ * The handle keeps one entry per batch slot in device memory: {temperature, topk, seed, counter, own_rng}.  A slot WITH an entry is sampled
+ * with its own temperature and top-k by every sampler that serves its row (csm_depth, csm_frame_step, csm_generate_frame_s1 at any batch
+ * size, and the batch-1 depth pass of csm_prefill_slot, which reads the entry of `slot`); a slot without one uses the call's scalars.
+ * topk == 1 in an entry is the greedy rule for that row only.  With a seed of its own the row draws Philox at (its seed, its own frame
+ * counter, sequence 0, codebook) instead of (handle seed, global frame counter, slot, codebook): the counter is the utterance's frame index --
+ * 0 for the frame 0 that csm_depth, csm_prefill_slot or the step after csm_refill_* samples, + 1 per committed frame, held while the slot is
+ * parked, and rewound by csm_slot_sampling_set, csm_prefill (rows 0..B-1), csm_prefill_slot and csm_refill_begin -- so a request's codes
+ * depend neither on the slot it landed in nor on what the batch did before it arrived.
+ *   csm_slot_sampling_set:   slots is a host array of n slots; temperature / topk hold one value per listed slot (temperature > 0,
+ *                            topk >= 1, slot in [0, max_batch), else CSM_E_INVALID and nothing is written); seed holds one per listed slot,
+ *                            or is NULL = the slots keep drawing from the handle's stream (csm_seed).  Stream-ordered, no host
+ *                            synchronisation (the values travel as kernel arguments): in force for everything enqueued after it; legal
+ *                            between frame steps and for a slot whose refill is parked.  The first call makes the handle's later frame steps
+ *                            capture a graph that carries the table (ONE graph per (B, topk, temperature) whatever the entries hold); a
+ *                            handle that never calls it runs exactly the launches it ran before this interface existed.
+ *   csm_slot_sampling_clear: removes the listed slots' entries (slots == NULL: all of them).  Stream-ordered.  csm_reset clears the whole
+ *                            table, csm_reset_slots leaves it alone.
+ *   csm_slot_sampling_get:   one slot's entry (any out pointer may be NULL); synchronises the stream.  For tests and diagnostics.          */
+int csm_slot_sampling_set(csm_handle h, const int32_t* slots /*host*/, int n, const float* temperature, const int32_t* topk,
+                          const uint64_t* seed, void* stream);
+int csm_slot_sampling_clear(csm_handle h, const int32_t* slots /*host; NULL = all*/, int n, void* stream);
+int csm_slot_sampling_get(csm_handle h, int slot, int32_t* has_entry, float* temperature, int32_t* topk, int32_t* own_rng,
+                          uint64_t* seed, uint64_t* counter, void* stream);
+
 /* The backbone half of Model.generate_frame (models.py:153-160) on B sequences x S rows:
  * masked embedding sum -> 16 layers with KV append at pos -> final norm of each sequence's
  * last row (kept in the handle as last_h).  tokens [B][S][33] i32, mask [B][S][33] u8,
@@ -128,7 +154,7 @@ int csm_depth(csm_handle h, int B, float temperature, int topk, const int32_t* f
  * backbone step, csm_depth, position += 1, frame appended to the history, EOS flag
  * (all 32 codes == 0, generator.py:285) accumulated per sequence.  No host sync; the whole
  * step is captured once into a hipGraph and replayed.  Up to 4 captured steps are kept per handle, keyed on
- * (B, topk, temperature) and replaced least-recently-used first: callers that alternate sampling parameters or batch
+ * (B, topk, temperature, carries the per-slot sampling table) and replaced least-recently-used first: callers that alternate sampling parameters or batch
  * sizes (tts_service.py:175 uses 0.9/50, :266 0.8/40) replay, they do not capture again.
  * Batch 1 on the CSM-1B shapes: codebooks 1..31 and every backbone layer run as launches of 256 workgroups
  * that must all be resident at once (csrc/dec_first.cuh, csrc/dec_persist.cuh, csrc/bb_block.cuh).  Drive ONE frame loop per GPU (batch, or

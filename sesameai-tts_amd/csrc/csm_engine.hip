@@ -78,6 +78,12 @@ struct CsmModel {
     uint8_t* cur_mask;
     uint64_t* rng;                      // [0..1] {seed, frame-step counter}; [2..3] the refill domain {seed ^ REFILL_SALT, refill counter} (rng_slot)
     uint64_t* rng_slot;
+    // per-slot sampling table (csm_slot_sampling_set): one entry per batch slot, read by every sampler of the slot's row.  The
+    // launches get the pointer only once the handle has set an entry (slot_tab_used); until then they get nullptr and every captured
+    // frame step is node for node what it is without the table -- the rule of the inject node
+    SlotSampling* slot_tab;             // [max_batch]
+    bool slot_tab_used;
+    std::vector<unsigned char> slot_tab_host;   // [max_batch] host mirror for csm_describe: bit 0 = has an entry, bit 1 = own seed
     int* frame_save;                    // [ncb] slot 0's newest frame while a slot refill's depth pass uses scratch row 0
     // refill beside the frame loop (csm_refill_begin / csm_refill_advance): a prompt runs a few backbone layers per call between frame
     // steps; its residual stream and the next layer's normalised input live in buffers of their own, everything else is transient
@@ -131,9 +137,9 @@ struct CsmModel {
     hipStream_t pf_stream; hipEvent_t pf_fork[CSM_MAX_LAYERS], pf_join[CSM_MAX_LAYERS];
     bool have_last;                     // prefill or a frame step has produced h for csm_depth
     int last_S;                         // rows per sequence of the h buffer feeding csm_depth
-    // captured frame steps: a small LRU keyed on (batch, top-k, temperature) -- a service whose requests alternate sampling parameters or
+    // captured frame steps: a small LRU keyed on (batch, top-k, temperature, carries the per-slot sampling table) -- a service whose requests alternate sampling parameters or
     // batch sizes (the reference's callers use 0.7/30, 0.8/40 and 0.9/50: tts_service.py:175,266) replays, it does not re-capture
-    struct FrameGraph { hipGraphExec_t exec; hipGraph_t graph; int B, topk; float temp; uint64_t used; };
+    struct FrameGraph { hipGraphExec_t exec; hipGraph_t graph; int B, topk; float temp; bool tab; uint64_t used; };     // tab: carries the per-slot sampling table
     FrameGraph graphs[CSM_FRAME_GRAPHS];
     uint64_t graph_clock;
     int graph_captures;                 // hipGraphInstantiate calls since csm_create (csm_debug_graph_captures)
@@ -819,8 +825,9 @@ static bool persist_usable(const CsmModel* m, int B) {
     if (m->persist_disabled) return false;
     return B == 1 ? m->persist : (B >= 2 && B <= m->pm_max_rows && m->persist_m);
 }
+static inline const SlotSampling* slot_table(const CsmModel* m) { return m->slot_tab_used ? m->slot_tab : nullptr; }
 static hipError_t launch_dec_persist(CsmModel* m, int B, float temperature, int topk, const int* forced, void* logits_out, const void* noise, hipStream_t st,
-                                     const uint64_t* rng = nullptr) {
+                                     const uint64_t* rng = nullptr, int slot_row0 = 0) {
     if (rng == nullptr) rng = m->rng;
     const CsmConfig& c = m->cfg;
     const int V = c.audio_vocab, ncb = c.n_codebooks;
@@ -832,6 +839,7 @@ static hipError_t launch_dec_persist(CsmModel* m, int B, float temperature, int 
         p.proj_emb = m->proj_emb; p.qkv0_tab = m->qkv0_tab; p.hdec = m->hdec; p.qd = m->qd;
         p.kc = m->dec.kc; p.vc = m->dec.vc; p.kv_layer_stride = m->dec.layer_stride;
         p.temperature = temperature; p.topk = topk; p.noise = (const bf16_t*)noise; p.rng = rng; p.forced = forced;
+        p.slot_tab = slot_table(m); p.slot_row0 = slot_row0;
         p.V = V; p.ncb = ncb; p.frame = m->frame; p.logits_out = (bf16_t*)logits_out; p.cb_first = 2; p.cb_last = ncb - 1;
         p.gQ = m->pg_q; p.gH1 = m->pg_h1; p.gH2 = m->pg_h2; p.gL = m->pg_l; p.gP = m->pg_p;
         p.err = m->p_state + 1; p.epoch = m->p_state; p.eps = c.decoder.norm_eps; p.trickle_sleep = m->p_trickle; p.poll_sleep = m->p_poll;
@@ -847,6 +855,7 @@ static hipError_t launch_dec_persist(CsmModel* m, int B, float temperature, int 
     p.proj_emb = m->proj_emb; p.qkv0_tab = m->qkv0_tab; p.hdec = m->hdec; p.qd = m->qd;
     p.kc = m->dec.kc; p.vc = m->dec.vc; p.kv_layer_stride = m->dec.layer_stride;
     p.temperature = temperature; p.topk = topk; p.noise = (const bf16_t*)noise; p.rng = rng; p.forced = forced;
+    p.slot_tab = slot_table(m);
     p.V = V; p.ncb = ncb; p.M = B; p.frame = m->frame; p.logits_out = (bf16_t*)logits_out; p.cb_first = 2; p.cb_last = ncb - 1;
     p.xchg = m->pm_xchg; p.stamps = m->p_stamps; p.err = m->p_state + 1; p.eps = c.decoder.norm_eps; p.trickle_sleep = m->pm_trickle; p.poll_sleep = m->p_poll;
     // every exchange dword starts as the poison (dec_persist_m.cuh).  A KERNEL node, not a memset node (round 4): with hipMemsetAsync captured
@@ -877,15 +886,16 @@ static hipError_t launch_dec_first(CsmModel* m, hipStream_t st) {
 
 // c0 head + 31 depth-decoder steps (models.py:160-184); h rows = [B][S][d_bb], last row used
 // rng: the Philox words the samplers draw from -- the frame loop's {seed, step} unless a slot refill passes its own domain
+// slot_row0: the batch slot row 0 belongs to (the batch-1 pass of csm_prefill_slot reads that slot's entry of the sampling table)
 static hipError_t run_depth(CsmModel* m, int B, int S, float temperature, int topk, const int* forced,
-                            void* logits_out, const void* noise, hipStream_t st, const uint64_t* rng = nullptr) {
+                            void* logits_out, const void* noise, hipStream_t st, const uint64_t* rng = nullptr, int slot_row0 = 0) {
     if (rng == nullptr) rng = m->rng;
     const CsmConfig& c = m->cfg;
     const int dbb = c.backbone.dim, dd = c.decoder.dim, V = c.audio_vocab, ncb = c.n_codebooks;
     hipError_t e;
     for (int cb = 0; cb < ncb; ++cb) {
         GemvArgs a;
-        if (cb == 2 && persist_usable(m, B)) return launch_dec_persist(m, B, temperature, topk, forced, logits_out, noise, st, rng);
+        if (cb == 2 && persist_usable(m, B)) return launch_dec_persist(m, B, temperature, topk, forced, logits_out, noise, st, rng, slot_row0);
         // codebook 1 at batch 1: the four layers on both rows AND the head as ONE launch (dec_first.cuh): the K / V of positions 0, 1 and the logits
         // row are left where the chain's step leaves them
         const bool one_launch = cb == 1 && first_usable(m, B);
@@ -959,6 +969,7 @@ static hipError_t run_depth(CsmModel* m, int B, int S, float temperature, int to
         s.logits = m->logits; s.ldl = m->ldl; s.V = V; s.temperature = temperature; s.topk = topk;
         s.noise = noise ? (const bf16_t*)noise + (size_t)cb * B * V : nullptr;
         s.rng = rng; s.codebook = cb; s.forced = forced; s.ncb = ncb; s.frame = m->frame;
+        s.slot_tab = slot_table(m); s.slot_row0 = slot_row0;
         // next decoder input = projection(embedding of the fed code) = one row of the table
         s.audio_emb = m->proj_emb; s.audio_vocab = V; s.d = dd;
         if (cb == 0) { s.emb_out = m->hdec + dd; s.emb_stride = 2L * dd; }
@@ -994,14 +1005,19 @@ static hipError_t launch_advance(CsmModel* m, int B, const int* fed, int pos_inc
     a.max_seq = m->cfg.backbone.max_seq; a.overflow = m->n_frames + 1;
     a.err0 = m->p_state + 1; a.err1 = m->b_state + 1;
     a.fresh = (pos_inc && frame_injects(m, B)) ? m->fresh : nullptr;        // only a step that carried the inject node consumes the flags
+    a.slot_tab = m->slot_tab_used ? m->slot_tab : nullptr;
     hipLaunchKernelGGL(k_advance, dim3(1), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 // (a position outside [0, max_seq) would be clamped by the kernels: raise the device-side flag that csm_read_frames
 //  turns into CSM_E_TOO_LONG instead of letting the clamp pass silently)
-__global__ void k_set_prefill_state(const int* pos, int B, int S, int* cur_pos, int max_seq, int* overflow) {
-    for (int b = threadIdx.x; b < B; b += blockDim.x) cur_pos[b] = pos[(long)b * S + S - 1] + 1;
+// slot_tab (optional, offset like cur_pos): an utterance starts in these rows -- their own frame counters restart
+__global__ void k_set_prefill_state(const int* pos, int B, int S, int* cur_pos, int max_seq, int* overflow, SlotSampling* slot_tab) {
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        cur_pos[b] = pos[(long)b * S + S - 1] + 1;
+        if (slot_tab != nullptr) slot_tab[b].counter = 0;
+    }
     for (int i = threadIdx.x; i < B * S; i += blockDim.x)
         if (pos[i] < 0 || pos[i] >= max_seq) *overflow = 1;
 }
@@ -1413,6 +1429,9 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     ALLOC(m->rng, 32);
     m->rng_slot = m->rng + 2;
     ALLOC(m->frame_save, (size_t)ncb * 4);
+    ALLOC(m->slot_tab, (size_t)max_batch * sizeof(SlotSampling));
+    HIPCHK((CsmModel*)nullptr, hipMemset(m->slot_tab, 0, (size_t)max_batch * sizeof(SlotSampling)));
+    m->slot_tab_used = false; m->slot_tab_host.assign((size_t)max_batch, 0);
     ALLOC(m->fresh, (size_t)max_batch * 4);
     HIPCHK((CsmModel*)nullptr, hipMemset(m->fresh, 0, (size_t)max_batch * 4));
     m->rf_h = m->rf_xn = m->rf_last = nullptr; m->rf_slot = -1; m->rf_S = 0; m->rf_layer = 0; m->rf_pos = nullptr;
@@ -1516,7 +1535,7 @@ extern "C" void csm_destroy(csm_handle m) {
     for (CsmPrefix* p : m->prefixes) { (void)hipFree(p->data); p->data = nullptr; p->owner = nullptr; }      // (the caller still destroys the objects)
     void* ptrs[] = {m->bb.kc, m->bb.vc, m->dec.kc, m->dec.vc, m->h, m->q, m->att, m->act, m->part, m->attn_ctr, m->dec_in, m->proj_emb, m->slab,
                     m->hdec, m->qd, m->attd, m->actd, m->logits, m->frame, m->cur_tokens, m->cur_mask, m->cur_pos,
-                    m->history, m->n_frames, m->eos_at, m->rng, m->frame_save, m->fresh, m->rf_h, m->rf_xn, m->rf_last, m->dec_pos, m->slot_scratch, m->p_state, m->b_state, m->qkv0_tab};
+                    m->history, m->n_frames, m->eos_at, m->rng, m->slot_tab, m->frame_save, m->fresh, m->rf_h, m->rf_xn, m->rf_last, m->dec_pos, m->slot_scratch, m->p_state, m->b_state, m->qkv0_tab};
     for (void* p : ptrs) (void)hipFree(p);
     for (void* p : m->pk_allocs) (void)hipFree(p);
     if (m->xslab) (void)hipFree(m->xslab);
@@ -1579,6 +1598,10 @@ extern "C" int csm_reset(csm_handle m, void* stream) {
     HIPCHK(m, hipMemsetAsync(m->cur_pos, 0, (size_t)m->max_batch * 4, st));
     HIPCHK(m, hipMemsetAsync(m->eos_at, 0xff, (size_t)m->max_batch * 4, st));
     HIPCHK(m, hipMemsetAsync(m->fresh, 0, (size_t)m->max_batch * 4, st));
+    if (m->slot_tab_used) {                                   // the table empties with the rest of the state (the handle keeps carrying it)
+        HIPCHK(m, hipMemsetAsync(m->slot_tab, 0, (size_t)m->max_batch * sizeof(SlotSampling), st));
+        m->slot_tab_host.assign(m->slot_tab_host.size(), 0);
+    }
     m->host_frames = 0; m->have_last = false; m->rf_slot = -1; fresh_clear_all(m);
     return CSM_OK;
 }
@@ -1593,6 +1616,96 @@ extern "C" int csm_seed(csm_handle m, uint64_t seed, void* stream) {
     return CSM_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// per-slot sampling table.  Set and clear are stream-ordered and never synchronise: the values travel in the kernel
+// arguments, SLOT_SET_CHUNK slots per launch (max_batch <= 256 entries would not fit one argument block).
+// ---------------------------------------------------------------------------------------
+#define SLOT_SET_CHUNK 64
+struct SlotSetArgs {
+    uint64_t seed[SLOT_SET_CHUNK];
+    float temperature[SLOT_SET_CHUNK];
+    int topk[SLOT_SET_CHUNK];
+    unsigned short slot[SLOT_SET_CHUNK];
+    int n, own_rng;
+};
+__global__ void k_slot_sampling_set(SlotSampling* tab, const SlotSetArgs a) {
+    const int i = threadIdx.x;
+    if (i >= a.n) return;
+    SlotSampling e;
+    e.temperature = a.temperature[i]; e.topk = a.topk[i]; e.own_rng = a.own_rng; e.pad_ = 0;
+    e.seed = a.own_rng ? a.seed[i] : 0; e.counter = 0;
+    tab[a.slot[i]] = e;
+}
+__global__ void k_slot_sampling_clear(SlotSampling* tab, const SlotSetArgs a) {
+    const int i = threadIdx.x;
+    if (i >= a.n) return;
+    SlotSampling e;
+    memset(&e, 0, sizeof e);
+    tab[a.slot[i]] = e;
+}
+
+extern "C" int csm_slot_sampling_set(csm_handle m, const int32_t* slots, int n, const float* temperature, const int32_t* topk,
+                                     const uint64_t* seed, void* stream) {
+    if (!m || !slots || !temperature || !topk || n < 0 || n > m->max_batch) return fail(m, CSM_E_INVALID, "csm_slot_sampling_set: null argument or more slots than max_batch");
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_slot_sampling_set: slot outside [0, max_batch)");
+        if (!(temperature[i] > 0.f) || topk[i] < 1) return fail(m, CSM_E_INVALID, "csm_slot_sampling_set: temperature must be > 0 and topk >= 1");
+    }
+    if (n == 0) return CSM_OK;
+    hipStream_t st = (hipStream_t)stream;
+    for (int i0 = 0; i0 < n; i0 += SLOT_SET_CHUNK) {
+        SlotSetArgs a;
+        memset(&a, 0, sizeof a);
+        a.n = n - i0 < SLOT_SET_CHUNK ? n - i0 : SLOT_SET_CHUNK; a.own_rng = seed != nullptr;
+        for (int i = 0; i < a.n; ++i) {
+            a.slot[i] = (unsigned short)slots[i0 + i]; a.temperature[i] = temperature[i0 + i]; a.topk[i] = topk[i0 + i];
+            a.seed[i] = seed ? seed[i0 + i] : 0;
+        }
+        hipLaunchKernelGGL(k_slot_sampling_set, dim3(1), dim3(SLOT_SET_CHUNK), 0, st, m->slot_tab, a);
+        HIPCHK(m, hipGetLastError());
+    }
+    for (int i = 0; i < n; ++i) m->slot_tab_host[(size_t)slots[i]] = (unsigned char)(1 | (seed ? 2 : 0));
+    m->slot_tab_used = true;             // from now on the launches carry the table (captured steps without it stay in the cache under their own key)
+    return CSM_OK;
+}
+
+extern "C" int csm_slot_sampling_clear(csm_handle m, const int32_t* slots, int n, void* stream) {
+    if (!m || (slots && (n < 0 || n > m->max_batch))) return fail(m, CSM_E_INVALID, "csm_slot_sampling_clear: bad argument");
+    if (slots) for (int i = 0; i < n; ++i)
+        if (slots[i] < 0 || slots[i] >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_slot_sampling_clear: slot outside [0, max_batch)");
+    hipStream_t st = (hipStream_t)stream;
+    if (!slots) {
+        HIPCHK(m, hipMemsetAsync(m->slot_tab, 0, (size_t)m->max_batch * sizeof(SlotSampling), st));
+        m->slot_tab_host.assign(m->slot_tab_host.size(), 0);
+        return CSM_OK;
+    }
+    for (int i0 = 0; i0 < n; i0 += SLOT_SET_CHUNK) {
+        SlotSetArgs a;
+        memset(&a, 0, sizeof a);
+        a.n = n - i0 < SLOT_SET_CHUNK ? n - i0 : SLOT_SET_CHUNK;
+        for (int i = 0; i < a.n; ++i) a.slot[i] = (unsigned short)slots[i0 + i];
+        hipLaunchKernelGGL(k_slot_sampling_clear, dim3(1), dim3(SLOT_SET_CHUNK), 0, st, m->slot_tab, a);
+        HIPCHK(m, hipGetLastError());
+    }
+    for (int i = 0; i < n; ++i) m->slot_tab_host[(size_t)slots[i]] = 0;
+    return CSM_OK;
+}
+
+extern "C" int csm_slot_sampling_get(csm_handle m, int slot, int32_t* has_entry, float* temperature, int32_t* topk, int32_t* own_rng,
+                                     uint64_t* seed, uint64_t* counter, void* stream) {
+    if (!m || slot < 0 || slot >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_slot_sampling_get: slot outside [0, max_batch)");
+    SlotSampling e;
+    HIPCHK(m, hipMemcpyAsync(&e, m->slot_tab + slot, sizeof e, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(m, hipStreamSynchronize((hipStream_t)stream));
+    if (has_entry) *has_entry = e.topk != 0;
+    if (temperature) *temperature = e.temperature;
+    if (topk) *topk = e.topk;
+    if (own_rng) *own_rng = e.own_rng;
+    if (seed) *seed = e.seed;
+    if (counter) *counter = e.counter;
+    return CSM_OK;
+}
+
 extern "C" int csm_prefill(csm_handle m, const int32_t* tokens, const uint8_t* mask, const int32_t* pos, int B, int S,
                            int prompt_mode, void* stream) {
     if (!m || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_prefill: null argument");
@@ -1601,7 +1714,8 @@ extern "C" int csm_prefill(csm_handle m, const int32_t* tokens, const uint8_t* m
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(m, launch_embed(m, tokens, mask, B * S, st));
     HIPCHK(m, run_stack(m, m->bb, m->h, m->q, m->att, m->act, B * S, S, pos, -1, st, prompt_mode != 0));
-    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, B, S, m->cur_pos, m->cfg.backbone.max_seq, m->n_frames + 1);
+    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, B, S, m->cur_pos, m->cfg.backbone.max_seq, m->n_frames + 1,
+                       m->slot_tab_used ? m->slot_tab : nullptr);
     HIPCHK(m, hipGetLastError());
     m->have_last = true; m->last_S = S;
     return CSM_OK;
@@ -1672,7 +1786,7 @@ extern "C" int csm_frame_step(csm_handle m, int B, float temperature, int topk, 
         CsmModel::FrameGraph* g = nullptr;
         CsmModel::FrameGraph* victim = &m->graphs[0];
         for (auto& c : m->graphs) {
-            if (c.exec && c.B == B && c.topk == topk && c.temp == temperature) { g = &c; break; }
+            if (c.exec && c.B == B && c.topk == topk && c.temp == temperature && c.tab == m->slot_tab_used) { g = &c; break; }
             if (!c.exec ? victim->exec != nullptr : (victim->exec && c.used < victim->used)) victim = &c;     // an empty entry, else the least recently used
         }
         if (!g) {
@@ -1688,7 +1802,7 @@ extern "C" int csm_frame_step(csm_handle m, int B, float temperature, int topk, 
             HIPCHK(m, e2);
             HIPCHK(m, hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
             m->graph_captures += 1;
-            g->B = B; g->topk = topk; g->temp = temperature;
+            g->B = B; g->topk = topk; g->temp = temperature; g->tab = m->slot_tab_used;
         }
         g->used = ++m->graph_clock;
         HIPCHK(m, hipGraphLaunch(g->exec, st));
@@ -1764,7 +1878,8 @@ __global__ void k_reset_slots(const int* slots, int n, int max_batch, int* cur_p
 // history entry of the newest global frame, the caller's copy
 // ... and puts slot 0's own newest frame back into row 0 (csm_copy_frame keeps returning the batch's last frame), bumps the refill counter
 __global__ void k_stage_slot(int* frame, const int* frame_save, int ncb, int slot, int bstride, int* history, int* n_frames, int max_frames, int* eos_at,
-                             int* cur_tokens, uint8_t* cur_mask, int* out_frame, const uint32_t* e0, const uint32_t* e1, uint64_t* rng_slot) {
+                             int* cur_tokens, uint8_t* cur_mask, int* out_frame, const uint32_t* e0, const uint32_t* e1, uint64_t* rng_slot,
+                             SlotSampling* slot_entry) {
     __shared__ int nz;
     const bool bad = (e0 != nullptr && *e0 != 0u) || (e1 != nullptr && *e1 != 0u);
     const int n = *n_frames, g = n > 0 ? n - 1 : 0;
@@ -1785,6 +1900,7 @@ __global__ void k_stage_slot(int* frame, const int* frame_save, int ncb, int slo
         eos_at[slot] = nz == 0 ? g : -1;
         if (n == 0) *n_frames = 1;                    // the first slots of a batch that is being filled slot by slot open global frame 0
         rng_slot[1] += 1;                             // every refill draws from its own Philox stream
+        if (slot_entry != nullptr) slot_entry->counter = 1;      // frame 0 was sampled at the utterance's counter 0: the next frame step is its frame 1
     }
 }
 
@@ -1820,12 +1936,14 @@ extern "C" int csm_prefill_slot(csm_handle m, int slot, const int32_t* tokens, c
     if (e == hipSuccess) e = run_stack(m, m->bb, m->h, m->q, m->att, m->act, S, S, pos, -1, st, prompt_mode != 0);
     m->bb.slot_off = 0;
     HIPCHK(m, e);
-    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1);
+    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1,
+                       m->slot_tab_used ? m->slot_tab + slot : nullptr);
     HIPCHK(m, hipGetLastError());
     HIPCHK(m, hipMemcpyAsync(m->frame_save, m->frame, (size_t)m->cfg.n_codebooks * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(m, run_depth(m, 1, S, temperature, topk, nullptr, nullptr, nullptr, st, m->rng_slot));
+    HIPCHK(m, run_depth(m, 1, S, temperature, topk, nullptr, nullptr, nullptr, st, m->rng_slot, slot));
     hipLaunchKernelGGL(k_stage_slot, dim3(1), dim3(64), 0, st, m->frame, m->frame_save, m->cfg.n_codebooks, slot, m->max_batch, m->history, m->n_frames,
-                       m->max_frames, m->eos_at, m->cur_tokens, m->cur_mask, out_frame, m->p_state + 1, m->b_state + 1, m->rng_slot);
+                       m->max_frames, m->eos_at, m->cur_tokens, m->cur_mask, out_frame, m->p_state + 1, m->b_state + 1, m->rng_slot,
+                       m->slot_tab_used ? m->slot_tab + slot : nullptr);
     HIPCHK(m, hipGetLastError());
     if (m->host_frames == 0) m->host_frames = 1;
     m->have_last = true; m->last_S = 1;
@@ -1851,7 +1969,8 @@ extern "C" int csm_refill_begin(csm_handle m, int slot, const int32_t* tokens, c
     }
     HIPCHK(m, launch_embed(m, tokens, mask, S, st, m->rf_h));
     // parked: until the prompt is complete the slot's row of the frame steps is a placeholder at positions >= S (its K/V land beyond the prompt's)
-    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1);
+    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1,
+                       m->slot_tab_used ? m->slot_tab + slot : nullptr);
     // ... and the frame steps HOLD it there (flag 2 = parked: k_advance neither advances it nor tests it against max_seq), however many
     // steps the prompt's layers take
     hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(64), 0, st, m->fresh + slot, 2, 1);
@@ -1874,7 +1993,7 @@ extern "C" int csm_refill_advance(csm_handle m, int max_layers, void* stream) {
     m->rf_layer = l1;
     if (l1 < L) return 0;
     // complete: position = prompt length again (the placeholder rows drifted beyond it), flag up -- the next frame step samples frame 0
-    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, m->rf_pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1);
+    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, m->rf_pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1, (SlotSampling*)nullptr);
     hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(64), 0, st, m->fresh + slot, 1, 1);
     HIPCHK(m, hipGetLastError());
     m->rf_slot = -1; m->rf_pos = nullptr;
@@ -2099,6 +2218,8 @@ extern "C" int csm_describe(csm_handle m, char* buf, int n) {
     t += tmp;
     { size_t pb = 0; for (const CsmPrefix* p : m->prefixes) pb += p->bytes;
       snprintf(tmp, sizeof tmp, "; prefix_store=%d prefixes, %zu bytes", (int)m->prefixes.size(), pb); t += tmp; }
+    { int ne = 0, ns = 0; for (unsigned char f : m->slot_tab_host) { ne += f & 1; ns += (f >> 1) & 1; }
+      snprintf(tmp, sizeof tmp, "; slot_sampling=%d entries (%d with own seed)%s", ne, ns, m->slot_tab_used ? ", frame steps carry the table" : ""); t += tmp; }
     const std::string sw = set_switches(true);
     t += "; switches=" + (sw.empty() ? std::string("none") : sw);
     if (buf && n > 0) { strncpy(buf, t.c_str(), (size_t)n - 1); buf[n - 1] = 0; }

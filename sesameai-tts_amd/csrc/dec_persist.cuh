@@ -85,6 +85,8 @@ struct DecPersistArgs {
     float temperature; int topk;
     const bf16_t* noise;              // optional [ncb][1][V]
     const uint64_t* rng;
+    const SlotSampling* slot_tab;     // optional per-slot sampling table; this pass samples on behalf of slot slot_row0
+    int slot_row0;
     const int* forced;                // optional [ncb]
     int V, ncb;
     int* frame;                       // [ncb]
@@ -147,6 +149,8 @@ static_assert(DP_OFF_CANDI + DP_CAND_SLOTS * 4 <= DP_OFF_LOGITS, "sampler candid
 #define DP_M_RNG 112     // 4 words: Philox {seed, step} of this frame (read once at kernel start: a global load at sampling time would
                          // wait behind every weight load the wave has in flight)
 #define DP_M_SARG 116    // 4 words: V, temperature (bits), top-k, 1 if a noise tensor was given -- the sampler's scalars, staged once
+                         // (both groups resolved against the slot's entry of the per-slot sampling table, if the launch carries one: the
+                         // step loop reads these LDS words only)
 #define DP_M_TILE 48     // 4 tiles x 16 floats: the gate | up sums of a tile on their way to the SwiGLU lanes
 
 enum { DP_E_Q = 0, DP_E_H1 = 1, DP_E_P = 2, DP_E_H2 = 3, DP_E_L = 4 };
@@ -684,8 +688,11 @@ static __global__ __launch_bounds__(512) void k_dec_persist(const DecPersistArgs
         }
         for (int i = threadIdx.x; i < 128; i += 512) dp_stq((dp_lu4*)(lds + DP_OFF_QB) + i, reinterpret_cast<const uint4*>(a.qd)[i]);
         if (threadIdx.x < 2) misc[DP_M_H0 + threadIdx.x] = reinterpret_cast<const uint32_t*>(a.hdec)[2 * cu + threadIdx.x];
-        if (threadIdx.x >= 64 && threadIdx.x < 68) misc[DP_M_RNG + threadIdx.x - 64] = a.rng ? reinterpret_cast<const uint32_t*>(a.rng)[threadIdx.x - 64] : 0u;
-        if (threadIdx.x == 128) { misc[DP_M_SARG] = (uint32_t)a.V; misc[DP_M_SARG + 1] = __float_as_uint(a.temperature); misc[DP_M_SARG + 2] = (uint32_t)a.topk; misc[DP_M_SARG + 3] = a.noise != nullptr; }
+        // the slot's entry of the sampling table (dwords: temperature, top-k, own_rng, -, seed, counter) replaces the scalars / the {seed, step} words
+        const uint32_t* se = a.slot_tab != nullptr ? reinterpret_cast<const uint32_t*>(a.slot_tab + a.slot_row0) : nullptr;
+        const bool has = se != nullptr && se[1] != 0u, own = has && se[2] != 0u;
+        if (threadIdx.x >= 64 && threadIdx.x < 68) misc[DP_M_RNG + threadIdx.x - 64] = own ? se[4 + threadIdx.x - 64] : (a.rng ? reinterpret_cast<const uint32_t*>(a.rng)[threadIdx.x - 64] : 0u);
+        if (threadIdx.x == 128) { misc[DP_M_SARG] = (uint32_t)a.V; misc[DP_M_SARG + 1] = has ? se[0] : __float_as_uint(a.temperature); misc[DP_M_SARG + 2] = has ? se[1] : (uint32_t)a.topk; misc[DP_M_SARG + 3] = a.noise != nullptr; }
     }
     __syncthreads();
     const uint32_t base = dp_sload32(a.epoch);

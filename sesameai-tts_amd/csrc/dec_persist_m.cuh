@@ -84,6 +84,7 @@ static_assert(DM_LDS_BYTES <= 163840, "LDS image exceeds 160 KB");
 #define DM_M_SWTOT 18
 #define DM_M_RNG 24
 #define DM_M_SARG 28
+#define DM_M_SSEQ 32     // Philox sequence index of my row: the row number, or 0 for a row that draws from its own seed (per-slot sampling table)
 
 struct DecPersistMArgs {
     const bf16_t* wsm;                // [4 layers][2560 rows][1024] (as DecPersistArgs)
@@ -101,6 +102,7 @@ struct DecPersistMArgs {
     float temperature; int topk;
     const bf16_t* noise;              // optional [ncb][M][V]
     const uint64_t* rng;
+    const SlotSampling* slot_tab;     // optional per-slot sampling table [max_batch]: row b is sampled by entry b
     const int* forced;                // optional [M][ncb]
     int V, ncb, M;
     int* frame;                       // [M][ncb]
@@ -710,7 +712,7 @@ __device__ __forceinline__ void dm_gather_wave(const DecPersistMArgs& a, char* l
             const int sV = (int)misc[DM_M_SARG], sK = (int)misc[DM_M_SARG + 2];
             const float sT = __uint_as_float(misc[DM_M_SARG + 1]);
             const bool sN = misc[DM_M_SARG + 3] != 0u;
-            const int tok = sample_body<2>(wv, sV, sT, sK, sN ? a.noise + ((long)cb * a.M + ob) * sV : nullptr, seed, step, ob, cb, sc, tid, sync);
+            const int tok = sample_body<2>(wv, sV, sT, sK, sN ? a.noise + ((long)cb * a.M + ob) * sV : nullptr, seed, step, (int)misc[DM_M_SSEQ], cb, sc, tid, sync);
             if (*ab) return;
             if (gw == 0) DM_STAMP(34);
             int fed = a.forced ? a.forced[(long)ob * a.ncb + cb] : tok;
@@ -786,9 +788,14 @@ __global__ __launch_bounds__(512) void k_dec_persist_m(const DecPersistMArgs a) 
             const int row = 2 * (3 * cu + u), e = (row < 1024 ? row : row - 1024) % DP_HD;
             ((dp_lu32*)(lds + DM_L_ROPE))[i] = reinterpret_cast<const uint32_t*>(a.rope)[pos * (DP_HD / 2) + e / 2];
         }
-        if (threadIdx.x >= 256 && threadIdx.x < 260) misc[DM_M_RNG + threadIdx.x - 256] = a.rng ? reinterpret_cast<const uint32_t*>(a.rng)[threadIdx.x - 256] : 0u;
+        // my row's entry of the sampling table (dwords: temperature, top-k, own_rng, -, seed, counter) replaces the scalars / the {seed, step}
+        // words; all eight owners of a row stage the same words, so they still sample alike
+        const uint32_t* se = a.slot_tab != nullptr && ob < a.M ? reinterpret_cast<const uint32_t*>(a.slot_tab + ob) : nullptr;
+        const bool has = se != nullptr && se[1] != 0u, own = has && se[2] != 0u;
+        if (threadIdx.x >= 256 && threadIdx.x < 260) misc[DM_M_RNG + threadIdx.x - 256] = own ? se[4 + threadIdx.x - 256] : (a.rng ? reinterpret_cast<const uint32_t*>(a.rng)[threadIdx.x - 256] : 0u);
         if (threadIdx.x == 320) {
-            misc[DM_M_SARG] = (uint32_t)a.V; misc[DM_M_SARG + 1] = __float_as_uint(a.temperature); misc[DM_M_SARG + 2] = (uint32_t)a.topk; misc[DM_M_SARG + 3] = a.noise != nullptr;
+            misc[DM_M_SARG] = (uint32_t)a.V; misc[DM_M_SARG + 1] = has ? se[0] : __float_as_uint(a.temperature); misc[DM_M_SARG + 2] = has ? se[1] : (uint32_t)a.topk; misc[DM_M_SARG + 3] = a.noise != nullptr;
+            misc[DM_M_SSEQ] = own ? 0u : (uint32_t)ob;
             misc[DM_M_FT] = 1u; misc[DM_M_FT + 1] = 1u;
         }
         for (int i = threadIdx.x; i < 9 * 128; i += 512) {

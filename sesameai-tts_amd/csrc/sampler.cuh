@@ -68,6 +68,20 @@ static __global__ __launch_bounds__(256) void k_embed_sum(const int* tokens /*[M
 // ---------------------------------------------------------------------------------------
 #define SAMPLE_MAX_ITERS 8   // supports V <= 8*512
 
+// One entry of the per-slot sampling table (csm_slot_sampling_set), 32 bytes.  topk == 0: no entry -- the slot is
+// sampled with the launch's scalars and the handle's stream.  own_rng: the slot draws Philox at key `seed` and counter (vocabulary
+// index, 0, codebook, `counter`), `counter` being the utterance's own frame index (k_advance).  {seed, counter} sit where a launch's
+// {seed, step} words sit, so a persistent kernel stages either pair with the same four dword loads.
+struct SlotSampling {
+    float temperature;
+    int topk;
+    int own_rng;
+    int pad_;
+    uint64_t seed;
+    uint64_t counter;
+};
+static_assert(sizeof(SlotSampling) == 32, "SlotSampling is addressed as 8 dwords");
+
 struct SampleArgs {
     const bf16_t* logits;     // [B][ldl]
     int ldl, V;
@@ -92,6 +106,9 @@ struct SampleArgs {
     const bf16_t* qkv0;       // [audio_vocab][nq + 2 nkv]
     int nq, nkv, kv_heads, smax, hd, next_pos;
     bf16_t *q_out, *k0, *v0;
+    // optional per-slot sampling table: row b reads entry slot_row0 + b (slot_row0 = the slot a batch-1 pass runs on behalf of)
+    const SlotSampling* slot_tab;
+    int slot_row0;
 };
 
 __device__ __forceinline__ uint32_t order_key(float t) {     // monotone map of a bf16-valued float
@@ -377,7 +394,17 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const bf16_t* lg = a.logits + (long)b * a.ldl;
     // issued now, consumed by wave 0 three barriers later (a dependent load there would sit on the critical path)
-    const uint64_t seed = a.rng ? a.rng[0] : 0, step = a.rng ? a.rng[1] : 0;
+    uint64_t seed = a.rng ? a.rng[0] : 0, step = a.rng ? a.rng[1] : 0;
+    // ... and so is the row's entry of the per-slot table, if the launch carries one (block-uniform: one block samples one row)
+    float temperature = a.temperature;
+    int topk = a.topk, seq = b;
+    if (a.slot_tab != nullptr) {
+        const SlotSampling e = a.slot_tab[a.slot_row0 + b];
+        if (e.topk != 0) {
+            temperature = e.temperature; topk = e.topk;
+            if (e.own_rng) { seed = e.seed; step = e.counter; seq = 0; }
+        }
+    }
     uint32_t w[ITERS][4];
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
@@ -388,7 +415,7 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
     SampleScratch sc;
     sc.cand_t = (lds_f32_t*)cand_t; sc.cand_i = (lds_i32_t*)cand_i; sc.s_max = (lds_u32_t*)s_max; sc.cand_q = (lds_f32_t*)s_max; sc.s_bv = (lds_f32_t*)s_bv;
     sc.s_bi = (lds_i32_t*)s_bi; sc.s_n = (lds_i32_t*)&s_n; sc.s_tok = (lds_i32_t*)&s_tok; sc.s_wtot = (lds_i32_t*)s_wtot;
-    const int tok = sample_body<ITERS>(w, a.V, a.temperature, a.topk, a.noise ? a.noise + (long)b * a.V : nullptr, seed, step, b,
+    const int tok = sample_body<ITERS>(w, a.V, temperature, topk, a.noise ? a.noise + (long)b * a.V : nullptr, seed, step, seq,
                                        a.codebook, sc, tid, SyncThreads());
     if (tid == 0) a.frame[(long)b * a.ncb + a.codebook] = tok;
     if (a.emb_out) {
@@ -436,6 +463,7 @@ struct AdvanceArgs {
     int max_seq;          // backbone positions are [0, max_seq)
     int* overflow;        // device flag: a step ran at a position >= max_seq (csm_read_frames -> CSM_E_TOO_LONG)
     const uint32_t *err0, *err1;   // optional give-up words of the all-CU launches: non-zero -> this frame's codes are invalid, recorded as -1
+    SlotSampling* slot_tab;   // optional [B]: a committed frame moves the row's own frame counter on (a parked row's is held, like its position)
     int* fresh;           // optional [B]: 1 = this frame is FRAME 0 of an utterance whose prompt was prefilled beside the frame loop
                           // (csm_refill_*): its backbone row of this step was a placeholder, so the position stays, the EOS word restarts;
                           // 2 = parked (the prompt is still running): position held, never tested against max_seq
@@ -468,6 +496,7 @@ static __global__ __launch_bounds__(256) void k_advance(const AdvanceArgs a) {
             if (a.pos_inc && a.cur_pos[b] >= a.max_seq) *a.overflow = 1;  // the step that just ran used this position
             a.cur_pos[b] += a.pos_inc;
         }
+        if (a.slot_tab != nullptr && flag != 2) a.slot_tab[b].counter += 1;
     }
     if (threadIdx.x == 0) { *a.n_frames = n + 1; a.rng[1] += 1; }
 }

@@ -29,10 +29,16 @@ class LiveBatch:
     refilled while the others keep generating.  How a free slot gets its next prompt is the subclass's business -- ``_feed(everything)``: called
     after every queued frame step, and with ``everything`` when nobody generates (True: it did something); ``_vacated``, ``_idle``,
     ``_report_order`` -- the rest happens here, once.  The Philox key of a sampled frame includes the global frame index, so the number of
-    frame steps between any two refill calls is part of the results (tests/test_live_batch_trace.py pins them)."""
+    frame steps between any two refill calls is part of the results (tests/test_live_batch_trace.py pins them) -- except for a prompt with a
+    seed of its own (``own``), which draws at (its seed, its own frame index) wherever and whenever it runs.
+    ``own[i]``: ``(temperature, topk, seed or None)`` of prompt ``i`` where it has values of its own, else None: the model's per-slot sampling
+    table gets them (``Model.set_slot_sampling``) immediately before the prompt's refill call, and a slot such a prompt leaves is cleared
+    before a prompt without own values takes it.  With no own values anywhere the model sees neither call."""
 
-    def __init__(self, model, prompts, limits: List[int], temperature: float, topk: int, poll: int, slots: int, store: list):
+    def __init__(self, model, prompts, limits: List[int], temperature: float, topk: int, poll: int, slots: int, store: list, own=None):
         self.m, self.prompts, self.limits, self.sampling, self.poll, self.B = model, prompts, limits, (temperature, topk), poll, slots
+        self.own = own if own is not None else [None] * len(prompts)
+        self.entries: set = set()                                   # slots that hold an entry of the sampling table (reset_caches empties it)
         # per prompt (rows P to copy, handle): the registered prefix with the longest match, (0, None) without one -- all matched before the loop
         # starts: no comparison's host synchronisation falls between frame steps; and {slot: handle} of the initial fill's shared copies
         self.plan = [match_stored_prefix(store, t, mk) for t, mk in prompts] if store else [(0, None)] * len(prompts)
@@ -103,10 +109,16 @@ class LiveBatch:
         """(tokens, mask, keywords) for the refill of ``slot`` with prompt ``i``.  A registered prefix's K/V are copied into the slot HERE (unless the
         initial fill's shared copy put them there) and only the rows after it run: the caller begins at once, no frame step between the two."""
         (t, mk), (P, handle) = self.prompts[i], self.plan[i]
+        if handle is not None and self.seeded.pop(slot, None) is not handle:
+            self.m.apply_prefix(handle, [slot])
+        if self.own[i] is not None:                                 # after the prefix copy, immediately before the refill call
+            self.m.set_slot_sampling([slot], *self.own[i])
+            self.entries.add(slot)
+        elif slot in self.entries:
+            self.m.clear_slot_sampling([slot])
+            self.entries.discard(slot)
         if handle is None:
             return t, mk, {}
-        if self.seeded.pop(slot, None) is not handle:
-            self.m.apply_prefix(handle, [slot])
         return t[P:], mk[P:], {"start": P}
 
     def _report_order(self, cuts: List[Tuple[int, bool]]) -> List[Tuple[int, bool]]:
@@ -178,9 +190,42 @@ class _BesideTheLoop(LiveBatch):
         return list(self.free)                                      # they step as placeholders until a prompt takes them: rewound after every block
 
 
-def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_batch, store, beside_the_loop, refill_row_layers, max_seq_len):
+def _per_prompt(value, n: int, name: str):
+    """(one value per prompt, whether ``value`` came as a sequence)."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{name}: one value, or one per prompt")
+        return list(value), True
+    return [value] * n, False
+
+
+def per_prompt_sampling(n: int, temperature, topk, seed):
+    """``temperature`` / ``topk``: one value or one per prompt; ``seed``: None or one optional int per prompt.  Returns the scalars every frame
+    step gets (the first prompt's where sequences were given) and, per prompt, ``(temperature, topk, seed)`` where the prompt has values of
+    its own -- with sequences every prompt has, else only one with a seed -- or None."""
+    temps, t_seq = _per_prompt(temperature, n, "temperature")
+    ks, k_seq = _per_prompt(topk, n, "topk")
+    seeds = [None] * n if seed is None else list(seed)
+    if len(seeds) != n:
+        raise ValueError("seed: None, or one optional int per prompt")
+    temps, ks = [float(t) for t in temps], [int(k) for k in ks]
+    if any(not t > 0 for t in temps) or any(k < 1 for k in ks):
+        raise ValueError("temperature must be > 0 and topk >= 1")
+    seeds = [None if s is None else int(s) for s in seeds]
+    if not n:
+        return (temperature, topk), []
+    scalars = (temps[0] if t_seq else temperature, ks[0] if k_seq else topk)
+    every = t_seq or k_seq
+    own = [(temps[i], ks[i], seeds[i]) if every or seeds[i] is not None else None for i in range(n)]
+    return scalars, own
+
+
+def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_batch, store, beside_the_loop, refill_row_layers, max_seq_len,
+               seed=None):
     """``LiveBatch.run`` over ``prompts`` [(tokens (S_i,33), mask (S_i,33)), ...] with one length limit for all or one per prompt (a
-    request's own max_audio_length_ms), refilling beside the loop where the model's frame steps of this batch size honour it."""
+    request's own max_audio_length_ms), refilling beside the loop where the model's frame steps of this batch size honour it.
+    ``temperature`` / ``topk``: one value, or one per prompt; ``seed``: one optional int per prompt (``per_prompt_sampling``)."""
+    (temperature, topk), own = per_prompt_sampling(len(prompts), temperature, topk, seed)
     limits = [int(max_generation_len)] * len(prompts) if isinstance(max_generation_len, (int, float)) else [int(x) for x in max_generation_len]
     if len(limits) != len(prompts):
         raise ValueError("max_generation_len: one value, or one per prompt")
@@ -190,7 +235,7 @@ def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_
     if not prompts:
         return
     B = min(max_batch, len(prompts))
-    args = (model, prompts, limits, temperature, topk, poll, B, store)
+    args = (model, prompts, limits, temperature, topk, poll, B, store, own if any(o is not None for o in own) else None)
     supported = getattr(model, "supports_refill_beside_the_loop", None)         # (a scripted model may lack it)
     beside = supported is not None and supported(B) and beside_the_loop
     yield from (_BesideTheLoop(*args, budget=refill_row_layers) if beside else _Stalling(*args)).run()

@@ -693,6 +693,52 @@ class Model:
         with self._on_device():
             check(lib.csm_reset_slots(self._h, arr, len(slots), _stream_ptr()), self._h)
 
+    def set_slot_sampling(self, slots, temperature, topk, seed=None) -> None:
+        """Temperature, top-k and (optionally) a Philox seed of their own for the listed batch slots (csm_slot_sampling_set): every
+        sampler that serves such a slot's row uses them instead of the call's scalars.  ``temperature`` / ``topk`` / ``seed``: one value
+        for all listed slots, or one per slot; ``seed=None`` keeps the slots on the model's stream (``seed``).  With a seed of its own a
+        slot draws at (its seed, the utterance's own frame index), so its codes do not depend on the slot or on the batch's schedule.
+        Stream-ordered, no synchronisation; call it immediately before the ``refill_slot`` / ``refill_begin`` / ``prefill`` of the request."""
+        self._require()
+        slots = [int(s) for s in slots]
+        n = len(slots)
+
+        def per_slot(v, name):
+            vals = list(v) if isinstance(v, (list, tuple)) else [v] * n
+            if len(vals) != n:
+                raise ValueError(f"{name}: {len(vals)} values for {n} slots")
+            return vals
+        temps = [float(t) for t in per_slot(temperature, "temperature")]
+        ks = [int(k) for k in per_slot(topk, "topk")]
+        seeds = None if seed is None else [int(s) for s in per_slot(seed, "seed")]
+        if any(not t > 0 for t in temps) or any(k < 1 for k in ks):
+            raise ValueError("set_slot_sampling: temperature must be > 0 and topk >= 1")
+        with self._on_device():
+            check(lib.csm_slot_sampling_set(self._h, (C.c_int32 * n)(*slots), n, (C.c_float * n)(*temps), (C.c_int32 * n)(*ks),
+                                            None if seeds is None else (C.c_uint64 * n)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds]),
+                                            _stream_ptr()), self._h)
+
+    def clear_slot_sampling(self, slots=None) -> None:
+        """Removes the listed slots' entries of the sampling table (``None``: all): they are sampled with the call's scalars again."""
+        self._require()
+        with self._on_device():
+            if slots is None:
+                check(lib.csm_slot_sampling_clear(self._h, None, 0, _stream_ptr()), self._h)
+            else:
+                arr = (C.c_int32 * len(slots))(*[int(s) for s in slots])
+                check(lib.csm_slot_sampling_clear(self._h, arr, len(slots), _stream_ptr()), self._h)
+
+    def slot_sampling(self, slot: int) -> dict:
+        """One slot's entry of the sampling table (csm_slot_sampling_get; synchronises): has_entry, temperature, topk, own_rng, seed, counter."""
+        self._require()
+        has, k, own = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        t, sd, ctr = C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+        with self._on_device():
+            check(lib.csm_slot_sampling_get(self._h, int(slot), C.byref(has), C.byref(t), C.byref(k), C.byref(own), C.byref(sd), C.byref(ctr),
+                                            _stream_ptr()), self._h)
+        return {"has_entry": bool(has.value), "temperature": float(t.value), "topk": int(k.value), "own_rng": bool(own.value),
+                "seed": int(sd.value), "counter": int(ctr.value)}
+
     def refill_slot(self, slot: int, tokens: torch.Tensor, tokens_mask: torch.Tensor, temperature: float, topk: int, start: int = 0) -> torch.Tensor:
         """A new prompt (S,33) starting at position 0 into batch slot ``slot`` of a live batch: backbone prefill into the slot's
         caches, depth pass, the new utterance's frame 0 staged as the slot's next input.  Returns frame 0 (32,) int32 on the
