@@ -215,6 +215,26 @@ int csm_refill_supported(csm_handle h, int B);
 int csm_refill_begin(csm_handle h, int slot, const int32_t* tokens, const uint8_t* mask, const int32_t* pos, int S, void* stream);
 int csm_refill_advance(csm_handle h, int max_layers, void* stream);
 
+/* The same for SEVERAL slots at once -- one ragged prefill.  Slots that retire in the same block would otherwise queue behind each other,
+ * each taking the backbone's whole launch chain for a handful of rows (after a prefix copy a refill is ~40 rows: launch-bound).
+ *   csm_refill_group_begin:   n <= 32 segments; segment i is the prompt rows of batch slot slots[i], rows[i] >= 1 of them, and the rows of all
+ *                       segments lie back to back in tokens [M][33] / mask [M][33] / pos [M] (dev; M = sum rows[i] <= max_rows; pos gives every
+ *                       row its true position -- a segment that follows a copied prefix starts at the prefix length -- and must stay valid
+ *                       until the group completes).  `slots` and `rows` are host arrays, read before the call returns; the segment table
+ *                       travels in the kernel arguments, so the call neither copies to the device nor synchronises.  What csm_refill_begin
+ *                       does for one slot happens for every listed slot: embedded, parked at its own pos[last row] + 1, sampling-table
+ *                       counter rewound.  CSM_E_INVALID (nothing is enqueued) for n outside [1, 32], a slot outside [0, max_batch) or listed
+ *                       twice, rows[i] < 1, M > max_rows.  One refill OR one group is in flight per handle: CSM_E_STATE while either is
+ *                       pending (csm_refill_begin likewise refuses while a group is).  Needs csm_refill_supported(h, max_batch).
+ *   csm_refill_group_advance: up to max_layers more backbone layers over all M rows.  1 when the group is complete -- the NEXT csm_frame_step
+ *                       yields frame 0 of all n utterances --, 0 while layers remain, < 0 on error.
+ * csm_reset_slots / csm_prefill_slot / csm_prefix_capture / csm_prefix_apply on a slot of a pending group are refused like for the slot of a
+ * pending csm_refill_begin.  Every row's K/V and every slot's frame 0 input are the bits the same segments give one after the other through
+ * csm_refill_begin / csm_refill_advance (a group of n = 1 included).                                                            */
+int csm_refill_group_begin(csm_handle h, const int32_t* slots /*host*/, const int32_t* rows /*host*/, int n,
+                           const int32_t* tokens /*dev [M][33]*/, const uint8_t* mask /*dev [M][33]*/, const int32_t* pos /*dev [M]*/, void* stream);
+int csm_refill_group_advance(csm_handle h, int max_layers, void* stream);
+
 /* Prefix store: shared voice-prompt K/V for the live batch.  A request is a 900-1,550-row voice prompt followed by a few dozen rows of new
  * text, and the reference re-runs the whole prompt for every sentence (tts_service.py:191-207).  In prompt mode a row's K/V do not depend on
  * how many rows share the call, so the backbone K/V rows of a prompt prefix are the same bits in every slot and for every request that starts

@@ -21,10 +21,16 @@ struct AttnArgs {
     int M, rows_per_seq, H, KV, smax, nsplit;
     float scale;
     bf16_t* out;            // [M][H*HD]                 (nsplit == 1)
+    union {
     float* part;            // [M][H][nsplit][ATTN_PS(HD)] (nsplit > 1): o[HD], m, l, padding to whole 128-byte lines
+    const int4* rag_tiles;  // RAG instantiation of k_attn_flash (nsplit == 1): its query tiles {slot, first row, rows, -} in launch order (k_rag_plan)
+    };
     int out_packed;         // out in matrix-core operand order (common.cuh xp_off), K = H*HD
+    union {
     int* ctr;               // nsplit > 1: [M][KV] arrival counters (zero between launches) -> the LAST key-range block of a
                             // (row, KV head) merges the partials itself (no k_attn_combine launch); nullptr: partials only
+    const int* row_slot;    // RAG instantiation of k_attn (nsplit == 1): [M] batch slot of each row (k_rag_plan)
+    };                      // (the RAG members share the words of members their launches never use: the argument block keeps its layout)
 };
 
 #define ATTN_MAX_SPLIT 8            // key ranges per (row, KV head) the in-kernel merge handles (csm_engine.hip BB_NSPLIT_MAX)
@@ -36,7 +42,9 @@ __device__ __forceinline__ void attn_st16_sc1(float* p, const float4& v) {
 __device__ __forceinline__ void attn_st4_sc1(float* p, float v) { asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
 
 // U = key rows per lane in flight per batch (hd 128 / depth decoder: 8, so its <= 32 keys are ONE round trip)
-template <int HD, int U = 4>
+// RAG (csm_refill_group_advance): the rows are prompt rows of DIFFERENT batch slots -- row m reads the K/V of slot a.row_slot[m]; nsplit == 1.
+// An instantiation of its own, like SEG of Mimi's k_gemm32: the code of the plain one is what it was.
+template <int HD, int U = 4, bool RAG = false>
 __global__ __launch_bounds__(256) void k_attn(const AttnArgs a) {
     constexpr int LPK = HD / 8;          // lanes per key
     constexpr int KPI = 64 / LPK;        // keys per wave-iteration
@@ -45,7 +53,7 @@ __global__ __launch_bounds__(256) void k_attn(const AttnArgs a) {
     const int G = a.H / a.KV;
     const int slot = lane / LPK, e = lane % LPK;
     const int p = min(max(a.pos[m], 0), a.smax - 1);
-    const int b = m / a.rows_per_seq;
+    const int b = RAG ? a.row_slot[m] : m / a.rows_per_seq;
     const int nkeys = p + 1;
     const int chunk = (nkeys + a.nsplit - 1) / a.nsplit;
     const int j0 = sp * chunk, j1 = min(nkeys, j0 + chunk);
@@ -124,7 +132,7 @@ __global__ __launch_bounds__(256) void k_attn(const AttnArgs a) {
             }
         }
     }
-    if (a.nsplit > 1 && a.ctr != nullptr) {
+    if (!RAG && a.nsplit > 1 && a.ctr != nullptr) {
         // The last of the nsplit blocks of this (row, KV head) to get here merges: k_attn_combine's arithmetic in k_attn_combine's
         // order (same bits), one launch less per layer.  No block waits for another (the merge is done by whoever comes last), so
         // nothing depends on the blocks being resident together.  The partials travel like the persistent launches' exchanges:

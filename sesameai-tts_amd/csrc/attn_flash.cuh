@@ -44,7 +44,13 @@ typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 #endif
 #define AF_GRP_BYTES (2 * 64 * AF_KLD * 2 + 2 * 64 * AF_VLD * 2)      // one group's K + V double buffers: 40 KB
 
-template <int HD, int NG>
+// RAG (csm_refill_group_advance): the rows of the call are the segments of a group (common.cuh RagSegs) -- prompt rows of different batch slots,
+// each segment with its own length and start position.  A segment's query tiles start at ITS row 0: tile k of segment i is rows
+// [row0_i + 32 k, + min(32, rows_i - 32 k)) over the K/V of slot_i, which is exactly the tile composition of a single-slot call of rows_i
+// rows -- pmax, the padding rows and the key walk are per tile, so every row keeps the bits it has there.  grid = (tiles, KV heads);
+// a.rag_tiles[x] = {slot, first row, rows} of the x-th tile, longest key walk first (k_rag_plan).  An instantiation of its own, like SEG of
+// Mimi's k_gemm32: the code of the plain one is what it was.
+template <int HD, int NG, bool RAG = false>
 __global__ __launch_bounds__(256 * NG) void k_attn_flash(const AttnArgs a) {
     static_assert(HD == 64, "k_attn_flash: head_dim 64");
     // (round 4: a buffer holds TWO 32-key tiles -- one global round trip, one LDS write and one barrier per 64 keys; the tiles are
@@ -61,9 +67,14 @@ __global__ __launch_bounds__(256 * NG) void k_attn_flash(const AttnArgs a) {
     const int groups = (a.rows_per_seq + 31) / 32;
     const int lin = blockIdx.x + gridDim.x * blockIdx.y;
     const int kvh = lin % a.KV, xi = lin / a.KV;
-    const int b = xi / groups, r0 = (groups - 1 - xi % groups) * 32;
-    const int nr = min(32, a.rows_per_seq - r0);                       // valid query rows of this tile
-    const int m_base = b * a.rows_per_seq + r0;
+    int b = xi / groups, r0 = (groups - 1 - xi % groups) * 32;
+    int nr = min(32, a.rows_per_seq - r0);                             // valid query rows of this tile
+    int m_base = b * a.rows_per_seq + r0;
+    if (RAG) {
+        const int4 t = a.rag_tiles[xi];
+        b = __builtin_amdgcn_readfirstlane(t.x); m_base = __builtin_amdgcn_readfirstlane(t.y); nr = __builtin_amdgcn_readfirstlane(t.z);
+        if (nr < 1 || nr > 32 || m_base < 0 || m_base + nr > a.M) return;      // (never: k_rag_plan wrote every tile of the launch)
+    }
     const int mq = m_base + min(r, nr - 1);                            // this lane's query row (padding repeats the last)
     const int pq = min(max(a.pos[mq], 0), a.smax - 1);
     const int pmax = (int)wave_max((float)pq);                          // same for the 4 waves (same 32 queries)
@@ -230,4 +241,28 @@ __global__ __launch_bounds__(256 * NG) void k_attn_flash(const AttnArgs a) {
     }
 #undef AF_GLOAD
 #undef AF_LWRITE
+}
+
+// What the ragged launches of a group read beside their arguments, written once at csm_refill_group_begin from the segment table and the rows'
+// positions: row_slot[m] = the batch slot of row m (q|k|v epilogue, k_attn<.., RAG>) and the query tiles of k_attn_flash<.., RAG> ordered by
+// the position of their last row, descending (ties: table order) -- the longest key walks are dispatched first.  One block;
+// n_tiles = sum ceil(rows_i / 32).
+__global__ void k_rag_plan(const RagSegs sg, const int* __restrict__ pos, int* __restrict__ row_slot, int4* __restrict__ tiles, int n_tiles) {
+    for (int i = 0; i < sg.n; ++i)
+        for (int r = threadIdx.x; r < sg.s[i].rows; r += blockDim.x) row_slot[sg.s[i].row0 + r] = sg.s[i].slot;
+    for (int t = threadIdx.x; t < n_tiles; t += blockDim.x) {
+        int seg = 0, k = 0, key = 0, rank = 0;
+        for (int pass = 0; pass < 2; ++pass) {                         // pass 0: this tile's (segment, k, key); pass 1: its rank among all tiles
+            int u = 0;
+            for (int i = 0; i < sg.n; ++i) {
+                const int nt = (sg.s[i].rows + 31) / 32;
+                for (int kk = 0; kk < nt; ++kk, ++u) {
+                    const int ku = pos[sg.s[i].row0 + min(32 * kk + 31, sg.s[i].rows - 1)];
+                    if (pass == 0) { if (u == t) { seg = i; k = kk; key = ku; } }
+                    else if (ku > key || (ku == key && u < t)) rank += 1;
+                }
+            }
+        }
+        tiles[rank] = make_int4(sg.s[seg].slot, sg.s[seg].row0 + 32 * k, min(32, sg.s[seg].rows - 32 * k), 0);
+    }
 }

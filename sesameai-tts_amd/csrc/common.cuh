@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rag_segs.h"                                                 // RagSegs: the segment table of a ragged group prefill
 
 typedef unsigned short bf16_t;                                       // raw bf16 bits
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;

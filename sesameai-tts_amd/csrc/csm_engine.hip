@@ -93,6 +93,11 @@ struct CsmModel {
     std::vector<char> rf_fresh_host;    // [max_batch] host mirror of `fresh` == 1: slots whose completed refill waits for a frame step to sample its
     int rf_fresh_count;                 // frame 0 -- several can wait at once (a generator fills B slots before the first step: ADVICE r5)
     const int* rf_pos;                  // the caller's position array of the pending refill (dev, valid until the refill completes)
+    // ... or a GROUP of them in one ragged prefill (csm_refill_group_begin / _advance): one refill OR one group is in flight per handle
+    RagSegs rg;                         // pending group: its segment table (rg.n == 0: none); rf_layer / rf_pos serve it too
+    int rg_tiles_n;                     // its 32-row query tiles
+    int* rg_row_slot;                   // [max_rows] batch slot of each of the group's rows        } written by k_rag_plan at begin
+    int4* rg_tiles;                     // [max_rows / 32 + 32] {slot, first row, rows, -} by walk  }
     int device;                         // the GPU this handle lives on (csm_generate_frame_s1 makes it current itself)
     int host_frames;                    // frames launched since reset (host mirror); the history is a ring of max_frames rows
     int wide_path;                      // MFMA path for M >= wide_min (env CSM_WIDE=0 disables)
@@ -273,7 +278,8 @@ static hipError_t launch_gemv8(int kind, int K, int hd, const GemvArgs& a, hipSt
     return hipErrorInvalidValue;
 }
 
-// wide-M projections on the matrix cores; kind as in launch_gemv (0 store, 1 +residual, 3 qkv/rope, 4 swiglu)
+// wide-M projections on the matrix cores; kind as in launch_gemv (0 store, 1 +residual, 3 qkv/rope, 4 swiglu); 6 = qkv/rope of a segment group
+// (a.row_slot names each row's cache slot: EPI_QKV_ROPE_RAG, here and in launch_mmt / launch_g128)
 // k_mm32 tile order (mm.cuh): one row tile -> plain 3-D grid; more -> n tiles per XCD with the row tiles adjacent
 static void mm_grid(const GemvArgs& a, int kg, dim3* grid, int* mtiles) {
     const int nt = (a.N + 31) / 32, mt = (a.M + 31) / 32;
@@ -292,6 +298,10 @@ static hipError_t launch_mm_t(int kind, int K, int hd, const GemvArgs& a, hipStr
                 else hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE, 128, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
                 break;
         case 4: hipLaunchKernelGGL((k_mm32<EPI_SWIGLU, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1); break;
+        case 6: if (WT != 0 || a.row_slot == nullptr) return hipErrorInvalidValue;            // q|k|v of a segment group: prompt rows, bf16 stream
+                if (hd == 64) hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE_RAG, 64, 4, 0, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
+                else hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE_RAG, 128, 4, 0, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
+                break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -318,6 +328,11 @@ static hipError_t launch_mmt_tm(int kind, int hd, int K, const GemvArgs& a, hipS
         const unsigned blocks = (unsigned)(8L * ((a.N / 64 + 7) / 8) * mgroups);
         if (hd == 64) hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE, 64, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
         else hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE, 128, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
+    } else if (kind == 6) {
+        if (a.row_slot == nullptr) return hipErrorInvalidValue;
+        const unsigned blocks = (unsigned)(8L * ((a.N / 64 + 7) / 8) * mgroups);
+        if (hd == 64) hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE_RAG, 64, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
+        else hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE_RAG, 128, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
     } else if (kind == 4) {
         const unsigned blocks = (unsigned)(8L * ((a.N / 32 + 7) / 8) * mgroups);
         hipLaunchKernelGGL((k_mmt<EPI_SWIGLU, 64, TM, 1, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
@@ -396,6 +411,8 @@ static hipError_t launch_g128(int kind, int K, int hd, const GemvArgs& a, hipStr
         case 5: return launch_g128_mi<EPI_SLAB, 64>(a, K, st);
         case 3: return hd == 64 ? launch_g128_mi<EPI_QKV_ROPE, 64>(a, K, st) : launch_g128_mi<EPI_QKV_ROPE, 128>(a, K, st);
         case 4: return launch_g128_mi<EPI_SWIGLU, 64>(a, K, st);
+        case 6: if (a.row_slot == nullptr) return hipErrorInvalidValue;
+                return hd == 64 ? launch_g128_mi<EPI_QKV_ROPE_RAG, 64>(a, K, st) : launch_g128_mi<EPI_QKV_ROPE_RAG, 128>(a, K, st);
     }
     return hipErrorInvalidValue;
 }
@@ -501,6 +518,33 @@ static hipError_t launch_attn_auto(const Stack& S, const AttnArgs& t, bool promp
     return launch_attn(S.hd, t, st);
 }
 
+// A segment group's rows (csm_refill_group_advance): the table, and what k_rag_plan derived from it at begin time
+struct RagLaunch { RagSegs sg; const int* row_slot; const int4* tiles; int n_tiles; };
+// prompt attention of a group: the kernel choice of launch_attn_auto for prompt rows (by shape only), K/V base by segment
+static hipError_t launch_attn_rag(const Stack& S, AttnArgs t, const RagLaunch& rg, hipStream_t st) {
+    t.nsplit = 1;
+    if (flash_ok(S)) {
+        t.rag_tiles = rg.tiles;
+        hipLaunchKernelGGL((k_attn_flash<64, AF_NG, true>), dim3(rg.n_tiles, t.KV), dim3(256 * AF_NG), 0, st, t);
+        return hipGetLastError();
+    }
+    t.row_slot = rg.row_slot;
+    dim3 grid(t.M, t.KV, 1);
+    if (S.hd == 64) hipLaunchKernelGGL((k_attn<64, 4, true>), grid, dim3(256), 0, st, t);
+    else if (S.hd == 128) {
+        if (t.smax <= 32) hipLaunchKernelGGL((k_attn<128, 8, true>), grid, dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((k_attn<128, 4, true>), grid, dim3(256), 0, st, t);
+    }
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// the final norm of a group: the finisher normalised every row into xn [M][d] (fin.scale); each segment's last row -> its slot's row of fin.out
+static hipError_t launch_rag_take_last(const bf16_t* xn, int d, bf16_t* out, long out_stride, const RagSegs& sg, hipStream_t st) {
+    if (d % 8 != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rag_take_last, dim3(sg.n), dim3(256), 0, st, xn, (long)d, d, out, out_stride, sg);
+    return hipGetLastError();
+}
+
 // rows from which batched decode runs gate/up through k_gemm128.  Off by default: it won at 256 rows against row-major
 // activations (15.6 -> 13.8 ms) but not against operand-order ones (13.7 ms with k_mm32 throughout), and it needs
 // row-major x / act around it.
@@ -511,7 +555,9 @@ struct FinalNorm { const bf16_t* scale; bf16_t* out; long out_stride; };
 
 static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf16_t* att, bf16_t* act,
                                  int M, int rows_per_seq, const int* pos, hipStream_t st, bool prompt, const FinalNorm& fin,
-                                 bool x_normed, bool qkv0_done, int l_begin = 0, int l_end = -1) {
+                                 bool x_normed, bool qkv0_done, int l_begin = 0, int l_end = -1, const RagLaunch* rag = nullptr) {
+    // rag: the M rows are the segments of a group (prompt rows of several slots, rows_per_seq == M): q|k|v appends each row to ITS slot's
+    // cache, attention walks each segment's own keys and the final norm takes each segment's last row; every other launch is row-wise
     // [l_begin, l_end): a prompt may run a few layers per call (csm_refill_advance): what carries over between calls is h (the residual
     // stream) and att (the next layer's normalised input, written by the previous layer's finisher) -- and the K/V the layers appended
     if (l_end < 0) l_end = S.d.n_layers;
@@ -536,12 +582,13 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
             a.N = S.nq + 2 * S.nkv; a.out = q; a.ldo = S.nq;
             a.nq = S.nq; a.nkv = S.nkv; a.smax = S.cache_len; a.rows_per_seq = rows_per_seq; a.kv_heads = S.d.n_kv_heads;
             a.pos = pos; a.rope = S.rope; a.kcache = kc; a.vcache = vc;
-            if ((e = launch_g128(3, d, S.hd, a, st)) != hipSuccess) return e;
+            if (rag) a.row_slot = rag->row_slot;
+            if ((e = launch_g128(rag ? 6 : 3, d, S.hd, a, st)) != hipSuccess) return e;
             AttnArgs t;
             t.q = q; t.kcache = kc; t.vcache = vc; t.pos = pos; t.M = M; t.rows_per_seq = rows_per_seq;
             t.H = S.d.n_heads; t.KV = S.d.n_kv_heads; t.smax = S.cache_len; t.nsplit = 1;
             t.scale = 1.0f / sqrtf((float)S.hd); t.out = att; t.part = m->part; t.out_packed = 0; t.ctr = nullptr;
-            if ((e = launch_attn_auto(S, t, prompt, st)) != hipSuccess) return e;
+            if ((e = rag ? launch_attn_rag(S, t, *rag, st) : launch_attn_auto(S, t, prompt, st)) != hipSuccess) return e;
             memset(&a, 0, sizeof a);
             // residual projections: d/128 column tiles only -- below ~2 tiles per CU split K into its four quarters over
             // blocks (fp32 slabs) and let the small path's finisher add them, the residual and the next norm
@@ -566,6 +613,10 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
                 a.slab = m->slab;
                 if ((e = launch_g128(5, S.d.ffn, S.hd, a, st)) != hipSuccess) return e;
                 if (l + 1 < S.d.n_layers) e = launch_resid_norm(h, m->slab, 4, M, d, 1, 0, M, (const bf16_t*)S.lw[l + 1].sa_norm, S.d.norm_eps, att, d, st);
+                else if (rag) {
+                    e = launch_resid_norm(h, m->slab, 4, M, d, 1, 0, M, fin.scale, S.d.norm_eps, att, d, st);
+                    if (e == hipSuccess) e = launch_rag_take_last(att, d, fin.out, fin.out_stride, rag->sg, st);
+                }
                 else e = launch_resid_norm(h, m->slab, 4, M, d, rows_per_seq, rows_per_seq - 1, nseq, fin.scale, S.d.norm_eps, fin.out, fin.out_stride, st);
                 if (e != hipSuccess) return e;
                 continue;
@@ -573,6 +624,9 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
             if ((e = launch_g128(1, S.d.ffn, S.hd, a, st)) != hipSuccess) return e;
             if (l + 1 < S.d.n_layers) {
                 if ((e = launch_rmsnorm_rows(h, d, 0, M, d, (const bf16_t*)S.lw[l + 1].sa_norm, S.d.norm_eps, att, d, st)) != hipSuccess) return e;
+            } else if (rag) {
+                if ((e = launch_rmsnorm_rows(h, d, 0, M, d, fin.scale, S.d.norm_eps, att, d, st)) != hipSuccess) return e;
+                if ((e = launch_rag_take_last(att, d, fin.out, fin.out_stride, rag->sg, st)) != hipSuccess) return e;
             } else {
                 if ((e = launch_rmsnorm_rows(h, (long)rows_per_seq * d, (long)(rows_per_seq - 1) * d, nseq, d, fin.scale, S.d.norm_eps,
                                              fin.out, fin.out_stride, st)) != hipSuccess) return e;
@@ -623,8 +677,9 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
                 a.s0 = (const float*)S.w8s[l].wq; a.s1 = (const float*)S.w8s[l].wk; a.s2 = (const float*)S.w8s[l].wv;
             }
             const bool xq = l > 0 ? xp : xp0;                  // (decode steps: layer 0's input comes row-major)
-            if (mid && (MMT_OPS & 1)) e = launch_mmt(3, S.hd, d, a, st, xq);
-            else e = launch_mm(3, d, S.hd, a, st, f8, xq);
+            if (rag) a.row_slot = rag->row_slot;
+            if (mid && (MMT_OPS & 1)) e = launch_mmt(rag ? 6 : 3, S.hd, d, a, st, xq);
+            else e = launch_mm(rag ? 6 : 3, d, S.hd, a, st, f8, xq);
             if (e != hipSuccess) return e;
         }
         AttnArgs t;
@@ -638,7 +693,7 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
             t.nsplit = ns < 1 ? 1 : (ns > BB_NSPLIT_MAX ? BB_NSPLIT_MAX : ns);
             if (t.nsplit > 1) t.ctr = m->attn_ctr;            // the last key-range block of a (row, KV head) merges (no k_attn_combine launch)
         }
-        if ((e = launch_attn_auto(S, t, prompt, st)) != hipSuccess) return e;
+        if ((e = rag ? launch_attn_rag(S, t, *rag, st) : launch_attn_auto(S, t, prompt, st)) != hipSuccess) return e;
         // o-proj -> fp32 slabs; finisher: h += sum(slabs), xn = mlp_norm(h)
         memset(&a, 0, sizeof a);
         a.x = att; a.x_row_stride = S.nq; a.M = M; a.w0 = (const bf16_t*)pk.wo; a.N = d; a.slab = m->slab;
@@ -678,8 +733,12 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
             // last layer: only each sequence's last row is read again (heads / last_h); its finisher applies the
             // stack's final norm
             const int nseq = M / rows_per_seq;
-            if ((e = launch_resid_norm(h, m->slab, kg, M, d, rows_per_seq, rows_per_seq - 1, nseq, fin.scale, S.d.norm_eps,
-                                       fin.out, fin.out_stride, st, prompt)) != hipSuccess) return e;
+            if (rag) {             // (row-major xn: the prompt form of the finisher, not in operand order)
+                e = launch_resid_norm(h, m->slab, kg, M, d, 1, 0, M, fin.scale, S.d.norm_eps, att, d, st, prompt);
+                if (e == hipSuccess) e = launch_rag_take_last(att, d, fin.out, fin.out_stride, rag->sg, st);
+            } else e = launch_resid_norm(h, m->slab, kg, M, d, rows_per_seq, rows_per_seq - 1, nseq, fin.scale, S.d.norm_eps,
+                                       fin.out, fin.out_stride, st, prompt);
+            if (e != hipSuccess) return e;
         }
     }
     return hipSuccess;
@@ -689,14 +748,16 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
 // (depth decoder), which lets the narrow path drop the dependent position load
 static hipError_t run_stack(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf16_t* att, bf16_t* act,
                             int M, int rows_per_seq, const int* pos_arr, int pos_const, hipStream_t st, bool force_wide = false,
-                            bool x_normed = false, bool qkv0_done = false, int l_begin = 0, int l_end = -1, bf16_t* fin_out = nullptr) {
+                            bool x_normed = false, bool qkv0_done = false, int l_begin = 0, int l_end = -1, bf16_t* fin_out = nullptr,
+                            const RagLaunch* rag = nullptr) {
     if ((M >= m->wide_min || force_wide) && m->wide_path) {
         FinalNorm fin;
         if (&S == &m->bb) { fin.scale = (const bf16_t*)m->w.bb_norm; fin.out = fin_out ? fin_out : m->dec_in; fin.out_stride = 2L * S.d.dim; }
         else { fin.scale = (const bf16_t*)m->w.dec_norm; fin.out = att; fin.out_stride = S.d.dim; }
-        return run_stack_wide(m, S, h, q, att, act, M, rows_per_seq, pos_arr, st, force_wide, fin, x_normed, qkv0_done, l_begin, l_end);
+        if (rag && (!force_wide || x_normed || qkv0_done || rows_per_seq != M || &S != &m->bb)) return hipErrorInvalidValue;     // a group: backbone prompt rows only
+        return run_stack_wide(m, S, h, q, att, act, M, rows_per_seq, pos_arr, st, force_wide, fin, x_normed, qkv0_done, l_begin, l_end, rag);
     }
-    if (l_begin != 0 || (l_end >= 0 && l_end != S.d.n_layers) || fin_out != nullptr) return hipErrorInvalidValue;      // layer ranges: matrix-core path only
+    if (l_begin != 0 || (l_end >= 0 && l_end != S.d.n_layers) || fin_out != nullptr || rag != nullptr) return hipErrorInvalidValue;      // layer ranges: matrix-core path only
     const int* pos = pos_const >= 0 ? nullptr : pos_arr;
     const int pos_base = pos_const >= 0 ? pos_const : 0;
     const int d = S.d.dim;
@@ -994,6 +1055,9 @@ static inline void fresh_clear(CsmModel* m, int slot) {
     if (slot >= 0 && slot < (int)m->rf_fresh_host.size() && m->rf_fresh_host[(size_t)slot]) { m->rf_fresh_host[(size_t)slot] = 0; m->rf_fresh_count -= 1; }
 }
 static inline void fresh_clear_all(CsmModel* m) { m->rf_fresh_host.assign(m->rf_fresh_host.size(), 0); m->rf_fresh_count = 0; }
+// a refill beside the loop, or a group of them, has begun and not completed / `slot` is (one of) its slot(s)
+static inline bool refill_pending(const CsmModel* m) { return m->rf_slot >= 0 || m->rg.n > 0; }
+static inline bool slot_refilling(const CsmModel* m, int slot) { return (m->rf_slot >= 0 && slot == m->rf_slot) || rag_segs_has_slot(m->rg, slot); }
 static inline bool refill_beside_ok(const CsmModel* m, int B) { return m->wide_path && B >= m->wide_min && B <= m->max_batch; }
 static inline bool frame_injects(const CsmModel* m, int B) { return m->rf_last != nullptr && refill_beside_ok(m, B); }
 
@@ -1434,7 +1498,7 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     m->slot_tab_used = false; m->slot_tab_host.assign((size_t)max_batch, 0);
     ALLOC(m->fresh, (size_t)max_batch * 4);
     HIPCHK((CsmModel*)nullptr, hipMemset(m->fresh, 0, (size_t)max_batch * 4));
-    m->rf_h = m->rf_xn = m->rf_last = nullptr; m->rf_slot = -1; m->rf_S = 0; m->rf_layer = 0; m->rf_pos = nullptr;
+    m->rf_h = m->rf_xn = m->rf_last = nullptr; m->rg.n = 0; m->rg_tiles_n = 0; m->rg_row_slot = nullptr; m->rg_tiles = nullptr; m->rf_slot = -1; m->rf_S = 0; m->rf_layer = 0; m->rf_pos = nullptr;
     m->rf_fresh_host.assign((size_t)max_batch, 0); m->rf_fresh_count = 0;
     ALLOC(m->dec_pos, (size_t)(ncb + 1) * 2 * max_batch * 4);
     ALLOC(m->slot_scratch, (size_t)max_batch * 4);
@@ -1535,7 +1599,7 @@ extern "C" void csm_destroy(csm_handle m) {
     for (CsmPrefix* p : m->prefixes) { (void)hipFree(p->data); p->data = nullptr; p->owner = nullptr; }      // (the caller still destroys the objects)
     void* ptrs[] = {m->bb.kc, m->bb.vc, m->dec.kc, m->dec.vc, m->h, m->q, m->att, m->act, m->part, m->attn_ctr, m->dec_in, m->proj_emb, m->slab,
                     m->hdec, m->qd, m->attd, m->actd, m->logits, m->frame, m->cur_tokens, m->cur_mask, m->cur_pos,
-                    m->history, m->n_frames, m->eos_at, m->rng, m->slot_tab, m->frame_save, m->fresh, m->rf_h, m->rf_xn, m->rf_last, m->dec_pos, m->slot_scratch, m->p_state, m->b_state, m->qkv0_tab};
+                    m->history, m->n_frames, m->eos_at, m->rng, m->slot_tab, m->frame_save, m->fresh, m->rf_h, m->rf_xn, m->rf_last, m->rg_row_slot, m->rg_tiles, m->dec_pos, m->slot_scratch, m->p_state, m->b_state, m->qkv0_tab};
     for (void* p : ptrs) (void)hipFree(p);
     for (void* p : m->pk_allocs) (void)hipFree(p);
     if (m->xslab) (void)hipFree(m->xslab);
@@ -1602,7 +1666,7 @@ extern "C" int csm_reset(csm_handle m, void* stream) {
         HIPCHK(m, hipMemsetAsync(m->slot_tab, 0, (size_t)m->max_batch * sizeof(SlotSampling), st));
         m->slot_tab_host.assign(m->slot_tab_host.size(), 0);
     }
-    m->host_frames = 0; m->have_last = false; m->rf_slot = -1; fresh_clear_all(m);
+    m->host_frames = 0; m->have_last = false; m->rf_slot = -1; m->rg.n = 0; fresh_clear_all(m);
     return CSM_OK;
 }
 
@@ -1776,7 +1840,7 @@ static hipError_t enqueue_frame(CsmModel* m, int B, float temperature, int topk,
 extern "C" int csm_frame_step(csm_handle m, int B, float temperature, int topk, int use_graph, void* stream) {
     if (!m || B < 1 || B > m->max_batch) return fail(m, CSM_E_INVALID, "csm_frame_step: bad batch");
     if (!(temperature > 0.f) || topk < 1) return fail(m, CSM_E_INVALID, "csm_frame_step: temperature must be > 0 and topk >= 1");
-    if ((m->rf_slot >= 0 || m->rf_fresh_count > 0) && !frame_injects(m, B))
+    if ((refill_pending(m) || m->rf_fresh_count > 0) && !frame_injects(m, B))
         return fail(m, CSM_E_STATE, "csm_frame_step: a refill beside the frame loop is pending and a step of this batch size does not take the matrix-core path "
                                     "(csm_refill_supported(h, B) == 0): its parked / fresh slot would be stepped like a generating one");
     hipStream_t st = (hipStream_t)stream;
@@ -1846,7 +1910,7 @@ extern "C" int csm_generate_frame_s1(csm_handle m, const int64_t* tokens, const 
     if (!m || !tokens || !mask || !pos || !out_frame || B < 1 || B > m->max_batch) return fail(m, CSM_E_INVALID, "csm_generate_frame_s1: bad argument");
     // everything csm_frame_step would refuse is refused BEFORE the step inputs are overwritten
     if (!(temperature > 0.f) || topk < 1) return fail(m, CSM_E_INVALID, "csm_generate_frame_s1: temperature must be > 0 and topk >= 1");
-    if ((m->rf_slot >= 0 || m->rf_fresh_count > 0) && !frame_injects(m, B)) return csm_frame_step(m, B, temperature, topk, 1, stream);   // (reports the state error)
+    if ((refill_pending(m) || m->rf_fresh_count > 0) && !frame_injects(m, B)) return csm_frame_step(m, B, temperature, topk, 1, stream);   // (reports the state error)
     int dev = m->device;
     (void)hipGetDevice(&dev);
     if (dev != m->device && hipSetDevice(m->device) != hipSuccess) return fail(m, CSM_E_HIP, "csm_generate_frame_s1: cannot make the handle's device current");
@@ -1908,7 +1972,7 @@ extern "C" int csm_reset_slots(csm_handle m, const int32_t* slots, int n, void* 
     if (!m || !slots || n < 0 || n > m->max_batch) return fail(m, CSM_E_INVALID, "csm_reset_slots: bad argument");
     if (n == 0) return CSM_OK;
     for (int i = 0; i < n; ++i) {
-        if (m->rf_slot >= 0 && slots[i] == m->rf_slot) return fail(m, CSM_E_STATE, "csm_reset_slots: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+        if (slot_refilling(m, slots[i])) return fail(m, CSM_E_STATE, "csm_reset_slots: the slot's refill beside the frame loop is still running (csm_refill_advance)");
     }
     for (int i = 0; i < n; ++i) fresh_clear(m, slots[i]);
     hipStream_t st = (hipStream_t)stream;
@@ -1925,7 +1989,7 @@ extern "C" int csm_prefill_slot(csm_handle m, int slot, const int32_t* tokens, c
     if (!m || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_prefill_slot: null argument");
     if (slot < 0 || slot >= m->max_batch || S < 1 || S > m->max_rows) return fail(m, CSM_E_INVALID, "csm_prefill_slot: slot / S outside the limits given to csm_create");
     if (!(temperature > 0.f) || topk < 1) return fail(m, CSM_E_INVALID, "csm_prefill_slot: temperature must be > 0 and topk >= 1");
-    if (slot == m->rf_slot) return fail(m, CSM_E_STATE, "csm_prefill_slot: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+    if (slot_refilling(m, slot)) return fail(m, CSM_E_STATE, "csm_prefill_slot: the slot's refill beside the frame loop is still running (csm_refill_advance)");
     hipStream_t st = (hipStream_t)stream;
     fresh_clear(m, slot);
     hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(64), 0, st, m->fresh + slot, 0, 1);      // a completed-but-unsampled refill of this slot is dropped
@@ -1953,20 +2017,26 @@ extern "C" int csm_prefill_slot(csm_handle m, int slot, const int32_t* tokens, c
 // ---------------------------------------------------------------------------------------
 // refill BESIDE the frame loop: the other slots never wait for a whole prompt
 // ---------------------------------------------------------------------------------------
+// the workspace of a refill beside the loop, made by the first begin call of a handle
+static int refill_buffers(CsmModel* m, hipStream_t st) {
+    if (m->rf_last != nullptr) return CSM_OK;
+    const int dbb = m->cfg.backbone.dim;
+    HIPCHK(m, hipMalloc((void**)&m->rf_h, (size_t)m->max_rows * dbb * 2));
+    HIPCHK(m, hipMalloc((void**)&m->rf_xn, (size_t)m->max_rows * m->bb.nq * 2));
+    HIPCHK(m, hipMalloc((void**)&m->rf_last, (size_t)m->max_batch * 2 * dbb * 2));
+    HIPCHK(m, hipMemsetAsync(m->rf_last, 0, (size_t)m->max_batch * 2 * dbb * 2, st));
+    drop_frame_graphs(m);                                                              // re-capture: the frame step gains its inject node
+    return CSM_OK;
+}
+
 extern "C" int csm_refill_begin(csm_handle m, int slot, const int32_t* tokens, const uint8_t* mask, const int32_t* pos, int S, void* stream) {
     if (!m || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_refill_begin: null argument");
     if (slot < 0 || slot >= m->max_batch || S < 1 || S > m->max_rows) return fail(m, CSM_E_INVALID, "csm_refill_begin: slot / S outside the limits given to csm_create");
     if (m->rf_slot >= 0) return fail(m, CSM_E_STATE, "csm_refill_begin: a refill is already in progress (finish it with csm_refill_advance)");
+    if (m->rg.n > 0) return fail(m, CSM_E_STATE, "csm_refill_begin: a refill group is in progress (finish it with csm_refill_group_advance)");
     if (!refill_beside_ok(m, m->max_batch)) return fail(m, CSM_E_STATE, "csm_refill_begin: needs the matrix-core decode path (csm_refill_supported); use csm_prefill_slot");
     hipStream_t st = (hipStream_t)stream;
-    const int dbb = m->cfg.backbone.dim;
-    if (m->rf_last == nullptr) {
-        HIPCHK(m, hipMalloc((void**)&m->rf_h, (size_t)m->max_rows * dbb * 2));
-        HIPCHK(m, hipMalloc((void**)&m->rf_xn, (size_t)m->max_rows * m->bb.nq * 2));
-        HIPCHK(m, hipMalloc((void**)&m->rf_last, (size_t)m->max_batch * 2 * dbb * 2));
-        HIPCHK(m, hipMemsetAsync(m->rf_last, 0, (size_t)m->max_batch * 2 * dbb * 2, st));
-        drop_frame_graphs(m);                                                              // re-capture: the frame step gains its inject node
-    }
+    { const int rc = refill_buffers(m, st); if (rc != CSM_OK) return rc; }
     HIPCHK(m, launch_embed(m, tokens, mask, S, st, m->rf_h));
     // parked: until the prompt is complete the slot's row of the frame steps is a placeholder at positions >= S (its K/V land beyond the prompt's)
     hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1,
@@ -1998,6 +2068,78 @@ extern "C" int csm_refill_advance(csm_handle m, int max_layers, void* stream) {
     HIPCHK(m, hipGetLastError());
     m->rf_slot = -1; m->rf_pos = nullptr;
     if (!m->rf_fresh_host[(size_t)slot]) { m->rf_fresh_host[(size_t)slot] = 1; m->rf_fresh_count += 1; }
+    return 1;
+}
+
+// ---------------------------------------------------------------------------------------
+// ... for SEVERAL slots at once: one ragged prefill whose rows are the prompts (or the suffixes after a copied prefix) of up to 32 slots, back
+// to back, each with its own length and start position.  Slots that retire in the same block share ONE launch chain per layer instead
+// of queueing behind each other with a handful of rows each.  Prompt rows keep their bits whatever shares their call.
+// ---------------------------------------------------------------------------------------
+// every listed slot's position = one past its segment's last row; its flag; (optionally) its sampling-table counter rewound
+__global__ void k_rag_set_state(const RagSegs sg, const int* pos, int M, int* cur_pos, int max_batch, int max_seq, int* overflow, SlotSampling* slot_tab,
+                                int* fresh, int flag) {
+    for (int i = threadIdx.x; i < sg.n; i += blockDim.x) {
+        const int b = sg.s[i].slot;
+        if (b < 0 || b >= max_batch) continue;
+        cur_pos[b] = pos[sg.s[i].row0 + sg.s[i].rows - 1] + 1;
+        if (slot_tab != nullptr) slot_tab[b].counter = 0;
+        fresh[b] = flag;
+    }
+    for (int i = threadIdx.x; i < M; i += blockDim.x)
+        if (pos[i] < 0 || pos[i] >= max_seq) *overflow = 1;
+}
+
+extern "C" int csm_refill_group_begin(csm_handle m, const int32_t* slots, const int32_t* rows, int n, const int32_t* tokens, const uint8_t* mask,
+                                      const int32_t* pos, void* stream) {
+    if (!m || !slots || !rows || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_refill_group_begin: null argument");
+    RagSegs sg;
+    int tiles = 0;
+    if (const char* why = rag_segs_build(slots, rows, n, m->max_batch, m->max_rows, &sg, &tiles)) {
+        const std::string msg = std::string("csm_refill_group_begin: ") + why;
+        return fail(m, CSM_E_INVALID, msg.c_str());
+    }
+    if (m->rf_slot >= 0) return fail(m, CSM_E_STATE, "csm_refill_group_begin: a refill is in progress (finish it with csm_refill_advance)");
+    if (m->rg.n > 0) return fail(m, CSM_E_STATE, "csm_refill_group_begin: a refill group is already in progress (finish it with csm_refill_group_advance)");
+    if (!refill_beside_ok(m, m->max_batch)) return fail(m, CSM_E_STATE, "csm_refill_group_begin: needs the matrix-core decode path (csm_refill_supported); use csm_prefill_slot");
+    hipStream_t st = (hipStream_t)stream;
+    { const int rc = refill_buffers(m, st); if (rc != CSM_OK) return rc; }
+    if (m->rg_row_slot == nullptr) {
+        HIPCHK(m, hipMalloc((void**)&m->rg_row_slot, (size_t)m->max_rows * 4));
+        HIPCHK(m, hipMalloc((void**)&m->rg_tiles, (size_t)(m->max_rows / 32 + RAG_MAX_SEGS) * sizeof(int4)));
+    }
+    const int M = rag_segs_rows(sg);
+    HIPCHK(m, launch_embed(m, tokens, mask, M, st, m->rf_h));
+    hipLaunchKernelGGL(k_rag_plan, dim3(1), dim3(256), 0, st, sg, pos, m->rg_row_slot, m->rg_tiles, tiles);
+    // parked (flag 2) at its own prompt length, like csm_refill_begin's slot -- all of them in one launch
+    hipLaunchKernelGGL(k_rag_set_state, dim3(1), dim3(256), 0, st, sg, pos, M, m->cur_pos, m->max_batch, m->cfg.backbone.max_seq, m->n_frames + 1,
+                       m->slot_tab_used ? m->slot_tab : nullptr, m->fresh, 2);
+    HIPCHK(m, hipGetLastError());
+    for (int i = 0; i < sg.n; ++i) fresh_clear(m, sg.s[i].slot);
+    m->rg = sg; m->rg_tiles_n = tiles; m->rf_layer = 0; m->rf_pos = pos;
+    return CSM_OK;
+}
+
+extern "C" int csm_refill_group_advance(csm_handle m, int max_layers, void* stream) {
+    if (!m || max_layers < 1) return fail(m, CSM_E_INVALID, "csm_refill_group_advance: bad argument");
+    if (m->rg.n < 1) return fail(m, CSM_E_STATE, "csm_refill_group_advance: no refill group in progress");
+    hipStream_t st = (hipStream_t)stream;
+    const int L = m->cfg.backbone.n_layers, M = rag_segs_rows(m->rg);
+    const int l0 = m->rf_layer, l1 = l0 + max_layers < L ? l0 + max_layers : L;
+    RagLaunch rl;
+    rl.sg = m->rg; rl.row_slot = m->rg_row_slot; rl.tiles = m->rg_tiles; rl.n_tiles = m->rg_tiles_n;
+    HIPCHK(m, run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, m->rf_pos, -1, st, true, false, false, l0, l1, m->rf_last, &rl));
+    m->rf_layer = l1;
+    if (l1 < L) return 0;
+    // complete: every slot back at its prompt length, flags up -- the next frame step samples frame 0 of all of them
+    hipLaunchKernelGGL(k_rag_set_state, dim3(1), dim3(256), 0, st, m->rg, m->rf_pos, M, m->cur_pos, m->max_batch, m->cfg.backbone.max_seq, m->n_frames + 1,
+                       (SlotSampling*)nullptr, m->fresh, 1);
+    HIPCHK(m, hipGetLastError());
+    for (int i = 0; i < m->rg.n; ++i) {
+        const size_t slot = (size_t)m->rg.s[i].slot;
+        if (!m->rf_fresh_host[slot]) { m->rf_fresh_host[slot] = 1; m->rf_fresh_count += 1; }
+    }
+    m->rg.n = 0; m->rf_pos = nullptr;
     return 1;
 }
 
@@ -2047,7 +2189,7 @@ static hipError_t launch_prefix_copy(CsmModel* m, const CsmPrefix* p, const Pref
 extern "C" int csm_prefix_capture(csm_handle m, int slot, int rows, csm_prefix* out, void* stream) {
     if (!m || !out) return fail(m, CSM_E_INVALID, "csm_prefix_capture: null argument");
     if (slot < 0 || slot >= m->max_batch || rows < 1 || rows >= m->cfg.backbone.max_seq) return fail(m, CSM_E_INVALID, "csm_prefix_capture: slot outside the batch or rows outside [1, max_seq)");
-    if (slot == m->rf_slot) return fail(m, CSM_E_STATE, "csm_prefix_capture: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+    if (slot_refilling(m, slot)) return fail(m, CSM_E_STATE, "csm_prefix_capture: the slot's refill beside the frame loop is still running (csm_refill_advance)");
     hipStream_t st = (hipStream_t)stream;
     int pos = 0;
     HIPCHK(m, hipMemcpyAsync(&pos, m->cur_pos + slot, 4, hipMemcpyDeviceToHost, st));
@@ -2077,7 +2219,7 @@ extern "C" int csm_prefix_apply(csm_handle m, csm_prefix p, const int32_t* slots
     PrefixSlots sl;
     for (int i = 0; i < n; ++i) {
         if (slots[i] < 0 || slots[i] >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_prefix_apply: slot outside the batch");
-        if (slots[i] == m->rf_slot) return fail(m, CSM_E_STATE, "csm_prefix_apply: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+        if (slot_refilling(m, slots[i])) return fail(m, CSM_E_STATE, "csm_prefix_apply: the slot's refill beside the frame loop is still running (csm_refill_advance)");
         sl.s[i] = (unsigned short)slots[i];
     }
     if (n == 0) return CSM_OK;

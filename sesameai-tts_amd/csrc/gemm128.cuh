@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, MI <= 2 ? 2 : 1) void k_gemm128(const GemvArgs
         if (EPI == EPI_SWIGLU) {                            // B rows: [wave column][gate 32 | up 32]
             n = min(n0 + (tr >> 6) * 32 + (tr & 31), a.N - 1);
             wsrc = ((tr >> 5) & 1) ? a.w1 : a.w0;
-        } else if (EPI == EPI_QKV_ROPE) {
+        } else if (EPI_IS_QKV(EPI)) {
             n = min(n0 + tr, a.N - 1);
             if (n < a.nq) wsrc = a.w0;
             else if (n < a.nq + a.nkv) { wsrc = a.w1; n -= a.nq; }
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256, MI <= 2 ? 2 : 1) void k_gemm128(const GemvArgs
             const bf16_t* wsrc;
             int n;
             if (EPI == EPI_SWIGLU) { n = min(n0 + (tr >> 6) * 32 + (tr & 31), a.N - 1); wsrc = ((tr >> 5) & 1) ? a.w1 : a.w0; }
-            else if (EPI == EPI_QKV_ROPE) {
+            else if (EPI_IS_QKV(EPI)) {
                 n = min(n0 + tr, a.N - 1);
                 if (n < a.nq) wsrc = a.w0;
                 else if (n < a.nq + a.nkv) { wsrc = a.w1; n -= a.nq; }

@@ -16,7 +16,10 @@
 #include "common.cuh"
 
 enum { PRO_PLAIN = 0, PRO_NORM = 1, PRO_ATTN = 2, PRO_COMBINE = 3 };
-enum { EPI_STORE = 0, EPI_RESID = 1, EPI_QKV_ROPE = 2, EPI_SWIGLU = 3, EPI_SLAB = 4 };
+enum { EPI_STORE = 0, EPI_RESID = 1, EPI_QKV_ROPE = 2, EPI_SWIGLU = 3, EPI_SLAB = 4, EPI_QKV_ROPE_RAG = 5 };
+// EPI_QKV_ROPE_RAG (wide-M kernels only; csm_refill_group_*): EPI_QKV_ROPE whose rows belong to DIFFERENT batch slots -- the cache slot of
+// row m is row_slot[m] instead of m / rows_per_seq.  An instantiation of its own: the code of EPI_QKV_ROPE is what it was.
+#define EPI_IS_QKV(E) ((E) == EPI_QKV_ROPE || (E) == EPI_QKV_ROPE_RAG)
 
 struct GemvArgs {
     // activations: row m lives at x + m * x_row_stride + x_row_offset (elements), K wide
@@ -46,7 +49,10 @@ struct GemvArgs {
     bf16_t* vcache;
     // PRO_ATTN (depth decoder: hd 128, <= 32 keys): the activation row IS the attention output of
     // q [M][aH*128] over keys [0,pos[m]] of kcache/vcache, computed in the prologue
-    const bf16_t* aq;
+    union {
+        const bf16_t* aq;
+        const int* row_slot;    // EPI_QKV_ROPE_RAG (never with PRO_ATTN): [M] batch slot of each row (same word as aq: the argument
+    };                          // block of every other instantiation keeps its layout)
     int aH;
     float ascale;
     int pos_base;               // used when pos == nullptr

@@ -27,6 +27,16 @@ __global__ __launch_bounds__(256) void k_rmsnorm_rows(const bf16_t* x, long x_ro
     else rmsnorm_row_wave(x + (long)row * x_row_stride + x_row_offset, K, scale, eps, out + (long)row * out_stride, lane);
 }
 
+// The final norm of a segment group (common.cuh RagSegs): the last layer's finisher normalises ALL rows of the group into xn [M][ld] (the strided
+// form's arithmetic per row, so the same bits); this takes each segment's LAST row to out + slot * out_stride.  One block per segment.
+__global__ __launch_bounds__(256) void k_rag_take_last(const bf16_t* xn, long ld, int K, bf16_t* out, long out_stride, const RagSegs sg) {
+    const int i = blockIdx.x;
+    if (i >= sg.n) return;
+    const uint4* src = reinterpret_cast<const uint4*>(xn + ((long)sg.s[i].row0 + sg.s[i].rows - 1) * ld);
+    uint4* dst = reinterpret_cast<uint4*>(out + (long)sg.s[i].slot * out_stride);
+    for (int c = threadIdx.x; c < K / 8; c += blockDim.x) dst[c] = src[c];
+}
+
 // Finishes a split-K residual projection of the wide path and (optionally) applies the next RMSNorm:
 //   h[r] = bf16(h[r] + bf16(sum_g slab[g][r]))      (fixed g order: deterministic)
 //   xn[i] = RMSNorm(h[r]) * scale                   (skipped when scale == nullptr)
@@ -222,11 +232,11 @@ template <int EPI, int HD>
 __device__ __forceinline__ void mm_finish(const GemvArgs& a, const int m, const int n, const float s0, const float s1) {
 #pragma clang fp contract(off)
     float y = round_bf(s0);
-    if (EPI == EPI_QKV_ROPE) {
+    if (EPI_IS_QKV(EPI)) {
         const float other = __shfl_xor(y, 1, WAVE);
         if (m < a.M && n < a.N) {
             const int p = row_pos(a, m);
-            const int b = m / a.rows_per_seq;
+            const int b = EPI == EPI_QKV_ROPE_RAG ? a.row_slot[m] : m / a.rows_per_seq;
             if (n < a.nq + a.nkv) {
                 const int e = (n < a.nq ? n : n - a.nq) % HD;
                 const uint32_t cs = reinterpret_cast<const uint32_t*>(a.rope)[(long)p * (HD / 2) + e / 2];
@@ -285,7 +295,7 @@ __global__ __launch_bounds__(NW * 64) void k_mm32(const GemvArgs a, const int K,
     const long tile_u4 = (long)(K / 64) * 256;            // pieces per n-tile
     float wscale0 = 1.0f, wscale1 = 1.0f;                 // WT == 1: power-of-two scale of this lane's weight row
     const int nl = min(n0 + r, a.N - 1);
-    if (EPI == EPI_QKV_ROPE) {                            // nq, nkv are multiples of 32: a tile never straddles q/k/v
+    if (EPI_IS_QKV(EPI)) {                                // nq, nkv are multiples of 32: a tile never straddles q/k/v
         if (n0 < a.nq) { wa = reinterpret_cast<const wfrag_t*>(a.w0) + (long)(n0 / 32) * tile_u4; if (WT) wscale0 = a.s0[nl]; }
         else if (n0 < a.nq + a.nkv) { wa = reinterpret_cast<const wfrag_t*>(a.w1) + (long)((n0 - a.nq) / 32) * tile_u4; if (WT) wscale0 = a.s1[nl - a.nq]; }
         else { wa = reinterpret_cast<const wfrag_t*>(a.w2) + (long)((n0 - a.nq - a.nkv) / 32) * tile_u4; if (WT) wscale0 = a.s2[nl - a.nq - a.nkv]; }
@@ -419,7 +429,7 @@ __global__ __launch_bounds__(NW * 64) void k_mm32(const GemvArgs a, const int K,
 // ---------------------------------------------------------------------------------------------------------------
 template <int EPI, int HD>
 __device__ __forceinline__ const uint4* mmt_weight_tile(const GemvArgs& a, const int n, const long tile_u4, const int which) {
-    if (EPI == EPI_QKV_ROPE) {
+    if (EPI_IS_QKV(EPI)) {
         if (n < a.nq) return reinterpret_cast<const uint4*>(a.w0) + (long)(n / 32) * tile_u4;
         if (n < a.nq + a.nkv) return reinterpret_cast<const uint4*>(a.w1) + (long)((n - a.nq) / 32) * tile_u4;
         return reinterpret_cast<const uint4*>(a.w2) + (long)((n - a.nq - a.nkv) / 32) * tile_u4;

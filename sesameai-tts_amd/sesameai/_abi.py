@@ -81,6 +81,8 @@ SIGNATURES = {
     "csm_refill_supported": (_i, [_vp, _i]),
     "csm_refill_begin": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
     "csm_refill_advance": (_i, [_vp, _i, _vp]),
+    "csm_refill_group_begin": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "csm_refill_group_advance": (_i, [_vp, _i, _vp]),
     "csm_prefix_capture": (_i, [_vp, _i, _i, C.POINTER(_vp), _vp]),
     "csm_prefix_apply": (_i, [_vp, _vp, _vp, _i, _vp]),
     "csm_prefix_rows": (_i, [_vp]),

@@ -294,7 +294,7 @@ class Generator:
     @torch.inference_mode()
     def iter_codes_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                               temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
-                              seed: Optional[Sequence[Optional[int]]] = None) -> PyGenerator[Tuple[int, torch.Tensor], None, None]:
+                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1) -> PyGenerator[Tuple[int, torch.Tensor], None, None]:
         """Any number of prompts [(tokens (S_i,33), mask (S_i,33)), ...] of any lengths through a batch of ``max_batch_size``
         slots that is kept FULL: an utterance that reaches its all-zero EOS frame (generator.py:285) or the length limit is
         retired and its slot re-prefilled with the next prompt (Model.refill_slot) while the other slots keep generating --
@@ -305,7 +305,7 @@ class Generator:
         a seed of its own yields the same frames whichever slot it takes and whatever the batch did before (Model.set_slot_sampling).  There is no limit on the total number of frame steps: the engine's frame history is a ring (include/csm_hip.h,
         csm_read_frames) and every block of ``poll`` steps is read before the next one is launched."""
         parts: dict = {}
-        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed):
+        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed, refill_group=refill_group):
             for i, _slot, frames, last in block or ():
                 parts.setdefault(i, []).append(frames)
                 if last:
@@ -315,7 +315,7 @@ class Generator:
     @torch.inference_mode()
     def _iter_blocks_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                                 temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
-                                seed: Optional[Sequence[Optional[int]]] = None):
+                                seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1):
         """The incremental form of ``iter_codes_continuous`` (same loop, same model calls in the same order): per polled block it
         yields a list of ``(index of the prompt, batch slot, that utterance's NEW frames [k][32] int32 CPU, last)`` -- ``last`` with
         the frames that complete the utterance (possibly none); an utterance that is empty before it ever holds a slot has slot -1.
@@ -324,33 +324,33 @@ class Generator:
         The scheduler is sesameai/live_batch.py; ``refill_beside_the_loop`` / ``refill_row_layers`` choose and tune how slots are refilled."""
         per_prompt_sampling(len(prompts), temperature, topk, seed)          # (a wrong length or a bad value raises before the model is touched)
         yield from live_batch(self._model, prompts, max_generation_len, temperature, topk, poll or self._eos_poll, self._max_batch,
-                              self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN, seed=seed)
+                              self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN, seed=seed, refill_group=refill_group)
 
     def generate_codes_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: int,
                                   temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
-                                  seed: Optional[Sequence[Optional[int]]] = None) -> List[torch.Tensor]:
+                                  seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1) -> List[torch.Tensor]:
         """``iter_codes_continuous`` collected: each prompt's frames [n_i][32] int32 (CPU), in the order of ``prompts``."""
         results: List[torch.Tensor] = [torch.empty(0, 32, dtype=torch.int32) for _ in prompts]
-        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed):
+        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed, refill_group=refill_group):
             results[i] = frames
         return results
 
     def generate_many(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                       temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
-                      seed: Optional[Sequence[Optional[int]]] = None) -> List[torch.Tensor]:
+                      seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1) -> List[torch.Tensor]:
         """``generate`` for a list of requests through the continuously refilled batch: one audio tensor per request
         (``max_audio_length_ms``, ``temperature``, ``topk``: one value, or one per request; ``seed``: one optional int per request)."""
         max_generation_len = _frames_for(max_audio_length_ms)
         prompts = [self._build_prompt(t, sp, ctx) for t, sp, ctx in zip(texts, speakers, contexts)]
         out: List[torch.Tensor] = [torch.tensor([]) for _ in prompts]
-        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed):
+        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group):
             if frames.shape[0]:                                       # decoded as each utterance finishes, not at the end
                 out[i] = self._decode_frames(frames.unsqueeze(1))
         return out
 
     def generate_many_stream(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                              temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
-                             seed: Optional[Sequence[Optional[int]]] = None
+                             seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1
                              ) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
@@ -379,7 +379,7 @@ class Generator:
             self._stream_pools[(B, size)] = codec.open_streams(B, max_chunk_frames=size)
         streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device)
         backlog: List[list] = []                                    # polled blocks whose audio is still to be decoded
-        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed):
+        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed, refill_group=refill_group):
             if block is not None:
                 backlog.append(block)
                 continue

@@ -157,13 +157,20 @@ class _BesideTheLoop(LiveBatch):
     extras.config3.refill_beside_the_loop) while the other slots keep generating, and the new utterance's frame 0 is sampled by the batch's next
     frame step.  Until then the slot's rows are placeholders and are skipped.  Only the rows after a registered prefix count against the budget."""
 
-    def __init__(self, *args, budget: int):
+    def __init__(self, *args, budget: int, group: int = 1):
         super().__init__(*args)
         self.budget, self.layers = budget, self.m.bb.num_layers
         self.refilling: Optional[Tuple[int, int, int]] = None       # (slot, prompt index, prompt rows to run)
+        # group > 1: free slots with prompts pending are refilled up to ``group`` at a time by ONE ragged prefill (Model.refill_group_begin /
+        # refill_group_advance) -- slots that retire in the same block share one launch chain per layer instead of queueing with a handful
+        # of rows each.  Requests with a seed of their own keep their codes whatever the group size (their draws do not depend on the schedule).
+        self.group = max(1, min(int(group), 32))
+        self.grouped: Optional[Tuple[List[Tuple[int, int]], int]] = None    # ([(slot, prompt index)], rows of the group), pending
 
     def _feed(self, everything: bool) -> bool:
         """One bounded piece of refill work (``everything``: nobody is generating, so run whole prompts).  False: there was none."""
+        if self.group > 1:
+            return self._feed_groups(everything)
         m, fed = self.m, False
         while self.refilling is not None or (self.free and self.pending):
             if self.refilling is None:
@@ -178,6 +185,59 @@ class _BesideTheLoop(LiveBatch):
             if m.refill_advance(self.layers if everything else min(per_call, self.layers)):
                 self.slots[slot] = _Utterance(i, self.limits[i], m.num_frames(), [])
                 self.refilling = None
+            fed = True
+            if not everything:
+                break
+        return fed
+
+    def _begin_group(self) -> None:
+        """Takes up to ``group`` free slots with a pending prompt each -- as many as fit ``max_prefill_rows`` together, at least one -- and begins
+        them as one group.  Everything ``_rows_to_run`` does per slot happens first, the prefix copies one per handle as in the initial fill,
+        then the sampling-table calls, then the ONE begin call: no frame step between any of them."""
+        m = self.m
+        cap = int(getattr(m, "max_prefill_rows", 0)) or (1 << 30)
+        take: List[Tuple[int, int]] = []
+        total = 0
+        while self.free and self.pending and len(take) < self.group:
+            i = self.pending[0]
+            rows = int(self.prompts[i][0].shape[0]) - (self.plan[i][0] if self.plan[i][1] is not None else 0)
+            if take and total + rows > cap:
+                break                                               # it waits for the next group
+            take.append((self.free.popleft(), self.pending.popleft()))
+            total += rows
+        copies: dict = {}                                           # id(handle) -> (handle, [slots]) still to copy
+        for slot, i in take:
+            handle = self.plan[i][1]
+            if handle is not None and self.seeded.pop(slot, None) is not handle:
+                copies.setdefault(id(handle), (handle, []))[1].append(slot)
+        for handle, slots in copies.values():
+            m.apply_prefix(handle, slots)
+        parts = []
+        for slot, i in take:
+            (t, mk), (P, handle) = self.prompts[i], self.plan[i]
+            if self.own[i] is not None:
+                m.set_slot_sampling([slot], *self.own[i])
+                self.entries.add(slot)
+            elif slot in self.entries:
+                m.clear_slot_sampling([slot])
+                self.entries.discard(slot)
+            parts.append((t[P:], mk[P:], P) if handle is not None else (t, mk, 0))
+        m.refill_group_begin([slot for slot, _ in take], [(t, mk) for t, mk, _ in parts], starts=[P for _, _, P in parts])
+        self.grouped = (take, total)
+
+    def _feed_groups(self, everything: bool) -> bool:
+        """``_feed`` with groups: the per-step budget is spent on the group's rows together."""
+        m, fed = self.m, False
+        while self.grouped is not None or (self.free and self.pending):
+            if self.grouped is None:
+                self._begin_group()
+            take, rows = self.grouped
+            per_call = max(1, self.budget * (1 + len(self.free)) // max(rows, 1))
+            if m.refill_group_advance(self.layers if everything else min(per_call, self.layers)):
+                first = m.num_frames()
+                for slot, i in take:
+                    self.slots[slot] = _Utterance(i, self.limits[i], first, [])
+                self.grouped = None
             fed = True
             if not everything:
                 break
@@ -221,10 +281,11 @@ def per_prompt_sampling(n: int, temperature, topk, seed):
 
 
 def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_batch, store, beside_the_loop, refill_row_layers, max_seq_len,
-               seed=None):
+               seed=None, refill_group: int = 1):
     """``LiveBatch.run`` over ``prompts`` [(tokens (S_i,33), mask (S_i,33)), ...] with one length limit for all or one per prompt (a
     request's own max_audio_length_ms), refilling beside the loop where the model's frame steps of this batch size honour it.
-    ``temperature`` / ``topk``: one value, or one per prompt; ``seed``: one optional int per prompt (``per_prompt_sampling``)."""
+    ``temperature`` / ``topk``: one value, or one per prompt; ``seed``: one optional int per prompt (``per_prompt_sampling``).
+    ``refill_group``: how many free slots one refill beside the loop may take together (1: one at a time, today's calls exactly)."""
     (temperature, topk), own = per_prompt_sampling(len(prompts), temperature, topk, seed)
     limits = [int(max_generation_len)] * len(prompts) if isinstance(max_generation_len, (int, float)) else [int(x) for x in max_generation_len]
     if len(limits) != len(prompts):
@@ -238,7 +299,9 @@ def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_
     args = (model, prompts, limits, temperature, topk, poll, B, store, own if any(o is not None for o in own) else None)
     supported = getattr(model, "supports_refill_beside_the_loop", None)         # (a scripted model may lack it)
     beside = supported is not None and supported(B) and beside_the_loop
-    yield from (_BesideTheLoop(*args, budget=refill_row_layers) if beside else _Stalling(*args)).run()
+    if int(refill_group) < 1:
+        raise ValueError("refill_group must be >= 1")
+    yield from (_BesideTheLoop(*args, budget=refill_row_layers, group=refill_group) if beside else _Stalling(*args)).run()
 
 
 class SlotStreams:

@@ -774,9 +774,10 @@ class Model:
         p = torch.arange(start, start + s, device=self.device, dtype=torch.int32)
         self.last_prefill_rows = s
         self.prefill_rows_total += s
-        self._refill_keep = (t, m, p)                             # the position array is read by every advance call
         with self._on_device():
             check(lib.csm_refill_begin(self._h, int(slot), t.data_ptr(), m.data_ptr(), p.data_ptr(), s, _stream_ptr()), self._h)
+        self._refill_keep = (t, m, p)                             # the position array is read by every advance call (kept only once the
+        #                                                           call was accepted: a refused begin must not drop a pending refill's arrays)
 
     def refill_advance(self, max_layers: int) -> bool:
         """Up to ``max_layers`` more backbone layers of the pending refill.  True when the prompt is complete: the NEXT frame step
@@ -788,6 +789,50 @@ class Model:
         if rc == 1:
             self._refill_keep = None
         return rc == 1
+
+    def refill_group_begin(self, slots, prompts, starts=None) -> None:
+        """``refill_begin`` for several slots at once (csm_refill_group_begin): ``prompts[i]`` = (tokens (S_i,33), mask (S_i,33)) are the rows of
+        batch slot ``slots[i]`` from position ``starts[i]`` on (default 0; rows [0, starts[i]) are in the slot's caches: ``apply_prefix``).  Up to
+        32 distinct slots, ``max_prefill_rows`` rows in all.  Their layers run over all rows together through ``refill_group_advance``.  One
+        refill or one group at a time per model."""
+        self._require()
+        slots = [int(x) for x in slots]
+        n = len(slots)
+        starts = [0] * n if starts is None else [int(x) for x in starts]
+        if n < 1 or len(prompts) != n or len(starts) != n:
+            raise ValueError("refill_group_begin: one prompt (and one start) per slot, at least one slot")
+        rows = [int(t.shape[0]) for t, _ in prompts]
+        for s, p in zip(rows, starts):
+            if s < 1 or p < 0 or p + s >= self.bb.max_seq_len:
+                raise ValueError(f"prompt of {s} rows from {p} exceeds max_seq_len {self.bb.max_seq_len}")
+        if sum(rows) > self.max_prefill_rows:
+            raise ValueError(f"group of {sum(rows)} rows exceeds max_prefill_rows {self.max_prefill_rows}")
+        self._kv_prompt = None
+        t = torch.cat([self._to_dev(t_, torch.int32) for t_, _ in prompts], 0).contiguous()
+        m = torch.cat([self._to_dev(m_, torch.uint8) for _, m_ in prompts], 0).contiguous()
+        p = torch.cat([torch.arange(p_, p_ + s_, dtype=torch.int32) for s_, p_ in zip(rows, starts)]).to(self.device)
+        with self._on_device():
+            check(lib.csm_refill_group_begin(self._h, (C.c_int32 * n)(*slots), (C.c_int32 * n)(*rows), n, t.data_ptr(), m.data_ptr(), p.data_ptr(),
+                                             _stream_ptr()), self._h)
+        self._refill_keep = (t, m, p)                             # the position array is read by every advance call (see refill_begin)
+        self.last_prefill_rows = sum(rows)
+        self.prefill_rows_total += sum(rows)
+
+    def refill_group_advance(self, max_layers: int) -> bool:
+        """Up to ``max_layers`` more backbone layers of the pending group.  True when it is complete: the NEXT frame step yields frame 0 of
+        every utterance of the group in its slot's row (csm_refill_group_advance)."""
+        with self._on_device():
+            rc = lib.csm_refill_group_advance(self._h, int(max_layers), _stream_ptr())
+        if rc < 0:
+            check(rc, self._h)
+        if rc == 1:
+            self._refill_keep = None
+        return rc == 1
+
+    @property
+    def max_prefill_rows(self) -> int:
+        """The most rows one prefill / refill call may carry (csm_create's max_rows)."""
+        return max(self._max_prefill_rows, 2 * self._max_batch)
 
     def supports_refill_beside_the_loop(self, batch: Optional[int] = None) -> bool:
         """Whether frame steps of ``batch`` rows (default: the handle's max batch) honour a refill beside the loop -- the engine's own
