@@ -26,6 +26,7 @@
 #include "dec_persist_m.cuh"
 #include "dec_first.cuh"
 #include "bb_block.cuh"
+#include "switches.h"
 
 #define BB_NSPLIT_MAX 8
 #define PART_ROWS 32
@@ -135,11 +136,6 @@ struct CsmModel {
     std::vector<void*> persist_allocs, bb_allocs;   // device memory of the optional all-CU launches
     char* xslab; size_t xslab_used, xslab_align;     // the small exchange buffers of the B = 1 all-CU launches live in one 2 MB-aligned slab (placement under our control)
     bool persist_disabled, bb_disabled;             // a launch gave up once: the chain runs from then on (the buffers stay: error words are still read)
-    // experiment (CSM_BB_PREFETCH=n, off by default): while the latency-bound kernels of a batched backbone layer run (q|k|v,
-    // split-key attention, o-proj, finisher: ~30 us with HBM nearly idle), n blocks on a SECOND stream touch that layer's gate/up/down weights
-    // (100 MB) so that the two MLP kernels find them in the 256 MB Infinity Cache; forked and joined with events (graph branches under capture)
-    int bb_prefetch;
-    hipStream_t pf_stream; hipEvent_t pf_fork[CSM_MAX_LAYERS], pf_join[CSM_MAX_LAYERS];
     bool have_last;                     // prefill or a frame step has produced h for csm_depth
     int last_S;                         // rows per sequence of the h buffer feeding csm_depth
     // captured frame steps: a small LRU keyed on (batch, top-k, temperature, carries the per-slot sampling table) -- a service whose requests alternate sampling parameters or
@@ -314,11 +310,11 @@ static hipError_t launch_mm(int kind, int K, int hd, const GemvArgs& a, hipStrea
 }
 
 // prompts of 64..255 rows (mm.cuh k_mmt / k_mmq): k_mm32's bits with several output tiles per wave.  w0/w1/w2 PACKED.
-static const int MMT_MIN_ROWS = getenv("CSM_MMT_MIN_ROWS") ? atoi(getenv("CSM_MMT_MIN_ROWS")) : 64;
+static const int MMT_MIN_ROWS = sw_int(SW_CSM_MMT_MIN_ROWS, 64);
 // which projections take them (bit 0 q|k|v, 1 gate/up, 2 o-proj, 3 down).  Measured per backbone layer at 190 rows, operand-order
 // x, us: q|k|v 21.3 vs k_mm32 14.9 (96 fat blocks leave 160 CUs idle and a CU pulls only ~30 GB/s from HBM whatever the
 // prefetch depth), gate/up 28.4 vs 41.6, o-proj 11.5 vs 13.0, down 37.4 vs 31.0  ->  default: gate/up and o-proj
-static const int MMT_OPS = getenv("CSM_MMT_OPS") ? atoi(getenv("CSM_MMT_OPS")) : 6;
+static const int MMT_OPS = sw_int(SW_CSM_MMT_OPS, 6);
 static bool mmt_ok(int M, int K, int N) { return M >= MMT_MIN_ROWS && M <= 256 && K % 1024 == 0 && N % 64 == 0; }   // K/4 quarters in rings of up to 8 half-chunks
 #define MMT_NBUF(TM_) 2                              // ring depth: 4 measured no faster than 2 at 190 rows and costs the second resident block (gate/up 31 vs 28 us)
 template <int TM, bool XP>
@@ -366,11 +362,11 @@ static hipError_t launch_mmq(int K, const GemvArgs& a, hipStream_t st, bool xp =
 
 // long prompts / batched prefill: LDS-tiled 128 x 128 kernel (gemm128.cuh); weights UNPACKED [N][K]
 // rows from which prefill takes the LDS-tiled kernels (measured: 190 rows 5.8 vs 6.7 ms with them, 380 rows 8.4 vs 7.8)
-static const int G128_MIN_ROWS = getenv("CSM_G128_MIN_ROWS") ? atoi(getenv("CSM_G128_MIN_ROWS")) : 256;
+static const int G128_MIN_ROWS = sw_int(SW_CSM_G128_MIN_ROWS, 256);
 // rows from which a block is 256 x 128 (4 row tiles per wave, one block per CU, operands by LDS-DMA into three LDS buffers; gemm128.cuh,
 // round 3).  OFF: measured SLOWER at every size (1,334 rows: gate/up 161 vs 136 us, q|k|v 92 vs 60; 32 x 190 rows: prefill + frame 0
 // 26.4 vs 23.0 ms) -- one wave per SIMD leaves the slice barrier and the fragment reads uncovered.  Bit-identical, kept for the A/B.
-static const int G256_MIN_ROWS = getenv("CSM_G256_MIN_ROWS") ? atoi(getenv("CSM_G256_MIN_ROWS")) : (1 << 30);
+static const int G256_MIN_ROWS = sw_int(SW_CSM_G256_MIN_ROWS, (1 << 30));
 template <int EPI, int HD, int MI>
 static hipError_t launch_g128_t(const GemvArgs& a, int K, hipStream_t st) {
     constexpr int SMEM = MI == 1 ? G64_SMEM : MI == 2 ? G128_SMEM : G256_SMEM, BM = 64 * MI;
@@ -386,7 +382,7 @@ static hipError_t launch_g128_t(const GemvArgs& a, int K, hipStream_t st) {
     }
     const int nout = EPI == EPI_SWIGLU ? 64 : 128;
     const int mtiles = (a.M + BM - 1) / BM, ntiles = (a.N + nout - 1) / nout;
-    static const int switch_tiles = getenv("CSM_G128_ROWTILES") ? atoi(getenv("CSM_G128_ROWTILES")) : 32;
+    static const int switch_tiles = sw_int(SW_CSM_G128_ROWTILES, 32);
     int mt8; unsigned blocks;
     if (mtiles * BM / 128 >= switch_tiles) { mt8 = (mtiles + 7) / 8; blocks = (unsigned)(8L * ntiles * mt8); }   // row tiles per XCD
     else { mt8 = -mtiles; blocks = (unsigned)(8L * ((ntiles + 7) / 8) * mtiles); }                            // column tiles per XCD
@@ -395,7 +391,7 @@ static hipError_t launch_g128_t(const GemvArgs& a, int K, hipStream_t st) {
     return hipGetLastError();
 }
 // 64-row blocks when the 128-row tiling would leave at most ~one block per CU (measured at 1,334 rows under rocprofv3: q|k|v 64 -> 47 us); same bits
-static const int G64_MAX_BLOCKS = getenv("CSM_G64_MAX_BLOCKS") ? atoi(getenv("CSM_G64_MAX_BLOCKS")) : 320;
+static const int G64_MAX_BLOCKS = sw_int(SW_CSM_G64_MAX_BLOCKS, 320);
 template <int EPI, int HD>
 static hipError_t launch_g128_mi(const GemvArgs& a, int K, hipStream_t st) {
     if (a.M >= G256_MIN_ROWS) return launch_g128_t<EPI, HD, 4>(a, K, st);
@@ -426,7 +422,7 @@ static int slab_groups(int K, bool prompt) {
     // Decode steps (M <= a few row tiles): one block pulls its bytes through ONE CU at ~70 GB/s, so spread K over
     // up to 8 blocks of >= 256 k each (measured at M = 32: K 1024 -> kg 1/2/4 = 5.1/3.9/3.3 us, K 2048 N 2048 ->
     // kg 2/4/8 = 5.4/4.3/4.4 us; K 8192 -> 8 x 1024: blocks of 2048 or 4096 k are 3 % / 12 % slower end to end)
-    static const int per_block = getenv("CSM_SLAB_K") ? atoi(getenv("CSM_SLAB_K")) : 256;
+    static const int per_block = sw_int(SW_CSM_SLAB_K, 256);
     int kg = K / per_block;
     return kg < 1 ? 1 : (kg > 8 ? 8 : kg);
 }
@@ -480,25 +476,6 @@ static hipError_t launch_attn(int hd, const AttnArgs& a, hipStream_t st, bool co
     return hipGetLastError();
 }
 
-// touch [p, p + n16) 16-byte pieces with ordinary (cache-allocating) loads; the value is folded into a store that never happens
-__global__ __launch_bounds__(256) void k_touch(const uint4* __restrict__ p0, long n0, const uint4* __restrict__ p1, long n1, const uint4* __restrict__ p2, long n2, uint32_t* sink) {
-    uint32_t acc = 0;
-    const long stride = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint4* ps[3] = {p0, p1, p2};
-    const long ns[3] = {n0, n1, n2};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const uint4* p = ps[q];
-        long i = t;
-        for (; i + 3 * stride < ns[q]; i += 4 * stride) {            // four loads in flight per thread; one 16-byte piece per 128-byte line would do,
-            const uint4 a = p[i], b = p[i + stride], c = p[i + 2 * stride], d = p[i + 3 * stride];   // but whole lines keep the access coalesced
-            acc ^= a.x ^ b.y ^ c.z ^ d.w;
-        }
-        for (; i < ns[q]; i += stride) acc ^= p[i].x;
-    }
-    if (acc == 0x9e3779b9u && sink != nullptr) *sink = acc;
-}
-
 // ---------------------------------------------------------------------------------------
 // one Llama stack over M token rows (in place on h)
 // ---------------------------------------------------------------------------------------
@@ -512,7 +489,7 @@ static bool flash_ok(const Stack& S) { return S.hd == 64 && S.d.n_heads % S.d.n_
 static hipError_t launch_attn_auto(const Stack& S, const AttnArgs& t, bool prompt, hipStream_t st) {
     if (flash_ok(S) && t.nsplit == 1 && (prompt || t.rows_per_seq >= FLASH_MIN_ROWS)) {
         dim3 grid((t.M / t.rows_per_seq) * ((t.rows_per_seq + 31) / 32), t.KV);
-        hipLaunchKernelGGL((k_attn_flash<64, AF_NG>), grid, dim3(256 * AF_NG), 0, st, t);
+        hipLaunchKernelGGL((k_attn_flash<64>), grid, dim3(256), 0, st, t);
         return hipGetLastError();
     }
     return launch_attn(S.hd, t, st);
@@ -525,7 +502,7 @@ static hipError_t launch_attn_rag(const Stack& S, AttnArgs t, const RagLaunch& r
     t.nsplit = 1;
     if (flash_ok(S)) {
         t.rag_tiles = rg.tiles;
-        hipLaunchKernelGGL((k_attn_flash<64, AF_NG, true>), dim3(rg.n_tiles, t.KV), dim3(256 * AF_NG), 0, st, t);
+        hipLaunchKernelGGL((k_attn_flash<64, true>), dim3(rg.n_tiles, t.KV), dim3(256), 0, st, t);
         return hipGetLastError();
     }
     t.row_slot = rg.row_slot;
@@ -544,11 +521,6 @@ static hipError_t launch_rag_take_last(const bf16_t* xn, int d, bf16_t* out, lon
     hipLaunchKernelGGL(k_rag_take_last, dim3(sg.n), dim3(256), 0, st, xn, (long)d, d, out, out_stride, sg);
     return hipGetLastError();
 }
-
-// rows from which batched decode runs gate/up through k_gemm128.  Off by default: it won at 256 rows against row-major
-// activations (15.6 -> 13.8 ms) but not against operand-order ones (13.7 ms with k_mm32 throughout), and it needs
-// row-major x / act around it.
-static const int g128_gateup_rows = getenv("CSM_G128_GATEUP_ROWS") ? atoi(getenv("CSM_G128_GATEUP_ROWS")) : (1 << 30);
 
 // where the stack's final RMSNorm of each sequence's LAST row goes on the wide path (fused into the last finisher)
 struct FinalNorm { const bf16_t* scale; bf16_t* out; long out_stride; };
@@ -641,7 +613,7 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
         // the kernels of a layer (common.cuh xp_off): producers write it, consumers read 1 KB pieces
         // (from 24 rows: a 1 KB piece always carries 32 rows, so for a few rows the row-major gather touches fewer lines:
         //  B=8 5.39 vs 5.52 ms packed, B=32 6.15 vs 6.01, B=64 7.42 vs 6.93, B=128 10.29 vs 9.07)
-        const bool xp_decode = m->xpack && !prompt && rows_per_seq <= 2 && M >= 24 && M < g128_gateup_rows && (d == 512 || d == 1024 || d == 2048);
+        const bool xp_decode = m->xpack && !prompt && rows_per_seq <= 2 && M >= 24 && (d == 512 || d == 1024 || d == 2048);
         // prompts below the LDS-tiled kernels' row count do the same (round 2): their projections were bound by exactly those
         // gathers (TA address cycles, 64 lines per fragment), not by bytes
         const bool xp_prompt = m->xpack_prompt && (prompt || rows_per_seq > 2) && !f8 && M >= 24 && d % 64 == 0 && S.nq % 64 == 0 && S.d.ffn % 64 == 0 && d <= 2048;
@@ -653,17 +625,6 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
         // layer 0 normalises h directly; later layers got xn from the previous down-projection's finisher.
         // (layer 0 of a depth-decoder step >= 2: q/k/v were gathered from the precomputed table by the sampler)
         int kg = 1;
-        const bool pf = m->bb_prefetch > 0 && &S == &m->bb && !prompt && rows_per_seq == 1 && !f8 && l_begin == 0 && l_end == S.d.n_layers;
-        if (pf) {
-            if ((e = hipEventRecord(m->pf_fork[l], st)) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(m->pf_stream, m->pf_fork[l], 0)) != hipSuccess) return e;
-            const long n13 = (long)((S.d.ffn + 31) / 32) * (d / 64) * 256, n2 = (long)((d + 31) / 32) * (S.d.ffn / 64) * 256;     // 16-byte pieces of the packed copies
-            hipLaunchKernelGGL(k_touch, dim3(m->bb_prefetch), dim3(256), 0, m->pf_stream, (const uint4*)pk.w1, n13, (const uint4*)pk.w3, n13, (const uint4*)pk.w2, n2,
-                               (uint32_t*)nullptr);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if ((e = hipEventRecord(m->pf_join[l], m->pf_stream)) != hipSuccess) return e;
-        }
-        {
         if (!(l == 0 && qkv0_done)) {
             if (l == 0 && !x_normed && (e = launch_rmsnorm_rows(h, d, 0, M, d, (const bf16_t*)w.sa_norm, S.d.norm_eps, att, d, st, xp0)) != hipSuccess) return e;
             memset(&a, 0, sizeof a);
@@ -703,22 +664,13 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
         else e = launch_mm_slab(S.nq, kg, a, st, f8, xp);
         if (e != hipSuccess) return e;
         if ((e = launch_resid_norm(h, m->slab, kg, M, d, 1, 0, M, (const bf16_t*)w.mlp_norm, S.d.norm_eps, att, d, st, prompt, xp)) != hipSuccess) return e;
-        }
-        if (pf && (e = hipStreamWaitEvent(st, m->pf_join[l], 0)) != hipSuccess) return e;       // join: the MLP kernels start once the layer's weights were touched
         memset(&a, 0, sizeof a);
         a.x = att; a.x_row_stride = d; a.M = M; a.w0 = (const bf16_t*)pk.w1; a.w1 = (const bf16_t*)pk.w3; a.N = S.d.ffn;
         a.out = act; a.ldo = S.d.ffn; a.out_packed = xp;
-        if (M >= g128_gateup_rows) {
-            // 8+ row tiles: the widest projection (N = 2 ffn) has enough 128 x 128 tiles for the LDS-tiled kernel, which
-            // reads each weight tile once per 128 rows instead of once per 32 (same bits as k_mm32)
-            a.w0 = (const bf16_t*)w.w1; a.w1 = (const bf16_t*)w.w3;
-            if ((e = launch_g128(4, d, S.hd, a, st)) != hipSuccess) return e;
-        } else {
-            if (f8) { a.w0 = (const bf16_t*)p8.w1; a.w1 = (const bf16_t*)p8.w3; a.s0 = (const float*)S.w8s[l].w1; a.s1 = (const float*)S.w8s[l].w3; }
-            if (mid && (MMT_OPS & 2)) e = launch_mmt(4, S.hd, d, a, st, xp);
-            else e = launch_mm(4, d, S.hd, a, st, f8, xp);
-            if (e != hipSuccess) return e;
-        }
+        if (f8) { a.w0 = (const bf16_t*)p8.w1; a.w1 = (const bf16_t*)p8.w3; a.s0 = (const float*)S.w8s[l].w1; a.s1 = (const float*)S.w8s[l].w3; }
+        if (mid && (MMT_OPS & 2)) e = launch_mmt(4, S.hd, d, a, st, xp);
+        else e = launch_mm(4, d, S.hd, a, st, f8, xp);
+        if (e != hipSuccess) return e;
         // down-proj -> slabs; finisher applies the NEXT layer's sa_norm (or nothing after the last layer)
         memset(&a, 0, sizeof a);
         a.x = act; a.x_row_stride = S.d.ffn; a.M = M; a.w0 = (const bf16_t*)pk.w2; a.N = d; a.slab = m->slab;
@@ -905,7 +857,7 @@ static hipError_t launch_dec_persist(CsmModel* m, int B, float temperature, int 
         p.gQ = m->pg_q; p.gH1 = m->pg_h1; p.gH2 = m->pg_h2; p.gL = m->pg_l; p.gP = m->pg_p;
         p.err = m->p_state + 1; p.epoch = m->p_state; p.eps = c.decoder.norm_eps; p.trickle_sleep = m->p_trickle; p.poll_sleep = m->p_poll;
         p.stamps = m->p_stamps;
-        { static int faults_left = getenv("CSM_PERSIST_FAULT") ? atoi(getenv("CSM_PERSIST_FAULT")) : 0;     // timeline build: the first n launches withhold a granule
+        { static int faults_left = sw_int(SW_CSM_PERSIST_FAULT, 0);     // timeline build: the first n launches withhold a granule
           p.fault = faults_left > 0 ? 1 : 0; if (faults_left > 0) --faults_left; }
         return csm_launch_dec_persist(p, st);
     }
@@ -1245,7 +1197,7 @@ struct OptAllocs {                                   // allocations of one optio
     }
 };
 static void note_fallback(const char* what, const char* why) {
-    if (getenv("CSM_QUIET") == nullptr) fprintf(stderr, "libcsm_hip: %s disabled (%s): the launch chain runs instead\n", what, why);
+    if (!sw_set(SW_CSM_QUIET)) fprintf(stderr, "libcsm_hip: %s disabled (%s): the launch chain runs instead\n", what, why);
 }
 // A launch of DP_NB workgroups whose waves wait for each other is only correct if all of them are resident at once: ask
 // the runtime whether one workgroup of this kernel (512 threads, `lds` bytes) fits a CU, and whether the device has DP_NB CUs.
@@ -1266,14 +1218,13 @@ static bool all_cu_launch_fits(K kernel, size_t lds, const char* what) {
 
 static void setup_persist(CsmModel* m) {
     const CsmConfig* cfg = &m->cfg;
-    const char* ev = getenv("CSM_PERSIST");
     const CsmLlamaDims& dc = cfg->decoder;
     // the in-kernel sampler's candidate lists hold DP_CAND_SLOTS entries each
     const bool shape_ok = dc.n_layers == DP_NL && dc.dim == DP_D && dc.ffn == DP_FFN && dc.n_heads == 8 && dc.n_kv_heads == 2 &&
                           cfg->n_codebooks >= 3 && cfg->n_codebooks <= 32 && cfg->audio_vocab <= DP_CAND_SLOTS && cfg->audio_vocab <= 2 * DP_LSLOTS;
     // (fp8 mode too: the launch streams the bf16 weights, which there ARE the dequantised e4m3 values -- byte * scale is
     //  exactly a bf16 -- so it computes what the fp8 chain computes; the decoder is bound by its hand-offs, not by bytes)
-    if ((ev && ev[0] == '0') || !shape_ok || m->qkv0_tab == nullptr) return;
+    if (!sw_on(SW_CSM_PERSIST) || !shape_ok || m->qkv0_tab == nullptr) return;
     if (!all_cu_launch_fits(csm_dec_persist_kernel(), DP_LDS_BYTES, "persistent depth decoder")) return;
     OptAllocs A;
     A.small(m, &m->pg_q, (size_t)DP_NREP * 768 * 8); A.small(m, &m->pg_h1, (size_t)DP_NREP * 512 * 8); A.small(m, &m->pg_h2, (size_t)DP_NREP * 512 * 8);
@@ -1297,13 +1248,12 @@ static void setup_persist(CsmModel* m) {
     }
     ok = ok && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     if (!ok) { (void)hipGetLastError(); A.drop(); note_fallback("persistent depth decoder", "weight re-tiling failed"); return; }
-    { const char* e2 = getenv("CSM_PERSIST_TRICKLE"); m->p_trickle = e2 ? atoi(e2) : 8; }       // (swept 4..16 x 0..3 at round 2's final state: 8 / 1; re-swept in round 3: 8..10 / 0)
-    { const char* e2 = getenv("CSM_PERSIST_POLL"); m->p_poll = e2 ? atoi(e2) : 0; }             // (round 3, alternating A/B at the final state: 0 beats 1 by 17 us per frame, 2.744 against 2.762 ms)
+    m->p_trickle = sw_int(SW_CSM_PERSIST_TRICKLE, 8);       // (swept 4..16 x 0..3 at round 2's final state: 8 / 1; re-swept in round 3: 8..10 / 0)
+    m->p_poll = sw_int(SW_CSM_PERSIST_POLL, 0);             // (round 3, alternating A/B at the final state: 0 beats 1 by 17 us per frame, 2.744 against 2.762 ms)
     m->persist = true;
     m->persist_allocs = A.ptrs;
     {   // ---- the first decoder step (positions 0, 1) as one launch: shares the decoder's re-tiled weights, own granule slots ----
-        const char* evf = getenv("CSM_DEC_FIRST");
-        if (!(evf && evf[0] == '0') && all_cu_launch_fits(csm_dec_first_kernel(), DF_LDS_BYTES, "first depth-decoder step")) {
+        if (sw_on(SW_CSM_DEC_FIRST) && all_cu_launch_fits(csm_dec_first_kernel(), DF_LDS_BYTES, "first depth-decoder step")) {
             OptAllocs F;
             F.small(m, &m->fg_q, (size_t)DP_NREP * 1536 * 8); F.small(m, &m->fg_h1, (size_t)DP_NREP * 1024 * 8); F.small(m, &m->fg_h2, (size_t)DP_NREP * 1024 * 8);
             F.get(&m->fg_p, (size_t)2 * 256 * 1024 * 8);
@@ -1312,10 +1262,9 @@ static void setup_persist(CsmModel* m) {
         }
     }
     // ---- the batched form (2..32 rows): shares the q|k|v|o rows and the norms, own packed MLP weights and exchange buffers ----
-    const char* evm = getenv("CSM_PERSIST_M");
-    { const char* e2 = getenv("CSM_PERSIST_M_TRICKLE"); m->pm_trickle = e2 ? atoi(e2) : 4; }
-    { const char* e2 = getenv("CSM_PERSIST_M_MAX"); m->pm_max_rows = e2 ? atoi(e2) : 32; if (m->pm_max_rows > 32) m->pm_max_rows = 32; }
-    if ((evm && evm[0] == '0') || m->max_batch < 2 || cfg->audio_vocab <= 2048 || cfg->audio_vocab > 2056) return;
+    m->pm_trickle = sw_int(SW_CSM_PERSIST_M_TRICKLE, 4);
+    m->pm_max_rows = sw_int(SW_CSM_PERSIST_M_MAX, 32); if (m->pm_max_rows > 32) m->pm_max_rows = 32;
+    if (!sw_on(SW_CSM_PERSIST_M) || m->max_batch < 2 || cfg->audio_vocab <= 2048 || cfg->audio_vocab > 2056) return;
     if (!all_cu_launch_fits(k_dec_persist_m<1>, DM_LDS_BYTES, "batched persistent depth decoder") ||
         !all_cu_launch_fits(k_dec_persist_m<2>, DM_LDS_BYTES, "batched persistent depth decoder")) return;
     OptAllocs Bm;
@@ -1333,13 +1282,11 @@ static void setup_persist(CsmModel* m) {
 }
 
 static void setup_bb_block(CsmModel* m) {
-    const char* ev = getenv("CSM_BB_BLOCK");
     const CsmLlamaDims& bc = m->cfg.backbone;
     const bool f8 = m->w.fp8 != 0;
     m->bb_layer8 = false; m->b_w2t8 = nullptr;
-    if ((ev && ev[0] == '0') || bc.dim != BB_D || bc.n_heads != BB_NH || bc.n_kv_heads != BB_NKV) return;
-    const char* ev2 = getenv("CSM_BB_LAYER");
-    const bool want_layer = !(ev2 && ev2[0] == '0') && bc.ffn == 8192;
+    if (!sw_on(SW_CSM_BB_BLOCK) || bc.dim != BB_D || bc.n_heads != BB_NH || bc.n_kv_heads != BB_NKV) return;
+    const bool want_layer = sw_on(SW_CSM_BB_LAYER) && bc.ffn == 8192;
     if (f8 && !want_layer) return;                       // the fp8 stream exists only in the one-launch layer (the three-launch block is bf16)
     if (!all_cu_launch_fits(k_bb_attn_block, 0, "one-launch backbone attention block")) return;
     OptAllocs A;
@@ -1371,16 +1318,6 @@ static void setup_bb_block(CsmModel* m) {
     if (f8) { m->b_w2t8 = w2t; m->bb_layer8 = true; } else { m->b_w2t = w2t; m->bb_layer = true; }
 }
 
-// Every CSM_* / MIMI_* environment switch this library, its Python host or the C examples read.  They exist so the A/Bs
-// can be re-run; none is needed in production.  A name under those prefixes that is NOT in the table selects nothing -- a typo would silently
-// leave the default in force -- so the first csm_create / mimi_create of a process lists such names once on stderr.
-static const char* const KNOWN_SWITCHES[] = {
-    "CSM_ATTN_MERGE", "CSM_BB_BLOCK", "CSM_BB_LAYER", "CSM_BB_PREFETCH", "CSM_C_HOST_GPUS", "CSM_DEC_FIRST", "CSM_DEC_MLP_NT", "CSM_FP8_WIDE", "CSM_FUSE_DEC_ATTN", "CSM_G128_GATEUP_ROWS",
-    "CSM_G128_MIN_ROWS", "CSM_G128_ROWTILES", "CSM_G256_MIN_ROWS", "CSM_G64_MAX_BLOCKS", "CSM_KEEP_FAST_PATHS", "CSM_MMT_MIN_ROWS", "CSM_MMT_OPS",
-    "CSM_PERSIST", "CSM_PERSIST_FAULT", "CSM_PERSIST_M", "CSM_PERSIST_M_MAX", "CSM_PERSIST_M_TRICKLE", "CSM_PERSIST_POLL", "CSM_PERSIST_TRICKLE",
-    "CSM_QKV0_TABLE", "CSM_QUIET", "CSM_SLAB_K", "CSM_WIDE", "CSM_WIDE_MIN", "CSM_XPACK", "CSM_XPACK_PROMPT", "CSM_XSLAB", "MIMI_GRAPH_MAX_T", "MIMI_KSPLIT",
-    // read by the Python host / the tools
-    "CSM_HIP_LIB", "CSM_HIP_TIMELINE", "CSM_MIMI_PATH", "CSM_MODEL_PATH", "CSM_NO_WARMUP", "CSM_SYNTHETIC", "CSM_TOKENIZER_JSON", "CSM_VOICE_DIR"};
 extern char** environ;
 static std::string set_switches(bool known) {
     std::string out;
@@ -1389,7 +1326,7 @@ static std::string set_switches(bool known) {
         const char* eq = strchr(*e, '=');
         const std::string name(*e, eq ? (size_t)(eq - *e) : strlen(*e));
         bool is_known = false;
-        for (const char* k : KNOWN_SWITCHES) is_known = is_known || name == k;
+        for (const char* k : SWITCH_NAMES) is_known = is_known || name == k;
         if (is_known != known) continue;
         if (!out.empty()) out += ' ';
         out += known ? std::string(*e) : name;
@@ -1429,31 +1366,18 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     m->graph_clock = 0; m->graph_captures = 0; m->cap_stream = nullptr;
     m->pk8_c0_head = nullptr; m->pk8_audio_head = nullptr; m->bb.has_pk8 = false; m->dec.has_pk8 = false;
     m->host_frames = 0; m->have_last = false; m->last_S = 1;
-    m->bb_prefetch = 0; m->pf_stream = nullptr;
-    { const char* ev = getenv("CSM_BB_PREFETCH"); if (ev && atoi(ev) > 0) m->bb_prefetch = atoi(ev); }
-    if (m->bb_prefetch > 0) {
-        HIPCHK((CsmModel*)nullptr, hipStreamCreateWithFlags(&m->pf_stream, hipStreamNonBlocking));
-        for (int l = 0; l < cfg->backbone.n_layers; ++l) {
-            HIPCHK((CsmModel*)nullptr, hipEventCreateWithFlags(&m->pf_fork[l], hipEventDisableTiming));
-            HIPCHK((CsmModel*)nullptr, hipEventCreateWithFlags(&m->pf_join[l], hipEventDisableTiming));
-        }
-    }
-    { const char* ev = getenv("CSM_FUSE_DEC_ATTN"); m->fuse_dec_attn = !(ev && ev[0] == '0'); }
-    { const char* ev = getenv("CSM_WIDE"); m->wide_path = !(ev && ev[0] == '0'); }
-    { const char* ev = getenv("CSM_WIDE_MIN"); m->wide_min = ev && atoi(ev) > 0 ? atoi(ev) : WIDE_MIN_ROWS; }
-    { const char* ev = getenv("CSM_FP8_WIDE"); m->fp8_wide = !(ev && ev[0] == '0'); }
-    { const char* ev = getenv("CSM_XPACK"); m->xpack = !(ev && ev[0] == '0'); }
-    { const char* ev = getenv("CSM_XPACK_PROMPT"); m->xpack_prompt = !(ev && ev[0] == '0'); }
+    m->fuse_dec_attn = sw_on(SW_CSM_FUSE_DEC_ATTN);
+    m->wide_path = sw_on(SW_CSM_WIDE);
+    { const int v = sw_int(SW_CSM_WIDE_MIN, 0); m->wide_min = v > 0 ? v : WIDE_MIN_ROWS; }
+    m->fp8_wide = sw_on(SW_CSM_FP8_WIDE);
+    m->xpack = sw_on(SW_CSM_XPACK);
+    m->xpack_prompt = sw_on(SW_CSM_XPACK_PROMPT);
     // Cache policy (measured, tools/microbench/gemv_bench.hip and whole frames): the backbone (1.9 GB, read once per
     // frame) and the heads stream non-temporally so they do not evict the depth decoder, whose 222 MB are re-read on
     // each of its 31 steps and about fit the 256 MB Infinity Cache.  The decoder itself keeps the default policy:
-    // non-temporal MLP loads made the frame slower (4.41 vs 4.24 ms), see CSM_DEC_MLP_NT.
-    {
-        const char* ev = getenv("CSM_DEC_MLP_NT");
-        const int dec_mlp_nt = (ev && ev[0] == '1');   // measured: default policy is faster for the decoder MLP (4.24 vs 4.41 ms/frame)
-        init_stack(m->bb, cfg->backbone, m->w.bb, w->bb_norm, w->bb_rope, cfg->backbone.max_seq, 1, 1);
-        init_stack(m->dec, cfg->decoder, m->w.dec, w->dec_norm, w->dec_rope, cfg->n_codebooks, 0, dec_mlp_nt);
-    }
+    // non-temporal MLP loads made the frame slower (4.41 vs 4.24 ms/frame).
+    init_stack(m->bb, cfg->backbone, m->w.bb, w->bb_norm, w->bb_rope, cfg->backbone.max_seq, 1, 1);
+    init_stack(m->dec, cfg->decoder, m->w.dec, w->dec_norm, w->dec_rope, cfg->n_codebooks, 0, 0);
     const int ncb = cfg->n_codebooks, dbb = cfg->backbone.dim, dd = cfg->decoder.dim;
 #define ALLOC(ptr, bytes) HIPCHK((CsmModel*)nullptr, hipMalloc((void**)&(ptr), (bytes)))   /* on failure the handle is leaked on purpose: the process cannot continue without it */
     m->bb.layer_stride = (long)max_batch * cfg->backbone.n_kv_heads * m->bb.cache_len * m->bb.hd;
@@ -1469,11 +1393,10 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     m->part_rows = max_batch > PART_ROWS ? max_batch : PART_ROWS;
     ALLOC(m->part, (size_t)m->part_rows * cfg->backbone.n_heads * BB_NSPLIT_MAX * ATTN_PS(m->bb.hd) * 4);
     m->attn_ctr = nullptr;
-    { const char* ev = getenv("CSM_ATTN_MERGE");
-      if (!(ev && ev[0] == '0')) {
-          ALLOC(m->attn_ctr, (size_t)m->part_rows * cfg->backbone.n_kv_heads * 4);
-          HIPCHK((CsmModel*)nullptr, hipMemset(m->attn_ctr, 0, (size_t)m->part_rows * cfg->backbone.n_kv_heads * 4));
-      } }
+    if (sw_on(SW_CSM_ATTN_MERGE)) {
+        ALLOC(m->attn_ctr, (size_t)m->part_rows * cfg->backbone.n_kv_heads * 4);
+        HIPCHK((CsmModel*)nullptr, hipMemset(m->attn_ctr, 0, (size_t)m->part_rows * cfg->backbone.n_kv_heads * 4));
+    }
     ALLOC(m->dec_in, (size_t)max_batch * 2 * dbb * 2);
     ALLOC(m->proj_emb, (size_t)ncb * cfg->audio_vocab * dd * 2);
     ALLOC(m->slab, (size_t)8 * max_rows * (dbb > dd ? dbb : dd) * 4);
@@ -1562,25 +1485,18 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     }
     HIPCHK((CsmModel*)nullptr, hipDeviceSynchronize());
     m->qkv0_tab = nullptr;
-    {
-        const char* ev = getenv("CSM_QKV0_TABLE");
-        if (!(ev && ev[0] == '0') && ncb > 2) HIPCHK((CsmModel*)nullptr, build_qkv0_table(m));
-    }
+    if (sw_on(SW_CSM_QKV0_TABLE) && ncb > 2) HIPCHK((CsmModel*)nullptr, build_qkv0_table(m));
     // ---- all-CU launches (persistent depth decoders, one-launch backbone layers): optional fast paths.  Anything that
     //      fails here (shape, device, occupancy, allocation) leaves the flag off and the launch chain in charge.
     m->persist = false; m->persist_m = false; m->dec_first = false; m->p_stamps = nullptr; m->bb_block = false; m->bb_layer = false; m->persist_disabled = false; m->bb_disabled = false;
     // the B = 1 launches' small exchange buffers (granule replicas: 18..96 KB each) come from ONE 2 MB-aligned slab at 4 KB steps instead of
     // wherever hipMalloc's sub-allocator has room -- same placement in every process (A/B: k_bb_layer 32.2..32.8 -> 31.9 us before the
-    // scalar-load fix, within the noise after it; kept for the determinism).  CSM_XSLAB=0: separate allocations.
+    // scalar-load fix, within the noise after it; kept for the determinism).  Separate allocations where the slab cannot be had or overflows.
     m->xslab = nullptr; m->xslab_used = 0; m->xslab_align = 4096;
-    {
-        const char* ev = getenv("CSM_XSLAB");
-        const bool want = !(ev && ev[0] == '0');
-        if (want && (hipMalloc((void**)&m->xslab, XSLAB_BYTES) != hipSuccess || hipMemset(m->xslab, 0, XSLAB_BYTES) != hipSuccess)) {
-            (void)hipGetLastError();
-            if (m->xslab) (void)hipFree(m->xslab);
-            m->xslab = nullptr;
-        }
+    if (hipMalloc((void**)&m->xslab, XSLAB_BYTES) != hipSuccess || hipMemset(m->xslab, 0, XSLAB_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        if (m->xslab) (void)hipFree(m->xslab);
+        m->xslab = nullptr;
     }
     setup_persist(m);
     setup_bb_block(m);
@@ -1591,10 +1507,6 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
 extern "C" void csm_destroy(csm_handle m) {
     if (!m) return;
     drop_frame_graphs(m);
-    if (m->pf_stream) {
-        for (int l = 0; l < m->cfg.backbone.n_layers; ++l) { (void)hipEventDestroy(m->pf_fork[l]); (void)hipEventDestroy(m->pf_join[l]); }
-        (void)hipStreamDestroy(m->pf_stream);
-    }
     if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
     for (CsmPrefix* p : m->prefixes) { (void)hipFree(p->data); p->data = nullptr; p->owner = nullptr; }      // (the caller still destroys the objects)
     void* ptrs[] = {m->bb.kc, m->bb.vc, m->dec.kc, m->dec.vc, m->h, m->q, m->att, m->act, m->part, m->attn_ctr, m->dec_in, m->proj_emb, m->slab,
@@ -2280,7 +2192,7 @@ extern "C" int csm_read_frames(csm_handle m, int B, int first, int n, int32_t* h
         char buf[256];
         snprintf(buf, sizeof buf, "%s launch gave up waiting (code 0x%x): frames since the last reset are invalid (-1); this handle now runs the launch chain "
                  "(call csm_reset and generate again)", bcode ? "backbone one-launch layer" : "persistent depth-decoder", bcode ? bcode : pcode);
-        if (getenv("CSM_KEEP_FAST_PATHS") == nullptr) {       // (the fault-injection test keeps them to check that the SAME path recovers)
+        if (!sw_set(SW_CSM_KEEP_FAST_PATHS)) {       // (the fault-injection test keeps them to check that the SAME path recovers)
             m->persist_disabled = m->persist_disabled || pcode != 0; m->bb_disabled = m->bb_disabled || bcode != 0;
             drop_frame_graphs(m);
         }
@@ -2499,7 +2411,7 @@ extern "C" int csm_op_attn(int M, int rows_per_seq, int H, int KV, int head_dim,
     if (nsplit < 1) {
         if (head_dim != 64 || H % KV != 0 || (H / KV) % 4 != 0) return CSM_E_INVALID;
         dim3 grid((M / rows_per_seq) * ((rows_per_seq + 31) / 32), KV);
-        hipLaunchKernelGGL((k_attn_flash<64, AF_NG>), grid, dim3(256 * AF_NG), 0, (hipStream_t)stream, t);
+        hipLaunchKernelGGL((k_attn_flash<64>), grid, dim3(256), 0, (hipStream_t)stream, t);
         e = hipGetLastError();
     } else e = launch_attn(head_dim, t, (hipStream_t)stream);
     if (e != hipSuccess) { g_create_err = std::string("csm_op_attn: ") + hipGetErrorString(e); return CSM_E_HIP; }

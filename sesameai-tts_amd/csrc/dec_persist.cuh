@@ -303,14 +303,13 @@ __device__ __forceinline__ void dp_reduce_partials(const uint32_t (&v)[16], floa
 // stage_attn (gemv.cuh) for one row and ONE head, with q / K / V in LDS (that kernel walks two heads of a KV group
 // per wave; per head the lane layout and the operation order are the same): lane l holds 16-byte pieces of keys
 // 4i + l/16 (i = 0..7) at element offset 8 (l % 16).  Eight waves take one head each.
-// NG = 4-key groups walked (8 = all 32 slots).  Groups beyond the live keys contribute exact zeros, so any NG with 4 NG >= nk gives the same bits
-// (DP_ATTN_GROUPS build: dp_attention_wave picks the smallest of 1 / 2 / 4 / 8 for the step's key count).
-template <int NG = 8>
 __device__ __forceinline__ void dp_attention_head(const dp_lu4* qb, const dp_lu4* kt, const dp_lu32* vt, dp_lf32* myps, dp_lu32* att,
                                                   int h, int nk, float ascale, int lane) {
     // stage_attn skips whole 4-key groups beyond nk by uniform branches; here every group is walked (its LDS reads and
     // DPP chains then overlap instead of running one group after the other) and dead keys contribute exact zeros:
     // score -inf -> p = 0, v read as 0 -> "+ 0.0" leaves every running sum's bits unchanged.
+    // (walking only the groups that hold live keys measured no effect: profiles/r06/attn_groups_ab.txt)
+    constexpr int NG = 8;                                    // 4-key groups: all 32 key slots
     const int grp = lane >> 4, sub = lane & 15;
     const uint4 qa = dp_ldq(qb + h * 16 + sub);
     uint4 kv[NG];
@@ -357,14 +356,7 @@ __device__ __forceinline__ void dp_attention_wave(char* lds, int wave, int l, in
     const dp_lu32* vt = (const dp_lu32*)(lds + DP_OFF_V + ((l * 2 + kvh) * 32) * 256);
     dp_lf32* ps = (dp_lf32*)(lds + DP_OFF_PS) + wave * 32;
     dp_lu32* att = (dp_lu32*)(lds + DP_OFF_ATT);
-#ifdef DP_ATTN_GROUPS
-    // the step's cb + 1 live keys sit in the first ceil((cb + 1) / 4) groups: walk 1 / 2 / 4 / 8 of them (uniform branch; same bits, see dp_attention_head)
-    if (cb < 4) dp_attention_head<1>(qb, kt, vt, ps, att, wave, cb + 1, 0.08838834764831845f, lane);
-    else if (cb < 8) dp_attention_head<2>(qb, kt, vt, ps, att, wave, cb + 1, 0.08838834764831845f, lane);
-    else if (cb < 16) dp_attention_head<4>(qb, kt, vt, ps, att, wave, cb + 1, 0.08838834764831845f, lane);
-    else
-#endif
-    dp_attention_head<8>(qb, kt, vt, ps, att, wave, cb + 1, 0.08838834764831845f, lane);
+    dp_attention_head(qb, kt, vt, ps, att, wave, cb + 1, 0.08838834764831845f, lane);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) __hip_atomic_fetch_add(misc + DP_M_ATTN, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -437,20 +429,17 @@ __device__ __forceinline__ int dp_sample_step(const DecPersistArgs& a, char* lds
 
 typedef __attribute__((ext_vector_type(8))) __bf16 dp_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float dp_f32x4;
-// Two instantiations only -- <true, 2>: waves 0..3 (a gate/up tile + 2 row blocks), <false, 3>: waves 4..6 (3 row blocks, the
-// sampler) -- with the small-op role a RUNTIME property of the wave (the kernel is instruction-cache bound: five instantiations were
-// 131 KB of code, and sharing one between waves 5 and 6 alone was worth 1.3 % of the frame).  So that hipcc's wait counts stay exact
-// every wave of an instantiation issues the SAME sequence of loads: a role that has no use for a load of the sequence re-reads an
-// address it reads anyway (cache hit, no HBM bytes).
+// Four instantiations -- <true, 2, .>: waves 0..3 (a gate/up tile + 2 row blocks), <false, 3, .>: waves 4..6 (3 row blocks, the
+// sampler) -- one per small-op role (the kernel is instruction-cache bound: five instantiations were 131 KB of code, and sharing one
+// between waves 5 and 6 alone was worth 1.3 % of the frame; fewer, with the role read from the wave index at run time, measured equal
+// or slower: docs/experiments/r02.md, r03.md).  So that hipcc's wait counts stay exact every wave of an instantiation issues the SAME
+// sequence of loads: a role that has no use for a load of the sequence re-reads an address it reads anyway (cache hit, no HBM bytes).
 //   role X (waves 0, 1): no small op;  A (2, 3, 4): q|k|v unit, rows in wsa;  B (5, 6): o-proj unit, rows in wsb.
-#ifndef DP_ROLES
-#define DP_ROLES 4              // instantiations of the compute wave: 4 = every role its own (measured best), 3 / 2 = roles by wave index at run time
-#endif
-template <bool HAS_TILE, int NBK, int TROLE>      // TROLE (tile waves): 0 = role by wave index at run time, 1 = X only, 2 = A only
+template <bool HAS_TILE, int NBK, int TROLE>      // TROLE: the first (1) or second (2) role of the instantiation's waves -- tile waves X / A, the others A / B
 __device__ __forceinline__ void dp_compute_wave(const DecPersistArgs& a, char* lds, const int wave, const unsigned lane, const int cu, const uint32_t base,
                                                 const uint32_t ropev) {
     constexpr bool HAS_B = !HAS_TILE;                 // the instantiation carries o-proj waves
-    const bool is_x = HAS_TILE && (TROLE == 1 || (TROLE == 0 && wave < 2)), is_a = HAS_TILE ? !is_x : (TROLE == 1 || (TROLE == 0 && wave == 4)), is_b = HAS_B && !is_a;
+    const bool is_x = HAS_TILE && TROLE == 1, is_a = HAS_TILE ? TROLE == 2 : TROLE == 1, is_b = HAS_B && !is_a;
     constexpr int NT = HAS_TILE ? 32 : 0, NCD = NT + NBK * 4, N1 = NCD / 3;
     dp_lu32* misc = (dp_lu32*)(lds + DP_OFF_MISC);
     dp_lvu32* ab = (dp_lvu32*)(misc + DP_M_ABORT);
@@ -819,19 +808,10 @@ static __global__ __launch_bounds__(512) void k_dec_persist(const DecPersistArgs
         if (cu == 0 && lane == 0) __hip_atomic_store(a.epoch, base + (uint32_t)(n_steps * DP_NL * 5 + 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-#if DP_ROLES == 4
     if (wave < 2) dp_compute_wave<true, 2, 1>(a, lds, wave, lane, cu, base, ropev);
     else if (wave < 4) dp_compute_wave<true, 2, 2>(a, lds, wave, lane, cu, base, ropev);
     else if (wave == 4) dp_compute_wave<false, 3, 1>(a, lds, wave, lane, cu, base, ropev);
     else dp_compute_wave<false, 3, 2>(a, lds, wave, lane, cu, base, ropev);
-#elif DP_ROLES == 3
-    if (wave < 2) dp_compute_wave<true, 2, 1>(a, lds, wave, lane, cu, base, ropev);
-    else if (wave < 4) dp_compute_wave<true, 2, 2>(a, lds, wave, lane, cu, base, ropev);
-    else dp_compute_wave<false, 3, 0>(a, lds, wave, lane, cu, base, ropev);
-#else
-    if (wave < 4) dp_compute_wave<true, 2, 0>(a, lds, wave, lane, cu, base, ropev);
-    else dp_compute_wave<false, 3, 0>(a, lds, wave, lane, cu, base, ropev);
-#endif
 }
 #endif
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/mimi_hip.h"
+#include "switches.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 static thread_local std::string g_mimi_err;
@@ -545,8 +546,7 @@ extern "C" int mimi_create(const MimiConfig* cfg, const MimiWeights* w, int max_
     A4(m->ffn, T2 * (cfg->tr_ffn > cfg->codebook_size ? cfg->tr_ffn : cfg->codebook_size));   // also the RVQ score buffer
     A4(m->kc, (long)cfg->tr_layers * m->cap_tokens * d); A4(m->vc, (long)cfg->tr_layers * m->cap_tokens * d);
     {   // K-split workspace (k_gemm32): the deep products' partial tiles and tile tickets.  MIMI_KSPLIT=0 in the environment: no split.
-        const char* ev = getenv("MIMI_KSPLIT");
-        const int want = ev ? atoi(ev) : MIMI_KSPLIT;
+        const int want = sw_int(SW_MIMI_KSPLIT, MIMI_KSPLIT);
         if (want == 2 || want == 4 || want == 8) {
             m->ksw.ksplit = want;
             const int ccap = cfg->n_filters << cfg->n_stages;                         // widest output of a split product (conv_in); >= hidden
@@ -727,7 +727,7 @@ static int decode_back(MimiDecoder* m, int T, float* pcm, hipStream_t st) {
 
 // chunk sizes whose middle is worth a graph (a streaming chunk is 10 frames, the last one of an utterance 1..9): captured at the
 // SECOND stateless decode of a T, replayed from then on.  Longer decodes (whole utterances, a different T every time) stay eager.
-static const int MIMI_GRAPH_MAX_T = getenv("MIMI_GRAPH_MAX_T") ? atoi(getenv("MIMI_GRAPH_MAX_T")) : 32;
+static const int MIMI_GRAPH_MAX_T = sw_int(SW_MIMI_GRAPH_MAX_T, 32);
 
 static int decode_one(MimiDecoder* m, const int32_t* codes, long stride_k, long stride_t, int T, float* pcm, hipStream_t st, bool stateless) {
     int rc = decode_front(m, codes, stride_k, stride_t, T, st);
@@ -1022,8 +1022,7 @@ static int pool_alloc(MimiStreamPool* p) {
     A4(p->kc, kv); A4(p->vc, kv);
     A4(p->tab, 2 * MIMI_POOL_MAX_STREAMS);
     {   // K-split workspace as in mimi_create (same switch, same shapes split: the sums are those of a single handle), sized for a full call
-        const char* ev = getenv("MIMI_KSPLIT");
-        const int want = ev ? atoi(ev) : MIMI_KSPLIT;
+        const int want = sw_int(SW_MIMI_KSPLIT, MIMI_KSPLIT);
         if (want == 2 || want == 4 || want == 8) {
             const int ccap = c.n_filters << c.n_stages;
             p->ksw.ksplit = want; p->ksw.cap_rows = M2; p->ksw.cap_cols = ccap > d ? ccap : d;
