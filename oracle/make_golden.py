@@ -34,6 +34,12 @@ Files (all torch.save'd dicts of small tensors):
                     1334-row prompt (copy layer 3, lag 700: a key in the middle of the split key range) and at B = 32; bf16 and
                     fp8-dequantised; margin >= 4 x gap on every row, the implied trajectory asserted, and KV faults injected into the
                     oracle (stale rows, a wrong RoPE position, a dropped key range, zeroed prompt rows) asserted to CHANGE the codes.
+  csm1b_decisive_dcopy.pt / tiny_decisive_dcopy.pt   (--only dcopy; dcopytiny / dcopyfull: one of the two)
+                    the DECODER-side copy checkpoint (oracle.csm_ref.decisive_dcopy_variant: step p of a frame names the code `lag` decoder
+                    positions back, read through one decoder layer's cached K / V): 8 free-running frames at B = 1, 4 of a batch whose
+                    utterances have last text tokens of their own, the twelve utterances of the refilled batch; per-row margins and gaps,
+                    checksums of every tensor; KV faults in that decoder layer asserted to CHANGE the codes, the same faults in another
+                    decoder layer, in the backbone, and on the two flavours above asserted to change nothing.
   csm1b_possweep.pt CSM-1B bench checkpoint, ONE 2046-row prompt cut at S in POSSWEEP_S: for every S the prompt frame and two teacher-forced
                     steps at positions S and S + 1 (top-8 logits, codes, margins, the bf16-vs-fp32 gap), bf16 and fp8-dequantised; plus 64
                     CONSECUTIVE teacher-forced steps after a 740-row prompt (positions 740..803: across the one-launch backbone layer's
@@ -161,7 +167,7 @@ def frames_golden_batch(shape: C.CsmShape, weights, toks, msks, n_frames: int):
 
 
 @torch.inference_mode()
-def free_run(shape: C.CsmShape, weights, toks, msks, n_frames: int, what: str):
+def free_run(shape: C.CsmShape, weights, toks, msks, n_frames: int, what: str, keep_rows: bool = False):
     """The oracle's FREE-RUNNING greedy loop (generator.py:283-294 with topk = 1) on B equal-length prompts, beside an fp32 oracle that is
     fed the bf16 oracle's codes: codes [n][B][32], the smallest top-1 / top-2 margin and the largest bf16-vs-fp32 logit gap per frame.
     Asserts what the decisive checkpoint is for: every decision's margin >= 4 x the gap, and the trajectory the construction implies."""
@@ -172,7 +178,7 @@ def free_run(shape: C.CsmShape, weights, toks, msks, n_frames: int, what: str):
     m32 = C.OracleModel(shape, {k: v.float() for k, v in weights.items()}, dtype=torch.float32); m32.setup_caches(B)
     cur_t, cur_m = toks.long(), msks
     pos = torch.arange(toks.size(1)).unsqueeze(0).repeat(B, 1)
-    codes, margins, gaps = [], [], []
+    codes, margins, gaps, rows = [], [], [], []
     t0 = time.time()
     for f in range(n_frames):
         tr, tr32 = C.FrameTrace(), C.FrameTrace()
@@ -183,14 +189,17 @@ def free_run(shape: C.CsmShape, weights, toks, msks, n_frames: int, what: str):
         margin, gap = (top2[..., 0] - top2[..., 1]), (lg - lg32).abs().amax(dim=-1)
         assert bool((margin >= 4.0 * gap.max()).all()), f"{what} frame {f}: margin {float(margin.min()):.3f} < 4 x gap {float(gap.max()):.4f}"
         assert not bool((s == 0).all(dim=1).any()), "an all-zero (EOS) frame"
-        codes.append(s.clone()); margins.append(margin.min()); gaps.append(gap.max())
+        codes.append(s.clone()); margins.append(margin.min()); gaps.append(gap.max()); rows.append((margin, gap))
         cur_t = torch.cat([s.long(), torch.zeros(B, 1).long()], dim=1).unsqueeze(1)
         cur_m = torch.cat([torch.ones_like(s).bool(), torch.zeros(B, 1).bool()], dim=1).unsqueeze(1)
         pos = pos[:, -1:] + 1
     codes = torch.stack(codes)
     print(f"  {what}: {n_frames} frames x {B} in {time.time() - t0:.0f}s, smallest margin {float(min(margins)):.3f}, largest gap "
           f"{float(max(gaps)):.4f} ({float(min(margins)) / float(max(gaps)):.0f} x)", flush=True)
-    return dict(codes=codes.to(torch.int16), min_margin=torch.stack(margins), max_gap=torch.stack(gaps))
+    out = dict(codes=codes.to(torch.int16), min_margin=torch.stack(margins), max_gap=torch.stack(gaps))
+    if keep_rows:           # per (frame, codebook, utterance)
+        out["margin"], out["gap"] = torch.stack([r[0] for r in rows]), torch.stack([r[1] for r in rows])
+    return out
 
 
 def decisive_many_prompts(shape: C.CsmShape):
@@ -328,6 +337,158 @@ def decisive_copy_golden(shape: C.CsmShape, seed: int, full: bool):
                 gold[f"{tag}_{name}"] = g
         del w
     gold["weight_checksums"] = sums
+    return gold
+
+
+# ---- the decoder-side copy checkpoint -----------------------------------------------------------------------------------------------
+DCOPY = dict(
+    full=dict(variants=("decisive_dcopy:0:1", "decisive_dcopy:3:2", "decisive_dcopy:1:7"), fp8=("decisive_dcopy:3:2",),
+              batched=("decisive_dcopy:0:1", "decisive_dcopy:1:7"), many=("decisive_dcopy:0:1",), batch=32, cross_frames=2),
+    tiny=dict(variants=("decisive_dcopy:0:1", "decisive_dcopy:1:3"), fp8=(), batched=("decisive_dcopy:0:1", "decisive_dcopy:1:3"), many=(),
+              batch=5, cross_frames=4),
+    frames=8, frames_batched=4)
+
+
+def dcopy_prompts(shape: C.CsmShape, full: bool):
+    """(the B = 1 prompt, the batch's prompts): config 2's 190-row prompt and config 3's 32, or their toy counterparts.  In the batch the
+    last text token of utterance b is 5000 + b (tiny: 500 + b): frame 0's first code follows from that token alone, and two of 32 seeded
+    tokens name the same code one time in four -- those two utterances would then run the same trajectory."""
+    if full:
+        one, batch, t0 = bench_prompt(shape, 2025), [bench_prompt(shape, 2025 + b) for b in range(DCOPY["full"]["batch"])], 5000
+    else:
+        one, batch, t0 = toy_prompt(shape, 11, 6, 5), [toy_prompt(shape, 100 + b, 6, 5) for b in range(DCOPY["tiny"]["batch"])], 500
+    for b, (tok, _) in enumerate(batch):
+        tok[-1, 32] = t0 + b
+    return one, batch
+
+
+def dcopy_many_prompts(shape: C.CsmShape):
+    """decisive_many_prompts' twelve prompts with limits of 3..7 frames: every frame is 31 decoder steps on a cache that starts empty."""
+    return [(p, 3 + (7 * i) % 5) for i, (p, _) in enumerate(decisive_many_prompts(shape))]
+
+
+def dcopy_decoder_faults(shape: C.CsmShape, lag: int):
+    """The KV faults of oracle.csm_ref.KV_FAULT for the decoder's cache: `zero_prompt` zeroes what the 2-row first call (positions 0, 1)
+    wrote, `drop_keys` hides the positions that are copied from (p - lag for p = lag + 1 .. 31)."""
+    return [{"kind": "stale"}, {"kind": "shift_rope", "delta": 1}, {"kind": "shift_rope", "delta": -1}, {"kind": "shift_write", "delta": -1},
+            {"kind": "zero_prompt"}, {"kind": "drop_keys", "lo": 1, "hi": shape.audio_num_codebooks - lag}]
+
+
+def dcopy_backbone_faults(rows: int, n: int):
+    return [{"kind": "stale"}, {"kind": "shift_rope", "delta": 1}, {"kind": "shift_write", "delta": -1}, {"kind": "zero_prompt"},
+            {"kind": "drop_keys", "lo": rows - 4, "hi": rows + n}]
+
+
+def fault_name(fault: dict) -> str:
+    return fault["kind"] + (f"{fault['delta']:+d}" if "delta" in fault else "")
+
+
+@torch.inference_mode()
+def faulted_frames(model: C.OracleModel, shape: C.CsmShape, tok, msk, want, stack: str, layer: int, faults) -> torch.Tensor:
+    """Per fault: how many of the first len(want) free-running frames leave `want` with that fault in (stack, layer)."""
+    n = want.shape[0]
+    changed = []
+    try:
+        for fault in faults:
+            C.KV_FAULT = dict(fault, stack=stack, layer=layer)
+            got = torch.cat(C.generate_codes(model, tok, msk, n * 80, 1.0, 1, greedy=True, max_seq_len=shape.backbone.max_seq_len))
+            changed.append(int((got != want).any(dim=1).sum()) if got.shape == want.shape else n)
+    finally:
+        C.KV_FAULT = None
+    return torch.tensor(changed)
+
+
+def dcopy_fault_matrix(shape: C.CsmShape, weights, flavour: str, tok, msk, want, backbone: bool = True):
+    """What the flavour is for, asserted on the oracle: every KV fault in the copy layer of the DECODER changes the free-running codes;
+    the same faults in another decoder layer, and KV faults in a backbone layer, change nothing."""
+    layer, lag = C.dcopy_flavour_params(shape, flavour)
+    other = (layer + 1) % shape.decoder.num_layers
+    faults = dcopy_decoder_faults(shape, lag)
+    m = C.OracleModel(shape, weights); m.setup_caches(1)
+    assert torch.equal(faulted_frames(m, shape, tok, msk, want, "decoder", layer, [{"kind": "none"}]), torch.tensor([0]))
+    out = dict(kinds=[fault_name(f) for f in faults], other_layer=other,
+               faults_changed=faulted_frames(m, shape, tok, msk, want, "decoder", layer, faults),
+               other_layer_changed=faulted_frames(m, shape, tok, msk, want, "decoder", other, faults))
+    assert bool((out["faults_changed"] > 0).all()), f"{flavour}: a fault in the copy layer's cache leaves the codes alone: {out}"
+    assert not bool(out["other_layer_changed"].any()), f"{flavour}: a fault in decoder layer {other} moves the codes: {out}"
+    if backbone:
+        bb = shape.backbone.num_layers // 2
+        out["backbone_layer"] = bb
+        out["backbone_changed"] = faulted_frames(m, shape, tok, msk, want, "backbone", bb, dcopy_backbone_faults(tok.shape[0], want.shape[0]))
+        assert not bool(out["backbone_changed"].any()), f"{flavour}: a backbone KV fault moves the codes: {out}"
+    print(f"  {flavour}: decoder KV faults {out['kinds']} change {out['faults_changed'].tolist()} of {want.shape[0]} frames in layer {layer}, "
+          f"{out['other_layer_changed'].tolist()} in layer {other}" + (f"; backbone faults {out['backbone_changed'].tolist()}" if backbone else ""), flush=True)
+    return out
+
+
+def dcopy_cross_check(shape: C.CsmShape, seed: int, tok, msk, n: int, decoder_layers):
+    """The gap this flavour closes: the decoder faults leave the free-running codes of `decisive` and `decisive_copy` as they are."""
+    out = {}
+    for flavour in ("decisive", "decisive_copy"):
+        w = C.make_weights(shape, seed=seed, flavour=flavour)
+        m = C.OracleModel(shape, w); m.setup_caches(1)
+        want = torch.cat(C.generate_codes(m, tok, msk, n * 80, 1.0, 1, greedy=True, max_seq_len=shape.backbone.max_seq_len))
+        assert want.shape[0] == n
+        changed = torch.stack([faulted_frames(m, shape, tok, msk, want, "decoder", layer, dcopy_decoder_faults(shape, 2)) for layer in decoder_layers])
+        assert not bool(changed.any()), f"{flavour} sees a decoder KV fault: {changed.tolist()}"
+        out[flavour] = dict(decoder_layers=list(decoder_layers), changed=changed)
+        print(f"  {flavour}: decoder KV faults in layers {list(decoder_layers)} change {changed.tolist()} of {n} frames", flush=True)
+        del w, m
+    return out
+
+
+def weight_checksums(w):
+    names = sorted(w)
+    return names, torch.stack([w[k].view(torch.int16).to(torch.int64).sum() for k in names])       # exact, order-free
+
+
+def dcopy_expected(shape: C.CsmShape, seed: int, tok, n: int, lag: int) -> torch.Tensor:
+    return C.decisive_dcopy_expected_codes(shape, seed, int(tok[-1, 32]), n, lag)
+
+
+def decisive_dcopy_golden(shape: C.CsmShape, seed: int, full: bool, path: str):
+    """Writes `path` after every variant (the CSM-1B oracle runs take a quarter of an hour on 8 CPU threads)."""
+    cfg = DCOPY["full" if full else "tiny"]
+    n1, nb = DCOPY["frames"], DCOPY["frames_batched"]
+    (tok, msk), batch = dcopy_prompts(shape, full)
+    btok, bmsk = torch.stack([p[0] for p in batch]), torch.stack([p[1] for p in batch])
+    gold = dict(weight_seed=seed, variants=[], prompt_rows=tok.shape[0], weight_checksums={}, runs={})
+    layers = sorted({C.dcopy_flavour_params(shape, f)[0] for f in cfg["variants"]}) if not full else [shape.decoder.num_layers - 1]
+    gold["cross"] = dcopy_cross_check(shape, seed, tok, msk, cfg["cross_frames"], layers)
+    w = C.make_weights(shape, seed=seed)
+    base = C.decisive_dcopy_base(shape, w, seed)
+    for flavour in cfg["variants"]:
+        layer, lag = C.dcopy_flavour_params(shape, flavour)
+        wts = C.decisive_dcopy_variant(shape, base, w, seed, layer, lag)
+        gold["weight_checksums"][flavour] = weight_checksums(wts)
+        runs = {}
+        for tag in ("bf16",) + (("fp8",) if flavour in cfg["fp8"] else ()):
+            wt = wts if tag == "bf16" else C.fp8_dequantized(wts)
+            g = free_run(shape, wt, tok, msk, n1, f"{flavour} {tag} B=1", keep_rows=True)
+            want = dcopy_expected(shape, seed, tok, n1, lag)
+            assert torch.equal(g["codes"][:, 0].to(torch.int32), want), "the oracle left the trajectory the construction implies"
+            g.update(dcopy_fault_matrix(shape, wt, flavour, tok, msk, want, backbone=tag == "bf16"))
+            runs[f"{tag}_s190"] = g
+        if flavour in cfg["batched"]:
+            g = free_run(shape, wts, btok, bmsk, nb, f"{flavour} bf16 B={btok.shape[0]}", keep_rows=True)
+            for b in range(btok.shape[0]):
+                assert torch.equal(g["codes"][:, b].to(torch.int32), dcopy_expected(shape, seed, btok[b], nb, lag)), "the batched oracle left the implied trajectory"
+            first = g["codes"][0]
+            assert all(not torch.equal(first[i], first[j]) for i in range(first.shape[0]) for j in range(i)), "two utterances of the batch share a first frame"
+            g["prompt_checksum"] = btok.sum(dim=(1, 2))
+            runs["bf16_b32"] = g
+        if flavour in cfg["many"]:
+            many = []
+            for i, ((t_, m_), lim) in enumerate(dcopy_many_prompts(shape)):
+                g = free_run(shape, wts, t_, m_, lim, f"{flavour} bf16 many[{i}] S={t_.shape[0]}")
+                assert torch.equal(g["codes"][:, 0].to(torch.int32), dcopy_expected(shape, seed, t_, lim, lag))
+                many.append(dict(codes=g["codes"][:, 0].clone(), min_margin=g["min_margin"], max_gap=g["max_gap"]))
+            runs["bf16_many"] = many
+        gold["runs"][flavour] = runs
+        gold["variants"].append(flavour)
+        torch.save(gold, path + ".part")
+        os.replace(path + ".part", path)
+        del wts
     return gold
 
 
@@ -612,6 +773,10 @@ def main():
         torch.save(decisive_copy_golden(C.csm_tiny(), 1234, full=False), os.path.join(OUT, "tiny_decisive_copy.pt"))
     if want("copy"):
         torch.save(decisive_copy_golden(C.csm_1b(), 1234, full=True), os.path.join(OUT, "csm1b_decisive_copy.pt"))
+    if want("dcopy") or a.only == "dcopytiny":      # "dcopytiny" / "dcopyfull": one of the two files alone
+        decisive_dcopy_golden(C.csm_tiny(), 1234, False, os.path.join(OUT, "tiny_decisive_dcopy.pt"))
+    if want("dcopy") or a.only == "dcopyfull":
+        decisive_dcopy_golden(C.csm_1b(), 1234, True, os.path.join(OUT, "csm1b_decisive_dcopy.pt"))
     if a.only == "copyx":
         # more copy layers / lags on the 190-row prompt, added to the existing file: the FIRST layer with lag 1 (layer 0 normalises the embedding
         # sum itself; lag 1 reads the row the immediately preceding frame step appended -- from frame 2 on) and the LAST layer with lag 7 (its

@@ -36,6 +36,23 @@ def _write_blob(path, model, tokens, mask):
             f.write(struct.pack("<q", len(b))); f.write(b)
 
 
+def run_greedy_host(model, tokens, mask, n, blob):
+    """Writes `model` and the prompt to `blob`, runs csm_c_host for n greedy frames in the environment this process has, and returns
+    (frames [n][32] int32, the line after them)."""
+    if not os.path.exists(HOST):
+        r = subprocess.run(["make", "-C", os.path.dirname(HOST)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+    _write_blob(blob, model, tokens, mask)
+    try:
+        r = subprocess.run([HOST, blob, str(n), "1.0", "1"], capture_output=True, text=True, timeout=600)
+    finally:
+        os.unlink(blob)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    # (RCCL may print a version banner on stdout when the host makes its communicator: keep the host's own lines)
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln[:1].isdigit() or ln[:1] == "-" or ln.startswith(("eos_at", "replicas"))]
+    return torch.tensor([[int(x) for x in ln.split()] for ln in lines[:n]], dtype=torch.int32), lines[n]
+
+
 def test_plain_c_host_produces_the_python_hosts_frames(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
