@@ -198,10 +198,13 @@ int csm_prefill_slot(csm_handle h, int slot, const int32_t* tokens, const uint8_
  * batch-1 depth pass (4 ms at 190 rows, > 8 ms at 1,334).  Here the prompt runs a few backbone layers per call between frame
  * steps, in buffers of its own, and the new utterance's frame 0 is sampled BY THE NEXT FRAME STEP, in the batch, from the prompt's
  * last row (an inject node in the frame-step graph; the slot's position stays for that one step and its EOS word restarts).
+ * ONE mechanism with two begin forms: a handle holds at most one pending refill, begun for one slot (csm_refill_begin) or for a group of
+ * slots in one ragged prefill (csm_refill_group_begin, below).  Parking, the frame steps' treatment of parked slots, completion and the
+ * refusals are the same for both; each form is advanced by its own call, and the other form's advance is refused (CSM_E_STATE).
  *   csm_refill_begin:   embeds the prompt rows (tokens [S][33] / mask [S][33] / pos [S], dev; pos must stay valid until the refill
  *                       completes) and parks the slot: until completion its rows of the frame steps are placeholders whose frames
  *                       the caller ignores and its position is HELD at S (however many steps the prompt takes, it never nears
- *                       max_seq).  One refill at a time per handle (CSM_E_STATE otherwise).  Needs csm_refill_supported(h, max_batch).
+ *                       max_seq).  CSM_E_STATE while a refill of either form is pending.  Needs csm_refill_supported(h, max_batch).
  *   csm_refill_advance: runs up to max_layers more backbone layers of the pending prompt.  Returns 1 when the prompt is complete --
  *                       the NEXT csm_frame_step then yields the utterance's frame 0 in that slot's row, at that step's global frame
  *                       index -- 0 while layers remain, < 0 on error.  Call both on the stream that runs the frame steps.
@@ -215,7 +218,7 @@ int csm_refill_supported(csm_handle h, int B);
 int csm_refill_begin(csm_handle h, int slot, const int32_t* tokens, const uint8_t* mask, const int32_t* pos, int S, void* stream);
 int csm_refill_advance(csm_handle h, int max_layers, void* stream);
 
-/* The same for SEVERAL slots at once -- one ragged prefill.  Slots that retire in the same block would otherwise queue behind each other,
+/* The other begin form: SEVERAL slots at once -- one ragged prefill.  Slots that retire in the same block would otherwise queue behind each other,
  * each taking the backbone's whole launch chain for a handful of rows (after a prefix copy a refill is ~40 rows: launch-bound).
  *   csm_refill_group_begin:   n <= 32 segments; segment i is the prompt rows of batch slot slots[i], rows[i] >= 1 of them, and the rows of all
  *                       segments lie back to back in tokens [M][33] / mask [M][33] / pos [M] (dev; M = sum rows[i] <= max_rows; pos gives every
@@ -224,12 +227,13 @@ int csm_refill_advance(csm_handle h, int max_layers, void* stream);
  *                       travels in the kernel arguments, so the call neither copies to the device nor synchronises.  What csm_refill_begin
  *                       does for one slot happens for every listed slot: embedded, parked at its own pos[last row] + 1, sampling-table
  *                       counter rewound.  CSM_E_INVALID (nothing is enqueued) for n outside [1, 32], a slot outside [0, max_batch) or listed
- *                       twice, rows[i] < 1, M > max_rows.  One refill OR one group is in flight per handle: CSM_E_STATE while either is
- *                       pending (csm_refill_begin likewise refuses while a group is).  Needs csm_refill_supported(h, max_batch).
+ *                       twice, rows[i] < 1, M > max_rows.  CSM_E_STATE while a refill of either form is pending.  Needs
+ *                       csm_refill_supported(h, max_batch).
  *   csm_refill_group_advance: up to max_layers more backbone layers over all M rows.  1 when the group is complete -- the NEXT csm_frame_step
  *                       yields frame 0 of all n utterances --, 0 while layers remain, < 0 on error.
- * csm_reset_slots / csm_prefill_slot / csm_prefix_capture / csm_prefix_apply on a slot of a pending group are refused like for the slot of a
- * pending csm_refill_begin.  Every row's K/V and every slot's frame 0 input are the bits the same segments give one after the other through
+ * csm_reset_slots / csm_prefill_slot / csm_prefix_capture / csm_prefix_apply on a slot of the pending refill are refused, whichever form
+ * began it.  The forms differ in the layer launches alone: one slot runs as a batch of one sequence, a group (also of one) through the
+ * ragged kernels.  Every row's K/V and every slot's frame 0 input are the bits the same segments give one after the other through
  * csm_refill_begin / csm_refill_advance (a group of n = 1 included).                                                            */
 int csm_refill_group_begin(csm_handle h, const int32_t* slots /*host*/, const int32_t* rows /*host*/, int n,
                            const int32_t* tokens /*dev [M][33]*/, const uint8_t* mask /*dev [M][33]*/, const int32_t* pos /*dev [M]*/, void* stream);

@@ -90,13 +90,9 @@ struct CsmModel {
     // steps; its residual stream and the next layer's normalised input live in buffers of their own, everything else is transient
     int* fresh;                         // [max_batch] device flags: the slot's next frame step yields its frame 0 from rf_last
     bf16_t *rf_h, *rf_xn, *rf_last;     // [max_rows][d_bb] x 2, [max_batch][2 d_bb] final-normed last prompt row per slot (dec_in layout)
-    int rf_slot, rf_S, rf_layer;        // pending refill: slot (-1 = none), prompt rows, next layer to run
     std::vector<char> rf_fresh_host;    // [max_batch] host mirror of `fresh` == 1: slots whose completed refill waits for a frame step to sample its
     int rf_fresh_count;                 // frame 0 -- several can wait at once (a generator fills B slots before the first step: ADVICE r5)
-    const int* rf_pos;                  // the caller's position array of the pending refill (dev, valid until the refill completes)
-    // ... or a GROUP of them in one ragged prefill (csm_refill_group_begin / _advance): one refill OR one group is in flight per handle
-    RagSegs rg;                         // pending group: its segment table (rg.n == 0: none); rf_layer / rf_pos serve it too
-    int rg_tiles_n;                     // its 32-row query tiles
+    RefillRec rf;                       // the pending refill, one slot (csm_refill_begin) or a group in one ragged prefill (csm_refill_group_begin): rag_segs.h
     int* rg_row_slot;                   // [max_rows] batch slot of each of the group's rows        } written by k_rag_plan at begin
     int4* rg_tiles;                     // [max_rows / 32 + 32] {slot, first row, rows, -} by walk  }
     int device;                         // the GPU this handle lives on (csm_generate_frame_s1 makes it current itself)
@@ -1008,8 +1004,8 @@ static inline void fresh_clear(CsmModel* m, int slot) {
 }
 static inline void fresh_clear_all(CsmModel* m) { m->rf_fresh_host.assign(m->rf_fresh_host.size(), 0); m->rf_fresh_count = 0; }
 // a refill beside the loop, or a group of them, has begun and not completed / `slot` is (one of) its slot(s)
-static inline bool refill_pending(const CsmModel* m) { return m->rf_slot >= 0 || m->rg.n > 0; }
-static inline bool slot_refilling(const CsmModel* m, int slot) { return (m->rf_slot >= 0 && slot == m->rf_slot) || rag_segs_has_slot(m->rg, slot); }
+static inline bool refill_pending(const CsmModel* m) { return refill_pending(m->rf); }
+static inline bool slot_refilling(const CsmModel* m, int slot) { return refill_has_slot(m->rf, slot); }
 static inline bool refill_beside_ok(const CsmModel* m, int B) { return m->wide_path && B >= m->wide_min && B <= m->max_batch; }
 static inline bool frame_injects(const CsmModel* m, int B) { return m->rf_last != nullptr && refill_beside_ok(m, B); }
 
@@ -1421,7 +1417,7 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     m->slot_tab_used = false; m->slot_tab_host.assign((size_t)max_batch, 0);
     ALLOC(m->fresh, (size_t)max_batch * 4);
     HIPCHK((CsmModel*)nullptr, hipMemset(m->fresh, 0, (size_t)max_batch * 4));
-    m->rf_h = m->rf_xn = m->rf_last = nullptr; m->rg.n = 0; m->rg_tiles_n = 0; m->rg_row_slot = nullptr; m->rg_tiles = nullptr; m->rf_slot = -1; m->rf_S = 0; m->rf_layer = 0; m->rf_pos = nullptr;
+    m->rf_h = m->rf_xn = m->rf_last = nullptr; m->rg_row_slot = nullptr; m->rg_tiles = nullptr; refill_clear(m->rf);
     m->rf_fresh_host.assign((size_t)max_batch, 0); m->rf_fresh_count = 0;
     ALLOC(m->dec_pos, (size_t)(ncb + 1) * 2 * max_batch * 4);
     ALLOC(m->slot_scratch, (size_t)max_batch * 4);
@@ -1578,7 +1574,7 @@ extern "C" int csm_reset(csm_handle m, void* stream) {
         HIPCHK(m, hipMemsetAsync(m->slot_tab, 0, (size_t)m->max_batch * sizeof(SlotSampling), st));
         m->slot_tab_host.assign(m->slot_tab_host.size(), 0);
     }
-    m->host_frames = 0; m->have_last = false; m->rf_slot = -1; m->rg.n = 0; fresh_clear_all(m);
+    m->host_frames = 0; m->have_last = false; refill_clear(m->rf); fresh_clear_all(m);
     return CSM_OK;
 }
 
@@ -1941,53 +1937,11 @@ static int refill_buffers(CsmModel* m, hipStream_t st) {
     return CSM_OK;
 }
 
-extern "C" int csm_refill_begin(csm_handle m, int slot, const int32_t* tokens, const uint8_t* mask, const int32_t* pos, int S, void* stream) {
-    if (!m || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_refill_begin: null argument");
-    if (slot < 0 || slot >= m->max_batch || S < 1 || S > m->max_rows) return fail(m, CSM_E_INVALID, "csm_refill_begin: slot / S outside the limits given to csm_create");
-    if (m->rf_slot >= 0) return fail(m, CSM_E_STATE, "csm_refill_begin: a refill is already in progress (finish it with csm_refill_advance)");
-    if (m->rg.n > 0) return fail(m, CSM_E_STATE, "csm_refill_begin: a refill group is in progress (finish it with csm_refill_group_advance)");
-    if (!refill_beside_ok(m, m->max_batch)) return fail(m, CSM_E_STATE, "csm_refill_begin: needs the matrix-core decode path (csm_refill_supported); use csm_prefill_slot");
-    hipStream_t st = (hipStream_t)stream;
-    { const int rc = refill_buffers(m, st); if (rc != CSM_OK) return rc; }
-    HIPCHK(m, launch_embed(m, tokens, mask, S, st, m->rf_h));
-    // parked: until the prompt is complete the slot's row of the frame steps is a placeholder at positions >= S (its K/V land beyond the prompt's)
-    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1,
-                       m->slot_tab_used ? m->slot_tab + slot : nullptr);
-    // ... and the frame steps HOLD it there (flag 2 = parked: k_advance neither advances it nor tests it against max_seq), however many
-    // steps the prompt's layers take
-    hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(64), 0, st, m->fresh + slot, 2, 1);
-    HIPCHK(m, hipGetLastError());
-    fresh_clear(m, slot);
-    m->rf_slot = slot; m->rf_S = S; m->rf_layer = 0; m->rf_pos = pos;
-    return CSM_OK;
-}
-
-extern "C" int csm_refill_advance(csm_handle m, int max_layers, void* stream) {
-    if (!m || max_layers < 1) return fail(m, CSM_E_INVALID, "csm_refill_advance: bad argument");
-    if (m->rf_slot < 0) return fail(m, CSM_E_STATE, "csm_refill_advance: no refill in progress");
-    hipStream_t st = (hipStream_t)stream;
-    const int L = m->cfg.backbone.n_layers, dbb = m->cfg.backbone.dim, slot = m->rf_slot, S = m->rf_S;
-    const int l0 = m->rf_layer, l1 = l0 + max_layers < L ? l0 + max_layers : L;
-    m->bb.slot_off = (long)slot * m->cfg.backbone.n_kv_heads * m->bb.cache_len * m->bb.hd;
-    hipError_t e = run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, S, S, m->rf_pos, -1, st, true, false, false, l0, l1, m->rf_last + (long)slot * 2 * dbb);
-    m->bb.slot_off = 0;
-    HIPCHK(m, e);
-    m->rf_layer = l1;
-    if (l1 < L) return 0;
-    // complete: position = prompt length again (the placeholder rows drifted beyond it), flag up -- the next frame step samples frame 0
-    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, m->rf_pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1, (SlotSampling*)nullptr);
-    hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(64), 0, st, m->fresh + slot, 1, 1);
-    HIPCHK(m, hipGetLastError());
-    m->rf_slot = -1; m->rf_pos = nullptr;
-    if (!m->rf_fresh_host[(size_t)slot]) { m->rf_fresh_host[(size_t)slot] = 1; m->rf_fresh_count += 1; }
-    return 1;
-}
-
-// ---------------------------------------------------------------------------------------
-// ... for SEVERAL slots at once: one ragged prefill whose rows are the prompts (or the suffixes after a copied prefix) of up to 32 slots, back
-// to back, each with its own length and start position.  Slots that retire in the same block share ONE launch chain per layer instead
-// of queueing behind each other with a handful of rows each.  Prompt rows keep their bits whatever shares their call.
-// ---------------------------------------------------------------------------------------
+// One slot (csm_refill_begin), or SEVERAL at once (csm_refill_group_begin): one ragged prefill whose rows are the prompts (or the suffixes
+// after a copied prefix) of up to 32 slots, back to back, each with its own length and start position.  Slots that retire in the same
+// block share ONE launch chain per layer instead of queueing behind each other with a handful of rows each.  Prompt rows keep their bits
+// whatever shares their call.  Both forms are ONE pending record (m->rf); `ragged` only chooses an advance's layer launches.
+//
 // every listed slot's position = one past its segment's last row; its flag; (optionally) its sampling-table counter rewound
 __global__ void k_rag_set_state(const RagSegs sg, const int* pos, int M, int* cur_pos, int max_batch, int max_seq, int* overflow, SlotSampling* slot_tab,
                                 int* fresh, int flag) {
@@ -2002,57 +1956,94 @@ __global__ void k_rag_set_state(const RagSegs sg, const int* pos, int M, int* cu
         if (pos[i] < 0 || pos[i] >= max_seq) *overflow = 1;
 }
 
-extern "C" int csm_refill_group_begin(csm_handle m, const int32_t* slots, const int32_t* rows, int n, const int32_t* tokens, const uint8_t* mask,
-                                      const int32_t* pos, void* stream) {
-    if (!m || !slots || !rows || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_refill_group_begin: null argument");
-    RagSegs sg;
-    int tiles = 0;
-    if (const char* why = rag_segs_build(slots, rows, n, m->max_batch, m->max_rows, &sg, &tiles)) {
-        const std::string msg = std::string("csm_refill_group_begin: ") + why;
-        return fail(m, CSM_E_INVALID, msg.c_str());
-    }
-    if (m->rf_slot >= 0) return fail(m, CSM_E_STATE, "csm_refill_group_begin: a refill is in progress (finish it with csm_refill_advance)");
-    if (m->rg.n > 0) return fail(m, CSM_E_STATE, "csm_refill_group_begin: a refill group is already in progress (finish it with csm_refill_group_advance)");
-    if (!refill_beside_ok(m, m->max_batch)) return fail(m, CSM_E_STATE, "csm_refill_group_begin: needs the matrix-core decode path (csm_refill_supported); use csm_prefill_slot");
-    hipStream_t st = (hipStream_t)stream;
+static int refill_refused(CsmModel* m, int code, const char* who, const char* why) {
+    const std::string msg = std::string(who) + ": " + why;
+    return fail(m, code, msg.c_str());
+}
+
+static int refill_begin(CsmModel* m, const char* who, const RagSegs& sg, int tiles, bool ragged, const int32_t* tokens, const uint8_t* mask,
+                        const int32_t* pos, hipStream_t st) {
+    if (refill_pending(m))
+        return refill_refused(m, CSM_E_STATE, who, m->rf.ragged ? "a refill group is in progress (finish it with csm_refill_group_advance)"
+                                                                : "a refill is in progress (finish it with csm_refill_advance)");
+    if (!refill_beside_ok(m, m->max_batch)) return refill_refused(m, CSM_E_STATE, who, "needs the matrix-core decode path (csm_refill_supported); use csm_prefill_slot");
     { const int rc = refill_buffers(m, st); if (rc != CSM_OK) return rc; }
-    if (m->rg_row_slot == nullptr) {
+    if (ragged && m->rg_row_slot == nullptr) {
         HIPCHK(m, hipMalloc((void**)&m->rg_row_slot, (size_t)m->max_rows * 4));
         HIPCHK(m, hipMalloc((void**)&m->rg_tiles, (size_t)(m->max_rows / 32 + RAG_MAX_SEGS) * sizeof(int4)));
     }
     const int M = rag_segs_rows(sg);
     HIPCHK(m, launch_embed(m, tokens, mask, M, st, m->rf_h));
-    hipLaunchKernelGGL(k_rag_plan, dim3(1), dim3(256), 0, st, sg, pos, m->rg_row_slot, m->rg_tiles, tiles);
-    // parked (flag 2) at its own prompt length, like csm_refill_begin's slot -- all of them in one launch
+    if (ragged) hipLaunchKernelGGL(k_rag_plan, dim3(1), dim3(256), 0, st, sg, pos, m->rg_row_slot, m->rg_tiles, tiles);
+    // parked (flag 2): until the prompt is complete a slot's row of the frame steps is a placeholder at positions >= its prompt length (its
+    // K/V land beyond the prompt's), and k_advance neither advances it nor tests it against max_seq, however many steps the layers take
     hipLaunchKernelGGL(k_rag_set_state, dim3(1), dim3(256), 0, st, sg, pos, M, m->cur_pos, m->max_batch, m->cfg.backbone.max_seq, m->n_frames + 1,
                        m->slot_tab_used ? m->slot_tab : nullptr, m->fresh, 2);
     HIPCHK(m, hipGetLastError());
     for (int i = 0; i < sg.n; ++i) fresh_clear(m, sg.s[i].slot);
-    m->rg = sg; m->rg_tiles_n = tiles; m->rf_layer = 0; m->rf_pos = pos;
+    m->rf.sg = sg; m->rf.ragged = ragged; m->rf.tiles = tiles; m->rf.layer = 0; m->rf.pos = pos;
     return CSM_OK;
+}
+
+static int refill_advance(CsmModel* m, int max_layers, hipStream_t st) {
+    RefillRec& r = m->rf;
+    const int M = rag_segs_rows(r.sg);
+    int l0, l1;
+    const bool complete = refill_layers(r, max_layers, m->cfg.backbone.n_layers, &l0, &l1);
+    hipError_t e;
+    if (r.ragged) {
+        RagLaunch rl;
+        rl.sg = r.sg; rl.row_slot = m->rg_row_slot; rl.tiles = m->rg_tiles; rl.n_tiles = r.tiles;
+        e = run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, r.pos, -1, st, true, false, false, l0, l1, m->rf_last, &rl);
+    } else {
+        // one slot keeps the launches of a batch of ONE sequence whose K/V land in the slot's part of the caches
+        const int slot = r.sg.s[0].slot;
+        m->bb.slot_off = (long)slot * m->cfg.backbone.n_kv_heads * m->bb.cache_len * m->bb.hd;
+        e = run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, r.pos, -1, st, true, false, false, l0, l1, m->rf_last + (long)slot * 2 * m->cfg.backbone.dim);
+        m->bb.slot_off = 0;
+    }
+    HIPCHK(m, e);
+    r.layer = l1;
+    if (!complete) return 0;
+    // complete: every slot at its prompt length again (the placeholder rows drifted beyond it), flags up -- the next frame step samples frame 0 of all of them
+    hipLaunchKernelGGL(k_rag_set_state, dim3(1), dim3(256), 0, st, r.sg, r.pos, M, m->cur_pos, m->max_batch, m->cfg.backbone.max_seq, m->n_frames + 1,
+                       (SlotSampling*)nullptr, m->fresh, 1);
+    HIPCHK(m, hipGetLastError());
+    for (int i = 0; i < r.sg.n; ++i) {
+        const size_t slot = (size_t)r.sg.s[i].slot;
+        if (!m->rf_fresh_host[slot]) { m->rf_fresh_host[slot] = 1; m->rf_fresh_count += 1; }
+    }
+    refill_clear(r);
+    return 1;
+}
+
+extern "C" int csm_refill_begin(csm_handle m, int slot, const int32_t* tokens, const uint8_t* mask, const int32_t* pos, int S, void* stream) {
+    if (!m || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_refill_begin: null argument");
+    RagSegs sg;
+    const int32_t s32 = slot, r32 = S;
+    if (rag_segs_build(&s32, &r32, 1, m->max_batch, m->max_rows, &sg, nullptr)) return fail(m, CSM_E_INVALID, "csm_refill_begin: slot / S outside the limits given to csm_create");
+    return refill_begin(m, "csm_refill_begin", sg, 0, false, tokens, mask, pos, (hipStream_t)stream);
+}
+
+extern "C" int csm_refill_advance(csm_handle m, int max_layers, void* stream) {
+    if (!m || max_layers < 1) return fail(m, CSM_E_INVALID, "csm_refill_advance: bad argument");
+    if (!refill_pending(m) || m->rf.ragged) return fail(m, CSM_E_STATE, "csm_refill_advance: no refill in progress");
+    return refill_advance(m, max_layers, (hipStream_t)stream);
+}
+
+extern "C" int csm_refill_group_begin(csm_handle m, const int32_t* slots, const int32_t* rows, int n, const int32_t* tokens, const uint8_t* mask,
+                                      const int32_t* pos, void* stream) {
+    if (!m || !slots || !rows || !tokens || !mask || !pos) return fail(m, CSM_E_INVALID, "csm_refill_group_begin: null argument");
+    RagSegs sg;
+    int tiles = 0;
+    if (const char* why = rag_segs_build(slots, rows, n, m->max_batch, m->max_rows, &sg, &tiles)) return refill_refused(m, CSM_E_INVALID, "csm_refill_group_begin", why);
+    return refill_begin(m, "csm_refill_group_begin", sg, tiles, true, tokens, mask, pos, (hipStream_t)stream);
 }
 
 extern "C" int csm_refill_group_advance(csm_handle m, int max_layers, void* stream) {
     if (!m || max_layers < 1) return fail(m, CSM_E_INVALID, "csm_refill_group_advance: bad argument");
-    if (m->rg.n < 1) return fail(m, CSM_E_STATE, "csm_refill_group_advance: no refill group in progress");
-    hipStream_t st = (hipStream_t)stream;
-    const int L = m->cfg.backbone.n_layers, M = rag_segs_rows(m->rg);
-    const int l0 = m->rf_layer, l1 = l0 + max_layers < L ? l0 + max_layers : L;
-    RagLaunch rl;
-    rl.sg = m->rg; rl.row_slot = m->rg_row_slot; rl.tiles = m->rg_tiles; rl.n_tiles = m->rg_tiles_n;
-    HIPCHK(m, run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, m->rf_pos, -1, st, true, false, false, l0, l1, m->rf_last, &rl));
-    m->rf_layer = l1;
-    if (l1 < L) return 0;
-    // complete: every slot back at its prompt length, flags up -- the next frame step samples frame 0 of all of them
-    hipLaunchKernelGGL(k_rag_set_state, dim3(1), dim3(256), 0, st, m->rg, m->rf_pos, M, m->cur_pos, m->max_batch, m->cfg.backbone.max_seq, m->n_frames + 1,
-                       (SlotSampling*)nullptr, m->fresh, 1);
-    HIPCHK(m, hipGetLastError());
-    for (int i = 0; i < m->rg.n; ++i) {
-        const size_t slot = (size_t)m->rg.s[i].slot;
-        if (!m->rf_fresh_host[slot]) { m->rf_fresh_host[slot] = 1; m->rf_fresh_count += 1; }
-    }
-    m->rg.n = 0; m->rf_pos = nullptr;
-    return 1;
+    if (!refill_pending(m) || !m->rf.ragged) return fail(m, CSM_E_STATE, "csm_refill_group_advance: no refill group in progress");
+    return refill_advance(m, max_layers, (hipStream_t)stream);
 }
 
 extern "C" int csm_refill_supported(csm_handle m, int B) { return m && B >= 1 && refill_beside_ok(m, B) ? 1 : 0; }

@@ -1,4 +1,5 @@
-// The segment table of a ragged group prefill (csm_refill_group_begin) and the host-side argument checks that build it.  Plain C++: no HIP,
+// The segment table of a ragged group prefill (csm_refill_group_begin), the host-side argument checks that build it, and the record of the
+// pending refill beside the frame loop that both begin forms share.  Plain C++: no HIP,
 // so the checks also compile into a stand-alone host program (tools/refill_group_args_check.cpp, run under the host sanitizers).
 #pragma once
 #include <stdint.h>
@@ -40,4 +41,24 @@ static inline bool rag_segs_has_slot(const RagSegs& g, int slot) {
     for (int i = 0; i < g.n; ++i)
         if (g.s[i].slot == slot) return true;
     return false;
+}
+
+// The refill beside the frame loop that a handle has begun and not completed: ONE record for both begin forms.  csm_refill_begin's slot is
+// a table of one segment at row 0; sg.n == 0 means nothing is pending.  `ragged` (begun by csm_refill_group_begin, also with one segment)
+// only chooses the layer launches of an advance; parking, completion and every predicate read the table alone.
+struct RefillRec {
+    RagSegs sg;
+    bool ragged;
+    int tiles;              // the table's 32-row query tiles (read by the ragged launches)
+    int layer;              // next backbone layer to run
+    const int32_t* pos;     // the caller's position array (device memory, valid until the refill completes)
+};
+static inline void refill_clear(RefillRec& r) { r.sg.n = 0; r.ragged = false; r.tiles = 0; r.layer = 0; r.pos = nullptr; }
+static inline bool refill_pending(const RefillRec& r) { return r.sg.n > 0; }
+static inline bool refill_has_slot(const RefillRec& r, int slot) { return rag_segs_has_slot(r.sg, slot); }
+// An advance of max_layers >= 1 runs layers [*l0, *l1) of n_layers; true when the refill is complete after them.
+static inline bool refill_layers(const RefillRec& r, int max_layers, int n_layers, int* l0, int* l1) {
+    *l0 = r.layer;
+    *l1 = max_layers < n_layers - r.layer ? r.layer + max_layers : n_layers;
+    return *l1 >= n_layers;
 }

@@ -105,21 +105,28 @@ class LiveBatch:
         self.g += n
         return cuts
 
-    def _rows_to_run(self, slot: int, i: int) -> Tuple[torch.Tensor, torch.Tensor, dict]:
-        """(tokens, mask, keywords) for the refill of ``slot`` with prompt ``i``.  A registered prefix's K/V are copied into the slot HERE (unless the
-        initial fill's shared copy put them there) and only the rows after it run: the caller begins at once, no frame step between the two."""
-        (t, mk), (P, handle) = self.prompts[i], self.plan[i]
-        if handle is not None and self.seeded.pop(slot, None) is not handle:
-            self.m.apply_prefix(handle, [slot])
-        if self.own[i] is not None:                                 # after the prefix copy, immediately before the refill call
-            self.m.set_slot_sampling([slot], *self.own[i])
-            self.entries.add(slot)
-        elif slot in self.entries:
-            self.m.clear_slot_sampling([slot])
-            self.entries.discard(slot)
-        if handle is None:
-            return t, mk, {}
-        return t[P:], mk[P:], {"start": P}
+    def _rows_to_run(self, take: List[Tuple[int, int]]) -> List[Tuple[torch.Tensor, torch.Tensor, dict]]:
+        """(tokens, mask, keywords) for the refill of each (slot, prompt index) of ``take``.  A registered prefix's K/V are copied into the slots HERE,
+        one copy per handle (unless the initial fill's shared copy put them there), then the sampling table gets or loses the slots' entries,
+        and only the rows after the prefix run: the caller begins at once, no frame step between any of it and the refill call."""
+        copies: dict = {}                                           # id(handle) -> (handle, [slots]) still to copy
+        for slot, i in take:
+            handle = self.plan[i][1]
+            if handle is not None and self.seeded.pop(slot, None) is not handle:
+                copies.setdefault(id(handle), (handle, []))[1].append(slot)
+        for handle, slots in copies.values():
+            self.m.apply_prefix(handle, slots)
+        parts = []
+        for slot, i in take:
+            (t, mk), (P, handle) = self.prompts[i], self.plan[i]
+            if self.own[i] is not None:                             # after the prefix copies, immediately before the refill call
+                self.m.set_slot_sampling([slot], *self.own[i])
+                self.entries.add(slot)
+            elif slot in self.entries:
+                self.m.clear_slot_sampling([slot])
+                self.entries.discard(slot)
+            parts.append((t[P:], mk[P:], {"start": P}) if handle is not None else (t, mk, {}))
+        return parts
 
     def _report_order(self, cuts: List[Tuple[int, bool]]) -> List[Tuple[int, bool]]:
         return cuts                                                 # by slot
@@ -132,7 +139,7 @@ class _Stalling(LiveBatch):
     def _vacated(self, slot: int) -> None:
         while self.pending:
             i = self.pending.popleft()
-            t, mk, kw = self._rows_to_run(slot, i)
+            (t, mk, kw), = self._rows_to_run([(slot, i)])
             f0 = self.m.refill_slot(slot, t, mk, *self.sampling, **kw).cpu()
             if self.limits[i] > 0 and not bool((f0 == 0).all()):
                 self.slots[slot] = _Utterance(i, self.limits[i], self.g, [f0])
@@ -160,40 +167,15 @@ class _BesideTheLoop(LiveBatch):
     def __init__(self, *args, budget: int, group: int = 1):
         super().__init__(*args)
         self.budget, self.layers = budget, self.m.bb.num_layers
-        self.refilling: Optional[Tuple[int, int, int]] = None       # (slot, prompt index, prompt rows to run)
         # group > 1: free slots with prompts pending are refilled up to ``group`` at a time by ONE ragged prefill (Model.refill_group_begin /
         # refill_group_advance) -- slots that retire in the same block share one launch chain per layer instead of queueing with a handful
         # of rows each.  Requests with a seed of their own keep their codes whatever the group size (their draws do not depend on the schedule).
         self.group = max(1, min(int(group), 32))
-        self.grouped: Optional[Tuple[List[Tuple[int, int]], int]] = None    # ([(slot, prompt index)], rows of the group), pending
+        self.refilling: Optional[Tuple[List[Tuple[int, int]], int]] = None      # ([(slot, prompt index)], prompt rows to run), pending
 
-    def _feed(self, everything: bool) -> bool:
-        """One bounded piece of refill work (``everything``: nobody is generating, so run whole prompts).  False: there was none."""
-        if self.group > 1:
-            return self._feed_groups(everything)
-        m, fed = self.m, False
-        while self.refilling is not None or (self.free and self.pending):
-            if self.refilling is None:
-                slot, i = self.free.popleft(), self.pending.popleft()
-                t, mk, kw = self._rows_to_run(slot, i)
-                m.refill_begin(slot, t, mk, **kw)
-                self.refilling = (slot, i, int(t.shape[0]))
-            slot, i, rows = self.refilling
-            # the per-step budget grows with the backlog: every slot that waits for a prompt is 1/B of the batch's throughput idle, and
-            # the refill work is the same whenever it is done -- with nobody waiting the steps stay within ~8 % of an undisturbed one
-            per_call = max(1, self.budget * (1 + len(self.free)) // max(rows, 1))
-            if m.refill_advance(self.layers if everything else min(per_call, self.layers)):
-                self.slots[slot] = _Utterance(i, self.limits[i], m.num_frames(), [])
-                self.refilling = None
-            fed = True
-            if not everything:
-                break
-        return fed
-
-    def _begin_group(self) -> None:
+    def _begin(self) -> None:
         """Takes up to ``group`` free slots with a pending prompt each -- as many as fit ``max_prefill_rows`` together, at least one -- and begins
-        them as one group.  Everything ``_rows_to_run`` does per slot happens first, the prefix copies one per handle as in the initial fill,
-        then the sampling-table calls, then the ONE begin call: no frame step between any of them."""
+        their refill: with ``group`` == 1 the slot's own (Model.refill_begin), else one group call, also for a single slot."""
         m = self.m
         cap = int(getattr(m, "max_prefill_rows", 0)) or (1 << 30)
         take: List[Tuple[int, int]] = []
@@ -205,39 +187,30 @@ class _BesideTheLoop(LiveBatch):
                 break                                               # it waits for the next group
             take.append((self.free.popleft(), self.pending.popleft()))
             total += rows
-        copies: dict = {}                                           # id(handle) -> (handle, [slots]) still to copy
-        for slot, i in take:
-            handle = self.plan[i][1]
-            if handle is not None and self.seeded.pop(slot, None) is not handle:
-                copies.setdefault(id(handle), (handle, []))[1].append(slot)
-        for handle, slots in copies.values():
-            m.apply_prefix(handle, slots)
-        parts = []
-        for slot, i in take:
-            (t, mk), (P, handle) = self.prompts[i], self.plan[i]
-            if self.own[i] is not None:
-                m.set_slot_sampling([slot], *self.own[i])
-                self.entries.add(slot)
-            elif slot in self.entries:
-                m.clear_slot_sampling([slot])
-                self.entries.discard(slot)
-            parts.append((t[P:], mk[P:], P) if handle is not None else (t, mk, 0))
-        m.refill_group_begin([slot for slot, _ in take], [(t, mk) for t, mk, _ in parts], starts=[P for _, _, P in parts])
-        self.grouped = (take, total)
+        parts = self._rows_to_run(take)
+        if self.group == 1:
+            (t, mk, kw), = parts
+            m.refill_begin(take[0][0], t, mk, **kw)
+        else:
+            m.refill_group_begin([slot for slot, _ in take], [(t, mk) for t, mk, _ in parts], starts=[kw.get("start", 0) for _, _, kw in parts])
+        self.refilling = (take, total)
 
-    def _feed_groups(self, everything: bool) -> bool:
-        """``_feed`` with groups: the per-step budget is spent on the group's rows together."""
+    def _feed(self, everything: bool) -> bool:
+        """One bounded piece of refill work (``everything``: nobody is generating, so run whole prompts).  False: there was none."""
         m, fed = self.m, False
-        while self.grouped is not None or (self.free and self.pending):
-            if self.grouped is None:
-                self._begin_group()
-            take, rows = self.grouped
+        advance = m.refill_advance if self.group == 1 else m.refill_group_advance
+        while self.refilling is not None or (self.free and self.pending):
+            if self.refilling is None:
+                self._begin()
+            take, rows = self.refilling
+            # the per-step budget grows with the backlog: every slot that waits for a prompt is 1/B of the batch's throughput idle, and
+            # the refill work is the same whenever it is done -- with nobody waiting the steps stay within ~8 % of an undisturbed one
             per_call = max(1, self.budget * (1 + len(self.free)) // max(rows, 1))
-            if m.refill_group_advance(self.layers if everything else min(per_call, self.layers)):
+            if advance(self.layers if everything else min(per_call, self.layers)):
                 first = m.num_frames()
                 for slot, i in take:
                     self.slots[slot] = _Utterance(i, self.limits[i], first, [])
-                self.grouped = None
+                self.refilling = None
             fed = True
             if not everything:
                 break

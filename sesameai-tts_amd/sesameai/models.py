@@ -739,95 +739,81 @@ class Model:
         return {"has_entry": bool(has.value), "temperature": float(t.value), "topk": int(k.value), "own_rng": bool(own.value),
                 "seed": int(sd.value), "counter": int(ctr.value)}
 
+    def _refill_call(self, prompts, starts, call, keep: bool) -> None:
+        """What refill_slot, refill_begin and refill_group_begin share.  ``prompts`` = [(tokens (S_i,33), mask (S_i,33))], rows of one call back
+        to back, prompt i at positions [starts[i], starts[i] + S_i).  Checks the limits, puts tokens, mask and positions on the device (the
+        positions are made there: no copy, no synchronisation), runs ``call(tokens, mask, positions, rows)`` -> return code, and, once the
+        call was accepted, counts its rows; ``keep``: the arrays stay alive until the refill completes (every advance call reads the
+        positions; a refused begin must not drop a pending refill's arrays)."""
+        self._require()
+        rows = [int(t.shape[0]) for t, _ in prompts]
+        for s, p in zip(rows, starts):
+            if p < 0 or p + s >= self.bb.max_seq_len:
+                raise ValueError(f"prompt of {s} rows from {p} exceeds max_seq_len {self.bb.max_seq_len}")
+        if sum(rows) > self.max_prefill_rows:
+            raise ValueError(f"{sum(rows)} prompt rows in one call exceed max_prefill_rows {self.max_prefill_rows}")
+        self._kv_prompt = None                                   # slot 0's cached prompt prefix no longer describes the caches
+
+        def cat(xs):
+            return xs[0] if len(xs) == 1 else torch.cat(xs, 0)
+        t = cat([self._to_dev(t_, torch.int32) for t_, _ in prompts])
+        m = cat([self._to_dev(m_, torch.uint8) for _, m_ in prompts])
+        p = cat([torch.arange(p_, p_ + s_, device=self.device, dtype=torch.int32) for s_, p_ in zip(rows, starts)])
+        with self._on_device():
+            check(call(t.data_ptr(), m.data_ptr(), p.data_ptr(), rows), self._h)
+        self.last_prefill_rows = sum(rows)
+        self.prefill_rows_total += sum(rows)
+        if keep:
+            self._refill_keep = (t, m, p)
+
+    def _refill_advance(self, advance, max_layers: int) -> bool:
+        with self._on_device():
+            rc = advance(self._h, int(max_layers), _stream_ptr())
+        if rc < 0:
+            check(rc, self._h)
+        if rc == 1:
+            self._refill_keep = None
+        return rc == 1
+
     def refill_slot(self, slot: int, tokens: torch.Tensor, tokens_mask: torch.Tensor, temperature: float, topk: int, start: int = 0) -> torch.Tensor:
         """A new prompt (S,33) starting at position 0 into batch slot ``slot`` of a live batch: backbone prefill into the slot's
         caches, depth pass, the new utterance's frame 0 staged as the slot's next input.  Returns frame 0 (32,) int32 on the
         device.  The other slots keep generating undisturbed (bit-identical frames); see include/csm_hip.h csm_prefill_slot.
         ``start``: the rows are the prompt's rows [start, start + S); rows [0, start) are already in the slot's caches (apply_prefix)."""
-        self._require()
-        s = tokens.shape[0]
-        if start < 0 or start + s >= self.bb.max_seq_len or s > max(self._max_prefill_rows, 2 * self._max_batch):
-            raise ValueError(f"prompt of {s} rows exceeds the limits (max_seq_len {self.bb.max_seq_len}, max_prefill_rows {self._max_prefill_rows})")
-        self._kv_prompt = None                                   # slot 0's cached prompt prefix no longer describes the caches
-        t = self._to_dev(tokens, torch.int32)
-        m = self._to_dev(tokens_mask, torch.uint8)
-        p = torch.arange(start, start + s, device=self.device, dtype=torch.int32)
-        self.last_prefill_rows = s
-        self.prefill_rows_total += s
         out = torch.empty(self.config.audio_num_codebooks, dtype=torch.int32, device=self.device)
-        with self._on_device():
-            check(lib.csm_prefill_slot(self._h, int(slot), t.data_ptr(), m.data_ptr(), p.data_ptr(), s, 1, float(temperature), int(topk),
-                                       out.data_ptr(), _stream_ptr()), self._h)
+        self._refill_call([(tokens, tokens_mask)], [int(start)], lambda t, m, p, rows: lib.csm_prefill_slot(
+            self._h, int(slot), t, m, p, rows[0], 1, float(temperature), int(topk), out.data_ptr(), _stream_ptr()), keep=False)
         return out
 
     def refill_begin(self, slot: int, tokens: torch.Tensor, tokens_mask: torch.Tensor, start: int = 0) -> None:
         """Starts a refill BESIDE the frame loop (csm_refill_begin): the prompt (S,33) is embedded and the slot parked; its layers run
         a few at a time through ``refill_advance`` between frame steps, so the other slots never wait for a whole prompt.  One
         refill at a time per model.  ``start``: as for ``refill_slot``."""
-        self._require()
-        s = tokens.shape[0]
-        if start < 0 or start + s >= self.bb.max_seq_len or s > max(self._max_prefill_rows, 2 * self._max_batch):
-            raise ValueError(f"prompt of {s} rows exceeds the limits (max_seq_len {self.bb.max_seq_len}, max_prefill_rows {self._max_prefill_rows})")
-        self._kv_prompt = None
-        t = self._to_dev(tokens, torch.int32)
-        m = self._to_dev(tokens_mask, torch.uint8)
-        p = torch.arange(start, start + s, device=self.device, dtype=torch.int32)
-        self.last_prefill_rows = s
-        self.prefill_rows_total += s
-        with self._on_device():
-            check(lib.csm_refill_begin(self._h, int(slot), t.data_ptr(), m.data_ptr(), p.data_ptr(), s, _stream_ptr()), self._h)
-        self._refill_keep = (t, m, p)                             # the position array is read by every advance call (kept only once the
-        #                                                           call was accepted: a refused begin must not drop a pending refill's arrays)
+        self._refill_call([(tokens, tokens_mask)], [int(start)], lambda t, m, p, rows: lib.csm_refill_begin(
+            self._h, int(slot), t, m, p, rows[0], _stream_ptr()), keep=True)
 
     def refill_advance(self, max_layers: int) -> bool:
         """Up to ``max_layers`` more backbone layers of the pending refill.  True when the prompt is complete: the NEXT frame step
         yields the new utterance's frame 0 in the slot's row (csm_refill_advance)."""
-        with self._on_device():
-            rc = lib.csm_refill_advance(self._h, int(max_layers), _stream_ptr())
-        if rc < 0:
-            check(rc, self._h)
-        if rc == 1:
-            self._refill_keep = None
-        return rc == 1
+        return self._refill_advance(lib.csm_refill_advance, max_layers)
 
     def refill_group_begin(self, slots, prompts, starts=None) -> None:
         """``refill_begin`` for several slots at once (csm_refill_group_begin): ``prompts[i]`` = (tokens (S_i,33), mask (S_i,33)) are the rows of
         batch slot ``slots[i]`` from position ``starts[i]`` on (default 0; rows [0, starts[i]) are in the slot's caches: ``apply_prefix``).  Up to
         32 distinct slots, ``max_prefill_rows`` rows in all.  Their layers run over all rows together through ``refill_group_advance``.  One
         refill or one group at a time per model."""
-        self._require()
         slots = [int(x) for x in slots]
         n = len(slots)
         starts = [0] * n if starts is None else [int(x) for x in starts]
-        if n < 1 or len(prompts) != n or len(starts) != n:
-            raise ValueError("refill_group_begin: one prompt (and one start) per slot, at least one slot")
-        rows = [int(t.shape[0]) for t, _ in prompts]
-        for s, p in zip(rows, starts):
-            if s < 1 or p < 0 or p + s >= self.bb.max_seq_len:
-                raise ValueError(f"prompt of {s} rows from {p} exceeds max_seq_len {self.bb.max_seq_len}")
-        if sum(rows) > self.max_prefill_rows:
-            raise ValueError(f"group of {sum(rows)} rows exceeds max_prefill_rows {self.max_prefill_rows}")
-        self._kv_prompt = None
-        t = torch.cat([self._to_dev(t_, torch.int32) for t_, _ in prompts], 0).contiguous()
-        m = torch.cat([self._to_dev(m_, torch.uint8) for _, m_ in prompts], 0).contiguous()
-        p = torch.cat([torch.arange(p_, p_ + s_, dtype=torch.int32) for s_, p_ in zip(rows, starts)]).to(self.device)
-        with self._on_device():
-            check(lib.csm_refill_group_begin(self._h, (C.c_int32 * n)(*slots), (C.c_int32 * n)(*rows), n, t.data_ptr(), m.data_ptr(), p.data_ptr(),
-                                             _stream_ptr()), self._h)
-        self._refill_keep = (t, m, p)                             # the position array is read by every advance call (see refill_begin)
-        self.last_prefill_rows = sum(rows)
-        self.prefill_rows_total += sum(rows)
+        if n < 1 or len(prompts) != n or len(starts) != n or any(t.shape[0] < 1 for t, _ in prompts):
+            raise ValueError("refill_group_begin: one prompt of at least one row (and one start) per slot, at least one slot")
+        self._refill_call(prompts, starts, lambda t, m, p, rows: lib.csm_refill_group_begin(
+            self._h, (C.c_int32 * n)(*slots), (C.c_int32 * n)(*rows), n, t, m, p, _stream_ptr()), keep=True)
 
     def refill_group_advance(self, max_layers: int) -> bool:
         """Up to ``max_layers`` more backbone layers of the pending group.  True when it is complete: the NEXT frame step yields frame 0 of
         every utterance of the group in its slot's row (csm_refill_group_advance)."""
-        with self._on_device():
-            rc = lib.csm_refill_group_advance(self._h, int(max_layers), _stream_ptr())
-        if rc < 0:
-            check(rc, self._h)
-        if rc == 1:
-            self._refill_keep = None
-        return rc == 1
+        return self._refill_advance(lib.csm_refill_group_advance, max_layers)
 
     @property
     def max_prefill_rows(self) -> int:

@@ -180,6 +180,7 @@ def test_refusals_enqueue_nothing():
             assert lib.csm_refill_group_advance(m._h, 0, None) == INVALID
             m.refill_begin(2, tok[:8], msk[:8])                                  # a single refill is pending: no group
             assert _raw_begin(m, [0, 1], [4, 4], 2, t, k, p) == STATE
+            assert lib.csm_refill_group_advance(m._h, 1, None) == STATE          # ... and the group's advance does not run it
             while not m.refill_advance(1):
                 pass
             pf = m.capture_prefix(0, 4)

@@ -1,4 +1,5 @@
-// Stand-alone host check of csm_refill_group_begin's argument validation and segment-table construction (sesameai-tts_amd/csrc/rag_segs.h).
+// Stand-alone host check of csm_refill_group_begin's argument validation and segment-table construction, and of the pending-refill record's
+// predicates that both refill forms share (sesameai-tts_amd/csrc/rag_segs.h).
 // No GPU, no HIP: build it with the host sanitizers and run it,
 //   hipcc -Xarch_host -fsanitize=address,undefined -I sesameai-tts_amd/csrc tools/refill_group_args_check.cpp -o /tmp/rgcheck && /tmp/rgcheck
 // (or any C++17 compiler with -fsanitize=address,undefined).  Exit status 0 and "ok" when every case behaves.
@@ -56,6 +57,39 @@ int main() {
     EXPECT(build({7}, {64}, 1, 8, 64, &g, &tiles) == nullptr && g.n == 1 && tiles == 2);
     RagSegs none; none.n = 0;
     EXPECT(!rag_segs_has_slot(none, 0) && rag_segs_rows(none) == 0);
+    // the pending-refill record: nothing pending
+    RefillRec r;
+    refill_clear(r);
+    EXPECT(!refill_pending(r) && !refill_has_slot(r, 0) && !r.ragged && r.layer == 0 && r.pos == nullptr);
+    // a single slot = a table of one segment at row 0
+    const int32_t slot = 6, S = 33;
+    EXPECT(rag_segs_build(&slot, &S, 1, 8, 64, &r.sg, nullptr) == nullptr);
+    EXPECT(refill_pending(r) && r.sg.n == 1 && r.sg.s[0].row0 == 0 && rag_segs_rows(r.sg) == 33);
+    EXPECT(refill_has_slot(r, 6) && !refill_has_slot(r, 0) && !refill_has_slot(r, 7) && !refill_has_slot(r, -1));
+    const int32_t slot8 = 8, none_rows = 0, too_many = 65;
+    EXPECT(rag_segs_build(&slot8, &S, 1, 8, 64, &r.sg, nullptr) != nullptr && !refill_pending(r));         // what csm_refill_begin refuses
+    EXPECT(rag_segs_build(&slot, &none_rows, 1, 8, 64, &r.sg, nullptr) != nullptr && !refill_pending(r));
+    EXPECT(rag_segs_build(&slot, &too_many, 1, 8, 64, &r.sg, nullptr) != nullptr && !refill_pending(r));
+    // a group
+    EXPECT(build({5, 0, 3}, {1, 33, 30}, 3, 8, 64, &r.sg, &r.tiles) == nullptr);
+    r.ragged = true;
+    EXPECT(refill_pending(r) && r.tiles == 4 && refill_has_slot(r, 0) && refill_has_slot(r, 3) && refill_has_slot(r, 5) && !refill_has_slot(r, 4));
+    // which layers an advance runs, and whether the refill is complete after them: from layer 0 and from mid-stack
+    const int L = 16;
+    struct { int layer, max_layers, l0, l1; bool complete; } cases[] = {
+        {0, 1, 0, 1, false},  {0, L - 1, 0, L - 1, false},  {0, L, 0, L, true},  {0, L + 1, 0, L, true},  {0, 2147483647, 0, L, true},
+        {7, 1, 7, 8, false},  {7, L - 8, 7, L - 1, false},  {7, L - 7, 7, L, true},  {7, L - 1, 7, L, true},  {7, L, 7, L, true},
+        {7, L + 1, 7, L, true},  {7, 2147483647, 7, L, true},  {L - 1, 1, L - 1, L, true},
+    };
+    for (const auto& c : cases) {
+        int l0 = -1, l1 = -1;
+        r.layer = c.layer;
+        EXPECT(refill_layers(r, c.max_layers, L, &l0, &l1) == c.complete && l0 == c.l0 && l1 == c.l1);
+    }
+    r.layer = 0;
+    { int l0 = -1, l1 = -1; EXPECT(refill_layers(r, 1, 1, &l0, &l1) && l0 == 0 && l1 == 1); }             // a one-layer stack
+    refill_clear(r);
+    EXPECT(!refill_pending(r) && !refill_has_slot(r, 5) && !r.ragged && r.tiles == 0);
     if (failures) return 1;
     std::puts("ok");
     return 0;
