@@ -17,6 +17,8 @@ extern "C" {
  * batched decode) of kinds 0, 1, 3, 4; x must already be normalised, K % 256 == 0.
  * kind + 20 (20, 21, 23, 24): the same through the 128 x 128 LDS-tiled kernel that long prompts (M >= 512 rows)
  * take; bit-identical to kind + 10.
+ * 31, 33, 34: kinds 1, 3, 4 through the several-tiles-per-wave prompt kernels (k_mmq + its finisher / k_mmt; 64 <= M <= 256,
+ * K % 1024 == 0, N % 64 == 0); bit-identical to kind + 10.  Every other number is CSM_E_INVALID, and nothing is launched.
  * Replaces torchtune's RMSNorm / nn.Linear / Llama3ScaledRoPE / KVCache.update / FeedForward
  * as called from sesameai/models.py:158,173.                          */
 int csm_op_gemv(int kind, int M, int K, int N, const void* x, long x_row_stride, long x_row_offset,

@@ -27,10 +27,7 @@
 #include "dec_first.cuh"
 #include "bb_block.cuh"
 #include "switches.h"
-
-#define BB_NSPLIT_MAX 8
-#define PART_ROWS 32
-#define WIDE_MIN_ROWS 3       // M >= this: MFMA path (mm.cuh) instead of the weight-stationary GEMV (measured: B=3 6.0 vs 6.5 ms, B=2 narrow wins)
+#include "stack_plan.h"
 
 #define CSM_FRAME_GRAPHS 4     // captured frame steps kept per handle
 #define CSM_REFILL_SALT 0x9E3779B97F4A7C15ull      /* Philox key domain of slot refills (csm_seed) */
@@ -216,62 +213,42 @@ static hipError_t launch_gemv_msplit(int which, bool fp8, GemvArgs a, hipStream_
     return hipGetLastError();
 }
 
-// kind: 0 = plain store, 1 = plain + residual, 2 = norm + store (head), 3 = norm + qkv/rope, 4 = norm + swiglu,
-//       5 = fused depth-decoder attention + residual (hd 128, <= 32 keys)
-//       6 = fused split-K attention merge + residual (hd 64)
-static hipError_t launch_gemv(int kind, int K, int hd, const GemvArgs& a, hipStream_t st) {
-    if (K % 512 != 0) return hipErrorInvalidValue;
-    const int ki = K / 512;
-#define GEMV_CASE(KI, RS, RG)                                                                                   \
-    case KI:                                                                                                    \
-        switch (kind) {                                                                                         \
-            case 0: return launch_gemv_mt<KI, RS, PRO_PLAIN, EPI_STORE, 64>(a, (a.N + RS - 1) / RS, st);        \
-            case 1: return launch_gemv_mt<KI, RS, PRO_PLAIN, EPI_RESID, 64>(a, (a.N + RS - 1) / RS, st);        \
-            case 2: return launch_gemv_mt<KI, RS, PRO_NORM, EPI_STORE, 64>(a, (a.N + RS - 1) / RS, st);         \
-            case 3: return hd == 64 ? launch_gemv_mt<KI, 2, PRO_NORM, EPI_QKV_ROPE, 64>(a, (a.N + 1) / 2, st)   \
-                                    : launch_gemv_mt<KI, 2, PRO_NORM, EPI_QKV_ROPE, 128>(a, (a.N + 1) / 2, st); \
-            case 4: return launch_gemv_mt<KI, RG, PRO_NORM, EPI_SWIGLU, 64>(a, (a.N + RG / 2 - 1) / (RG / 2), st); \
-            case 5: return launch_gemv_mt<KI, RS, PRO_ATTN, EPI_RESID, 64>(a, (a.N + RS - 1) / RS, st);        \
-            case 6: return launch_gemv_mt<KI, RS, PRO_COMBINE, EPI_RESID, 64>(a, (a.N + RS - 1) / RS, st);     \
-        }                                                                                                       \
-        return hipErrorInvalidValue;
-    switch (ki) {
-        GEMV_CASE(1, 4, 4)
-        GEMV_CASE(2, 2, 2)     // gate/up at K=1024: one (gate, up) row pair per wave measured fastest (7.4 vs 7.9 vs 8.9 us for 1/2/4 pairs)
-        GEMV_CASE(4, 2, 2)
-        GEMV_CASE(16, 1, 2)
+// ONE table for both weight streams (WT 0 = bf16 rows; 1 = OCP-e4m3 rows, a.s0/s1/s2 = per-row scales).  RS = weight rows per wave of the
+// plain / residual / head / fused-attention forms, RG / 2 = (gate, up) row pairs per wave.  The ops are stack_plan.h's; QKV and SWIGLU are PRO_NORM here.
+template <int KI, int RS, int RG, int WT>
+static hipError_t launch_gemv_k(Op op, int hd, const GemvArgs& a, hipStream_t st) {
+    const int u = (a.N + RS - 1) / RS;
+    switch (op) {
+        case Op::STORE: if constexpr (WT == 0) return launch_gemv_mt<KI, RS, PRO_PLAIN, EPI_STORE, 64>(a, u, st);      // cell 3: nothing streams e4m3 into a plain store
+                        break;
+        case Op::RESID: return launch_gemv_mt<KI, RS, PRO_PLAIN, EPI_RESID, 64, WT>(a, u, st);
+        case Op::NORM_STORE: return launch_gemv_mt<KI, RS, PRO_NORM, EPI_STORE, 64, WT>(a, u, st);
+        case Op::QKV: return hd == 64 ? launch_gemv_mt<KI, 2, PRO_NORM, EPI_QKV_ROPE, 64, WT>(a, (a.N + 1) / 2, st)
+                                      : launch_gemv_mt<KI, 2, PRO_NORM, EPI_QKV_ROPE, 128, WT>(a, (a.N + 1) / 2, st);
+        case Op::SWIGLU: return launch_gemv_mt<KI, RG, PRO_NORM, EPI_SWIGLU, 64, WT>(a, (a.N + RG / 2 - 1) / (RG / 2), st);
+        case Op::ATTN_RESID: return launch_gemv_mt<KI, RS, PRO_ATTN, EPI_RESID, 64, WT>(a, u, st);
+        case Op::COMBINE_RESID: return launch_gemv_mt<KI, RS, PRO_COMBINE, EPI_RESID, 64, WT>(a, u, st);
+        default: break;
     }
-#undef GEMV_CASE
     return hipErrorInvalidValue;
 }
-
-// OCP-e4m3 weight stream (a.s0/s1/s2 = per-row scales); same kinds as launch_gemv
-static hipError_t launch_gemv8(int kind, int K, int hd, const GemvArgs& a, hipStream_t st) {
+template <int WT>
+static hipError_t launch_gemv_wt(Op op, int K, int hd, const GemvArgs& a, hipStream_t st) {
     if (K % 512 != 0) return hipErrorInvalidValue;
-#define GEMV8_CASE(KI, RS)                                                                                          \
-    case KI:                                                                                                        \
-        switch (kind) {                                                                                             \
-            case 1: return launch_gemv_mt<KI, RS, PRO_PLAIN, EPI_RESID, 64, 1>(a, (a.N + RS - 1) / RS, st);         \
-            case 2: return launch_gemv_mt<KI, RS, PRO_NORM, EPI_STORE, 64, 1>(a, (a.N + RS - 1) / RS, st);          \
-            case 3: return hd == 64 ? launch_gemv_mt<KI, 2, PRO_NORM, EPI_QKV_ROPE, 64, 1>(a, (a.N + 1) / 2, st)    \
-                                    : launch_gemv_mt<KI, 2, PRO_NORM, EPI_QKV_ROPE, 128, 1>(a, (a.N + 1) / 2, st);  \
-            case 4: return launch_gemv_mt<KI, 2, PRO_NORM, EPI_SWIGLU, 64, 1>(a, a.N, st);                          \
-            case 5: return launch_gemv_mt<KI, RS, PRO_ATTN, EPI_RESID, 64, 1>(a, (a.N + RS - 1) / RS, st);          \
-            case 6: return launch_gemv_mt<KI, RS, PRO_COMBINE, EPI_RESID, 64, 1>(a, (a.N + RS - 1) / RS, st);       \
-        }                                                                                                           \
-        return hipErrorInvalidValue;
     switch (K / 512) {
-        GEMV8_CASE(1, 2)
-        GEMV8_CASE(2, 2)
-        GEMV8_CASE(4, 2)
-        GEMV8_CASE(16, 1)
+        case 1: return launch_gemv_k<1, WT ? 2 : 4, WT ? 2 : 4, WT>(op, hd, a, st);    // cells 1 and 2: the e4m3 stream keeps RS = 2 and one (gate, up) pair per wave at K = 512
+        case 2: return launch_gemv_k<2, 2, 2, WT>(op, hd, a, st);     // gate/up at K=1024: one (gate, up) row pair per wave measured fastest (7.4 vs 7.9 vs 8.9 us for 1/2/4 pairs)
+        case 4: return launch_gemv_k<4, 2, 2, WT>(op, hd, a, st);
+        case 16: return launch_gemv_k<16, 1, 2, WT>(op, hd, a, st);
     }
-#undef GEMV8_CASE
     return hipErrorInvalidValue;
 }
+static hipError_t launch_gemv(Op op, int K, int hd, const GemvArgs& a, hipStream_t st, bool e4m3 = false) {
+    return e4m3 ? launch_gemv_wt<1>(op, K, hd, a, st) : launch_gemv_wt<0>(op, K, hd, a, st);
+}
 
-// wide-M projections on the matrix cores; kind as in launch_gemv (0 store, 1 +residual, 3 qkv/rope, 4 swiglu); 6 = qkv/rope of a segment group
-// (a.row_slot names each row's cache slot: EPI_QKV_ROPE_RAG, here and in launch_mmt / launch_g128)
+// wide-M projections on the matrix cores (STORE, RESID, QKV, SWIGLU read normalised rows; QKV_RAG: here and in launch_mmt / launch_g128;
+// SLAB: fp32 partial tiles into a.slab, K split over `kg` blocks)
 // k_mm32 tile order (mm.cuh): one row tile -> plain 3-D grid; more -> n tiles per XCD with the row tiles adjacent
 static void mm_grid(const GemvArgs& a, int kg, dim3* grid, int* mtiles) {
     const int nt = (a.N + 31) / 32, mt = (a.M + 31) / 32;
@@ -279,18 +256,19 @@ static void mm_grid(const GemvArgs& a, int kg, dim3* grid, int* mtiles) {
     else { *mtiles = 0; *grid = dim3(nt, mt, kg); }
 }
 template <int WT, bool XP>
-static hipError_t launch_mm_t(int kind, int K, int hd, const GemvArgs& a, hipStream_t st) {
-    if (K % 256 != 0) return hipErrorInvalidValue;
+static hipError_t launch_mm_t(Op op, int K, int hd, const GemvArgs& a, hipStream_t st, int kg) {
+    if (K % (256 * kg) != 0 || (kg != 1 && op != Op::SLAB)) return hipErrorInvalidValue;
     dim3 grid; int mtiles;
-    mm_grid(a, 1, &grid, &mtiles);
-    switch (kind) {
-        case 0: hipLaunchKernelGGL((k_mm32<EPI_STORE, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1); break;
-        case 1: hipLaunchKernelGGL((k_mm32<EPI_RESID, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1); break;
-        case 3: if (hd == 64) hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
+    mm_grid(a, kg, &grid, &mtiles);
+    switch (op) {
+        case Op::STORE: hipLaunchKernelGGL((k_mm32<EPI_STORE, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1); break;
+        case Op::RESID: hipLaunchKernelGGL((k_mm32<EPI_RESID, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1); break;
+        case Op::QKV: if (hd == 64) hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
                 else hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE, 128, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
                 break;
-        case 4: hipLaunchKernelGGL((k_mm32<EPI_SWIGLU, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1); break;
-        case 6: if (WT != 0 || a.row_slot == nullptr) return hipErrorInvalidValue;            // q|k|v of a segment group: prompt rows, bf16 stream
+        case Op::SWIGLU: hipLaunchKernelGGL((k_mm32<EPI_SWIGLU, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1); break;
+        case Op::SLAB: hipLaunchKernelGGL((k_mm32<EPI_SLAB, 64, 4, WT, XP>), grid, dim3(256), 0, st, a, K, mtiles, kg); break;
+        case Op::QKV_RAG: if (WT != 0 || a.row_slot == nullptr) return hipErrorInvalidValue;            // q|k|v of a segment group: prompt rows, bf16 stream
                 if (hd == 64) hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE_RAG, 64, 4, 0, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
                 else hipLaunchKernelGGL((k_mm32<EPI_QKV_ROPE_RAG, 128, 4, 0, XP>), grid, dim3(256), 0, st, a, K, mtiles, 1);
                 break;
@@ -300,43 +278,39 @@ static hipError_t launch_mm_t(int kind, int K, int hd, const GemvArgs& a, hipStr
 }
 // f8: w0/w1/w2 are k_pack_w8 copies of the e4m3 stream and s0/s1/s2 the per-row scales
 // xp: a.x is in matrix-core operand order (common.cuh xp_off; x_row_stride = K), as the decode-step producers write it
-static hipError_t launch_mm(int kind, int K, int hd, const GemvArgs& a, hipStream_t st, bool f8 = false, bool xp = false) {
-    if (xp) return f8 ? launch_mm_t<1, true>(kind, K, hd, a, st) : launch_mm_t<0, true>(kind, K, hd, a, st);
-    return f8 ? launch_mm_t<1, false>(kind, K, hd, a, st) : launch_mm_t<0, false>(kind, K, hd, a, st);
+static hipError_t launch_mm(Op op, int K, int hd, const GemvArgs& a, hipStream_t st, bool f8 = false, bool xp = false, int kg = 1) {
+    if (xp) return f8 ? launch_mm_t<1, true>(op, K, hd, a, st, kg) : launch_mm_t<0, true>(op, K, hd, a, st, kg);
+    return f8 ? launch_mm_t<1, false>(op, K, hd, a, st, kg) : launch_mm_t<0, false>(op, K, hd, a, st, kg);
 }
 
 // prompts of 64..255 rows (mm.cuh k_mmt / k_mmq): k_mm32's bits with several output tiles per wave.  w0/w1/w2 PACKED.
 static const int MMT_MIN_ROWS = sw_int(SW_CSM_MMT_MIN_ROWS, 64);
-// which projections take them (bit 0 q|k|v, 1 gate/up, 2 o-proj, 3 down).  Measured per backbone layer at 190 rows, operand-order
-// x, us: q|k|v 21.3 vs k_mm32 14.9 (96 fat blocks leave 160 CUs idle and a CU pulls only ~30 GB/s from HBM whatever the
-// prefetch depth), gate/up 28.4 vs 41.6, o-proj 11.5 vs 13.0, down 37.4 vs 31.0  ->  default: gate/up and o-proj
-static const int MMT_OPS = sw_int(SW_CSM_MMT_OPS, 6);
-static bool mmt_ok(int M, int K, int N) { return M >= MMT_MIN_ROWS && M <= 256 && K % 1024 == 0 && N % 64 == 0; }   // K/4 quarters in rings of up to 8 half-chunks
+static const int MMT_OPS = sw_int(SW_CSM_MMT_OPS, 6);       // which projections take them: stack_plan.h plan_wide
 #define MMT_NBUF(TM_) 2                              // ring depth: 4 measured no faster than 2 at 190 rows and costs the second resident block (gate/up 31 vs 28 us)
 template <int TM, bool XP>
-static hipError_t launch_mmt_tm(int kind, int hd, int K, const GemvArgs& a, hipStream_t st) {
+static hipError_t launch_mmt_tm(Op op, int hd, int K, const GemvArgs& a, hipStream_t st) {
     const int mgroups = (a.M + 32 * TM - 1) / (32 * TM);
-    if (kind == 3) {
+    if (op == Op::QKV) {
         const unsigned blocks = (unsigned)(8L * ((a.N / 64 + 7) / 8) * mgroups);
         if (hd == 64) hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE, 64, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
         else hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE, 128, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
-    } else if (kind == 6) {
+    } else if (op == Op::QKV_RAG) {
         if (a.row_slot == nullptr) return hipErrorInvalidValue;
         const unsigned blocks = (unsigned)(8L * ((a.N / 64 + 7) / 8) * mgroups);
         if (hd == 64) hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE_RAG, 64, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
         else hipLaunchKernelGGL((k_mmt<EPI_QKV_ROPE_RAG, 128, TM, 2, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
-    } else if (kind == 4) {
+    } else if (op == Op::SWIGLU) {
         const unsigned blocks = (unsigned)(8L * ((a.N / 32 + 7) / 8) * mgroups);
         hipLaunchKernelGGL((k_mmt<EPI_SWIGLU, 64, TM, 1, XP, MMT_NBUF(TM)>), dim3(blocks), dim3(256), 0, st, a, K, mgroups);
     } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 // xp: a.x in operand order (xp_off, row stride K)
-static hipError_t launch_mmt(int kind, int hd, int K, const GemvArgs& a, hipStream_t st, bool xp = false) {
+static hipError_t launch_mmt(Op op, int hd, int K, const GemvArgs& a, hipStream_t st, bool xp = false) {
     // 96-row groups unless 64-row groups pad fewer rows
     const int pad3 = (a.M + 95) / 96 * 96, pad2 = (a.M + 63) / 64 * 64;
-    if (xp) return pad3 <= pad2 ? launch_mmt_tm<3, true>(kind, hd, K, a, st) : launch_mmt_tm<2, true>(kind, hd, K, a, st);
-    return pad3 <= pad2 ? launch_mmt_tm<3, false>(kind, hd, K, a, st) : launch_mmt_tm<2, false>(kind, hd, K, a, st);
+    if (xp) return pad3 <= pad2 ? launch_mmt_tm<3, true>(op, hd, K, a, st) : launch_mmt_tm<2, true>(op, hd, K, a, st);
+    return pad3 <= pad2 ? launch_mmt_tm<3, false>(op, hd, K, a, st) : launch_mmt_tm<2, false>(op, hd, K, a, st);
 }
 // residual projection of a prompt: the four K-quarter slabs (the finisher adds them in order: KG = 4)
 template <bool XP>
@@ -395,44 +369,31 @@ static hipError_t launch_g128_mi(const GemvArgs& a, int K, hipStream_t st) {
     const long blocks128 = (long)((a.M + 127) / 128) * ((a.N + nout - 1) / nout) * (EPI == EPI_SLAB ? 4 : 1);
     return blocks128 <= G64_MAX_BLOCKS ? launch_g128_t<EPI, HD, 1>(a, K, st) : launch_g128_t<EPI, HD, 2>(a, K, st);
 }
-static hipError_t launch_g128(int kind, int K, int hd, const GemvArgs& a, hipStream_t st) {
+static hipError_t launch_g128(Op op, int K, int hd, const GemvArgs& a, hipStream_t st) {
     if (K % 256 != 0) return hipErrorInvalidValue;
-    switch (kind) {
-        case 0: return launch_g128_mi<EPI_STORE, 64>(a, K, st);
-        case 1: return launch_g128_mi<EPI_RESID, 64>(a, K, st);
-        case 5: return launch_g128_mi<EPI_SLAB, 64>(a, K, st);
-        case 3: return hd == 64 ? launch_g128_mi<EPI_QKV_ROPE, 64>(a, K, st) : launch_g128_mi<EPI_QKV_ROPE, 128>(a, K, st);
-        case 4: return launch_g128_mi<EPI_SWIGLU, 64>(a, K, st);
-        case 6: if (a.row_slot == nullptr) return hipErrorInvalidValue;
+    switch (op) {
+        case Op::STORE: return launch_g128_mi<EPI_STORE, 64>(a, K, st);
+        case Op::RESID: return launch_g128_mi<EPI_RESID, 64>(a, K, st);
+        case Op::SLAB: return launch_g128_mi<EPI_SLAB, 64>(a, K, st);         // the four fp32 K-quarter slabs
+        case Op::QKV: return hd == 64 ? launch_g128_mi<EPI_QKV_ROPE, 64>(a, K, st) : launch_g128_mi<EPI_QKV_ROPE, 128>(a, K, st);
+        case Op::SWIGLU: return launch_g128_mi<EPI_SWIGLU, 64>(a, K, st);
+        case Op::QKV_RAG: if (a.row_slot == nullptr) return hipErrorInvalidValue;
                 return hd == 64 ? launch_g128_mi<EPI_QKV_ROPE_RAG, 64>(a, K, st) : launch_g128_mi<EPI_QKV_ROPE_RAG, 128>(a, K, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+// one projection through the family the plan (or the public kind) names; kg: slabs of Op::SLAB (k_mmq and k_gemm128 always write four)
+static hipError_t launch_proj(Fam fam, Op op, int K, int hd, const GemvArgs& a, hipStream_t st, bool f8 = false, bool xp = false, int kg = 1) {
+    switch (fam) {
+        case Fam::GEMV: return launch_gemv(op, K, hd, a, st, f8);
+        case Fam::MM32: return launch_mm(op, K, hd, a, st, f8, xp, kg);
+        case Fam::MMT: return f8 ? hipErrorInvalidValue : launch_mmt(op, hd, K, a, st, xp);
+        case Fam::MMQ: return f8 || op != Op::SLAB ? hipErrorInvalidValue : launch_mmq(K, a, st, xp);
+        case Fam::G128: return f8 || xp ? hipErrorInvalidValue : launch_g128(op, K, hd, a, st);
     }
     return hipErrorInvalidValue;
 }
 
-// residual projections of the wide path: fp32 partial tiles into a.slab, K split over `kg` blocks
-static int slab_groups(int K, bool prompt) {
-    // Prompt rows must not depend on how many rows share the call (prefix-KV reuse is bit-identical to a cold
-    // prefill): no split there -- the four K quarters of a block's waves are the canonical summation order that
-    // k_gemm128 reproduces for long prompts.
-    if (prompt) return 1;
-    // Decode steps (M <= a few row tiles): one block pulls its bytes through ONE CU at ~70 GB/s, so spread K over
-    // up to 8 blocks of >= 256 k each (measured at M = 32: K 1024 -> kg 1/2/4 = 5.1/3.9/3.3 us, K 2048 N 2048 ->
-    // kg 2/4/8 = 5.4/4.3/4.4 us; K 8192 -> 8 x 1024: blocks of 2048 or 4096 k are 3 % / 12 % slower end to end)
-    static const int per_block = sw_int(SW_CSM_SLAB_K, 256);
-    int kg = K / per_block;
-    return kg < 1 ? 1 : (kg > 8 ? 8 : kg);
-}
-static hipError_t launch_mm_slab(int K, int kg, const GemvArgs& a, hipStream_t st, bool f8 = false, bool xp = false) {
-    if (K % (256 * kg) != 0) return hipErrorInvalidValue;
-    dim3 grid; int mtiles;
-    mm_grid(a, kg, &grid, &mtiles);
-    if (xp) {
-        if (f8) hipLaunchKernelGGL((k_mm32<EPI_SLAB, 64, 4, 1, true>), grid, dim3(256), 0, st, a, K, mtiles, kg);
-        else hipLaunchKernelGGL((k_mm32<EPI_SLAB, 64, 4, 0, true>), grid, dim3(256), 0, st, a, K, mtiles, kg);
-    } else if (f8) hipLaunchKernelGGL((k_mm32<EPI_SLAB, 64, 4, 1>), grid, dim3(256), 0, st, a, K, mtiles, kg);
-    else hipLaunchKernelGGL((k_mm32<EPI_SLAB, 64, 4, 0>), grid, dim3(256), 0, st, a, K, mtiles, kg);
-    return hipGetLastError();
-}
 static hipError_t launch_resid_norm(bf16_t* h, const float* slab, int kg, int M, int N, long row_step, long row_first, int M_out,
                                     const bf16_t* scale, float eps, bf16_t* xn, long xn_stride, hipStream_t st, bool prompt = true,
                                     bool xn_packed = false) {
@@ -521,173 +482,134 @@ static hipError_t launch_rag_take_last(const bf16_t* xn, int d, bf16_t* out, lon
 // where the stack's final RMSNorm of each sequence's LAST row goes on the wide path (fused into the last finisher)
 struct FinalNorm { const bf16_t* scale; bf16_t* out; long out_stride; };
 
-static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf16_t* att, bf16_t* act,
-                                 int M, int rows_per_seq, const int* pos, hipStream_t st, bool prompt, const FinalNorm& fin,
-                                 bool x_normed, bool qkv0_done, int l_begin = 0, int l_end = -1, const RagLaunch* rag = nullptr) {
-    // rag: the M rows are the segments of a group (prompt rows of several slots, rows_per_seq == M): q|k|v appends each row to ITS slot's
-    // cache, attention walks each segment's own keys and the final norm takes each segment's last row; every other launch is row-wise
-    // [l_begin, l_end): a prompt may run a few layers per call (csm_refill_advance): what carries over between calls is h (the residual
-    // stream) and att (the next layer's normalised input, written by the previous layer's finisher) -- and the K/V the layers appended
-    if (l_end < 0) l_end = S.d.n_layers;
-    // unfused wide-M layer: norm -> MFMA qkv(+rope, KV append) -> attention -> MFMA o-proj(+res) ->
-    // norm -> MFMA gate/up(SiLU*up) -> MFMA down(+res).  `att` doubles as the normalised-activation buffer.
-    const int d = S.d.dim;
+// the seven matrices of a layer in one of the four streams (stack_plan.h), with their per-row scales (nullptr for bf16)
+struct LayerW { const bf16_t *wq, *wk, *wv, *wo, *w1, *w3, *w2; const float *sq, *sk, *sv, *so, *s1, *s3, *s2; };
+static LayerW layer_weights(const Stack& S, int l, Stream stream) {
+    const CsmLayerWeights& w = stream == Stream::ROW_BF16 ? S.lw[l] : stream == Stream::ROW_E4M3 ? S.w8[l] : stream == Stream::PACK_BF16 ? S.pk[l] : S.pk8[l];
+    LayerW r = {(const bf16_t*)w.wq, (const bf16_t*)w.wk, (const bf16_t*)w.wv, (const bf16_t*)w.wo, (const bf16_t*)w.w1, (const bf16_t*)w.w3, (const bf16_t*)w.w2,
+                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (stream_e4m3(stream)) {
+        const CsmLayerWeights& c = S.w8s[l];
+        r.sq = (const float*)c.wq; r.sk = (const float*)c.wk; r.sv = (const float*)c.wv; r.so = (const float*)c.wo;
+        r.s1 = (const float*)c.w1; r.s3 = (const float*)c.w3; r.s2 = (const float*)c.w2;
+    }
+    return r;
+}
+static StackDims stack_dims(const CsmModel* m, const Stack& S) {
+    return StackDims{S.d.dim, S.nq, S.nkv, S.d.ffn, S.hd, S.d.n_heads, S.d.n_kv_heads, S.cache_len, &S == &m->bb};
+}
+// THE place that hands the selection its inputs (stack_plan.h)
+static PlanKnobs plan_knobs(const CsmModel* m) {
+    static const int slab_k = sw_int(SW_CSM_SLAB_K, 256);
+    return PlanKnobs{m->wide_path, m->wide_min, G128_MIN_ROWS, MMT_MIN_ROWS, MMT_OPS, slab_k, m->part_rows, m->xpack != 0, m->xpack_prompt != 0, m->fp8_wide != 0,
+                     m->attn_ctr != nullptr, m->bb_block && !m->bb_disabled, m->bb_layer, m->bb_layer8, m->fuse_dec_attn != 0};
+}
+
+// One layer's launches read their rows through these.  x [M][K] (stride K) against w0 (w1, w2) / s0 (s1, s2) of N rows; every other word zero.
+static GemvArgs proj_args(const bf16_t* x, int K, int M, int N, const bf16_t* w0, const float* s0, const bf16_t* w1 = nullptr, const float* s1 = nullptr) {
+    GemvArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = x; a.x_row_stride = K; a.M = M; a.N = N; a.w0 = w0; a.s0 = s0; a.w1 = w1; a.s1 = s1;
+    return a;
+}
+// a layer's cache rows, positions and row shape: what q|k|v, the attention and the fused o-proj share
+struct LayerRows { bf16_t *kc, *vc; int M, rows_per_seq; const int* pos; int pos_base; };
+// q|k|v + RoPE + KV append into q [M][nq] (the narrow form adds its norm; a group adds row_slot -- never both row_slot and aq: one word)
+static GemvArgs qkv_args(const Stack& S, const LayerW& W, const LayerRows& r, const bf16_t* x, bf16_t* q, long ldo) {
+    GemvArgs a = proj_args(x, S.d.dim, r.M, S.nq + 2 * S.nkv, W.wq, W.sq, W.wk, W.sk);
+    a.w2 = W.wv; a.s2 = W.sv; a.out = q; a.ldo = ldo;
+    a.nq = S.nq; a.nkv = S.nkv; a.smax = S.cache_len; a.rows_per_seq = r.rows_per_seq; a.kv_heads = S.d.n_kv_heads;
+    a.pos = r.pos; a.pos_base = r.pos_base; a.rope = S.rope; a.kcache = r.kc; a.vcache = r.vc;
+    return a;
+}
+static AttnArgs attn_args(const CsmModel* m, const Stack& S, const LayerRows& r, const bf16_t* q, bf16_t* out, int nsplit) {
+    AttnArgs t;
+    t.q = q; t.kcache = r.kc; t.vcache = r.vc; t.pos = r.pos; t.M = r.M; t.rows_per_seq = r.rows_per_seq;
+    t.H = S.d.n_heads; t.KV = S.d.n_kv_heads; t.smax = S.cache_len; t.nsplit = nsplit;
+    t.scale = 1.0f / sqrtf((float)S.hd); t.out = out; t.part = m->part; t.out_packed = 0; t.ctr = nullptr;
+    return t;
+}
+// o-proj and down: x [M][K] -> h [M][d], as fp32 slabs for a finisher (slab != nullptr) or with the kernel's own residual epilogue
+static GemvArgs resid_args(const bf16_t* x, int K, int M, int d, const bf16_t* w, const float* s, bf16_t* h, float* slab) {
+    GemvArgs a = proj_args(x, K, M, d, w, s);
+    if (slab) a.slab = slab;
+    else { a.out = h; a.ldo = d; a.resid = h; }
+    return a;
+}
+static GemvArgs swiglu_args(const Stack& S, const LayerW& W, const bf16_t* x, int M, bf16_t* act) {
+    GemvArgs a = proj_args(x, S.d.dim, M, S.d.ffn, W.w1, W.s1, W.w3, W.s3);
+    a.out = act; a.ldo = S.d.ffn;
+    return a;
+}
+// a head: V logits of each of the B rows x + b * stride + offset
+static GemvArgs head_args(const bf16_t* x, long stride, long offset, int K, int B, int V, const void* w, const void* s, bf16_t* logits, long ldl) {
+    GemvArgs a = proj_args(x, K, B, V, (const bf16_t*)w, (const float*)s);
+    a.x_row_stride = stride; a.x_row_offset = offset; a.out = logits; a.ldo = ldl; a.nt = 1;
+    return a;
+}
+
+// what a run_stack call sets beyond its rows; the defaults are a whole decode step on the path its row count selects
+struct StackOpts {
+    bool force_wide = false;        // prompt rows: the matrix-core path whatever M, in its prompt forms
+    bool x_normed = false;          // att already holds layer 0's normalised input
+    bool qkv0_done = false;         // layer 0's q / k / v are in place (depth-decoder step >= 2: gathered from the precomputed table by the sampler)
+    int l_begin = 0, l_end = -1;    // layers [l_begin, l_end), -1 = all: a prompt may run a few layers per call (csm_refill_advance): what carries over between
+                                    // calls is h (the residual stream) and att (the next layer's normalised input, written by the previous layer's finisher) -- and the K/V
+    bf16_t* fin_out = nullptr;      // backbone: where the final-normed last rows go instead of dec_in
+    const RagLaunch* rag = nullptr; // the M rows are the segments of a group (prompt rows of several slots, rows_per_seq == M): q|k|v appends each row to ITS slot's
+                                    // cache, attention walks each segment's own keys and the final norm takes each segment's last row; every other launch is row-wise
+};
+
+static StackOpts prompt_opts(bool prompt) { StackOpts o; o.force_wide = prompt; return o; }
+
+// unfused wide-M layer: norm -> MFMA qkv(+rope, KV append) -> attention -> MFMA o-proj -> finisher (h += slabs, mlp_norm) ->
+// MFMA gate/up(SiLU*up) -> MFMA down -> finisher (next layer's sa_norm, or the stack's final norm).  `att` doubles as the normalised-activation
+// buffer.  Which kernel each step launches is the plan's (stack_plan.h), computed by run_stack once for the call.
+static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf16_t* att, bf16_t* act, int M, int rows_per_seq, const int* pos,
+                                 hipStream_t st, const WidePlan& P, const FinalNorm& fin, const StackOpts& o) {
+    const int d = S.d.dim, l_end = o.l_end < 0 ? S.d.n_layers : o.l_end;
+    const bool prompt = o.force_wide, fprompt = P.big || prompt;      // (the LDS-tiled arm's finishers are always the prompt form)
+    const RagLaunch* rag = o.rag;
     hipError_t e;
-    // 128 x 128 LDS-tiled kernels (same bits as the path below) for prefill; decode steps (<= 2 rows per sequence) stay on
-    // the 32-row-tile kernels with operand-order activations whatever the batch (B = 256: 13.7 vs 21 ms)
-    const bool big = M >= G128_MIN_ROWS && (prompt || rows_per_seq > 2);
-    for (int l = l_begin; l < l_end; ++l) {
+    // h += the kg slabs (kg == 0: the projection added them itself), then rows row_first + i * row_step, i < M_out, normalised into xn
+    auto finish = [&](int kg, const void* scale, long row_step, long row_first, int M_out, bf16_t* xn, long xn_stride, bool packed) {
+        if (kg) return launch_resid_norm(h, m->slab, kg, M, d, row_step, row_first, M_out, (const bf16_t*)scale, S.d.norm_eps, xn, xn_stride, st, fprompt, packed);
+        return launch_rmsnorm_rows(h, row_step * d, row_first * d, M_out, d, (const bf16_t*)scale, S.d.norm_eps, xn, xn_stride, st);
+    };
+    for (int l = o.l_begin; l < l_end; ++l) {
         const CsmLayerWeights& w = S.lw[l];
-        const CsmLayerWeights& pk = S.pk[l];
-        bf16_t* kc = S.kc + (long)l * S.layer_stride + S.slot_off;
-        bf16_t* vc = S.vc + (long)l * S.layer_stride + S.slot_off;
-        GemvArgs a;
-        if (big) {
-            if (l == 0 && !x_normed && (e = launch_rmsnorm_rows(h, d, 0, M, d, (const bf16_t*)w.sa_norm, S.d.norm_eps, att, d, st)) != hipSuccess) return e;
-            memset(&a, 0, sizeof a);
-            a.x = att; a.x_row_stride = d; a.M = M;
-            a.w0 = (const bf16_t*)w.wq; a.w1 = (const bf16_t*)w.wk; a.w2 = (const bf16_t*)w.wv;
-            a.N = S.nq + 2 * S.nkv; a.out = q; a.ldo = S.nq;
-            a.nq = S.nq; a.nkv = S.nkv; a.smax = S.cache_len; a.rows_per_seq = rows_per_seq; a.kv_heads = S.d.n_kv_heads;
-            a.pos = pos; a.rope = S.rope; a.kcache = kc; a.vcache = vc;
-            if (rag) a.row_slot = rag->row_slot;
-            if ((e = launch_g128(rag ? 6 : 3, d, S.hd, a, st)) != hipSuccess) return e;
-            AttnArgs t;
-            t.q = q; t.kcache = kc; t.vcache = vc; t.pos = pos; t.M = M; t.rows_per_seq = rows_per_seq;
-            t.H = S.d.n_heads; t.KV = S.d.n_kv_heads; t.smax = S.cache_len; t.nsplit = 1;
-            t.scale = 1.0f / sqrtf((float)S.hd); t.out = att; t.part = m->part; t.out_packed = 0; t.ctr = nullptr;
-            if ((e = rag ? launch_attn_rag(S, t, *rag, st) : launch_attn_auto(S, t, prompt, st)) != hipSuccess) return e;
-            memset(&a, 0, sizeof a);
-            // residual projections: d/128 column tiles only -- below ~2 tiles per CU split K into its four quarters over
-            // blocks (fp32 slabs) and let the small path's finisher add them, the residual and the next norm
-            const bool quarter_slabs = (long)((M + 127) / 128) * ((d + 127) / 128) < 512 && d <= 2048;
-            a.x = att; a.x_row_stride = S.nq; a.M = M; a.w0 = (const bf16_t*)w.wo; a.N = d; a.out = h; a.ldo = d; a.resid = h;
-            if (quarter_slabs) {
-                a.slab = m->slab;
-                if ((e = launch_g128(5, S.nq, S.hd, a, st)) != hipSuccess) return e;
-                if ((e = launch_resid_norm(h, m->slab, 4, M, d, 1, 0, M, (const bf16_t*)w.mlp_norm, S.d.norm_eps, att, d, st)) != hipSuccess) return e;
-            } else {
-                if ((e = launch_g128(1, S.nq, S.hd, a, st)) != hipSuccess) return e;
-                if ((e = launch_rmsnorm_rows(h, d, 0, M, d, (const bf16_t*)w.mlp_norm, S.d.norm_eps, att, d, st)) != hipSuccess) return e;
-            }
-            memset(&a, 0, sizeof a);
-            a.x = att; a.x_row_stride = d; a.M = M; a.w0 = (const bf16_t*)w.w1; a.w1 = (const bf16_t*)w.w3; a.N = S.d.ffn;
-            a.out = act; a.ldo = S.d.ffn;
-            if ((e = launch_g128(4, d, S.hd, a, st)) != hipSuccess) return e;
-            memset(&a, 0, sizeof a);
-            a.x = act; a.x_row_stride = S.d.ffn; a.M = M; a.w0 = (const bf16_t*)w.w2; a.N = d; a.out = h; a.ldo = d; a.resid = h;
-            const int nseq = M / rows_per_seq;
-            if (quarter_slabs) {
-                a.slab = m->slab;
-                if ((e = launch_g128(5, S.d.ffn, S.hd, a, st)) != hipSuccess) return e;
-                if (l + 1 < S.d.n_layers) e = launch_resid_norm(h, m->slab, 4, M, d, 1, 0, M, (const bf16_t*)S.lw[l + 1].sa_norm, S.d.norm_eps, att, d, st);
-                else if (rag) {
-                    e = launch_resid_norm(h, m->slab, 4, M, d, 1, 0, M, fin.scale, S.d.norm_eps, att, d, st);
-                    if (e == hipSuccess) e = launch_rag_take_last(att, d, fin.out, fin.out_stride, rag->sg, st);
-                }
-                else e = launch_resid_norm(h, m->slab, 4, M, d, rows_per_seq, rows_per_seq - 1, nseq, fin.scale, S.d.norm_eps, fin.out, fin.out_stride, st);
-                if (e != hipSuccess) return e;
-                continue;
-            }
-            if ((e = launch_g128(1, S.d.ffn, S.hd, a, st)) != hipSuccess) return e;
-            if (l + 1 < S.d.n_layers) {
-                if ((e = launch_rmsnorm_rows(h, d, 0, M, d, (const bf16_t*)S.lw[l + 1].sa_norm, S.d.norm_eps, att, d, st)) != hipSuccess) return e;
-            } else if (rag) {
-                if ((e = launch_rmsnorm_rows(h, d, 0, M, d, fin.scale, S.d.norm_eps, att, d, st)) != hipSuccess) return e;
-                if ((e = launch_rag_take_last(att, d, fin.out, fin.out_stride, rag->sg, st)) != hipSuccess) return e;
-            } else {
-                if ((e = launch_rmsnorm_rows(h, (long)rows_per_seq * d, (long)(rows_per_seq - 1) * d, nseq, d, fin.scale, S.d.norm_eps,
-                                             fin.out, fin.out_stride, st)) != hipSuccess) return e;
-            }
-            continue;
-        }
-        // decode steps in fp8 mode stream the e4m3 copies (same values as the bf16 weights, which are their
-        // dequantisation: identical bits, half the bytes); prompts keep the bf16 stream they share with k_gemm128
-        const bool f8 = S.has_pk8 && !prompt && m->fp8_wide;
-        const CsmLayerWeights& p8 = S.pk8[l];
-        // decode steps keep their activations (xn, attention output, SiLU*up) in matrix-core operand order between
-        // the kernels of a layer (common.cuh xp_off): producers write it, consumers read 1 KB pieces
-        // (from 24 rows: a 1 KB piece always carries 32 rows, so for a few rows the row-major gather touches fewer lines:
-        //  B=8 5.39 vs 5.52 ms packed, B=32 6.15 vs 6.01, B=64 7.42 vs 6.93, B=128 10.29 vs 9.07)
-        const bool xp_decode = m->xpack && !prompt && rows_per_seq <= 2 && M >= 24 && (d == 512 || d == 1024 || d == 2048);
-        // prompts below the LDS-tiled kernels' row count do the same (round 2): their projections were bound by exactly those
-        // gathers (TA address cycles, 64 lines per fragment), not by bytes
-        const bool xp_prompt = m->xpack_prompt && (prompt || rows_per_seq > 2) && !f8 && M >= 24 && d % 64 == 0 && S.nq % 64 == 0 && S.d.ffn % 64 == 0 && d <= 2048;
-        const bool xp = xp_decode || xp_prompt;
-        const bool xp0 = xp_prompt && !x_normed;            // layer 0's normalised input is written here: operand order too
-        // prompts of 64..256 rows (prompt mode or a plain multi-row prefill; never decode steps): the several-tiles-per-wave
-        // forms of k_mm32 (prompt mode: same bits; half the L2 traffic)
-        const bool mid = (prompt || rows_per_seq > 2) && !f8 && mmt_ok(M, d, S.nq + 2 * S.nkv) && mmt_ok(M, S.nq, d) && mmt_ok(M, d, S.d.ffn) && mmt_ok(M, S.d.ffn, d);
+        const LayerW W = layer_weights(S, l, P.stream);
+        const LayerRows r = {S.kc + (long)l * S.layer_stride + S.slot_off, S.vc + (long)l * S.layer_stride + S.slot_off, M, rows_per_seq, pos, 0};
         // layer 0 normalises h directly; later layers got xn from the previous down-projection's finisher.
-        // (layer 0 of a depth-decoder step >= 2: q/k/v were gathered from the precomputed table by the sampler)
-        int kg = 1;
-        if (!(l == 0 && qkv0_done)) {
-            if (l == 0 && !x_normed && (e = launch_rmsnorm_rows(h, d, 0, M, d, (const bf16_t*)w.sa_norm, S.d.norm_eps, att, d, st, xp0)) != hipSuccess) return e;
-            memset(&a, 0, sizeof a);
-            a.x = att; a.x_row_stride = d; a.M = M;
-            a.w0 = (const bf16_t*)pk.wq; a.w1 = (const bf16_t*)pk.wk; a.w2 = (const bf16_t*)pk.wv;
-            a.N = S.nq + 2 * S.nkv; a.out = q; a.ldo = S.nq;
-            a.nq = S.nq; a.nkv = S.nkv; a.smax = S.cache_len; a.rows_per_seq = rows_per_seq; a.kv_heads = S.d.n_kv_heads;
-            a.pos = pos; a.rope = S.rope; a.kcache = kc; a.vcache = vc;
-            if (f8) {
-                a.w0 = (const bf16_t*)p8.wq; a.w1 = (const bf16_t*)p8.wk; a.w2 = (const bf16_t*)p8.wv;
-                a.s0 = (const float*)S.w8s[l].wq; a.s1 = (const float*)S.w8s[l].wk; a.s2 = (const float*)S.w8s[l].wv;
-            }
-            const bool xq = l > 0 ? xp : xp0;                  // (decode steps: layer 0's input comes row-major)
+        if (!(l == 0 && o.qkv0_done)) {
+            if (l == 0 && !o.x_normed && (e = launch_rmsnorm_rows(h, d, 0, M, d, (const bf16_t*)w.sa_norm, S.d.norm_eps, att, d, st, P.xp0)) != hipSuccess) return e;
+            GemvArgs a = qkv_args(S, W, r, att, q, S.nq);
             if (rag) a.row_slot = rag->row_slot;
-            if (mid && (MMT_OPS & 1)) e = launch_mmt(rag ? 6 : 3, S.hd, d, a, st, xq);
-            else e = launch_mm(rag ? 6 : 3, d, S.hd, a, st, f8, xq);
-            if (e != hipSuccess) return e;
+            if ((e = launch_proj(P.qkv, qkv_op(rag != nullptr), d, S.hd, a, st, P.f8, l > 0 ? P.xp : P.xp0)) != hipSuccess) return e;
         }
-        AttnArgs t;
-        t.q = q; t.kcache = kc; t.vcache = vc; t.pos = pos; t.M = M; t.rows_per_seq = rows_per_seq;
-        t.H = S.d.n_heads; t.KV = S.d.n_kv_heads; t.smax = S.cache_len; t.nsplit = 1;
-        t.scale = 1.0f / sqrtf((float)S.hd); t.out = att; t.part = m->part; t.out_packed = xp; t.ctr = nullptr;
-        // batched backbone decode step (one row per sequence, long key ranges): a (row, KV head) block alone walks
-        // its ~200+ keys in ~8 dependent round trips -- split the keys over up to 8 blocks like the B = 1 path
-        if (!prompt && rows_per_seq == 1 && &S == &m->bb && M <= m->part_rows) {
-            int ns = 1024 / (M * S.d.n_kv_heads);
-            t.nsplit = ns < 1 ? 1 : (ns > BB_NSPLIT_MAX ? BB_NSPLIT_MAX : ns);
-            if (t.nsplit > 1) t.ctr = m->attn_ctr;            // the last key-range block of a (row, KV head) merges (no k_attn_combine launch)
-        }
+        AttnArgs t = attn_args(m, S, r, q, att, P.nsplit);
+        t.out_packed = P.xp;
+        if (P.merge_in_kernel) t.ctr = m->attn_ctr;            // the last key-range block of a (row, KV head) merges (no k_attn_combine launch)
         if ((e = rag ? launch_attn_rag(S, t, *rag, st) : launch_attn_auto(S, t, prompt, st)) != hipSuccess) return e;
-        // o-proj -> fp32 slabs; finisher: h += sum(slabs), xn = mlp_norm(h)
-        memset(&a, 0, sizeof a);
-        a.x = att; a.x_row_stride = S.nq; a.M = M; a.w0 = (const bf16_t*)pk.wo; a.N = d; a.slab = m->slab;
-        kg = mid && (MMT_OPS & 4) ? 4 : slab_groups(S.nq, prompt);
-        if (f8) { a.w0 = (const bf16_t*)p8.wo; a.s0 = (const float*)S.w8s[l].wo; }
-        if (mid && (MMT_OPS & 4)) e = launch_mmq(S.nq, a, st, xp);
-        else e = launch_mm_slab(S.nq, kg, a, st, f8, xp);
+        // o-proj; finisher: h += sum(slabs), xn = mlp_norm(h)
+        GemvArgs a = resid_args(att, S.nq, M, d, W.wo, W.so, h, P.o_proj.kg ? m->slab : nullptr);
+        if ((e = launch_proj(P.o_proj.fam, P.o_proj.kg ? Op::SLAB : Op::RESID, S.nq, S.hd, a, st, P.f8, P.xp, P.o_proj.kg)) != hipSuccess) return e;
+        if ((e = finish(P.o_proj.kg, w.mlp_norm, 1, 0, M, att, d, P.xp)) != hipSuccess) return e;
+        a = swiglu_args(S, W, att, M, act);
+        a.out_packed = P.xp;
+        if ((e = launch_proj(P.gate_up, Op::SWIGLU, d, S.hd, a, st, P.f8, P.xp)) != hipSuccess) return e;
+        // down-proj; finisher applies the NEXT layer's sa_norm
+        const int kg = P.down.kg;
+        a = resid_args(act, S.d.ffn, M, d, W.w2, W.s2, h, kg ? m->slab : nullptr);
+        if ((e = launch_proj(P.down.fam, kg ? Op::SLAB : Op::RESID, S.d.ffn, S.hd, a, st, P.f8, P.xp, kg)) != hipSuccess) return e;
+        if (l + 1 < S.d.n_layers) e = finish(kg, S.lw[l + 1].sa_norm, 1, 0, M, att, d, P.xp);
+        else if (rag) {
+            // last layer of a group: the stack's final norm of every row (row-major xn: the prompt form, not in operand order), then each segment's last row
+            e = finish(kg, fin.scale, 1, 0, M, att, d, false);
+            if (e == hipSuccess) e = launch_rag_take_last(att, d, fin.out, fin.out_stride, rag->sg, st);
+        }   // last layer: only each sequence's last row is read again (heads / last_h); its finisher applies the stack's final norm
+        else e = finish(kg, fin.scale, rows_per_seq, rows_per_seq - 1, M / rows_per_seq, fin.out, fin.out_stride, false);
         if (e != hipSuccess) return e;
-        if ((e = launch_resid_norm(h, m->slab, kg, M, d, 1, 0, M, (const bf16_t*)w.mlp_norm, S.d.norm_eps, att, d, st, prompt, xp)) != hipSuccess) return e;
-        memset(&a, 0, sizeof a);
-        a.x = att; a.x_row_stride = d; a.M = M; a.w0 = (const bf16_t*)pk.w1; a.w1 = (const bf16_t*)pk.w3; a.N = S.d.ffn;
-        a.out = act; a.ldo = S.d.ffn; a.out_packed = xp;
-        if (f8) { a.w0 = (const bf16_t*)p8.w1; a.w1 = (const bf16_t*)p8.w3; a.s0 = (const float*)S.w8s[l].w1; a.s1 = (const float*)S.w8s[l].w3; }
-        if (mid && (MMT_OPS & 2)) e = launch_mmt(4, S.hd, d, a, st, xp);
-        else e = launch_mm(4, d, S.hd, a, st, f8, xp);
-        if (e != hipSuccess) return e;
-        // down-proj -> slabs; finisher applies the NEXT layer's sa_norm (or nothing after the last layer)
-        memset(&a, 0, sizeof a);
-        a.x = act; a.x_row_stride = S.d.ffn; a.M = M; a.w0 = (const bf16_t*)pk.w2; a.N = d; a.slab = m->slab;
-        kg = mid && (MMT_OPS & 8) ? 4 : slab_groups(S.d.ffn, prompt);
-        if (f8) { a.w0 = (const bf16_t*)p8.w2; a.s0 = (const float*)S.w8s[l].w2; }
-        if (mid && (MMT_OPS & 8)) e = launch_mmq(S.d.ffn, a, st, xp);
-        else e = launch_mm_slab(S.d.ffn, kg, a, st, f8, xp);
-        if (e != hipSuccess) return e;
-        if (l + 1 < S.d.n_layers) {
-            if ((e = launch_resid_norm(h, m->slab, kg, M, d, 1, 0, M, (const bf16_t*)S.lw[l + 1].sa_norm, S.d.norm_eps, att, d, st, prompt, xp)) != hipSuccess) return e;
-        } else {
-            // last layer: only each sequence's last row is read again (heads / last_h); its finisher applies the
-            // stack's final norm
-            const int nseq = M / rows_per_seq;
-            if (rag) {             // (row-major xn: the prompt form of the finisher, not in operand order)
-                e = launch_resid_norm(h, m->slab, kg, M, d, 1, 0, M, fin.scale, S.d.norm_eps, att, d, st, prompt);
-                if (e == hipSuccess) e = launch_rag_take_last(att, d, fin.out, fin.out_stride, rag->sg, st);
-            } else e = launch_resid_norm(h, m->slab, kg, M, d, rows_per_seq, rows_per_seq - 1, nseq, fin.scale, S.d.norm_eps,
-                                       fin.out, fin.out_stride, st, prompt);
-            if (e != hipSuccess) return e;
-        }
     }
     return hipSuccess;
 }
@@ -695,124 +617,76 @@ static hipError_t run_stack_wide(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf
 // pos: per-row positions (always valid); pos_const >= 0: all rows of a sequence sit at pos_const + row-in-sequence
 // (depth decoder), which lets the narrow path drop the dependent position load
 static hipError_t run_stack(CsmModel* m, Stack& S, bf16_t* h, bf16_t* q, bf16_t* att, bf16_t* act,
-                            int M, int rows_per_seq, const int* pos_arr, int pos_const, hipStream_t st, bool force_wide = false,
-                            bool x_normed = false, bool qkv0_done = false, int l_begin = 0, int l_end = -1, bf16_t* fin_out = nullptr,
-                            const RagLaunch* rag = nullptr) {
-    if ((M >= m->wide_min || force_wide) && m->wide_path) {
+                            int M, int rows_per_seq, const int* pos_arr, int pos_const, hipStream_t st, const StackOpts& o = StackOpts()) {
+    const StackDims dims = stack_dims(m, S);
+    const PlanKnobs knobs = plan_knobs(m);
+    if (stack_is_wide(knobs, M, o.force_wide)) {
         FinalNorm fin;
-        if (&S == &m->bb) { fin.scale = (const bf16_t*)m->w.bb_norm; fin.out = fin_out ? fin_out : m->dec_in; fin.out_stride = 2L * S.d.dim; }
+        if (&S == &m->bb) { fin.scale = (const bf16_t*)m->w.bb_norm; fin.out = o.fin_out ? o.fin_out : m->dec_in; fin.out_stride = 2L * S.d.dim; }
         else { fin.scale = (const bf16_t*)m->w.dec_norm; fin.out = att; fin.out_stride = S.d.dim; }
-        if (rag && (!force_wide || x_normed || qkv0_done || rows_per_seq != M || &S != &m->bb)) return hipErrorInvalidValue;     // a group: backbone prompt rows only
-        return run_stack_wide(m, S, h, q, att, act, M, rows_per_seq, pos_arr, st, force_wide, fin, x_normed, qkv0_done, l_begin, l_end, rag);
+        if (o.rag && (!o.force_wide || o.x_normed || o.qkv0_done || rows_per_seq != M || &S != &m->bb)) return hipErrorInvalidValue;     // a group: backbone prompt rows only
+        return run_stack_wide(m, S, h, q, att, act, M, rows_per_seq, pos_arr, st, plan_wide(dims, knobs, M, rows_per_seq, o.force_wide, o.x_normed, S.has_pk8), fin, o);
     }
-    if (l_begin != 0 || (l_end >= 0 && l_end != S.d.n_layers) || fin_out != nullptr || rag != nullptr) return hipErrorInvalidValue;      // layer ranges: matrix-core path only
+    if (o.l_begin != 0 || (o.l_end >= 0 && o.l_end != S.d.n_layers) || o.fin_out != nullptr || o.rag != nullptr) return hipErrorInvalidValue;      // layer ranges: matrix-core path only
     const int* pos = pos_const >= 0 ? nullptr : pos_arr;
-    const int pos_base = pos_const >= 0 ? pos_const : 0;
     const int d = S.d.dim;
-    int nsplit = 1;
-    if (&S == &m->bb && M <= PART_ROWS) {
-        nsplit = 256 / (M * S.d.n_kv_heads);
-        nsplit = nsplit < 1 ? 1 : (nsplit > BB_NSPLIT_MAX ? BB_NSPLIT_MAX : nsplit);
-    }
+    const NarrowPlan P = plan_narrow(dims, knobs, M, S.w8 != nullptr, pos != nullptr);
+    const bool f8 = stream_e4m3(P.stream);
     hipError_t e;
     for (int l = 0; l < S.d.n_layers; ++l) {
         const CsmLayerWeights& w = S.lw[l];
-        bf16_t* kc = S.kc + (long)l * S.layer_stride + S.slot_off;
-        bf16_t* vc = S.vc + (long)l * S.layer_stride + S.slot_off;
-        GemvArgs a;
-        memset(&a, 0, sizeof a);
-        a.nt = S.nt_attn;
-        // (1) RMSNorm -> q/k/v projections -> RoPE -> KV append
-        a.x = h; a.x_row_stride = d; a.M = M;
-        a.norm_scale = (const bf16_t*)w.sa_norm; a.eps = S.d.norm_eps;
-        a.w0 = (const bf16_t*)w.wq; a.w1 = (const bf16_t*)w.wk; a.w2 = (const bf16_t*)w.wv;
-        a.N = S.nq + 2 * S.nkv; a.out = q; a.ldo = S.nq;
-        a.nq = S.nq; a.nkv = S.nkv; a.smax = S.cache_len; a.rows_per_seq = rows_per_seq; a.kv_heads = S.d.n_kv_heads;
-        a.pos = pos; a.pos_base = pos_base; a.rope = S.rope; a.kcache = kc; a.vcache = vc;
-        const bool f8 = S.w8 != nullptr;
-        if (f8) {
-            a.w0 = (const bf16_t*)S.w8[l].wq; a.w1 = (const bf16_t*)S.w8[l].wk; a.w2 = (const bf16_t*)S.w8[l].wv;
-            a.s0 = (const float*)S.w8s[l].wq; a.s1 = (const float*)S.w8s[l].wk; a.s2 = (const float*)S.w8s[l].wv;
-        }
-        bool block_done = false;
-        if (&S == &m->bb && M == 1 && m->bb_block && !m->bb_disabled && (!f8 || m->bb_layer8) && pos != nullptr) {
-            // (1)-(3) as ONE launch (bb_block.cuh): q|k|v + RoPE + KV append -> attention -> o-projection + residual
-            BbBlockArgs b;
-            memset(&b, 0, sizeof b);
-            b.wq = (const bf16_t*)w.wq; b.wk = (const bf16_t*)w.wk; b.wv = (const bf16_t*)w.wv; b.wo = (const bf16_t*)w.wo;
-            b.sa_norm = (const bf16_t*)w.sa_norm; b.rope = S.rope; b.h = h; b.kc = kc; b.vc = vc; b.pos = pos; b.smax = S.cache_len;
-            b.eps = S.d.norm_eps; b.gQ = m->bg_q; b.gA = m->bg_a; b.gS = m->bg_s; b.err = m->b_state + 1; b.epoch = m->b_state; b.poll_sleep = m->persist ? m->p_poll : 1;
-            if (m->bb_layer || f8) {
-                // ... and the MLP: the whole layer in one launch
+        const LayerW W = layer_weights(S, l, P.stream);
+        const LayerRows r = {S.kc + (long)l * S.layer_stride + S.slot_off, S.vc + (long)l * S.layer_stride + S.slot_off, M, rows_per_seq, pos, pos_const >= 0 ? pos_const : 0};
+        if (P.layer != NarrowLayer::CHAIN) {
+            // (1)-(3) as ONE launch (bb_block.cuh): q|k|v + RoPE + KV append -> attention -> o-projection + residual; ONE_LAUNCH: and the MLP, the whole
+            // layer (k_bb_layer<true>: the e4m3 stream, bytes + one power-of-two scale per output row)
+            auto fill = [&](auto& b) {                           // BbLayerArgs begins with BbBlockArgs' members
+                memset(&b, 0, sizeof b);
+                b.wq = W.wq; b.wk = W.wk; b.wv = W.wv; b.wo = W.wo; b.sa_norm = (const bf16_t*)w.sa_norm; b.rope = S.rope; b.h = h; b.kc = r.kc; b.vc = r.vc;
+                b.pos = pos; b.smax = S.cache_len; b.eps = S.d.norm_eps; b.gQ = m->bg_q; b.gA = m->bg_a; b.gS = m->bg_s; b.err = m->b_state + 1; b.epoch = m->b_state;
+                b.poll_sleep = m->persist ? m->p_poll : 1;
+            };
+            if (P.layer == NarrowLayer::ATTN_BLOCK) {
+                BbBlockArgs b;
+                fill(b);
+                hipLaunchKernelGGL(k_bb_attn_block, dim3(DP_NB), dim3(512), 0, st, b);
+            } else {
                 BbLayerArgs L;
-                memset(&L, 0, sizeof L);
-                L.wq = b.wq; L.wk = b.wk; L.wv = b.wv; L.wo = b.wo; L.sa_norm = b.sa_norm; L.rope = b.rope; L.h = b.h; L.kc = b.kc; L.vc = b.vc;
-                L.pos = b.pos; L.smax = b.smax; L.eps = b.eps; L.gQ = b.gQ; L.gA = b.gA; L.gS = b.gS; L.err = b.err; L.epoch = b.epoch; L.poll_sleep = b.poll_sleep;
-                L.w1 = (const bf16_t*)w.w1; L.w3 = (const bf16_t*)w.w3; L.mlp_norm = (const bf16_t*)w.mlp_norm;
-                L.gH = m->bg_h; L.gP = m->bg_p;
+                fill(L);
+                L.w1 = W.w1; L.w3 = W.w3; L.mlp_norm = (const bf16_t*)w.mlp_norm; L.gH = m->bg_h; L.gP = m->bg_p;
+                L.sq = W.sq; L.sk = W.sk; L.sv = W.sv; L.so = W.so; L.s1 = W.s1; L.s3 = W.s3; L.s2 = W.s2;
                 L.stamps = (m->p_stamps != nullptr && l == 8) ? m->p_stamps + 5312 : nullptr;        // (timeline build only)
-                if (f8) {
-                    // the e4m3 stream: bytes + one power-of-two scale per output row (k_bb_layer<true>)
-                    const CsmLayerWeights &w8 = S.w8[l], &s8 = S.w8s[l];
-                    L.wq = (const bf16_t*)w8.wq; L.wk = (const bf16_t*)w8.wk; L.wv = (const bf16_t*)w8.wv; L.wo = (const bf16_t*)w8.wo;
-                    L.w1 = (const bf16_t*)w8.w1; L.w3 = (const bf16_t*)w8.w3;
-                    L.sq = (const float*)s8.wq; L.sk = (const float*)s8.wk; L.sv = (const float*)s8.wv; L.so = (const float*)s8.wo;
-                    L.s1 = (const float*)s8.w1; L.s3 = (const float*)s8.w3; L.s2 = (const float*)s8.w2;
-                    L.w2t = m->b_w2t8 + (size_t)l * 256 * 2 * BB_D;
-                    hipLaunchKernelGGL(k_bb_layer<true>, dim3(DP_NB), dim3(512), BL_LDS_BYTES, st, L);
-                } else {
-                    L.w2t = m->b_w2t + (size_t)l * 256 * 4 * BB_D;
-                    hipLaunchKernelGGL(k_bb_layer<false>, dim3(DP_NB), dim3(512), BL_LDS_BYTES, st, L);
-                }
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                continue;
+                L.w2t = f8 ? m->b_w2t8 + (size_t)l * 256 * 2 * BB_D : m->b_w2t + (size_t)l * 256 * 4 * BB_D;
+                if (f8) hipLaunchKernelGGL(k_bb_layer<true>, dim3(DP_NB), dim3(512), BL_LDS_BYTES, st, L);
+                else hipLaunchKernelGGL(k_bb_layer<false>, dim3(DP_NB), dim3(512), BL_LDS_BYTES, st, L);
             }
-            hipLaunchKernelGGL(k_bb_attn_block, dim3(DP_NB), dim3(512), 0, st, b);
             if ((e = hipGetLastError()) != hipSuccess) return e;
-            block_done = true;
-        }
-        // (layer 0 of a depth-decoder step >= 2: the sampler already gathered q/k/v from the precomputed table)
-        if (!block_done && !(l == 0 && qkv0_done) && (e = f8 ? launch_gemv8(3, d, S.hd, a, st) : launch_gemv(3, d, S.hd, a, st)) != hipSuccess) return e;
-        bool fuse_comb = false;
-        const bool fuse_attn = S.hd == 128 && S.cache_len <= 32 && m->fuse_dec_attn && (S.d.n_heads / S.d.n_kv_heads) % 2 == 0;
-        if (!fuse_attn && !block_done) {
+            if (P.layer == NarrowLayer::ONE_LAUNCH) continue;
+        } else {
+            // (1) RMSNorm -> q/k/v projections -> RoPE -> KV append
+            GemvArgs a = qkv_args(S, W, r, h, q, S.nq);
+            a.nt = S.nt_attn; a.norm_scale = (const bf16_t*)w.sa_norm; a.eps = S.d.norm_eps;
+            if (!(l == 0 && o.qkv0_done) && (e = launch_gemv(Op::QKV, d, S.hd, a, st, f8)) != hipSuccess) return e;
             // (2) attention over keys [0, pos]
-            AttnArgs t;
-            t.q = q; t.kcache = kc; t.vcache = vc; t.pos = pos; t.M = M; t.rows_per_seq = rows_per_seq;
-            t.H = S.d.n_heads; t.KV = S.d.n_kv_heads; t.smax = S.cache_len; t.nsplit = nsplit;
-            t.scale = 1.0f / sqrtf((float)S.hd); t.out = att; t.part = m->part; t.out_packed = 0; t.ctr = nullptr;
-            fuse_comb = nsplit > 1 && S.hd == 64;
-            if ((e = launch_attn(S.hd, t, st, !fuse_comb)) != hipSuccess) return e;
-        }
-        // (3) output projection + residual (depth decoder: attention fused into its prologue)
-        memset(&a, 0, sizeof a);
-        a.nt = S.nt_attn;
-        a.x = att; a.x_row_stride = S.nq; a.M = M; a.w0 = (const bf16_t*)w.wo; a.N = d;
-        a.out = h; a.ldo = d; a.resid = h;
-        if (fuse_attn) {
-            a.aq = q; a.aH = S.d.n_heads; a.ascale = 1.0f / sqrtf((float)S.hd); a.kcache = kc; a.vcache = vc;
-            a.pos = pos; a.pos_base = pos_base; a.smax = S.cache_len; a.rows_per_seq = rows_per_seq; a.kv_heads = S.d.n_kv_heads;
-        }
-        if (fuse_comb) { a.part = m->part; a.nsplit = nsplit; a.aH = S.d.n_heads; }
-        if (f8) { a.w0 = (const bf16_t*)S.w8[l].wo; a.s0 = (const float*)S.w8s[l].wo; }
-        if (!block_done) {
-            const int kind = fuse_attn ? 5 : (fuse_comb ? 6 : 1);
-            if ((e = f8 ? launch_gemv8(kind, S.nq, S.hd, a, st) : launch_gemv(kind, S.nq, S.hd, a, st)) != hipSuccess) return e;
+            if (!P.fuse_attn && (e = launch_attn(S.hd, attn_args(m, S, r, q, att, P.nsplit), st, !P.fuse_comb)) != hipSuccess) return e;
+            // (3) output projection + residual (depth decoder: attention fused into its prologue)
+            a = resid_args(att, S.nq, M, d, W.wo, W.so, h, nullptr);
+            a.nt = S.nt_attn;
+            if (P.fuse_attn) {
+                a.aq = q; a.aH = S.d.n_heads; a.ascale = 1.0f / sqrtf((float)S.hd); a.kcache = r.kc; a.vcache = r.vc;
+                a.pos = pos; a.pos_base = r.pos_base; a.smax = S.cache_len; a.rows_per_seq = rows_per_seq; a.kv_heads = S.d.n_kv_heads;
+            }
+            if (P.fuse_comb) { a.part = m->part; a.nsplit = P.nsplit; a.aH = S.d.n_heads; }
+            if ((e = launch_gemv(P.fuse_attn ? Op::ATTN_RESID : P.fuse_comb ? Op::COMBINE_RESID : Op::RESID, S.nq, S.hd, a, st, f8)) != hipSuccess) return e;
         }
         // (4) RMSNorm -> gate/up -> SiLU*up
-        memset(&a, 0, sizeof a);
-        a.nt = S.nt_mlp;
-        a.x = h; a.x_row_stride = d; a.M = M; a.norm_scale = (const bf16_t*)w.mlp_norm; a.eps = S.d.norm_eps;
-        a.w0 = (const bf16_t*)w.w1; a.w1 = (const bf16_t*)w.w3; a.N = S.d.ffn; a.out = act; a.ldo = S.d.ffn;
-        if (f8) { a.w0 = (const bf16_t*)S.w8[l].w1; a.w1 = (const bf16_t*)S.w8[l].w3; a.s0 = (const float*)S.w8s[l].w1; a.s1 = (const float*)S.w8s[l].w3; }
-        if ((e = f8 ? launch_gemv8(4, d, S.hd, a, st) : launch_gemv(4, d, S.hd, a, st)) != hipSuccess) return e;
+        GemvArgs a = swiglu_args(S, W, h, M, act);
+        a.nt = S.nt_mlp; a.norm_scale = (const bf16_t*)w.mlp_norm; a.eps = S.d.norm_eps;
+        if ((e = launch_gemv(Op::SWIGLU, d, S.hd, a, st, f8)) != hipSuccess) return e;
         // (5) down projection + residual
-        memset(&a, 0, sizeof a);
+        a = resid_args(act, S.d.ffn, M, d, W.w2, W.s2, h, nullptr);
         a.nt = S.nt_mlp;
-        a.x = act; a.x_row_stride = S.d.ffn; a.M = M; a.w0 = (const bf16_t*)w.w2; a.N = d;
-        a.out = h; a.ldo = d; a.resid = h;
-        if (f8) { a.w0 = (const bf16_t*)S.w8[l].w2; a.s0 = (const float*)S.w8s[l].w2; }
-        if ((e = f8 ? launch_gemv8(1, S.d.ffn, S.hd, a, st) : launch_gemv(1, S.d.ffn, S.hd, a, st)) != hipSuccess) return e;
+        if ((e = launch_gemv(Op::RESID, S.d.ffn, S.hd, a, st, f8)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -901,6 +775,8 @@ static hipError_t run_depth(CsmModel* m, int B, int S, float temperature, int to
     if (rng == nullptr) rng = m->rng;
     const CsmConfig& c = m->cfg;
     const int dbb = c.backbone.dim, dd = c.decoder.dim, V = c.audio_vocab, ncb = c.n_codebooks;
+    const PlanKnobs knobs = plan_knobs(m);
+    const bool wide = stack_is_wide(knobs, B, false);        // the projection, the heads and the decoder steps of B rows (2 B at codebook 1) on the matrix cores
     hipError_t e;
     for (int cb = 0; cb < ncb; ++cb) {
         GemvArgs a;
@@ -913,12 +789,9 @@ static hipError_t run_depth(CsmModel* m, int B, int S, float temperature, int to
             if (cb == 1) {
                 // first decoder call: rows (last_h, emb(c0)) per sequence.  Row 1 was gathered from the
                 // projected-embedding table by the c0 sampler; row 0 = projection(last_h) is the one GEMV.
-                memset(&a, 0, sizeof a);
-                a.x = m->dec_in; a.x_row_stride = 2L * dbb; a.M = B;
-                a.w0 = (const bf16_t*)m->w.projection; a.N = dd; a.out = m->hdec; a.ldo = 2L * dd; a.nt = 0;
-                if (B >= m->wide_min && m->wide_path) { a.w0 = m->pk_projection; e = launch_mm(0, dbb, 0, a, st); }
-                else e = launch_gemv(0, dbb, 0, a, st);
-                if (e != hipSuccess) return e;
+                a = proj_args(m->dec_in, dbb, B, dd, wide ? m->pk_projection : (const bf16_t*)m->w.projection, nullptr);
+                a.x_row_stride = 2L * dbb; a.out = m->hdec; a.ldo = 2L * dd;
+                if ((e = launch_proj(wide ? Fam::MM32 : Fam::GEMV, Op::STORE, dbb, 0, a, st)) != hipSuccess) return e;
             }
             if (one_launch) {
                 if ((e = launch_dec_first(m, st)) != hipSuccess) return e;
@@ -926,47 +799,33 @@ static hipError_t run_depth(CsmModel* m, int B, int S, float temperature, int to
                 // decoder positions are static per step: rows (0,1) on the first call, then cb
                 const int* pos = m->dec_pos + (long)(cb == 1 ? 0 : cb) * 2 * m->max_batch;
                 // cb >= 2 on the wide path: the previous sampler already wrote sa_norm(row) into attd
-                const bool wide_next = B >= m->wide_min && m->wide_path;
-                const bool qkv0_done = cb >= 2 && m->qkv0_tab != nullptr;
-                const bool x_normed = cb >= 2 && wide_next && !qkv0_done;
-                if ((e = run_stack(m, m->dec, m->hdec, m->qd, m->attd, m->actd, rows, cb == 1 ? 2 : 1, pos, cb == 1 ? 0 : cb, st, false, x_normed,
-                                   qkv0_done)) != hipSuccess) return e;
+                StackOpts o;
+                o.qkv0_done = cb >= 2 && m->qkv0_tab != nullptr;
+                o.x_normed = cb >= 2 && wide && !o.qkv0_done;
+                if ((e = run_stack(m, m->dec, m->hdec, m->qd, m->attd, m->actd, rows, cb == 1 ? 2 : 1, pos, cb == 1 ? 0 : cb, st, o)) != hipSuccess) return e;
             }
         }
-        // final RMSNorm + head -> logits (bf16, padded rows)
+        // final RMSNorm + head -> logits (bf16, padded rows): head cb of the stream the plan names (the packed audio heads lie pk_head_stride apart, e4m3 ones 1 byte per element)
         if (!one_launch) {
-        memset(&a, 0, sizeof a);
-        if (cb == 0) {
-            a.x = m->h; a.x_row_stride = (long)S * dbb; a.x_row_offset = (long)(S - 1) * dbb;
-            a.norm_scale = (const bf16_t*)m->w.bb_norm; a.eps = c.backbone.norm_eps;
-            a.normed_out = m->dec_in; a.normed_stride = 2L * dbb;
-            a.w0 = (const bf16_t*)m->w.c0_head; a.nt = 1;
-        } else {
-            const int rps = cb == 1 ? 2 : 1;
-            a.x = m->hdec; a.x_row_stride = (long)rps * dd; a.x_row_offset = (long)(rps - 1) * dd;
-            a.norm_scale = (const bf16_t*)m->w.dec_norm; a.eps = c.decoder.norm_eps;
-            a.w0 = (const bf16_t*)m->w.audio_head_t + (long)(cb - 1) * V * dd; a.nt = 1;
-        }
-        a.M = B; a.N = V; a.out = m->logits; a.ldo = m->ldl;
-        if (B >= m->wide_min && m->wide_path) {
-            // normalised last row of each sequence (= last_h for cb == 0), then the MFMA head
-            const int Kh = cb == 0 ? dbb : dd;
-            bf16_t* xn = cb == 0 ? m->dec_in : m->attd;
-            const long xs = cb == 0 ? 2L * dbb : (long)dd;
-            // (the final norm was applied by the stack's last finisher: run_stack_wide)
-            a.x = xn; a.x_row_stride = xs; a.x_row_offset = 0;
-            a.w0 = cb == 0 ? m->pk_c0_head : m->pk_audio_head + (long)(cb - 1) * m->pk_head_stride;
-            const bool f8h = m->pk8_c0_head != nullptr && m->fp8_wide;
-            if (f8h) {
-                a.w0 = (const bf16_t*)(cb == 0 ? m->pk8_c0_head : m->pk8_audio_head + (long)(cb - 1) * m->pk_head_stride);   // 1 byte per element
-                a.s0 = cb == 0 ? (const float*)m->w.c0_head8s : (const float*)m->w.audio_head8s + (long)(cb - 1) * V;
+            const Stream hs = plan_head(knobs, wide, m->pk8_c0_head != nullptr, m->w.fp8 != 0);
+            const int Kh = cb == 0 ? dbb : dd, rps = cb == 1 ? 2 : 1;
+            const long hoff = (long)(cb - 1) * (wide ? m->pk_head_stride : (long)V * dd);
+            const void* hw = hs == Stream::ROW_BF16    ? (cb == 0 ? m->w.c0_head : (const void*)((const bf16_t*)m->w.audio_head_t + hoff))
+                             : hs == Stream::ROW_E4M3  ? (cb == 0 ? m->w.c0_head8 : (const void*)((const char*)m->w.audio_head8 + hoff))
+                             : hs == Stream::PACK_BF16 ? (const void*)(cb == 0 ? m->pk_c0_head : m->pk_audio_head + hoff)
+                                                       : (const void*)(cb == 0 ? m->pk8_c0_head : m->pk8_audio_head + hoff);
+            const void* hsc = !stream_e4m3(hs) ? nullptr : cb == 0 ? m->w.c0_head8s : (const void*)((const float*)m->w.audio_head8s + (long)(cb - 1) * V);
+            if (wide) {
+                // normalised last row of each sequence (= last_h for cb == 0): the final norm was applied by the stack's last finisher (run_stack_wide)
+                a = cb == 0 ? head_args(m->dec_in, 2L * dbb, 0, Kh, B, V, hw, hsc, m->logits, m->ldl) : head_args(m->attd, dd, 0, Kh, B, V, hw, hsc, m->logits, m->ldl);
+            } else if (cb == 0) {
+                a = head_args(m->h, (long)S * dbb, (long)(S - 1) * dbb, Kh, B, V, hw, hsc, m->logits, m->ldl);
+                a.norm_scale = (const bf16_t*)m->w.bb_norm; a.eps = c.backbone.norm_eps; a.normed_out = m->dec_in; a.normed_stride = 2L * dbb;
+            } else {
+                a = head_args(m->hdec, (long)rps * dd, (long)(rps - 1) * dd, Kh, B, V, hw, hsc, m->logits, m->ldl);
+                a.norm_scale = (const bf16_t*)m->w.dec_norm; a.eps = c.decoder.norm_eps;
             }
-            if ((e = launch_mm(0, Kh, 0, a, st, f8h)) != hipSuccess) return e;
-        } else if (m->w.fp8) {
-            if (cb == 0) { a.w0 = (const bf16_t*)m->w.c0_head8; a.s0 = (const float*)m->w.c0_head8s; }
-            else { a.w0 = (const bf16_t*)((const char*)m->w.audio_head8 + (long)(cb - 1) * V * dd); a.s0 = (const float*)m->w.audio_head8s + (long)(cb - 1) * V; }
-            if ((e = launch_gemv8(2, cb == 0 ? dbb : dd, 0, a, st)) != hipSuccess) return e;
-        } else if ((e = launch_gemv(2, cb == 0 ? dbb : dd, 0, a, st)) != hipSuccess) return e;
+            if ((e = launch_proj(wide ? Fam::MM32 : Fam::GEMV, wide ? Op::STORE : Op::NORM_STORE, Kh, 0, a, st, stream_e4m3(hs))) != hipSuccess) return e;
         }
         if (logits_out) {
             e = hipMemcpy2DAsync((char*)logits_out + (size_t)cb * B * V * 2, (size_t)V * 2, m->logits, (size_t)m->ldl * 2,
@@ -984,7 +843,7 @@ static hipError_t run_depth(CsmModel* m, int B, int S, float temperature, int to
         if (cb == 0) { s.emb_out = m->hdec + dd; s.emb_stride = 2L * dd; }
         else if (cb < ncb - 1) {
             s.emb_out = m->hdec; s.emb_stride = dd;
-            if (m->qkv0_tab == nullptr && B >= m->wide_min && m->wide_path) {   // wide next step without the table: hand it layer 0's normalised input
+            if (m->qkv0_tab == nullptr && wide) {   // wide next step without the table: hand it layer 0's normalised input
                 s.xn_scale = (const bf16_t*)m->dec.lw[0].sa_norm; s.xn_eps = c.decoder.norm_eps; s.xn_out = m->attd; s.xn_stride = dd;
             } else if (m->qkv0_tab) {                     // layer 0's q/k/v of the next step are a table row
                 s.qkv0 = m->qkv0_tab + (long)(cb - 1) * V * (m->dec.nq + 2 * m->dec.nkv);
@@ -1143,22 +1002,11 @@ static hipError_t build_qkv0_table(CsmModel* m) {
     if ((e = hipMalloc((void**)&vt, kv_bytes)) != hipSuccess) { (void)hipFree(kt); return e; }
     for (int cb = 1; cb <= ncb - 2 && e == hipSuccess; ++cb) {
         bf16_t* tab = m->qkv0_tab + (long)(cb - 1) * V * ld;
-        GemvArgs a;
-        memset(&a, 0, sizeof a);
-        a.nt = S.nt_attn;
-        a.x = m->proj_emb + (long)cb * V * dd; a.x_row_stride = dd; a.M = V;
-        a.norm_scale = (const bf16_t*)S.lw[0].sa_norm; a.eps = S.d.norm_eps;
-        a.w0 = (const bf16_t*)S.lw[0].wq; a.w1 = (const bf16_t*)S.lw[0].wk; a.w2 = (const bf16_t*)S.lw[0].wv;
-        a.N = ld; a.out = tab; a.ldo = ld;
-        a.nq = S.nq; a.nkv = S.nkv; a.smax = S.cache_len; a.rows_per_seq = 1; a.kv_heads = c.decoder.n_kv_heads;
-        a.pos = nullptr; a.pos_base = cb + 1; a.rope = S.rope; a.kcache = kt; a.vcache = vt;
         const bool f8 = S.w8 != nullptr;
-        if (f8) {
-            a.w0 = (const bf16_t*)S.w8[0].wq; a.w1 = (const bf16_t*)S.w8[0].wk; a.w2 = (const bf16_t*)S.w8[0].wv;
-            a.s0 = (const float*)S.w8s[0].wq; a.s1 = (const float*)S.w8s[0].wk; a.s2 = (const float*)S.w8s[0].wv;
-        }
-        e = (dd == 1024 && S.hd == 128) ? launch_gemv_msplit(1, f8, a, nullptr)
-                                        : (f8 ? launch_gemv8(3, dd, S.hd, a, nullptr) : launch_gemv(3, dd, S.hd, a, nullptr));
+        const LayerRows r = {kt, vt, V, 1, nullptr, cb + 1};
+        GemvArgs a = qkv_args(S, layer_weights(S, 0, f8 ? Stream::ROW_E4M3 : Stream::ROW_BF16), r, m->proj_emb + (long)cb * V * dd, tab, ld);
+        a.nt = S.nt_attn; a.norm_scale = (const bf16_t*)S.lw[0].sa_norm; a.eps = S.d.norm_eps;
+        e = (dd == 1024 && S.hd == 128) ? launch_gemv_msplit(1, f8, a, nullptr) : launch_gemv(Op::QKV, dd, S.hd, a, nullptr, f8);
         if (e != hipSuccess) break;
         hipLaunchKernelGGL(k_gather_kv_rows, dim3(1024), dim3(256), 0, nullptr, kt, vt, V, c.decoder.n_kv_heads, S.cache_len, S.hd, cb + 1,
                            S.nq, tab);
@@ -1477,7 +1325,7 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
         memset(&a, 0, sizeof a);
         a.x = (const bf16_t*)w->audio_emb; a.x_row_stride = dbb; a.M = ncb * cfg->audio_vocab;
         a.w0 = (const bf16_t*)w->projection; a.N = dd; a.out = m->proj_emb; a.ldo = dd; a.nt = 0;
-        HIPCHK((CsmModel*)nullptr, dbb == 2048 ? launch_gemv_msplit(0, false, a, nullptr) : launch_gemv(0, dbb, 0, a, nullptr));
+        HIPCHK((CsmModel*)nullptr, dbb == 2048 ? launch_gemv_msplit(0, false, a, nullptr) : launch_gemv(Op::STORE, dbb, 0, a, nullptr));
     }
     HIPCHK((CsmModel*)nullptr, hipDeviceSynchronize());
     m->qkv0_tab = nullptr;
@@ -1685,7 +1533,7 @@ extern "C" int csm_prefill(csm_handle m, const int32_t* tokens, const uint8_t* m
         return fail(m, CSM_E_INVALID, "csm_prefill: B/S outside the limits given to csm_create");
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(m, launch_embed(m, tokens, mask, B * S, st));
-    HIPCHK(m, run_stack(m, m->bb, m->h, m->q, m->att, m->act, B * S, S, pos, -1, st, prompt_mode != 0));
+    HIPCHK(m, run_stack(m, m->bb, m->h, m->q, m->att, m->act, B * S, S, pos, -1, st, prompt_opts(prompt_mode != 0)));
     hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, B, S, m->cur_pos, m->cfg.backbone.max_seq, m->n_frames + 1,
                        m->slot_tab_used ? m->slot_tab : nullptr);
     HIPCHK(m, hipGetLastError());
@@ -1905,7 +1753,7 @@ extern "C" int csm_prefill_slot(csm_handle m, int slot, const int32_t* tokens, c
     // pass use scratch row 0 (every per-frame workspace is dead between frame steps)
     m->bb.slot_off = (long)slot * m->cfg.backbone.n_kv_heads * m->bb.cache_len * m->bb.hd;
     hipError_t e = launch_embed(m, tokens, mask, S, st);
-    if (e == hipSuccess) e = run_stack(m, m->bb, m->h, m->q, m->att, m->act, S, S, pos, -1, st, prompt_mode != 0);
+    if (e == hipSuccess) e = run_stack(m, m->bb, m->h, m->q, m->att, m->act, S, S, pos, -1, st, prompt_opts(prompt_mode != 0));
     m->bb.slot_off = 0;
     HIPCHK(m, e);
     hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1,
@@ -1991,15 +1839,19 @@ static int refill_advance(CsmModel* m, int max_layers, hipStream_t st) {
     int l0, l1;
     const bool complete = refill_layers(r, max_layers, m->cfg.backbone.n_layers, &l0, &l1);
     hipError_t e;
+    StackOpts o = prompt_opts(true);
+    o.l_begin = l0; o.l_end = l1;
     if (r.ragged) {
         RagLaunch rl;
         rl.sg = r.sg; rl.row_slot = m->rg_row_slot; rl.tiles = m->rg_tiles; rl.n_tiles = r.tiles;
-        e = run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, r.pos, -1, st, true, false, false, l0, l1, m->rf_last, &rl);
+        o.fin_out = m->rf_last; o.rag = &rl;
+        e = run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, r.pos, -1, st, o);
     } else {
         // one slot keeps the launches of a batch of ONE sequence whose K/V land in the slot's part of the caches
         const int slot = r.sg.s[0].slot;
         m->bb.slot_off = (long)slot * m->cfg.backbone.n_kv_heads * m->bb.cache_len * m->bb.hd;
-        e = run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, r.pos, -1, st, true, false, false, l0, l1, m->rf_last + (long)slot * 2 * m->cfg.backbone.dim);
+        o.fin_out = m->rf_last + (long)slot * 2 * m->cfg.backbone.dim;
+        e = run_stack(m, m->bb, m->rf_h, m->q, m->rf_xn, m->act, M, M, r.pos, -1, st, o);
         m->bb.slot_off = 0;
     }
     HIPCHK(m, e);
@@ -2338,6 +2190,8 @@ extern "C" int csm_op_gemv(int kind, int M, int K, int N, const void* x, long x_
                            const void* resid, void* out, long ldo, void* normed_out, long normed_stride, int nt,
                            int head_dim, int nq, int nkv, int kv_heads, int smax, int rows_per_seq, const int32_t* pos,
                            const void* rope, void* kcache, void* vcache, void* stream) {
+    Fam fam; Op op;
+    if (!public_kind(kind, &fam, &op)) { g_create_err = "csm_op_gemv: no such kind"; return CSM_E_INVALID; }
     GemvArgs a;
     memset(&a, 0, sizeof a);
     a.x = (const bf16_t*)x; a.x_row_stride = x_row_stride; a.x_row_offset = x_row_offset; a.M = M;
@@ -2351,9 +2205,9 @@ extern "C" int csm_op_gemv(int kind, int M, int K, int N, const void* x, long x_
     // kinds 20/21/23/24: the same through the 128 x 128 LDS-tiled kernel of long prompts (gemm128.cuh, row-major weights)
     // kinds 31/33/34: the same through the several-tiles-per-wave prompt kernels (mm.cuh k_mmq + finisher / k_mmt), 64..256 rows
     hipError_t e;
-    if (kind >= 20 && kind < 30) {
-        e = launch_g128(kind - 20, K, head_dim, a, (hipStream_t)stream);
-    } else if (kind >= 10) {
+    if (fam == Fam::GEMV || fam == Fam::G128) {
+        e = launch_proj(fam, op, K, head_dim, a, (hipStream_t)stream);
+    } else {
         std::vector<void*> tmp;
         auto pack = [&](const bf16_t* w, int n) -> const bf16_t* {
             if (!w) return nullptr;
@@ -2364,28 +2218,23 @@ extern "C" int csm_op_gemv(int kind, int M, int K, int N, const void* x, long x_
             hipLaunchKernelGGL(k_pack_w, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, n, K, (bf16_t*)t);
             return (const bf16_t*)t;
         };
-        if (kind % 10 == 3) { a.w0 = pack(a.w0, nq); a.w1 = pack(a.w1, nkv); a.w2 = pack(a.w2, nkv); }
-        else if (kind % 10 == 4) { a.w0 = pack(a.w0, N); a.w1 = pack(a.w1, N); }
+        if (op == Op::QKV) { a.w0 = pack(a.w0, nq); a.w1 = pack(a.w1, nkv); a.w2 = pack(a.w2, nkv); }
+        else if (op == Op::SWIGLU) { a.w0 = pack(a.w0, N); a.w1 = pack(a.w1, N); }
         else a.w0 = pack(a.w0, N);
-        if (kind >= 30) {
-            if (!mmt_ok(M, K, N)) e = hipErrorInvalidValue;
-            else if (kind == 31) {
-                void* slab = nullptr;
-                e = hipMalloc(&slab, (size_t)4 * M * N * 4);
-                if (e == hipSuccess) {
-                    tmp.push_back(slab);
-                    a.slab = (float*)slab;
-                    e = launch_mmq(K, a, (hipStream_t)stream);
-                    if (e == hipSuccess && out != resid) e = hipMemcpyAsync(out, resid, (size_t)M * N * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-                    if (e == hipSuccess) e = launch_resid_norm((bf16_t*)out, (const float*)slab, 4, M, N, 1, 0, M, nullptr, 0.f, nullptr, 0, (hipStream_t)stream);
-                }
-            } else e = launch_mmt(kind - 30, head_dim, K, a, (hipStream_t)stream);
-        } else
-        e = launch_mm(kind - 10, K, head_dim, a, (hipStream_t)stream);
+        if (fam != Fam::MM32 && !mmt_ok(MMT_MIN_ROWS, M, K, N)) e = hipErrorInvalidValue;
+        else if (fam == Fam::MMQ) {
+            void* slab = nullptr;
+            e = hipMalloc(&slab, (size_t)4 * M * N * 4);
+            if (e == hipSuccess) {
+                tmp.push_back(slab);
+                a.slab = (float*)slab;
+                e = launch_proj(fam, op, K, head_dim, a, (hipStream_t)stream);
+                if (e == hipSuccess && out != resid) e = hipMemcpyAsync(out, resid, (size_t)M * N * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+                if (e == hipSuccess) e = launch_resid_norm((bf16_t*)out, (const float*)slab, 4, M, N, 1, 0, M, nullptr, 0.f, nullptr, 0, (hipStream_t)stream);
+            }
+        } else e = launch_proj(fam, op, K, head_dim, a, (hipStream_t)stream);
         (void)hipStreamSynchronize((hipStream_t)stream);
         for (void* t : tmp) (void)hipFree(t);
-    } else {
-        e = launch_gemv(kind, K, head_dim, a, (hipStream_t)stream);
     }
     if (e != hipSuccess) { g_create_err = std::string("csm_op_gemv: ") + hipGetErrorString(e); return e == hipErrorInvalidValue ? CSM_E_INVALID : CSM_E_HIP; }
     return CSM_OK;
@@ -2418,7 +2267,7 @@ extern "C" int csm_op_attn_oproj(int M, int rows_per_seq, int H, int KV, int sma
     a.M = M; a.w0 = (const bf16_t*)wo; a.N = N; a.out = (bf16_t*)out; a.ldo = N; a.resid = (const bf16_t*)resid;
     a.aq = (const bf16_t*)q; a.aH = H; a.ascale = 1.0f / sqrtf(128.f); a.kcache = (bf16_t*)kcache; a.vcache = (bf16_t*)vcache;
     a.pos = pos; a.smax = smax; a.rows_per_seq = rows_per_seq; a.kv_heads = KV;
-    hipError_t e = launch_gemv(5, H * 128, 128, a, (hipStream_t)stream);
+    hipError_t e = launch_gemv(Op::ATTN_RESID, H * 128, 128, a, (hipStream_t)stream);
     if (e != hipSuccess) { g_create_err = std::string("csm_op_attn_oproj: ") + hipGetErrorString(e); return CSM_E_HIP; }
     return CSM_OK;
 }
