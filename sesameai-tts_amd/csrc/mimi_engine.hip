@@ -457,125 +457,6 @@ __global__ __launch_bounds__(256) void k_rvq_pick(const float* score, int ncodes
     for (int d = tid; d < dim; d += 256) resid[(long)t * dim + d] -= book[(long)e * dim + d];
 }
 
-// ---------------------------------------------------------------------------------------
-struct HBuf {            // activation buffer with `hist` rows of left context in front of row 0
-    float* base = nullptr;
-    int hist = 0, C = 0;
-    float* row0() const { return base + (long)hist * C; }
-};
-
-
-struct MimiDecoder {
-    MimiConfig cfg;
-    MimiWeights w;
-    int max_frames;
-    long cap_tokens;                    // transformer KV capacity (tokens)
-    int offset;                         // tokens already in the KV caches (stateful stream)
-    HBuf rvq, a0, s0;                   // rvq out (hist 1), transformer out (hist kernel-1), conv_in out (hist 1)
-    HBuf u[MIMI_MAX_STAGES], xj[MIMI_MAX_STAGES];
-    float *r1[MIMI_MAX_STAGES];
-    float *tok, *ln, *q, *att, *ffn, *kc, *vc;
-    KSplitWs ksw = {nullptr, nullptr, 0, 0, 0, 0};
-    hipStream_t cap_stream = nullptr;   // graph capture of decode_middle
-    hipGraphExec_t mid_exec[65] = {};   // by T (stateless decodes of up to MIMI_GRAPH_MAX_T frames)
-    int mid_uses[65] = {};
-    std::string err;
-};
-
-#define MCHK(h, x)                                                                                     \
-    do {                                                                                               \
-        hipError_t e_ = (x);                                                                           \
-        if (e_ != hipSuccess) {                                                                        \
-            char b_[256];                                                                              \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            if (h) (h)->err = b_; else g_mimi_err = b_;                                                \
-            return -2;                                                                                 \
-        }                                                                                              \
-    } while (0)
-
-static int mfail(MimiDecoder* h, const char* msg) {
-    if (h) h->err = msg; else g_mimi_err = msg;
-    return -1;
-}
-
-static hipError_t alloc_hbuf(HBuf& b, int hist, long rows, int C) {
-    b.hist = hist; b.C = C;
-    hipError_t e = hipMalloc((void**)&b.base, (size_t)(hist + rows) * C * 4);
-    if (e != hipSuccess) return e;
-    return hipMemset(b.base, 0, (size_t)(hist + rows) * C * 4);
-}
-
-extern "C" void csm_warn_unknown_switches(void);     // csm_engine.hip: names under CSM_ / MIMI_ that no switch reads, once per process
-
-// what the kernels assume of a configuration (mimi_create and mimi_pool_create)
-static const char* config_error(const MimiConfig* cfg) {
-    if (cfg->hidden % 32 || cfg->hidden > 1024 || cfg->codebook_dim % 4 || cfg->tr_ffn % 32 || cfg->hidden / cfg->tr_heads != 64)
-        return "mimi_create: hidden%32, hidden<=1024, tr_ffn%32 and head_dim==64 required";
-    if (cfg->n_stages < 1 || cfg->n_stages > MIMI_MAX_STAGES || cfg->tr_layers > MIMI_MAX_TR_LAYERS || cfg->tr_context > 1024)
-        return "mimi_create: too many stages/layers or context > 1024";
-    if (cfg->kernel > MAX_TAPS || cfg->res_kernel > MAX_TAPS) return "mimi_create: kernel too wide";
-    int c = cfg->n_filters << cfg->n_stages;
-    for (int j = 0; j < cfg->n_stages; ++j) { c /= 2; if ((c / 2) % 32) return "mimi_create: SEANet channels must stay multiples of 32"; }
-    return nullptr;
-}
-
-extern "C" int mimi_create(const MimiConfig* cfg, const MimiWeights* w, int max_frames, int reserved, mimi_handle* out) {
-    csm_warn_unknown_switches();
-    (void)reserved;
-    if (!cfg || !w || !out || max_frames < 1) return mfail(nullptr, "mimi_create: null/invalid argument");
-    if (const char* bad = config_error(cfg)) return mfail(nullptr, bad);
-    MimiDecoder* m = new MimiDecoder();
-    m->cfg = *cfg; m->w = *w; m->max_frames = max_frames; m->offset = 0;
-    const int d = cfg->hidden;
-    const long T2 = 2L * max_frames;
-    m->cap_tokens = T2;
-    MCHK((MimiDecoder*)nullptr, alloc_hbuf(m->rvq, 1, max_frames, d));
-    MCHK((MimiDecoder*)nullptr, alloc_hbuf(m->a0, cfg->kernel - 1, T2, d));
-    int C = cfg->n_filters << cfg->n_stages;
-    MCHK((MimiDecoder*)nullptr, alloc_hbuf(m->s0, 1, T2, C));
-    long Tj = T2;
-    for (int j = 0; j < cfg->n_stages; ++j) {
-        Tj *= cfg->ratios[j]; C /= 2;
-        MCHK((MimiDecoder*)nullptr, alloc_hbuf(m->u[j], cfg->res_kernel - 1, Tj, C));
-        MCHK((MimiDecoder*)nullptr, hipMalloc((void**)&m->r1[j], (size_t)Tj * (C / 2) * 4));
-        const int nh = (j + 1 < cfg->n_stages) ? 1 : cfg->last_kernel - 1;
-        MCHK((MimiDecoder*)nullptr, alloc_hbuf(m->xj[j], nh, Tj, C));
-    }
-#define A4(p, n) MCHK((MimiDecoder*)nullptr, hipMalloc((void**)&(p), (size_t)(n) * 4))
-    A4(m->tok, T2 * d); A4(m->ln, T2 * d); A4(m->q, T2 * d); A4(m->att, T2 * d);
-    A4(m->ffn, T2 * (cfg->tr_ffn > cfg->codebook_size ? cfg->tr_ffn : cfg->codebook_size));   // also the RVQ score buffer
-    A4(m->kc, (long)cfg->tr_layers * m->cap_tokens * d); A4(m->vc, (long)cfg->tr_layers * m->cap_tokens * d);
-    {   // K-split workspace (k_gemm32): the deep products' partial tiles and tile tickets.  MIMI_KSPLIT=0 in the environment: no split.
-        const int want = sw_int(SW_MIMI_KSPLIT, MIMI_KSPLIT);
-        if (want == 2 || want == 4 || want == 8) {
-            m->ksw.ksplit = want;
-            const int ccap = cfg->n_filters << cfg->n_stages;                         // widest output of a split product (conv_in); >= hidden
-            m->ksw.cap_rows = T2; m->ksw.cap_cols = ccap > d ? ccap : d;
-            m->ksw.n_tickets = (int)((T2 + 31) / 32) * ((m->ksw.cap_cols + 31) / 32);
-            A4(m->ksw.part, (long)want * m->ksw.cap_rows * m->ksw.cap_cols);
-            MCHK((MimiDecoder*)nullptr, hipMalloc((void**)&m->ksw.ticket, (size_t)m->ksw.n_tickets * 4));
-            MCHK((MimiDecoder*)nullptr, hipMemset(m->ksw.ticket, 0, (size_t)m->ksw.n_tickets * 4));
-        }
-    }
-#undef A4
-    MCHK((MimiDecoder*)nullptr, hipDeviceSynchronize());
-    *out = m;
-    return 0;
-}
-
-extern "C" void mimi_destroy(mimi_handle m) {
-    if (!m) return;
-    (void)hipFree(m->rvq.base); (void)hipFree(m->a0.base); (void)hipFree(m->s0.base);
-    for (int j = 0; j < m->cfg.n_stages; ++j) { (void)hipFree(m->u[j].base); (void)hipFree(m->xj[j].base); (void)hipFree(m->r1[j]); }
-    void* ps[] = {m->tok, m->ln, m->q, m->att, m->ffn, m->kc, m->vc, m->ksw.part, m->ksw.ticket};
-    for (void* p : ps) (void)hipFree(p);
-    for (hipGraphExec_t g : m->mid_exec) if (g) (void)hipGraphExecDestroy(g);
-    if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
-    delete m;
-}
-
-extern "C" const char* mimi_last_error(mimi_handle m) { return m ? m->err.c_str() : g_mimi_err.c_str(); }
-
 // the left-context rows of every activation buffer, zeroed by ONE launch (was 11 hipMemsetAsync per stateless decode)
 struct ZeroRegions { float* p[3 + 2 * MIMI_MAX_STAGES]; int n[3 + 2 * MIMI_MAX_STAGES]; int count; };
 __global__ void k_zero_regions(const ZeroRegions z) {
@@ -584,336 +465,7 @@ __global__ void k_zero_regions(const ZeroRegions z) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < z.n[reg]; i += gridDim.x * blockDim.x) z.p[reg][i] = 0.f;
 }
 
-extern "C" int mimi_reset_stream(mimi_handle m, void* stream) {
-    if (!m) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    ZeroRegions z;
-    z.count = 0;
-    auto add = [&](const HBuf& b) { if (b.hist) { z.p[z.count] = b.base; z.n[z.count] = b.hist * b.C; ++z.count; } };
-    add(m->rvq); add(m->a0); add(m->s0);
-    for (int j = 0; j < m->cfg.n_stages; ++j) { add(m->u[j]); add(m->xj[j]); }
-    if (z.count) {
-        hipLaunchKernelGGL(k_zero_regions, dim3(8, z.count), dim3(256), 0, st, z);
-        MCHK(m, hipGetLastError());
-    }
-    m->offset = 0;
-    return 0;
-}
-
-struct RopeOut { float *q, *k, *v; const float* freqs; int offset, d; };
-struct SegArgs { int T, x, o, r, by_id, ring; const int* tab; };       // GemmArgs.seg_*: a product over the stacked rows of a stream pool
-static hipError_t gemm(hipStream_t st, const float* x, long ldx, long T_in, const float* w, const float* bias, int C_in,
-                       int C_out, int taps, int phases, const int* shifts, int elu_in, int act_out, const float* col_scale,
-                       const float* resid, long ldr, float* out, long ldo, int in_stride = 1, int edge = 0, int row_lo = 0,
-                       int row_hi = 0, const RopeOut* rope = nullptr, const KSplitWs* ksw = nullptr, const SegArgs* seg = nullptr) {
-    GemmArgs a;
-    memset(&a, 0, sizeof a);
-    if (rope) { a.rope_q = rope->q; a.rope_k = rope->k; a.rope_v = rope->v; a.rope_freqs = rope->freqs; a.rope_offset = rope->offset; a.rope_d = rope->d; }
-    a.in_stride = in_stride; a.edge = edge; a.row_lo = row_lo; a.row_hi = row_hi;
-    a.x = x; a.ldx = ldx; a.T_in = (int)T_in; a.C_in = C_in; a.C_out = C_out; a.w = w; a.bias = bias; a.taps = taps;
-    a.phases = phases;
-    a.shift0 = shifts[0]; a.dshift = taps > 1 ? shifts[1] - shifts[0] : 0;
-    for (int j = 0; j < taps; ++j) if (shifts[j] != a.shift0 + j * a.dshift) return hipErrorInvalidValue;   // (every convolution here is an arithmetic progression of taps)
-    a.act_out = act_out; a.col_scale = col_scale; a.resid = resid; a.ldr = ldr; a.out = out; a.ldo = ldo;
-    dim3 grid((unsigned)((T_in + 31) / 32), (unsigned)((C_out + 31) / 32), (unsigned)phases);
-    // (the choice depends on the product's shape alone, never on T_in: a streamed chunk and the whole clip sum in the same order)
-    const int iters = taps * (C_in / 32);
-    if (ksw != nullptr && ksw->part != nullptr && phases == 1 && rope == nullptr && iters >= MIMI_KSPLIT_MIN_ITERS && iters % ksw->ksplit == 0) {
-        // (the workspace is sized for the handle's max_frames at mimi_create, so a product the decoder accepts always fits; if one ever
-        //  does not, it runs unsplit -- same value to fp32 rounding -- instead of failing the decode: ADVICE r5)
-        if (T_in <= ksw->cap_rows && C_out <= ksw->cap_cols && (long)grid.x * grid.y <= ksw->n_tickets) {
-            a.ksplit = ksw->ksplit; a.kpart = ksw->part; a.kticket = ksw->ticket;
-            grid.z = (unsigned)ksw->ksplit;
-        }
-    }
-    if (seg != nullptr) {
-        a.seg_T = seg->T; a.seg_x = seg->x; a.seg_o = seg->o; a.seg_r = seg->r; a.seg_by_id = seg->by_id; a.rope_ring = seg->ring; a.seg_tab = seg->tab;
-        if (elu_in) hipLaunchKernelGGL((k_gemm32<true, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        else hipLaunchKernelGGL((k_gemm32<false, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        return hipGetLastError();
-    }
-    if (elu_in) hipLaunchKernelGGL(k_gemm32<true>, grid, dim3(64 * G32_NW), 0, st, a);
-    else hipLaunchKernelGGL(k_gemm32<false>, grid, dim3(64 * G32_NW), 0, st, a);
-    return hipGetLastError();
-}
-
-static hipError_t slide(const HBuf& b, long T, hipStream_t st) {
-    if (!b.hist) return hipSuccess;
-    hipLaunchKernelGGL(k_slide_hist, dim3((b.C + 255) / 256), dim3(256), 0, st, b.base, b.hist, T, b.C);
-    return hipGetLastError();
-}
-
-// A decode is three pieces: front (the only kernel that reads the caller's codes), middle (everything between buffers the handle
-// owns: up-sampling, transformer, SEANet stages -- ~70 launches whose arguments depend on T and the stream offset only) and back (the
-// only kernel that writes the caller's PCM).  The middle of a STATELESS decode (offset 0) is replayed from a hipGraph per T.
-static int decode_front(MimiDecoder* m, const int32_t* codes, long stride_k, long stride_t, int T, hipStream_t st) {
-    const MimiConfig& c = m->cfg;
-    const int d = c.hidden;
-    // 1. RVQ lookup-sum + output projections -> rvq [T][d]
-    hipLaunchKernelGGL(k_rvq, dim3(T, (d + 63) / 64), dim3(256), (size_t)(2 * c.codebook_dim + c.n_codebooks) * 4, st, codes, stride_k, stride_t, T, c.n_codebooks,
-                       c.n_semantic, c.codebook_size, c.codebook_dim, d, m->w.codebooks, m->w.proj_first, m->w.proj_rest,
-                       m->rvq.row0(), (long)d);
-    MCHK(m, hipGetLastError());
-    return 0;
-}
-
-static int decode_middle(MimiDecoder* m, int T, hipStream_t st) {
-    const MimiConfig& c = m->cfg;
-    const int d = c.hidden;
-    const long T2 = 2L * T;
-    const int zero = 0;
-    // (ONE stream per handle: the K-split partial tiles and their tickets are per handle, include/mimi_hip.h)
-    // 2. depthwise transposed conv x2 -> tok [2T][d]
-    {
-        const long n = T2 * d;
-        hipLaunchKernelGGL(k_upsample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->rvq.row0(), (long)d, T, d,
-                           m->w.upsample, m->tok, (long)d, m->ksw.ticket, m->ksw.ticket ? m->ksw.n_tickets : 0);
-        MCHK(m, hipGetLastError());
-    }
-    // 3. transformer
-    for (int l = 0; l < c.tr_layers; ++l) {
-        const MimiTrLayer& L = m->w.tr[l];
-        float* kc = m->kc + (long)l * m->cap_tokens * d;
-        float* vc = m->vc + (long)l * m->cap_tokens * d;
-        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)T2), dim3(64), 0, st, m->tok, d, L.ln1_w, L.ln1_b, c.norm_eps, m->ln);
-        const RopeOut ro = {m->q, kc, vc, m->w.rope_freqs, m->offset, d};
-        MCHK(m, gemm(st, m->ln, d, T2, L.in_proj, nullptr, d, 3 * d, 1, 1, &zero, 0, 0, nullptr, nullptr, 0, nullptr, 0, 1, 0, 0, 0, &ro));
-        hipLaunchKernelGGL(k_mimi_attn, dim3((unsigned)T2, c.tr_heads), dim3(64), 0, st, m->q, kc, vc, d, m->offset, c.tr_context, m->att);
-        MCHK(m, gemm(st, m->att, d, T2, L.out_proj, nullptr, d, d, 1, 1, &zero, 0, 0, L.ls1, m->tok, d, m->tok, d));
-        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)T2), dim3(64), 0, st, m->tok, d, L.ln2_w, L.ln2_b, c.norm_eps, m->ln);
-        MCHK(m, gemm(st, m->ln, d, T2, L.lin1, nullptr, d, c.tr_ffn, 1, 1, &zero, 0, 1, nullptr, nullptr, 0, m->ffn, c.tr_ffn));
-        float* dst = (l + 1 < c.tr_layers) ? m->tok : m->a0.row0();
-        MCHK(m, gemm(st, m->ffn, c.tr_ffn, T2, L.lin2, nullptr, c.tr_ffn, d, 1, 1, &zero, 0, 0, L.ls2, m->tok, d, dst, d, 1, 0, 0, 0, nullptr, &m->ksw));
-        MCHK(m, hipGetLastError());
-    }
-    // 4. SEANet decoder
-    int shifts[MAX_TAPS];
-    for (int j = 0; j < c.kernel; ++j) shifts[j] = j - (c.kernel - 1);
-    const MimiConv& ci = m->w.conv_in;
-    MCHK(m, gemm(st, m->a0.row0(), d, T2, ci.w, ci.bias, ci.c_in, ci.c_out, ci.taps, 1, shifts, 0, 0, nullptr, nullptr, 0,
-                 m->s0.row0(), ci.c_out, 1, 0, 0, 0, nullptr, &m->ksw));
-    const float* xin = m->s0.row0();
-    int Cin = ci.c_out;
-    long Tj = T2;
-    for (int j = 0; j < c.n_stages; ++j) {
-        const MimiConv &up = m->w.up[j], &r1 = m->w.res1[j], &r2 = m->w.res2[j];
-        const int tshift[2] = {0, -1};
-        // ELU -> ConvTranspose1d (stride phases, 2 taps each)
-        MCHK(m, gemm(st, xin, Cin, Tj, up.w, up.bias, up.c_in, up.c_out, 2, up.phases, tshift, 1, 0, nullptr, nullptr, 0,
-                     m->u[j].row0(), up.c_out));
-        Tj *= up.phases;
-        // residual block: u + conv_k1(ELU(conv_k3(ELU(u))))
-        for (int k = 0; k < r1.taps; ++k) shifts[k] = k - (r1.taps - 1);
-        MCHK(m, gemm(st, m->u[j].row0(), up.c_out, Tj, r1.w, r1.bias, r1.c_in, r1.c_out, r1.taps, 1, shifts, 1, 0, nullptr, nullptr,
-                     0, m->r1[j], r1.c_out));
-        MCHK(m, gemm(st, m->r1[j], r1.c_out, Tj, r2.w, r2.bias, r2.c_in, r2.c_out, 1, 1, &zero, 1, 0, nullptr, m->u[j].row0(),
-                     up.c_out, m->xj[j].row0(), r2.c_out));
-        xin = m->xj[j].row0(); Cin = r2.c_out;
-    }
-    return 0;
-}
-
-static int decode_back(MimiDecoder* m, int T, float* pcm, hipStream_t st) {
-    const MimiConfig& c = m->cfg;
-    long Tj = 2L * T;
-    for (int j = 0; j < c.n_stages; ++j) Tj *= m->w.up[j].phases;
-    const HBuf& last = m->xj[c.n_stages - 1];
-    const MimiConv& co = m->w.conv_out;
-    hipLaunchKernelGGL(k_conv_out, dim3((unsigned)((Tj + 255) / 256)), dim3(256), 0, st, last.row0(), (long)last.C, Tj, co.c_in, co.taps, co.w,
-                       co.bias, pcm);
-    MCHK(m, hipGetLastError());
-    return 0;
-}
-
-// chunk sizes whose middle is worth a graph (a streaming chunk is 10 frames, the last one of an utterance 1..9): captured at the
-// SECOND stateless decode of a T, replayed from then on.  Longer decodes (whole utterances, a different T every time) stay eager.
-static const int MIMI_GRAPH_MAX_T = sw_int(SW_MIMI_GRAPH_MAX_T, 32);
-
-static int decode_one(MimiDecoder* m, const int32_t* codes, long stride_k, long stride_t, int T, float* pcm, hipStream_t st, bool stateless) {
-    int rc = decode_front(m, codes, stride_k, stride_t, T, st);
-    if (rc) return rc;
-    if (stateless && T <= MIMI_GRAPH_MAX_T && T < (int)(sizeof m->mid_uses / sizeof m->mid_uses[0]) && m->offset == 0) {
-        if (!m->mid_exec[T] && ++m->mid_uses[T] >= 2) {
-            if (!m->cap_stream) MCHK(m, hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
-            hipGraph_t g = nullptr;
-            MCHK(m, hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
-            const int rc_mid = decode_middle(m, T, m->cap_stream);
-            const hipError_t e2 = hipStreamEndCapture(m->cap_stream, &g);
-            if (rc_mid) { if (g) (void)hipGraphDestroy(g); return rc_mid; }
-            MCHK(m, e2);
-            const hipError_t e3 = hipGraphInstantiate(&m->mid_exec[T], g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            MCHK(m, e3);
-        }
-        if (m->mid_exec[T]) {
-            MCHK(m, hipGraphLaunch(m->mid_exec[T], st));
-            return decode_back(m, T, pcm, st);
-        }
-    }
-    rc = decode_middle(m, T, st);
-    if (rc) return rc;
-    return decode_back(m, T, pcm, st);
-}
-
-static int slide_all(MimiDecoder* m, int T, hipStream_t st) {
-    const MimiConfig& c = m->cfg;
-    long Tj = 2L * T;
-    MCHK(m, slide(m->rvq, T, st)); MCHK(m, slide(m->a0, Tj, st)); MCHK(m, slide(m->s0, Tj, st));
-    for (int j = 0; j < c.n_stages; ++j) {
-        Tj *= c.ratios[j];
-        MCHK(m, slide(m->u[j], Tj, st)); MCHK(m, slide(m->xj[j], Tj, st));
-    }
-    return 0;
-}
-
-static long ceil_div(long a, long b) { return (a + b - 1) / b; }
-
-static int transformer_pass(MimiDecoder* m, const MimiTrLayer* layers, long T2, int offset, float* last_out, hipStream_t st) {
-    const MimiConfig& c = m->cfg;
-    const int d = c.hidden;
-    const int zero = 0;
-    for (int l = 0; l < c.tr_layers; ++l) {
-        const MimiTrLayer& L = layers[l];
-        float* kc = m->kc + (long)l * m->cap_tokens * d;
-        float* vc = m->vc + (long)l * m->cap_tokens * d;
-        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)T2), dim3(64), 0, st, m->tok, d, L.ln1_w, L.ln1_b, c.norm_eps, m->ln);
-        const RopeOut ro = {m->q, kc, vc, m->w.rope_freqs, offset, d};
-        MCHK(m, gemm(st, m->ln, d, T2, L.in_proj, nullptr, d, 3 * d, 1, 1, &zero, 0, 0, nullptr, nullptr, 0, nullptr, 0, 1, 0, 0, 0, &ro));
-        hipLaunchKernelGGL(k_mimi_attn, dim3((unsigned)T2, c.tr_heads), dim3(64), 0, st, m->q, kc, vc, d, offset, c.tr_context, m->att);
-        MCHK(m, gemm(st, m->att, d, T2, L.out_proj, nullptr, d, d, 1, 1, &zero, 0, 0, L.ls1, m->tok, d, m->tok, d));
-        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)T2), dim3(64), 0, st, m->tok, d, L.ln2_w, L.ln2_b, c.norm_eps, m->ln);
-        MCHK(m, gemm(st, m->ln, d, T2, L.lin1, nullptr, d, c.tr_ffn, 1, 1, &zero, 0, 1, nullptr, nullptr, 0, m->ffn, c.tr_ffn));
-        float* dst = (l + 1 < c.tr_layers) ? m->tok : last_out;
-        MCHK(m, gemm(st, m->ffn, c.tr_ffn, T2, L.lin2, nullptr, c.tr_ffn, d, 1, 1, &zero, 0, 0, L.ls2, m->tok, d, dst, d));
-        MCHK(m, hipGetLastError());
-    }
-    return 0;
-}
-
-static int encode_one(MimiDecoder* m, const float* wav, long n, int32_t* codes, long T, hipStream_t st) {
-    const MimiConfig& c = m->cfg;
-    const MimiWeights& w = m->w;
-    const int d = c.hidden, S = c.n_stages;
-    const int zero = 0;
-    int shifts[MAX_TAPS];
-    // SEANet encoder; stage j lives in the decoder's stage buffers of index S-1-j (same time scale and width)
-    long L = n;
-    int C = c.n_filters;
-    {
-        const long tot = L * C;
-        hipLaunchKernelGGL(k_enc_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, L, c.kernel, C,
-                           w.enc_conv_in_w, w.enc_conv_in_b, m->u[S - 1].row0());
-    }
-    for (int j = 0; j < S; ++j) {
-        const int bi = S - 1 - j;
-        const MimiConv &r1 = w.enc_res1[j], &r2 = w.enc_res2[j], &dn = w.enc_down[j];
-        float* x = m->u[bi].row0();
-        for (int k = 0; k < r1.taps; ++k) shifts[k] = k - (r1.taps - 1);
-        MCHK(m, gemm(st, x, C, L, r1.w, r1.bias, r1.c_in, r1.c_out, r1.taps, 1, shifts, 1, 0, nullptr, nullptr, 0, m->r1[bi], r1.c_out,
-                     1, 1, 0, (int)L));
-        MCHK(m, gemm(st, m->r1[bi], r1.c_out, L, r2.w, r2.bias, r2.c_in, r2.c_out, 1, 1, &zero, 1, 0, nullptr, x, C, m->xj[bi].row0(), C,
-                     1, 1, 0, (int)L));
-        // ELU -> strided conv k = 2r: out[t] = sum_k W_k x[t*r + k - r]; zero padding on both sides
-        const int r = dn.taps / 2;
-        const long Lo = ceil_div(L, r);
-        for (int k = 0; k < dn.taps; ++k) shifts[k] = k - r;
-        float* out = (j + 1 < S) ? m->u[bi - 1].row0() : m->s0.row0();
-        MCHK(m, gemm(st, m->xj[bi].row0(), C, Lo, dn.w, dn.bias, dn.c_in, dn.c_out, dn.taps, 1, shifts, 1, 0, nullptr, nullptr, 0, out,
-                     dn.c_out, r, 1, 0, (int)L));
-        L = Lo; C = dn.c_out;
-    }
-    const MimiConv& co = w.enc_conv_out;
-    for (int k = 0; k < co.taps; ++k) shifts[k] = k - (co.taps - 1);
-    MCHK(m, gemm(st, m->s0.row0(), C, L, co.w, co.bias, co.c_in, co.c_out, co.taps, 1, shifts, 1, 0, nullptr, nullptr, 0, m->tok, d,
-                 1, 1, 0, (int)L));
-    // encoder transformer (stateless) -> a0
-    if (transformer_pass(m, w.enc_tr, L, 0, m->a0.row0(), st)) return -2;
-    // stride-2 downsample, replicate padding, no bias -> rvq buffer [T][d]
-    const int dshift[4] = {-2, -1, 0, 1};
-    MCHK(m, gemm(st, m->a0.row0(), d, T, w.downsample, nullptr, d, d, 4, 1, dshift, 0, 0, nullptr, nullptr, 0, m->rvq.row0(), d,
-                 2, 2, 0, (int)L));
-    // split RVQ: semantic level on in_proj_first(z), acoustic levels on in_proj_rest(z)
-    const int cd = c.codebook_dim;
-    float* res_first = m->ln;                   // [T][cd]
-    float* res_rest = m->q;                     // [T][cd]
-    MCHK(m, gemm(st, m->rvq.row0(), d, T, w.in_proj_first, nullptr, d, cd, 1, 1, &zero, 0, 0, nullptr, nullptr, 0, res_first, cd));
-    MCHK(m, gemm(st, m->rvq.row0(), d, T, w.in_proj_rest, nullptr, d, cd, 1, 1, &zero, 0, 0, nullptr, nullptr, 0, res_rest, cd));
-    for (int k = 0; k < c.n_codebooks; ++k) {
-        float* res = k < c.n_semantic ? res_first : res_rest;
-        const float* book = w.codebooks + (long)k * c.codebook_size * cd;
-        MCHK(m, gemm(st, res, cd, T, book, nullptr, cd, c.codebook_size, 1, 1, &zero, 0, 0, nullptr, nullptr, 0, m->ffn, c.codebook_size));
-        hipLaunchKernelGGL(k_rvq_pick, dim3((unsigned)T), dim3(256), 0, st, m->ffn, c.codebook_size,
-                           w.codebook_sqnorm + (long)k * c.codebook_size, book, cd, res, codes + (long)k * T, 1L);
-        MCHK(m, hipGetLastError());
-    }
-    return 0;
-}
-
-extern "C" int mimi_encode(mimi_handle m, const float* wav, long n_samples, long stride_b, int B, int32_t* codes, void* stream) {
-    if (!m || !wav || !codes || B < 1 || n_samples < 1) return mfail(m, "mimi_encode: bad argument");
-    if (!m->w.has_encoder) return mfail(m, "mimi_encode: this codec was created without encoder weights");
-    long hop = 2;
-    for (int j = 0; j < m->cfg.n_stages; ++j) hop *= m->cfg.ratios[j];
-    const long T = ceil_div(n_samples, hop);
-    if (T > m->max_frames) return mfail(m, "mimi_encode: audio longer than hop * max_frames");
-    hipStream_t st = (hipStream_t)stream;
-    for (int b = 0; b < B; ++b) {
-        int rc = encode_one(m, wav + (long)b * stride_b, n_samples, codes + (long)b * m->cfg.n_codebooks * T, T, st);
-        if (rc) return rc;
-    }
-    return mimi_reset_stream(m, stream);      // the work buffers were reused: start any later stream from scratch
-}
-
-extern "C" int mimi_decode_strided(mimi_handle m, const int32_t* codes, int B, int T, long stride_b, long stride_k, long stride_t,
-                                   void* pcm, int stateful, void* stream) {
-    if (!m || !codes || !pcm || B < 1 || T < 1) return mfail(m, "mimi_decode: bad argument");
-    if (T > m->max_frames) return mfail(m, "mimi_decode: T exceeds max_frames given to mimi_create");
-    if (stateful && B != 1) return mfail(m, "mimi_decode: stateful streaming needs B == 1");
-    hipStream_t st = (hipStream_t)stream;
-    long hop = 2;
-    for (int j = 0; j < m->cfg.n_stages; ++j) hop *= m->cfg.ratios[j];
-    for (int b = 0; b < B; ++b) {
-        if (!stateful) { int rc = mimi_reset_stream(m, stream); if (rc) return rc; }
-        if (m->offset + 2L * T > m->cap_tokens) return mfail(m, "mimi_decode: stream longer than max_frames; call mimi_reset_stream");
-        int rc = decode_one(m, codes + (long)b * stride_b, stride_k, stride_t, T, (float*)pcm + (long)b * hop * T, st, !stateful);
-        if (rc) return rc;
-        if (stateful) { rc = slide_all(m, T, st); if (rc) return rc; m->offset += 2 * T; }
-    }
-    return 0;
-}
-
-extern "C" int mimi_decode(mimi_handle m, const int32_t* codes, int B, int T, long stride_b, long stride_k, void* pcm,
-                           int stateful, void* stream) {
-    return mimi_decode_strided(m, codes, B, T, stride_b, stride_k, 1, pcm, stateful, stream);
-}
-
-// ---- stream pool: N stateful streams decoded by one launch chain (include/mimi_hip.h) ------------------------------------------------
-// Buffers that feed a causal op keep EVERY stream's segment in place: stream s owns rows [s * seg, (s + 1) * seg) with seg = hist + the rows
-// of max_chunk_frames, its history in front -- so a call needs no gather and the slide is what it is for one stream.  Work buffers between
-// two such buffers (tok, ln, q, att, ffn, r1) are dense: the listed streams' rows one after the other.  Products between dense buffers are
-// the plain k_gemm32 over n * rows rows; those that touch a segmented buffer, and the q|k|v projection, are its SEG instantiation.
-struct PBuf {
-    float* base = nullptr;
-    int hist = 0, C = 0;
-    long cap = 0;                                   // rows of one stream's chunk at this level
-    int seg() const { return (int)(hist + cap); }   // rows between two streams' segments
-    float* row0() const { return base + (long)hist * C; }       // row 0 of stream 0
-};
-
-struct MimiStreamPool {
-    MimiConfig cfg;
-    MimiWeights w;
-    int n_streams = 0, max_chunk = 0, ring = 0;
-    std::vector<long> offset;                       // tokens each stream has decoded so far
-    PBuf rvq, a0, s0, u[MIMI_MAX_STAGES], xj[MIMI_MAX_STAGES];
-    float* r1[MIMI_MAX_STAGES] = {};
-    float *tok = nullptr, *ln = nullptr, *q = nullptr, *att = nullptr, *ffn = nullptr;
-    float *kc = nullptr, *vc = nullptr;             // [layer][stream][ring][d]
-    int* tab = nullptr;                             // device table of the running call: [i] stream id, [MIMI_POOL_MAX_STREAMS + i] token offset
-    KSplitWs ksw = {nullptr, nullptr, 0, 0, 0, 0};
-    std::string err;
-};
-
+// ---- stream-pool kernels: N stateful streams decoded by one launch chain (include/mimi_hip.h; the segment layout: struct Ladder) -------
 struct PoolIds { int n; int sid[MIMI_POOL_MAX_STREAMS]; int off[MIMI_POOL_MAX_STREAMS]; };
 #define POOL_MAX_REGIONS (3 + 2 * MIMI_MAX_STAGES)
 struct PoolRegions { float* base[POOL_MAX_REGIONS]; int hist[POOL_MAX_REGIONS], C[POOL_MAX_REGIONS], seg[POOL_MAX_REGIONS]; long T[POOL_MAX_REGIONS]; int count; };
@@ -975,79 +527,510 @@ __global__ void k_pool_zero_hist(const PoolRegions z, const PoolIds ids) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < z.hist[reg] * z.C[reg]; i += gridDim.x * blockDim.x) base[i] = 0.f;
 }
 
-static int pfail(MimiStreamPool* p, const char* msg) {
-    if (p) p->err = msg; else g_mimi_err = msg;
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+// Activation buffer of N streams that keeps EVERY stream's segment in place: stream s owns rows [s * seg, (s + 1) * seg) with seg = hist +
+// the rows of the longest chunk, its `hist` rows of left context in front of its row 0.  A handle is the N = 1 case.
+struct SegBuf {
+    float* base = nullptr;
+    int hist = 0, C = 0, rate = 0;                  // rate: rows per frame at this level
+    long cap = 0;                                   // rows of one stream's longest chunk at this level
+    int seg() const { return (int)(hist + cap); }   // rows between two streams' segments
+    float* row0() const { return base + (long)hist * C; }       // row 0 of stream 0
+};
+
+// The buffer ladder that a handle (MimiDecoder, N = 1) and a stream pool embed.  Buffers that feed a causal op are segmented (SegBuf) -- so a
+// pool call needs no gather and the slide is what it is for one stream.  Work buffers between two such buffers (tok, ln, q, att, ffn, r1) are
+// dense: the listed streams' rows one after the other.  Products between dense buffers are the plain k_gemm32 over n * rows rows; those of a
+// pool that touch a segmented buffer, and its q|k|v projection, are the SEG instantiation.
+struct Ladder {
+    SegBuf sb[3 + 2 * MIMI_MAX_STAGES];             // every buffer with history, in slide order: rvq, a0, s0, then u[j], xj[j] per stage
+    int n_sb = 0;
+    SegBuf &rvq = sb[0], &a0 = sb[1], &s0 = sb[2];  // rvq out (hist 1), transformer out (hist kernel-1), conv_in out (hist 1)
+    SegBuf& u(int j) { return sb[3 + 2 * j]; }
+    SegBuf& xj(int j) { return sb[4 + 2 * j]; }
+    float* r1[MIMI_MAX_STAGES] = {};
+    float *tok = nullptr, *ln = nullptr, *q = nullptr, *att = nullptr, *ffn = nullptr;
+    float *kc = nullptr, *vc = nullptr;             // handle: [layer][cap_tokens][d]; pool: [layer][stream][ring][d]
+    long kv_layer = 0;                              // floats of one layer in kc / vc
+    KSplitWs ksw = {nullptr, nullptr, 0, 0, 0, 0};
+};
+
+struct MimiDecoder {
+    MimiConfig cfg;
+    MimiWeights w;
+    int max_frames;
+    long cap_tokens;                    // transformer KV capacity (tokens)
+    int offset;                         // tokens already in the KV caches (stateful stream)
+    Ladder b;
+    hipStream_t cap_stream = nullptr;   // graph capture of decode_middle
+    hipGraphExec_t mid_exec[65] = {};   // by T (stateless decodes of up to MIMI_GRAPH_MAX_T frames)
+    int mid_uses[65] = {};
+    std::string err;
+};
+
+struct MimiStreamPool {
+    MimiConfig cfg;
+    MimiWeights w;
+    int n_streams = 0, max_chunk = 0, ring = 0;
+    std::vector<long> offset;                       // tokens each stream has decoded so far
+    Ladder b;
+    int* tab = nullptr;                             // device table of the running call: [i] stream id, [MIMI_POOL_MAX_STREAMS + i] token offset
+    std::string err;
+};
+
+// h: a handle or a pool (anything with .err), or a null pointer of either type: the thread's error
+#define MCHK(h, x)                                                                                     \
+    do {                                                                                               \
+        hipError_t e_ = (x);                                                                           \
+        if (e_ != hipSuccess) {                                                                        \
+            char b_[256];                                                                              \
+            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
+            if (h) (h)->err = b_; else g_mimi_err = b_;                                                \
+            return -2;                                                                                 \
+        }                                                                                              \
+    } while (0)
+
+template <class H>
+static int fail(H* h, const char* msg) {
+    if (h) h->err = msg; else g_mimi_err = msg;
     return -1;
 }
+static int fail(decltype(nullptr), const char* msg) { return fail((MimiDecoder*)nullptr, msg); }
 
-// the segmented buffers of a pool, with the rows a chunk of T frames adds to each
-static PoolRegions pool_regions(const MimiStreamPool* p, int T) {
-    PoolRegions z;
-    z.count = 0;
-    auto add = [&](const PBuf& b, long rows) {
-        if (!b.hist) return;
-        z.base[z.count] = b.base; z.hist[z.count] = b.hist; z.C[z.count] = b.C; z.seg[z.count] = b.seg(); z.T[z.count] = rows; ++z.count;
-    };
-    long Tj = 2L * T;
-    add(p->rvq, T); add(p->a0, Tj); add(p->s0, Tj);
-    for (int j = 0; j < p->cfg.n_stages; ++j) { Tj *= p->cfg.ratios[j]; add(p->u[j], Tj); add(p->xj[j], Tj); }
-    return z;
+extern "C" void csm_warn_unknown_switches(void);     // csm_engine.hip: names under CSM_ / MIMI_ that no switch reads, once per process
+
+// what the kernels assume of a configuration (mimi_create and mimi_pool_create)
+static const char* config_error(const MimiConfig* cfg) {
+    if (cfg->hidden % 32 || cfg->hidden > 1024 || cfg->codebook_dim % 4 || cfg->tr_ffn % 32 || cfg->hidden / cfg->tr_heads != 64)
+        return "mimi_create: hidden%32, hidden<=1024, tr_ffn%32 and head_dim==64 required";
+    if (cfg->n_stages < 1 || cfg->n_stages > MIMI_MAX_STAGES || cfg->tr_layers > MIMI_MAX_TR_LAYERS || cfg->tr_context > 1024)
+        return "mimi_create: too many stages/layers or context > 1024";
+    if (cfg->kernel > MAX_TAPS || cfg->res_kernel > MAX_TAPS) return "mimi_create: kernel too wide";
+    int c = cfg->n_filters << cfg->n_stages;
+    for (int j = 0; j < cfg->n_stages; ++j) { c /= 2; if ((c / 2) % 32) return "mimi_create: SEANet channels must stay multiples of 32"; }
+    return nullptr;
 }
 
-static int pool_alloc(MimiStreamPool* p) {
-    const MimiConfig& c = p->cfg;
-    const int d = c.hidden, N = p->n_streams;
-    const long T2 = 2L * p->max_chunk;
-    auto abuf = [&](PBuf& b, int hist, long rows, int C) {
-        b.hist = hist; b.C = C; b.cap = rows;
-        const size_t bytes = (size_t)N * (hist + rows) * C * 4;
-        hipError_t e = hipMalloc((void**)&b.base, bytes);
-        return e != hipSuccess ? e : hipMemset(b.base, 0, bytes);
+// The ladder of N streams of up to `frames` frames a call, kv_rows K/V rows per stream and layer, ffn_cols columns of ffn.
+template <class H>
+static int ladder_alloc(H* h, Ladder& b, const MimiConfig& c, int N, long frames, long kv_rows, int ffn_cols) {
+    const int d = c.hidden;
+    const long M2 = 2L * N * frames;                 // rows of a full call at the transformer's rate
+    auto seg = [&](SegBuf& s, int hist, int rate, int C) {
+        s.hist = hist; s.C = C; s.rate = rate; s.cap = frames * rate;
+        const size_t bytes = (size_t)N * (hist + s.cap) * C * 4;
+        hipError_t e = hipMalloc((void**)&s.base, bytes);
+        return e != hipSuccess ? e : hipMemset(s.base, 0, bytes);
     };
-    MCHK(p, abuf(p->rvq, 1, p->max_chunk, d));
-    MCHK(p, abuf(p->a0, c.kernel - 1, T2, d));
-    int C = c.n_filters << c.n_stages;
-    MCHK(p, abuf(p->s0, 1, T2, C));
-    long Tj = T2;
+#define A4(ptr, n) MCHK(h, hipMalloc((void**)&(ptr), (size_t)(n) * 4))
+    int C = c.n_filters << c.n_stages, rate = 2;
+    const int ccap = C > d ? C : d;                  // widest output of a split product (conv_in); >= hidden
+    b.n_sb = 3 + 2 * c.n_stages;
+    MCHK(h, seg(b.rvq, 1, 1, d));
+    MCHK(h, seg(b.a0, c.kernel - 1, 2, d));
+    MCHK(h, seg(b.s0, 1, 2, C));
     for (int j = 0; j < c.n_stages; ++j) {
-        Tj *= c.ratios[j]; C /= 2;
-        MCHK(p, abuf(p->u[j], c.res_kernel - 1, Tj, C));
-        MCHK(p, hipMalloc((void**)&p->r1[j], (size_t)N * Tj * (C / 2) * 4));
-        MCHK(p, abuf(p->xj[j], (j + 1 < c.n_stages) ? 1 : c.last_kernel - 1, Tj, C));
+        rate *= c.ratios[j]; C /= 2;
+        MCHK(h, seg(b.u(j), c.res_kernel - 1, rate, C));
+        A4(b.r1[j], N * frames * rate * (C / 2));
+        MCHK(h, seg(b.xj(j), (j + 1 < c.n_stages) ? 1 : c.last_kernel - 1, rate, C));
     }
-    const long M2 = N * T2;                          // rows of a full call at the transformer's rate
-#define A4(ptr, n) MCHK(p, hipMalloc((void**)&(ptr), (size_t)(n) * 4))
-    A4(p->tok, M2 * d); A4(p->ln, M2 * d); A4(p->q, M2 * d); A4(p->att, M2 * d); A4(p->ffn, M2 * c.tr_ffn);
-    const long kv = (long)c.tr_layers * N * p->ring * d;
-    A4(p->kc, kv); A4(p->vc, kv);
-    A4(p->tab, 2 * MIMI_POOL_MAX_STREAMS);
-    {   // K-split workspace as in mimi_create (same switch, same shapes split: the sums are those of a single handle), sized for a full call
-        const int want = sw_int(SW_MIMI_KSPLIT, MIMI_KSPLIT);
-        if (want == 2 || want == 4 || want == 8) {
-            const int ccap = c.n_filters << c.n_stages;
-            p->ksw.ksplit = want; p->ksw.cap_rows = M2; p->ksw.cap_cols = ccap > d ? ccap : d;
-            p->ksw.n_tickets = (int)((M2 + 31) / 32) * ((p->ksw.cap_cols + 31) / 32);
-            A4(p->ksw.part, (long)want * p->ksw.cap_rows * p->ksw.cap_cols);
-            A4(p->ksw.ticket, p->ksw.n_tickets);
-            MCHK(p, hipMemset(p->ksw.ticket, 0, (size_t)p->ksw.n_tickets * 4));
-        }
+    A4(b.tok, M2 * d); A4(b.ln, M2 * d); A4(b.q, M2 * d); A4(b.att, M2 * d); A4(b.ffn, M2 * ffn_cols);
+    b.kv_layer = N * kv_rows * d;
+    A4(b.kc, c.tr_layers * b.kv_layer); A4(b.vc, c.tr_layers * b.kv_layer);
+    // K-split workspace (k_gemm32): the deep products' partial tiles and tile tickets, sized for a full call.  MIMI_KSPLIT=0 in the
+    // environment: no split.  (A pool splits the same shapes as a handle: its sums are those of a single handle.)
+    const int want = sw_int(SW_MIMI_KSPLIT, MIMI_KSPLIT);
+    if (want == 2 || want == 4 || want == 8) {
+        b.ksw.ksplit = want; b.ksw.cap_rows = M2; b.ksw.cap_cols = ccap;
+        b.ksw.n_tickets = (int)((M2 + 31) / 32) * ((ccap + 31) / 32);
+        A4(b.ksw.part, (long)want * M2 * ccap);
+        A4(b.ksw.ticket, b.ksw.n_tickets);
+        MCHK(h, hipMemset(b.ksw.ticket, 0, (size_t)b.ksw.n_tickets * 4));
     }
 #undef A4
-    MCHK(p, hipDeviceSynchronize());
+    MCHK(h, hipDeviceSynchronize());
     return 0;
 }
 
+static void ladder_free(Ladder& b) {                 // (safe on a half-built ladder: every pointer starts null)
+    for (SegBuf& s : b.sb) (void)hipFree(s.base);
+    for (float* p : b.r1) (void)hipFree(p);
+    void* ps[] = {b.tok, b.ln, b.q, b.att, b.ffn, b.kc, b.vc, b.ksw.part, b.ksw.ticket};
+    for (void* p : ps) (void)hipFree(p);
+}
+
+// the buffers with history, with the rows a chunk of T frames adds to each (reset: T = 0)
+static PoolRegions hist_regions(const Ladder& b, int T) {
+    PoolRegions z;
+    z.count = 0;
+    for (int i = 0; i < b.n_sb; ++i) {
+        const SegBuf& s = b.sb[i];
+        if (!s.hist) continue;
+        z.base[z.count] = s.base; z.hist[z.count] = s.hist; z.C[z.count] = s.C; z.seg[z.count] = s.seg(); z.T[z.count] = (long)T * s.rate; ++z.count;
+    }
+    return z;
+}
+
+extern "C" int mimi_create(const MimiConfig* cfg, const MimiWeights* w, int max_frames, int reserved, mimi_handle* out) {
+    csm_warn_unknown_switches();
+    (void)reserved;
+    if (!cfg || !w || !out || max_frames < 1) return fail(nullptr, "mimi_create: null/invalid argument");
+    if (const char* bad = config_error(cfg)) return fail(nullptr, bad);
+    MimiDecoder* m = new MimiDecoder();
+    m->cfg = *cfg; m->w = *w; m->max_frames = max_frames; m->offset = 0;
+    m->cap_tokens = 2L * max_frames;
+    // (ffn is also the encoder's RVQ score buffer)
+    const int rc = ladder_alloc(m, m->b, *cfg, 1, max_frames, m->cap_tokens, cfg->tr_ffn > cfg->codebook_size ? cfg->tr_ffn : cfg->codebook_size);
+    if (rc) { g_mimi_err = m->err; mimi_destroy(m); return rc; }
+    *out = m;
+    return 0;
+}
+
+extern "C" void mimi_destroy(mimi_handle m) {
+    if (!m) return;
+    ladder_free(m->b);
+    for (hipGraphExec_t g : m->mid_exec) if (g) (void)hipGraphExecDestroy(g);
+    if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
+    delete m;
+}
+
+extern "C" const char* mimi_last_error(mimi_handle m) { return m ? m->err.c_str() : g_mimi_err.c_str(); }
+
+extern "C" int mimi_reset_stream(mimi_handle m, void* stream) {
+    if (!m) return -1;
+    const PoolRegions r = hist_regions(m->b, 0);
+    ZeroRegions z;
+    z.count = r.count;
+    for (int i = 0; i < r.count; ++i) { z.p[i] = r.base[i]; z.n[i] = r.hist[i] * r.C[i]; }
+    if (z.count) {
+        hipLaunchKernelGGL(k_zero_regions, dim3(8, z.count), dim3(256), 0, (hipStream_t)stream, z);
+        MCHK(m, hipGetLastError());
+    }
+    m->offset = 0;
+    return 0;
+}
+
+// ---- one product ---------------------------------------------------------------------------------------------------------------------
+struct RopeOut { float *q, *k, *v; const float* freqs; int offset, d; };
+struct SegArgs { int T, x, o, r, by_id, ring; const int* tab; };       // GemmArgs.seg_*: a product over the stacked rows of a stream pool
+
+// One k_gemm32 launch as its call site states it.  The operands every product has come first (linear() / conv() below fill them); everything
+// else is named by a setter and otherwise keeps the default written here.
+struct Product {
+    const float* x; long ldx, rows;
+    const float *w, *bias; int c_in, c_out, taps, phases;
+    float* out; long ldo;
+    int shift0 = 0, dshift = 0;                     // tap j reads row t * in_stride + shift0 + j * dshift
+    bool elu_in = false, gelu_out = false;
+    const float *col_scale = nullptr, *resid = nullptr; long ldr = 0;
+    int in_stride = 1, edge = 0, row_lo = 0, row_hi = 0;
+    RopeOut ro = {};                                // ro.q != nullptr: the q|k|v projection
+    const KSplitWs* ksw = nullptr;
+    SegArgs sg = {};                                // sg.tab != nullptr: the SEG instantiation
+    Product& taps_at(int s0, int ds) { shift0 = s0; dshift = taps > 1 ? ds : 0; return *this; }
+    Product& elu() { elu_in = true; return *this; }
+    Product& gelu() { gelu_out = true; return *this; }
+    Product& residual(const float* r, long ld) { resid = r; ldr = ld; return *this; }
+    Product& scale_residual(const float* cs, const float* r, long ld) { col_scale = cs; return residual(r, ld); }      // LayerScale, then + r
+    Product& rope(const RopeOut& r) { ro = r; return *this; }
+    Product& ksplit(const KSplitWs& k) { ksw = &k; return *this; }
+    Product& seg(const SegArgs& s) { if (s.tab) sg = s; return *this; }        // (no table: a handle's one stream, the plain instantiation)
+    Product& stride(int s) { in_stride = s; return *this; }                       // a down-sampling conv
+    Product& zero_padded(long lo, long hi) { edge = 1; row_lo = (int)lo; row_hi = (int)hi; return *this; }       // input rows outside [lo, hi) read as zero
+    Product& replicate_padded(long lo, long hi) { edge = 2; row_lo = (int)lo; row_hi = (int)hi; return *this; }  // ... are clamped into [lo, hi)
+};
+static Product linear(const float* x, long ldx, long rows, const float* w, int c_in, int c_out, float* out, long ldo) {
+    return Product{x, ldx, rows, w, nullptr, c_in, c_out, 1, 1, out, ldo};
+}
+// a MimiConv brings its own w, bias, c_in, c_out, taps, phases; causal (tap j reads row t + j - (taps - 1)) unless taps_at() says otherwise
+static Product conv(const float* x, long ldx, long rows, const MimiConv& cv, float* out, long ldo) {
+    return Product{x, ldx, rows, cv.w, cv.bias, cv.c_in, cv.c_out, cv.taps, cv.phases, out, ldo}.taps_at(-(cv.taps - 1), 1);
+}
+
+static hipError_t gemm(hipStream_t st, const Product& g) {
+    GemmArgs a;
+    memset(&a, 0, sizeof a);
+    const bool rope = g.ro.q != nullptr, seg = g.sg.tab != nullptr;
+    if (rope) { a.rope_q = g.ro.q; a.rope_k = g.ro.k; a.rope_v = g.ro.v; a.rope_freqs = g.ro.freqs; a.rope_offset = g.ro.offset; a.rope_d = g.ro.d; }
+    a.in_stride = g.in_stride; a.edge = g.edge; a.row_lo = g.row_lo; a.row_hi = g.row_hi;
+    a.x = g.x; a.ldx = g.ldx; a.T_in = (int)g.rows; a.C_in = g.c_in; a.C_out = g.c_out; a.w = g.w; a.bias = g.bias; a.taps = g.taps;
+    a.phases = g.phases;
+    a.shift0 = g.shift0; a.dshift = g.dshift;           // (every convolution here is an arithmetic progression of taps)
+    a.act_out = g.gelu_out ? 1 : 0; a.col_scale = g.col_scale; a.resid = g.resid; a.ldr = g.ldr; a.out = g.out; a.ldo = g.ldo;
+    dim3 grid((unsigned)((g.rows + 31) / 32), (unsigned)((g.c_out + 31) / 32), (unsigned)g.phases);
+    // (the choice depends on the product's shape alone, never on T_in: a streamed chunk and the whole clip sum in the same order)
+    const int iters = g.taps * (g.c_in / 32);
+    const KSplitWs* ksw = g.ksw;
+    if (ksw != nullptr && ksw->part != nullptr && g.phases == 1 && !rope && iters >= MIMI_KSPLIT_MIN_ITERS && iters % ksw->ksplit == 0) {
+        // (the workspace is sized for the handle's max_frames at mimi_create, so a product the decoder accepts always fits; if one ever
+        //  does not, it runs unsplit -- same value to fp32 rounding -- instead of failing the decode: ADVICE r5)
+        if (g.rows <= ksw->cap_rows && g.c_out <= ksw->cap_cols && (long)grid.x * grid.y <= ksw->n_tickets) {
+            a.ksplit = ksw->ksplit; a.kpart = ksw->part; a.kticket = ksw->ticket;
+            grid.z = (unsigned)ksw->ksplit;
+        }
+    }
+    if (seg) {
+        const SegArgs& s = g.sg;
+        a.seg_T = s.T; a.seg_x = s.x; a.seg_o = s.o; a.seg_r = s.r; a.seg_by_id = s.by_id; a.rope_ring = s.ring; a.seg_tab = s.tab;
+        if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        else hipLaunchKernelGGL((k_gemm32<false, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        return hipGetLastError();
+    }
+    if (g.elu_in) hipLaunchKernelGGL(k_gemm32<true>, grid, dim3(64 * G32_NW), 0, st, a);
+    else hipLaunchKernelGGL(k_gemm32<false>, grid, dim3(64 * G32_NW), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---- the two chains every user shares --------------------------------------------------------------------------------------------------
+// What differs between the transformer's three users: the handle's decode, its encode, and the pool.
+struct TrPass {
+    const MimiTrLayer* layers;
+    long rows;                      // 2T (decode), L (encode), n * 2T (pool: the listed streams' rows stacked)
+    int offset = 0;                 // tokens already in the handle's linear K/V cache: RoPE position and cache row of row 0 (encode: 0)
+    bool lin2_ksplit = true;        // false for the encoder alone: unsplit, its lin2 sums in another order, and the encode goldens were recorded so
+    const int* tab = nullptr;       // pool only: the call's table (position and K/V ring row per stream come from it), rows per stream, ring
+    int T2 = 0, ring = 0;
+};
+
+// layernorm, q|k|v + RoPE, attention, out-proj + LayerScale + residual, layernorm, lin1 + GELU, lin2 + LayerScale + residual: tok -> a0
+template <class H>
+static int transformer(H* h, const MimiConfig& c, const MimiWeights& w, Ladder& b, const TrPass& p, hipStream_t st) {
+    const int d = c.hidden;
+    for (int l = 0; l < c.tr_layers; ++l) {
+        const MimiTrLayer& L = p.layers[l];
+        const bool last = l + 1 == c.tr_layers;
+        float *kc = b.kc + l * b.kv_layer, *vc = b.vc + l * b.kv_layer;
+        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)p.rows), dim3(64), 0, st, b.tok, d, L.ln1_w, L.ln1_b, c.norm_eps, b.ln);
+        MCHK(h, gemm(st, linear(b.ln, d, p.rows, L.in_proj, d, 3 * d, nullptr, 0).rope({b.q, kc, vc, w.rope_freqs, p.offset, d})
+                             .seg({p.T2, p.T2, p.T2, p.T2, 0, p.ring, p.tab})));
+        if (p.tab) hipLaunchKernelGGL(k_pool_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.T2, p.ring, c.tr_context, p.tab, b.att);
+        else hipLaunchKernelGGL(k_mimi_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.offset, c.tr_context, b.att);
+        MCHK(h, gemm(st, linear(b.att, d, p.rows, L.out_proj, d, d, b.tok, d).scale_residual(L.ls1, b.tok, d)));
+        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)p.rows), dim3(64), 0, st, b.tok, d, L.ln2_w, L.ln2_b, c.norm_eps, b.ln);
+        MCHK(h, gemm(st, linear(b.ln, d, p.rows, L.lin1, d, c.tr_ffn, b.ffn, c.tr_ffn).gelu()));
+        Product g = linear(b.ffn, c.tr_ffn, p.rows, L.lin2, c.tr_ffn, d, last ? b.a0.row0() : b.tok, d).scale_residual(L.ls2, b.tok, d);
+        if (p.lin2_ksplit) g.ksplit(b.ksw);
+        if (last) g.seg({p.T2, p.T2, b.a0.seg(), p.T2, 2, 0, p.tab});            // the last layer writes the streams' a0 segments
+        MCHK(h, gemm(st, g));
+        MCHK(h, hipGetLastError());
+    }
+    return 0;
+}
+
+// SEANet decoder: a0 -> conv_in -> per stage up / res1 / res2 -> xj[last], for n streams of T2 rows each (a handle: n = 1, no table)
+template <class H>
+static int seanet_decoder(H* h, const MimiWeights& w, int n_stages, Ladder& b, int n, int T2, const int* tab, hipStream_t st) {
+    MCHK(h, gemm(st, conv(b.a0.row0(), b.a0.C, (long)n * T2, w.conv_in, b.s0.row0(), w.conv_in.c_out).ksplit(b.ksw)
+                         .seg({T2, b.a0.seg(), b.s0.seg(), 0, 1 | 2, 0, tab})));
+    const SegBuf* xin = &b.s0;
+    int Tj = T2;                                                        // rows per stream at the current level
+    for (int j = 0; j < n_stages; ++j) {
+        const MimiConv &up = w.up[j], &r1 = w.res1[j], &r2 = w.res2[j];
+        const SegBuf &u = b.u(j), &xj = b.xj(j);
+        // ELU -> ConvTranspose1d (stride phases, 2 taps each: rows t and t - 1)
+        MCHK(h, gemm(st, conv(xin->row0(), xin->C, (long)n * Tj, up, u.row0(), up.c_out).taps_at(0, -1).elu()
+                             .seg({Tj, xin->seg(), u.seg(), 0, 1 | 2, 0, tab})));
+        Tj *= up.phases;
+        // residual block: u + conv_k1(ELU(conv_k3(ELU(u))))
+        MCHK(h, gemm(st, conv(u.row0(), up.c_out, (long)n * Tj, r1, b.r1[j], r1.c_out).elu().seg({Tj, u.seg(), Tj, 0, 1, 0, tab})));
+        MCHK(h, gemm(st, conv(b.r1[j], r1.c_out, (long)n * Tj, r2, xj.row0(), r2.c_out).elu().residual(u.row0(), up.c_out)
+                             .seg({Tj, Tj, xj.seg(), u.seg(), 2 | 4, 0, tab})));
+        xin = &xj;
+    }
+    return 0;
+}
+
+// ---- single handle ---------------------------------------------------------------------------------------------------------------------
+// A decode is three pieces: front (the only kernel that reads the caller's codes), middle (everything between buffers the handle
+// owns: up-sampling, transformer, SEANet stages -- ~70 launches whose arguments depend on T and the stream offset only) and back (the
+// only kernel that writes the caller's PCM).  The middle of a STATELESS decode (offset 0) is replayed from a hipGraph per T.
+static int decode_front(MimiDecoder* m, const int32_t* codes, long stride_k, long stride_t, int T, hipStream_t st) {
+    const MimiConfig& c = m->cfg;
+    const int d = c.hidden;
+    // RVQ lookup-sum + output projections -> rvq [T][d]
+    hipLaunchKernelGGL(k_rvq, dim3(T, (d + 63) / 64), dim3(256), (size_t)(2 * c.codebook_dim + c.n_codebooks) * 4, st, codes, stride_k, stride_t, T, c.n_codebooks,
+                       c.n_semantic, c.codebook_size, c.codebook_dim, d, m->w.codebooks, m->w.proj_first, m->w.proj_rest,
+                       m->b.rvq.row0(), (long)d);
+    MCHK(m, hipGetLastError());
+    return 0;
+}
+
+static int decode_middle(MimiDecoder* m, int T, hipStream_t st) {
+    Ladder& b = m->b;
+    const int d = m->cfg.hidden;
+    // (ONE stream per handle: the K-split partial tiles and their tickets are per handle, include/mimi_hip.h)
+    // depthwise transposed conv x2 -> tok [2T][d]
+    hipLaunchKernelGGL(k_upsample, dim3((unsigned)((2L * T * d + 255) / 256)), dim3(256), 0, st, b.rvq.row0(), (long)d, T, d,
+                       m->w.upsample, b.tok, (long)d, b.ksw.ticket, b.ksw.ticket ? b.ksw.n_tickets : 0);
+    MCHK(m, hipGetLastError());
+    TrPass tp{m->w.tr, 2L * T};
+    tp.offset = m->offset;
+    if (int rc = transformer(m, m->cfg, m->w, b, tp, st)) return rc;
+    return seanet_decoder(m, m->w, m->cfg.n_stages, b, 1, 2 * T, nullptr, st);
+}
+
+static int decode_back(MimiDecoder* m, int T, float* pcm, hipStream_t st) {
+    const SegBuf& last = m->b.xj(m->cfg.n_stages - 1);
+    const long Tj = (long)T * last.rate;
+    const MimiConv& co = m->w.conv_out;
+    hipLaunchKernelGGL(k_conv_out, dim3((unsigned)((Tj + 255) / 256)), dim3(256), 0, st, last.row0(), (long)last.C, Tj, co.c_in, co.taps, co.w,
+                       co.bias, pcm);
+    MCHK(m, hipGetLastError());
+    return 0;
+}
+
+// chunk sizes whose middle is worth a graph (a streaming chunk is 10 frames, the last one of an utterance 1..9): captured at the
+// SECOND stateless decode of a T, replayed from then on.  Longer decodes (whole utterances, a different T every time) stay eager.
+static const int MIMI_GRAPH_MAX_T = sw_int(SW_MIMI_GRAPH_MAX_T, 32);
+
+static int decode_one(MimiDecoder* m, const int32_t* codes, long stride_k, long stride_t, int T, float* pcm, hipStream_t st, bool stateless) {
+    int rc = decode_front(m, codes, stride_k, stride_t, T, st);
+    if (rc) return rc;
+    if (stateless && T <= MIMI_GRAPH_MAX_T && T < (int)(sizeof m->mid_uses / sizeof m->mid_uses[0]) && m->offset == 0) {
+        if (!m->mid_exec[T] && ++m->mid_uses[T] >= 2) {
+            if (!m->cap_stream) MCHK(m, hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
+            hipGraph_t g = nullptr;
+            MCHK(m, hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
+            const int rc_mid = decode_middle(m, T, m->cap_stream);
+            const hipError_t e2 = hipStreamEndCapture(m->cap_stream, &g);
+            if (rc_mid) { if (g) (void)hipGraphDestroy(g); return rc_mid; }
+            MCHK(m, e2);
+            const hipError_t e3 = hipGraphInstantiate(&m->mid_exec[T], g, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(g);
+            MCHK(m, e3);
+        }
+        if (m->mid_exec[T]) {
+            MCHK(m, hipGraphLaunch(m->mid_exec[T], st));
+            return decode_back(m, T, pcm, st);
+        }
+    }
+    rc = decode_middle(m, T, st);
+    if (rc) return rc;
+    return decode_back(m, T, pcm, st);
+}
+
+// slide the left-context window of every buffer with history by a chunk of T frames
+static int slide_all(MimiDecoder* m, int T, hipStream_t st) {
+    const PoolRegions z = hist_regions(m->b, T);
+    for (int r = 0; r < z.count; ++r) {
+        hipLaunchKernelGGL(k_slide_hist, dim3((z.C[r] + 255) / 256), dim3(256), 0, st, z.base[r], z.hist[r], z.T[r], z.C[r]);
+        MCHK(m, hipGetLastError());
+    }
+    return 0;
+}
+
+static long ceil_div(long a, long b) { return (a + b - 1) / b; }
+
+static int encode_one(MimiDecoder* m, const float* wav, long n, int32_t* codes, long T, hipStream_t st) {
+    const MimiConfig& c = m->cfg;
+    const MimiWeights& w = m->w;
+    Ladder& b = m->b;
+    const int d = c.hidden, S = c.n_stages;
+    // SEANet encoder; stage j lives in the decoder's stage buffers of index S-1-j (same time scale and width).  There is no left context
+    // here: the products read their input zero-padded over [0, L)
+    long L = n;
+    int C = c.n_filters;
+    {
+        const long tot = L * C;
+        hipLaunchKernelGGL(k_enc_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, L, c.kernel, C,
+                           w.enc_conv_in_w, w.enc_conv_in_b, b.u(S - 1).row0());
+    }
+    for (int j = 0; j < S; ++j) {
+        const int bi = S - 1 - j;
+        const MimiConv &r1 = w.enc_res1[j], &r2 = w.enc_res2[j], &dn = w.enc_down[j];
+        float* x = b.u(bi).row0();
+        MCHK(m, gemm(st, conv(x, C, L, r1, b.r1[bi], r1.c_out).elu().zero_padded(0, L)));
+        MCHK(m, gemm(st, conv(b.r1[bi], r1.c_out, L, r2, b.xj(bi).row0(), C).elu().residual(x, C).zero_padded(0, L)));
+        // ELU -> strided conv k = 2r: out[t] = sum_k W_k x[t*r + k - r]; zero padding on both sides
+        const int r = dn.taps / 2;
+        const long Lo = ceil_div(L, r);
+        float* out = (j + 1 < S) ? b.u(bi - 1).row0() : b.s0.row0();
+        MCHK(m, gemm(st, conv(b.xj(bi).row0(), C, Lo, dn, out, dn.c_out).taps_at(-r, 1).stride(r).elu().zero_padded(0, L)));
+        L = Lo; C = dn.c_out;
+    }
+    MCHK(m, gemm(st, conv(b.s0.row0(), C, L, w.enc_conv_out, b.tok, d).elu().zero_padded(0, L)));
+    // encoder transformer (stateless) -> a0
+    TrPass tp{w.enc_tr, L};
+    tp.lin2_ksplit = false;
+    if (transformer(m, c, w, b, tp, st)) return -2;
+    // stride-2 downsample, taps at rows 2t - 2 .. 2t + 1, replicate padding, no bias -> rvq buffer [T][d]
+    const MimiConv down = {w.downsample, nullptr, d, d, 4, 1};
+    MCHK(m, gemm(st, conv(b.a0.row0(), d, T, down, b.rvq.row0(), d).taps_at(-2, 1).stride(2).replicate_padded(0, L)));
+    // split RVQ: semantic level on in_proj_first(z), acoustic levels on in_proj_rest(z)
+    const int cd = c.codebook_dim;
+    float* res_first = b.ln;                    // [T][cd]
+    float* res_rest = b.q;                      // [T][cd]
+    MCHK(m, gemm(st, linear(b.rvq.row0(), d, T, w.in_proj_first, d, cd, res_first, cd)));
+    MCHK(m, gemm(st, linear(b.rvq.row0(), d, T, w.in_proj_rest, d, cd, res_rest, cd)));
+    for (int k = 0; k < c.n_codebooks; ++k) {
+        float* res = k < c.n_semantic ? res_first : res_rest;
+        const float* book = w.codebooks + (long)k * c.codebook_size * cd;
+        MCHK(m, gemm(st, linear(res, cd, T, book, cd, c.codebook_size, b.ffn, c.codebook_size)));
+        hipLaunchKernelGGL(k_rvq_pick, dim3((unsigned)T), dim3(256), 0, st, b.ffn, c.codebook_size,
+                           w.codebook_sqnorm + (long)k * c.codebook_size, book, cd, res, codes + (long)k * T, 1L);
+        MCHK(m, hipGetLastError());
+    }
+    return 0;
+}
+
+static long hop_of(const MimiConfig& c) {
+    long hop = 2;
+    for (int j = 0; j < c.n_stages; ++j) hop *= c.ratios[j];
+    return hop;
+}
+
+extern "C" int mimi_encode(mimi_handle m, const float* wav, long n_samples, long stride_b, int B, int32_t* codes, void* stream) {
+    if (!m || !wav || !codes || B < 1 || n_samples < 1) return fail(m, "mimi_encode: bad argument");
+    if (!m->w.has_encoder) return fail(m, "mimi_encode: this codec was created without encoder weights");
+    const long T = ceil_div(n_samples, hop_of(m->cfg));
+    if (T > m->max_frames) return fail(m, "mimi_encode: audio longer than hop * max_frames");
+    hipStream_t st = (hipStream_t)stream;
+    for (int b = 0; b < B; ++b) {
+        int rc = encode_one(m, wav + (long)b * stride_b, n_samples, codes + (long)b * m->cfg.n_codebooks * T, T, st);
+        if (rc) return rc;
+    }
+    return mimi_reset_stream(m, stream);      // the work buffers were reused: start any later stream from scratch
+}
+
+extern "C" int mimi_decode_strided(mimi_handle m, const int32_t* codes, int B, int T, long stride_b, long stride_k, long stride_t,
+                                   void* pcm, int stateful, void* stream) {
+    if (!m || !codes || !pcm || B < 1 || T < 1) return fail(m, "mimi_decode: bad argument");
+    if (T > m->max_frames) return fail(m, "mimi_decode: T exceeds max_frames given to mimi_create");
+    if (stateful && B != 1) return fail(m, "mimi_decode: stateful streaming needs B == 1");
+    hipStream_t st = (hipStream_t)stream;
+    const long hop = hop_of(m->cfg);
+    for (int b = 0; b < B; ++b) {
+        if (!stateful) { int rc = mimi_reset_stream(m, stream); if (rc) return rc; }
+        if (m->offset + 2L * T > m->cap_tokens) return fail(m, "mimi_decode: stream longer than max_frames; call mimi_reset_stream");
+        int rc = decode_one(m, codes + (long)b * stride_b, stride_k, stride_t, T, (float*)pcm + (long)b * hop * T, st, !stateful);
+        if (rc) return rc;
+        if (stateful) { rc = slide_all(m, T, st); if (rc) return rc; m->offset += 2 * T; }
+    }
+    return 0;
+}
+
+extern "C" int mimi_decode(mimi_handle m, const int32_t* codes, int B, int T, long stride_b, long stride_k, void* pcm,
+                           int stateful, void* stream) {
+    return mimi_decode_strided(m, codes, B, T, stride_b, stride_k, 1, pcm, stateful, stream);
+}
+
+// ---- stream pool -----------------------------------------------------------------------------------------------------------------------
 extern "C" int mimi_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_pool* out) {
     csm_warn_unknown_switches();
-    if (!cfg || !w || !out) return pfail(nullptr, "mimi_pool_create: null argument");
-    if (n_streams < 1 || n_streams > MIMI_POOL_MAX_STREAMS) return pfail(nullptr, "mimi_pool_create: n_streams must be 1 .. MIMI_POOL_MAX_STREAMS (64)");
-    if (max_chunk_frames < 1 || max_chunk_frames > 64) return pfail(nullptr, "mimi_pool_create: max_chunk_frames must be 1 .. 64");
-    if (const char* bad = config_error(cfg)) return pfail(nullptr, bad);
+    if (!cfg || !w || !out) return fail(nullptr, "mimi_pool_create: null argument");
+    if (n_streams < 1 || n_streams > MIMI_POOL_MAX_STREAMS) return fail(nullptr, "mimi_pool_create: n_streams must be 1 .. MIMI_POOL_MAX_STREAMS (64)");
+    if (max_chunk_frames < 1 || max_chunk_frames > 64) return fail(nullptr, "mimi_pool_create: max_chunk_frames must be 1 .. 64");
+    if (const char* bad = config_error(cfg)) return fail(nullptr, bad);
     MimiStreamPool* p = new MimiStreamPool();
     p->cfg = *cfg; p->w = *w; p->n_streams = n_streams; p->max_chunk = max_chunk_frames;
     p->ring = cfg->tr_context + 2 * max_chunk_frames;        // a call's oldest key (offset - context + 1) and newest (offset + 2T - 1) never share a row
     p->offset.assign(n_streams, 0);
-    const int rc = pool_alloc(p);
+    auto alloc = [&]() {
+        MCHK(p, hipMalloc((void**)&p->tab, (size_t)2 * MIMI_POOL_MAX_STREAMS * 4));
+        return ladder_alloc(p, p->b, *cfg, n_streams, max_chunk_frames, p->ring, cfg->tr_ffn);
+    };
+    const int rc = alloc();
     if (rc) { g_mimi_err = p->err; mimi_pool_destroy(p); return rc; }
     *out = p;
     return 0;
@@ -1055,10 +1038,8 @@ extern "C" int mimi_pool_create(const MimiConfig* cfg, const MimiWeights* w, int
 
 extern "C" void mimi_pool_destroy(mimi_pool p) {
     if (!p) return;
-    (void)hipFree(p->rvq.base); (void)hipFree(p->a0.base); (void)hipFree(p->s0.base);
-    for (int j = 0; j < MIMI_MAX_STAGES; ++j) { (void)hipFree(p->u[j].base); (void)hipFree(p->xj[j].base); (void)hipFree(p->r1[j]); }
-    void* ps[] = {p->tok, p->ln, p->q, p->att, p->ffn, p->kc, p->vc, p->tab, p->ksw.part, p->ksw.ticket};
-    for (void* x : ps) (void)hipFree(x);
+    ladder_free(p->b);
+    (void)hipFree(p->tab);
     delete p;
 }
 
@@ -1079,10 +1060,10 @@ static const char* pool_ids(const MimiStreamPool* p, const int32_t* streams, int
 }
 
 extern "C" int mimi_pool_reset(mimi_pool p, const int32_t* streams, int n, void* stream) {
-    if (!p) return pfail(nullptr, "mimi_pool_reset: null pool");
+    if (!p) return fail(p, "mimi_pool_reset: null pool");
     PoolIds ids;
     if (const char* bad = pool_ids(p, streams, n, &ids)) { p->err = std::string("mimi_pool_reset: ") + bad; return -1; }
-    const PoolRegions z = pool_regions(p, 0);
+    const PoolRegions z = hist_regions(p->b, 0);
     // (the rings need no clearing: a window never starts before position 0, and every position is written before it is read)
     hipLaunchKernelGGL(k_pool_zero_hist, dim3(8, n, z.count), dim3(256), 0, (hipStream_t)stream, z, ids);
     MCHK(p, hipGetLastError());
@@ -1092,84 +1073,43 @@ extern "C" int mimi_pool_reset(mimi_pool p, const int32_t* streams, int n, void*
 
 extern "C" int mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, const int32_t* codes, int T, long stride_s, long stride_k,
                                 long stride_t, void* pcm_out, void* stream) {
-    if (!p) return pfail(nullptr, "mimi_pool_decode: null pool");
-    if (!codes || !pcm_out) return pfail(p, "mimi_pool_decode: null codes or pcm");
-    if (T < 1 || T > p->max_chunk) return pfail(p, "mimi_pool_decode: T must be 1 .. max_chunk_frames given to mimi_pool_create");
+    if (!p) return fail(p, "mimi_pool_decode: null pool");
+    if (!codes || !pcm_out) return fail(p, "mimi_pool_decode: null codes or pcm");
+    if (T < 1 || T > p->max_chunk) return fail(p, "mimi_pool_decode: T must be 1 .. max_chunk_frames given to mimi_pool_create");
     PoolIds ids;
     if (const char* bad = pool_ids(p, streams, n, &ids)) { p->err = std::string("mimi_pool_decode: ") + bad; return -1; }
     for (int i = 0; i < n; ++i) {
-        if (p->offset[ids.sid[i]] + 2L * T > 0x7fffffffL) return pfail(p, "mimi_pool_decode: a stream passed 2^31 tokens; reset it");
+        if (p->offset[ids.sid[i]] + 2L * T > 0x7fffffffL) return fail(p, "mimi_pool_decode: a stream passed 2^31 tokens; reset it");
         ids.off[i] = (int)p->offset[ids.sid[i]];
     }
     hipStream_t st = (hipStream_t)stream;
     const MimiConfig& c = p->cfg;
-    const int d = c.hidden, zero = 0;
+    Ladder& b = p->b;
+    const int d = c.hidden;
     const int T2 = 2 * T;
     const long M2 = (long)n * T2;
     const int* tab = p->tab;
-    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(256), 0, st, ids, p->tab, p->ksw.ticket, p->ksw.ticket ? p->ksw.n_tickets : 0);
-    // 1. RVQ lookup-sum + output projections -> rvq segments
+    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(256), 0, st, ids, p->tab, b.ksw.ticket, b.ksw.ticket ? b.ksw.n_tickets : 0);
+    // RVQ lookup-sum + output projections -> rvq segments
     hipLaunchKernelGGL(k_pool_rvq, dim3(n * T, (d + 63) / 64), dim3(256), (size_t)(2 * c.codebook_dim + c.n_codebooks) * 4, st, codes, stride_s,
                        stride_k, stride_t, T, c.n_codebooks, c.n_semantic, c.codebook_size, c.codebook_dim, d, p->w.codebooks, p->w.proj_first,
-                       p->w.proj_rest, p->rvq.row0(), p->rvq.seg(), tab);
-    // 2. depthwise transposed conv x2 -> tok (dense)
-    hipLaunchKernelGGL(k_pool_upsample, dim3((unsigned)((M2 * d + 255) / 256)), dim3(256), 0, st, p->rvq.row0(), p->rvq.seg(), tab, T, n, d,
-                       p->w.upsample, p->tok);
+                       p->w.proj_rest, b.rvq.row0(), b.rvq.seg(), tab);
+    // depthwise transposed conv x2 -> tok (dense)
+    hipLaunchKernelGGL(k_pool_upsample, dim3((unsigned)((M2 * d + 255) / 256)), dim3(256), 0, st, b.rvq.row0(), b.rvq.seg(), tab, T, n, d,
+                       p->w.upsample, b.tok);
     MCHK(p, hipGetLastError());
-    // 3. transformer: every product as in decode_middle, over n * 2T rows
-    for (int l = 0; l < c.tr_layers; ++l) {
-        const MimiTrLayer& L = p->w.tr[l];
-        float* kc = p->kc + (long)l * p->n_streams * p->ring * d;
-        float* vc = p->vc + (long)l * p->n_streams * p->ring * d;
-        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)M2), dim3(64), 0, st, p->tok, d, L.ln1_w, L.ln1_b, c.norm_eps, p->ln);
-        const RopeOut ro = {p->q, kc, vc, p->w.rope_freqs, 0, d};
-        const SegArgs sq = {T2, T2, T2, T2, 0, p->ring, tab};
-        MCHK(p, gemm(st, p->ln, d, M2, L.in_proj, nullptr, d, 3 * d, 1, 1, &zero, 0, 0, nullptr, nullptr, 0, nullptr, 0, 1, 0, 0, 0, &ro, nullptr, &sq));
-        hipLaunchKernelGGL(k_pool_attn, dim3((unsigned)M2, c.tr_heads), dim3(64), 0, st, p->q, kc, vc, d, T2, p->ring, c.tr_context, tab, p->att);
-        MCHK(p, gemm(st, p->att, d, M2, L.out_proj, nullptr, d, d, 1, 1, &zero, 0, 0, L.ls1, p->tok, d, p->tok, d));
-        hipLaunchKernelGGL(k_layernorm, dim3((unsigned)M2), dim3(64), 0, st, p->tok, d, L.ln2_w, L.ln2_b, c.norm_eps, p->ln);
-        MCHK(p, gemm(st, p->ln, d, M2, L.lin1, nullptr, d, c.tr_ffn, 1, 1, &zero, 0, 1, nullptr, nullptr, 0, p->ffn, c.tr_ffn));
-        if (l + 1 < c.tr_layers) {
-            MCHK(p, gemm(st, p->ffn, c.tr_ffn, M2, L.lin2, nullptr, c.tr_ffn, d, 1, 1, &zero, 0, 0, L.ls2, p->tok, d, p->tok, d, 1, 0, 0, 0, nullptr, &p->ksw));
-        } else {                                                        // the last layer writes the streams' a0 segments
-            const SegArgs sa = {T2, T2, p->a0.seg(), T2, 2, 0, tab};
-            MCHK(p, gemm(st, p->ffn, c.tr_ffn, M2, L.lin2, nullptr, c.tr_ffn, d, 1, 1, &zero, 0, 0, L.ls2, p->tok, d, p->a0.row0(), d, 1, 0, 0, 0, nullptr,
-                         &p->ksw, &sa));
-        }
-        MCHK(p, hipGetLastError());
-    }
-    // 4. SEANet decoder
-    int shifts[MAX_TAPS];
-    for (int j = 0; j < c.kernel; ++j) shifts[j] = j - (c.kernel - 1);
-    const MimiConv& ci = p->w.conv_in;
-    {
-        const SegArgs s = {T2, p->a0.seg(), p->s0.seg(), 0, 1 | 2, 0, tab};
-        MCHK(p, gemm(st, p->a0.row0(), d, M2, ci.w, ci.bias, ci.c_in, ci.c_out, ci.taps, 1, shifts, 0, 0, nullptr, nullptr, 0, p->s0.row0(), ci.c_out,
-                     1, 0, 0, 0, nullptr, &p->ksw, &s));
-    }
-    const PBuf* xin = &p->s0;
-    int Tj = T2;                                                        // rows per stream at the current level
-    for (int j = 0; j < c.n_stages; ++j) {
-        const MimiConv &up = p->w.up[j], &r1 = p->w.res1[j], &r2 = p->w.res2[j];
-        const int tshift[2] = {0, -1};
-        const SegArgs su = {Tj, xin->seg(), p->u[j].seg(), 0, 1 | 2, 0, tab};
-        MCHK(p, gemm(st, xin->row0(), xin->C, (long)n * Tj, up.w, up.bias, up.c_in, up.c_out, 2, up.phases, tshift, 1, 0, nullptr, nullptr, 0,
-                     p->u[j].row0(), up.c_out, 1, 0, 0, 0, nullptr, nullptr, &su));
-        Tj *= up.phases;
-        for (int k = 0; k < r1.taps; ++k) shifts[k] = k - (r1.taps - 1);
-        const SegArgs s1 = {Tj, p->u[j].seg(), Tj, 0, 1, 0, tab};
-        MCHK(p, gemm(st, p->u[j].row0(), up.c_out, (long)n * Tj, r1.w, r1.bias, r1.c_in, r1.c_out, r1.taps, 1, shifts, 1, 0, nullptr, nullptr, 0,
-                     p->r1[j], r1.c_out, 1, 0, 0, 0, nullptr, nullptr, &s1));
-        const SegArgs s2 = {Tj, Tj, p->xj[j].seg(), p->u[j].seg(), 2 | 4, 0, tab};
-        MCHK(p, gemm(st, p->r1[j], r1.c_out, (long)n * Tj, r2.w, r2.bias, r2.c_in, r2.c_out, 1, 1, &zero, 1, 0, nullptr, p->u[j].row0(), up.c_out,
-                     p->xj[j].row0(), r2.c_out, 1, 0, 0, 0, nullptr, nullptr, &s2));
-        xin = &p->xj[j];
-    }
-    // 5. output convolution -> pcm [n][hop * T], then every segmented buffer's history slides by the chunk
+    // transformer and SEANet decoder: every product as in a handle's decode_middle, over n * 2T rows
+    TrPass tp{p->w.tr, M2};
+    tp.tab = tab; tp.T2 = T2; tp.ring = p->ring;
+    if (int rc = transformer(p, c, p->w, b, tp, st)) return rc;
+    if (int rc = seanet_decoder(p, p->w, c.n_stages, b, n, T2, tab, st)) return rc;
+    // output convolution -> pcm [n][hop * T], then every segmented buffer's history slides by the chunk
+    const SegBuf& last = b.xj(c.n_stages - 1);
+    const long Tj = (long)T * last.rate;
     const MimiConv& co = p->w.conv_out;
-    hipLaunchKernelGGL(k_pool_conv_out, dim3((unsigned)(((long)n * Tj + 255) / 256)), dim3(256), 0, st, xin->row0(), xin->seg(), tab, (long)Tj, n, co.c_in,
+    hipLaunchKernelGGL(k_pool_conv_out, dim3((unsigned)((n * Tj + 255) / 256)), dim3(256), 0, st, last.row0(), last.seg(), tab, Tj, n, co.c_in,
                        co.taps, co.w, co.bias, (float*)pcm_out);
-    const PoolRegions z = pool_regions(p, T);
+    const PoolRegions z = hist_regions(b, T);
     int maxC = 0;
     for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
     hipLaunchKernelGGL(k_pool_slide, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);

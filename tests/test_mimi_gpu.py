@@ -154,6 +154,29 @@ def test_tiny_encode_vs_oracle(tiny_codec):
     assert pcm.shape == (2, 1, 10 * 1920) and torch.isfinite(pcm).all()
 
 
+def test_decodes_after_an_encode_equal_those_of_a_codec_that_never_encoded():
+    """Encode runs in the decoder's own buffers (stage buffers, tok / ln / q / ffn, the K/V cache, the history rows) and ends the stream:
+    a stateless decode and a stateful stream that follow it give the bits of a fresh codec that never encoded."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from sesameai.mimi import MimiCodec, mimi_tiny_args, synthetic_state_dict
+    args = mimi_tiny_args()
+    used, fresh = (MimiCodec(args, synthetic_state_dict(args, seed=4321), max_frames=64) for _ in range(2))
+    g = torch.Generator().manual_seed(21)
+    wav = torch.randn(1, 1, args.hop * 3 + 1, generator=g) * 0.3          # not a multiple of the hop: 4 frames
+    c4 = torch.randint(0, 2048, (1, 32, 4), generator=g)
+    assert used.encode(wav).shape == (1, 32, 4)
+
+    def decodes(codec):
+        out = [codec.decode(c4)]
+        codec.reset_stream()
+        return out + [codec.decode_stream(c4[..., :2]), codec.decode_stream(c4[..., 2:])]
+
+    for what, got, want in zip(("stateless T=4", "stream chunk 1", "stream chunk 2"), decodes(used), decodes(fresh)):
+        assert torch.isfinite(want).all() and want.abs().max().item() > 0
+        assert torch.equal(got, want), f"{what} after an encode differs from a fresh codec's"
+
+
 def test_full_size_encode_vs_oracle():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")

@@ -1,5 +1,5 @@
 import sys, os, time, torch
-sys.path.insert(0, "/root/repo/sesameai-tts_amd"); sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/sesameai-tts_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sesameai-tts_amd"))
 from sesameai.mimi import MimiArgs, MimiCodec
 codec = MimiCodec(MimiArgs(), None, device="cuda", max_frames=136)
 g = torch.Generator().manual_seed(0)
