@@ -11,6 +11,7 @@
 #include <string.h>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/csm_hip.h"
@@ -28,6 +29,7 @@
 #include "bb_block.cuh"
 #include "switches.h"
 #include "stack_plan.h"
+#include "dev_pool.h"
 
 #define CSM_FRAME_GRAPHS 4     // captured frame steps kept per handle
 #define CSM_REFILL_SALT 0x9E3779B97F4A7C15ull      /* Philox key domain of slot refills (csm_seed) */
@@ -42,15 +44,23 @@ struct Stack {
     int hd, nq, nkv, cache_len;
     bf16_t *kc, *vc;            // [L][B][KV][cache_len][hd]
     long layer_stride;          // elements per layer
-    long slot_off;              // elements: batch slot the rows of the current call belong to (csm_prefill_slot), else 0
+    long slot_off = 0;          // elements: batch slot the rows of the current call belong to (csm_prefill_slot), else 0
     int nt_attn, nt_mlp;        // cache policy of the q/k/v/o and of the gate/up/down weight streams
-    const CsmLayerWeights *w8, *w8s;      // fp8 weight stream + scales (nullptr = bf16)
+    const CsmLayerWeights *w8 = nullptr, *w8s = nullptr;      // fp8 weight stream + scales (nullptr = bf16)
     CsmLayerWeights pk[CSM_MAX_LAYERS];   // matrix-core operand-order copies of wq..w3 (k_pack_w) for the wide-M path
     CsmLayerWeights pk8[CSM_MAX_LAYERS];  // the same for the e4m3 weight stream (k_pack_w8); valid when has_pk8
-    bool has_pk8;
+    bool has_pk8 = false;
 };
 
+// THE binding of the handle's device-memory owner (dev_pool.h) to HIP.  One rule for this file: after a failed allocation or fill, HIP's
+// last-error word is read and discarded before returning, so the next launch check of the process does not trip over it.
+static const DevBackend HIP_BACKEND = {[](void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }, [](void* p) { return (int)hipFree(p); },
+                                       [](void* p, int byte, size_t bytes) { return (int)hipMemset(p, byte, bytes); }};
+
+// Initial values are stated HERE, once (members without an initialiser start as zero: new CsmModel() value-initialises); csm_create assigns
+// only what it computes from its arguments or reads from a switch.
 struct CsmModel {
+    DevPool pool{&HIP_BACKEND};         // owns every device allocation of the handle: csm_destroy and a failed csm_create release it, nothing else frees
     CsmConfig cfg;
     CsmWeights w;
     int max_batch, max_rows, max_frames, ldl;
@@ -59,14 +69,13 @@ struct CsmModel {
     bf16_t *h, *q, *att, *act;          // backbone rows [max_rows][..]
     float* part;                        // [max(PART_ROWS, max_batch)][H][NSPLIT][ATTN_PS(hd)] split-K attention partials
     int part_rows;
-    int* attn_ctr;                      // [part_rows][KV heads] arrival counters of the split-K attention's in-kernel merge (attn.cuh); nullptr: CSM_ATTN_MERGE=0
+    int* attn_ctr = nullptr;            // [part_rows][KV heads] arrival counters of the split-K attention's in-kernel merge (attn.cuh); nullptr: CSM_ATTN_MERGE=0
     bf16_t *dec_in;                     // [B][2][d_bb]   row0 = last_h, row1 = c0 embedding
     float* slab;                        // [8][max_rows][max(d_bb, d_dec)] fp32 split-K partials of the wide path
     bf16_t *pk_projection, *pk_c0_head, *pk_audio_head;   // packed copies for the wide-M path
-    uint8_t *pk8_c0_head, *pk8_audio_head;                // e4m3 heads in operand order (fp8 mode)
+    uint8_t *pk8_c0_head = nullptr, *pk8_audio_head = nullptr;    // e4m3 heads in operand order (fp8 mode)
     long pk_head_stride;                // elements between packed audio heads
-    std::vector<void*> pk_allocs;
-    bf16_t *qkv0_tab;                   // [(n_codebooks-2)*audio_vocab][nq + 2 nkv]: layer-0 q | k | v of the depth decoder for every
+    bf16_t *qkv0_tab = nullptr;         // [(n_codebooks-2)*audio_vocab][nq + 2 nkv]: layer-0 q | k | v of the depth decoder for every
                                         // (codebook c in 1..ncb-2, token) at its fixed position c+1 (env CSM_QKV0_TABLE=0 disables)
     bf16_t *proj_emb;                   // [n_codebooks*audio_vocab][d_dec] = projection(audio_embeddings), built once at create:
                                         // the decoder input of steps >= 2 is a 2 KB row gather instead of a 4.2 MB GEMV
@@ -80,20 +89,21 @@ struct CsmModel {
     // launches get the pointer only once the handle has set an entry (slot_tab_used); until then they get nullptr and every captured
     // frame step is node for node what it is without the table -- the rule of the inject node
     SlotSampling* slot_tab;             // [max_batch]
-    bool slot_tab_used;
+    bool slot_tab_used = false;
     std::vector<unsigned char> slot_tab_host;   // [max_batch] host mirror for csm_describe: bit 0 = has an entry, bit 1 = own seed
     int* frame_save;                    // [ncb] slot 0's newest frame while a slot refill's depth pass uses scratch row 0
     // refill beside the frame loop (csm_refill_begin / csm_refill_advance): a prompt runs a few backbone layers per call between frame
     // steps; its residual stream and the next layer's normalised input live in buffers of their own, everything else is transient
     int* fresh;                         // [max_batch] device flags: the slot's next frame step yields its frame 0 from rf_last
-    bf16_t *rf_h, *rf_xn, *rf_last;     // [max_rows][d_bb] x 2, [max_batch][2 d_bb] final-normed last prompt row per slot (dec_in layout)
+    bf16_t *rf_h = nullptr, *rf_xn = nullptr, *rf_last = nullptr;     // [max_rows][d_bb] x 2, [max_batch][2 d_bb] final-normed last prompt row per slot (dec_in
+                                        // layout).  Made together by the handle's first begin call (refill_buffers): all three or none
     std::vector<char> rf_fresh_host;    // [max_batch] host mirror of `fresh` == 1: slots whose completed refill waits for a frame step to sample its
-    int rf_fresh_count;                 // frame 0 -- several can wait at once (a generator fills B slots before the first step: ADVICE r5)
-    RefillRec rf;                       // the pending refill, one slot (csm_refill_begin) or a group in one ragged prefill (csm_refill_group_begin): rag_segs.h
-    int* rg_row_slot;                   // [max_rows] batch slot of each of the group's rows        } written by k_rag_plan at begin
-    int4* rg_tiles;                     // [max_rows / 32 + 32] {slot, first row, rows, -} by walk  }
-    int device;                         // the GPU this handle lives on (csm_generate_frame_s1 makes it current itself)
-    int host_frames;                    // frames launched since reset (host mirror); the history is a ring of max_frames rows
+    int rf_fresh_count = 0;             // frame 0 -- several can wait at once (a generator fills B slots before the first step: ADVICE r5)
+    RefillRec rf = {};                  // (nothing pending) the pending refill, one slot (csm_refill_begin) or a group in one ragged prefill (csm_refill_group_begin): rag_segs.h
+    int* rg_row_slot = nullptr;         // [max_rows] batch slot of each of the group's rows        } written by k_rag_plan at begin; made together
+    int4* rg_tiles = nullptr;           // [max_rows / 32 + 32] {slot, first row, rows, -} by walk  } by the handle's first group begin: both or none
+    int device = 0;                     // the GPU this handle lives on (csm_generate_frame_s1 makes it current itself)
+    int host_frames = 0;                // frames launched since reset (host mirror); the history is a ring of max_frames rows
     int wide_path;                      // MFMA path for M >= wide_min (env CSM_WIDE=0 disables)
     int wide_min;                       // WIDE_MIN_ROWS unless env CSM_WIDE_MIN overrides (tuning knob)
     int xpack;                          // batched decode steps keep activations in operand order (env CSM_XPACK=0 disables)
@@ -101,43 +111,42 @@ struct CsmModel {
     int fp8_wide;                       // fp8 mode: batched decode steps stream e4m3 on the matrix-core path too (env CSM_FP8_WIDE=0 disables)
     int fuse_dec_attn;                  // depth-decoder attention fused into the O-projection (env CSM_FUSE_DEC_ATTN=0 disables)
     // persistent depth decoder (dec_persist.cuh): steps 2..ncb-1 of a batch-1 frame as one launch (env CSM_PERSIST=0 disables)
-    bool persist;
+    bool persist = false;
     dp_u64 *pg_q, *pg_h1, *pg_h2, *pg_l, *pg_p;
     uint32_t* p_state;                  // [0] tag epoch, [1] give-up code of the last launch (0 = ok), [2] tag epoch of the first-step launch
     // the first decoder step (codebook 1: positions 0, 1) of a batch-1 frame as one launch (dec_first.cuh; env CSM_DEC_FIRST=0 disables)
-    bool dec_first;
+    bool dec_first = false;
     dp_u64 *fg_q, *fg_h1, *fg_h2, *fg_p;
     // backbone attention block of a batch-1 decode step as one launch per layer (bb_block.cuh)
-    bool bb_block;
+    bool bb_block = false;
     dp_u64 *bg_q, *bg_a, *bg_s;
-    bool bb_layer;                      // ... and the MLP in the same launch (k_bb_layer)
+    bool bb_layer = false;              // ... and the MLP in the same launch (k_bb_layer)
     dp_u64 *bg_h, *bg_p;
     uint4* b_w2t;                       // [layers] W2 re-tiled, 256 * 4 * 2048 pieces each
-    uint4* b_w2t8;                      // fp8 mode: [layers] e4m3 W2 re-tiled, 256 * 2 * 2048 pieces each
-    bool bb_layer8;                     // fp8 mode: the one-launch layer streams the e4m3 bytes (k_bb_layer<true>)
+    uint4* b_w2t8 = nullptr;            // fp8 mode: [layers] e4m3 W2 re-tiled, 256 * 2 * 2048 pieces each
+    bool bb_layer8 = false;             // fp8 mode: the one-launch layer streams the e4m3 bytes (k_bb_layer<true>)
     uint32_t* b_state;                  // [0] tag epoch, [1] give-up code
     uint4 *p_w2s, *p_w13p;              // [4 layers] re-tiled W2 / packed W1|W3, constant layer stride
     bf16_t *p_wsm, *p_norms;            // [4][2560][1024] q|k|v|o rows, [4][2][1024] norm scales
     int p_trickle, p_poll;
     // the same for 2..32 batched utterances (dec_persist_m.cuh; env CSM_PERSIST_M=0 disables)
-    bool persist_m;
+    bool persist_m = false;
     uint4 *pm_w13, *pm_w2;              // [4 layers] A-operand packed W1 | W3 / W2
     char* pm_xchg;                      // exchange buffers (DM_XCHG_BYTES), 0xFF-filled in front of every launch
     int pm_max_rows;                    // rows up to which the launch is used (env CSM_PERSIST_M_MAX, default 32)
     int pm_trickle;                     // its weight-trickle nap (env CSM_PERSIST_M_TRICKLE; swept 2..16 x poll 0..4 at B = 4 and 32: 4)
-    dp_u64* p_stamps;                   // debug timeline (csm_debug_persist_stamps), else nullptr
-    std::vector<void*> persist_allocs, bb_allocs;   // device memory of the optional all-CU launches
-    char* xslab; size_t xslab_used, xslab_align;     // the small exchange buffers of the B = 1 all-CU launches live in one 2 MB-aligned slab (placement under our control)
-    bool persist_disabled, bb_disabled;             // a launch gave up once: the chain runs from then on (the buffers stay: error words are still read)
-    bool have_last;                     // prefill or a frame step has produced h for csm_depth
-    int last_S;                         // rows per sequence of the h buffer feeding csm_depth
+    dp_u64* p_stamps = nullptr;         // debug timeline (csm_debug_persist_stamps), else nullptr
+    char* xslab = nullptr; size_t xslab_used = 0, xslab_align = 4096;     // the small exchange buffers of the B = 1 all-CU launches live in one 2 MB-aligned slab (placement under our control)
+    bool persist_disabled = false, bb_disabled = false;     // a launch gave up once: the chain runs from then on (the buffers stay: error words are still read)
+    bool have_last = false;             // prefill or a frame step has produced h for csm_depth
+    int last_S = 1;                     // rows per sequence of the h buffer feeding csm_depth
     // captured frame steps: a small LRU keyed on (batch, top-k, temperature, carries the per-slot sampling table) -- a service whose requests alternate sampling parameters or
     // batch sizes (the reference's callers use 0.7/30, 0.8/40 and 0.9/50: tts_service.py:175,266) replays, it does not re-capture
-    struct FrameGraph { hipGraphExec_t exec; hipGraph_t graph; int B, topk; float temp; bool tab; uint64_t used; };     // tab: carries the per-slot sampling table
+    struct FrameGraph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; int B = -1, topk = 0; float temp = 0.f; bool tab = false; uint64_t used = 0; };     // tab: carries the per-slot sampling table
     FrameGraph graphs[CSM_FRAME_GRAPHS];
-    uint64_t graph_clock;
-    int graph_captures;                 // hipGraphInstantiate calls since csm_create (csm_debug_graph_captures)
-    hipStream_t cap_stream;             // capture happens on an internal stream: the caller's may be the legacy NULL stream
+    uint64_t graph_clock = 0;
+    int graph_captures = 0;             // hipGraphInstantiate calls since csm_create (csm_debug_graph_captures)
+    hipStream_t cap_stream = nullptr;   // capture happens on an internal stream: the caller's may be the legacy NULL stream
     std::vector<struct CsmPrefix*> prefixes;     // live K/V snapshots captured from this handle (csm_prefix_capture); orphaned by csm_destroy
     std::string err;
 };
@@ -173,6 +182,13 @@ static void drop_frame_graphs(CsmModel* m) {
 static int fail(CsmModel* h, int code, const char* msg) {
     if (h) h->err = msg; else g_create_err = msg;
     return code;
+}
+
+// a device allocation the handle owns, optionally with every byte set to `fill`; *p stays null on failure (and the last-error word is clean)
+template <class T> static hipError_t dev_get(CsmModel* m, T** p, size_t bytes, int fill = DevPool::NO_FILL) {
+    const hipError_t e = (hipError_t)m->pool.get(p, bytes, fill);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -708,39 +724,40 @@ static bool persist_usable(const CsmModel* m, int B) {
     if (m->persist_disabled) return false;
     return B == 1 ? m->persist : (B >= 2 && B <= m->pm_max_rows && m->persist_m);
 }
-static inline const SlotSampling* slot_table(const CsmModel* m) { return m->slot_tab_used ? m->slot_tab : nullptr; }
+// the per-slot sampling table as the launches get it (from entry `slot` on): nullptr until the handle has set an entry
+static inline SlotSampling* slot_table(const CsmModel* m, int slot = 0) { return m->slot_tab_used ? m->slot_tab + slot : nullptr; }
+// The three decoder argument structs (kernel ABI: DecPersistArgs, DecPersistMArgs, DecFirstArgs), zeroed, with the fields they share: the
+// re-tiled weights, the caches, the error word and the naps.  The two persistent forms also share what a sampling pass is given.
+struct DecPass { float temperature; int topk; const int* forced; void* logits_out; const void* noise; const uint64_t* rng; };
+template <class A> static A dec_args(const CsmModel* m, int trickle, const DecPass* s = nullptr) {
+    A p;
+    memset(&p, 0, sizeof p);
+    p.wsm = m->p_wsm; p.norms = m->p_norms;
+    p.dec_norm = (const bf16_t*)m->w.dec_norm; p.head_t = (const bf16_t*)m->w.audio_head_t; p.rope = m->dec.rope;
+    p.hdec = m->hdec; p.kc = m->dec.kc; p.vc = m->dec.vc; p.kv_layer_stride = m->dec.layer_stride;
+    p.V = m->cfg.audio_vocab; p.err = m->p_state + 1; p.eps = m->cfg.decoder.norm_eps; p.trickle_sleep = trickle; p.poll_sleep = m->p_poll;
+    if constexpr (!std::is_same<A, DecFirstArgs>::value) {
+        p.proj_emb = m->proj_emb; p.qkv0_tab = m->qkv0_tab; p.qd = m->qd;
+        p.temperature = s->temperature; p.topk = s->topk; p.noise = (const bf16_t*)s->noise; p.rng = s->rng; p.forced = s->forced;
+        p.slot_tab = slot_table(m);
+        p.ncb = m->cfg.n_codebooks; p.frame = m->frame; p.logits_out = (bf16_t*)s->logits_out; p.cb_first = 2; p.cb_last = p.ncb - 1;
+        p.stamps = m->p_stamps;
+    }
+    return p;
+}
 static hipError_t launch_dec_persist(CsmModel* m, int B, float temperature, int topk, const int* forced, void* logits_out, const void* noise, hipStream_t st,
                                      const uint64_t* rng = nullptr, int slot_row0 = 0) {
-    if (rng == nullptr) rng = m->rng;
-    const CsmConfig& c = m->cfg;
-    const int V = c.audio_vocab, ncb = c.n_codebooks;
+    const DecPass s = {temperature, topk, forced, logits_out, noise, rng ? rng : m->rng};
     if (B == 1) {
-        DecPersistArgs p;
-        memset(&p, 0, sizeof p);
-        p.wsm = m->p_wsm; p.norms = m->p_norms; p.w2s = m->p_w2s; p.w13p = m->p_w13p;
-        p.dec_norm = (const bf16_t*)m->w.dec_norm; p.head_t = (const bf16_t*)m->w.audio_head_t; p.rope = m->dec.rope;
-        p.proj_emb = m->proj_emb; p.qkv0_tab = m->qkv0_tab; p.hdec = m->hdec; p.qd = m->qd;
-        p.kc = m->dec.kc; p.vc = m->dec.vc; p.kv_layer_stride = m->dec.layer_stride;
-        p.temperature = temperature; p.topk = topk; p.noise = (const bf16_t*)noise; p.rng = rng; p.forced = forced;
-        p.slot_tab = slot_table(m); p.slot_row0 = slot_row0;
-        p.V = V; p.ncb = ncb; p.frame = m->frame; p.logits_out = (bf16_t*)logits_out; p.cb_first = 2; p.cb_last = ncb - 1;
-        p.gQ = m->pg_q; p.gH1 = m->pg_h1; p.gH2 = m->pg_h2; p.gL = m->pg_l; p.gP = m->pg_p;
-        p.err = m->p_state + 1; p.epoch = m->p_state; p.eps = c.decoder.norm_eps; p.trickle_sleep = m->p_trickle; p.poll_sleep = m->p_poll;
-        p.stamps = m->p_stamps;
+        DecPersistArgs p = dec_args<DecPersistArgs>(m, m->p_trickle, &s);
+        p.w2s = m->p_w2s; p.w13p = m->p_w13p; p.slot_row0 = slot_row0;
+        p.gQ = m->pg_q; p.gH1 = m->pg_h1; p.gH2 = m->pg_h2; p.gL = m->pg_l; p.gP = m->pg_p; p.epoch = m->p_state;
         { static int faults_left = sw_int(SW_CSM_PERSIST_FAULT, 0);     // timeline build: the first n launches withhold a granule
           p.fault = faults_left > 0 ? 1 : 0; if (faults_left > 0) --faults_left; }
         return csm_launch_dec_persist(p, st);
     }
-    DecPersistMArgs p;
-    memset(&p, 0, sizeof p);
-    p.wsm = m->p_wsm; p.norms = m->p_norms; p.w2m = m->pm_w2; p.w13m = m->pm_w13;
-    p.dec_norm = (const bf16_t*)m->w.dec_norm; p.head_t = (const bf16_t*)m->w.audio_head_t; p.rope = m->dec.rope;
-    p.proj_emb = m->proj_emb; p.qkv0_tab = m->qkv0_tab; p.hdec = m->hdec; p.qd = m->qd;
-    p.kc = m->dec.kc; p.vc = m->dec.vc; p.kv_layer_stride = m->dec.layer_stride;
-    p.temperature = temperature; p.topk = topk; p.noise = (const bf16_t*)noise; p.rng = rng; p.forced = forced;
-    p.slot_tab = slot_table(m);
-    p.V = V; p.ncb = ncb; p.M = B; p.frame = m->frame; p.logits_out = (bf16_t*)logits_out; p.cb_first = 2; p.cb_last = ncb - 1;
-    p.xchg = m->pm_xchg; p.stamps = m->p_stamps; p.err = m->p_state + 1; p.eps = c.decoder.norm_eps; p.trickle_sleep = m->pm_trickle; p.poll_sleep = m->p_poll;
+    DecPersistMArgs p = dec_args<DecPersistMArgs>(m, m->pm_trickle, &s);
+    p.w2m = m->pm_w2; p.w13m = m->pm_w13; p.M = B; p.xchg = m->pm_xchg;
     // every exchange dword starts as the poison (dec_persist_m.cuh).  A KERNEL node, not a memset node (round 4): with hipMemsetAsync captured
     // into the frame-step graph, a handle replaying its graph beside another handle whose graph has a different shape (tools/dbg/two_handles_diag2.py:
     // CSM_ATTN_MERGE=0 beside =1) got garbage from codebook 2 on -- the launch saw exchange buffers that were not (yet) poisoned; eager launches,
@@ -756,14 +773,9 @@ static hipError_t launch_dec_persist(CsmModel* m, int B, float temperature, int 
 
 static bool first_usable(const CsmModel* m, int B) { return B == 1 && m->dec_first && m->persist && !m->persist_disabled; }
 static hipError_t launch_dec_first(CsmModel* m, hipStream_t st) {
-    DecFirstArgs p;
-    memset(&p, 0, sizeof p);
-    p.wsm = m->p_wsm; p.norms = m->p_norms; p.w2s = m->p_w2s; p.w13p = m->p_w13p;
-    p.dec_norm = (const bf16_t*)m->w.dec_norm; p.head_t = (const bf16_t*)m->w.audio_head_t; p.rope = m->dec.rope;
-    p.hdec = m->hdec; p.kc = m->dec.kc; p.vc = m->dec.vc; p.kv_layer_stride = m->dec.layer_stride;
-    p.V = m->cfg.audio_vocab; p.logits = m->logits;
-    p.gQ = m->fg_q; p.gH1 = m->fg_h1; p.gH2 = m->fg_h2; p.gP = m->fg_p;
-    p.err = m->p_state + 1; p.epoch = m->p_state + 2; p.eps = m->cfg.decoder.norm_eps; p.trickle_sleep = m->p_trickle; p.poll_sleep = m->p_poll;
+    DecFirstArgs p = dec_args<DecFirstArgs>(m, m->p_trickle);
+    p.w2s = m->p_w2s; p.w13p = m->p_w13p; p.logits = m->logits;
+    p.gQ = m->fg_q; p.gH1 = m->fg_h1; p.gH2 = m->fg_h2; p.gP = m->fg_p; p.epoch = m->p_state + 2;
     return csm_launch_dec_first(p, st);
 }
 
@@ -876,7 +888,7 @@ static hipError_t launch_advance(CsmModel* m, int B, const int* fed, int pos_inc
     a.max_seq = m->cfg.backbone.max_seq; a.overflow = m->n_frames + 1;
     a.err0 = m->p_state + 1; a.err1 = m->b_state + 1;
     a.fresh = (pos_inc && frame_injects(m, B)) ? m->fresh : nullptr;        // only a step that carried the inject node consumes the flags
-    a.slot_tab = m->slot_tab_used ? m->slot_tab : nullptr;
+    a.slot_tab = slot_table(m);
     hipLaunchKernelGGL(k_advance, dim3(1), dim3(256), 0, st, a);
     return hipGetLastError();
 }
@@ -897,6 +909,12 @@ __global__ void k_invalidate_on_error(int32_t* out, int n, const uint32_t* e0, c
     if (!((e0 != nullptr && *e0 != 0u) || (e1 != nullptr && *e1 != 0u))) return;
     for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = -1;
 }
+// ... of the B frames at out_frame; only handles that run an all-CU launch carry the node
+static hipError_t launch_invalidate_on_error(CsmModel* m, int32_t* out_frame, int B, hipStream_t st) {
+    if (!(m->persist || m->bb_block)) return hipSuccess;
+    hipLaunchKernelGGL(k_invalidate_on_error, dim3(1), dim3(256), 0, st, out_frame, B * m->cfg.n_codebooks, m->p_state + 1, m->b_state + 1);
+    return hipGetLastError();
+}
 __global__ void k_fill_i32(int* p, int v, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = v;
 }
@@ -909,58 +927,32 @@ __global__ void k_copy_step_inputs(const int* tokens, const uint8_t* mask, const
     }
 }
 
-static hipError_t pack_weight(CsmModel* m, const void* w, int N, int K, bf16_t** out) {
-    const long pieces = (long)((N + 31) / 32) * (K / 64) * 256;
-    hipError_t e = hipMalloc((void**)out, (size_t)pieces * 16);
+// Operand-order copies for the matrix-core path, by element type: bf16_t through k_pack_w, uint8_t (the e4m3 stream) through k_pack_w8.
+// A matrix [N][K] becomes ceil(N / 32) * (K / 64) * 256 pieces of 8 elements.
+static long pack_pieces(int N, int K) { return (long)((N + 31) / 32) * (K / 64) * 256; }
+static void launch_pack(const void* w, int N, int K, bf16_t* dst, unsigned blocks) { hipLaunchKernelGGL(k_pack_w, dim3(blocks), dim3(256), 0, nullptr, (const bf16_t*)w, N, K, dst); }
+static void launch_pack(const void* w, int N, int K, uint8_t* dst, unsigned blocks) { hipLaunchKernelGGL(k_pack_w8, dim3(blocks), dim3(256), 0, nullptr, (const uint8_t*)w, N, K, (uint2*)dst); }
+// `count` matrices [N][K] that lie one after the other at w, into ONE allocation of the handle's
+template <class T> static hipError_t pack_weight(CsmModel* m, const void* w, int N, int K, T** out, int count = 1) {
+    const long pieces = pack_pieces(N, K);
+    hipError_t e = dev_get(m, out, (size_t)pieces * 8 * sizeof(T) * count);
     if (e != hipSuccess) return e;
-    m->pk_allocs.push_back(*out);
-    hipLaunchKernelGGL(k_pack_w, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, nullptr, (const bf16_t*)w, N, K, *out);
+    for (int i = 0; i < count; ++i) launch_pack((const T*)w + (long)i * N * K, N, K, *out + (long)i * pieces * 8, (unsigned)((pieces + 255) / 256));
     return hipGetLastError();
 }
-
-static hipError_t pack_weight8(CsmModel* m, const void* w, int N, int K, uint8_t** out) {
-    const long pieces = (long)((N + 31) / 32) * (K / 64) * 256;
-    hipError_t e = hipMalloc((void**)out, (size_t)pieces * 8);
-    if (e != hipSuccess) return e;
-    m->pk_allocs.push_back(*out);
-    hipLaunchKernelGGL(k_pack_w8, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, nullptr, (const uint8_t*)w, N, K, (uint2*)*out);
-    return hipGetLastError();
-}
-
-static hipError_t pack_stack8(CsmModel* m, Stack& S) {
-    hipError_t e;
-    const int d = S.d.dim;
-    for (int l = 0; l < S.d.n_layers; ++l) {
-        const CsmLayerWeights& w = S.w8[l];
-        CsmLayerWeights& p = S.pk8[l];
-        uint8_t* t;
-        if ((e = pack_weight8(m, w.wq, S.nq, d, &t)) != hipSuccess) return e; p.wq = t;
-        if ((e = pack_weight8(m, w.wk, S.nkv, d, &t)) != hipSuccess) return e; p.wk = t;
-        if ((e = pack_weight8(m, w.wv, S.nkv, d, &t)) != hipSuccess) return e; p.wv = t;
-        if ((e = pack_weight8(m, w.wo, d, S.nq, &t)) != hipSuccess) return e; p.wo = t;
-        if ((e = pack_weight8(m, w.w1, S.d.ffn, d, &t)) != hipSuccess) return e; p.w1 = t;
-        if ((e = pack_weight8(m, w.w3, S.d.ffn, d, &t)) != hipSuccess) return e; p.w3 = t;
-        if ((e = pack_weight8(m, w.w2, d, S.d.ffn, &t)) != hipSuccess) return e; p.w2 = t;
-    }
-    S.has_pk8 = true;
-    return hipSuccess;
-}
-
-static hipError_t pack_stack(CsmModel* m, Stack& S) {
-    hipError_t e;
-    const int d = S.d.dim;
-    for (int l = 0; l < S.d.n_layers; ++l) {
-        const CsmLayerWeights& w = S.lw[l];
-        CsmLayerWeights& p = S.pk[l];
-        bf16_t* t;
-        if ((e = pack_weight(m, w.wq, S.nq, d, &t)) != hipSuccess) return e; p.wq = t;
-        if ((e = pack_weight(m, w.wk, S.nkv, d, &t)) != hipSuccess) return e; p.wk = t;
-        if ((e = pack_weight(m, w.wv, S.nkv, d, &t)) != hipSuccess) return e; p.wv = t;
-        if ((e = pack_weight(m, w.wo, d, S.nq, &t)) != hipSuccess) return e; p.wo = t;
-        if ((e = pack_weight(m, w.w1, S.d.ffn, d, &t)) != hipSuccess) return e; p.w1 = t;
-        if ((e = pack_weight(m, w.w3, S.d.ffn, d, &t)) != hipSuccess) return e; p.w3 = t;
-        if ((e = pack_weight(m, w.w2, d, S.d.ffn, &t)) != hipSuccess) return e; p.w2 = t;
-    }
+// the seven matrices of every layer: src = S.lw -> S.pk (bf16_t), S.w8 -> S.pk8 (uint8_t)
+template <class T> static hipError_t pack_stack(CsmModel* m, const Stack& S, const CsmLayerWeights* src, CsmLayerWeights* dst) {
+    const int d = S.d.dim, f = S.d.ffn;
+    const void* CsmLayerWeights::* const mat[7] = {&CsmLayerWeights::wq, &CsmLayerWeights::wk, &CsmLayerWeights::wv, &CsmLayerWeights::wo,
+                                                   &CsmLayerWeights::w1, &CsmLayerWeights::w3, &CsmLayerWeights::w2};      // (in allocation order: placement is a measured property)
+    const int N[7] = {S.nq, S.nkv, S.nkv, d, f, f, d}, K[7] = {d, d, d, S.nq, d, d, f};
+    for (int l = 0; l < S.d.n_layers; ++l)
+        for (int i = 0; i < 7; ++i) {
+            T* t;
+            const hipError_t e = pack_weight(m, src[l].*mat[i], N[i], K[i], &t);
+            if (e != hipSuccess) return e;
+            dst[l].*mat[i] = t;
+        }
     return hipSuccess;
 }
 
@@ -970,7 +962,6 @@ static hipError_t pack_stack(CsmModel* m, Stack& S) {
 static void init_stack(Stack& S, const CsmLlamaDims& d, const CsmLayerWeights* lw, const void* norm, const void* rope,
                        int cache_len, int nt_attn, int nt_mlp) {
     S.d = d; S.lw = lw; S.final_norm = (const bf16_t*)norm; S.rope = (const bf16_t*)rope;
-    S.w8 = nullptr; S.w8s = nullptr; S.slot_off = 0;
     S.hd = d.dim / d.n_heads; S.nq = d.n_heads * S.hd; S.nkv = d.n_kv_heads * S.hd; S.cache_len = cache_len; S.nt_attn = nt_attn; S.nt_mlp = nt_mlp;
 }
 
@@ -995,11 +986,11 @@ static hipError_t build_qkv0_table(CsmModel* m) {
     Stack& S = m->dec;
     const int V = c.audio_vocab, ncb = c.n_codebooks, dd = c.decoder.dim, ld = S.nq + 2 * S.nkv;
     hipError_t e;
-    if ((e = hipMalloc((void**)&m->qkv0_tab, (size_t)(ncb - 2) * V * ld * 2)) != hipSuccess) return e;
-    bf16_t *kt = nullptr, *vt = nullptr;                 // scratch caches: one "sequence" per vocabulary entry
+    if ((e = dev_get(m, &m->qkv0_tab, (size_t)(ncb - 2) * V * ld * 2)) != hipSuccess) return e;
+    bf16_t *kt = nullptr, *vt = nullptr;                 // scratch caches: one "sequence" per vocabulary entry (not handle memory: freed below)
     const size_t kv_bytes = (size_t)V * c.decoder.n_kv_heads * S.cache_len * S.hd * 2;
-    if ((e = hipMalloc((void**)&kt, kv_bytes)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&vt, kv_bytes)) != hipSuccess) { (void)hipFree(kt); return e; }
+    if ((e = hipMalloc((void**)&kt, kv_bytes)) == hipSuccess) e = hipMalloc((void**)&vt, kv_bytes);
+    if (e != hipSuccess) (void)hipGetLastError();
     for (int cb = 1; cb <= ncb - 2 && e == hipSuccess; ++cb) {
         bf16_t* tab = m->qkv0_tab + (long)(cb - 1) * V * ld;
         const bool f8 = S.w8 != nullptr;
@@ -1013,7 +1004,7 @@ static hipError_t build_qkv0_table(CsmModel* m) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(kt); (void)hipFree(vt);
+    (void)hipFree(kt); (void)hipFree(vt);                // (null after a failed allocation: a no-op)
     return e;
 }
 
@@ -1021,19 +1012,16 @@ static hipError_t build_qkv0_table(CsmModel* m) {
 // optional all-CU launches: set-up that may fail without failing csm_create
 // ---------------------------------------------------------------------------------------
 #define XSLAB_BYTES ((size_t)4 << 20)
-struct OptAllocs {                                   // allocations of one optional block: freed together when the block is abandoned
-    std::vector<void*> ptrs;
-    bool ok = true;
+struct OptAllocs {                                   // one optional block: what it took from the handle's pool is given back together when the block is abandoned
+    CsmModel* m; size_t mark; bool ok = true;
+    explicit OptAllocs(CsmModel* m_) : m(m_), mark(m_->pool.mark()) {}
     template <class T> void get(T** p, size_t bytes, int fill = 0) {
         *p = nullptr;
-        if (!ok) return;
-        void* v = nullptr;
-        if (hipMalloc(&v, bytes) != hipSuccess || hipMemset(v, fill, bytes) != hipSuccess) { (void)hipGetLastError(); if (v) (void)hipFree(v); ok = false; return; }
-        ptrs.push_back(v); *p = (T*)v;
+        if (ok && dev_get(m, p, bytes, fill) != hipSuccess) ok = false;
     }
-    void drop() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
+    void drop() { m->pool.release_to(mark); }           // (blocks nest: a block is dropped before the one it was opened inside)
     // a small exchange buffer, carved from the model's slab (zero-filled at creation; never freed on its own)
-    template <class T> void small(CsmModel* m, T** p, size_t bytes) {
+    template <class T> void small(T** p, size_t bytes) {
         if (m->xslab == nullptr) { get(p, bytes); return; }
         const size_t al = m->xslab_align, off = (m->xslab_used + al - 1) / al * al;
         if (off + bytes > XSLAB_BYTES) { get(p, bytes); return; }
@@ -1070,9 +1058,9 @@ static void setup_persist(CsmModel* m) {
     //  exactly a bf16 -- so it computes what the fp8 chain computes; the decoder is bound by its hand-offs, not by bytes)
     if (!sw_on(SW_CSM_PERSIST) || !shape_ok || m->qkv0_tab == nullptr) return;
     if (!all_cu_launch_fits(csm_dec_persist_kernel(), DP_LDS_BYTES, "persistent depth decoder")) return;
-    OptAllocs A;
-    A.small(m, &m->pg_q, (size_t)DP_NREP * 768 * 8); A.small(m, &m->pg_h1, (size_t)DP_NREP * 512 * 8); A.small(m, &m->pg_h2, (size_t)DP_NREP * 512 * 8);
-    A.small(m, &m->pg_l, (size_t)DP_NREP * DP_LSLOTS * 8); A.get(&m->pg_p, (size_t)256 * 1024 * 8);
+    OptAllocs A(m);
+    A.small(&m->pg_q, (size_t)DP_NREP * 768 * 8); A.small(&m->pg_h1, (size_t)DP_NREP * 512 * 8); A.small(&m->pg_h2, (size_t)DP_NREP * 512 * 8);
+    A.small(&m->pg_l, (size_t)DP_NREP * DP_LSLOTS * 8); A.get(&m->pg_p, (size_t)256 * 1024 * 8);
     A.get(&m->p_w2s, (size_t)DP_NL * DP_W2S_U4 * 16); A.get(&m->p_w13p, (size_t)DP_NL * DP_W13P_U4 * 16);
     A.get(&m->p_wsm, (size_t)DP_NL * DP_WSM_ROWS * DP_D * 2); A.get(&m->p_norms, (size_t)DP_NL * 2 * DP_D * 2);
     if (!A.ok) { A.drop(); note_fallback("persistent depth decoder", "allocation failed"); return; }
@@ -1095,14 +1083,13 @@ static void setup_persist(CsmModel* m) {
     m->p_trickle = sw_int(SW_CSM_PERSIST_TRICKLE, 8);       // (swept 4..16 x 0..3 at round 2's final state: 8 / 1; re-swept in round 3: 8..10 / 0)
     m->p_poll = sw_int(SW_CSM_PERSIST_POLL, 0);             // (round 3, alternating A/B at the final state: 0 beats 1 by 17 us per frame, 2.744 against 2.762 ms)
     m->persist = true;
-    m->persist_allocs = A.ptrs;
     {   // ---- the first decoder step (positions 0, 1) as one launch: shares the decoder's re-tiled weights, own granule slots ----
         if (sw_on(SW_CSM_DEC_FIRST) && all_cu_launch_fits(csm_dec_first_kernel(), DF_LDS_BYTES, "first depth-decoder step")) {
-            OptAllocs F;
-            F.small(m, &m->fg_q, (size_t)DP_NREP * 1536 * 8); F.small(m, &m->fg_h1, (size_t)DP_NREP * 1024 * 8); F.small(m, &m->fg_h2, (size_t)DP_NREP * 1024 * 8);
+            OptAllocs F(m);
+            F.small(&m->fg_q, (size_t)DP_NREP * 1536 * 8); F.small(&m->fg_h1, (size_t)DP_NREP * 1024 * 8); F.small(&m->fg_h2, (size_t)DP_NREP * 1024 * 8);
             F.get(&m->fg_p, (size_t)2 * 256 * 1024 * 8);
             if (!F.ok) { F.drop(); note_fallback("first depth-decoder step", "allocation failed"); }
-            else { m->dec_first = true; m->persist_allocs.insert(m->persist_allocs.end(), F.ptrs.begin(), F.ptrs.end()); }
+            else m->dec_first = true;
         }
     }
     // ---- the batched form (2..32 rows): shares the q|k|v|o rows and the norms, own packed MLP weights and exchange buffers ----
@@ -1111,7 +1098,7 @@ static void setup_persist(CsmModel* m) {
     if (!sw_on(SW_CSM_PERSIST_M) || m->max_batch < 2 || cfg->audio_vocab <= 2048 || cfg->audio_vocab > 2056) return;
     if (!all_cu_launch_fits(k_dec_persist_m<1>, DM_LDS_BYTES, "batched persistent depth decoder") ||
         !all_cu_launch_fits(k_dec_persist_m<2>, DM_LDS_BYTES, "batched persistent depth decoder")) return;
-    OptAllocs Bm;
+    OptAllocs Bm(m);
     Bm.get(&m->pm_w13, (size_t)DP_NL * DM_W13M_U4 * 16); Bm.get(&m->pm_w2, (size_t)DP_NL * DM_W2M_U4 * 16); Bm.get(&m->pm_xchg, (size_t)DM_XCHG_BYTES, 0xFF);
     if (!Bm.ok) { Bm.drop(); note_fallback("batched persistent depth decoder", "allocation failed"); return; }
     for (int l = 0; l < DP_NL; ++l) {
@@ -1122,27 +1109,25 @@ static void setup_persist(CsmModel* m) {
     }
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); Bm.drop(); note_fallback("batched persistent depth decoder", "weight packing failed"); return; }
     m->persist_m = true;
-    m->persist_allocs.insert(m->persist_allocs.end(), Bm.ptrs.begin(), Bm.ptrs.end());
 }
 
 static void setup_bb_block(CsmModel* m) {
     const CsmLlamaDims& bc = m->cfg.backbone;
     const bool f8 = m->w.fp8 != 0;
-    m->bb_layer8 = false; m->b_w2t8 = nullptr;
     if (!sw_on(SW_CSM_BB_BLOCK) || bc.dim != BB_D || bc.n_heads != BB_NH || bc.n_kv_heads != BB_NKV) return;
     const bool want_layer = sw_on(SW_CSM_BB_LAYER) && bc.ffn == 8192;
     if (f8 && !want_layer) return;                       // the fp8 stream exists only in the one-launch layer (the three-launch block is bf16)
     if (!all_cu_launch_fits(k_bb_attn_block, 0, "one-launch backbone attention block")) return;
-    OptAllocs A;
-    A.small(m, &m->bg_q, (size_t)DP_NREP * BB_NQKV_PAIRS * 8); A.small(m, &m->bg_a, (size_t)DP_NREP * 1024 * 8);
-    A.small(m, &m->bg_s, (size_t)BB_NH * 8 * 72 * 8);
+    OptAllocs A(m);
+    A.small(&m->bg_q, (size_t)DP_NREP * BB_NQKV_PAIRS * 8); A.small(&m->bg_a, (size_t)DP_NREP * 1024 * 8);
+    A.small(&m->bg_s, (size_t)BB_NH * 8 * 72 * 8);
     if (!A.ok || hipDeviceSynchronize() != hipSuccess) { A.drop(); note_fallback("one-launch backbone attention block", "allocation failed"); return; }
-    if (!want_layer) { m->bb_block = true; m->bb_allocs = A.ptrs; return; }
+    if (!want_layer) { m->bb_block = true; return; }
     const bool fits = f8 ? all_cu_launch_fits(k_bb_layer<true>, BL_LDS_BYTES, "one-launch backbone layer (fp8)") : all_cu_launch_fits(k_bb_layer<false>, BL_LDS_BYTES, "one-launch backbone layer");
-    if (!fits) { if (f8) { A.drop(); } else { m->bb_block = true; m->bb_allocs = A.ptrs; } return; }
+    if (!fits) { if (f8) A.drop(); else m->bb_block = true; return; }
     const size_t per_layer = (size_t)256 * (f8 ? 2 : 4) * BB_D;
-    OptAllocs L;
-    L.small(m, &m->bg_h, (size_t)DP_NREP * 1024 * 8); L.get(&m->bg_p, (size_t)256 * 256 * 8 * 8);
+    OptAllocs L(m);
+    L.small(&m->bg_h, (size_t)DP_NREP * 1024 * 8); L.get(&m->bg_p, (size_t)256 * 256 * 8 * 8);
     uint4* w2t = nullptr;
     L.get(&w2t, per_layer * 16 * bc.n_layers);
     bool ok = L.ok;
@@ -1153,12 +1138,10 @@ static void setup_bb_block(CsmModel* m) {
     ok = ok && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         (void)hipGetLastError(); L.drop(); note_fallback("one-launch backbone layer", "allocation / weight re-tiling failed");
-        if (f8) { A.drop(); } else { m->bb_block = true; m->bb_allocs = A.ptrs; }
+        if (f8) A.drop(); else m->bb_block = true;
         return;
     }
     m->bb_block = true;
-    m->bb_allocs = A.ptrs;
-    m->bb_allocs.insert(m->bb_allocs.end(), L.ptrs.begin(), L.ptrs.end());
     if (f8) { m->b_w2t8 = w2t; m->bb_layer8 = true; } else { m->b_w2t = w2t; m->bb_layer = true; }
 }
 
@@ -1185,31 +1168,14 @@ extern "C" void csm_warn_unknown_switches(void) {
     if (!bad.empty()) fprintf(stderr, "libcsm_hip: environment names under CSM_ / MIMI_ that no switch reads (typo? the defaults are in force): %s\n", bad.c_str());
 }
 
-extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_batch, int max_rows, int max_frames,
-                          csm_handle* out) {
-    csm_warn_unknown_switches();
-    if (!cfg || !w || !out || max_batch < 1 || max_frames < 1) return fail(nullptr, CSM_E_INVALID, "csm_create: null/invalid argument");
-    const CsmLlamaDims* dims[2] = {&cfg->backbone, &cfg->decoder};
-    for (const CsmLlamaDims* d : dims) {
-        if (d->n_layers < 1 || d->n_layers > CSM_MAX_LAYERS || d->dim % 512 || d->ffn % 512 || d->n_heads % d->n_kv_heads)
-            return fail(nullptr, CSM_E_INVALID, "csm_create: dims must satisfy dim%512==0, ffn%512==0, layers<=32");
-        const int hd = d->dim / d->n_heads, ki = d->dim / 512, kf = d->ffn / 512;
-        if (hd != 64 && hd != 128) return fail(nullptr, CSM_E_INVALID, "csm_create: head_dim must be 64 or 128");
-        if ((ki != 1 && ki != 2 && ki != 4 && ki != 16) || (kf != 1 && kf != 2 && kf != 4 && kf != 16))
-            return fail(nullptr, CSM_E_INVALID, "csm_create: dim and ffn must be 512*{1,2,4,16}");
-    }
-    if (cfg->audio_vocab > 4096 || cfg->n_codebooks > 63 || max_batch > 256) return fail(nullptr, CSM_E_INVALID, "csm_create: audio_vocab <= 4096, n_codebooks <= 63, max_batch <= 256 required");
-    if (cfg->n_codebooks > cfg->decoder.max_seq) return fail(nullptr, CSM_E_INVALID, "csm_create: n_codebooks > decoder max_seq");
-    CsmModel* m = new CsmModel();
-    m->cfg = *cfg; m->w = *w; m->max_batch = max_batch; m->max_frames = max_frames;
+// csm_create after `new CsmModel()`.  A failure returns at once, the thread's error text naming what failed; csm_create has the ONE exit path.
+static int create_build(CsmModel* m, int max_rows) {
+    const CsmConfig* cfg = &m->cfg; const CsmWeights* w = &m->w;
+    const int max_batch = m->max_batch, max_frames = m->max_frames;
     if (max_rows < 2 * max_batch) max_rows = 2 * max_batch;
     max_rows = (max_rows + 31) / 32 * 32;      // operand-order activations are addressed by whole 32-row tiles
     m->max_rows = max_rows;
     m->ldl = ((cfg->audio_vocab + 511) / 512) * 512;
-    for (auto& g : m->graphs) { g.exec = nullptr; g.graph = nullptr; g.B = -1; g.used = 0; }
-    m->graph_clock = 0; m->graph_captures = 0; m->cap_stream = nullptr;
-    m->pk8_c0_head = nullptr; m->pk8_audio_head = nullptr; m->bb.has_pk8 = false; m->dec.has_pk8 = false;
-    m->host_frames = 0; m->have_last = false; m->last_S = 1;
     m->fuse_dec_attn = sw_on(SW_CSM_FUSE_DEC_ATTN);
     m->wide_path = sw_on(SW_CSM_WIDE);
     { const int v = sw_int(SW_CSM_WIDE_MIN, 0); m->wide_min = v > 0 ? v : WIDE_MIN_ROWS; }
@@ -1223,7 +1189,8 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     init_stack(m->bb, cfg->backbone, m->w.bb, w->bb_norm, w->bb_rope, cfg->backbone.max_seq, 1, 1);
     init_stack(m->dec, cfg->decoder, m->w.dec, w->dec_norm, w->dec_rope, cfg->n_codebooks, 0, 0);
     const int ncb = cfg->n_codebooks, dbb = cfg->backbone.dim, dd = cfg->decoder.dim;
-#define ALLOC(ptr, bytes) HIPCHK((CsmModel*)nullptr, hipMalloc((void**)&(ptr), (bytes)))   /* on failure the handle is leaked on purpose: the process cannot continue without it */
+#define CREATE(x) HIPCHK((CsmModel*)nullptr, x)
+#define ALLOC(ptr, ...) CREATE(dev_get(m, &(ptr), __VA_ARGS__))      /* (bytes [, fill byte]) from the handle's pool.  The ORDER and the sizes of these are a measured property (see xslab below) */
     m->bb.layer_stride = (long)max_batch * cfg->backbone.n_kv_heads * m->bb.cache_len * m->bb.hd;
     m->dec.layer_stride = (long)max_batch * cfg->decoder.n_kv_heads * m->dec.cache_len * m->dec.hd;
     ALLOC(m->bb.kc, (size_t)m->bb.layer_stride * cfg->backbone.n_layers * 2);
@@ -1236,11 +1203,7 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     ALLOC(m->act, (size_t)max_rows * cfg->backbone.ffn * 2);
     m->part_rows = max_batch > PART_ROWS ? max_batch : PART_ROWS;
     ALLOC(m->part, (size_t)m->part_rows * cfg->backbone.n_heads * BB_NSPLIT_MAX * ATTN_PS(m->bb.hd) * 4);
-    m->attn_ctr = nullptr;
-    if (sw_on(SW_CSM_ATTN_MERGE)) {
-        ALLOC(m->attn_ctr, (size_t)m->part_rows * cfg->backbone.n_kv_heads * 4);
-        HIPCHK((CsmModel*)nullptr, hipMemset(m->attn_ctr, 0, (size_t)m->part_rows * cfg->backbone.n_kv_heads * 4));
-    }
+    if (sw_on(SW_CSM_ATTN_MERGE)) ALLOC(m->attn_ctr, (size_t)m->part_rows * cfg->backbone.n_kv_heads * 4, 0);
     ALLOC(m->dec_in, (size_t)max_batch * 2 * dbb * 2);
     ALLOC(m->proj_emb, (size_t)ncb * cfg->audio_vocab * dd * 2);
     ALLOC(m->slab, (size_t)8 * max_rows * (dbb > dd ? dbb : dd) * 4);
@@ -1249,75 +1212,51 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
     ALLOC(m->qd, dec_rows * m->dec.nq * 2);
     ALLOC(m->attd, dec_rows * m->dec.nq * 2);
     ALLOC(m->actd, dec_rows * cfg->decoder.ffn * 2);
-    ALLOC(m->logits, (size_t)max_batch * m->ldl * 2);
+    ALLOC(m->logits, (size_t)max_batch * m->ldl * 2, 0);
     ALLOC(m->frame, (size_t)max_batch * ncb * 4);
     ALLOC(m->cur_tokens, (size_t)max_batch * (ncb + 1) * 4);
     ALLOC(m->cur_mask, (size_t)max_batch * (ncb + 1));
-    ALLOC(m->cur_pos, (size_t)max_batch * 4);
+    ALLOC(m->cur_pos, (size_t)max_batch * 4, 0);
     ALLOC(m->history, (size_t)max_frames * max_batch * ncb * 4);
-    ALLOC(m->n_frames, 16);
-    ALLOC(m->eos_at, (size_t)max_batch * 4);
+    ALLOC(m->n_frames, 16, 0);
+    ALLOC(m->eos_at, (size_t)max_batch * 4, 0xff);
     ALLOC(m->rng, 32);
     m->rng_slot = m->rng + 2;
     ALLOC(m->frame_save, (size_t)ncb * 4);
-    ALLOC(m->slot_tab, (size_t)max_batch * sizeof(SlotSampling));
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->slot_tab, 0, (size_t)max_batch * sizeof(SlotSampling)));
-    m->slot_tab_used = false; m->slot_tab_host.assign((size_t)max_batch, 0);
-    ALLOC(m->fresh, (size_t)max_batch * 4);
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->fresh, 0, (size_t)max_batch * 4));
-    m->rf_h = m->rf_xn = m->rf_last = nullptr; m->rg_row_slot = nullptr; m->rg_tiles = nullptr; refill_clear(m->rf);
-    m->rf_fresh_host.assign((size_t)max_batch, 0); m->rf_fresh_count = 0;
+    ALLOC(m->slot_tab, (size_t)max_batch * sizeof(SlotSampling), 0);
+    m->slot_tab_host.assign((size_t)max_batch, 0);
+    ALLOC(m->fresh, (size_t)max_batch * 4, 0);
+    m->rf_fresh_host.assign((size_t)max_batch, 0);
     ALLOC(m->dec_pos, (size_t)(ncb + 1) * 2 * max_batch * 4);
     ALLOC(m->slot_scratch, (size_t)max_batch * 4);
-    ALLOC(m->p_state, 16);
-    ALLOC(m->b_state, 16);
+    ALLOC(m->p_state, 16, 0);
+    ALLOC(m->b_state, 16, 0);
 #undef ALLOC
     // decoder positions: slot 0 = {0,1} pairs (first decoder call), slot k = k (one row per sequence)
     std::vector<int> dp((size_t)(ncb + 1) * 2 * max_batch);
     for (int k = 0; k <= ncb; ++k)
         for (int i = 0; i < 2 * max_batch; ++i) dp[(size_t)k * 2 * max_batch + i] = k == 0 ? (i & 1) : k;
-    HIPCHK((CsmModel*)nullptr, hipMemcpy(m->dec_pos, dp.data(), dp.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->logits, 0, (size_t)max_batch * m->ldl * 2));
+    CREATE(hipMemcpy(m->dec_pos, dp.data(), dp.size() * 4, hipMemcpyHostToDevice));
     {   // unseeded handle: seed 0 in both Philox domains
         const uint64_t v[4] = {0, 0, CSM_REFILL_SALT, 0};
-        HIPCHK((CsmModel*)nullptr, hipMemcpy(m->rng, v, 32, hipMemcpyHostToDevice));
+        CREATE(hipMemcpy(m->rng, v, 32, hipMemcpyHostToDevice));
     }
-    m->device = 0; (void)hipGetDevice(&m->device);
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->p_state, 0, 16));
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->b_state, 0, 16));
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->n_frames, 0, 16));
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->cur_pos, 0, (size_t)max_batch * 4));
-    HIPCHK((CsmModel*)nullptr, hipMemset(m->eos_at, 0xff, (size_t)max_batch * 4));
+    (void)hipGetDevice(&m->device);
     if (w->fp8) { m->bb.w8 = m->w.bb8; m->bb.w8s = m->w.bb8s; m->dec.w8 = m->w.dec8; m->dec.w8s = m->w.dec8s; }
     if (m->wide_path) {
-        HIPCHK((CsmModel*)nullptr, pack_stack(m, m->bb));
-        HIPCHK((CsmModel*)nullptr, pack_stack(m, m->dec));
-        HIPCHK((CsmModel*)nullptr, pack_weight(m, w->projection, dd, dbb, &m->pk_projection));
-        HIPCHK((CsmModel*)nullptr, pack_weight(m, w->c0_head, cfg->audio_vocab, dbb, &m->pk_c0_head));
+        CREATE(pack_stack<bf16_t>(m, m->bb, m->bb.lw, m->bb.pk));
+        CREATE(pack_stack<bf16_t>(m, m->dec, m->dec.lw, m->dec.pk));
+        CREATE(pack_weight(m, w->projection, dd, dbb, &m->pk_projection));
+        CREATE(pack_weight(m, w->c0_head, cfg->audio_vocab, dbb, &m->pk_c0_head));
         // the 31 audio heads: packed one after the other (each padded to a multiple of 32 rows)
-        m->pk_head_stride = (long)((cfg->audio_vocab + 31) / 32) * (dd / 64) * 256 * 8;
-        HIPCHK((CsmModel*)nullptr, hipMalloc((void**)&m->pk_audio_head, (size_t)m->pk_head_stride * 2 * (ncb - 1)));
-        m->pk_allocs.push_back(m->pk_audio_head);
-        for (int i = 0; i < ncb - 1; ++i) {
-            const long pieces = m->pk_head_stride / 8;
-            hipLaunchKernelGGL(k_pack_w, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, nullptr,
-                               (const bf16_t*)w->audio_head_t + (long)i * cfg->audio_vocab * dd, cfg->audio_vocab, dd,
-                               m->pk_audio_head + (long)i * m->pk_head_stride);
-        }
-        HIPCHK((CsmModel*)nullptr, hipGetLastError());
+        m->pk_head_stride = pack_pieces(cfg->audio_vocab, dd) * 8;
+        CREATE(pack_weight(m, w->audio_head_t, cfg->audio_vocab, dd, &m->pk_audio_head, ncb - 1));
         if (w->fp8) {                                     // e4m3 stream in operand order for batched decode steps
-            HIPCHK((CsmModel*)nullptr, pack_stack8(m, m->bb));
-            HIPCHK((CsmModel*)nullptr, pack_stack8(m, m->dec));
-            HIPCHK((CsmModel*)nullptr, pack_weight8(m, w->c0_head8, cfg->audio_vocab, dbb, &m->pk8_c0_head));
-            HIPCHK((CsmModel*)nullptr, hipMalloc((void**)&m->pk8_audio_head, (size_t)m->pk_head_stride * (ncb - 1)));
-            m->pk_allocs.push_back(m->pk8_audio_head);
-            for (int i = 0; i < ncb - 1; ++i) {
-                const long pieces = m->pk_head_stride / 8;
-                hipLaunchKernelGGL(k_pack_w8, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, nullptr,
-                                   (const uint8_t*)w->audio_head8 + (long)i * cfg->audio_vocab * dd, cfg->audio_vocab, dd,
-                                   (uint2*)(m->pk8_audio_head + (long)i * m->pk_head_stride));
-            }
-            HIPCHK((CsmModel*)nullptr, hipGetLastError());
+            CREATE(pack_stack<uint8_t>(m, m->bb, m->bb.w8, m->bb.pk8));
+            CREATE(pack_stack<uint8_t>(m, m->dec, m->dec.w8, m->dec.pk8));
+            m->bb.has_pk8 = m->dec.has_pk8 = true;
+            CREATE(pack_weight(m, w->c0_head8, cfg->audio_vocab, dbb, &m->pk8_c0_head));
+            CREATE(pack_weight(m, w->audio_head8, cfg->audio_vocab, dd, &m->pk8_audio_head, ncb - 1));
         }
     }
     {   // proj_emb = Linear(projection)(audio_embeddings), with the production GEMV kernel (same rounding as at run time)
@@ -1325,25 +1264,42 @@ extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_bat
         memset(&a, 0, sizeof a);
         a.x = (const bf16_t*)w->audio_emb; a.x_row_stride = dbb; a.M = ncb * cfg->audio_vocab;
         a.w0 = (const bf16_t*)w->projection; a.N = dd; a.out = m->proj_emb; a.ldo = dd; a.nt = 0;
-        HIPCHK((CsmModel*)nullptr, dbb == 2048 ? launch_gemv_msplit(0, false, a, nullptr) : launch_gemv(Op::STORE, dbb, 0, a, nullptr));
+        CREATE(dbb == 2048 ? launch_gemv_msplit(0, false, a, nullptr) : launch_gemv(Op::STORE, dbb, 0, a, nullptr));
     }
-    HIPCHK((CsmModel*)nullptr, hipDeviceSynchronize());
-    m->qkv0_tab = nullptr;
-    if (sw_on(SW_CSM_QKV0_TABLE) && ncb > 2) HIPCHK((CsmModel*)nullptr, build_qkv0_table(m));
+    CREATE(hipDeviceSynchronize());
+    if (sw_on(SW_CSM_QKV0_TABLE) && ncb > 2) CREATE(build_qkv0_table(m));
+#undef CREATE
     // ---- all-CU launches (persistent depth decoders, one-launch backbone layers): optional fast paths.  Anything that
     //      fails here (shape, device, occupancy, allocation) leaves the flag off and the launch chain in charge.
-    m->persist = false; m->persist_m = false; m->dec_first = false; m->p_stamps = nullptr; m->bb_block = false; m->bb_layer = false; m->persist_disabled = false; m->bb_disabled = false;
     // the B = 1 launches' small exchange buffers (granule replicas: 18..96 KB each) come from ONE 2 MB-aligned slab at 4 KB steps instead of
     // wherever hipMalloc's sub-allocator has room -- same placement in every process (A/B: k_bb_layer 32.2..32.8 -> 31.9 us before the
     // scalar-load fix, within the noise after it; kept for the determinism).  Separate allocations where the slab cannot be had or overflows.
-    m->xslab = nullptr; m->xslab_used = 0; m->xslab_align = 4096;
-    if (hipMalloc((void**)&m->xslab, XSLAB_BYTES) != hipSuccess || hipMemset(m->xslab, 0, XSLAB_BYTES) != hipSuccess) {
-        (void)hipGetLastError();
-        if (m->xslab) (void)hipFree(m->xslab);
-        m->xslab = nullptr;
-    }
+    (void)dev_get(m, &m->xslab, XSLAB_BYTES, 0);
     setup_persist(m);
     setup_bb_block(m);
+    return CSM_OK;
+}
+
+extern "C" int csm_create(const CsmConfig* cfg, const CsmWeights* w, int max_batch, int max_rows, int max_frames,
+                          csm_handle* out) {
+    csm_warn_unknown_switches();
+    if (!cfg || !w || !out || max_batch < 1 || max_frames < 1) return fail(nullptr, CSM_E_INVALID, "csm_create: null/invalid argument");
+    *out = nullptr;
+    const CsmLlamaDims* dims[2] = {&cfg->backbone, &cfg->decoder};
+    for (const CsmLlamaDims* d : dims) {
+        if (d->n_layers < 1 || d->n_layers > CSM_MAX_LAYERS || d->dim % 512 || d->ffn % 512 || d->n_heads % d->n_kv_heads)
+            return fail(nullptr, CSM_E_INVALID, "csm_create: dims must satisfy dim%512==0, ffn%512==0, layers<=32");
+        const int hd = d->dim / d->n_heads, ki = d->dim / 512, kf = d->ffn / 512;
+        if (hd != 64 && hd != 128) return fail(nullptr, CSM_E_INVALID, "csm_create: head_dim must be 64 or 128");
+        if ((ki != 1 && ki != 2 && ki != 4 && ki != 16) || (kf != 1 && kf != 2 && kf != 4 && kf != 16))
+            return fail(nullptr, CSM_E_INVALID, "csm_create: dim and ffn must be 512*{1,2,4,16}");
+    }
+    if (cfg->audio_vocab > 4096 || cfg->n_codebooks > 63 || max_batch > 256) return fail(nullptr, CSM_E_INVALID, "csm_create: audio_vocab <= 4096, n_codebooks <= 63, max_batch <= 256 required");
+    if (cfg->n_codebooks > cfg->decoder.max_seq) return fail(nullptr, CSM_E_INVALID, "csm_create: n_codebooks > decoder max_seq");
+    CsmModel* m = new CsmModel();
+    m->cfg = *cfg; m->w = *w; m->max_batch = max_batch; m->max_frames = max_frames;
+    const int rc = create_build(m, max_rows);
+    if (rc != CSM_OK) { (void)hipGetLastError(); csm_destroy(m); return rc; }      // THE exit path of a failed create: everything made so far is given back, *out stays null
     *out = m;
     return CSM_OK;
 }
@@ -1353,15 +1309,7 @@ extern "C" void csm_destroy(csm_handle m) {
     drop_frame_graphs(m);
     if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
     for (CsmPrefix* p : m->prefixes) { (void)hipFree(p->data); p->data = nullptr; p->owner = nullptr; }      // (the caller still destroys the objects)
-    void* ptrs[] = {m->bb.kc, m->bb.vc, m->dec.kc, m->dec.vc, m->h, m->q, m->att, m->act, m->part, m->attn_ctr, m->dec_in, m->proj_emb, m->slab,
-                    m->hdec, m->qd, m->attd, m->actd, m->logits, m->frame, m->cur_tokens, m->cur_mask, m->cur_pos,
-                    m->history, m->n_frames, m->eos_at, m->rng, m->slot_tab, m->frame_save, m->fresh, m->rf_h, m->rf_xn, m->rf_last, m->rg_row_slot, m->rg_tiles, m->dec_pos, m->slot_scratch, m->p_state, m->b_state, m->qkv0_tab};
-    for (void* p : ptrs) (void)hipFree(p);
-    for (void* p : m->pk_allocs) (void)hipFree(p);
-    if (m->xslab) (void)hipFree(m->xslab);
-    for (void* p : m->persist_allocs) (void)hipFree(p);
-    for (void* p : m->bb_allocs) (void)hipFree(p);
-    if (m->p_stamps) (void)hipFree(m->p_stamps);
+    m->pool.release_all();
     delete m;
 }
 
@@ -1534,8 +1482,7 @@ extern "C" int csm_prefill(csm_handle m, const int32_t* tokens, const uint8_t* m
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(m, launch_embed(m, tokens, mask, B * S, st));
     HIPCHK(m, run_stack(m, m->bb, m->h, m->q, m->att, m->act, B * S, S, pos, -1, st, prompt_opts(prompt_mode != 0)));
-    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, B, S, m->cur_pos, m->cfg.backbone.max_seq, m->n_frames + 1,
-                       m->slot_tab_used ? m->slot_tab : nullptr);
+    hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, B, S, m->cur_pos, m->cfg.backbone.max_seq, m->n_frames + 1, slot_table(m));
     HIPCHK(m, hipGetLastError());
     m->have_last = true; m->last_S = S;
     return CSM_OK;
@@ -1550,10 +1497,7 @@ extern "C" int csm_depth(csm_handle m, int B, float temperature, int topk, const
     HIPCHK(m, run_depth(m, B, m->last_S, temperature, topk, forced, logits_out, noise, st));
     if (out_frame) {
         HIPCHK(m, hipMemcpyAsync(out_frame, m->frame, (size_t)B * m->cfg.n_codebooks * 4, hipMemcpyDeviceToDevice, st));
-        if (m->persist || m->bb_block) {
-            hipLaunchKernelGGL(k_invalidate_on_error, dim3(1), dim3(256), 0, st, out_frame, B * m->cfg.n_codebooks, m->p_state + 1, m->b_state + 1);
-            HIPCHK(m, hipGetLastError());
-        }
+        HIPCHK(m, launch_invalidate_on_error(m, out_frame, B, st));
     }
     if (commit) {
         HIPCHK(m, launch_advance(m, B, forced, 0, st));
@@ -1565,10 +1509,7 @@ extern "C" int csm_depth(csm_handle m, int B, float temperature, int topk, const
 extern "C" int csm_copy_frame(csm_handle m, int B, int32_t* out_frame, void* stream) {
     if (!m || !out_frame || B < 1 || B > m->max_batch) return fail(m, CSM_E_INVALID, "csm_copy_frame: bad argument");
     HIPCHK(m, hipMemcpyAsync(out_frame, m->frame, (size_t)B * m->cfg.n_codebooks * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (m->persist || m->bb_block) {      // (a frame step's k_advance has already turned an invalid frame into -1; this covers frames that were not committed)
-        hipLaunchKernelGGL(k_invalidate_on_error, dim3(1), dim3(256), 0, (hipStream_t)stream, out_frame, B * m->cfg.n_codebooks, m->p_state + 1, m->b_state + 1);
-        HIPCHK(m, hipGetLastError());
-    }
+    HIPCHK(m, launch_invalidate_on_error(m, out_frame, B, (hipStream_t)stream));      // (a frame step's k_advance has already turned an invalid frame into -1; this covers frames that were not committed)
     return CSM_OK;
 }
 
@@ -1757,13 +1698,13 @@ extern "C" int csm_prefill_slot(csm_handle m, int slot, const int32_t* tokens, c
     m->bb.slot_off = 0;
     HIPCHK(m, e);
     hipLaunchKernelGGL(k_set_prefill_state, dim3(1), dim3(256), 0, st, pos, 1, S, m->cur_pos + slot, m->cfg.backbone.max_seq, m->n_frames + 1,
-                       m->slot_tab_used ? m->slot_tab + slot : nullptr);
+                       slot_table(m, slot));
     HIPCHK(m, hipGetLastError());
     HIPCHK(m, hipMemcpyAsync(m->frame_save, m->frame, (size_t)m->cfg.n_codebooks * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(m, run_depth(m, 1, S, temperature, topk, nullptr, nullptr, nullptr, st, m->rng_slot, slot));
     hipLaunchKernelGGL(k_stage_slot, dim3(1), dim3(64), 0, st, m->frame, m->frame_save, m->cfg.n_codebooks, slot, m->max_batch, m->history, m->n_frames,
                        m->max_frames, m->eos_at, m->cur_tokens, m->cur_mask, out_frame, m->p_state + 1, m->b_state + 1, m->rng_slot,
-                       m->slot_tab_used ? m->slot_tab + slot : nullptr);
+                       slot_table(m, slot));
     HIPCHK(m, hipGetLastError());
     if (m->host_frames == 0) m->host_frames = 1;
     m->have_last = true; m->last_S = 1;
@@ -1774,13 +1715,24 @@ extern "C" int csm_prefill_slot(csm_handle m, int slot, const int32_t* tokens, c
 // refill BESIDE the frame loop: the other slots never wait for a whole prompt
 // ---------------------------------------------------------------------------------------
 // the workspace of a refill beside the loop, made by the first begin call of a handle
-static int refill_buffers(CsmModel* m, hipStream_t st) {
+// A workspace the handle makes at its first use is all or nothing: the site takes a mark, allocates everything, and publishes the pointers
+// (and drops the captured frame steps, where the step's node list changes) only then.  Otherwise: back to the mark, every pointer still null.
+static int lazy_failed(CsmModel* m, size_t mark, const char* what, hipError_t e) {
+    m->pool.release_to(mark);
+    const std::string msg = std::string(what) + ": allocation failed: " + hipGetErrorString(e);
+    return fail(m, CSM_E_HIP, msg.c_str());
+}
+
+// the workspace of a refill beside the loop, made by the first begin call of a handle
+static int refill_buffers(CsmModel* m) {
     if (m->rf_last != nullptr) return CSM_OK;
     const int dbb = m->cfg.backbone.dim;
-    HIPCHK(m, hipMalloc((void**)&m->rf_h, (size_t)m->max_rows * dbb * 2));
-    HIPCHK(m, hipMalloc((void**)&m->rf_xn, (size_t)m->max_rows * m->bb.nq * 2));
-    HIPCHK(m, hipMalloc((void**)&m->rf_last, (size_t)m->max_batch * 2 * dbb * 2));
-    HIPCHK(m, hipMemsetAsync(m->rf_last, 0, (size_t)m->max_batch * 2 * dbb * 2, st));
+    const size_t mark = m->pool.mark();
+    bf16_t *h, *xn, *last;
+    hipError_t e;
+    if ((e = dev_get(m, &h, (size_t)m->max_rows * dbb * 2)) != hipSuccess || (e = dev_get(m, &xn, (size_t)m->max_rows * m->bb.nq * 2)) != hipSuccess ||
+        (e = dev_get(m, &last, (size_t)m->max_batch * 2 * dbb * 2, 0)) != hipSuccess) return lazy_failed(m, mark, "refill workspace", e);
+    m->rf_h = h; m->rf_xn = xn; m->rf_last = last;
     drop_frame_graphs(m);                                                              // re-capture: the frame step gains its inject node
     return CSM_OK;
 }
@@ -1815,18 +1767,21 @@ static int refill_begin(CsmModel* m, const char* who, const RagSegs& sg, int til
         return refill_refused(m, CSM_E_STATE, who, m->rf.ragged ? "a refill group is in progress (finish it with csm_refill_group_advance)"
                                                                 : "a refill is in progress (finish it with csm_refill_advance)");
     if (!refill_beside_ok(m, m->max_batch)) return refill_refused(m, CSM_E_STATE, who, "needs the matrix-core decode path (csm_refill_supported); use csm_prefill_slot");
-    { const int rc = refill_buffers(m, st); if (rc != CSM_OK) return rc; }
-    if (ragged && m->rg_row_slot == nullptr) {
-        HIPCHK(m, hipMalloc((void**)&m->rg_row_slot, (size_t)m->max_rows * 4));
-        HIPCHK(m, hipMalloc((void**)&m->rg_tiles, (size_t)(m->max_rows / 32 + RAG_MAX_SEGS) * sizeof(int4)));
+    { const int rc = refill_buffers(m); if (rc != CSM_OK) return rc; }
+    if (ragged && m->rg_tiles == nullptr) {             // (the pointer the launches need: k_rag_plan writes it, the flash kernel walks it)
+        const size_t mark = m->pool.mark();
+        int* row_slot; int4* tl;
+        hipError_t e;
+        if ((e = dev_get(m, &row_slot, (size_t)m->max_rows * 4)) != hipSuccess ||
+            (e = dev_get(m, &tl, (size_t)(m->max_rows / 32 + RAG_MAX_SEGS) * sizeof(int4))) != hipSuccess) return lazy_failed(m, mark, "refill group tables", e);
+        m->rg_row_slot = row_slot; m->rg_tiles = tl;
     }
     const int M = rag_segs_rows(sg);
     HIPCHK(m, launch_embed(m, tokens, mask, M, st, m->rf_h));
     if (ragged) hipLaunchKernelGGL(k_rag_plan, dim3(1), dim3(256), 0, st, sg, pos, m->rg_row_slot, m->rg_tiles, tiles);
     // parked (flag 2): until the prompt is complete a slot's row of the frame steps is a placeholder at positions >= its prompt length (its
     // K/V land beyond the prompt's), and k_advance neither advances it nor tests it against max_seq, however many steps the layers take
-    hipLaunchKernelGGL(k_rag_set_state, dim3(1), dim3(256), 0, st, sg, pos, M, m->cur_pos, m->max_batch, m->cfg.backbone.max_seq, m->n_frames + 1,
-                       m->slot_tab_used ? m->slot_tab : nullptr, m->fresh, 2);
+    hipLaunchKernelGGL(k_rag_set_state, dim3(1), dim3(256), 0, st, sg, pos, M, m->cur_pos, m->max_batch, m->cfg.backbone.max_seq, m->n_frames + 1, slot_table(m), m->fresh, 2);
     HIPCHK(m, hipGetLastError());
     for (int i = 0; i < sg.n; ++i) fresh_clear(m, sg.s[i].slot);
     m->rf.sg = sg; m->rf.ragged = ragged; m->rf.tiles = tiles; m->rf.layer = 0; m->rf.pos = pos;
@@ -2078,8 +2033,11 @@ extern "C" int csm_debug_persist_stamps(csm_handle m, uint64_t* host, int n_word
     return CSM_E_STATE;
 #endif
     if (!m->p_stamps) {
-        HIPCHK(m, hipMalloc((void**)&m->p_stamps, (32 * 32 + 4096 + 256) * 8));
-        HIPCHK(m, hipMemset(m->p_stamps, 0, (32 * 32 + 4096 + 256) * 8));
+        const size_t mark = m->pool.mark();
+        dp_u64* stamps;
+        const hipError_t e = dev_get(m, &stamps, (32 * 32 + 4096 + 256) * 8, 0);
+        if (e != hipSuccess) return lazy_failed(m, mark, "csm_debug_persist_stamps", e);
+        m->p_stamps = stamps;
         drop_frame_graphs(m);                                                             // re-capture with the stamp pointer
     }
     if (host) {
