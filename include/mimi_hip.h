@@ -106,6 +106,21 @@ int mimi_reset_stream(mimi_handle h, void* stream);
  * work buffers: it ends any stateful decode stream.  n_samples <= hop * max_frames.            */
 int mimi_encode(mimi_handle h, const float* wav, long n_samples, long stride_b, int B, int32_t* codes, void* stream);
 
+/* Several clips of DIFFERENT lengths through ONE launch chain (a request's context segments, a batch of voice prompts).
+ * Clip i = n_samples[i] fp32 samples at wav + wav_off[i] (wav: device memory; wav_off, n_samples: host arrays, read before the call
+ * returns).  With T_i = ceil(n_samples[i] / hop), F_i = T_0 + .. + T_(i-1) and F = sum T_i the output is codes[n_codebooks][F] int32
+ * (device): clip i owns columns [F_i, F_i + T_i) of every level.  The clips' rows are stacked along the row axis of every product in
+ * frame-aligned slots -- at a level with R rows per frame clip i owns rows [R * F_i, R * F_i + L_i), L_i <= R * T_i -- in the handle's
+ * existing work buffers; the kernels that reach beyond their own row (the convolutions with taps or a stride, the q|k|v epilogue's RoPE
+ * position, the attention window, the first convolution) find the row's clip in a small device table the chain's first kernel writes from
+ * the kernel arguments: no host-to-device copy, no synchronisation.  No encode product takes a K split and every element's summation
+ * order depends on the product's shape alone, so a clip's codes are, bit for bit, those of mimi_encode of that clip alone, whatever
+ * shares the call and wherever the clip sits in the list.  Like mimi_encode it ends any stateful decode stream of the handle.
+ * Returns -1 with a message in mimi_last_error, nothing enqueued and the handle still usable, for: n outside [1, MIMI_ENCODE_MAX_CLIPS],
+ * an n_samples[i] < 1 (or a negative wav_off[i]), F > max_frames, a handle without encoder weights, a null pointer.                     */
+#define MIMI_ENCODE_MAX_CLIPS 64
+int mimi_encode_many(mimi_handle h, const float* wav, const long* wav_off, const long* n_samples, int n, int32_t* codes, void* stream);
+
 /* ---- A pool of stateful decode streams decoded TOGETHER (many callers served from one batch of the frame loop) ----
  * A pool holds n_streams independent streams: per stream the left-context rows of every causal buffer, a per-layer K/V ring of
  * tr_context + 2 * max_chunk_frames tokens and its own token offset (RoPE position, window start).  A stream runs for any number of

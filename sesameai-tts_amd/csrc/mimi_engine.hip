@@ -24,6 +24,9 @@
 
 #include "../../include/mimi_hip.h"
 #include "switches.h"
+#define ENC_SEGS_FN __host__ __device__ static inline
+#include "enc_segs.h"
+static_assert(ENC_MAX_CLIPS == MIMI_ENCODE_MAX_CLIPS && ENC_MAX_STAGES == MIMI_MAX_STAGES, "enc_segs.h and mimi_hip.h disagree");
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 static thread_local std::string g_mimi_err;
@@ -35,6 +38,11 @@ static thread_local std::string g_mimi_err;
 #define MIMI_KSPLIT_MAX 8
 #define MIMI_KSPLIT_MIN_ITERS 64        // deep products only: (taps * C_in / 32) iterations, e.g. the K = 2048 linear (64), the 7-tap 512 -> 1024 conv (112)
 struct KSplitWs { float* part; int* ticket; long cap_rows; int cap_cols, n_tickets, ksplit; };
+
+// Device table of a ragged encode (mimi_encode_many; written by k_enc_plan, the first kernel of the chain): per clip where its samples
+// start, its first frame and its rows at every level (enc_segs.h); behind the clips, frame -> clip for the call's F frames.
+struct EncClipTab { long wav_off; int F0; int L[ENC_MAX_LEVELS]; };
+struct RagArgs { const EncClipTab* clips; const int* frame_clip; int lvl_in, lvl_out, rate_in, rate_out; };
 
 struct GemmArgs {
     const float* x; long ldx;       // A row for output time t, tap j: x + (t * in_stride + shift0 + j * dshift) * ldx
@@ -66,6 +74,12 @@ struct GemmArgs {
     // token offset seg_tab[MIMI_POOL_MAX_STREAMS + si].
     int seg_T, seg_x, seg_o, seg_r, seg_by_id, rope_ring;
     const int* seg_tab;
+    // Ragged encode (the RAG instantiation only; mimi_encode_many below): the rows of the launch are those of several clips, frame-aligned:
+    // at a level with R rows per frame clip c owns rows [R * F0_c, R * F0_c + L_c(level)).  Output row g belongs to the clip of frame
+    // g / rate_out; with edge != 0 its A rows start at rate_in * F0_c + (g - rate_out * F0_c) * in_stride and the edge bounds are the CLIP's
+    // [rate_in * F0_c, + L_c(lvl_in)): a tap reads neither a neighbour's rows nor the unused tail of its own slot.  (edge 0: a dense product,
+    // A row = output row.)  The q|k|v epilogue takes the RoPE position from the token's index inside its clip; the K/V row is the global row.
+    RagArgs rag;
 };
 
 __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expf(v) - 1.0f; }
@@ -88,7 +102,7 @@ __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expf(v) - 
 // the weights re-tiled into MFMA operand order so that every wave load is one contiguous 1 KB (the K = 2048 linear 24 us against
 // 19.5 row-major: with one 32-row tile these launches sit on 16..64 CUs and are bound by the fp32 matrix pipe -- 128 dependent
 // 64-cycle v_mfma_f32_32x32x2_f32 per wave, two waves per SIMD = 6.8 us -- plus the ~4.7 us of a dependent launch, not by loads).
-template <bool ELU, bool SEG = false>
+template <bool ELU, bool SEG = false, bool RAG = false>
 __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
     __shared__ float red[G32_NW][16][64];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -107,14 +121,20 @@ __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
         const int si = trow / a.seg_T, tl = trow - si * a.seg_T;
         arow0 = ((a.seg_by_id & 1) ? a.seg_tab[si] : si) * a.seg_x + tl * a.in_stride + a.shift0;
     }
+    int row_lo = a.row_lo, row_hi = a.row_hi;
+    if (RAG && a.edge != 0) {
+        const EncClipTab& c = a.rag.clips[a.rag.frame_clip[trow / a.rag.rate_out]];
+        row_lo = a.rag.rate_in * c.F0; row_hi = row_lo + c.L[a.rag.lvl_in];
+        arow0 = row_lo + (trow - a.rag.rate_out * c.F0) * a.in_stride + a.shift0;
+    }
     const float* const wrow = a.w + ((long)p * a.taps * a.C_out + nrow) * a.C_in + h * 16;
     const int it_lo = a.ksplit > 1 ? ks * (iters / a.ksplit) : 0, it_hi = a.ksplit > 1 ? it_lo + iters / a.ksplit : iters;
     for (int it = it_lo + wave; it < it_hi; it += G32_NW) {
         const int j = it / kchunks, kc = (it - j * kchunks) * 32;
         int arow = arow0 + j * a.dshift;
         bool use = trow_ok;
-        if (a.edge == 1) { use = trow_ok && arow >= a.row_lo && arow < a.row_hi; arow = min(max(arow, a.row_lo), a.row_hi - 1); }
-        else if (a.edge == 2) arow = min(max(arow, a.row_lo), a.row_hi - 1);
+        if (a.edge == 1) { use = trow_ok && arow >= row_lo && arow < row_hi; arow = min(max(arow, row_lo), row_hi - 1); }
+        else if (a.edge == 2) arow = min(max(arow, row_lo), row_hi - 1);
         const float* xa = a.x + (long)arow * a.ldx + h * 16 + kc;
         const float* wb = wrow + (long)j * a.C_out * a.C_in + kc;
         float4 av[4], bv[4];
@@ -221,6 +241,7 @@ __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
             rrow = (long)((a.seg_by_id & 4) ? sid : si) * a.seg_r + (long)tl * a.phases + p;
             if (a.rope_q) { pos = a.seg_tab[MIMI_POOL_MAX_STREAMS + si] + tl; kvrow = (long)sid * a.rope_ring + pos % a.rope_ring; }
         }
+        if (RAG && a.rope_q) pos = t - a.rag.rate_out * a.rag.clips[a.rag.frame_clip[t / a.rag.rate_out]].F0;       // (kvrow stays t)
         float v = sum + bias;
         if (a.rope_q) {                                                 // (whole 32-channel tiles: every lane of the half-wave is here)
             const float partner = __shfl_xor(v, 1, 64);
@@ -457,6 +478,58 @@ __global__ __launch_bounds__(256) void k_rvq_pick(const float* score, int ncodes
     for (int d = tid; d < dim; d += 256) resid[(long)t * dim + d] -= book[(long)e * dim + d];
 }
 
+// ---- ragged encode: several clips in one chain (mimi_encode_many; layout: enc_segs.h) ---------------------------------------------------
+// first kernel of a call: the per-clip header of the kernel arguments -> the device table every later kernel reads.  One block.
+__global__ __launch_bounds__(256) void k_enc_plan(const EncHeader hdr, EncClipTab* clips, int* frame_clip) {
+    __shared__ int f0[ENC_MAX_CLIPS + 1];
+    const long hop = enc_level_rate(hdr.ratios, hdr.S, 0);
+    if (threadIdx.x == 0) {
+        int F = 0;
+        for (int i = 0; i < hdr.n; ++i) { f0[i] = F; F += (int)enc_ceil_div(hdr.c[i].n_samples, hop); }
+        f0[hdr.n] = F;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < hdr.n; i += blockDim.x) {
+        clips[i].wav_off = hdr.c[i].wav_off; clips[i].F0 = f0[i];
+        for (int l = 0; l < ENC_MAX_LEVELS; ++l) clips[i].L[l] = l <= hdr.S + 1 ? (int)enc_level_len(hdr.c[i].n_samples, hdr.ratios, hdr.S, l) : 0;
+    }
+    for (int f = threadIdx.x; f < f0[hdr.n]; f += blockDim.x) {
+        int c = 0;
+        while (f >= f0[c + 1]) ++c;
+        frame_clip[f] = c;
+    }
+}
+
+// k_enc_conv_in over the clips' sample slots: a sample's clip comes from its frame, the taps read the clip's own samples, and the rows of
+// a slot's unused tail (no sample behind them) are left alone
+__global__ void k_enc_conv_in_many(const float* wav, long rows, int hop, int taps, int C, const float* w, const float* b, const EncClipTab* clips,
+                                   const int* frame_clip, float* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * C) return;
+    const long g = i / C;
+    const int co = (int)(i % C);
+    const EncClipTab& c = clips[frame_clip[g / hop]];
+    const long t = g - (long)hop * c.F0;                    // the sample's index inside its clip
+    if (t >= c.L[0]) return;
+    const float* x = wav + c.wav_off;
+    float acc = b[co];
+    for (int k = 0; k < taps; ++k) {
+        const long ti = t - (taps - 1) + k;
+        if (ti >= 0) acc = fmaf(x[ti], w[k * C + co], acc);
+    }
+    out[i] = acc;
+}
+
+// k_mimi_attn over the clips' token slots: position = the token's index inside its clip, keys from the clip's row 0
+__global__ __launch_bounds__(64) void k_enc_attn(const float* q, const float* kc, const float* vc, int d, int context, const EncClipTab* clips,
+                                                 const int* frame_clip, float* out) {
+    __shared__ float pbuf[1024];
+    const int g = blockIdx.x, hh = blockIdx.y;
+    const long row0 = 2L * clips[frame_clip[g >> 1]].F0;
+    attn_row<false>(pbuf, q + (long)g * d + hh * 64, kc + row0 * d + hh * 64, vc + row0 * d + hh * 64, d, (int)(g - row0), context, 0,
+                    out + (long)g * d + hh * 64);
+}
+
 // the left-context rows of every activation buffer, zeroed by ONE launch (was 11 hipMemsetAsync per stateless decode)
 struct ZeroRegions { float* p[3 + 2 * MIMI_MAX_STAGES]; int n[3 + 2 * MIMI_MAX_STAGES]; int count; };
 __global__ void k_zero_regions(const ZeroRegions z) {
@@ -565,6 +638,8 @@ struct MimiDecoder {
     hipStream_t cap_stream = nullptr;   // graph capture of decode_middle
     hipGraphExec_t mid_exec[65] = {};   // by T (stateless decodes of up to MIMI_GRAPH_MAX_T frames)
     int mid_uses[65] = {};
+    EncClipTab* enc_clips = nullptr;    // device table of a ragged encode: [MIMI_ENCODE_MAX_CLIPS] clips, then frame -> clip [max_frames]
+    int* enc_frame_clip = nullptr;      // (inside the enc_clips allocation)
     std::string err;
 };
 
@@ -683,6 +758,13 @@ extern "C" int mimi_create(const MimiConfig* cfg, const MimiWeights* w, int max_
     // (ffn is also the encoder's RVQ score buffer)
     const int rc = ladder_alloc(m, m->b, *cfg, 1, max_frames, m->cap_tokens, cfg->tr_ffn > cfg->codebook_size ? cfg->tr_ffn : cfg->codebook_size);
     if (rc) { g_mimi_err = m->err; mimi_destroy(m); return rc; }
+    if (w->has_encoder) {
+        const size_t clips_bytes = sizeof(EncClipTab) * MIMI_ENCODE_MAX_CLIPS;
+        if (hipMalloc((void**)&m->enc_clips, clips_bytes + (size_t)max_frames * 4) != hipSuccess) {
+            g_mimi_err = "mimi_create: hipMalloc of the ragged encode's table failed"; mimi_destroy(m); return -2;
+        }
+        m->enc_frame_clip = reinterpret_cast<int*>(reinterpret_cast<char*>(m->enc_clips) + clips_bytes);
+    }
     *out = m;
     return 0;
 }
@@ -690,6 +772,7 @@ extern "C" int mimi_create(const MimiConfig* cfg, const MimiWeights* w, int max_
 extern "C" void mimi_destroy(mimi_handle m) {
     if (!m) return;
     ladder_free(m->b);
+    (void)hipFree(m->enc_clips);
     for (hipGraphExec_t g : m->mid_exec) if (g) (void)hipGraphExecDestroy(g);
     if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
     delete m;
@@ -728,6 +811,7 @@ struct Product {
     RopeOut ro = {};                                // ro.q != nullptr: the q|k|v projection
     const KSplitWs* ksw = nullptr;
     SegArgs sg = {};                                // sg.tab != nullptr: the SEG instantiation
+    RagArgs rg = {};                                // rg.clips != nullptr: the RAG instantiation (a ragged encode)
     Product& taps_at(int s0, int ds) { shift0 = s0; dshift = taps > 1 ? ds : 0; return *this; }
     Product& elu() { elu_in = true; return *this; }
     Product& gelu() { gelu_out = true; return *this; }
@@ -736,6 +820,11 @@ struct Product {
     Product& rope(const RopeOut& r) { ro = r; return *this; }
     Product& ksplit(const KSplitWs& k) { ksw = &k; return *this; }
     Product& seg(const SegArgs& s) { if (s.tab) sg = s; return *this; }        // (no table: a handle's one stream, the plain instantiation)
+    // a product of a ragged encode from level lvl_in to lvl_out (enc_segs.h); no table: one clip, the plain instantiation
+    Product& rag(const RagArgs* r, int lvl_in, int lvl_out, const MimiConfig& c) {
+        if (r) { rg = *r; rg.lvl_in = lvl_in; rg.lvl_out = lvl_out; rg.rate_in = (int)enc_level_rate(c.ratios, c.n_stages, lvl_in); rg.rate_out = (int)enc_level_rate(c.ratios, c.n_stages, lvl_out); }
+        return *this;
+    }
     Product& stride(int s) { in_stride = s; return *this; }                       // a down-sampling conv
     Product& zero_padded(long lo, long hi) { edge = 1; row_lo = (int)lo; row_hi = (int)hi; return *this; }       // input rows outside [lo, hi) read as zero
     Product& replicate_padded(long lo, long hi) { edge = 2; row_lo = (int)lo; row_hi = (int)hi; return *this; }  // ... are clamped into [lo, hi)
@@ -777,6 +866,12 @@ static hipError_t gemm(hipStream_t st, const Product& g) {
         else hipLaunchKernelGGL((k_gemm32<false, true>), grid, dim3(64 * G32_NW), 0, st, a);
         return hipGetLastError();
     }
+    if (g.rg.clips != nullptr) {
+        a.rag = g.rg;
+        if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        else hipLaunchKernelGGL((k_gemm32<false, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        return hipGetLastError();
+    }
     if (g.elu_in) hipLaunchKernelGGL(k_gemm32<true>, grid, dim3(64 * G32_NW), 0, st, a);
     else hipLaunchKernelGGL(k_gemm32<false>, grid, dim3(64 * G32_NW), 0, st, a);
     return hipGetLastError();
@@ -791,6 +886,7 @@ struct TrPass {
     bool lin2_ksplit = true;        // false for the encoder alone: unsplit, its lin2 sums in another order, and the encode goldens were recorded so
     const int* tab = nullptr;       // pool only: the call's table (position and K/V ring row per stream come from it), rows per stream, ring
     int T2 = 0, ring = 0;
+    const RagArgs* rag = nullptr;   // ragged encode only: the clips' table (RoPE position and attention window inside the token's clip)
 };
 
 // layernorm, q|k|v + RoPE, attention, out-proj + LayerScale + residual, layernorm, lin1 + GELU, lin2 + LayerScale + residual: tok -> a0
@@ -803,8 +899,9 @@ static int transformer(H* h, const MimiConfig& c, const MimiWeights& w, Ladder& 
         float *kc = b.kc + l * b.kv_layer, *vc = b.vc + l * b.kv_layer;
         hipLaunchKernelGGL(k_layernorm, dim3((unsigned)p.rows), dim3(64), 0, st, b.tok, d, L.ln1_w, L.ln1_b, c.norm_eps, b.ln);
         MCHK(h, gemm(st, linear(b.ln, d, p.rows, L.in_proj, d, 3 * d, nullptr, 0).rope({b.q, kc, vc, w.rope_freqs, p.offset, d})
-                             .seg({p.T2, p.T2, p.T2, p.T2, 0, p.ring, p.tab})));
-        if (p.tab) hipLaunchKernelGGL(k_pool_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.T2, p.ring, c.tr_context, p.tab, b.att);
+                             .seg({p.T2, p.T2, p.T2, p.T2, 0, p.ring, p.tab}).rag(p.rag, c.n_stages, c.n_stages, c)));
+        if (p.rag) hipLaunchKernelGGL(k_enc_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, c.tr_context, p.rag->clips, p.rag->frame_clip, b.att);
+        else if (p.tab) hipLaunchKernelGGL(k_pool_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.T2, p.ring, c.tr_context, p.tab, b.att);
         else hipLaunchKernelGGL(k_mimi_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.offset, c.tr_context, b.att);
         MCHK(h, gemm(st, linear(b.att, d, p.rows, L.out_proj, d, d, b.tok, d).scale_residual(L.ls1, b.tok, d)));
         hipLaunchKernelGGL(k_layernorm, dim3((unsigned)p.rows), dim3(64), 0, st, b.tok, d, L.ln2_w, L.ln2_b, c.norm_eps, b.ln);
@@ -922,41 +1019,48 @@ static int slide_all(MimiDecoder* m, int T, hipStream_t st) {
 
 static long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
-static int encode_one(MimiDecoder* m, const float* wav, long n, int32_t* codes, long T, hipStream_t st) {
+// One clip of n samples (T frames), or -- rag: the table of a ragged encode -- the clips of the table in their frame-aligned slots: T = the
+// call's frames in all, every level runs over all of its rate * T rows, and the products that reach beyond their own row take the edge
+// bounds of the row's clip from the table (the RAG instantiation) in place of [0, L).
+static int encode_one(MimiDecoder* m, const float* wav, long n, int32_t* codes, long T, hipStream_t st, const RagArgs* rag = nullptr) {
     const MimiConfig& c = m->cfg;
     const MimiWeights& w = m->w;
     Ladder& b = m->b;
     const int d = c.hidden, S = c.n_stages;
     // SEANet encoder; stage j lives in the decoder's stage buffers of index S-1-j (same time scale and width).  There is no left context
     // here: the products read their input zero-padded over [0, L)
-    long L = n;
+    const long hop = enc_level_rate(c.ratios, S, 0);
+    long L = rag ? hop * T : n;
     int C = c.n_filters;
     {
         const long tot = L * C;
-        hipLaunchKernelGGL(k_enc_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, L, c.kernel, C,
+        if (rag) hipLaunchKernelGGL(k_enc_conv_in_many, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, L, (int)hop, c.kernel, C,
+                                    w.enc_conv_in_w, w.enc_conv_in_b, rag->clips, rag->frame_clip, b.u(S - 1).row0());
+        else hipLaunchKernelGGL(k_enc_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, L, c.kernel, C,
                            w.enc_conv_in_w, w.enc_conv_in_b, b.u(S - 1).row0());
     }
     for (int j = 0; j < S; ++j) {
         const int bi = S - 1 - j;
         const MimiConv &r1 = w.enc_res1[j], &r2 = w.enc_res2[j], &dn = w.enc_down[j];
         float* x = b.u(bi).row0();
-        MCHK(m, gemm(st, conv(x, C, L, r1, b.r1[bi], r1.c_out).elu().zero_padded(0, L)));
+        MCHK(m, gemm(st, conv(x, C, L, r1, b.r1[bi], r1.c_out).elu().zero_padded(0, L).rag(rag, j, j, c)));
         MCHK(m, gemm(st, conv(b.r1[bi], r1.c_out, L, r2, b.xj(bi).row0(), C).elu().residual(x, C).zero_padded(0, L)));
         // ELU -> strided conv k = 2r: out[t] = sum_k W_k x[t*r + k - r]; zero padding on both sides
         const int r = dn.taps / 2;
-        const long Lo = ceil_div(L, r);
+        const long Lo = rag ? L / r : ceil_div(L, r);
         float* out = (j + 1 < S) ? b.u(bi - 1).row0() : b.s0.row0();
-        MCHK(m, gemm(st, conv(b.xj(bi).row0(), C, Lo, dn, out, dn.c_out).taps_at(-r, 1).stride(r).elu().zero_padded(0, L)));
+        MCHK(m, gemm(st, conv(b.xj(bi).row0(), C, Lo, dn, out, dn.c_out).taps_at(-r, 1).stride(r).elu().zero_padded(0, L).rag(rag, j, j + 1, c)));
         L = Lo; C = dn.c_out;
     }
-    MCHK(m, gemm(st, conv(b.s0.row0(), C, L, w.enc_conv_out, b.tok, d).elu().zero_padded(0, L)));
+    MCHK(m, gemm(st, conv(b.s0.row0(), C, L, w.enc_conv_out, b.tok, d).elu().zero_padded(0, L).rag(rag, S, S, c)));
     // encoder transformer (stateless) -> a0
     TrPass tp{w.enc_tr, L};
     tp.lin2_ksplit = false;
+    tp.rag = rag;
     if (transformer(m, c, w, b, tp, st)) return -2;
     // stride-2 downsample, taps at rows 2t - 2 .. 2t + 1, replicate padding, no bias -> rvq buffer [T][d]
     const MimiConv down = {w.downsample, nullptr, d, d, 4, 1};
-    MCHK(m, gemm(st, conv(b.a0.row0(), d, T, down, b.rvq.row0(), d).taps_at(-2, 1).stride(2).replicate_padded(0, L)));
+    MCHK(m, gemm(st, conv(b.a0.row0(), d, T, down, b.rvq.row0(), d).taps_at(-2, 1).stride(2).replicate_padded(0, L).rag(rag, S, S + 1, c)));
     // split RVQ: semantic level on in_proj_first(z), acoustic levels on in_proj_rest(z)
     const int cd = c.codebook_dim;
     float* res_first = b.ln;                    // [T][cd]
@@ -991,6 +1095,22 @@ extern "C" int mimi_encode(mimi_handle m, const float* wav, long n_samples, long
         if (rc) return rc;
     }
     return mimi_reset_stream(m, stream);      // the work buffers were reused: start any later stream from scratch
+}
+
+extern "C" int mimi_encode_many(mimi_handle m, const float* wav, const long* wav_off, const long* n_samples, int n, int32_t* codes, void* stream) {
+    if (!m) return fail(m, "mimi_encode_many: null handle");
+    EncHeader hdr;
+    EncSegs sg;
+    if (const char* bad = enc_segs_build(wav, wav_off, n_samples, n, codes, m->w.has_encoder, m->cfg.ratios, m->cfg.n_stages, m->max_frames, &hdr, &sg)) {
+        m->err = std::string("mimi_encode_many: ") + bad;
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_enc_plan, dim3(1), dim3(256), 0, st, hdr, m->enc_clips, m->enc_frame_clip);
+    MCHK(m, hipGetLastError());
+    const RagArgs rag = {m->enc_clips, m->enc_frame_clip, 0, 0, 0, 0};
+    if (int rc = encode_one(m, wav, 0, codes, sg.F, st, &rag)) return rc;
+    return mimi_reset_stream(m, stream);      // as mimi_encode
 }
 
 extern "C" int mimi_decode_strided(mimi_handle m, const int32_t* codes, int B, int T, long stride_b, long stride_k, long stride_t,

@@ -119,6 +119,7 @@ MIMI_SIGNATURES = {
     "mimi_decode_strided": (_i, [_vp, _vp, _i, _i, _l, _l, _l, _vp, _i, _vp]),
     "mimi_reset_stream": (_i, [_vp, _vp]),
     "mimi_encode": (_i, [_vp, _vp, _l, _l, _i, _vp, _vp]),
+    "mimi_encode_many": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _i, _vp, _vp]),
     "mimi_pool_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
     "mimi_pool_destroy": (None, [_vp]),
     "mimi_pool_last_error": (C.c_char_p, [_vp]),

@@ -29,6 +29,11 @@ def _frames_for(max_audio_length_ms):
     return int(max_audio_length_ms / FRAME_MS) if isinstance(max_audio_length_ms, (int, float)) else [int(x / FRAME_MS) for x in max_audio_length_ms]
 
 
+# Distinct unencoded context clips from which prompt building uses the ragged encode (MimiCodec.encode_many) instead of one ``encode``
+# per clip: the measured break-even (docs/experiments/encode_many.md).
+ENCODE_MANY_MIN_CLIPS = 2
+
+
 @dataclass
 class Segment:
     """reference: sesameai/generator.py:16-21.  ``audio`` is (num_samples,) @ 24 kHz.
@@ -152,15 +157,44 @@ class Generator:
         mask[:, :-1] = True
         return frame, mask
 
-    def _tokenize_segment(self, segment: Segment) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _tokenize_segment(self, segment: Segment, encoded: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         t, tm = self._tokenize_text_segment(segment.text, segment.speaker)
-        a, am = self._tokenize_audio(segment.audio, segment.audio_codes)
+        codes = segment.audio_codes
+        if codes is None and encoded:
+            codes = encoded.get(id(segment.audio))          # (the Segment itself is left as it came)
+        a, am = self._tokenize_audio(segment.audio, codes)
         return torch.cat([t, a], dim=0), torch.cat([tm, am], dim=0)
 
-    def _build_prompt(self, text, speaker: int, context: List[Segment]):
+    def _encode_contexts(self, contexts: Sequence[List[Segment]]) -> dict:
+        """{id(audio tensor): codes (32, T)} of every context Segment that has ``audio`` and no ``audio_codes``, from ragged encode
+        calls (``MimiCodec.encode_many``: all clips, whatever their lengths, in one launch chain; the codes are bit for bit those of
+        the per-segment ``encode``).  A tensor that several segments or requests share (the same object) is encoded once.  Empty --
+        the segments then go through today's per-segment ``encode`` calls -- for a codec without ``encode_many`` and for fewer than
+        ENCODE_MANY_MIN_CLIPS distinct clips."""
+        tok = self._audio_tokenizer
+        if tok is None or not hasattr(tok, "encode_many"):
+            return {}
+        clips: dict = {}
+        for ctx in contexts:
+            for seg in ctx:
+                if seg.audio is not None and seg.audio_codes is None and id(seg.audio) not in clips:
+                    assert seg.audio.ndim == 1, "Audio must be single channel"
+                    clips[id(seg.audio)] = seg.audio
+        if len(clips) < max(2, ENCODE_MANY_MIN_CLIPS):
+            return {}
+        return dict(zip(clips.keys(), tok.encode_many(list(clips.values()))))
+
+    def _build_prompts(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]]):
+        """The prompts of several requests; their unencoded context audio goes through the Mimi encoder together (_encode_contexts)."""
+        encoded = self._encode_contexts(contexts)
+        return [self._build_prompt(t, sp, ctx, encoded) for t, sp, ctx in zip(texts, speakers, contexts)]
+
+    def _build_prompt(self, text, speaker: int, context: List[Segment], encoded: Optional[dict] = None):
+        if encoded is None:
+            encoded = self._encode_contexts([context])
         toks, masks = [], []
         for seg in context:
-            t, m = self._tokenize_segment(seg)
+            t, m = self._tokenize_segment(seg, encoded)
             toks.append(t); masks.append(m)
         t, m = self._tokenize_text_segment(text, speaker)
         toks.append(t); masks.append(m)
@@ -341,7 +375,7 @@ class Generator:
         """``generate`` for a list of requests through the continuously refilled batch: one audio tensor per request
         (``max_audio_length_ms``, ``temperature``, ``topk``: one value, or one per request; ``seed``: one optional int per request)."""
         max_generation_len = _frames_for(max_audio_length_ms)
-        prompts = [self._build_prompt(t, sp, ctx) for t, sp, ctx in zip(texts, speakers, contexts)]
+        prompts = self._build_prompts(texts, speakers, contexts)
         out: List[torch.Tensor] = [torch.tensor([]) for _ in prompts]
         for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group):
             if frames.shape[0]:                                       # decoded as each utterance finishes, not at the end
@@ -368,7 +402,7 @@ class Generator:
             raise RuntimeError("generate_many_stream needs a Mimi codec with stream pools (MimiCodec.open_streams)")
         max_generation_len = _frames_for(max_audio_length_ms)
         with torch.inference_mode():
-            prompts = [self._build_prompt(t, sp, ctx) for t, sp, ctx in zip(texts, speakers, contexts)]
+            prompts = self._build_prompts(texts, speakers, contexts)
         if not prompts:
             return
         size = self._stream_buffer_size

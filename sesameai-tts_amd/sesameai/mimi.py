@@ -20,6 +20,7 @@ from . import _abi
 from ._abi import check, lib
 
 MAX_TR, MAX_ST = 16, 8
+MAX_ENCODE_CLIPS = 64           # MIMI_ENCODE_MAX_CLIPS: clips one mimi_encode_many call takes
 
 
 class _MimiConfig(C.Structure):
@@ -367,6 +368,41 @@ class MimiCodec:
         codes = torch.empty(B, self.args.num_codebooks, T, dtype=torch.int32, device=self.device)
         check(lib.mimi_encode(self._h, x.data_ptr(), n, x.stride(0), B, codes.data_ptr(), _stream()), self._h, mimi=True)
         return codes.long()
+
+    @torch.inference_mode()
+    def encode_many(self, wavs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """Clips of different lengths, each (n_i,) fp32 @ 24 kHz -> their codes, each (32, ceil(n_i/1920)) int64: bit for bit what
+        ``encode`` gives for the clip alone, from ONE launch chain per call of ``mimi_encode_many`` (include/mimi_hip.h).  The list is
+        split greedily, in input order, into calls of at most ``max_frames`` frames and MAX_ENCODE_CLIPS clips."""
+        if not self.has_encoder:
+            raise RuntimeError("this MimiCodec was built without encoder weights; pass Segment.audio_codes instead")
+        hop = self.args.hop
+        frames = []
+        for w in wavs:
+            assert w.dim() == 1 and w.shape[0] >= 1, "every clip must be (n,) with n >= 1"
+            frames.append(-(-w.shape[0] // hop))
+            if frames[-1] > self.max_frames:
+                raise ValueError(f"a clip of {frames[-1]} frames is longer than max_frames = {self.max_frames}")
+        out: List[torch.Tensor] = []
+        i = 0
+        while i < len(wavs):
+            j, F = i, 0
+            while j < len(wavs) and j - i < MAX_ENCODE_CLIPS and F + frames[j] <= self.max_frames:
+                F += frames[j]; j += 1
+            out += self._encode_call(wavs[i:j], frames[i:j], F)
+            i = j
+        return out
+
+    def _encode_call(self, wavs: Sequence[torch.Tensor], frames: List[int], F: int) -> List[torch.Tensor]:
+        n = len(wavs)
+        packed = torch.cat([w.to(device=self.device, dtype=torch.float32) for w in wavs])       # one device buffer, clip after clip
+        lens = [int(w.shape[0]) for w in wavs]
+        offs = [sum(lens[:k]) for k in range(n)]
+        codes = torch.empty(self.args.num_codebooks, F, dtype=torch.int32, device=self.device)
+        check(lib.mimi_encode_many(self._h, packed.data_ptr(), (C.c_long * n)(*offs), (C.c_long * n)(*lens), n, codes.data_ptr(), _stream()),
+              self._h, mimi=True)
+        codes = codes.long()
+        return list(codes.split(frames, dim=1))
 
     def _run(self, codes: torch.Tensor, stateful: bool) -> torch.Tensor:
         assert codes.dim() == 3 and codes.shape[1] == self.args.num_codebooks, "codes must be (B, 32, T)"
