@@ -144,6 +144,27 @@ int  mimi_pool_reset(mimi_pool p, const int32_t* streams, int n, void* stream);
 int  mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, const int32_t* codes, int T,
                       long stride_s, long stride_k, long stride_t, void* pcm, void* stream);
 
+/* The same for streams with DIFFERENT numbers of new frames: stream streams[i] gets T_i = frames[i] frames (streams, frames: host arrays,
+ * read before the call returns; 1 <= T_i <= max_chunk_frames), element (i,k,t) of codes at codes[i*stride_s + k*stride_k + t*stride_t] for
+ * t < T_i.  With F_i = T_0 + .. + T_(i-1) and F = sum T_i the output is pcm[hop * F] fp32 (device): stream i owns samples
+ * [hop * F_i, hop * (F_i + T_i)).  ONE launch chain of the length of mimi_pool_decode's, whatever the T_i are: the streams' rows are stacked
+ * frame-aligned, as in mimi_encode_many -- at a level with R rows per frame (1 at the frames, 2 at the transformer's tokens, each SEANet
+ * stage's rate above that) segment i owns dense rows [R * F_i, R * (F_i + T_i)); decode only up-samples, so there are no tails -- while the
+ * buffers with history keep every stream in place, as for the uniform call.  The chain's first kernel expands a header of at most
+ * MIMI_POOL_MAX_STREAMS entries {id, token offset, T_i} from the kernel arguments into the pool's device table ({id, offset, F_i, T_i} per
+ * segment and the segment of every frame): no host-to-device copy, no synchronisation.  Each stream's history slides by ITS chunk and its
+ * token offset advances by its own 2 * T_i.
+ * NUMERICAL RULE: a stream's PCM from a ragged call is, bit for bit, what mimi_pool_decode gives that stream for the same chunk schedule --
+ * and so, by the rule above, what a single handle's stateful mimi_decode and the whole-clip decode's stream give -- whatever shares the
+ * call, whatever the others' T_j are and wherever the stream sits in the list: an MFMA output element depends on its own A rows, the wave
+ * split and the K split depend on the product's shape (taps, C_in) alone, and everything else is per row or per sample.  (F <= n_streams *
+ * max_chunk_frames, so every split product fits the workspace of the uniform call at T = max_chunk_frames.)
+ * Returns -1 with a message in mimi_pool_last_error, nothing enqueued, no offset advanced and the pool still usable, for: n outside
+ * [1, n_streams], a duplicate or out-of-range id, a frames[i] outside [1, max_chunk_frames], a null pointer, a stream that would pass
+ * 2^31 tokens.                                                                                                                         */
+int  mimi_pool_decode_ragged(mimi_pool p, const int32_t* streams, const int32_t* frames, int n, const int32_t* codes,
+                             long stride_s, long stride_k, long stride_t, void* pcm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,9 @@
 #define ENC_SEGS_FN __host__ __device__ static inline
 #include "enc_segs.h"
 static_assert(ENC_MAX_CLIPS == MIMI_ENCODE_MAX_CLIPS && ENC_MAX_STAGES == MIMI_MAX_STAGES, "enc_segs.h and mimi_hip.h disagree");
+#define POOL_SEGS_FN __host__ __device__ static inline
+#include "pool_segs.h"
+static_assert(POOL_SEG_MAX_STREAMS == MIMI_POOL_MAX_STREAMS, "pool_segs.h and mimi_hip.h disagree");
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 static thread_local std::string g_mimi_err;
@@ -72,6 +75,9 @@ struct GemmArgs {
     // keeps every stream's history in place (bit 0 / 1 / 2 of seg_by_id: x / out / resid) and si for a dense work buffer.  A tap therefore
     // reaches back into its OWN stream's history rows, never into its neighbour's.  RoPE position and K/V ring slot come from the stream's
     // token offset seg_tab[MIMI_POOL_MAX_STREAMS + si].
+    // Ragged pool call (the PRG instantiation, with SEG; mimi_pool_decode_ragged): the streams' rows are stacked frame-aligned and seg_T is the
+    // launch's rows per FRAME, R.  Global row g belongs to segment si = frame_seg[g / R] (seg_tab + POOL_TAB_FRAME) at tl = g - R * F0_si; a dense
+    // buffer's segment starts at row R * F0_si (times `phases` on the output side) where the uniform call has si * seg_x.  Everything else is SEG.
     int seg_T, seg_x, seg_o, seg_r, seg_by_id, rope_ring;
     const int* seg_tab;
     // Ragged encode (the RAG instantiation only; mimi_encode_many below): the rows of the launch are those of several clips, frame-aligned:
@@ -102,7 +108,7 @@ __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expf(v) - 
 // the weights re-tiled into MFMA operand order so that every wave load is one contiguous 1 KB (the K = 2048 linear 24 us against
 // 19.5 row-major: with one 32-row tile these launches sit on 16..64 CUs and are bound by the fp32 matrix pipe -- 128 dependent
 // 64-cycle v_mfma_f32_32x32x2_f32 per wave, two waves per SIMD = 6.8 us -- plus the ~4.7 us of a dependent launch, not by loads).
-template <bool ELU, bool SEG = false, bool RAG = false>
+template <bool ELU, bool SEG = false, bool RAG = false, bool PRG = false>
 __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
     __shared__ float red[G32_NW][16][64];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -118,8 +124,13 @@ __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
     const int kchunks = a.C_in / 32, iters = a.taps * kchunks;
     int arow0 = trow * a.in_stride + a.shift0;
     if (SEG) {
-        const int si = trow / a.seg_T, tl = trow - si * a.seg_T;
-        arow0 = ((a.seg_by_id & 1) ? a.seg_tab[si] : si) * a.seg_x + tl * a.in_stride + a.shift0;
+        if (PRG) {
+            const int si = a.seg_tab[POOL_TAB_FRAME + trow / a.seg_T], r0 = a.seg_T * a.seg_tab[POOL_TAB_F0 + si];
+            arow0 = ((a.seg_by_id & 1) ? a.seg_tab[si] * a.seg_x : r0) + (trow - r0) * a.in_stride + a.shift0;
+        } else {
+            const int si = trow / a.seg_T, tl = trow - si * a.seg_T;
+            arow0 = ((a.seg_by_id & 1) ? a.seg_tab[si] : si) * a.seg_x + tl * a.in_stride + a.shift0;
+        }
     }
     int row_lo = a.row_lo, row_hi = a.row_hi;
     if (RAG && a.edge != 0) {
@@ -235,11 +246,18 @@ __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
         long orow = (long)t * a.phases + p, rrow = orow;
         int pos = a.rope_offset + t;                                    // token position (RoPE angle)
         long kvrow = pos;                                               // its row in the K / V cache
-        if (SEG) {
+        if (SEG && !PRG) {
             const int si = t / a.seg_T, tl = t - si * a.seg_T, sid = a.seg_tab[si];
             orow = (long)((a.seg_by_id & 2) ? sid : si) * a.seg_o + (long)tl * a.phases + p;
             rrow = (long)((a.seg_by_id & 4) ? sid : si) * a.seg_r + (long)tl * a.phases + p;
             if (a.rope_q) { pos = a.seg_tab[MIMI_POOL_MAX_STREAMS + si] + tl; kvrow = (long)sid * a.rope_ring + pos % a.rope_ring; }
+        }
+        if (SEG && PRG) {
+            const int si = a.seg_tab[POOL_TAB_FRAME + t / a.seg_T], r0 = a.seg_T * a.seg_tab[POOL_TAB_F0 + si], tl = t - r0, sid = a.seg_tab[si];
+            const long dense0 = (long)r0 * a.phases;                    // the segment's first row of a dense output at this launch's rate
+            orow = ((a.seg_by_id & 2) ? (long)sid * a.seg_o : dense0) + (long)tl * a.phases + p;
+            rrow = ((a.seg_by_id & 4) ? (long)sid * a.seg_r : dense0) + (long)tl * a.phases + p;
+            if (a.rope_q) { pos = a.seg_tab[POOL_TAB_OFF + si] + tl; kvrow = (long)sid * a.rope_ring + pos % a.rope_ring; }
         }
         if (RAG && a.rope_q) pos = t - a.rag.rate_out * a.rag.clips[a.rag.frame_clip[t / a.rag.rate_out]].F0;       // (kvrow stays t)
         float v = sum + bias;
@@ -549,49 +567,81 @@ __global__ void k_pool_begin(const PoolIds ids, int* tab, int* tickets, int n_ti
     for (int j = threadIdx.x; j < n_tickets; j += blockDim.x) tickets[j] = 0;
 }
 
+// its ragged twin (mimi_pool_decode_ragged; layout: pool_segs.h): per segment {stream id, token offset, first frame, frames}, then frame ->
+// segment for the call's F frames.  One block.
+__global__ __launch_bounds__(256) void k_pool_begin_ragged(const PoolSegHeader hdr, int* tab, int* tickets, int n_tickets) {
+    __shared__ int f0[POOL_SEG_MAX_STREAMS + 1];
+    if (threadIdx.x == 0) pool_segs_prefix(&hdr, f0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < hdr.n; i += blockDim.x) {
+        tab[POOL_TAB_SID + i] = hdr.sid[i]; tab[POOL_TAB_OFF + i] = hdr.off[i]; tab[POOL_TAB_F0 + i] = f0[i]; tab[POOL_TAB_T + i] = hdr.T[i];
+    }
+    for (int f = threadIdx.x; f < f0[hdr.n]; f += blockDim.x) tab[POOL_TAB_FRAME + f] = pool_seg_of_frame(f0, f);
+    for (int j = threadIdx.x; j < n_tickets; j += blockDim.x) tickets[j] = 0;
+}
+
+// The kernels below map a dense row g to (si, tl): the si-th listed stream and the row inside its chunk.  Uniform call: `rows` rows per
+// stream, si = g / rows.  PRG (a ragged call): `rows` is the level's rows per FRAME and si = frame_seg[g / rows], tl = g - rows * F0_si.
+// (I: int or long, the index type the uniform kernel has always divided in)
+template <bool PRG, class I>
+__device__ __forceinline__ void pool_row(const int* tab, I g, I rows, int& si, I& tl) {
+    if (PRG) { si = tab[POOL_TAB_FRAME + g / rows]; tl = g - rows * tab[POOL_TAB_F0 + si]; }
+    else { si = (int)(g / rows); tl = g - si * rows; }
+}
+
+template <bool PRG = false>
 __global__ __launch_bounds__(256) void k_pool_rvq(const int* codes, long stride_s, long stride_k, long stride_t, int T, int ncb, int nsem,
                                                   int cbsize, int cbdim, int hidden, const float* books, const float* pf, const float* pr,
                                                   float* out /*row 0 of stream 0*/, int seg, const int* tab) {
     extern __shared__ float q[];
-    const int si = blockIdx.x / T, t = blockIdx.x - si * T;
+    int si, t;
+    pool_row<PRG, int>(tab, blockIdx.x, T, si, t);
     rvq_frame(q, codes + si * stride_s + t * stride_t, stride_k, ncb, nsem, cbsize, cbdim, hidden, books, pf, pr,
               out + ((long)tab[si] * seg + t) * hidden);
 }
 
+template <bool PRG = false>
 __global__ void k_pool_upsample(const float* x /*row 0 of stream 0*/, int seg, const int* tab, int T, int n, int C, const float* w, float* out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)n * T * 2 * C) return;
     const int c = (int)(i % C);
     const long g = i / C;                           // dense output row
-    const int si = (int)(g / (2 * T)), nl = (int)(g - (long)si * 2 * T);
+    int si; long nl;
+    pool_row<PRG, long>(tab, g, 2 * T, si, nl);
     out[g * C + c] = upsample_tap2(x + ((long)tab[si] * seg + (nl >> 1)) * C, (long)C, w, nl & 1, C, c);
 }
 
+template <bool PRG = false>
 __global__ __launch_bounds__(64) void k_pool_attn(const float* q, const float* kc, const float* vc, int d, int T2, int ring, int context,
                                                   const int* tab, float* out) {
     __shared__ float pbuf[1024];
     const int g = blockIdx.x, hh = blockIdx.y;
-    const int si = g / T2, tl = g - si * T2;
+    int si, tl;
+    pool_row<PRG, int>(tab, g, T2, si, tl);
     const long cache = (long)tab[si] * ring * d + hh * 64;
     attn_row<true>(pbuf, q + (long)g * d + hh * 64, kc + cache, vc + cache, d, tab[MIMI_POOL_MAX_STREAMS + si] + tl, context, ring,
                    out + (long)g * d + hh * 64);
 }
 
+template <bool PRG = false>
 __global__ void k_pool_conv_out(const float* x /*row 0 of stream 0*/, int seg, const int* tab, long Tj, int n, int C_in, int taps, const float* w,
                                 const float* bias, float* pcm) {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= Tj * n) return;
-    const int si = (int)(g / Tj);
-    const long tl = g - si * Tj;
+    int si; long tl;
+    pool_row<PRG, long>(tab, g, Tj, si, tl);
     pcm[g] = conv_out_sample(x + ((long)tab[si] * seg + tl) * C_in, (long)C_in, C_in, taps, w, bias);
 }
 
-// k_slide_hist for every segmented buffer (blockIdx.z) of every listed stream (blockIdx.y) in one launch
+// k_slide_hist for every segmented buffer (blockIdx.z) of every listed stream (blockIdx.y) in one launch.  PRG: z.T is the buffer's rows per
+// FRAME and each stream's history moves by ITS chunk, z.T * T_si rows.
+template <bool PRG = false>
 __global__ void k_pool_slide(const PoolRegions z, const int* tab) {
     const int reg = blockIdx.z, c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= z.C[reg]) return;
     float* base = z.base[reg] + (long)tab[blockIdx.y] * z.seg[reg] * z.C[reg];
-    for (int r = 0; r < z.hist[reg]; ++r) base[(long)r * z.C[reg] + c] = base[((long)r + z.T[reg]) * z.C[reg] + c];    // ascending r: source is always ahead
+    const long T = PRG ? z.T[reg] * tab[POOL_TAB_T + blockIdx.y] : z.T[reg];
+    for (int r = 0; r < z.hist[reg]; ++r) base[(long)r * z.C[reg] + c] = base[((long)r + T) * z.C[reg] + c];    // ascending r: source is always ahead
 }
 
 __global__ void k_pool_zero_hist(const PoolRegions z, const PoolIds ids) {
@@ -649,7 +699,8 @@ struct MimiStreamPool {
     int n_streams = 0, max_chunk = 0, ring = 0;
     std::vector<long> offset;                       // tokens each stream has decoded so far
     Ladder b;
-    int* tab = nullptr;                             // device table of the running call: [i] stream id, [MIMI_POOL_MAX_STREAMS + i] token offset
+    int* tab = nullptr;                             // device table of the running call: [i] stream id, [MIMI_POOL_MAX_STREAMS + i] token offset;
+                                                    // a ragged call also fills the rest: per segment F0 and T, then frame -> segment (pool_segs.h)
     std::string err;
 };
 
@@ -796,7 +847,8 @@ extern "C" int mimi_reset_stream(mimi_handle m, void* stream) {
 
 // ---- one product ---------------------------------------------------------------------------------------------------------------------
 struct RopeOut { float *q, *k, *v; const float* freqs; int offset, d; };
-struct SegArgs { int T, x, o, r, by_id, ring; const int* tab; };       // GemmArgs.seg_*: a product over the stacked rows of a stream pool
+// GemmArgs.seg_*: a product over the stacked rows of a stream pool; ragged: T = the launch's rows per frame (the PRG instantiation)
+struct SegArgs { int T, x, o, r, by_id, ring; const int* tab; bool ragged; };
 
 // One k_gemm32 launch as its call site states it.  The operands every product has come first (linear() / conv() below fill them); everything
 // else is named by a setter and otherwise keeps the default written here.
@@ -853,7 +905,10 @@ static hipError_t gemm(hipStream_t st, const Product& g) {
     const KSplitWs* ksw = g.ksw;
     if (ksw != nullptr && ksw->part != nullptr && g.phases == 1 && !rope && iters >= MIMI_KSPLIT_MIN_ITERS && iters % ksw->ksplit == 0) {
         // (the workspace is sized for the handle's max_frames at mimi_create, so a product the decoder accepts always fits; if one ever
-        //  does not, it runs unsplit -- same value to fp32 rounding -- instead of failing the decode: ADVICE r5)
+        //  does not, it runs unsplit -- same value to fp32 rounding -- instead of failing the decode: ADVICE r5.  A ragged pool call has
+        //  F <= n_streams * max_chunk_frames frames, so its split products -- lin2 and conv_in, 2 F token rows -- fit the workspace of the
+        //  uniform call at T = max_chunk_frames that mimi_pool_create sized it for: the unsplit branch stays unreachable, and a stream's
+        //  sums stay those of the uniform call.)
         if (g.rows <= ksw->cap_rows && g.c_out <= ksw->cap_cols && (long)grid.x * grid.y <= ksw->n_tickets) {
             a.ksplit = ksw->ksplit; a.kpart = ksw->part; a.kticket = ksw->ticket;
             grid.z = (unsigned)ksw->ksplit;
@@ -862,7 +917,11 @@ static hipError_t gemm(hipStream_t st, const Product& g) {
     if (seg) {
         const SegArgs& s = g.sg;
         a.seg_T = s.T; a.seg_x = s.x; a.seg_o = s.o; a.seg_r = s.r; a.seg_by_id = s.by_id; a.rope_ring = s.ring; a.seg_tab = s.tab;
-        if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        if (s.ragged) {
+            if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
+            else hipLaunchKernelGGL((k_gemm32<false, true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        }
+        else if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true>), grid, dim3(64 * G32_NW), 0, st, a);
         else hipLaunchKernelGGL((k_gemm32<false, true>), grid, dim3(64 * G32_NW), 0, st, a);
         return hipGetLastError();
     }
@@ -886,6 +945,7 @@ struct TrPass {
     bool lin2_ksplit = true;        // false for the encoder alone: unsplit, its lin2 sums in another order, and the encode goldens were recorded so
     const int* tab = nullptr;       // pool only: the call's table (position and K/V ring row per stream come from it), rows per stream, ring
     int T2 = 0, ring = 0;
+    bool ragged = false;            // pool only: a ragged call -- rows = 2 F, T2 = 2 (the tokens of one frame), the streams frame-aligned
     const RagArgs* rag = nullptr;   // ragged encode only: the clips' table (RoPE position and attention window inside the token's clip)
 };
 
@@ -899,27 +959,29 @@ static int transformer(H* h, const MimiConfig& c, const MimiWeights& w, Ladder& 
         float *kc = b.kc + l * b.kv_layer, *vc = b.vc + l * b.kv_layer;
         hipLaunchKernelGGL(k_layernorm, dim3((unsigned)p.rows), dim3(64), 0, st, b.tok, d, L.ln1_w, L.ln1_b, c.norm_eps, b.ln);
         MCHK(h, gemm(st, linear(b.ln, d, p.rows, L.in_proj, d, 3 * d, nullptr, 0).rope({b.q, kc, vc, w.rope_freqs, p.offset, d})
-                             .seg({p.T2, p.T2, p.T2, p.T2, 0, p.ring, p.tab}).rag(p.rag, c.n_stages, c.n_stages, c)));
+                             .seg({p.T2, p.T2, p.T2, p.T2, 0, p.ring, p.tab, p.ragged}).rag(p.rag, c.n_stages, c.n_stages, c)));
         if (p.rag) hipLaunchKernelGGL(k_enc_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, c.tr_context, p.rag->clips, p.rag->frame_clip, b.att);
-        else if (p.tab) hipLaunchKernelGGL(k_pool_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.T2, p.ring, c.tr_context, p.tab, b.att);
+        else if (p.tab && p.ragged) hipLaunchKernelGGL(k_pool_attn<true>, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.T2, p.ring, c.tr_context, p.tab, b.att);
+        else if (p.tab) hipLaunchKernelGGL(k_pool_attn<false>, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.T2, p.ring, c.tr_context, p.tab, b.att);
         else hipLaunchKernelGGL(k_mimi_attn, dim3((unsigned)p.rows, c.tr_heads), dim3(64), 0, st, b.q, kc, vc, d, p.offset, c.tr_context, b.att);
         MCHK(h, gemm(st, linear(b.att, d, p.rows, L.out_proj, d, d, b.tok, d).scale_residual(L.ls1, b.tok, d)));
         hipLaunchKernelGGL(k_layernorm, dim3((unsigned)p.rows), dim3(64), 0, st, b.tok, d, L.ln2_w, L.ln2_b, c.norm_eps, b.ln);
         MCHK(h, gemm(st, linear(b.ln, d, p.rows, L.lin1, d, c.tr_ffn, b.ffn, c.tr_ffn).gelu()));
         Product g = linear(b.ffn, c.tr_ffn, p.rows, L.lin2, c.tr_ffn, d, last ? b.a0.row0() : b.tok, d).scale_residual(L.ls2, b.tok, d);
         if (p.lin2_ksplit) g.ksplit(b.ksw);
-        if (last) g.seg({p.T2, p.T2, b.a0.seg(), p.T2, 2, 0, p.tab});            // the last layer writes the streams' a0 segments
+        if (last) g.seg({p.T2, p.T2, b.a0.seg(), p.T2, 2, 0, p.tab, p.ragged});            // the last layer writes the streams' a0 segments
         MCHK(h, gemm(st, g));
         MCHK(h, hipGetLastError());
     }
     return 0;
 }
 
-// SEANet decoder: a0 -> conv_in -> per stage up / res1 / res2 -> xj[last], for n streams of T2 rows each (a handle: n = 1, no table)
+// SEANet decoder: a0 -> conv_in -> per stage up / res1 / res2 -> xj[last], for n streams of T2 rows each (a handle: n = 1, no table).
+// A ragged pool call: n = the call's frames, T2 = 2 -- every level's rows per FRAME where the uniform call has rows per stream.
 template <class H>
-static int seanet_decoder(H* h, const MimiWeights& w, int n_stages, Ladder& b, int n, int T2, const int* tab, hipStream_t st) {
+static int seanet_decoder(H* h, const MimiWeights& w, int n_stages, Ladder& b, int n, int T2, const int* tab, hipStream_t st, bool rg = false) {
     MCHK(h, gemm(st, conv(b.a0.row0(), b.a0.C, (long)n * T2, w.conv_in, b.s0.row0(), w.conv_in.c_out).ksplit(b.ksw)
-                         .seg({T2, b.a0.seg(), b.s0.seg(), 0, 1 | 2, 0, tab})));
+                         .seg({T2, b.a0.seg(), b.s0.seg(), 0, 1 | 2, 0, tab, rg})));
     const SegBuf* xin = &b.s0;
     int Tj = T2;                                                        // rows per stream at the current level
     for (int j = 0; j < n_stages; ++j) {
@@ -927,12 +989,12 @@ static int seanet_decoder(H* h, const MimiWeights& w, int n_stages, Ladder& b, i
         const SegBuf &u = b.u(j), &xj = b.xj(j);
         // ELU -> ConvTranspose1d (stride phases, 2 taps each: rows t and t - 1)
         MCHK(h, gemm(st, conv(xin->row0(), xin->C, (long)n * Tj, up, u.row0(), up.c_out).taps_at(0, -1).elu()
-                             .seg({Tj, xin->seg(), u.seg(), 0, 1 | 2, 0, tab})));
+                             .seg({Tj, xin->seg(), u.seg(), 0, 1 | 2, 0, tab, rg})));
         Tj *= up.phases;
         // residual block: u + conv_k1(ELU(conv_k3(ELU(u))))
-        MCHK(h, gemm(st, conv(u.row0(), up.c_out, (long)n * Tj, r1, b.r1[j], r1.c_out).elu().seg({Tj, u.seg(), Tj, 0, 1, 0, tab})));
+        MCHK(h, gemm(st, conv(u.row0(), up.c_out, (long)n * Tj, r1, b.r1[j], r1.c_out).elu().seg({Tj, u.seg(), Tj, 0, 1, 0, tab, rg})));
         MCHK(h, gemm(st, conv(b.r1[j], r1.c_out, (long)n * Tj, r2, xj.row0(), r2.c_out).elu().residual(u.row0(), up.c_out)
-                             .seg({Tj, Tj, xj.seg(), u.seg(), 2 | 4, 0, tab})));
+                             .seg({Tj, Tj, xj.seg(), u.seg(), 2 | 4, 0, tab, rg})));
         xin = &xj;
     }
     return 0;
@@ -1147,7 +1209,7 @@ extern "C" int mimi_pool_create(const MimiConfig* cfg, const MimiWeights* w, int
     p->ring = cfg->tr_context + 2 * max_chunk_frames;        // a call's oldest key (offset - context + 1) and newest (offset + 2T - 1) never share a row
     p->offset.assign(n_streams, 0);
     auto alloc = [&]() {
-        MCHK(p, hipMalloc((void**)&p->tab, (size_t)2 * MIMI_POOL_MAX_STREAMS * 4));
+        MCHK(p, hipMalloc((void**)&p->tab, (size_t)pool_tab_words(n_streams, max_chunk_frames) * 4));
         return ladder_alloc(p, p->b, *cfg, n_streams, max_chunk_frames, p->ring, cfg->tr_ffn);
     };
     const int rc = alloc();
@@ -1191,6 +1253,45 @@ extern "C" int mimi_pool_reset(mimi_pool p, const int32_t* streams, int n, void*
     return 0;
 }
 
+// The launch chain behind the call's first kernel, for both kinds of call.  The kernels take a UNIT and rows per unit: in a uniform call
+// the unit is a listed stream (`units` = n streams of `per` = T frames each), in a ragged call (PRG) it is a FRAME of the call (`units` = F,
+// `per` = 1) and the table says whose frame it is.  `n` streams slide.  Same launches, same grids per row, in the same order.
+template <bool PRG>
+static int pool_chain(MimiStreamPool* p, const int32_t* codes, long stride_s, long stride_k, long stride_t, float* pcm, int n, int units, int per,
+                      hipStream_t st) {
+    const MimiConfig& c = p->cfg;
+    Ladder& b = p->b;
+    const int d = c.hidden;
+    const int T2 = 2 * per;
+    const long M2 = (long)units * T2;
+    const int* tab = p->tab;
+    // RVQ lookup-sum + output projections -> rvq segments
+    hipLaunchKernelGGL(k_pool_rvq<PRG>, dim3(units * per, (d + 63) / 64), dim3(256), (size_t)(2 * c.codebook_dim + c.n_codebooks) * 4, st, codes, stride_s,
+                       stride_k, stride_t, per, c.n_codebooks, c.n_semantic, c.codebook_size, c.codebook_dim, d, p->w.codebooks, p->w.proj_first,
+                       p->w.proj_rest, b.rvq.row0(), b.rvq.seg(), tab);
+    // depthwise transposed conv x2 -> tok (dense)
+    hipLaunchKernelGGL(k_pool_upsample<PRG>, dim3((unsigned)((M2 * d + 255) / 256)), dim3(256), 0, st, b.rvq.row0(), b.rvq.seg(), tab, per, units, d,
+                       p->w.upsample, b.tok);
+    MCHK(p, hipGetLastError());
+    // transformer and SEANet decoder: every product as in a handle's decode_middle, over all the call's token rows
+    TrPass tp{p->w.tr, M2};
+    tp.tab = tab; tp.T2 = T2; tp.ring = p->ring; tp.ragged = PRG;
+    if (int rc = transformer(p, c, p->w, b, tp, st)) return rc;
+    if (int rc = seanet_decoder(p, p->w, c.n_stages, b, units, T2, tab, st, PRG)) return rc;
+    // output convolution -> pcm, stream after stream, then every segmented buffer's history slides by its stream's chunk
+    const SegBuf& last = b.xj(c.n_stages - 1);
+    const long Tj = (long)per * last.rate;
+    const MimiConv& co = p->w.conv_out;
+    hipLaunchKernelGGL(k_pool_conv_out<PRG>, dim3((unsigned)((units * Tj + 255) / 256)), dim3(256), 0, st, last.row0(), last.seg(), tab, Tj, units, co.c_in,
+                       co.taps, co.w, co.bias, pcm);
+    const PoolRegions z = hist_regions(b, per);
+    int maxC = 0;
+    for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
+    hipLaunchKernelGGL(k_pool_slide<PRG>, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
+    MCHK(p, hipGetLastError());
+    return 0;
+}
+
 extern "C" int mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, const int32_t* codes, int T, long stride_s, long stride_k,
                                 long stride_t, void* pcm_out, void* stream) {
     if (!p) return fail(p, "mimi_pool_decode: null pool");
@@ -1203,37 +1304,24 @@ extern "C" int mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, cons
         ids.off[i] = (int)p->offset[ids.sid[i]];
     }
     hipStream_t st = (hipStream_t)stream;
-    const MimiConfig& c = p->cfg;
-    Ladder& b = p->b;
-    const int d = c.hidden;
-    const int T2 = 2 * T;
-    const long M2 = (long)n * T2;
-    const int* tab = p->tab;
-    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(256), 0, st, ids, p->tab, b.ksw.ticket, b.ksw.ticket ? b.ksw.n_tickets : 0);
-    // RVQ lookup-sum + output projections -> rvq segments
-    hipLaunchKernelGGL(k_pool_rvq, dim3(n * T, (d + 63) / 64), dim3(256), (size_t)(2 * c.codebook_dim + c.n_codebooks) * 4, st, codes, stride_s,
-                       stride_k, stride_t, T, c.n_codebooks, c.n_semantic, c.codebook_size, c.codebook_dim, d, p->w.codebooks, p->w.proj_first,
-                       p->w.proj_rest, b.rvq.row0(), b.rvq.seg(), tab);
-    // depthwise transposed conv x2 -> tok (dense)
-    hipLaunchKernelGGL(k_pool_upsample, dim3((unsigned)((M2 * d + 255) / 256)), dim3(256), 0, st, b.rvq.row0(), b.rvq.seg(), tab, T, n, d,
-                       p->w.upsample, b.tok);
-    MCHK(p, hipGetLastError());
-    // transformer and SEANet decoder: every product as in a handle's decode_middle, over n * 2T rows
-    TrPass tp{p->w.tr, M2};
-    tp.tab = tab; tp.T2 = T2; tp.ring = p->ring;
-    if (int rc = transformer(p, c, p->w, b, tp, st)) return rc;
-    if (int rc = seanet_decoder(p, p->w, c.n_stages, b, n, T2, tab, st)) return rc;
-    // output convolution -> pcm [n][hop * T], then every segmented buffer's history slides by the chunk
-    const SegBuf& last = b.xj(c.n_stages - 1);
-    const long Tj = (long)T * last.rate;
-    const MimiConv& co = p->w.conv_out;
-    hipLaunchKernelGGL(k_pool_conv_out, dim3((unsigned)((n * Tj + 255) / 256)), dim3(256), 0, st, last.row0(), last.seg(), tab, Tj, n, co.c_in,
-                       co.taps, co.w, co.bias, (float*)pcm_out);
-    const PoolRegions z = hist_regions(b, T);
-    int maxC = 0;
-    for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
-    hipLaunchKernelGGL(k_pool_slide, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
-    MCHK(p, hipGetLastError());
-    for (int i = 0; i < n; ++i) p->offset[ids.sid[i]] += T2;
+    hipLaunchKernelGGL(k_pool_begin, dim3(1), dim3(256), 0, st, ids, p->tab, p->b.ksw.ticket, p->b.ksw.ticket ? p->b.ksw.n_tickets : 0);
+    if (int rc = pool_chain<false>(p, codes, stride_s, stride_k, stride_t, (float*)pcm_out, n, n, T, st)) return rc;
+    for (int i = 0; i < n; ++i) p->offset[ids.sid[i]] += 2 * T;
+    return 0;
+}
+
+extern "C" int mimi_pool_decode_ragged(mimi_pool p, const int32_t* streams, const int32_t* frames, int n, const int32_t* codes, long stride_s,
+                                       long stride_k, long stride_t, void* pcm_out, void* stream) {
+    if (!p) return fail(p, "mimi_pool_decode_ragged: null pool");
+    PoolSegHeader hdr;
+    PoolSegs sg;
+    if (const char* bad = pool_segs_build(streams, frames, n, codes, pcm_out, p->n_streams, p->max_chunk, p->offset.data(), &hdr, &sg)) {
+        p->err = std::string("mimi_pool_decode_ragged: ") + bad;
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_pool_begin_ragged, dim3(1), dim3(256), 0, st, hdr, p->tab, p->b.ksw.ticket, p->b.ksw.ticket ? p->b.ksw.n_tickets : 0);
+    if (int rc = pool_chain<true>(p, codes, stride_s, stride_k, stride_t, (float*)pcm_out, n, sg.F, 1, st)) return rc;
+    for (int i = 0; i < n; ++i) p->offset[hdr.sid[i]] += 2 * hdr.T[i];
     return 0;
 }

@@ -125,6 +125,7 @@ MIMI_SIGNATURES = {
     "mimi_pool_last_error": (C.c_char_p, [_vp]),
     "mimi_pool_reset": (_i, [_vp, _vp, _i, _vp]),
     "mimi_pool_decode": (_i, [_vp, _vp, _i, _vp, _i, _l, _l, _l, _vp, _vp]),
+    "mimi_pool_decode_ragged": (_i, [_vp, _vp, _vp, _i, _vp, _l, _l, _l, _vp, _vp]),
 }
 
 for _name, (_res, _args) in list(SIGNATURES.items()) + list(MIMI_SIGNATURES.items()):

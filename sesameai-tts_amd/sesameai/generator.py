@@ -349,16 +349,19 @@ class Generator:
     @torch.inference_mode()
     def _iter_blocks_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                                 temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
-                                seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1):
+                                seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
+                                first_chunk_frames: Optional[int] = None):
         """The incremental form of ``iter_codes_continuous`` (same loop, same model calls in the same order): per polled block it
         yields a list of ``(index of the prompt, batch slot, that utterance's NEW frames [k][32] int32 CPU, last)`` -- ``last`` with
         the frames that complete the utterance (possibly none); an utterance that is empty before it ever holds a slot has slot -1.
         In between it yields ``None`` each time a block's frame steps have just been queued and before it waits for them: the
         moment for a consumer to start work that should run beside those steps (generate_many_stream's Mimi decode).
-        The scheduler is sesameai/live_batch.py; ``refill_beside_the_loop`` / ``refill_row_layers`` choose and tune how slots are refilled."""
+        The scheduler is sesameai/live_batch.py; ``refill_beside_the_loop`` / ``refill_row_layers`` choose and tune how slots are refilled;
+        ``first_chunk_frames``: its short blocks while a request waits for its first chunk (None: every block is ``poll`` steps)."""
         per_prompt_sampling(len(prompts), temperature, topk, seed)          # (a wrong length or a bad value raises before the model is touched)
         yield from live_batch(self._model, prompts, max_generation_len, temperature, topk, poll or self._eos_poll, self._max_batch,
-                              self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN, seed=seed, refill_group=refill_group)
+                              self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN, seed=seed, refill_group=refill_group,
+                              first_chunk_frames=first_chunk_frames)
 
     def generate_codes_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: int,
                                   temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
@@ -384,7 +387,7 @@ class Generator:
 
     def generate_many_stream(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                              temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
-                             seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1
+                             seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None
                              ) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
@@ -396,7 +399,20 @@ class Generator:
         yields just that.  All other chunks are ``_stream_buffer_size`` frames.
         The streams are STATEFUL: the chunks of one request, concatenated, are the whole-clip decode of its frames (what
         ``generate_many`` returns for them).  ``generate_stream`` differs: it keeps the reference's stateless 10-frame chunks.
-        ``temperature`` / ``topk`` / ``seed``: as for ``generate_many``."""
+        ``temperature`` / ``topk`` / ``seed``: as for ``generate_many``.
+        ``first_chunk_frames`` = k, 1 <= k < ``_stream_buffer_size`` (None, the default: the calls described above, exactly): a request's
+        first audio does not wait for a whole block.  While some request has had no chunk yet, a block of frame steps ends as soon as that
+        request has k frames queued, and after every block ONE ragged pool call (``MimiStreamPool.decode_ragged``) takes every slot with a
+        full chunk, every slot whose request has had no chunk and holds at least k frames -- its first chunk is all it holds -- and the
+        endings' remainders.  So chunk lengths become: the first >= k frames (or the whole request, if shorter), later ones
+        ``_stream_buffer_size``, the last whatever remains; everything else above holds, and a request's chunks concatenated are still its
+        whole-clip decode, bit for bit what the uniform calls give.  The Philox key of a sampled frame holds the global frame index, so --
+        as with ``refill_group`` -- the sampled codes of requests WITHOUT a seed of their own may differ between None and k (the shorter
+        blocks see the retirements at other steps); requests with their own seed, and greedy runs, give the same codes for every k."""
+        size = self._stream_buffer_size
+        if first_chunk_frames is not None and not 1 <= int(first_chunk_frames) < size:
+            raise ValueError(f"first_chunk_frames must be None or 1 .. {size - 1}")
+        first = None if first_chunk_frames is None else int(first_chunk_frames)
         codec = self._audio_tokenizer
         if codec is None or not hasattr(codec, "open_streams"):
             raise RuntimeError("generate_many_stream needs a Mimi codec with stream pools (MimiCodec.open_streams)")
@@ -405,15 +421,15 @@ class Generator:
             prompts = self._build_prompts(texts, speakers, contexts)
         if not prompts:
             return
-        size = self._stream_buffer_size
         B = min(self._max_batch, len(prompts))
         if self._stream_pools is None:
             self._stream_pools = {}
         if (B, size) not in self._stream_pools:
             self._stream_pools[(B, size)] = codec.open_streams(B, max_chunk_frames=size)
-        streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device)
+        streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device, **({} if first is None else {"first": first}))
         backlog: List[list] = []                                    # polled blocks whose audio is still to be decoded
-        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed, refill_group=refill_group):
+        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed, refill_group=refill_group,
+                                                  **({} if first is None else {"first_chunk_frames": first})):
             if block is not None:
                 backlog.append(block)
                 continue

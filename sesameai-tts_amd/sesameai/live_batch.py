@@ -33,10 +33,15 @@ class LiveBatch:
     seed of its own (``own``), which draws at (its seed, its own frame index) wherever and whenever it runs.
     ``own[i]``: ``(temperature, topk, seed or None)`` of prompt ``i`` where it has values of its own, else None: the model's per-slot sampling
     table gets them (``Model.set_slot_sampling``) immediately before the prompt's refill call, and a slot such a prompt leaves is cleared
-    before a prompt without own values takes it.  With no own values anywhere the model sees neither call."""
+    before a prompt without own values takes it.  With no own values anywhere the model sees neither call.
+    ``first_chunk`` = k (None: off, today's blocks exactly): while some utterance has had fewer than k of its frames handed out, a block of
+    frame steps ends as soon as that utterance has k frames QUEUED -- evaluated after every queued step, because a refill may complete in the
+    middle of a block -- so that its first audio need not wait for a whole block.  Otherwise blocks are ``poll`` steps as before."""
 
-    def __init__(self, model, prompts, limits: List[int], temperature: float, topk: int, poll: int, slots: int, store: list, own=None):
+    def __init__(self, model, prompts, limits: List[int], temperature: float, topk: int, poll: int, slots: int, store: list, own=None,
+                 first_chunk: Optional[int] = None):
         self.m, self.prompts, self.limits, self.sampling, self.poll, self.B = model, prompts, limits, (temperature, topk), poll, slots
+        self.first_chunk = first_chunk
         self.own = own if own is not None else [None] * len(prompts)
         self.entries: set = set()                                   # slots that hold an entry of the sampling table (reset_caches empties it)
         # per prompt (rows P to copy, handle): the registered prefix with the longest match, (0, None) without one -- all matched before the loop
@@ -70,9 +75,12 @@ class LiveBatch:
             cuts = [(s, True) for s, u in enumerate(self.slots) if u is not None and u.frames and len(u.frames) >= u.limit]
             if not cuts:                                            # (else an utterance that came with its frame 0 is complete already: no steps)
                 n = max(min(self.poll, min(u.limit - len(u.frames) for u in active)), 1)
-                for _ in range(n):
+                for done in range(1, n + 1):
                     m.step(B, *self.sampling)
                     self._feed(False)
+                    if self.first_chunk is not None and self._first_chunk_queued(done):
+                        n = done                                    # a short block: somebody's first chunk is ready to be read
+                        break
                 yield None                                          # (the block's steps are queued)
                 cuts = self._read(n)
             for s, last in self._report_order(cuts):
@@ -87,6 +95,17 @@ class LiveBatch:
             idle = self._idle([s for s, last in cuts if last])
             if idle and (self.pending or any(u is not None for u in self.slots)):
                 m.reset_slots(idle)                                 # a retired slot keeps stepping: keep its position away from max_seq
+
+    def _first_chunk_queued(self, steps: int) -> bool:
+        """Whether, ``steps`` queued steps into the block, an utterance that has had fewer than ``first_chunk`` frames handed out has that many
+        queued (held, or sampled by this block's steps since it took its slot) -- or all its limit allows."""
+        k = self.first_chunk
+        for u in self.slots:
+            if u is not None and u.reported < k:
+                queued = len(u.frames) + max(0, self.g + steps - max(u.first, self.g))
+                if queued >= min(k, u.limit):
+                    return True
+        return False
 
     def _read(self, n: int) -> List[Tuple[int, bool]]:
         """Reads the block of ``n`` steps and gives every slot its rows, cut at its EOS.  Returns [(slot, whether its utterance is over)]."""
@@ -164,8 +183,8 @@ class _BesideTheLoop(LiveBatch):
     extras.config3.refill_beside_the_loop) while the other slots keep generating, and the new utterance's frame 0 is sampled by the batch's next
     frame step.  Until then the slot's rows are placeholders and are skipped.  Only the rows after a registered prefix count against the budget."""
 
-    def __init__(self, *args, budget: int, group: int = 1):
-        super().__init__(*args)
+    def __init__(self, *args, budget: int, group: int = 1, **kw):
+        super().__init__(*args, **kw)
         self.budget, self.layers = budget, self.m.bb.num_layers
         # group > 1: free slots with prompts pending are refilled up to ``group`` at a time by ONE ragged prefill (Model.refill_group_begin /
         # refill_group_advance) -- slots that retire in the same block share one launch chain per layer instead of queueing with a handful
@@ -254,11 +273,12 @@ def per_prompt_sampling(n: int, temperature, topk, seed):
 
 
 def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_batch, store, beside_the_loop, refill_row_layers, max_seq_len,
-               seed=None, refill_group: int = 1):
+               seed=None, refill_group: int = 1, first_chunk_frames: Optional[int] = None):
     """``LiveBatch.run`` over ``prompts`` [(tokens (S_i,33), mask (S_i,33)), ...] with one length limit for all or one per prompt (a
     request's own max_audio_length_ms), refilling beside the loop where the model's frame steps of this batch size honour it.
     ``temperature`` / ``topk``: one value, or one per prompt; ``seed``: one optional int per prompt (``per_prompt_sampling``).
-    ``refill_group``: how many free slots one refill beside the loop may take together (1: one at a time, today's calls exactly)."""
+    ``refill_group``: how many free slots one refill beside the loop may take together (1: one at a time, today's calls exactly).
+    ``first_chunk_frames``: ``LiveBatch``'s ``first_chunk`` (None: today's blocks exactly)."""
     (temperature, topk), own = per_prompt_sampling(len(prompts), temperature, topk, seed)
     limits = [int(max_generation_len)] * len(prompts) if isinstance(max_generation_len, (int, float)) else [int(x) for x in max_generation_len]
     if len(limits) != len(prompts):
@@ -274,15 +294,19 @@ def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_
     beside = supported is not None and supported(B) and beside_the_loop
     if int(refill_group) < 1:
         raise ValueError("refill_group must be >= 1")
-    yield from (_BesideTheLoop(*args, budget=refill_row_layers, group=refill_group) if beside else _Stalling(*args)).run()
+    kw = {} if first_chunk_frames is None else {"first_chunk": int(first_chunk_frames)}
+    yield from (_BesideTheLoop(*args, budget=refill_row_layers, group=refill_group, **kw) if beside else _Stalling(*args, **kw)).run()
 
 
 class SlotStreams:
     """The stream state of ``generate_many_stream``: each batch slot is one stream of a ``MimiStreamPool``; ``owner[slot]`` is the request
-    whose audio the slot's stream carries, ``held[slot]`` its frames not decoded yet.  Decodes run on ``side`` (a HIP stream, or None)."""
+    whose audio the slot's stream carries, ``held[slot]`` its frames not decoded yet.  Decodes run on ``side`` (a HIP stream, or None).
+    ``first`` = k (None: off, today's calls exactly): a request's first chunk goes out as soon as its slot holds k frames, and everything
+    that is ready after a block -- full chunks, first chunks, the endings' remainders -- goes into ONE ragged pool call (``_ragged_calls``)."""
 
-    def __init__(self, pool, slots: int, size: int, side, device):
-        self.pool, self.size, self.side = pool, size, side
+    def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None):
+        self.pool, self.size, self.side, self.first = pool, size, side, first
+        self.started: List[bool] = [False] * slots                  # whether the slot's request has had a chunk (``first`` only)
         self.owner: List[Optional[int]] = [None] * slots
         self.held: List[List[torch.Tensor]] = [[] for _ in range(slots)]
         self.no_pcm = torch.empty(0, dtype=torch.float32, device=device)
@@ -298,12 +322,12 @@ class SlotStreams:
                 out.append((i, self.no_pcm, _NO_FRAMES, True))
                 continue
             if owner[slot] != i:
-                owner[slot], held[slot] = i, []
+                owner[slot], held[slot], self.started[slot] = i, [], False
                 fresh.append(slot)
             held[slot].extend(fr.unbind(0))
             if last:
                 ending.append(slot)
-        calls: List[Tuple[List[int], torch.Tensor, torch.Tensor]] = []
+        calls: list = []                                            # (slots, their frames, their PCM (.., 1, samples)) per pool call
 
         def decode(slots: List[int], T: int) -> None:
             frames = torch.stack([torch.stack(held[s_][:T]) for s_ in slots]).to(torch.int32)      # (n, T, 32)
@@ -314,7 +338,9 @@ class SlotStreams:
         with torch.inference_mode(), (torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext()):
             if fresh:
                 pool.reset(fresh)
-            while full := [s_ for s_, h in enumerate(held) if len(h) >= self.size]:
+            if self.first is not None:
+                self._ragged_calls(ending, calls)
+            while self.first is None and (full := [s_ for s_, h in enumerate(held) if len(h) >= self.size]):
                 decode(full, self.size)
             for T in sorted({len(held[s_]) for s_ in ending} - {0}):
                 decode([s_ for s_ in ending if len(held[s_]) == T], T)
@@ -322,9 +348,26 @@ class SlotStreams:
             self.side.synchronize()
         final = {s_: k for k, (slots, _, _) in enumerate(calls) for s_ in slots}       # the call that holds a slot's newest chunk
         for k, (slots, frames, pcm) in enumerate(calls):
-            out.extend((owner[s_], pcm[j, 0], frames[j], s_ in ending and final[s_] == k) for j, s_ in enumerate(slots))
+            out.extend((owner[s_], pcm[j][0], frames[j], s_ in ending and final[s_] == k) for j, s_ in enumerate(slots))
         for s_ in ending:
             if s_ not in final:                                     # nothing was left to decode: the closing chunk is empty
                 out.append((owner[s_], self.no_pcm, _NO_FRAMES, True))
             owner[s_] = None
         return out
+
+    def _ragged_calls(self, ending: List[int], calls: list) -> None:
+        """With ``first`` = k: ONE ``decode_ragged`` call takes every slot that holds a full chunk (``size`` frames), every slot whose request
+        has had no chunk yet and holds at least k frames (its first chunk is ALL it holds, up to ``size``) and every ending slot with frames
+        left (up to ``size``); a slot that then still holds something to send -- it held more than ``size`` -- goes into a further call."""
+        held, size = self.held, self.size
+        while True:
+            take = [(s_, min(len(h), size)) for s_, h in enumerate(held)
+                    if h and (len(h) >= size or s_ in ending or (not self.started[s_] and len(h) >= self.first))]
+            if not take:
+                return
+            slots = [s_ for s_, _ in take]
+            frames = [torch.stack(held[s_][:T]).to(torch.int32) for s_, T in take]             # each (T_i, 32)
+            for s_, T in take:
+                del held[s_][:T]
+                self.started[s_] = True
+            calls.append((slots, frames, self.pool.decode_ragged(slots, [f.t() for f in frames])))

@@ -444,7 +444,8 @@ class MimiStreamPool:
     """``n`` independent stateful Mimi decode streams (include/mimi_hip.h, mimi_pool_*): stream ``i`` keeps its own conv left
     contexts, K/V ring and token offset, and runs for any number of frames.  ``decode(ids, codes)`` continues the listed
     streams by the same ``T <= max_chunk_frames`` frames each; a stream's PCM does not depend on which other streams share the
-    call, and its chunks, concatenated, are ``MimiCodec.decode`` of its concatenated codes.  Streams start reset."""
+    call, and its chunks, concatenated, are ``MimiCodec.decode`` of its concatenated codes.  ``decode_ragged`` does the same for streams
+    with a different number of frames each, still in one launch chain.  Streams start reset."""
 
     def __init__(self, codec: MimiCodec, n: int, max_chunk_frames: int = 10):
         self.codec = codec                        # keeps the device weights alive
@@ -481,6 +482,36 @@ class MimiStreamPool:
         pcm = torch.empty(n, 1, s.hop * T, dtype=torch.float32, device=self.codec.device)
         self._check(lib.mimi_pool_decode(self._h, arr, n, c.data_ptr(), T, c.stride(0), c.stride(1), c.stride(2), pcm.data_ptr(), _stream()))
         return pcm
+
+    @torch.inference_mode()
+    def decode_ragged(self, ids: Sequence[int], codes, lengths: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """``decode`` for streams with DIFFERENT numbers of new frames, in ONE launch chain (mimi_pool_decode_ragged): ``codes`` is a list of
+        (32, T_i) int tensors, row i for stream ids[i], or one padded (n, 32, Tmax) tensor with ``lengths`` = [T_i].  Returns one PCM tensor
+        (1, hop*T_i) per stream, views into one output buffer.  A stream's PCM is, bit for bit, what ``decode`` gives it for the same chunk
+        schedule, whatever the others' lengths are and wherever it sits in the list."""
+        arr, n = self._ids(ids)
+        s = self.codec.args
+        if isinstance(codes, torch.Tensor):
+            assert lengths is not None, "a padded codes tensor needs the streams' lengths"
+            lengths = [int(t) for t in lengths]
+            assert codes.dim() == 3 and codes.shape[0] == n == len(lengths) and codes.shape[1] == s.num_codebooks, "codes must be (len(ids), 32, Tmax)"
+            assert all(t <= codes.shape[2] for t in lengths), "a length beyond the padded tensor"
+            c = codes.to(device=self.codec.device, dtype=torch.int32)
+        else:
+            assert lengths is None and len(codes) == n, "one (32, T_i) tensor per id"
+            assert all(x.dim() == 2 and x.shape[0] == s.num_codebooks for x in codes), "every stream's codes must be (32, T_i)"
+            lengths = [int(x.shape[1]) for x in codes]
+            c = torch.zeros(max(n, 1), s.num_codebooks, max(lengths + [1]), dtype=torch.int32, device=self.codec.device)
+            for i, x in enumerate(codes):
+                c[i, :, :lengths[i]] = x.to(device=self.codec.device, dtype=torch.int32)
+        hop = s.hop
+        pcm = torch.empty(1, hop * max(sum(t for t in lengths if t > 0), 1), dtype=torch.float32, device=self.codec.device)
+        self._check(lib.mimi_pool_decode_ragged(self._h, arr, (C.c_int32 * n)(*lengths), n, c.data_ptr(), c.stride(0), c.stride(1), c.stride(2),
+                                                pcm.data_ptr(), _stream()))
+        out, at = [], 0
+        for t in lengths:
+            out.append(pcm[:, hop * at:hop * (at + t)]); at += t
+        return out
 
     def __del__(self):
         try:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Multi-stream Mimi decode on an MI355X: one pool call for N streams (mimi_pool_decode) against the way the same work was done
 before the pool existed -- N single-stream handles, each running one stateful 10-frame chunk decode (decode_stream) -- and what a
-32-stream pool call per 10 frame steps on the side stream costs the B = 32 frame loop.
+32-stream pool call per 10 frame steps on the side stream costs the B = 32 frame loop.  And the ragged call (mimi_pool_decode_ragged)
+against the uniform calls it replaces: 32 streams of which 24 have a full chunk and 8 end with 1..8 frames -- one ragged call against one
+uniform call of 24 plus eight calls of one -- and all 32 at 10 frames against the one uniform call (the price of the table lookup).
 
 Full-size codec (synthetic weights), 10-frame chunks, N = 1, 8, 32.  Times are GPU times between HIP events on the launching
 stream, per round (one pool call / N single-stream calls); the two ways alternate round by round in one process, after warm-up
@@ -15,6 +17,7 @@ import json
 import os
 import statistics
 import sys
+import time
 import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,6 +95,55 @@ def pool_vs_singles(codec, N, rounds, warmup, per_reset=4):
             "singles_over_pool": med(t_single) / med(t_pool), "pcm_bit_identical": bool(same)}
 
 
+def timed_both(fn):
+    """(GPU ms between HIP events, host ms the calls took to return) of fn()."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    t0 = time.perf_counter(); fn(); t1 = time.perf_counter()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1), (t1 - t0) * 1e3
+
+
+def _stats(v):
+    return {"median": statistics.median(v), "mean": statistics.fmean(v), "min": min(v), "max": max(v)}
+
+
+def ragged_leg(codec, rounds, warmup, N=32):
+    """One ragged call against the uniform calls it replaces, on twin pools (same codes, same schedule, PCM compared), alternating round by
+    round after warm-up rounds of both.  `endings`: 24 streams x 10 frames and 8 streams with 1..8 frames; `all_full`: 32 x 10."""
+    dev = codec.device
+    codes = torch.randint(0, 2048, (N, 32, CHUNK), generator=torch.Generator().manual_seed(300 + N)).to(device=dev, dtype=torch.int32)
+    ids = list(range(N))
+    res = {"streams": N, "rounds": rounds}
+    for name, lens in (("endings", [CHUNK] * (N - 8) + list(range(1, 9))), ("all_full", [CHUNK] * N)):
+        rag_pool, uni_pool = codec.open_streams(N, max_chunk_frames=CHUNK), codec.open_streams(N, max_chunk_frames=CHUNK)
+        groups = {}
+        for i, T in enumerate(lens):
+            groups.setdefault(T, []).append(i)
+        out = {}
+
+        def run_ragged():
+            out["rag"] = rag_pool.decode_ragged(ids, codes, lens)
+
+        def run_grouped():                                     # today's grouping: one uniform call per distinct length
+            out["uni"] = {T: uni_pool.decode(g, codes[g[0]:g[-1] + 1, :, :T]) for T, g in sorted(groups.items(), reverse=True)}
+
+        t = {"ragged_gpu": [], "ragged_host": [], "grouped_gpu": [], "grouped_host": []}
+        same = True
+        for r in range(warmup + rounds):
+            a, b = timed_both(run_ragged), timed_both(run_grouped)
+            same = same and all(torch.equal(out["rag"][i][0], out["uni"][T][g.index(i), 0]) for T, g in groups.items() for i in g)
+            if r >= warmup:
+                t["ragged_gpu"].append(a[0]); t["ragged_host"].append(a[1]); t["grouped_gpu"].append(b[0]); t["grouped_host"].append(b[1])
+        res[name] = {"frames": lens, "uniform_calls_replaced": len(groups), "pcm_bit_identical": bool(same),
+                     "one_ragged_call_gpu_ms": _stats(t["ragged_gpu"]), "one_ragged_call_host_ms": _stats(t["ragged_host"]),
+                     "uniform_calls_gpu_ms": _stats(t["grouped_gpu"]), "uniform_calls_host_ms": _stats(t["grouped_host"]),
+                     "uniform_over_ragged_gpu": statistics.median(t["grouped_gpu"]) / statistics.median(t["ragged_gpu"]),
+                     "uniform_over_ragged_host": statistics.median(t["grouped_host"]) / statistics.median(t["ragged_host"])}
+    return res
+
+
 def frame_loop_leg(codec, steps, reps):
     """B = 32 frame steps of the 1B model with and without one 32-stream pool call per 10 steps on a side stream; ms per step."""
     import bench
@@ -149,6 +201,7 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-frame-loop", action="store_true")
+    ap.add_argument("--skip-ragged", action="store_true", help="(a library built before mimi_pool_decode_ragged, named by CSM_HIP_LIB, has no such leg)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("mimi_streams_bench: needs a GPU (there is nothing to measure without one)")
@@ -158,6 +211,9 @@ def main():
            "what": "GPU ms (HIP events) of one mimi_pool_decode of N streams x 10 frames vs N single-stream handles each running one stateful 10-frame decode",
            "pool_vs_singles": [pool_vs_singles(codec, N, args.rounds, args.warmup) for N in (1, 8, 32)]}
     print(json.dumps(res["pool_vs_singles"]), flush=True)
+    if not args.skip_ragged:
+        res["ragged_vs_uniform_calls"] = ragged_leg(codec, args.rounds, args.warmup)
+        print(json.dumps(res["ragged_vs_uniform_calls"]), flush=True)
     if not args.skip_frame_loop:
         res["frame_loop_b32"] = frame_loop_leg(codec, args.steps, args.reps)
     line = json.dumps(res)
