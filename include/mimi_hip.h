@@ -1,6 +1,7 @@
 /*
  * libcsm_hip.so -- Mimi codec DECODE path (RVQ lookup + upsample + 8-layer transformer +
- * SEANet conv decoder), fp32, gfx950.
+ * SEANet conv decoder), fp32, gfx950; below it the ENCODE path, and both as pools of stateful
+ * streams (mimi_pool_*: decode, mimi_enc_pool_*: encode).
  *
  * Replaces `self._audio_tokenizer.decode(codes)` of the reference, i.e. moshi 0.2.2
  * `MimiModel.decode` as called at sesameai/generator.py:116 (stateless 10-frame stream
@@ -164,6 +165,37 @@ int  mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, const int32_t*
  * 2^31 tokens.                                                                                                                         */
 int  mimi_pool_decode_ragged(mimi_pool p, const int32_t* streams, const int32_t* frames, int n, const int32_t* codes,
                              long stride_s, long stride_k, long stride_t, void* pcm, void* stream);
+
+/* ---- A pool of stateful ENCODE streams fed TOGETHER (every microphone's new frames as they arrive, all conversations in one chain) ----
+ * A pool holds n_streams independent encode streams: per stream the rows of left context in front of every convolution of the encoder (the
+ * last kernel - 1 samples, res_kernel - 1 rows in front of each stage's residual convolution, r_j rows in front of its strided one, 2 in
+ * front of the output convolution and of the downsample), a per-layer K/V ring of tr_context + 2 * max_chunk_frames tokens and its token
+ * offset.  Nothing in a stream grows with its length.
+ * mimi_enc_pool_encode: stream streams[i] gets n_samples[i] >= 1 new samples at wav + wav_off[i] (wav: device memory; streams, wav_off,
+ * n_samples: host arrays, read before the call returns).  With T_i = ceil(n_samples[i] / hop) <= max_chunk_frames, F_i = T_0 + .. + T_(i-1)
+ * and F = sum T_i the output is codes[n_codebooks][F] int32 (device): stream i owns columns [F_i, F_i + T_i).  ONE launch chain per call,
+ * whatever n and the T_i are; the plan travels in the kernel arguments and the chain's first kernel expands it into the pool's device table
+ * ({id, token offset, F_i, T_i, rows per level, first} per segment and the segment of every frame): no host-to-device copy, no
+ * synchronisation.
+ * A chunk whose n_samples[i] is NOT a multiple of hop ends its stream: its last frame follows the whole-clip rule (every level's length is the
+ * rounded-up division chain of the chunk's own samples; zero padding behind the strided convolutions, replicate behind the downsample), and
+ * the stream is refused until mimi_enc_pool_reset.  A stream that ends on a frame boundary is simply reset.
+ * NUMERICAL RULE: a stream's columns, concatenated over its calls, are BIT FOR BIT mimi_encode of its concatenated samples -- for every chunk
+ * schedule, every company in the call and every position in the list.  Every encode op is causal, its left padding is the history rows (zero
+ * after a reset; the downsample replicates the first token at offset 0 and reads history afterwards), hop divides into every level's
+ * stride, no product takes a K split, the wave split depends on (taps, C_in) alone and the attention walks its keys in chronological order.
+ * Returns -1 with a message in mimi_enc_pool_last_error, nothing enqueued, no offset moved and the pool still usable, for: n outside
+ * [1, n_streams], a duplicate or out-of-range id, an n_samples[i] < 1, a negative wav_off[i], T_i > max_chunk_frames, an ended stream, a null
+ * pointer, a stream that would pass 2^31 tokens.  -2: a HIP error.  Drive ONE HIP stream per pool at a time.
+ * The pool shares the caller's MimiWeights (device memory the caller keeps alive); creation is refused when has_encoder == 0.            */
+#define MIMI_ENC_POOL_MAX_STREAMS 64
+typedef struct MimiEncStreamPool* mimi_enc_pool;
+int  mimi_enc_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_enc_pool* out);
+void mimi_enc_pool_destroy(mimi_enc_pool p);
+const char* mimi_enc_pool_last_error(mimi_enc_pool p);   /* p == NULL: why mimi_enc_pool_create failed (this thread) */
+int  mimi_enc_pool_reset(mimi_enc_pool p, const int32_t* streams, int n, void* stream);
+int  mimi_enc_pool_encode(mimi_enc_pool p, const int32_t* streams, const long* wav_off, const long* n_samples, int n,
+                          const float* wav, int32_t* codes, void* stream);
 
 #ifdef __cplusplus
 }

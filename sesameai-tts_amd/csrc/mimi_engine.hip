@@ -30,6 +30,8 @@ static_assert(ENC_MAX_CLIPS == MIMI_ENCODE_MAX_CLIPS && ENC_MAX_STAGES == MIMI_M
 #define POOL_SEGS_FN __host__ __device__ static inline
 #include "pool_segs.h"
 static_assert(POOL_SEG_MAX_STREAMS == MIMI_POOL_MAX_STREAMS, "pool_segs.h and mimi_hip.h disagree");
+#include "enc_stream_segs.h"
+static_assert(ENC_STREAM_MAX_STREAMS == MIMI_ENC_POOL_MAX_STREAMS, "enc_stream_segs.h and mimi_hip.h disagree");
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 static thread_local std::string g_mimi_err;
@@ -86,6 +88,11 @@ struct GemmArgs {
     // [rate_in * F0_c, + L_c(lvl_in)): a tap reads neither a neighbour's rows nor the unused tail of its own slot.  (edge 0: a dense product,
     // A row = output row.)  The q|k|v epilogue takes the RoPE position from the token's index inside its clip; the K/V row is the global row.
     RagArgs rag;
+    // Encode stream pool (the ENS instantiation, with SEG and PRG; mimi_enc_pool_encode): a product whose taps reach past the rows its segment
+    // got in this call.  x keeps every stream in place (seg_by_id bit 0) and the edge bounds are the SEGMENT's: below, row_lo rows relative to
+    // the stream's row 0 (-hist: its saved history, or -- edge 2 at token offset 0, the downsample's replicate padding -- row 0 itself); above,
+    // the rows the segment has at the input level, seg_tab[ens_L + si] (enc_stream_segs.h).
+    int ens_L;
 };
 
 __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expf(v) - 1.0f; }
@@ -108,7 +115,7 @@ __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expf(v) - 
 // the weights re-tiled into MFMA operand order so that every wave load is one contiguous 1 KB (the K = 2048 linear 24 us against
 // 19.5 row-major: with one 32-row tile these launches sit on 16..64 CUs and are bound by the fp32 matrix pipe -- 128 dependent
 // 64-cycle v_mfma_f32_32x32x2_f32 per wave, two waves per SIMD = 6.8 us -- plus the ~4.7 us of a dependent launch, not by loads).
-template <bool ELU, bool SEG = false, bool RAG = false, bool PRG = false>
+template <bool ELU, bool SEG = false, bool RAG = false, bool PRG = false, bool ENS = false>
 __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
     __shared__ float red[G32_NW][16][64];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -123,16 +130,21 @@ __global__ __launch_bounds__(64 * G32_NW) void k_gemm32(const GemmArgs a) {
     const int nrow = nrow_ok ? (n0 + r) : (a.C_out - 1);
     const int kchunks = a.C_in / 32, iters = a.taps * kchunks;
     int arow0 = trow * a.in_stride + a.shift0;
+    int row_lo = a.row_lo, row_hi = a.row_hi;
     if (SEG) {
         if (PRG) {
             const int si = a.seg_tab[POOL_TAB_FRAME + trow / a.seg_T], r0 = a.seg_T * a.seg_tab[POOL_TAB_F0 + si];
             arow0 = ((a.seg_by_id & 1) ? a.seg_tab[si] * a.seg_x : r0) + (trow - r0) * a.in_stride + a.shift0;
+            if (ENS) {
+                const int base = a.seg_tab[si] * a.seg_x;
+                row_lo = base + ((a.edge == 2 && a.seg_tab[ENC_STREAM_TAB_FIRST + si]) ? 0 : a.row_lo);
+                row_hi = base + a.seg_tab[a.ens_L + si];
+            }
         } else {
             const int si = trow / a.seg_T, tl = trow - si * a.seg_T;
             arow0 = ((a.seg_by_id & 1) ? a.seg_tab[si] : si) * a.seg_x + tl * a.in_stride + a.shift0;
         }
     }
-    int row_lo = a.row_lo, row_hi = a.row_hi;
     if (RAG && a.edge != 0) {
         const EncClipTab& c = a.rag.clips[a.rag.frame_clip[trow / a.rag.rate_out]];
         row_lo = a.rag.rate_in * c.F0; row_hi = row_lo + c.L[a.rag.lvl_in];
@@ -650,6 +662,58 @@ __global__ void k_pool_zero_hist(const PoolRegions z, const PoolIds ids) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < z.hist[reg] * z.C[reg]; i += gridDim.x * blockDim.x) base[i] = 0.f;
 }
 
+// ---- encode stream pool: N stateful ENCODE streams fed by one launch chain (mimi_enc_pool_encode; layout: enc_stream_segs.h) ---------------
+// first kernel of a call: the header of the kernel arguments -> the device table every later kernel reads.  One block.
+__global__ __launch_bounds__(256) void k_enc_stream_plan(const EncStreamHeader hdr, int* tab, long* ltab) {
+    __shared__ int f0[POOL_SEG_MAX_STREAMS + 1];
+    if (threadIdx.x == 0) enc_stream_prefix(&hdr, f0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < hdr.n; i += blockDim.x) {
+        tab[POOL_TAB_SID + i] = hdr.sid[i]; tab[POOL_TAB_OFF + i] = hdr.off[i]; tab[POOL_TAB_F0 + i] = f0[i]; tab[POOL_TAB_T + i] = f0[i + 1] - f0[i];
+        for (int l = 0; l < ENC_MAX_LEVELS; ++l) tab[ENC_STREAM_TAB_L(l) + i] = l <= hdr.S + 1 ? (int)enc_level_len(hdr.n_samples[i], hdr.ratios, hdr.S, l) : 0;
+        tab[ENC_STREAM_TAB_FIRST + i] = hdr.off[i] == 0;
+        ltab[ENC_STREAM_LTAB_WAV_OFF + i] = hdr.wav_off[i];
+    }
+    for (int f = threadIdx.x; f < f0[hdr.n]; f += blockDim.x) tab[POOL_TAB_FRAME + f] = pool_seg_of_frame(f0, f);
+}
+
+// k_enc_conv_in over the streams' new samples: a sample's segment comes from its frame, the taps in front of the chunk read the stream's
+// saved tail (its last taps - 1 samples; zeros after a reset), the output goes to the stream's own segment, and the rows of a last partial
+// frame that have no sample behind them are left alone
+__global__ void k_enc_stream_conv_in(const float* wav, long rows, int hop, int taps, int C, const float* w, const float* b, const int* tab,
+                                     const long* ltab, const float* tail /*[stream][taps - 1]*/, float* out /*row 0 of stream 0*/, int seg) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * C) return;
+    const long g = i / C;
+    const int co = (int)(i % C);
+    const int si = tab[POOL_TAB_FRAME + g / hop];
+    const int t = (int)(g - (long)hop * tab[POOL_TAB_F0 + si]);         // the sample's index inside its chunk
+    if (t >= tab[ENC_STREAM_TAB_L(0) + si]) return;
+    const int sid = tab[POOL_TAB_SID + si];
+    const float* x = wav + ltab[ENC_STREAM_LTAB_WAV_OFF + si];
+    const float* th = tail + (long)sid * (taps - 1);
+    float acc = b[co];
+    for (int k = 0; k < taps; ++k) {
+        const int ti = t - (taps - 1) + k;
+        acc = fmaf(ti >= 0 ? x[ti] : th[taps - 1 + ti], w[k * C + co], acc);
+    }
+    out[((long)sid * seg + t) * C + co] = acc;
+}
+
+// after it: every listed stream's tail = the last `hist` samples of (old tail ++ the chunk).  One block; all reads before any write.
+__global__ __launch_bounds__(256) void k_enc_stream_tail(const float* wav, int n, int hist, const int* tab, const long* ltab, float* tail) {
+    __shared__ float v[POOL_SEG_MAX_STREAMS * (MAX_TAPS - 1)];
+    for (int i = threadIdx.x; i < n * hist; i += blockDim.x) {
+        const int si = i / hist, j = tab[ENC_STREAM_TAB_L(0) + si] + (i - si * hist);      // index into (old tail ++ the chunk)
+        v[i] = j < hist ? tail[(long)tab[POOL_TAB_SID + si] * hist + j] : wav[ltab[ENC_STREAM_LTAB_WAV_OFF + si] + j - hist];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n * hist; i += blockDim.x) {
+        const int si = i / hist;
+        tail[(long)tab[POOL_TAB_SID + si] * hist + (i - si * hist)] = v[i];
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 // Activation buffer of N streams that keeps EVERY stream's segment in place: stream s owns rows [s * seg, (s + 1) * seg) with seg = hist +
 // the rows of the longest chunk, its `hist` rows of left context in front of its row 0.  A handle is the N = 1 case.
@@ -738,8 +802,11 @@ static const char* config_error(const MimiConfig* cfg) {
 }
 
 // The ladder of N streams of up to `frames` frames a call, kv_rows K/V rows per stream and layer, ffn_cols columns of ffn.
+// enc: the histories the ENCODER's taps need (an encode stream pool): two rows of a0 in front of the 4-tap downsample, last_kernel - 1 rows
+// of s0 in front of the output convolution, ratios[j] rows of xj[j] in front of the strided convolution (taps at -r .. r - 1), none of rvq
+// (the downsample's dense output); no K-split workspace, since no encode product takes a K split.
 template <class H>
-static int ladder_alloc(H* h, Ladder& b, const MimiConfig& c, int N, long frames, long kv_rows, int ffn_cols) {
+static int ladder_alloc(H* h, Ladder& b, const MimiConfig& c, int N, long frames, long kv_rows, int ffn_cols, bool enc = false) {
     const int d = c.hidden;
     const long M2 = 2L * N * frames;                 // rows of a full call at the transformer's rate
     auto seg = [&](SegBuf& s, int hist, int rate, int C) {
@@ -752,14 +819,14 @@ static int ladder_alloc(H* h, Ladder& b, const MimiConfig& c, int N, long frames
     int C = c.n_filters << c.n_stages, rate = 2;
     const int ccap = C > d ? C : d;                  // widest output of a split product (conv_in); >= hidden
     b.n_sb = 3 + 2 * c.n_stages;
-    MCHK(h, seg(b.rvq, 1, 1, d));
-    MCHK(h, seg(b.a0, c.kernel - 1, 2, d));
-    MCHK(h, seg(b.s0, 1, 2, C));
+    MCHK(h, seg(b.rvq, enc ? 0 : 1, 1, d));
+    MCHK(h, seg(b.a0, enc ? 2 : c.kernel - 1, 2, d));
+    MCHK(h, seg(b.s0, enc ? c.last_kernel - 1 : 1, 2, C));
     for (int j = 0; j < c.n_stages; ++j) {
         rate *= c.ratios[j]; C /= 2;
         MCHK(h, seg(b.u(j), c.res_kernel - 1, rate, C));
         A4(b.r1[j], N * frames * rate * (C / 2));
-        MCHK(h, seg(b.xj(j), (j + 1 < c.n_stages) ? 1 : c.last_kernel - 1, rate, C));
+        MCHK(h, seg(b.xj(j), enc ? c.ratios[j] : (j + 1 < c.n_stages) ? 1 : c.last_kernel - 1, rate, C));
     }
     A4(b.tok, M2 * d); A4(b.ln, M2 * d); A4(b.q, M2 * d); A4(b.att, M2 * d); A4(b.ffn, M2 * ffn_cols);
     b.kv_layer = N * kv_rows * d;
@@ -767,7 +834,7 @@ static int ladder_alloc(H* h, Ladder& b, const MimiConfig& c, int N, long frames
     // K-split workspace (k_gemm32): the deep products' partial tiles and tile tickets, sized for a full call.  MIMI_KSPLIT=0 in the
     // environment: no split.  (A pool splits the same shapes as a handle: its sums are those of a single handle.)
     const int want = sw_int(SW_MIMI_KSPLIT, MIMI_KSPLIT);
-    if (want == 2 || want == 4 || want == 8) {
+    if (!enc && (want == 2 || want == 4 || want == 8)) {
         b.ksw.ksplit = want; b.ksw.cap_rows = M2; b.ksw.cap_cols = ccap;
         b.ksw.n_tickets = (int)((M2 + 31) / 32) * ((ccap + 31) / 32);
         A4(b.ksw.part, (long)want * M2 * ccap);
@@ -864,6 +931,7 @@ struct Product {
     const KSplitWs* ksw = nullptr;
     SegArgs sg = {};                                // sg.tab != nullptr: the SEG instantiation
     RagArgs rg = {};                                // rg.clips != nullptr: the RAG instantiation (a ragged encode)
+    int ens_L = -1;                                 // >= 0: the ENS instantiation (an encode stream pool), with seg()
     Product& taps_at(int s0, int ds) { shift0 = s0; dshift = taps > 1 ? ds : 0; return *this; }
     Product& elu() { elu_in = true; return *this; }
     Product& gelu() { gelu_out = true; return *this; }
@@ -880,6 +948,9 @@ struct Product {
     Product& stride(int s) { in_stride = s; return *this; }                       // a down-sampling conv
     Product& zero_padded(long lo, long hi) { edge = 1; row_lo = (int)lo; row_hi = (int)hi; return *this; }       // input rows outside [lo, hi) read as zero
     Product& replicate_padded(long lo, long hi) { edge = 2; row_lo = (int)lo; row_hi = (int)hi; return *this; }  // ... are clamped into [lo, hi)
+    // a product of an encode stream pool whose taps pass its segment's rows: `hist` rows of the stream's history below (a replicate edge at
+    // token offset 0: row 0), the segment's rows at level lvl_in above, padded as `edge_mode` says (1 zero, 2 replicate)
+    Product& seg_edges(int edge_mode, int hist, int lvl_in) { edge = edge_mode; row_lo = -hist; row_hi = 0; ens_L = ENC_STREAM_TAB_L(lvl_in); return *this; }
 };
 static Product linear(const float* x, long ldx, long rows, const float* w, int c_in, int c_out, float* out, long ldo) {
     return Product{x, ldx, rows, w, nullptr, c_in, c_out, 1, 1, out, ldo};
@@ -917,7 +988,12 @@ static hipError_t gemm(hipStream_t st, const Product& g) {
     if (seg) {
         const SegArgs& s = g.sg;
         a.seg_T = s.T; a.seg_x = s.x; a.seg_o = s.o; a.seg_r = s.r; a.seg_by_id = s.by_id; a.rope_ring = s.ring; a.seg_tab = s.tab;
-        if (s.ragged) {
+        if (s.ragged && g.ens_L >= 0) {
+            a.ens_L = g.ens_L;
+            if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true, false, true, true>), grid, dim3(64 * G32_NW), 0, st, a);
+            else hipLaunchKernelGGL((k_gemm32<false, true, false, true, true>), grid, dim3(64 * G32_NW), 0, st, a);
+        }
+        else if (s.ragged) {
             if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
             else hipLaunchKernelGGL((k_gemm32<false, true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
         }
@@ -1323,5 +1399,160 @@ extern "C" int mimi_pool_decode_ragged(mimi_pool p, const int32_t* streams, cons
     hipLaunchKernelGGL(k_pool_begin_ragged, dim3(1), dim3(256), 0, st, hdr, p->tab, p->b.ksw.ticket, p->b.ksw.ticket ? p->b.ksw.n_tickets : 0);
     if (int rc = pool_chain<true>(p, codes, stride_s, stride_k, stride_t, (float*)pcm_out, n, sg.F, 1, st)) return rc;
     for (int i = 0; i < n; ++i) p->offset[hdr.sid[i]] += 2 * hdr.T[i];
+    return 0;
+}
+
+// ---- encode stream pool ------------------------------------------------------------------------------------------------------------------
+// The encoder on the pool's ladder: stage j lives in the stage buffers of index S-1-j, as in encode_one, but every buffer that feeds a
+// convolution with taps keeps each stream's rows IN PLACE behind its history, so the left padding of the whole-clip encode (zeros; row 0
+// replicated for the downsample) becomes the rows the stream's previous call left there.
+struct MimiEncStreamPool {
+    MimiConfig cfg;
+    MimiWeights w;
+    int n_streams = 0, max_chunk = 0, ring = 0;
+    std::vector<long> offset;                       // tokens each stream has encoded so far
+    std::vector<unsigned char> ended;               // the stream took a partial last frame: refused until reset
+    Ladder b;
+    int* tab = nullptr;                             // device table of the running call (enc_stream_segs.h): ENC_STREAM_TAB_WORDS words ...
+    long* ltab = nullptr;                           // ... and ENC_STREAM_LTAB_LONGS longs behind them (same allocation)
+    float* wav_tail = nullptr;                      // [stream][kernel - 1]: the samples in front of the next chunk's first
+    std::string err;
+};
+
+extern "C" int mimi_enc_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_enc_pool* out) {
+    csm_warn_unknown_switches();
+    if (!cfg || !w || !out) return fail(nullptr, "mimi_enc_pool_create: null argument");
+    if (!w->has_encoder) return fail(nullptr, "mimi_enc_pool_create: these weights have no encoder");
+    if (n_streams < 1 || n_streams > MIMI_ENC_POOL_MAX_STREAMS) return fail(nullptr, "mimi_enc_pool_create: n_streams must be 1 .. MIMI_ENC_POOL_MAX_STREAMS (64)");
+    if (max_chunk_frames < 1 || max_chunk_frames > ENC_STREAM_MAX_CHUNK) return fail(nullptr, "mimi_enc_pool_create: max_chunk_frames must be 1 .. 64");
+    if (const char* bad = config_error(cfg)) return fail(nullptr, bad);
+    // the histories below are sized from the configuration: the weights must have its taps
+    bool taps_ok = cfg->kernel >= 2 && cfg->codebook_dim % 32 == 0 && cfg->codebook_dim <= 2 * cfg->hidden && w->enc_conv_out.taps == cfg->last_kernel;
+    for (int j = 0; j < cfg->n_stages; ++j)
+        taps_ok = taps_ok && w->enc_res1[j].taps == cfg->res_kernel && w->enc_res2[j].taps == 1 && w->enc_down[j].taps == 2 * cfg->ratios[cfg->n_stages - 1 - j];
+    if (!taps_ok) return fail(nullptr, "mimi_enc_pool_create: encoder weights whose taps are not the configuration's (or codebook_dim % 32)");
+    MimiEncStreamPool* p = new MimiEncStreamPool();
+    p->cfg = *cfg; p->w = *w; p->n_streams = n_streams; p->max_chunk = max_chunk_frames;
+    p->ring = cfg->tr_context + 2 * max_chunk_frames;        // as a decode pool's: a call's oldest key and its newest never share a row
+    p->offset.assign(n_streams, 0);
+    p->ended.assign(n_streams, 0);
+    auto alloc = [&]() {
+        MCHK(p, hipMalloc((void**)&p->tab, (size_t)ENC_STREAM_TAB_WORDS * 4 + (size_t)ENC_STREAM_LTAB_LONGS * 8));
+        static_assert(ENC_STREAM_TAB_WORDS % 2 == 0, "the longs behind the table must be 8-byte aligned");
+        p->ltab = reinterpret_cast<long*>(p->tab + ENC_STREAM_TAB_WORDS);
+        const size_t tail_bytes = (size_t)n_streams * (cfg->kernel - 1) * 4;
+        MCHK(p, hipMalloc((void**)&p->wav_tail, tail_bytes));
+        MCHK(p, hipMemset(p->wav_tail, 0, tail_bytes));
+        // (ffn is also the RVQ score buffer, as in mimi_create)
+        return ladder_alloc(p, p->b, *cfg, n_streams, max_chunk_frames, p->ring, cfg->tr_ffn > cfg->codebook_size ? cfg->tr_ffn : cfg->codebook_size, true);
+    };
+    const int rc = alloc();
+    if (rc) { g_mimi_err = p->err; mimi_enc_pool_destroy(p); return rc; }
+    *out = p;
+    return 0;
+}
+
+extern "C" void mimi_enc_pool_destroy(mimi_enc_pool p) {
+    if (!p) return;
+    ladder_free(p->b);
+    (void)hipFree(p->tab);
+    (void)hipFree(p->wav_tail);
+    delete p;
+}
+
+extern "C" const char* mimi_enc_pool_last_error(mimi_enc_pool p) { return p ? p->err.c_str() : g_mimi_err.c_str(); }
+
+extern "C" int mimi_enc_pool_reset(mimi_enc_pool p, const int32_t* streams, int n, void* stream) {
+    if (!p) return fail(p, "mimi_enc_pool_reset: null pool");
+    PoolIds ids;
+    if (!streams || n < 1 || n > p->n_streams) return fail(p, "mimi_enc_pool_reset: stream list: need 1 .. n_streams ids");
+    bool seen[MIMI_ENC_POOL_MAX_STREAMS] = {};
+    for (int i = 0; i < n; ++i) {
+        if (streams[i] < 0 || streams[i] >= p->n_streams) return fail(p, "mimi_enc_pool_reset: stream id outside [0, n_streams)");
+        if (seen[streams[i]]) return fail(p, "mimi_enc_pool_reset: duplicate stream id in one call");
+        seen[streams[i]] = true;
+        ids.sid[i] = streams[i]; ids.off[i] = 0;
+    }
+    ids.n = n;
+    // every history row and the sample tail to zero: the whole-clip encode's left padding.  (The rings need no clearing, as in a decode pool.)
+    PoolRegions z = hist_regions(p->b, 0);
+    z.base[z.count] = p->wav_tail; z.hist[z.count] = p->cfg.kernel - 1; z.C[z.count] = 1; z.seg[z.count] = p->cfg.kernel - 1; z.T[z.count] = 0; ++z.count;
+    hipLaunchKernelGGL(k_pool_zero_hist, dim3(8, n, z.count), dim3(256), 0, (hipStream_t)stream, z, ids);
+    MCHK(p, hipGetLastError());
+    for (int i = 0; i < n; ++i) { p->offset[ids.sid[i]] = 0; p->ended[ids.sid[i]] = 0; }
+    return 0;
+}
+
+extern "C" int mimi_enc_pool_encode(mimi_enc_pool p, const int32_t* streams, const long* wav_off, const long* n_samples, int n, const float* wav,
+                                    int32_t* codes, void* stream) {
+    if (!p) return fail(p, "mimi_enc_pool_encode: null pool");
+    const MimiConfig& c = p->cfg;
+    const MimiWeights& w = p->w;
+    EncStreamHeader hdr;
+    EncStreamSegs sg;
+    if (const char* bad = enc_stream_segs_build(streams, wav_off, n_samples, n, wav, codes, p->n_streams, p->max_chunk, p->offset.data(), p->ended.data(),
+                                                c.ratios, c.n_stages, &hdr, &sg)) {
+        p->err = std::string("mimi_enc_pool_encode: ") + bad;
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    Ladder& b = p->b;
+    const int d = c.hidden, S = c.n_stages, F = sg.F;
+    const int* tab = p->tab;
+    hipLaunchKernelGGL(k_enc_stream_plan, dim3(1), dim3(256), 0, st, hdr, p->tab, p->ltab);
+    // first convolution into the streams' level-0 segments, then the sample tails move on
+    int R = (int)enc_level_rate(c.ratios, S, 0), C = c.n_filters;          // rows per frame and channels at the current level
+    {
+        const SegBuf& x0 = b.u(S - 1);
+        const long tot = (long)F * R * C;
+        hipLaunchKernelGGL(k_enc_stream_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, (long)F * R, R, c.kernel, C, w.enc_conv_in_w,
+                           w.enc_conv_in_b, tab, p->ltab, p->wav_tail, x0.row0(), x0.seg());
+        hipLaunchKernelGGL(k_enc_stream_tail, dim3(1), dim3(256), 0, st, wav, n, c.kernel - 1, tab, p->ltab, p->wav_tail);
+        MCHK(p, hipGetLastError());
+    }
+    // Every product below runs over ALL the call's rows at its level, frame-aligned (R rows per frame).  Those whose taps stay inside
+    // [-hist, own row] are a decode pool's ragged products; the strided convolutions and the downsample also reach FORWARD, up to the end of
+    // the segment's rows, where the last partial frame of a stream has the whole-clip encode's right padding (seg_edges).
+    for (int j = 0; j < S; ++j) {
+        const int bi = S - 1 - j;
+        const MimiConv &r1 = w.enc_res1[j], &r2 = w.enc_res2[j], &dn = w.enc_down[j];
+        const SegBuf &u = b.u(bi), &xj = b.xj(bi), &nxt = (j + 1 < S) ? b.u(bi - 1) : b.s0;
+        MCHK(p, gemm(st, conv(u.row0(), C, (long)F * R, r1, b.r1[bi], r1.c_out).elu().seg({R, u.seg(), R, 0, 1, 0, tab, true})));
+        MCHK(p, gemm(st, conv(b.r1[bi], r1.c_out, (long)F * R, r2, xj.row0(), C).elu().residual(u.row0(), C).seg({R, R, xj.seg(), u.seg(), 2 | 4, 0, tab, true})));
+        const int r = dn.taps / 2;
+        const int Rn = R / r;
+        MCHK(p, gemm(st, conv(xj.row0(), C, (long)F * Rn, dn, nxt.row0(), dn.c_out).taps_at(-r, 1).stride(r).elu().seg_edges(1, xj.hist, j)
+                             .seg({Rn, xj.seg(), nxt.seg(), 0, 1 | 2, 0, tab, true})));
+        R = Rn; C = dn.c_out;
+    }
+    MCHK(p, gemm(st, conv(b.s0.row0(), C, 2L * F, w.enc_conv_out, b.tok, d).elu().seg({2, b.s0.seg(), 2, 0, 1, 0, tab, true})));
+    // encoder transformer on the streams' K/V rings -> a0 segments.  No K split, as in mimi_encode.
+    TrPass tp{w.enc_tr, 2L * F};
+    tp.lin2_ksplit = false;
+    tp.tab = tab; tp.T2 = 2; tp.ring = p->ring; tp.ragged = true;
+    if (int rc = transformer(p, c, w, b, tp, st)) return rc;
+    // stride-2 downsample, taps at rows 2t - 2 .. 2t + 1 -> rvq [F][d] (dense)
+    const MimiConv down = {w.downsample, nullptr, d, d, 4, 1};
+    MCHK(p, gemm(st, conv(b.a0.row0(), d, F, down, b.rvq.row0(), d).taps_at(-2, 1).stride(2).seg_edges(2, b.a0.hist, S).seg({1, b.a0.seg(), 1, 0, 1, 0, tab, true})));
+    // split RVQ, per row over the call's F frames
+    const int cd = c.codebook_dim;
+    float *res_first = b.ln, *res_rest = b.q;       // [F][cd]
+    MCHK(p, gemm(st, linear(b.rvq.row0(), d, F, w.in_proj_first, d, cd, res_first, cd)));
+    MCHK(p, gemm(st, linear(b.rvq.row0(), d, F, w.in_proj_rest, d, cd, res_rest, cd)));
+    for (int k = 0; k < c.n_codebooks; ++k) {
+        float* res = k < c.n_semantic ? res_first : res_rest;
+        const float* book = w.codebooks + (long)k * c.codebook_size * cd;
+        MCHK(p, gemm(st, linear(res, cd, F, book, cd, c.codebook_size, b.ffn, c.codebook_size)));
+        hipLaunchKernelGGL(k_rvq_pick, dim3((unsigned)F), dim3(256), 0, st, b.ffn, c.codebook_size, w.codebook_sqnorm + (long)k * c.codebook_size, book, cd,
+                           res, codes + (long)k * F, 1L);
+        MCHK(p, hipGetLastError());
+    }
+    // every buffer's history slides by its stream's chunk.  (A stream that ended slides rows nobody reads: its reset zeroes them.)
+    const PoolRegions z = hist_regions(b, 1);
+    int maxC = 0;
+    for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
+    hipLaunchKernelGGL(k_pool_slide<true>, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
+    MCHK(p, hipGetLastError());
+    for (int i = 0; i < n; ++i) { p->offset[hdr.sid[i]] += 2 * sg.T[i]; p->ended[hdr.sid[i]] = sg.ends[i]; }
     return 0;
 }

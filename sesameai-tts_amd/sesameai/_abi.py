@@ -126,6 +126,11 @@ MIMI_SIGNATURES = {
     "mimi_pool_reset": (_i, [_vp, _vp, _i, _vp]),
     "mimi_pool_decode": (_i, [_vp, _vp, _i, _vp, _i, _l, _l, _l, _vp, _vp]),
     "mimi_pool_decode_ragged": (_i, [_vp, _vp, _vp, _i, _vp, _l, _l, _l, _vp, _vp]),
+    "mimi_enc_pool_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "mimi_enc_pool_destroy": (None, [_vp]),
+    "mimi_enc_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_enc_pool_reset": (_i, [_vp, _vp, _i, _vp]),
+    "mimi_enc_pool_encode": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _i, _vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in list(SIGNATURES.items()) + list(MIMI_SIGNATURES.items()):

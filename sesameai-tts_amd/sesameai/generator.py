@@ -200,6 +200,15 @@ class Generator:
         toks.append(t); masks.append(m)
         return torch.cat(toks, 0).long().to(self.device), torch.cat(masks, 0).bool().to(self.device)
 
+    def open_turn_streams(self, n: int, chunk_frames: int = 10):
+        """``n`` spoken turns encoded while they are spoken (sesameai/turns.py): ``feed`` / ``pump`` as the microphones deliver, then
+        ``finish(sid, speaker, text)`` gives the ``Segment`` of the turn, its codes bit for bit those of ``Segment(audio=the turn)``."""
+        from .turns import TurnStreams
+        tok = self._audio_tokenizer
+        if tok is None or not hasattr(tok, "open_encode_streams"):
+            raise RuntimeError("no Mimi encoder with encode streams available: pass Segment.audio_codes")
+        return TurnStreams(tok.open_encode_streams(n, max_chunk_frames=chunk_frames), tok.args.hop, chunk_frames)
+
     # -- prefix store: a voice prompt's K/V computed once, copied into any slot ----------------------
     def _store(self) -> list:
         """[(tokens (P,33) zeroed where masked, mask (P,33), handle)] of the registered prefixes.  The list lives on the model:

@@ -432,6 +432,13 @@ class MimiCodec:
         of streams in it); shares this codec's device weights.  See ``MimiStreamPool``."""
         return MimiStreamPool(self, n, max_chunk_frames)
 
+    def open_encode_streams(self, n: int, max_chunk_frames: int = 10) -> "MimiEncodeStreamPool":
+        """A pool of ``n`` stateful ENCODE streams that are fed together (one launch chain per call, whatever the number of streams
+        and their chunk lengths); shares this codec's device weights.  See ``MimiEncodeStreamPool``."""
+        if not self.has_encoder:
+            raise RuntimeError("this MimiCodec was built without encoder weights; pass Segment.audio_codes instead")
+        return MimiEncodeStreamPool(self, n, max_chunk_frames)
+
     def __del__(self):
         try:
             if self._h:
@@ -517,5 +524,71 @@ class MimiStreamPool:
         try:
             if self._h:
                 lib.mimi_pool_destroy(self._h)
+        except Exception:
+            pass
+
+
+class MimiEncodeStreamPool:
+    """``n`` independent stateful Mimi ENCODE streams (include/mimi_hip.h, mimi_enc_pool_*): stream ``i`` keeps the left context of every
+    convolution of the encoder, its K/V ring and its token offset, and runs for any number of frames.  ``encode(ids, wavs)`` feeds the
+    listed streams their new samples, a different number each, in ONE launch chain.  A stream's codes, concatenated over its calls, are
+    bit for bit ``MimiCodec.encode`` of its concatenated samples, whatever the chunk schedule, the company in the call and the place in the
+    list.  A chunk that is no whole number of frames ENDS its stream: the partial last frame is encoded as the whole-clip encode does, and
+    the stream is refused until ``reset``.  Streams start reset."""
+
+    def __init__(self, codec: MimiCodec, n: int, max_chunk_frames: int = 10):
+        self.codec = codec                        # keeps the device weights alive
+        self.n_streams, self.max_chunk_frames = int(n), int(max_chunk_frames)
+        self._ended = [False] * self.n_streams
+        self._h = C.c_void_p(None)
+        cfg, w = codec._cfg_w
+        with torch.cuda.device(codec.device):
+            rc = lib.mimi_enc_pool_create(C.byref(cfg), C.byref(w), self.n_streams, self.max_chunk_frames, C.byref(self._h))
+        if rc != 0:
+            raise _abi.CsmError(rc, (lib.mimi_enc_pool_last_error(None) or b"").decode())
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise _abi.CsmError(rc, (lib.mimi_enc_pool_last_error(self._h) or b"").decode())
+
+    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
+        """Start the listed streams (default: all) afresh."""
+        ids = [int(i) for i in (range(self.n_streams) if ids is None else ids)]
+        self._check(lib.mimi_enc_pool_reset(self._h, (C.c_int32 * len(ids))(*ids), len(ids), _stream()))
+        for i in ids:
+            self._ended[i] = False
+
+    def ended(self, sid: int) -> bool:
+        """Whether the stream took a partial last frame and waits for its ``reset``."""
+        return self._ended[int(sid)]
+
+    @torch.inference_mode()
+    def encode(self, ids: Sequence[int], wavs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """ids: n distinct stream ids; wavs[i]: (n_i,) fp32 @ 24 kHz, CPU or device, the new samples of stream ids[i] (at most
+        ``max_chunk_frames`` frames) -> one (32, ceil(n_i / hop)) int64 tensor per stream."""
+        ids = [int(i) for i in ids]
+        n = len(ids)
+        assert len(wavs) == n, "one chunk per id"
+        assert all(w.dim() == 1 for w in wavs), "every chunk must be (n,)"
+        dev, hop = self.codec.device, self.codec.args.hop
+        lens = [int(w.shape[0]) for w in wavs]
+        frames = [-(-x // hop) for x in lens]
+        offs = [sum(lens[:k]) for k in range(n)]
+        packed = torch.cat([w.to(device=dev, dtype=torch.float32) for w in wavs]) if n else torch.zeros(1, device=dev)    # one device buffer, as _encode_call
+        if packed.numel() == 0:
+            packed = torch.zeros(1, device=dev)
+        F = max(sum(f for f in frames if f > 0), 1)
+        codes = torch.empty(self.codec.args.num_codebooks, F, dtype=torch.int32, device=dev)
+        m = max(n, 1)
+        self._check(lib.mimi_enc_pool_encode(self._h, (C.c_int32 * m)(*ids), (C.c_long * m)(*offs), (C.c_long * m)(*lens), n, packed.data_ptr(),
+                                             codes.data_ptr(), _stream()))
+        for i, x in zip(ids, lens):
+            self._ended[i] = x % hop != 0
+        return list(codes.long().split(frames, dim=1))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib.mimi_enc_pool_destroy(self._h)
         except Exception:
             pass
