@@ -30,6 +30,7 @@ extern "C" {
 #define CSM_E_HIP        -2   /* a HIP runtime call failed                              */
 #define CSM_E_STATE      -3   /* call order violated (e.g. frame step before prefill)   */
 #define CSM_E_TOO_LONG   -4   /* position would exceed max_seq (generator.py:276-281)   */
+#define CSM_E_NO_PAGES   -5   /* the session store's pool is too short for this save    */
 
 #define CSM_MAX_LAYERS   32
 
@@ -84,6 +85,7 @@ typedef struct CsmWeights {
 
 typedef struct CsmModel* csm_handle;
 typedef struct CsmPrefix* csm_prefix;   /* a K/V snapshot of a prompt prefix (csm_prefix_capture) */
+typedef struct CsmSession* csm_session; /* a conversation's K/V in pages of the handle's session store (csm_session_open) */
 
 /* Model(config) + setup_caches(max_batch) (models.py:107-130): allocates KV caches
  * [L][B][KV][max_seq][hd] (backbone) / [L][B][KV][n_codebooks][hd] (decoder) and workspaces.
@@ -265,6 +267,50 @@ size_t csm_prefix_bytes(csm_prefix prefix);
 int    csm_prefix_read(csm_prefix prefix, void* host_buf, size_t bytes, void* stream);
 void   csm_prefix_destroy(csm_prefix prefix);
 
+/* Session store: a conversation's backbone K/V carried from turn to turn.  A spoken dialogue's prompt is its whole history -- the voice
+ * prompt, every earlier turn, the audio generated a second ago -- and all of its rows but the few dozen of the new turn were in the slot's
+ * cache when the last reply ended.  A prefix snapshot (above) could keep them, but every capture allocates a dense block, synchronises and
+ * copies all rows again: right once per voice, wrong once per turn between two frame steps.  A SESSION keeps the rows in fixed-size pages
+ * of one pool that the handle allocates once: a page holds page_rows rows of every layer's K and V of every kv head
+ * ([layer][K|V][kv head][page_rows][hd] bf16; 2 MB at CSM-1B with 64 rows).  At the end of a turn only the new rows are appended; at the
+ * start of the next the pages are gathered into whichever slot the request gets and only the rows after them are prefilled.
+ * ORDERING: csm_session_save, csm_session_load and csm_session_truncate allocate nothing, copy nothing from the host and never
+ * synchronise (the page numbers travel in kernel arguments into a device table that the load reads).  They are meant for the frame
+ * loop's stream, between frame steps, and that ONE stream is what makes page reuse safe: a page that a truncate or close gives back may
+ * be handed to the next save at once, because every load that still reads it was enqueued earlier on the same stream.  Calls on a second
+ * stream need the caller's own events between them.
+ *   csm_session_store_create: the pool of n_pages pages of page_rows rows (1 <= page_rows <= max_seq), once per handle (CSM_E_STATE the
+ *                       second time; CSM_E_HIP, and no store, when the allocation fails).  Up to n_pages + 32 sessions can be open.
+ *   csm_session_open:   a new, empty session.
+ *   csm_session_save:   appends rows [csm_session_rows(s), rows) of `slot`'s caches, all layers; the session then holds `rows` rows.  The
+ *                       rows must have been written (rows <= the slot's position: the CALLER's knowledge -- reading the position would
+ *                       synchronise).  CSM_E_NO_PAGES when the pool has too few free pages: a code of its own, so that the host can
+ *                       truncate or close another session and call again.
+ *   csm_session_load:   writes the rows [0, rows_i) of n <= 32 sessions into the slots slots[i] (host arrays) in ONE launch -- sessions of
+ *                       different lengths resume together in one refill group.  Rows at and beyond rows_i of a slot are not written;
+ *                       positions and every other state of the slots are untouched: the caller runs the suffix at its true positions
+ *                       (pos starts at rows_i), exactly as after csm_prefix_apply, and enqueues the load IMMEDIATELY before that call.
+ *   csm_session_truncate: the session keeps its first `rows` rows (barge-in: the listener heard only part of the last reply); whole
+ *                       pages beyond the new end return to the pool.  Host bookkeeping only.
+ *   csm_session_rows / csm_session_pages: rows held / pages owned (0 for NULL or after csm_destroy of the handle).
+ *   csm_session_read:   the session's rows, dense in csm_prefix_read's layout [layer][K|V][kv head][rows][hd] (bytes must match;
+ *                       synchronises).  For tests.
+ *   csm_session_close:  returns the pages and frees the object.
+ * Refused with nothing enqueued and the session unchanged: rows below the session's row count or >= max_seq (CSM_E_INVALID); a slot
+ * outside the batch or listed twice in one load (CSM_E_INVALID); a slot whose refill beside the loop is running (CSM_E_STATE, the
+ * predicate of the prefix calls); a session of another handle or a closed one (CSM_E_INVALID); a pool too short (CSM_E_NO_PAGES).
+ * csm_destroy releases the pool; session objects still alive can then only be closed.  csm_describe reports
+ * `session_store=<n> sessions, <used>/<total> pages`.                                                                                  */
+int  csm_session_store_create(csm_handle h, int n_pages, int page_rows);
+int  csm_session_open(csm_handle h, csm_session* out);
+int  csm_session_save(csm_handle h, csm_session s, int slot, int rows, void* stream);
+int  csm_session_load(csm_handle h, const csm_session* ss, const int32_t* slots /*host*/, int n, void* stream);
+int  csm_session_truncate(csm_session s, int rows);
+int  csm_session_rows(csm_session s);
+int  csm_session_pages(csm_session s);
+int  csm_session_read(csm_session s, void* host_buf, size_t bytes, void* stream);
+void csm_session_close(csm_session s);
+
 /* Start-up weight broadcast (SURVEY.md 8b's csm_broadcast_weights; 8e: "one RCCL ncclBroadcast of the packed weight blob at start-up
  * over xGMI ... no per-step collective").  The reference has no counterpart (it is single-GPU: every process downloads its own
  * checkpoint, sesameai/generator.py:330-346); in the replica layout rank `root` holds the weights and every other
@@ -279,7 +325,7 @@ void   csm_prefix_destroy(csm_prefix prefix);
 int csm_broadcast_weights(void* dev_blob, size_t bytes, void* rccl_comm, int root, void* stream);
 
 /* What this handle runs, as one line of text: weight stream, the kernels of a batch-1 / batched backbone step, of the depth decoder and of
- * prompts, the frame-graph cache, the live prefixes of the prefix store (number, total bytes), and every CSM_* / MIMI_* switch set in the environment.  Writes at most n - 1 characters + NUL into buf (may
+ * prompts, the frame-graph cache, the live prefixes of the prefix store (number, total bytes), the session store (open sessions, pages used / total), and every CSM_* / MIMI_* switch set in the environment.  Writes at most n - 1 characters + NUL into buf (may
  * be NULL) and returns the length the whole text needs.  The reference has no counterpart (it has one eager path); bench.py records it with
  * every number it prints (config.paths).                                                                                              */
 int csm_describe(csm_handle h, char* buf, int n);

@@ -30,8 +30,9 @@
 #include "switches.h"
 #include "stack_plan.h"
 #include "dev_pool.h"
+#include "session_pages.h"
 
-#define CSM_FRAME_GRAPHS 4     // captured frame steps kept per handle
+#define CSM_FRAME_GRAPHS 4    // captured frame steps kept per handle
 #define CSM_REFILL_SALT 0x9E3779B97F4A7C15ull      /* Philox key domain of slot refills (csm_seed) */
 
 static thread_local std::string g_create_err;
@@ -148,7 +149,19 @@ struct CsmModel {
     int graph_captures = 0;             // hipGraphInstantiate calls since csm_create (csm_debug_graph_captures)
     hipStream_t cap_stream = nullptr;   // capture happens on an internal stream: the caller's may be the legacy NULL stream
     std::vector<struct CsmPrefix*> prefixes;     // live K/V snapshots captured from this handle (csm_prefix_capture); orphaned by csm_destroy
+    // session store (csm_session_store_create): conversations' backbone K/V in fixed-size pages of ONE pool allocation
+    SessionPages* sess = nullptr;       // the bookkeeping (session_pages.h); nullptr: no store
+    bf16_t* sess_pool = nullptr;        // [n_pages][layer][K|V][kv head][page_rows][hd]
+    int* sess_tab = nullptr;            // [max sessions][sess_tab_stride] device page table: row = session id, entry k = the session's logical page k
+    int sess_tab_stride = 0;            //   (written by k_session_save from its kernel arguments, read by k_session_load: no host-to-device copy)
+    std::vector<struct CsmSession*> sessions;    // open session objects of this handle; orphaned by csm_destroy
     std::string err;
+};
+
+// One conversation's place in the handle's session store: all state is in m->sess under `id`.
+struct CsmSession {
+    CsmModel* owner;                    // nullptr once the handle is destroyed: the pages are gone with it
+    int id;
 };
 
 // A voice prompt's backbone K/V rows [0, rows) of every layer, dense: [layer][K|V][kv head][rows][hd] bf16 (csm_prefix_capture).
@@ -1309,6 +1322,8 @@ extern "C" void csm_destroy(csm_handle m) {
     drop_frame_graphs(m);
     if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
     for (CsmPrefix* p : m->prefixes) { (void)hipFree(p->data); p->data = nullptr; p->owner = nullptr; }      // (the caller still destroys the objects)
+    for (CsmSession* s : m->sessions) s->owner = nullptr;                                                     // (likewise: they can only be closed now)
+    delete m->sess;
     m->pool.release_all();
     delete m;
 }
@@ -1958,6 +1973,201 @@ extern "C" void csm_prefix_destroy(csm_prefix p) {
     delete p;
 }
 
+// ---------------------------------------------------------------------------------------
+// session store: a conversation's backbone K/V carried from turn to turn.  The prefix store snapshots a slot into a dense
+// allocation of its own -- right once per voice, wrong once per turn between two frame steps (an allocation, a synchronisation, every row
+// copied again).  Here the rows live in fixed-size pages of ONE pool allocated at csm_session_store_create: a page holds page_rows rows
+// of each of the L * 2 * KV runs of a slot's cache, [run][page_rows][hd] -- at CSM-1B with 64 rows 8 KB per run, 2 MB per page.  A save
+// appends only the rows the session does not hold; a load gathers the pages of up to 32 sessions into as many slots in one launch.
+// The page lists reach the kernels through a device table [session id][logical page] that the SAVE writes from its kernel arguments
+// (k_session_tab, <= 256 entries per launch) ahead of the copy; the load passes (session id, slot, rows) per pair in its arguments and
+// reads the table.  So save, load and truncate allocate nothing, copy nothing from the host and never synchronise, and a page that a
+// truncate or close gives back may go to the next save at once: everything that still reads it was enqueued earlier on the one stream.
+// Both copies are k_prefix_copy's: 16 B per lane, four independent loads in flight per lane before the first store, indexed by the
+// position in the slot's run (each lane finds its own page: neighbouring lanes share it, the table entry comes from the cache).
+// ---------------------------------------------------------------------------------------
+#define SESS_VECS_PER_BLOCK (256 * 4)
+#define SESS_TAB_PER_LAUNCH 256
+#define SESS_MAX_LOAD 32
+struct SessTabEntries { int page[SESS_TAB_PER_LAUNCH]; };
+struct SessLoadPairs { int id[SESS_MAX_LOAD], slot[SESS_MAX_LOAD], rows[SESS_MAX_LOAD]; };
+struct SessGeom { long layer_stride, slot_stride, head_stride; int kv_heads, n_runs, page_rows, hv; };     // hv: 16-byte pieces per row (hd / 8)
+
+__global__ __launch_bounds__(SESS_TAB_PER_LAUNCH) void k_session_tab(int* tab_row, int first, int n, SessTabEntries e) {
+    if ((int)threadIdx.x < n) tab_row[first + threadIdx.x] = e.page[threadIdx.x];
+}
+
+// pieces [i0 + j * 256 (j < 4)) below `end` of run `run` of one slot <-> the session's pages; i counts 16-byte pieces from the run's row 0
+template <bool LOAD>
+__device__ __forceinline__ void session_copy(uint4* c, uint4* pool, const int* tab_row, const SessGeom& g, int run, long i0, long end) {
+    const long page_vecs = (long)g.page_rows * g.hv;
+    uint4* pp[4];
+    uint4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long i = i0 + j * 256;
+        if (i < end) {
+            const long lp = i / page_vecs;
+            pp[j] = pool + ((long)tab_row[lp] * g.n_runs + run) * page_vecs + (i - lp * page_vecs);
+            v[j] = LOAD ? *pp[j] : c[i];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long i = i0 + j * 256;
+        if (i < end) { if (LOAD) c[i] = v[j]; else *pp[j] = v[j]; }
+    }
+}
+
+__device__ __forceinline__ uint4* session_run(bf16_t* kc, bf16_t* vc, const SessGeom& g, int run, long slot) {
+    const int kvh = run % g.kv_heads, which = (run / g.kv_heads) & 1, l = run / (2 * g.kv_heads);
+    return (uint4*)((which ? vc : kc) + (long)l * g.layer_stride + slot * g.slot_stride + (long)kvh * g.head_stride);
+}
+
+// slot rows [from, to) -> the session's pages.  grid = (pieces of the range, run)
+__global__ __launch_bounds__(256) void k_session_save(bf16_t* kc, bf16_t* vc, bf16_t* pool, const int* tab_row, SessGeom g, int slot, int from, int to) {
+    const int run = blockIdx.y;
+    session_copy<false>(session_run(kc, vc, g, run, slot), (uint4*)pool, tab_row, g, run,
+                        (long)from * g.hv + (long)blockIdx.x * SESS_VECS_PER_BLOCK + threadIdx.x, (long)to * g.hv);
+}
+
+// the pages of pair z's session -> rows [0, rows[z]) of slot[z], all pairs in one launch.  grid = (pieces of the longest, run, pair)
+__global__ __launch_bounds__(256) void k_session_load(bf16_t* kc, bf16_t* vc, bf16_t* pool, const int* tab, int tab_stride, SessGeom g, SessLoadPairs a) {
+    const int run = blockIdx.y, z = blockIdx.z;
+    const long end = (long)a.rows[z] * g.hv, b0 = (long)blockIdx.x * SESS_VECS_PER_BLOCK;
+    if (b0 >= end) return;                                      // (a shorter session of the group)
+    session_copy<true>(session_run(kc, vc, g, run, a.slot[z]), (uint4*)pool, tab + (long)a.id[z] * tab_stride, g, run, b0 + threadIdx.x, end);
+}
+
+static SessGeom session_geom(const CsmModel* m) {
+    const Stack& S = m->bb;
+    SessGeom g;
+    g.head_stride = (long)S.cache_len * S.hd; g.slot_stride = (long)S.d.n_kv_heads * g.head_stride; g.layer_stride = S.layer_stride;
+    g.kv_heads = S.d.n_kv_heads; g.n_runs = S.d.n_layers * 2 * S.d.n_kv_heads; g.page_rows = m->sess->page_rows(); g.hv = S.hd / 8;
+    return g;
+}
+
+static bool session_live(const CsmModel* m, const CsmSession* s) {     // by address: a closed session's object is gone and is never read
+    return s && std::find(m->sessions.begin(), m->sessions.end(), s) != m->sessions.end();
+}
+
+extern "C" int csm_session_store_create(csm_handle m, int n_pages, int page_rows) {
+    if (!m) return fail(m, CSM_E_INVALID, "csm_session_store_create: null handle");
+    if (m->sess) return fail(m, CSM_E_STATE, "csm_session_store_create: this handle has a session store already");
+    const Stack& S = m->bb;
+    if (n_pages < 1 || page_rows < 1 || page_rows > S.cache_len || S.hd % 8 != 0) return fail(m, CSM_E_INVALID, "csm_session_store_create: n_pages >= 1, 1 <= page_rows <= max_seq, head_dim % 8 == 0 required");
+    const size_t page_bytes = (size_t)S.d.n_layers * 2 * S.d.n_kv_heads * page_rows * S.hd * 2;
+    const int stride = (S.cache_len + page_rows - 1) / page_rows, max_sessions = n_pages + 32;
+    const size_t mark = m->pool.mark();
+    hipError_t e = dev_get(m, &m->sess_pool, page_bytes * (size_t)n_pages);
+    if (e == hipSuccess) e = dev_get(m, &m->sess_tab, (size_t)max_sessions * stride * sizeof(int), 0);
+    if (e != hipSuccess) { m->pool.release_to(mark); m->sess_pool = nullptr; m->sess_tab = nullptr; HIPCHK(m, e); }
+    m->sess_tab_stride = stride;
+    m->sess = new SessionPages(n_pages, page_rows, max_sessions);
+    return CSM_OK;
+}
+
+extern "C" int csm_session_open(csm_handle m, csm_session* out) {
+    if (!m || !out) return fail(m, CSM_E_INVALID, "csm_session_open: null argument");
+    if (!m->sess) return fail(m, CSM_E_STATE, "csm_session_open: no session store (csm_session_store_create)");
+    const int id = m->sess->open();
+    if (id < 0) return fail(m, CSM_E_STATE, "csm_session_open: too many open sessions (pages + 32)");
+    CsmSession* s = new CsmSession{m, id};
+    m->sessions.push_back(s);
+    *out = s;
+    return CSM_OK;
+}
+
+extern "C" int csm_session_save(csm_handle m, csm_session s, int slot, int rows, void* stream) {
+    if (!m || !m->sess) return fail(m, m ? CSM_E_STATE : CSM_E_INVALID, "csm_session_save: null handle or no session store");
+    if (!session_live(m, s)) return fail(m, CSM_E_INVALID, "csm_session_save: not an open session of this handle");
+    const int from = m->sess->rows(s->id);
+    if (slot < 0 || slot >= m->max_batch || rows < from || rows >= m->cfg.backbone.max_seq)
+        return fail(m, CSM_E_INVALID, "csm_session_save: slot outside the batch, rows below the session's row count, or rows >= max_seq");
+    if (slot_refilling(m, slot)) return fail(m, CSM_E_STATE, "csm_session_save: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+    if (rows == from) return CSM_OK;
+    const int had_pages = m->sess->pages(s->id);
+    if (!m->sess->grow_to(s->id, rows)) return fail(m, CSM_E_NO_PAGES, "csm_session_save: the pool has too few free pages (truncate or close a session and call again)");
+    hipStream_t st = (hipStream_t)stream;
+    int* tab_row = m->sess_tab + (long)s->id * m->sess_tab_stride;
+    hipError_t e = hipSuccess;
+    for (int first = had_pages; first < m->sess->pages(s->id) && e == hipSuccess; first += SESS_TAB_PER_LAUNCH) {     // the new pages' table entries, ahead of the copy
+        SessTabEntries te;
+        const int n = std::min(m->sess->pages(s->id) - first, SESS_TAB_PER_LAUNCH);
+        for (int k = 0; k < n; ++k) te.page[k] = m->sess->page_at(s->id, first + k);
+        hipLaunchKernelGGL(k_session_tab, dim3(1), dim3(SESS_TAB_PER_LAUNCH), 0, st, tab_row, first, n, te);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        const SessGeom g = session_geom(m);
+        const long vecs = (long)(rows - from) * g.hv;
+        hipLaunchKernelGGL(k_session_save, dim3((unsigned)((vecs + SESS_VECS_PER_BLOCK - 1) / SESS_VECS_PER_BLOCK), (unsigned)g.n_runs), dim3(256), 0, st,
+                           m->bb.kc, m->bb.vc, m->sess_pool, (const int*)tab_row, g, slot, from, rows);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { (void)m->sess->truncate(s->id, from); HIPCHK(m, e); }
+    return CSM_OK;
+}
+
+extern "C" int csm_session_load(csm_handle m, const csm_session* ss, const int32_t* slots, int n, void* stream) {
+    if (!m || !m->sess) return fail(m, m ? CSM_E_STATE : CSM_E_INVALID, "csm_session_load: null handle or no session store");
+    if (!ss || !slots || n < 0 || n > SESS_MAX_LOAD) return fail(m, CSM_E_INVALID, "csm_session_load: null argument or n outside [0, 32]");
+    SessLoadPairs a;
+    int longest = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!session_live(m, ss[i])) return fail(m, CSM_E_INVALID, "csm_session_load: not an open session of this handle");
+        if (slots[i] < 0 || slots[i] >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_session_load: slot outside the batch");
+        for (int j = 0; j < i; ++j)
+            if (slots[j] == slots[i]) return fail(m, CSM_E_INVALID, "csm_session_load: a slot is listed twice");
+        if (slot_refilling(m, slots[i])) return fail(m, CSM_E_STATE, "csm_session_load: the slot's refill beside the frame loop is still running (csm_refill_advance)");
+        a.id[i] = ss[i]->id; a.slot[i] = slots[i]; a.rows[i] = m->sess->rows(ss[i]->id);
+        longest = std::max(longest, a.rows[i]);
+    }
+    if (longest == 0) return CSM_OK;
+    const SessGeom g = session_geom(m);
+    const long vecs = (long)longest * g.hv;
+    hipLaunchKernelGGL(k_session_load, dim3((unsigned)((vecs + SESS_VECS_PER_BLOCK - 1) / SESS_VECS_PER_BLOCK), (unsigned)g.n_runs, (unsigned)n), dim3(256), 0,
+                       (hipStream_t)stream, m->bb.kc, m->bb.vc, m->sess_pool, (const int*)m->sess_tab, m->sess_tab_stride, g, a);
+    HIPCHK(m, hipGetLastError());
+    return CSM_OK;
+}
+
+extern "C" int csm_session_truncate(csm_session s, int rows) {
+    if (!s || !s->owner) return fail(nullptr, CSM_E_INVALID, "csm_session_truncate: null session, or its handle has been destroyed");
+    if (!s->owner->sess->truncate(s->id, rows)) return fail(s->owner, CSM_E_INVALID, "csm_session_truncate: rows outside [0, the session's row count]");
+    return CSM_OK;
+}
+
+extern "C" int csm_session_rows(csm_session s) { return s && s->owner ? s->owner->sess->rows(s->id) : 0; }
+extern "C" int csm_session_pages(csm_session s) { return s && s->owner ? s->owner->sess->pages(s->id) : 0; }
+
+extern "C" int csm_session_read(csm_session s, void* host_buf, size_t bytes, void* stream) {
+    if (!s || !s->owner) return fail(nullptr, CSM_E_INVALID, "csm_session_read: null session, or its handle has been destroyed");
+    CsmModel* m = s->owner;
+    const SessGeom g = session_geom(m);
+    const int rows = m->sess->rows(s->id);
+    const size_t row_bytes = (size_t)g.hv * 16, page_run_bytes = row_bytes * g.page_rows;
+    if (bytes != row_bytes * rows * g.n_runs || (!host_buf && bytes)) return fail(m, CSM_E_INVALID, "csm_session_read: bytes != layers * 2 * kv heads * rows * head_dim * 2, or a null buffer");
+    std::vector<SessionCopy> plan;
+    (void)m->sess->plan(s->id, 0, rows, &plan);
+    for (const SessionCopy& c : plan)                       // one strided copy per page: the page's piece of every run
+        HIPCHK(m, hipMemcpy2DAsync((char*)host_buf + c.slot_row * row_bytes, row_bytes * rows,
+                                   (const char*)m->sess_pool + (size_t)c.page * g.n_runs * page_run_bytes + c.page_row * row_bytes, page_run_bytes,
+                                   c.rows * row_bytes, (size_t)g.n_runs, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(m, hipStreamSynchronize((hipStream_t)stream));
+    return CSM_OK;
+}
+
+extern "C" void csm_session_close(csm_session s) {
+    if (!s) return;
+    if (s->owner) {
+        s->owner->sess->close(s->id);
+        auto& v = s->owner->sessions;
+        v.erase(std::remove(v.begin(), v.end(), s), v.end());
+    }
+    delete s;
+}
+
 extern "C" int csm_num_frames(csm_handle m) { return m ? m->host_frames : 0; }
 
 extern "C" int csm_read_frames(csm_handle m, int B, int first, int n, int32_t* host_frames, int32_t* host_eos_at, void* stream) {
@@ -2073,6 +2283,8 @@ extern "C" int csm_describe(csm_handle m, char* buf, int n) {
     t += tmp;
     { size_t pb = 0; for (const CsmPrefix* p : m->prefixes) pb += p->bytes;
       snprintf(tmp, sizeof tmp, "; prefix_store=%d prefixes, %zu bytes", (int)m->prefixes.size(), pb); t += tmp; }
+    snprintf(tmp, sizeof tmp, "; session_store=%d sessions, %d/%d pages", m->sess ? m->sess->sessions() : 0, m->sess ? m->sess->pages_used() : 0, m->sess ? m->sess->pages_total() : 0);
+    t += tmp;
     { int ne = 0, ns = 0; for (unsigned char f : m->slot_tab_host) { ne += f & 1; ns += (f >> 1) & 1; }
       snprintf(tmp, sizeof tmp, "; slot_sampling=%d entries (%d with own seed)%s", ne, ns, m->slot_tab_used ? ", frame steps carry the table" : ""); t += tmp; }
     const std::string sw = set_switches(true);

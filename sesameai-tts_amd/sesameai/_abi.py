@@ -27,7 +27,7 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 
 CSM_MAX_LAYERS = 32
-ERRORS = {-1: "CSM_E_INVALID", -2: "CSM_E_HIP", -3: "CSM_E_STATE", -4: "CSM_E_TOO_LONG"}
+ERRORS = {-1: "CSM_E_INVALID", -2: "CSM_E_HIP", -3: "CSM_E_STATE", -4: "CSM_E_TOO_LONG", -5: "CSM_E_NO_PAGES"}
 
 
 class CsmLlamaDims(C.Structure):
@@ -89,6 +89,15 @@ SIGNATURES = {
     "csm_prefix_bytes": (C.c_size_t, [_vp]),
     "csm_prefix_read": (_i, [_vp, _vp, C.c_size_t, _vp]),
     "csm_prefix_destroy": (None, [_vp]),
+    "csm_session_store_create": (_i, [_vp, _i, _i]),
+    "csm_session_open": (_i, [_vp, C.POINTER(_vp)]),
+    "csm_session_save": (_i, [_vp, _vp, _i, _i, _vp]),
+    "csm_session_load": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "csm_session_truncate": (_i, [_vp, _i]),
+    "csm_session_rows": (_i, [_vp]),
+    "csm_session_pages": (_i, [_vp]),
+    "csm_session_read": (_i, [_vp, _vp, C.c_size_t, _vp]),
+    "csm_session_close": (None, [_vp]),
     "csm_broadcast_weights": (_i, [_vp, C.c_size_t, _vp, _i, _vp]),
     "csm_num_frames": (_i, [_vp]),
     "csm_read_frames": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),

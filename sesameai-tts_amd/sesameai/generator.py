@@ -19,6 +19,7 @@ import torch
 
 from .live_batch import SlotStreams, live_batch, per_prompt_sampling
 from .models import Model, ModelArgs, csm_1b_args
+from .sessions import Conversation, ConversationSet, check_sessions
 
 FRAME_MS = 80                     # generator.py:257
 MAX_SEQ_LEN = 2048                # generator.py:276
@@ -86,6 +87,7 @@ class Generator:
     refill_beside_the_loop = True              # refill a few layers per frame step where the model supports it (sesameai/live_batch.py) ...
     refill_row_layers = 600                    # ... about this many prompt-row x layer units per step
     _stream_pools: Optional[dict] = None       # {(slots, chunk frames): MimiStreamPool} of generate_many_stream, made on first use and kept
+    _conversations: Optional[ConversationSet] = None   # the sessions opened on this Generator (open_session), made on first use
 
     def __init__(self, model: Model, audio_tokenizer=None, text_tokenizer=None, max_batch_size: int = 1):
         self._model = model
@@ -250,10 +252,25 @@ class Generator:
         """Handles of the registered prefixes, oldest first."""
         return [e[2] for e in self._store()]
 
+    # -- conversation sessions: a dialogue's K/V carried from turn to turn (sesameai/sessions.py) -------
+    def open_session_store(self, pages: int, page_rows: int = 64) -> None:
+        """The model's pool of K/V pages for ``open_session`` (Model.open_session_store): ``pages`` pages of ``page_rows`` rows, 2 MB each
+        at CSM-1B with 64 rows; a 1,334-row history holds 21 of them.  Once per Generator."""
+        self._model.open_session_store(pages, page_rows)
+
+    def open_session(self) -> Conversation:
+        """A new conversation (sesameai/sessions.py ``Conversation``) for ``session=`` / ``sessions=``: every turn's call then lists only the
+        segments that are new since the last one, the history's K/V are loaded from the session's pages and only the new rows are
+        prefilled.  The results are those of the cold call with the whole history as its context, to bf16 rounding (see the module's
+        docstring); ``truncate_last`` covers barge-in, ``close`` returns the pages.  Needs ``open_session_store``."""
+        if self._conversations is None:
+            self._conversations = ConversationSet()
+        return self._conversations.new(self._model.open_session())
+
     # -- the frame loop -----------------------------------------------------------------------
     def _frame_blocks(self, prompt_tokens: torch.Tensor, prompt_mask: torch.Tensor, max_generation_len: int,
-                      temperature: float, topk: int, poll: int, gate: Optional["_FirstBlockGate"] = None
-                      ) -> PyGenerator[torch.Tensor, None, None]:
+                      temperature: float, topk: int, poll: int, gate: Optional["_FirstBlockGate"] = None,
+                      session: Optional[Conversation] = None) -> PyGenerator[torch.Tensor, None, None]:
         """Yields the generated frames in blocks [n][B][32] int32 (CPU) of about ``poll`` frames, cut at EOS for
         B == 1.  The NEXT block's frame steps are already enqueued on the GPU when a block is yielded, so whatever
         the consumer does with it (Mimi decode on another stream, playback) overlaps the language model.
@@ -263,16 +280,23 @@ class Generator:
         squeezing between frame steps whose persistent launches occupy every CU (first 10-frame chunk: 38.8 -> 31 ms) -- and
         the second block is queued when the consumer calls ``gate.release()`` (generate_stream: right after submitting the
         first decode, BEFORE the chunk goes to the user) or, at the latest, when it asks for the next block.  Without a gate
-        (generate_codes: nobody decodes between blocks) every block, the first included, is followed at once by the next."""
+        (generate_codes: nobody decodes between blocks) every block, the first included, is followed at once by the next.
+        ``session`` (B == 1; the prompt is the session's FULL prompt, ``Conversation.full_prompt``): the rows its pages hold are loaded into
+        slot 0 and only the rows after them run; when the last block has been read the slot's new rows are saved, before it is yielded."""
         B = prompt_tokens.shape[0]
         m = self._model
         m.reset_caches()
         self.last_eos_at = torch.full((B,), -1, dtype=torch.int32)
         if max_generation_len <= 0:
             return
-        m.prefill_prompt(prompt_tokens, prompt_mask)        # reuses the cached KV of a shared voice-prompt prefix
+        if session is not None and session.rows > 0:
+            m.load_sessions([session.device], [0])          # (slot 0 is nobody's cached prompt now) immediately before the suffix's prefill
+            m.prefill_prompt(prompt_tokens, prompt_mask, start=session.rows)
+        else:
+            m.prefill_prompt(prompt_tokens, prompt_mask)    # reuses the cached KV of a shared voice-prompt prefix
         m.depth(B, temperature, topk, commit=True)
         launched, delivered = 1, 0
+        kept: List[torch.Tensor] = []                       # a session's turn: every frame handed out, for its mirror
 
         def enqueue(want: int) -> int:
             n = max(min(want, max_generation_len - launched), 0)
@@ -304,6 +328,10 @@ class Generator:
                 if B == 1 and eos[0] >= 0:
                     fr = fr[: max(int(eos[0]) - delivered, 0)]
                 delivered = upto
+                if session is not None:
+                    kept.append(fr[:, 0])
+                    if done:                                                    # the last block has been read: the slot's new rows go to the pages
+                        session.turn_over(m, 0, prompt_tokens[0], prompt_mask[0], torch.cat(kept), max_generation_len, [session])
                 if fr.shape[0]:
                     yield fr
                 if done:
@@ -317,27 +345,39 @@ class Generator:
     @torch.inference_mode()
     def generate_codes(self, prompt_tokens: torch.Tensor, prompt_mask: torch.Tensor, max_generation_len: int,
                        temperature: float, topk: int, on_frames: Optional[Callable[[torch.Tensor], None]] = None,
-                       poll: Optional[int] = None) -> torch.Tensor:
+                       poll: Optional[int] = None, session: Optional[Conversation] = None) -> torch.Tensor:
         """prompt (S,33) or (B,S,33) -> frames [n][B][32] int32 (CPU), cut at each sequence's EOS
         for B == 1 (the reference is batch-1: generator.py:47).  For B > 1 all sequences run
-        ``max_generation_len`` frames unless every one hit EOS; the caller trims with ``last_eos_at``."""
+        ``max_generation_len`` frames unless every one hit EOS; the caller trims with ``last_eos_at``.
+        ``session`` (one sequence): the prompt holds only the rows that are NEW since the session's last turn (``open_session``)."""
         if prompt_tokens.dim() == 2:
             prompt_tokens, prompt_mask = prompt_tokens.unsqueeze(0), prompt_mask.unsqueeze(0)
+        if session is not None:
+            prompt_tokens, prompt_mask = self._session_prompt(session, prompt_tokens, prompt_mask)
         B, S, _ = prompt_tokens.shape
         max_context_len = MAX_SEQ_LEN - max_generation_len
         if S >= max_context_len:
             raise ValueError(f"Inputs too long, must be below max_seq_len - max_generation_len: {max_context_len}")
         blocks = []
-        for fr in self._frame_blocks(prompt_tokens, prompt_mask, max_generation_len, temperature, topk, poll or self._eos_poll):
+        for fr in self._frame_blocks(prompt_tokens, prompt_mask, max_generation_len, temperature, topk, poll or self._eos_poll, session=session):
             if on_frames is not None:
                 on_frames(fr)
             blocks.append(fr)
         return torch.cat(blocks) if blocks else torch.empty(0, B, 32, dtype=torch.int32)
 
+    @staticmethod
+    def _session_prompt(session: Conversation, tokens: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(1,S,33) new rows -> the session's full prompt (1,S',33)."""
+        if tokens.shape[0] != 1:
+            raise ValueError("session=: one sequence per call (sessions= of generate_many takes several)")
+        t, mk = session.full_prompt(tokens[0], mask[0])
+        return t.unsqueeze(0), mk.unsqueeze(0)
+
     @torch.inference_mode()
     def iter_codes_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                               temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
-                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1) -> PyGenerator[Tuple[int, torch.Tensor], None, None]:
+                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
+                              sessions: Optional[Sequence[Optional[Conversation]]] = None) -> PyGenerator[Tuple[int, torch.Tensor], None, None]:
         """Any number of prompts [(tokens (S_i,33), mask (S_i,33)), ...] of any lengths through a batch of ``max_batch_size``
         slots that is kept FULL: an utterance that reaches its all-zero EOS frame (generator.py:285) or the length limit is
         retired and its slot re-prefilled with the next prompt (Model.refill_slot) while the other slots keep generating --
@@ -346,9 +386,13 @@ class Generator:
         all prompts or one per prompt), so a long run hands its results out as it
         goes.  ``temperature`` / ``topk``: one value for all prompts or one per prompt; ``seed``: one optional int per prompt -- a prompt with
         a seed of its own yields the same frames whichever slot it takes and whatever the batch did before (Model.set_slot_sampling).  There is no limit on the total number of frame steps: the engine's frame history is a ring (include/csm_hip.h,
-        csm_read_frames) and every block of ``poll`` steps is read before the next one is launched."""
+        csm_read_frames) and every block of ``poll`` steps is read before the next one is launched.
+        ``sessions``: one ``Conversation`` or None per prompt, at most one prompt per session (else ValueError): such a prompt holds only the
+        rows that are NEW since its session's last turn; the pages of all sessions of a refill group are loaded by one call immediately
+        before the group's refill, and a finished turn's rows are saved between frame steps (``open_session``).  None: today's calls exactly."""
         parts: dict = {}
-        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed, refill_group=refill_group):
+        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed, refill_group=refill_group,
+                                                  **({} if sessions is None else {"sessions": sessions})):
             for i, _slot, frames, last in block or ():
                 parts.setdefault(i, []).append(frames)
                 if last:
@@ -359,7 +403,7 @@ class Generator:
     def _iter_blocks_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                                 temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
                                 seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
-                                first_chunk_frames: Optional[int] = None):
+                                first_chunk_frames: Optional[int] = None, sessions: Optional[Sequence[Optional[Conversation]]] = None):
         """The incremental form of ``iter_codes_continuous`` (same loop, same model calls in the same order): per polled block it
         yields a list of ``(index of the prompt, batch slot, that utterance's NEW frames [k][32] int32 CPU, last)`` -- ``last`` with
         the frames that complete the utterance (possibly none); an utterance that is empty before it ever holds a slot has slot -1.
@@ -368,35 +412,45 @@ class Generator:
         The scheduler is sesameai/live_batch.py; ``refill_beside_the_loop`` / ``refill_row_layers`` choose and tune how slots are refilled;
         ``first_chunk_frames``: its short blocks while a request waits for its first chunk (None: every block is ``poll`` steps)."""
         per_prompt_sampling(len(prompts), temperature, topk, seed)          # (a wrong length or a bad value raises before the model is touched)
+        kw = {}
+        if sessions is not None:                                            # the sessions' prompts become their full prompts
+            kw["sessions"] = sessions = check_sessions(sessions, len(prompts))
+            prompts = [(t, mk) if c is None else c.full_prompt(t, mk) for (t, mk), c in zip(prompts, sessions)]
         yield from live_batch(self._model, prompts, max_generation_len, temperature, topk, poll or self._eos_poll, self._max_batch,
                               self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN, seed=seed, refill_group=refill_group,
-                              first_chunk_frames=first_chunk_frames)
+                              first_chunk_frames=first_chunk_frames, **kw)
 
     def generate_codes_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: int,
                                   temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
-                                  seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1) -> List[torch.Tensor]:
+                                  seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
+                                  sessions: Optional[Sequence[Optional[Conversation]]] = None) -> List[torch.Tensor]:
         """``iter_codes_continuous`` collected: each prompt's frames [n_i][32] int32 (CPU), in the order of ``prompts``."""
         results: List[torch.Tensor] = [torch.empty(0, 32, dtype=torch.int32) for _ in prompts]
-        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed, refill_group=refill_group):
+        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, poll, seed=seed, refill_group=refill_group,
+                                                    **({} if sessions is None else {"sessions": sessions})):
             results[i] = frames
         return results
 
     def generate_many(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                       temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
-                      seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1) -> List[torch.Tensor]:
+                      seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
+                      sessions: Optional[Sequence[Optional[Conversation]]] = None) -> List[torch.Tensor]:
         """``generate`` for a list of requests through the continuously refilled batch: one audio tensor per request
-        (``max_audio_length_ms``, ``temperature``, ``topk``: one value, or one per request; ``seed``: one optional int per request)."""
+        (``max_audio_length_ms``, ``temperature``, ``topk``: one value, or one per request; ``seed``: one optional int per request;
+        ``sessions``: one ``Conversation`` or None per request -- the context of a request with a session lists only the NEW segments)."""
         max_generation_len = _frames_for(max_audio_length_ms)
         prompts = self._build_prompts(texts, speakers, contexts)
         out: List[torch.Tensor] = [torch.tensor([]) for _ in prompts]
-        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group):
+        for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group,
+                                                    **({} if sessions is None else {"sessions": sessions})):
             if frames.shape[0]:                                       # decoded as each utterance finishes, not at the end
                 out[i] = self._decode_frames(frames.unsqueeze(1))
         return out
 
     def generate_many_stream(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                              temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
-                             seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None
+                             seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None,
+                             sessions: Optional[Sequence[Optional[Conversation]]] = None
                              ) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
@@ -417,7 +471,8 @@ class Generator:
         ``_stream_buffer_size``, the last whatever remains; everything else above holds, and a request's chunks concatenated are still its
         whole-clip decode, bit for bit what the uniform calls give.  The Philox key of a sampled frame holds the global frame index, so --
         as with ``refill_group`` -- the sampled codes of requests WITHOUT a seed of their own may differ between None and k (the shorter
-        blocks see the retirements at other steps); requests with their own seed, and greedy runs, give the same codes for every k."""
+        blocks see the retirements at other steps); requests with their own seed, and greedy runs, give the same codes for every k.
+        ``sessions``: as for ``generate_many``."""
         size = self._stream_buffer_size
         if first_chunk_frames is not None and not 1 <= int(first_chunk_frames) < size:
             raise ValueError(f"first_chunk_frames must be None or 1 .. {size - 1}")
@@ -438,7 +493,8 @@ class Generator:
         streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device, **({} if first is None else {"first": first}))
         backlog: List[list] = []                                    # polled blocks whose audio is still to be decoded
         for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed, refill_group=refill_group,
-                                                  **({} if first is None else {"first_chunk_frames": first})):
+                                                  **({} if first is None else {"first_chunk_frames": first}),
+                                                  **({} if sessions is None else {"sessions": sessions})):
             if block is not None:
                 backlog.append(block)
                 continue
@@ -466,16 +522,19 @@ class Generator:
 
     def generate_stream(self, text, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                         temperature: float = 0.7, topk: int = 30,
-                        on_chunk_generated: Optional[Callable[[torch.Tensor], None]] = None
-                        ) -> PyGenerator[torch.Tensor, None, None]:
+                        on_chunk_generated: Optional[Callable[[torch.Tensor], None]] = None,
+                        session: Optional[Conversation] = None) -> PyGenerator[torch.Tensor, None, None]:
         """reference: generator.py:119-210 -- yields audio every ``_stream_buffer_size`` frames as soon as it exists,
         each buffer decoded statelessly like the reference.  Mimi runs on its own HIP stream while the frame steps
-        of the next buffer (already enqueued) run on the caller's stream."""
+        of the next buffer (already enqueued) run on the caller's stream.
+        ``session``: ``context`` lists only the segments that are NEW since the session's last turn (``open_session``)."""
         max_generation_len = int(max_audio_length_ms / FRAME_MS)
         with torch.inference_mode():
             tokens, mask = self._build_prompt(text, speaker, context)
         if tokens.dim() == 2:
             tokens, mask = tokens.unsqueeze(0), mask.unsqueeze(0)
+        if session is not None:
+            tokens, mask = self._session_prompt(session, tokens, mask)
         if tokens.shape[1] >= MAX_SEQ_LEN - max_generation_len:
             raise ValueError(f"Inputs too long, must be below max_seq_len - max_generation_len: {MAX_SEQ_LEN - max_generation_len}")
         side = self._side_stream()
@@ -493,7 +552,7 @@ class Generator:
             return pcm
 
         gate = _FirstBlockGate()
-        blocks = self._frame_blocks(tokens, mask, max_generation_len, temperature, topk, size, gate=gate)
+        blocks = self._frame_blocks(tokens, mask, max_generation_len, temperature, topk, size, gate=gate, session=session)
         while True:
             with torch.inference_mode():
                 fr = next(blocks, None)
@@ -514,14 +573,15 @@ class Generator:
 
     @torch.inference_mode()
     def generate(self, text, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
-                 temperature: float = 0.7, topk: int = 30, stream: bool = False) -> torch.Tensor:
-        """reference: generator.py:212-300."""
+                 temperature: float = 0.7, topk: int = 30, stream: bool = False, session: Optional[Conversation] = None) -> torch.Tensor:
+        """reference: generator.py:212-300.  ``session``: ``context`` lists only the segments that are NEW since the session's last turn
+        (``open_session``)."""
         if stream:
-            chunks = list(self.generate_stream(text, speaker, context, max_audio_length_ms, temperature, topk))
+            chunks = list(self.generate_stream(text, speaker, context, max_audio_length_ms, temperature, topk, session=session))
             return torch.cat(chunks) if chunks else torch.tensor([])
         max_generation_len = int(max_audio_length_ms / FRAME_MS)
         tokens, mask = self._build_prompt(text, speaker, context)
-        frames = self.generate_codes(tokens, mask, max_generation_len, temperature, topk)
+        frames = self.generate_codes(tokens, mask, max_generation_len, temperature, topk, session=session)
         if frames.shape[0] == 0:
             return torch.tensor([])
         return self._decode_frames(frames)

@@ -36,17 +36,27 @@ class LiveBatch:
     before a prompt without own values takes it.  With no own values anywhere the model sees neither call.
     ``first_chunk`` = k (None: off, today's blocks exactly): while some utterance has had fewer than k of its frames handed out, a block of
     frame steps ends as soon as that utterance has k frames QUEUED -- evaluated after every queued step, because a refill may complete in the
-    middle of a block -- so that its first audio need not wait for a whole block.  Otherwise blocks are ``poll`` steps as before."""
+    middle of a block -- so that its first audio need not wait for a whole block.  Otherwise blocks are ``poll`` steps as before.
+    ``sessions[i]``: the ``Conversation`` (sesameai/sessions.py) prompt ``i`` is a turn of, or None; ``prompts[i]`` is then the session's FULL
+    prompt.  The rows its pages hold are not run: the pages of all sessions of one refill call are loaded by ONE ``Model.load_sessions``
+    immediately before that call (``_rows_to_run``), and when the turn is over its slot's new rows are saved -- after the block has been read,
+    before the slot is rewound or refilled (``run``).  With no sessions (None) the model sees neither call."""
 
     def __init__(self, model, prompts, limits: List[int], temperature: float, topk: int, poll: int, slots: int, store: list, own=None,
-                 first_chunk: Optional[int] = None):
+                 first_chunk: Optional[int] = None, sessions=None):
         self.m, self.prompts, self.limits, self.sampling, self.poll, self.B = model, prompts, limits, (temperature, topk), poll, slots
         self.first_chunk = first_chunk
+        self.sessions = sessions if sessions is not None else [None] * len(prompts)
+        # rows of prompt i that its session's pages hold (0: no session, or a cold one -- it runs like any prompt, through the prefix store);
+        # fixed here: only a save can take a session's pages away, and never those of a session of the running call before its own turn is over
+        self.warm = [min(c.rows, t.shape[0] - 1) if c is not None else 0 for c, (t, _) in zip(self.sessions, prompts)]
         self.own = own if own is not None else [None] * len(prompts)
         self.entries: set = set()                                   # slots that hold an entry of the sampling table (reset_caches empties it)
         # per prompt (rows P to copy, handle): the registered prefix with the longest match, (0, None) without one -- all matched before the loop
         # starts: no comparison's host synchronisation falls between frame steps; and {slot: handle} of the initial fill's shared copies
         self.plan = [match_stored_prefix(store, t, mk) for t, mk in prompts] if store else [(0, None)] * len(prompts)
+        if sessions is not None:
+            self.plan = [(0, None) if w else p for w, p in zip(self.warm, self.plan)]
         self.seeded = {slot: handle for slot, (_, handle) in enumerate(self.plan[:slots]) if handle is not None}
         self.pending = deque(range(len(prompts)))
         self.free = deque(range(slots))                             # slots waiting for a prompt
@@ -90,11 +100,20 @@ class LiveBatch:
                 if fs or last:
                     self.events.append((u.index, s, torch.stack(fs).to(torch.int32) if fs else _NO_FRAMES, last))
                 if last:
+                    self._turn_over(u.index, s, u.frames[:max(u.limit, 0)])
                     self.slots[s] = None
                     self._vacated(s)
             idle = self._idle([s for s, last in cuts if last])
             if idle and (self.pending or any(u is not None for u in self.slots)):
                 m.reset_slots(idle)                                 # a retired slot keeps stepping: keep its position away from max_seq
+
+    def _turn_over(self, i: int, slot: int, frames: List[torch.Tensor]) -> None:
+        """Prompt ``i``'s utterance is over in ``slot`` with all ``frames`` handed out.  A session's turn: its slot's new rows go to its pages now
+        (the block has been read; the slot has been neither rewound nor refilled).  A limit <= 0 generated nothing: the session stays as it was."""
+        c = self.sessions[i]
+        if c is not None and self.limits[i] > 0:
+            t, mk = self.prompts[i]
+            c.turn_over(self.m, slot, t, mk, torch.stack(frames) if frames else _NO_FRAMES, self.limits[i], [x for x in self.sessions if x is not None])
 
     def _first_chunk_queued(self, steps: int) -> bool:
         """Whether, ``steps`` queued steps into the block, an utterance that has had fewer than ``first_chunk`` frames handed out has that many
@@ -144,7 +163,14 @@ class LiveBatch:
             elif slot in self.entries:
                 self.m.clear_slot_sampling([slot])
                 self.entries.discard(slot)
-            parts.append((t[P:], mk[P:], {"start": P}) if handle is not None else (t, mk, {}))
+            if self.warm[i]:
+                P = self.warm[i]
+                parts.append((t[P:], mk[P:], {"start": P}))
+            else:
+                parts.append((t[P:], mk[P:], {"start": P}) if handle is not None else (t, mk, {}))
+        loads = [(self.sessions[i].device, slot) for slot, i in take if self.warm[i]]
+        if loads:                                                   # all sessions of this refill call in one launch, immediately before it
+            self.m.load_sessions([d for d, _ in loads], [slot for _, slot in loads])
         return parts
 
     def _report_order(self, cuts: List[Tuple[int, bool]]) -> List[Tuple[int, bool]]:
@@ -163,6 +189,7 @@ class _Stalling(LiveBatch):
             if self.limits[i] > 0 and not bool((f0 == 0).all()):
                 self.slots[slot] = _Utterance(i, self.limits[i], self.g, [f0])
                 return
+            self._turn_over(i, slot, [])                            # (an empty reply is a turn too: the prompt's rows are in the slot)
             self.events.append((i, -1, _NO_FRAMES, True))
 
     def _feed(self, everything: bool) -> bool:
@@ -201,7 +228,7 @@ class _BesideTheLoop(LiveBatch):
         total = 0
         while self.free and self.pending and len(take) < self.group:
             i = self.pending[0]
-            rows = int(self.prompts[i][0].shape[0]) - (self.plan[i][0] if self.plan[i][1] is not None else 0)
+            rows = int(self.prompts[i][0].shape[0]) - (self.warm[i] or (self.plan[i][0] if self.plan[i][1] is not None else 0))
             if take and total + rows > cap:
                 break                                               # it waits for the next group
             take.append((self.free.popleft(), self.pending.popleft()))
@@ -273,12 +300,12 @@ def per_prompt_sampling(n: int, temperature, topk, seed):
 
 
 def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_batch, store, beside_the_loop, refill_row_layers, max_seq_len,
-               seed=None, refill_group: int = 1, first_chunk_frames: Optional[int] = None):
+               seed=None, refill_group: int = 1, first_chunk_frames: Optional[int] = None, sessions=None):
     """``LiveBatch.run`` over ``prompts`` [(tokens (S_i,33), mask (S_i,33)), ...] with one length limit for all or one per prompt (a
     request's own max_audio_length_ms), refilling beside the loop where the model's frame steps of this batch size honour it.
     ``temperature`` / ``topk``: one value, or one per prompt; ``seed``: one optional int per prompt (``per_prompt_sampling``).
     ``refill_group``: how many free slots one refill beside the loop may take together (1: one at a time, today's calls exactly).
-    ``first_chunk_frames``: ``LiveBatch``'s ``first_chunk`` (None: today's blocks exactly)."""
+    ``first_chunk_frames``: ``LiveBatch``'s ``first_chunk`` (None: today's blocks exactly).  ``sessions``: ``LiveBatch``'s (None: none)."""
     (temperature, topk), own = per_prompt_sampling(len(prompts), temperature, topk, seed)
     limits = [int(max_generation_len)] * len(prompts) if isinstance(max_generation_len, (int, float)) else [int(x) for x in max_generation_len]
     if len(limits) != len(prompts):
@@ -295,6 +322,8 @@ def live_batch(model, prompts, max_generation_len, temperature, topk, poll, max_
     if int(refill_group) < 1:
         raise ValueError("refill_group must be >= 1")
     kw = {} if first_chunk_frames is None else {"first_chunk": int(first_chunk_frames)}
+    if sessions is not None and any(c is not None for c in sessions):
+        kw["sessions"] = list(sessions)
     yield from (_BesideTheLoop(*args, budget=refill_row_layers, group=refill_group, **kw) if beside else _Stalling(*args, **kw)).run()
 
 

@@ -376,6 +376,61 @@ class Prefix:
             pass
 
 
+class SessionPoolFull(RuntimeError):
+    """``Model.save_session``: the session store has too few free pages (CSM_E_NO_PAGES).  Nothing was enqueued and the session is unchanged:
+    truncate or close another session and save again."""
+
+
+class Session:
+    """A conversation's backbone K/V in pages of the model's session store (include/csm_hip.h csm_session_*): ``Model.save_session``
+    appends a slot's new rows, ``Model.load_sessions`` gathers the pages into any slots.  ``close()`` (or garbage collection) returns
+    the pages; a model's ``setup_caches`` closes the sessions opened on it."""
+
+    def __init__(self, model: "Model", ptr: int):
+        self._model, self._p = model, C.c_void_p(ptr)
+
+    @property
+    def alive(self) -> bool:
+        return bool(self._p)
+
+    def _ptr(self) -> C.c_void_p:
+        if not self._p:
+            raise ValueError("this session has been closed")
+        return self._p
+
+    @property
+    def rows(self) -> int:
+        return int(lib.csm_session_rows(self._p)) if self._p else 0
+
+    @property
+    def pages(self) -> int:
+        return int(lib.csm_session_pages(self._p)) if self._p else 0
+
+    def truncate(self, rows: int) -> None:
+        """Keeps the first ``rows`` rows; whole pages beyond them return to the pool (csm_session_truncate: host bookkeeping only)."""
+        check(lib.csm_session_truncate(self._ptr(), int(rows)), self._model._h)
+
+    def read(self) -> torch.Tensor:
+        """The rows [layers][2 (K, V)][kv heads][rows][head_dim] bf16 on the host, ``Prefix.read``'s layout (csm_session_read; synchronises)."""
+        m = self._model
+        out = torch.empty(m.bb.num_layers, 2, m.bb.num_kv_heads, self.rows, m.bb.head_dim, dtype=torch.bfloat16)
+        with m._on_device():
+            check(lib.csm_session_read(self._ptr(), out.data_ptr(), out.numel() * 2, _stream_ptr()), m._h)
+        return out
+
+    def close(self) -> None:
+        if self._p:
+            lib.csm_session_close(self._p)
+            self._p = C.c_void_p(None)
+            self._model._sessions = [r for r in self._model._sessions if r() not in (None, self)]
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def common_prefix_rows(t: torch.Tensor, m: torch.Tensor, ot: torch.Tensor, om: torch.Tensor) -> int:
     """Leading rows on which two prompts (S,33) / (S',33) agree: tokens under the mask and the mask itself, as ``prefill_prompt``
     compares (tokens already zeroed where the mask is off)."""
@@ -457,6 +512,8 @@ class Model:
         self._prefixes: list = []
         self.stored_prefixes: List[Tuple[torch.Tensor, torch.Tensor, Prefix]] = []
         self.prefill_rows_total = 0           # prompt rows run by prefill_prompt / refill_slot / refill_begin since construction
+        self._sessions: list = []             # weak references to the sessions opened on this handle (open_session)
+        self.session_page_rows = 0            # rows per page of the session store; 0: none (open_session_store)
 
     # -- reference-compatible construction helpers ------------------------------------------
     @classmethod
@@ -518,6 +575,7 @@ class Model:
         """reference: Model.setup_caches (sesameai/models.py:120-130)."""
         if self._h:
             self._drop_prefixes()
+            self._drop_sessions()
             lib.csm_destroy(self._h)
             self._h = C.c_void_p(None)
         cfg, w = self._cfg_struct(), self._weights_struct()
@@ -600,10 +658,20 @@ class Model:
         self._prefixes = []
         del self.stored_prefixes[:]                              # (the list is shared with the Generator that registered them)
 
+    def _drop_sessions(self) -> None:
+        """The pages live in the handle's pool and die with it."""
+        for r in list(self._sessions):
+            s = r()
+            if s is not None:
+                s.close()
+        self._sessions = []
+        self.session_page_rows = 0
+
     def __del__(self):
         try:
             if self._h:
                 self._drop_prefixes()
+                self._drop_sessions()
                 lib.csm_destroy(self._h)
         except Exception:
             pass
@@ -624,17 +692,30 @@ class Model:
         with self._on_device():
             check(lib.csm_prefill(self._h, t.data_ptr(), m.data_ptr(), p.data_ptr(), b, s, int(_keeps_prompt_prefix), _stream_ptr()), self._h)
 
-    def prefill_prompt(self, tokens: torch.Tensor, tokens_mask: torch.Tensor) -> int:
+    def prefill_prompt(self, tokens: torch.Tensor, tokens_mask: torch.Tensor, start: Optional[int] = None) -> int:
         """Prefill a prompt that starts at position 0 (B,S,33), reusing the cached backbone KV of the
         longest common row prefix with the previous prompt.  Returns the number of rows actually run.
         The KV entries of the reused rows were produced by the same deterministic kernels from the
-        same inputs at the same positions, so the result is bit-identical to a full prefill."""
+        same inputs at the same positions, so the result is bit-identical to a full prefill.
+        ``start`` (B = 1): rows [0, start) are in slot 0's caches already -- ``load_sessions`` put them there -- so nothing is compared and
+        only rows [start, S) run; the slot is nobody's cached prompt afterwards (a session's rows came from decode steps: equal to a
+        prompt's to bf16 rounding, not bit for bit)."""
         b, s, _ = tokens.shape
         if s > self.bb.max_seq_len:
             raise ValueError(f"prompt of {s} rows exceeds max_seq_len={self.bb.max_seq_len}")
         t = self._to_dev(tokens, torch.int32)
         m = self._to_dev(tokens_mask, torch.uint8).to(torch.bool)
         t = torch.where(m, t, torch.zeros_like(t))                    # masked slots do not matter
+        if start is not None:
+            if b != 1:
+                raise ValueError("prefill_prompt: start= is for one sequence")
+            start = max(0, min(int(start), s - 1))
+            pos = torch.arange(start, s, device=self.device, dtype=torch.int32).unsqueeze(0)
+            self.prefill(t[:, start:], m[:, start:], pos, _keeps_prompt_prefix=True)
+            self._kv_prompt = None
+            self.last_prefill_rows = s - start
+            self.prefill_rows_total += s - start
+            return s - start
         start = 0
         if self.prefix_reuse and self._kv_prompt is not None and self._kv_prompt[0].shape[0] == b:
             ot, om = self._kv_prompt
@@ -685,6 +766,52 @@ class Model:
         last row always runs -- (0, None) when none agrees on any.  A prefix that agrees only partway is used up to that row: the
         rows of the snapshot beyond it are overwritten by the suffix's own."""
         return match_stored_prefix(self.stored_prefixes, tokens, mask)
+
+    # -- session store --------------------------------------------------------------------------
+    def open_session_store(self, pages: int, page_rows: int = 64) -> None:
+        """The pool that carries conversations' backbone K/V from turn to turn: ``pages`` pages of ``page_rows`` rows, allocated once per
+        ``setup_caches`` (csm_session_store_create; 32 KB per row at CSM-1B, so 2 MB per 64-row page)."""
+        self._require()
+        with self._on_device():
+            check(lib.csm_session_store_create(self._h, int(pages), int(page_rows)), self._h)
+        self.session_page_rows = int(page_rows)
+
+    def open_session(self) -> Session:
+        """A new, empty session of the store (csm_session_open)."""
+        self._require()
+        out = C.c_void_p(None)
+        check(lib.csm_session_open(self._h, C.byref(out)), self._h)
+        s = Session(self, out.value)
+        import weakref
+        self._sessions.append(weakref.ref(s))
+        return s
+
+    def save_session(self, session: Session, slot: int, rows: int) -> None:
+        """Appends rows [session.rows, rows) of batch slot ``slot``'s caches to the session (csm_session_save): stream-ordered, no allocation, no
+        synchronisation -- call it between frame steps, once the slot's rows below ``rows`` have been written.  ``SessionPoolFull`` when the pool
+        has too few free pages (nothing enqueued, the session unchanged)."""
+        self._require()
+        with self._on_device():
+            rc = lib.csm_session_save(self._h, session._ptr(), int(slot), int(rows), _stream_ptr())
+        if rc == -5:
+            raise SessionPoolFull(f"session store: no pages for rows [{session.rows}, {int(rows)})")
+        check(rc, self._h)
+
+    def load_sessions(self, sessions, slots) -> None:
+        """Writes each session's rows [0, session.rows) into the slot of the same index, up to 32 pairs in ONE launch (csm_session_load); the
+        slots' positions are untouched.  Call it IMMEDIATELY before the ``refill_slot`` / ``refill_begin`` / ``refill_group_begin`` / ``prefill``
+        that runs the rows after them (``start`` = the session's rows), as ``apply_prefix``."""
+        self._require()
+        slots = [int(x) for x in slots]
+        n = len(slots)
+        if len(sessions) != n:
+            raise ValueError("load_sessions: one slot per session")
+        ptrs = (C.c_void_p * max(n, 1))(*[s._ptr().value for s in sessions])
+        arr = (C.c_int32 * max(n, 1))(*slots)
+        with self._on_device():
+            check(lib.csm_session_load(self._h, ptrs, arr, n, _stream_ptr()), self._h)
+        if 0 in slots:
+            self._kv_prompt = None                               # slot 0's rows are the session's now
 
     def reset_slots(self, slots) -> None:
         """Position 0 and "no EOS yet" for the listed batch slots; the other slots are untouched (csm_reset_slots)."""
