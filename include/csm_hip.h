@@ -274,7 +274,7 @@ void   csm_prefix_destroy(csm_prefix prefix);
  * of one pool that the handle allocates once: a page holds page_rows rows of every layer's K and V of every kv head
  * ([layer][K|V][kv head][page_rows][hd] bf16; 2 MB at CSM-1B with 64 rows).  At the end of a turn only the new rows are appended; at the
  * start of the next the pages are gathered into whichever slot the request gets and only the rows after them are prefilled.
- * ORDERING: csm_session_save, csm_session_load and csm_session_truncate allocate nothing, copy nothing from the host and never
+ * ORDERING: csm_session_save, csm_session_load, csm_session_forget and csm_session_truncate allocate nothing, copy nothing from the host and never
  * synchronise (the page numbers travel in kernel arguments into a device table that the load reads).  They are meant for the frame
  * loop's stream, between frame steps, and that ONE stream is what makes page reuse safe: a page that a truncate or close gives back may
  * be handed to the next save at once, because every load that still reads it was enqueued earlier on the same stream.  Calls on a second
@@ -292,6 +292,19 @@ void   csm_prefix_destroy(csm_prefix prefix);
  *                       (pos starts at rows_i), exactly as after csm_prefix_apply, and enqueues the load IMMEDIATELY before that call.
  *   csm_session_truncate: the session keeps its first `rows` rows (barge-in: the listener heard only part of the last reply); whole
  *                       pages beyond the new end return to the pool.  Host bookkeeping only.
+ *   csm_session_forget: the session drops its rows [from, to) IN PLACE (an endless conversation forgets its oldest turns and keeps the
+ *                       voice prompt).  Rows below `from` stay where they are (attention is causal: they never saw what
+ *                       is dropped); rows from `to` on move down by d = to - from, V as it is and K -- stored rotated -- rotated BACK by d
+ *                       positions: a pair (x0, x1) becomes (x0 c + x1 s, x1 c - x0 s) with rot[j] = (c, s) = (cos, sin)(d * theta_j), a
+ *                       HOST array [head_dim / 2][2] of floats that the caller computes from the frequencies of its rope table (the
+ *                       library does not know theta).  fp32 on the bf16 values, multiplies and adds kept apart, ONE rounding to bf16 per
+ *                       forget.  Logical pages below from / page_rows keep their page numbers; the rows from there on are rewritten into
+ *                       FRESH pages (pages_for(rows - d) - from / page_rows of them) by one copy launch, and the old pages return to the
+ *                       pool in the same call.  Like save and load it allocates nothing, copies nothing from the host and never
+ *                       synchronises: rot and the new page numbers travel in kernel arguments.  to == rows is a truncate to `from`;
+ *                       from == to returns CSM_OK and enqueues nothing.  head_dim 64 and 128.  Refused with nothing enqueued and the
+ *                       session unchanged: a range outside [0, rows] or to < from, a NULL rot, a closed session or one of another handle
+ *                       (CSM_E_INVALID); too few free pages (CSM_E_NO_PAGES).
  *   csm_session_rows / csm_session_pages: rows held / pages owned (0 for NULL or after csm_destroy of the handle).
  *   csm_session_read:   the session's rows, dense in csm_prefix_read's layout [layer][K|V][kv head][rows][hd] (bytes must match;
  *                       synchronises).  For tests.
@@ -300,11 +313,12 @@ void   csm_prefix_destroy(csm_prefix prefix);
  * outside the batch or listed twice in one load (CSM_E_INVALID); a slot whose refill beside the loop is running (CSM_E_STATE, the
  * predicate of the prefix calls); a session of another handle or a closed one (CSM_E_INVALID); a pool too short (CSM_E_NO_PAGES).
  * csm_destroy releases the pool; session objects still alive can then only be closed.  csm_describe reports
- * `session_store=<n> sessions, <used>/<total> pages`.                                                                                  */
+ * `session_store=<n> sessions, <used>/<total> pages; session_forgets=<n> (<rows> rows moved)`. */
 int  csm_session_store_create(csm_handle h, int n_pages, int page_rows);
 int  csm_session_open(csm_handle h, csm_session* out);
 int  csm_session_save(csm_handle h, csm_session s, int slot, int rows, void* stream);
 int  csm_session_load(csm_handle h, const csm_session* ss, const int32_t* slots /*host*/, int n, void* stream);
+int  csm_session_forget(csm_handle h, csm_session s, int from, int to, const float* rot /*host, [head_dim/2][2]*/, void* stream);
 int  csm_session_truncate(csm_session s, int rows);
 int  csm_session_rows(csm_session s);
 int  csm_session_pages(csm_session s);

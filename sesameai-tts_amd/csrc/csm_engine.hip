@@ -153,7 +153,10 @@ struct CsmModel {
     SessionPages* sess = nullptr;       // the bookkeeping (session_pages.h); nullptr: no store
     bf16_t* sess_pool = nullptr;        // [n_pages][layer][K|V][kv head][page_rows][hd]
     int* sess_tab = nullptr;            // [max sessions][sess_tab_stride] device page table: row = session id, entry k = the session's logical page k
-    int sess_tab_stride = 0;            //   (written by k_session_save from its kernel arguments, read by k_session_load: no host-to-device copy)
+    int sess_tab_stride = 0;            //   (written by k_session_save from its kernel arguments, read by k_session_load: no host-to-device copy);
+                                        //   one row more than sessions can be open: csm_session_forget's staging row (the new page list while the kernel reads the old)
+    int sess_forgets = 0;               // csm_session_forget calls that dropped rows, and the rows they moved down (csm_describe)
+    long sess_forget_moved = 0;
     std::vector<struct CsmSession*> sessions;    // open session objects of this handle; orphaned by csm_destroy
     std::string err;
 };
@@ -2039,6 +2042,62 @@ __global__ __launch_bounds__(256) void k_session_load(bf16_t* kc, bf16_t* vc, bf
     session_copy<true>(session_run(kc, vc, g, run, a.slot[z]), (uint4*)pool, tab + (long)a.id[z] * tab_stride, g, run, b0 + threadIdx.x, end);
 }
 
+// csm_session_forget: the session's rows [first, rows) rewritten into fresh pages without its old rows [from, from + d).  New row r < from is
+// old row r; new row r >= from is old row r + d, verbatim in V runs and with its keys rotated BACK by d positions in K runs (K is stored
+// rotated; rot[j] = (cos, sin)(d * theta_j), so a pair (x0, x1) becomes (x0 c + x1 s, x1 c - x0 s)): fp32 on the bf16 values, multiplies and
+// adds kept apart as in dp_rope_pair so that they equal torch's bit for bit, one rounding to bf16.  old_row: the session's table row (still
+// the old page list: it is rewritten after this launch), new_row: the staging row.  k_session_load's shape: 16 B per lane, four
+// independent loads in flight per lane before the first store; grid = (pieces of the rewritten range, run).  rot is staged into LDS
+// while the loads fly (a lane-varying index into kernel arguments would go to scratch).
+#define SESS_ROT_MAX 64                 // head_dim / 2 at head_dim 128
+struct SessRot { float cs[SESS_ROT_MAX][2]; };
+__device__ __forceinline__ uint32_t session_unrope_pair(uint32_t w, float2 cs) {
+#pragma clang fp contract(off)
+    const float x0 = lo2f(w), x1 = hi2f(w);
+    const float o0 = x0 * cs.x + x1 * cs.y;
+    const float o1 = x1 * cs.x - x0 * cs.y;
+    return pack_bf(o0, o1);
+}
+__global__ __launch_bounds__(256) void k_session_forget(bf16_t* pool_, const int* old_row, const int* new_row, SessGeom g, int first, int from, int d, int rows, int n_rot, SessRot rot) {
+    __shared__ float2 lrot[SESS_ROT_MAX];
+    uint4* pool = (uint4*)pool_;
+    const int run = blockIdx.y;
+    const bool is_k = ((run / g.kv_heads) & 1) == 0;
+    const long page_vecs = (long)g.page_rows * g.hv, end = (long)rows * g.hv, moved_from = (long)from * g.hv;
+    const long i0 = (long)first * g.hv + (long)blockIdx.x * SESS_VECS_PER_BLOCK + threadIdx.x;
+    uint4* pp[4];
+    uint4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long i = i0 + j * 256;
+        if (i < end) {
+            const long si = i >= moved_from ? i + (long)d * g.hv : i, sp = si / page_vecs, lp = i / page_vecs;
+            v[j] = pool[((long)old_row[sp] * g.n_runs + run) * page_vecs + (si - sp * page_vecs)];
+            pp[j] = pool + ((long)new_row[lp] * g.n_runs + run) * page_vecs + (i - lp * page_vecs);
+        }
+    }
+    if (is_k) {                                                 // (uniform over the block)
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < SESS_ROT_MAX; ++j)
+                if (j < n_rot) lrot[j] = make_float2(rot.cs[j][0], rot.cs[j][1]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long i = i0 + j * 256;
+            if (i < end && i >= moved_from) {
+                const int p = (int)(i % g.hv) * 4;              // the row's pair index of this piece's first pair
+                v[j].x = session_unrope_pair(v[j].x, lrot[p]);     v[j].y = session_unrope_pair(v[j].y, lrot[p + 1]);
+                v[j].z = session_unrope_pair(v[j].z, lrot[p + 2]); v[j].w = session_unrope_pair(v[j].w, lrot[p + 3]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (i0 + j * 256 < end) *pp[j] = v[j];
+}
+
 static SessGeom session_geom(const CsmModel* m) {
     const Stack& S = m->bb;
     SessGeom g;
@@ -2060,7 +2119,7 @@ extern "C" int csm_session_store_create(csm_handle m, int n_pages, int page_rows
     const int stride = (S.cache_len + page_rows - 1) / page_rows, max_sessions = n_pages + 32;
     const size_t mark = m->pool.mark();
     hipError_t e = dev_get(m, &m->sess_pool, page_bytes * (size_t)n_pages);
-    if (e == hipSuccess) e = dev_get(m, &m->sess_tab, (size_t)max_sessions * stride * sizeof(int), 0);
+    if (e == hipSuccess) e = dev_get(m, &m->sess_tab, (size_t)(max_sessions + 1) * stride * sizeof(int), 0);     // (+ 1: csm_session_forget's staging row)
     if (e != hipSuccess) { m->pool.release_to(mark); m->sess_pool = nullptr; m->sess_tab = nullptr; HIPCHK(m, e); }
     m->sess_tab_stride = stride;
     m->sess = new SessionPages(n_pages, page_rows, max_sessions);
@@ -2078,6 +2137,19 @@ extern "C" int csm_session_open(csm_handle m, csm_session* out) {
     return CSM_OK;
 }
 
+// entries [first, end) of a table row from the session's page list, <= 256 per launch
+static hipError_t session_tab_write(CsmModel* m, int id, int* tab_row, int first, int end, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    for (; first < end && e == hipSuccess; first += SESS_TAB_PER_LAUNCH) {
+        SessTabEntries te;
+        const int n = std::min(end - first, SESS_TAB_PER_LAUNCH);
+        for (int k = 0; k < n; ++k) te.page[k] = m->sess->page_at(id, first + k);
+        hipLaunchKernelGGL(k_session_tab, dim3(1), dim3(SESS_TAB_PER_LAUNCH), 0, st, tab_row, first, n, te);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
 extern "C" int csm_session_save(csm_handle m, csm_session s, int slot, int rows, void* stream) {
     if (!m || !m->sess) return fail(m, m ? CSM_E_STATE : CSM_E_INVALID, "csm_session_save: null handle or no session store");
     if (!session_live(m, s)) return fail(m, CSM_E_INVALID, "csm_session_save: not an open session of this handle");
@@ -2090,14 +2162,7 @@ extern "C" int csm_session_save(csm_handle m, csm_session s, int slot, int rows,
     if (!m->sess->grow_to(s->id, rows)) return fail(m, CSM_E_NO_PAGES, "csm_session_save: the pool has too few free pages (truncate or close a session and call again)");
     hipStream_t st = (hipStream_t)stream;
     int* tab_row = m->sess_tab + (long)s->id * m->sess_tab_stride;
-    hipError_t e = hipSuccess;
-    for (int first = had_pages; first < m->sess->pages(s->id) && e == hipSuccess; first += SESS_TAB_PER_LAUNCH) {     // the new pages' table entries, ahead of the copy
-        SessTabEntries te;
-        const int n = std::min(m->sess->pages(s->id) - first, SESS_TAB_PER_LAUNCH);
-        for (int k = 0; k < n; ++k) te.page[k] = m->sess->page_at(s->id, first + k);
-        hipLaunchKernelGGL(k_session_tab, dim3(1), dim3(SESS_TAB_PER_LAUNCH), 0, st, tab_row, first, n, te);
-        e = hipGetLastError();
-    }
+    hipError_t e = session_tab_write(m, s->id, tab_row, had_pages, m->sess->pages(s->id), st);     // the new pages' table entries, ahead of the copy
     if (e == hipSuccess) {
         const SessGeom g = session_geom(m);
         const long vecs = (long)(rows - from) * g.hv;
@@ -2129,6 +2194,40 @@ extern "C" int csm_session_load(csm_handle m, const csm_session* ss, const int32
     hipLaunchKernelGGL(k_session_load, dim3((unsigned)((vecs + SESS_VECS_PER_BLOCK - 1) / SESS_VECS_PER_BLOCK), (unsigned)g.n_runs, (unsigned)n), dim3(256), 0,
                        (hipStream_t)stream, m->bb.kc, m->bb.vc, m->sess_pool, (const int*)m->sess_tab, m->sess_tab_stride, g, a);
     HIPCHK(m, hipGetLastError());
+    return CSM_OK;
+}
+
+extern "C" int csm_session_forget(csm_handle m, csm_session s, int from, int to, const float* rot, void* stream) {
+    if (!m || !m->sess) return fail(m, m ? CSM_E_STATE : CSM_E_INVALID, "csm_session_forget: null handle or no session store");
+    if (!session_live(m, s)) return fail(m, CSM_E_INVALID, "csm_session_forget: not an open session of this handle");
+    const int had = m->sess->rows(s->id), hd = m->bb.hd;
+    if (from < 0 || to < from || to > had) return fail(m, CSM_E_INVALID, "csm_session_forget: 0 <= from <= to <= the session's row count required");
+    if (from == to) return CSM_OK;
+    if (!rot || (hd != 64 && hd != 128)) return fail(m, CSM_E_INVALID, "csm_session_forget: null rotation table, or a head_dim other than 64 or 128");
+    SessRot r;
+    for (int j = 0; j < hd / 2; ++j) { r.cs[j][0] = rot[2 * j]; r.cs[j][1] = rot[2 * j + 1]; }
+    for (int j = hd / 2; j < SESS_ROT_MAX; ++j) { r.cs[j][0] = 1.f; r.cs[j][1] = 0.f; }
+    const int rc = m->sess->forget(s->id, from, to);
+    if (rc == SessionPages::FORGET_NO_PAGES) return fail(m, CSM_E_NO_PAGES, "csm_session_forget: the pool has too few free pages for the rewritten rows (truncate or close a session and call again)");
+    if (rc != SessionPages::FORGET_OK) return fail(m, CSM_E_INVALID, "csm_session_forget: refused by the page bookkeeping");
+    const SessGeom g = session_geom(m);
+    const int k0 = from / g.page_rows, first = k0 * g.page_rows, rows = m->sess->rows(s->id), pages = m->sess->pages(s->id);
+    hipStream_t st = (hipStream_t)stream;
+    int* tab_row = m->sess_tab + (long)s->id * m->sess_tab_stride;
+    int* stage_row = m->sess_tab + (long)m->sess->max_sessions() * m->sess_tab_stride;
+    hipError_t e = hipSuccess;
+    if (rows > first) {                                         // the new page list into the staging row, the copy (it reads the old list in the session's row), then the session's row
+        e = session_tab_write(m, s->id, stage_row, k0, pages, st);
+        if (e == hipSuccess) {
+            const long vecs = (long)(rows - first) * g.hv;
+            hipLaunchKernelGGL(k_session_forget, dim3((unsigned)((vecs + SESS_VECS_PER_BLOCK - 1) / SESS_VECS_PER_BLOCK), (unsigned)g.n_runs), dim3(256), 0, st,
+                               m->sess_pool, (const int*)tab_row, (const int*)stage_row, g, first, from, to - from, rows, hd / 2, r);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = session_tab_write(m, s->id, tab_row, k0, pages, st);
+    }
+    if (e != hipSuccess) { (void)m->sess->truncate(s->id, first); HIPCHK(m, e); }       // (the kept pages below `first` are whole and untouched)
+    m->sess_forgets += 1; m->sess_forget_moved += rows - from;
     return CSM_OK;
 }
 
@@ -2284,6 +2383,8 @@ extern "C" int csm_describe(csm_handle m, char* buf, int n) {
     { size_t pb = 0; for (const CsmPrefix* p : m->prefixes) pb += p->bytes;
       snprintf(tmp, sizeof tmp, "; prefix_store=%d prefixes, %zu bytes", (int)m->prefixes.size(), pb); t += tmp; }
     snprintf(tmp, sizeof tmp, "; session_store=%d sessions, %d/%d pages", m->sess ? m->sess->sessions() : 0, m->sess ? m->sess->pages_used() : 0, m->sess ? m->sess->pages_total() : 0);
+    t += tmp;
+    snprintf(tmp, sizeof tmp, "; session_forgets=%d (%ld rows moved)", m->sess_forgets, m->sess_forget_moved);
     t += tmp;
     { int ne = 0, ns = 0; for (unsigned char f : m->slot_tab_host) { ne += f & 1; ns += (f >> 1) & 1; }
       snprintf(tmp, sizeof tmp, "; slot_sampling=%d entries (%d with own seed)%s", ne, ns, m->slot_tab_used ? ", frame steps carry the table" : ""); t += tmp; }

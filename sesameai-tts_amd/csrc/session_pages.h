@@ -1,8 +1,9 @@
 // Page bookkeeping of the session store (include/csm_hip.h csm_session_*): a pool of n_pages pages of page_rows K/V rows each with a free
 // list, and per session an ordered page list and a row count -- logical page k of a session holds its rows [k * page_rows, (k + 1) *
 // page_rows).  No HIP here: csm_engine.hip owns the device memory the page numbers index and enqueues the copies this header plans;
-// tools/session_pages_check.cpp drives it on the CPU.  Session ids are small integers handed out again after close (the engine uses them
-// as rows of its device page table); every operation on an id that is not open is refused and changes nothing.
+// tools/session_pages_check.cpp and tools/session_forget_check.cpp drive it on the CPU.  Session ids are small integers handed out again
+// after close (the engine uses them as rows of its device page table); every operation on an id that is not open is refused and changes
+// nothing.
 #pragma once
 #include <vector>
 
@@ -24,6 +25,7 @@ public:
     int pages_total() const { return n_pages_; }
     int pages_used() const { return n_pages_ - (int)free_.size(); }
     int sessions() const { return open_; }
+    int max_sessions() const { return max_sessions_; }
     bool is_open(int id) const { return id >= 0 && id < (int)s_.size() && s_[id].open; }
     int rows(int id) const { return is_open(id) ? s_[id].rows : 0; }
     int pages(int id) const { return is_open(id) ? (int)s_[id].pages.size() : 0; }
@@ -56,6 +58,27 @@ public:
         while ((int)s.pages.size() > pages_for(rows)) { free_.push_back(s.pages.back()); s.pages.pop_back(); }
         s.rows = rows;
         return true;
+    }
+    // the session drops its rows [from, to) (0 <= from < to <= rows): rows [to, rows) move down by to - from.  Logical pages below
+    // k0 = from / page_rows keep their page numbers; the rows from k0 * page_rows on are rewritten into FRESH pages from the free list
+    // (a parallel copy that compacts rows inside the old pages would overwrite sources another block has not read), and the old pages
+    // from k0 on go back to the free list in the same call -- whoever still reads them was enqueued earlier on the one stream.  *old_tail
+    // receives those old page numbers (logical k0, k0 + 1, ...), in case the caller's copy wants them.  Returns FORGET_OK, FORGET_BAD
+    // (a closed id or a range outside the session) or FORGET_NO_PAGES; all or nothing: unless FORGET_OK nothing changes.
+    enum { FORGET_OK = 0, FORGET_BAD = 1, FORGET_NO_PAGES = 2 };
+    int forget(int id, int from, int to, std::vector<int>* old_tail = nullptr) {
+        if (old_tail) old_tail->clear();
+        if (!is_open(id) || from < 0 || to <= from || to > s_[id].rows) return FORGET_BAD;
+        Sess& s = s_[id];
+        const int k0 = from / page_rows_, rows = s.rows - (to - from), fresh = pages_for(rows) - k0;
+        if (fresh > (int)free_.size()) return FORGET_NO_PAGES;
+        std::vector<int> old(s.pages.begin() + k0, s.pages.end());
+        s.pages.resize(k0);
+        for (int k = 0; k < fresh; ++k) { s.pages.push_back(free_.back()); free_.pop_back(); }    // taken BEFORE the old ones return: never one of them
+        for (int k = (int)old.size() - 1; k >= 0; --k) free_.push_back(old[k]);
+        s.rows = rows;
+        if (old_tail) old_tail->swap(old);
+        return FORGET_OK;
     }
     void close(int id) {
         if (!is_open(id)) return;

@@ -93,6 +93,7 @@ SIGNATURES = {
     "csm_session_open": (_i, [_vp, C.POINTER(_vp)]),
     "csm_session_save": (_i, [_vp, _vp, _i, _i, _vp]),
     "csm_session_load": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "csm_session_forget": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "csm_session_truncate": (_i, [_vp, _i]),
     "csm_session_rows": (_i, [_vp]),
     "csm_session_pages": (_i, [_vp]),

@@ -19,7 +19,7 @@ import torch
 
 from .live_batch import SlotStreams, live_batch, per_prompt_sampling
 from .models import Model, ModelArgs, csm_1b_args
-from .sessions import Conversation, ConversationSet, check_sessions
+from .sessions import Conversation, ConversationSet, check_sessions, make_room
 
 FRAME_MS = 80                     # generator.py:257
 MAX_SEQ_LEN = 2048                # generator.py:276
@@ -258,14 +258,27 @@ class Generator:
         at CSM-1B with 64 rows; a 1,334-row history holds 21 of them.  Once per Generator."""
         self._model.open_session_store(pages, page_rows)
 
-    def open_session(self) -> Conversation:
+    def open_session(self, on_full: str = "raise", pinned: int = 1) -> Conversation:
         """A new conversation (sesameai/sessions.py ``Conversation``) for ``session=`` / ``sessions=``: every turn's call then lists only the
         segments that are new since the last one, the history's K/V are loaded from the session's pages and only the new rows are
         prefilled.  The results are those of the cold call with the whole history as its context, to bf16 rounding (see the module's
-        docstring); ``truncate_last`` covers barge-in, ``close`` returns the pages.  Needs ``open_session_store``."""
+        docstring); ``truncate_last`` covers barge-in, ``close`` returns the pages.  Needs ``open_session_store``.
+
+        ``on_full``: what a turn does whose history + new rows no longer fit below MAX_SEQ_LEN - max_generation_len.  "raise": the
+        ``ValueError`` of every entry point, as without sessions.  "forget": an endless conversation -- before the turn's full prompt is built
+        (``generate``, ``generate_stream``, ``generate_codes``, ``generate_many``, ``generate_many_stream``, ``iter_codes_continuous``) the
+        session drops the smallest number of consecutive closed units (segments: ``Conversation.units``) from unit ``pinned`` on that makes
+        the prompt fit; the first ``pinned`` units (the voice prompt), the open unit (the last reply) and the new rows are never dropped,
+        and if the prompt still does not fit nothing is dropped and the ValueError is raised.  The pages drop the rows in place, ahead of
+        the turn's load (``Session.forget``); nothing is recomputed.  A WARM turn after a forget is DEFINED as the oracle run on the cache
+        edited that way (kept rows before the cut untouched; later rows moved down, their keys rotated back by the rows dropped); a COLD
+        turn (the first, or after an eviction) runs the trimmed history.  The two differ by more than rounding, because kept rows have
+        attended to dropped ones; they give the same greedy codes on the decisive checkpoints; sampled runs are not comparable."""
+        if on_full not in ("raise", "forget") or int(pinned) < 0:
+            raise ValueError('open_session: on_full is "raise" or "forget", pinned >= 0')
         if self._conversations is None:
             self._conversations = ConversationSet()
-        return self._conversations.new(self._model.open_session())
+        return self._conversations.new(self._model.open_session(), on_full, int(pinned))
 
     # -- the frame loop -----------------------------------------------------------------------
     def _frame_blocks(self, prompt_tokens: torch.Tensor, prompt_mask: torch.Tensor, max_generation_len: int,
@@ -353,7 +366,7 @@ class Generator:
         if prompt_tokens.dim() == 2:
             prompt_tokens, prompt_mask = prompt_tokens.unsqueeze(0), prompt_mask.unsqueeze(0)
         if session is not None:
-            prompt_tokens, prompt_mask = self._session_prompt(session, prompt_tokens, prompt_mask)
+            prompt_tokens, prompt_mask = self._session_prompt(session, prompt_tokens, prompt_mask, max_generation_len)
         B, S, _ = prompt_tokens.shape
         max_context_len = MAX_SEQ_LEN - max_generation_len
         if S >= max_context_len:
@@ -366,10 +379,11 @@ class Generator:
         return torch.cat(blocks) if blocks else torch.empty(0, B, 32, dtype=torch.int32)
 
     @staticmethod
-    def _session_prompt(session: Conversation, tokens: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(1,S,33) new rows -> the session's full prompt (1,S',33)."""
+    def _session_prompt(session: Conversation, tokens: torch.Tensor, mask: torch.Tensor, limit: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(1,S,33) new rows -> the session's full prompt (1,S',33); an ``on_full="forget"`` session first drops what the turn needs dropped."""
         if tokens.shape[0] != 1:
             raise ValueError("session=: one sequence per call (sessions= of generate_many takes several)")
+        make_room([session], [tokens.shape[1]], [limit], MAX_SEQ_LEN)
         t, mk = session.full_prompt(tokens[0], mask[0])
         return t.unsqueeze(0), mk.unsqueeze(0)
 
@@ -415,6 +429,9 @@ class Generator:
         kw = {}
         if sessions is not None:                                            # the sessions' prompts become their full prompts
             kw["sessions"] = sessions = check_sessions(sessions, len(prompts))
+            limits = [int(max_generation_len)] * len(prompts) if isinstance(max_generation_len, (int, float)) else [int(x) for x in max_generation_len]
+            if len(limits) == len(prompts):                                 # (a wrong length is live_batch's ValueError) on_full="forget": make room first
+                make_room(sessions, [t.shape[0] for t, _ in prompts], limits, MAX_SEQ_LEN)
             prompts = [(t, mk) if c is None else c.full_prompt(t, mk) for (t, mk), c in zip(prompts, sessions)]
         yield from live_batch(self._model, prompts, max_generation_len, temperature, topk, poll or self._eos_poll, self._max_batch,
                               self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN, seed=seed, refill_group=refill_group,
@@ -534,7 +551,7 @@ class Generator:
         if tokens.dim() == 2:
             tokens, mask = tokens.unsqueeze(0), mask.unsqueeze(0)
         if session is not None:
-            tokens, mask = self._session_prompt(session, tokens, mask)
+            tokens, mask = self._session_prompt(session, tokens, mask, max_generation_len)
         if tokens.shape[1] >= MAX_SEQ_LEN - max_generation_len:
             raise ValueError(f"Inputs too long, must be below max_seq_len - max_generation_len: {MAX_SEQ_LEN - max_generation_len}")
         side = self._side_stream()

@@ -40,7 +40,9 @@ class LiveBatch:
     ``sessions[i]``: the ``Conversation`` (sesameai/sessions.py) prompt ``i`` is a turn of, or None; ``prompts[i]`` is then the session's FULL
     prompt.  The rows its pages hold are not run: the pages of all sessions of one refill call are loaded by ONE ``Model.load_sessions``
     immediately before that call (``_rows_to_run``), and when the turn is over its slot's new rows are saved -- after the block has been read,
-    before the slot is rewound or refilled (``run``).  With no sessions (None) the model sees neither call."""
+    before the slot is rewound or refilled (``run``).  With no sessions (None) the model sees neither call.  An ``on_full="forget"`` session
+    has dropped what its turn needs dropped BEFORE its full prompt was built (``sessions.make_room``, called by the Generator): its forget is
+    on the stream ahead of every load of this batch, and ``warm`` below counts the rows its pages hold after it."""
 
     def __init__(self, model, prompts, limits: List[int], temperature: float, topk: int, poll: int, slots: int, store: list, own=None,
                  first_chunk: Optional[int] = None, sessions=None):

@@ -377,8 +377,8 @@ class Prefix:
 
 
 class SessionPoolFull(RuntimeError):
-    """``Model.save_session``: the session store has too few free pages (CSM_E_NO_PAGES).  Nothing was enqueued and the session is unchanged:
-    truncate or close another session and save again."""
+    """``Model.save_session`` / ``Session.forget``: the session store has too few free pages (CSM_E_NO_PAGES).  Nothing was enqueued and the
+    session is unchanged: truncate or close another session and call again."""
 
 
 class Session:
@@ -409,6 +409,24 @@ class Session:
     def truncate(self, rows: int) -> None:
         """Keeps the first ``rows`` rows; whole pages beyond them return to the pool (csm_session_truncate: host bookkeeping only)."""
         check(lib.csm_session_truncate(self._ptr(), int(rows)), self._model._h)
+
+    def forget(self, a: int, b: int) -> None:
+        """Drops rows [a, b) in place (csm_session_forget): rows below ``a`` stay, rows from ``b`` on move down by d = b - a with their keys
+        rotated back by d positions (K is stored rotated; V moves as it is), all in one stream-ordered launch into fresh pages -- no
+        allocation, no host copy, no synchronisation; enqueue it ahead of the session's load.  The rotation (cos, sin)(d * theta) is computed
+        here from ``llama3_rope_theta`` -- the frequencies of the model's rope table -- in float64 and rounded once to float: a row survives
+        many forgets, and each costs it only the one bf16 rounding of the rotated key.  ``SessionPoolFull`` when the pool has too few free
+        pages for the rewritten rows (nothing enqueued, the session unchanged)."""
+        m = self._model
+        if m._bb_theta is None:
+            m._bb_theta = llama3_rope_theta(m.bb).double()
+        ang = float(int(b) - int(a)) * m._bb_theta
+        rot = torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1).float().contiguous()
+        with m._on_device():
+            rc = lib.csm_session_forget(m._h, self._ptr(), int(a), int(b), rot.data_ptr(), _stream_ptr())
+        if rc == -5:
+            raise SessionPoolFull(f"session store: no pages to rewrite rows [{int(a) // max(m.session_page_rows, 1) * m.session_page_rows}, {self.rows - (int(b) - int(a))})")
+        check(rc, m._h)
 
     def read(self) -> torch.Tensor:
         """The rows [layers][2 (K, V)][kv heads][rows][head_dim] bf16 on the host, ``Prefix.read``'s layout (csm_session_read; synchronises)."""
@@ -514,6 +532,7 @@ class Model:
         self.prefill_rows_total = 0           # prompt rows run by prefill_prompt / refill_slot / refill_begin since construction
         self._sessions: list = []             # weak references to the sessions opened on this handle (open_session)
         self.session_page_rows = 0            # rows per page of the session store; 0: none (open_session_store)
+        self._bb_theta = None                 # the backbone rope's frequencies in float64 (Session.forget), made on first use
 
     # -- reference-compatible construction helpers ------------------------------------------
     @classmethod
