@@ -104,8 +104,21 @@ int mimi_reset_stream(mimi_handle h, void* stream);
 /* MimiModel.encode (sesameai/generator.py:86): wav [B] rows of n_samples fp32 @ 24 kHz (row b at
  * wav + b*stride_b) -> codes [B][n_codebooks][T] int32, T = ceil(n_samples / hop).  Residual
  * vector quantisation = nearest centroid per level (first index on ties).  Uses the decoder's
- * work buffers: it ends any stateful decode stream.  n_samples <= hop * max_frames.            */
+ * work buffers: it ends any stateful decode stream.  n_samples <= hop * max_frames.
+ * NON-FINITE AUDIO (a NaN or +-Inf sample) is not checked on the host -- that would synchronise -- and flows through as NaN: every op of
+ * the chain is causal, so the frames that end before the bad sample keep their codes and their latent rows bit for bit; from the bad
+ * sample's frame on the latent is NaN, no centroid is nearest, and every level's code is 0 (what an argmin over an all-NaN row gives);
+ * the residual update subtracts centroid 0 and stays NaN.  A code written by any encode entry point is always inside
+ * [0, codebook_size).  Nothing of it outlives the call: the handle's, and after mimi_enc_pool_reset the stream's, next results are those
+ * of a fresh one, and the other clips of a mimi_encode_many call and the other streams of a pool call are untouched.                      */
 int mimi_encode(mimi_handle h, const float* wav, long n_samples, long stride_b, int B, int32_t* codes, void* stream);
+
+/* For tests: the pre-quantisation latent of the handle's LAST encode call ([rows][hidden] fp32, the stride-2 downsample's output that both
+ * RVQ input projections read), copied device to device on `stream`; `rows` = that call's frames -- T of mimi_encode, where for B > 1 only the
+ * LAST clip's latent is still there, or F of mimi_encode_many (clip i owns rows [F_i, F_i + T_i)).  Read only: no encode kernel changes for it.
+ * Returns -1 with a message in mimi_last_error when `rows` is not the last encode call's frame count, when there was none, or when a decode
+ * has since reused the buffer.                                                                                                            */
+int mimi_debug_encode_latent(mimi_handle h, float* out, long rows, void* stream);
 
 /* Several clips of DIFFERENT lengths through ONE launch chain (a request's context segments, a batch of voice prompts).
  * Clip i = n_samples[i] fp32 samples at wav + wav_off[i] (wav: device memory; wav_off, n_samples: host arrays, read before the call
@@ -196,6 +209,8 @@ const char* mimi_enc_pool_last_error(mimi_enc_pool p);   /* p == NULL: why mimi_
 int  mimi_enc_pool_reset(mimi_enc_pool p, const int32_t* streams, int n, void* stream);
 int  mimi_enc_pool_encode(mimi_enc_pool p, const int32_t* streams, const long* wav_off, const long* n_samples, int n,
                           const float* wav, int32_t* codes, void* stream);
+/* As mimi_debug_encode_latent, for the pool's last mimi_enc_pool_encode call: rows = its F, stream i of the call owns rows [F_i, F_i + T_i). */
+int  mimi_enc_pool_debug_latent(mimi_enc_pool p, float* out, long rows, void* stream);
 
 #ifdef __cplusplus
 }

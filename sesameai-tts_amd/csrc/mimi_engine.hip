@@ -482,13 +482,15 @@ __global__ void k_enc_conv_in(const float* wav, long n, int taps, int C, const f
 
 // nearest centroid of one RVQ level + residual update: score[t][c] = r_t . e_c (from the GEMM),
 // code = argmin_c (|e_c|^2 - 2 score) (first index on ties), r_t -= e_code.   grid = T, block = 256
+// A row without a finite minimum (non-finite audio: every score NaN, no comparison below is ever true) takes code 0, the argmin a
+// reference gives for an all-NaN row; the residual then stays NaN.  The index written and read through is always inside [0, ncodes).
 __global__ __launch_bounds__(256) void k_rvq_pick(const float* score, int ncodes, const float* sqnorm, const float* book, int dim,
                                                   float* resid, int32_t* codes, long code_stride_t) {
     __shared__ float bv[4];
     __shared__ int bi[4];
     __shared__ int pick;
     const int t = blockIdx.x, tid = threadIdx.x;
-    float best = INFINITY; int idx = 0x7fffffff;
+    float best = INFINITY; int idx = 0;                      // (a thread that takes no candidate ties at +inf and loses to any lower index)
     for (int c = tid; c < ncodes; c += 256) {
         const float dsc = sqnorm[c] - 2.0f * score[(long)t * ncodes + c];
         if (dsc < best) { best = dsc; idx = c; }             // ascending c per thread: keeps the first minimum
@@ -501,6 +503,7 @@ __global__ __launch_bounds__(256) void k_rvq_pick(const float* score, int ncodes
     __syncthreads();
     if (tid == 0) {
         for (int x = 1; x < 4; ++x) if (bv[x] < best || (bv[x] == best && bi[x] < idx)) { best = bv[x]; idx = bi[x]; }
+        if ((unsigned)idx >= (unsigned)ncodes) idx = 0;      // never write, or read the codebook through, an index outside it
         pick = idx; codes[(long)t * code_stride_t] = idx;
     }
     __syncthreads();
@@ -754,6 +757,7 @@ struct MimiDecoder {
     int mid_uses[65] = {};
     EncClipTab* enc_clips = nullptr;    // device table of a ragged encode: [MIMI_ENCODE_MAX_CLIPS] clips, then frame -> clip [max_frames]
     int* enc_frame_clip = nullptr;      // (inside the enc_clips allocation)
+    long enc_rows = 0;                  // frames of the last encode call whose latent still lies in b.rvq (0: none; a decode reuses the buffer)
     std::string err;
 };
 
@@ -1232,6 +1236,7 @@ extern "C" int mimi_encode(mimi_handle m, const float* wav, long n_samples, long
         int rc = encode_one(m, wav + (long)b * stride_b, n_samples, codes + (long)b * m->cfg.n_codebooks * T, T, st);
         if (rc) return rc;
     }
+    m->enc_rows = T;
     return mimi_reset_stream(m, stream);      // the work buffers were reused: start any later stream from scratch
 }
 
@@ -1248,7 +1253,27 @@ extern "C" int mimi_encode_many(mimi_handle m, const float* wav, const long* wav
     MCHK(m, hipGetLastError());
     const RagArgs rag = {m->enc_clips, m->enc_frame_clip, 0, 0, 0, 0};
     if (int rc = encode_one(m, wav, 0, codes, sg.F, st, &rag)) return rc;
+    m->enc_rows = sg.F;
     return mimi_reset_stream(m, stream);      // as mimi_encode
+}
+
+// The pre-quantisation latent of the last encode call, which the chain leaves dense in the rvq buffer ([rows][hidden]; mimi_reset_stream
+// zeroes history rows only): a device-to-device copy on the caller's stream, nothing else.
+template <class H>
+static int copy_encode_latent(H* h, const char* who, const float* src, long have, int hidden, float* out, long rows, void* stream) {
+    if (rows < 1 || rows != have) {
+        h->err = std::string(who) + ": rows is not the frame count of the last encode call (" + std::to_string(have) +
+                 "; 0: no encode yet, or a decode has reused the buffer)";
+        return -1;
+    }
+    if (!out) { h->err = std::string(who) + ": null pointer"; return -1; }
+    MCHK(h, hipMemcpyAsync(out, src, (size_t)rows * hidden * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int mimi_debug_encode_latent(mimi_handle m, float* out, long rows, void* stream) {
+    if (!m) return fail(m, "mimi_debug_encode_latent: null handle");
+    return copy_encode_latent(m, "mimi_debug_encode_latent", m->b.rvq.row0(), m->enc_rows, m->cfg.hidden, out, rows, stream);
 }
 
 extern "C" int mimi_decode_strided(mimi_handle m, const int32_t* codes, int B, int T, long stride_b, long stride_k, long stride_t,
@@ -1256,6 +1281,7 @@ extern "C" int mimi_decode_strided(mimi_handle m, const int32_t* codes, int B, i
     if (!m || !codes || !pcm || B < 1 || T < 1) return fail(m, "mimi_decode: bad argument");
     if (T > m->max_frames) return fail(m, "mimi_decode: T exceeds max_frames given to mimi_create");
     if (stateful && B != 1) return fail(m, "mimi_decode: stateful streaming needs B == 1");
+    m->enc_rows = 0;                           // the code lookup writes the rvq buffer: the last encode's latent is gone
     hipStream_t st = (hipStream_t)stream;
     const long hop = hop_of(m->cfg);
     for (int b = 0; b < B; ++b) {
@@ -1416,6 +1442,7 @@ struct MimiEncStreamPool {
     int* tab = nullptr;                             // device table of the running call (enc_stream_segs.h): ENC_STREAM_TAB_WORDS words ...
     long* ltab = nullptr;                           // ... and ENC_STREAM_LTAB_LONGS longs behind them (same allocation)
     float* wav_tail = nullptr;                      // [stream][kernel - 1]: the samples in front of the next chunk's first
+    long enc_rows = 0;                              // frames of the last encode call: its latent lies dense in b.rvq
     std::string err;
 };
 
@@ -1554,5 +1581,11 @@ extern "C" int mimi_enc_pool_encode(mimi_enc_pool p, const int32_t* streams, con
     hipLaunchKernelGGL(k_pool_slide<true>, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
     MCHK(p, hipGetLastError());
     for (int i = 0; i < n; ++i) { p->offset[hdr.sid[i]] += 2 * sg.T[i]; p->ended[hdr.sid[i]] = sg.ends[i]; }
+    p->enc_rows = F;
     return 0;
+}
+
+extern "C" int mimi_enc_pool_debug_latent(mimi_enc_pool p, float* out, long rows, void* stream) {
+    if (!p) return fail(p, "mimi_enc_pool_debug_latent: null pool");
+    return copy_encode_latent(p, "mimi_enc_pool_debug_latent", p->b.rvq.row0(), p->enc_rows, p->cfg.hidden, out, rows, stream);
 }

@@ -130,6 +130,7 @@ MIMI_SIGNATURES = {
     "mimi_reset_stream": (_i, [_vp, _vp]),
     "mimi_encode": (_i, [_vp, _vp, _l, _l, _i, _vp, _vp]),
     "mimi_encode_many": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _i, _vp, _vp]),
+    "mimi_debug_encode_latent": (_i, [_vp, _vp, _l, _vp]),
     "mimi_pool_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
     "mimi_pool_destroy": (None, [_vp]),
     "mimi_pool_last_error": (C.c_char_p, [_vp]),
@@ -141,6 +142,7 @@ MIMI_SIGNATURES = {
     "mimi_enc_pool_last_error": (C.c_char_p, [_vp]),
     "mimi_enc_pool_reset": (_i, [_vp, _vp, _i, _vp]),
     "mimi_enc_pool_encode": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _i, _vp, _vp, _vp]),
+    "mimi_enc_pool_debug_latent": (_i, [_vp, _vp, _l, _vp]),
 }
 
 for _name, (_res, _args) in list(SIGNATURES.items()) + list(MIMI_SIGNATURES.items()):

@@ -404,6 +404,16 @@ class MimiCodec:
         codes = codes.long()
         return list(codes.split(frames, dim=1))
 
+    @torch.inference_mode()
+    def encode_latent(self, frames: int) -> torch.Tensor:
+        """For tests: the pre-quantisation latent of the LAST ``encode`` / ``_encode_call`` on this codec, (frames, hidden) fp32 -- what both
+        RVQ input projections read (mimi_debug_encode_latent, include/mimi_hip.h).  ``frames`` is that call's frame count: T of ``encode``
+        (for B > 1 the rows are the last clip's), the sum of the clips' frames of one ``encode_many`` call, clip i in rows [F_i, F_i + T_i).
+        A count that disagrees with the call is refused."""
+        out = torch.empty(int(frames), self.args.hidden, dtype=torch.float32, device=self.device)
+        check(lib.mimi_debug_encode_latent(self._h, out.data_ptr(), int(frames), _stream()), self._h, mimi=True)
+        return out
+
     def _run(self, codes: torch.Tensor, stateful: bool) -> torch.Tensor:
         assert codes.dim() == 3 and codes.shape[1] == self.args.num_codebooks, "codes must be (B, 32, T)"
         B, K, T = codes.shape
@@ -585,6 +595,14 @@ class MimiEncodeStreamPool:
         for i, x in zip(ids, lens):
             self._ended[i] = x % hop != 0
         return list(codes.long().split(frames, dim=1))
+
+    @torch.inference_mode()
+    def encode_latent(self, frames: int) -> torch.Tensor:
+        """For tests: the pre-quantisation latent of the pool's LAST ``encode`` call, (frames, hidden) fp32, ``frames`` = the sum of that
+        call's chunk frames; chunk i owns rows [F_i, F_i + T_i) (mimi_enc_pool_debug_latent).  A count that disagrees is refused."""
+        out = torch.empty(int(frames), self.codec.args.hidden, dtype=torch.float32, device=self.codec.device)
+        self._check(lib.mimi_enc_pool_debug_latent(self._h, out.data_ptr(), int(frames), _stream()))
+        return out
 
     def __del__(self):
         try:

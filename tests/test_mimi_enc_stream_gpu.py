@@ -87,9 +87,10 @@ def test_seam_clips_one_call_on_fresh_streams_and_the_oracle(tiny):
     s, w, codec, clips, alone = tiny
     pool = codec.open_encode_streams(len(clips), max_chunk_frames=17)
     got = pool.encode(range(len(clips)), clips)                         # 42 frames: the 32-row tile seam inside a stream and between streams
+    lat = pool.encode_latent(sum(SEAM_FRAMES)).split(SEAM_FRAMES)       # the call's latent: stream i owns rows [F_i, F_i + T_i)
     for i, (g, a, c) in enumerate(zip(got, alone, clips)):
         assert g.shape == (32, SEAM_FRAMES[i]) and torch.equal(g, a), f"clip {i} ({c.shape[0]} samples) differs from its single encode"
-        _check_codes(g.unsqueeze(0), s, w, c.view(1, 1, -1), f"encode stream, clip {i} ({c.shape[0]} samples)")
+        _check_codes(g.unsqueeze(0), s, w, c.view(1, 1, -1), f"encode stream, clip {i} ({c.shape[0]} samples)", latent=lat[i])
         assert pool.ended(i) == (c.shape[0] % HOP != 0)
     pool.reset()
     for i, (c, a) in enumerate(zip(clips, alone)):                      # each alone, on a stream that has just been used

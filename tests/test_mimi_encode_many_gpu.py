@@ -52,10 +52,11 @@ def test_seams_every_clip_equals_its_single_encode_and_the_oracle(tiny):
     s, w, codec, clips, alone = tiny
     got = codec.encode_many(clips)
     assert len(got) == len(clips)
+    lat = codec.encode_latent(sum(SEAM_FRAMES)).split(SEAM_FRAMES)      # one call of 42 frames: clip i owns rows [F_i, F_i + T_i)
     for i, (g, a, c) in enumerate(zip(got, alone, clips)):
         assert g.dtype == torch.int64 and g.shape == (32, SEAM_FRAMES[i])
         assert torch.equal(g, a), f"clip {i} ({c.shape[0]} samples) differs from its single encode"
-        _check_codes(g.unsqueeze(0), s, w, c.view(1, 1, -1), f"ragged encode, clip {i} ({c.shape[0]} samples)")
+        _check_codes(g.unsqueeze(0), s, w, c.view(1, 1, -1), f"ragged encode, clip {i} ({c.shape[0]} samples)", latent=lat[i])
 
 
 def test_company_and_order_do_not_matter(tiny):

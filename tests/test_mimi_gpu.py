@@ -105,14 +105,52 @@ def test_codes_beyond_codebook_are_clamped(tiny_codec):
     assert torch.equal(codec.decode(hi), codec.decode(cl))
 
 
-def _check_codes(got, s, w, wav, what):
+def _teacher_forced_walk(got, s, w, latent, what):
+    """The quantiser on its own, EVERY level of EVERY frame: ``latent`` is the GPU's own pre-quantisation latent, (b, T, hidden) -- or
+    (T, hidden), b = 1 -- of the LAST b rows of ``got`` (B, K, T), so the encoder's rounding is out of the way.  In float64: project it
+    with the oracle's input projections, form each level's residual from the centroids the GPU chose so far, and require the GPU's pick
+    to be within 1e-4 (relative distance) of the minimum over all centroids -- also on the levels of a frame that parted from the oracle
+    earlier.  A pick that is not the float64 argmin must be one of the walk's own near-ties: their number is capped by the number of
+    float64 decisions whose two nearest centroids are closer than 1e-4, which is counted here."""
+    z = latent.detach().cpu().double()
+    z = z[None] if z.dim() == 2 else z
+    g = got[got.shape[0] - z.shape[0]:]
+    assert z.shape[:2] == (g.shape[0], g.shape[2]) and z.shape[2] == s.hidden, f"{what}: latent {tuple(z.shape)} for codes {tuple(g.shape)}"
+    assert torch.isfinite(z).all(), f"{what}: the GPU latent is not finite"
+    emb = lambda k: w[f"rvq.{k}.embedding_sum"].double() / w[f"rvq.{k}.cluster_usage"].double().clamp(min=1e-5)[:, None]
+    n_off, n_close, worst, decisions = 0, 0, 0.0, 0
+    for proj, levels in (("rvq_first.input_proj.weight", range(0, s.num_semantic)), ("rvq_rest.input_proj.weight", range(s.num_semantic, s.num_codebooks))):
+        res = z @ w[proj][:, :, 0].double().t()                                      # (b, T, D)
+        for k in levels:
+            e = emb(k)
+            d = torch.cdist(res.reshape(1, -1, res.shape[-1]), e[None], p=2)[0].view(*res.shape[:2], -1)
+            two = d.topk(2, dim=-1, largest=False).values
+            n_close += int(((two[..., 1] - two[..., 0]) / two[..., 0].clamp(min=1e-12) < 1e-4).sum())
+            dg = torch.gather(d, 2, g[:, k].unsqueeze(-1))[..., 0]
+            rel = (dg - two[..., 0]) / two[..., 0].clamp(min=1e-12)
+            worst = max(worst, rel.max().item())
+            assert rel.max().item() <= 1e-4, (f"{what}: level {k}, given the GPU's own latent and earlier picks, takes a centroid "
+                                              f"{rel.max().item():.3g} farther (relative) than the float64 nearest")
+            n_off += int((g[:, k] != d.argmin(dim=-1)).sum())
+            decisions += g[:, k].numel()
+            res = res - torch.nn.functional.embedding(g[:, k], e)
+    print(f"{what}: teacher-forced float64 walk on the GPU latent: {decisions} decisions, {n_off} not the float64 argmin "
+          f"(worst relative distance gap {worst:.2e}), {n_close} float64 near-ties under 1e-4")
+    assert n_off <= n_close, f"{what}: {n_off} picks are not the float64 argmin, but only {n_close} decisions of the walk are near-ties"
+
+
+def _check_codes(got, s, w, wav, what, latent=None):
     """RVQ codes are integers: bit-exact, except that an fp32 near-tie between two centroids may fall the other way, after
     which the remaining levels of that frame's stack legitimately differ.  So walk the oracle's residual quantiser and
     require, at the FIRST level where a frame's codes part, that the two centroids are equidistant to 1e-4 (relative) from
-    the oracle's residual; everything before that level must be identical, and >= 90 % of the frames must match throughout."""
+    the oracle's residual; everything before that level must be identical, and >= 90 % of the frames must match throughout.
+    ``latent``: the GPU's own latent of the last rows of ``got``; then the quantiser is also graded on its own, with no frame
+    excused (``_teacher_forced_walk``)."""
     import torch.nn.functional as F
     from oracle import mimi_ref as M
     got = got.cpu()
+    if latent is not None:
+        _teacher_forced_walk(got, s, w, latent, what)
     want = M.encode(s, w, wav)
     assert got.shape == want.shape and got.dtype == torch.int64
     z = M.encode_latent(s, w, wav)
@@ -148,7 +186,7 @@ def test_tiny_encode_vs_oracle(tiny_codec):
     wav = torch.randn(2, 1, 1920 * 9 + 777, generator=torch.Generator().manual_seed(12)) * 0.3
     codes = codec.encode(wav)
     assert codes.shape == (2, 32, 10)
-    _check_codes(codes, s, w, wav, "tiny encode")
+    _check_codes(codes, s, w, wav, "tiny encode", latent=codec.encode_latent(10))        # (B = 2: the last clip's latent)
     # encode -> decode round trip runs and has the right length
     pcm = codec.decode(codes)
     assert pcm.shape == (2, 1, 10 * 1920) and torch.isfinite(pcm).all()
@@ -186,7 +224,8 @@ def test_full_size_encode_vs_oracle():
     w = M.make_weights(s, seed=4321, encoder=True)
     codec = MimiCodec(MimiArgs(), synthetic_state_dict(MimiArgs(), seed=4321), max_frames=32)
     wav = torch.randn(1, 1, 1920 * 20 + 5, generator=torch.Generator().manual_seed(13)) * 0.3
-    _check_codes(codec.encode(wav), s, w, wav, "full-size encode")
+    codes = codec.encode(wav)
+    _check_codes(codes, s, w, wav, "full-size encode", latent=codec.encode_latent(21))
 
 
 def test_full_size_decode_vs_golden():

@@ -231,9 +231,10 @@ def test_voice_prompts_encode_vs_golden_and_oracle(full):
         wav = mimi_long_wav(int(g["wav_seed"]), n)
         assert abs(float(wav.double().abs().sum()) - g["wav_checksum"]) <= 1e-9 * g["wav_checksum"], "the seeded prompt is not the fixture's"
         T = -(-n // 1920)
-        codes = _codec(sd, T).encode(wav)
+        codec = _codec(sd, T)
+        codes = codec.encode(wav)
         assert codes.shape == (1, 32, T) == tuple(g["codes"].shape)
-        _check_codes(codes, s, w, wav, f"full-size encode, {n} samples ({T} frames)")
+        _check_codes(codes, s, w, wav, f"full-size encode, {n} samples ({T} frames)", latent=codec.encode_latent(T))
         same = (codes.cpu() == g["codes"].long()).all(dim=1).float().mean().item()
         print(f"full-size encode, {n} samples: frames identical to the golden on all levels {same:.3f}")
         assert same >= 0.9
@@ -250,11 +251,11 @@ def test_encode_batch_of_two_and_length_edges_vs_oracle(full):
     codec = _codec(sd, T)
     codes = codec.encode(wav)
     assert codes.shape == (2, 32, T)
-    _check_codes(codes, s, w, wav, f"full-size encode, B = 2, {n} samples")
+    _check_codes(codes, s, w, wav, f"full-size encode, B = 2, {n} samples", latent=codec.encode_latent(T))      # (the last clip's latent)
     assert [m for m, _ in MIMI_LONG["encode_edges"]] == [1919, 1920, 1921, 9600]
     for n, seed in MIMI_LONG["encode_edges"]:
         wav = mimi_long_wav(seed, n)
         T = -(-n // 1920)
         codes = codec.encode(wav)
         assert codes.shape == (1, 32, T), f"{n} samples: {tuple(codes.shape)}"
-        _check_codes(codes, s, w, wav, f"full-size encode, {n} samples ({T} frame{'s' if T > 1 else ''})")
+        _check_codes(codes, s, w, wav, f"full-size encode, {n} samples ({T} frame{'s' if T > 1 else ''})", latent=codec.encode_latent(T))
