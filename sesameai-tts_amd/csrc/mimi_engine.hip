@@ -761,16 +761,32 @@ struct MimiDecoder {
     std::string err;
 };
 
-struct MimiStreamPool {
+// What a decode pool and an encode pool are alike in: N streams on one ladder, each with its token offset and its K/V ring.
+struct PoolBase {
     MimiConfig cfg;
     MimiWeights w;
     int n_streams = 0, max_chunk = 0, ring = 0;
-    std::vector<long> offset;                       // tokens each stream has decoded so far
+    std::vector<long> offset;                       // tokens each stream has decoded / encoded so far
     Ladder b;
     int* tab = nullptr;                             // device table of the running call: [i] stream id, [MIMI_POOL_MAX_STREAMS + i] token offset;
-                                                    // a ragged call also fills the rest: per segment F0 and T, then frame -> segment (pool_segs.h)
+                                                    // a ragged call also fills the rest (pool_segs.h; an encode pool's: enc_stream_segs.h)
     std::string err;
+    ~PoolBase();                                    // frees the ladder and the table (safe on a half-built pool: every pointer starts null)
 };
+
+struct MimiStreamPool : PoolBase {};
+
+// The encoder on the pool's ladder: stage j lives in the stage buffers of index S-1-j, as in a handle's encode, but every buffer that feeds
+// a convolution with taps keeps each stream's rows IN PLACE behind its history, so the left padding of the whole-clip encode (zeros; row 0
+// replicated for the downsample) becomes the rows the stream's previous call left there.
+struct MimiEncStreamPool : PoolBase {
+    std::vector<unsigned char> ended;               // the stream took a partial last frame: refused until reset
+    long* ltab = nullptr;                           // ENC_STREAM_LTAB_LONGS longs behind the table's words (same allocation)
+    float* wav_tail = nullptr;                      // [stream][kernel - 1]: the samples in front of the next chunk's first
+    long enc_rows = 0;                              // frames of the last encode call: its latent lies dense in b.rvq
+    ~MimiEncStreamPool() { (void)hipFree(wav_tail); }
+};
+static_assert(MIMI_ENC_POOL_MAX_STREAMS == MIMI_POOL_MAX_STREAMS, "PoolIds and pool_ids() serve both kinds of pool");
 
 // h: a handle or a pool (anything with .err), or a null pointer of either type: the thread's error
 #define MCHK(h, x)                                                                                     \
@@ -790,6 +806,9 @@ static int fail(H* h, const char* msg) {
     return -1;
 }
 static int fail(decltype(nullptr), const char* msg) { return fail((MimiDecoder*)nullptr, msg); }
+// "<the entry point's name>: <what a plan or a check found wrong>"
+template <class H>
+static int fail(H* h, const char* who, const char* bad) { return fail(h, (std::string(who) + ": " + bad).c_str()); }
 
 extern "C" void csm_warn_unknown_switches(void);     // csm_engine.hip: names under CSM_ / MIMI_ that no switch reads, once per process
 
@@ -804,6 +823,11 @@ static const char* config_error(const MimiConfig* cfg) {
     for (int j = 0; j < cfg->n_stages; ++j) { c /= 2; if ((c / 2) % 32) return "mimi_create: SEANet channels must stay multiples of 32"; }
     return nullptr;
 }
+
+// columns of ffn where an encoder runs on the ladder (a handle, an encode pool): ffn is also the RVQ score buffer of quantize()
+static int enc_ffn_cols(const MimiConfig& c) { return c.tr_ffn > c.codebook_size ? c.tr_ffn : c.codebook_size; }
+// samples per frame: rows per frame at level 0 of the encoder (enc_segs.h), the decoder's 2 * prod(ratios)
+static long samples_per_frame(const MimiConfig& c) { return enc_level_rate(c.ratios, c.n_stages, 0); }
 
 // The ladder of N streams of up to `frames` frames a call, kv_rows K/V rows per stream and layer, ffn_cols columns of ffn.
 // enc: the histories the ENCODER's taps need (an encode stream pool): two rows of a0 in front of the 4-tap downsample, last_kernel - 1 rows
@@ -856,6 +880,7 @@ static void ladder_free(Ladder& b) {                 // (safe on a half-built la
     void* ps[] = {b.tok, b.ln, b.q, b.att, b.ffn, b.kc, b.vc, b.ksw.part, b.ksw.ticket};
     for (void* p : ps) (void)hipFree(p);
 }
+PoolBase::~PoolBase() { ladder_free(b); (void)hipFree(tab); }
 
 // the buffers with history, with the rows a chunk of T frames adds to each (reset: T = 0)
 static PoolRegions hist_regions(const Ladder& b, int T) {
@@ -877,8 +902,7 @@ extern "C" int mimi_create(const MimiConfig* cfg, const MimiWeights* w, int max_
     MimiDecoder* m = new MimiDecoder();
     m->cfg = *cfg; m->w = *w; m->max_frames = max_frames; m->offset = 0;
     m->cap_tokens = 2L * max_frames;
-    // (ffn is also the encoder's RVQ score buffer)
-    const int rc = ladder_alloc(m, m->b, *cfg, 1, max_frames, m->cap_tokens, cfg->tr_ffn > cfg->codebook_size ? cfg->tr_ffn : cfg->codebook_size);
+    const int rc = ladder_alloc(m, m->b, *cfg, 1, max_frames, m->cap_tokens, enc_ffn_cols(*cfg));
     if (rc) { g_mimi_err = m->err; mimi_destroy(m); return rc; }
     if (w->has_encoder) {
         const size_t clips_bytes = sizeof(EncClipTab) * MIMI_ENCODE_MAX_CLIPS;
@@ -964,6 +988,16 @@ static Product conv(const float* x, long ldx, long rows, const MimiConv& cv, flo
     return Product{x, ldx, rows, cv.w, cv.bias, cv.c_in, cv.c_out, cv.taps, cv.phases, out, ldo}.taps_at(-(cv.taps - 1), 1);
 }
 
+// the ten k_gemm32 instantiations there are, [variant][ELU]: <ELU, SEG, RAG, PRG, ENS>
+enum { G32_PLAIN, G32_SEG, G32_SEG_PRG, G32_SEG_PRG_ENS, G32_RAG };
+static void (*const k_gemm32_of[5][2])(const GemmArgs) = {
+    {k_gemm32<false>, k_gemm32<true>},
+    {k_gemm32<false, true>, k_gemm32<true, true>},
+    {k_gemm32<false, true, false, true>, k_gemm32<true, true, false, true>},
+    {k_gemm32<false, true, false, true, true>, k_gemm32<true, true, false, true, true>},
+    {k_gemm32<false, false, true>, k_gemm32<true, false, true>},
+};
+
 static hipError_t gemm(hipStream_t st, const Product& g) {
     GemmArgs a;
     memset(&a, 0, sizeof a);
@@ -989,35 +1023,23 @@ static hipError_t gemm(hipStream_t st, const Product& g) {
             grid.z = (unsigned)ksw->ksplit;
         }
     }
+    // the instantiation: a variant (a table wins over a clip list, as it always has; ens_L counts in a ragged pool call only) and ELU
+    int v = G32_PLAIN;
     if (seg) {
         const SegArgs& s = g.sg;
         a.seg_T = s.T; a.seg_x = s.x; a.seg_o = s.o; a.seg_r = s.r; a.seg_by_id = s.by_id; a.rope_ring = s.ring; a.seg_tab = s.tab;
-        if (s.ragged && g.ens_L >= 0) {
-            a.ens_L = g.ens_L;
-            if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true, false, true, true>), grid, dim3(64 * G32_NW), 0, st, a);
-            else hipLaunchKernelGGL((k_gemm32<false, true, false, true, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        }
-        else if (s.ragged) {
-            if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
-            else hipLaunchKernelGGL((k_gemm32<false, true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        }
-        else if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        else hipLaunchKernelGGL((k_gemm32<false, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        return hipGetLastError();
-    }
-    if (g.rg.clips != nullptr) {
+        v = !s.ragged ? G32_SEG : g.ens_L < 0 ? G32_SEG_PRG : G32_SEG_PRG_ENS;
+        if (v == G32_SEG_PRG_ENS) a.ens_L = g.ens_L;
+    } else if (g.rg.clips != nullptr) {
         a.rag = g.rg;
-        if (g.elu_in) hipLaunchKernelGGL((k_gemm32<true, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        else hipLaunchKernelGGL((k_gemm32<false, false, true>), grid, dim3(64 * G32_NW), 0, st, a);
-        return hipGetLastError();
+        v = G32_RAG;
     }
-    if (g.elu_in) hipLaunchKernelGGL(k_gemm32<true>, grid, dim3(64 * G32_NW), 0, st, a);
-    else hipLaunchKernelGGL(k_gemm32<false>, grid, dim3(64 * G32_NW), 0, st, a);
+    hipLaunchKernelGGL(k_gemm32_of[v][g.elu_in], grid, dim3(64 * G32_NW), 0, st, a);
     return hipGetLastError();
 }
 
-// ---- the two chains every user shares --------------------------------------------------------------------------------------------------
-// What differs between the transformer's three users: the handle's decode, its encode, and the pool.
+// ---- the chains every user shares: transformer, SEANet decoder, encoder ------------------------------------------------------------------
+// What differs between the transformer's users: the handle's decode, the decode pool, and the encoder's three (EncPass below).
 struct TrPass {
     const MimiTrLayer* layers;
     long rows;                      // 2T (decode), L (encode), n * 2T (pool: the listed streams' rows stacked)
@@ -1028,6 +1050,36 @@ struct TrPass {
     bool ragged = false;            // pool only: a ragged call -- rows = 2 F, T2 = 2 (the tokens of one frame), the streams frame-aligned
     const RagArgs* rag = nullptr;   // ragged encode only: the clips' table (RoPE position and attention window inside the token's clip)
 };
+
+// What differs between the encoder's three users: one clip (mimi_encode), a clip list (mimi_encode_many) and an encode stream pool.  The
+// last two are frame-aligned: a clip or a chunk owns whole frames, R rows each at a level with R rows per frame.
+struct EncPass {
+    long rows0, frames;             // rows at level 0 (the one clip's samples, or frames * samples per frame); frames: the latent's rows
+    const RagArgs* rag = nullptr;   // clip list only: the clips' table (the RAG instantiation)
+    const int* tab = nullptr;       // pool only: the call's table (SEG + PRG; ENS where a product reaches forward) and the K/V ring
+    int ring = 0;
+    // the encoder transformer's pass over `rows` tokens: stateless, or on the pool's rings.  No K split (TrPass::lin2_ksplit says why).
+    TrPass tr(const MimiWeights& w, long rows) const {
+        TrPass tp{w.enc_tr, rows};
+        tp.lin2_ksplit = false; tp.rag = rag; tp.tab = tab; tp.T2 = 2; tp.ring = ring; tp.ragged = tab != nullptr;
+        return tp;
+    }
+    // The ONE place that says how a product learns where its input ends.  reach: the rows its taps read -- its OWN, BACK from it, also
+    // FORWARD; kind: 1 zero, 2 replicate padding; L: the launch's rows at the input level; hist: the input buffer's history rows.
+    //  * Clips: [0, L), and from the clip list's table the row's own clip inside it.  The one-tap res2 never leaves its row, so it takes no
+    //    table: in a clip list too it stays the plain instantiation, its padding an edge that is never reached.
+    //  * Pool: every stream's history lies in place, so res2, res1 and the output convolution read rows that are always there -- a decode
+    //    pool's ragged product, no edge.  The strided products (down-convolutions, downsample) also reach forward, to where a stream's
+    //    last partial frame has the whole-clip encode's right padding: seg_edges.
+    enum Reach { OWN, BACK, FORWARD };
+    Product& edges(Product& g, const MimiConfig& c, Reach reach, int lvl_in, int lvl_out, int kind, long L, int hist) const {
+        if (tab) return reach == FORWARD ? g.seg_edges(kind, hist, lvl_in) : g;
+        if (kind == 1) g.zero_padded(0, L); else g.replicate_padded(0, L);
+        return reach == OWN ? g : g.rag(rag, lvl_in, lvl_out, c);
+    }
+};
+
+static long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
 // layernorm, q|k|v + RoPE, attention, out-proj + LayerScale + residual, layernorm, lin1 + GELU, lin2 + LayerScale + residual: tok -> a0
 template <class H>
@@ -1077,6 +1129,78 @@ static int seanet_decoder(H* h, const MimiWeights& w, int n_stages, Ladder& b, i
                              .seg({Tj, Tj, xj.seg(), u.seg(), 2 | 4, 0, tab, rg})));
         xin = &xj;
     }
+    return 0;
+}
+
+// SEANet encoder, from the first convolution's output (in u[S-1]; the front kernels write it) to tok: per stage res1 / res2 / strided
+// down-conv, then the output convolution.  Stage j lives in the decoder's stage buffers of index S-1-j (same time scale and width).
+// *tok_rows: the rows at the tokens' level.  (.seg() without a table -- the clips -- is a no-op, as in seanet_decoder.)
+template <class H>
+static int seanet_encoder(H* h, const MimiConfig& c, const MimiWeights& w, Ladder& b, const EncPass& p, hipStream_t st, long* tok_rows) {
+    const int S = c.n_stages;
+    long L = p.rows0;                                                   // rows of a launch at the current level
+    int R = (int)samples_per_frame(c), C = c.n_filters;                 // its rows per frame, its channels
+    for (int j = 0; j < S; ++j) {
+        const int bi = S - 1 - j;
+        const MimiConv &r1 = w.enc_res1[j], &r2 = w.enc_res2[j], &dn = w.enc_down[j];
+        const SegBuf &u = b.u(bi), &xj = b.xj(bi), &nxt = (j + 1 < S) ? b.u(bi - 1) : b.s0;
+        // residual block: u + conv_k1(ELU(conv_k3(ELU(u))))
+        MCHK(h, gemm(st, p.edges(conv(u.row0(), C, L, r1, b.r1[bi], r1.c_out).elu().seg({R, u.seg(), R, 0, 1, 0, p.tab, true}),
+                                 c, EncPass::BACK, j, j, 1, L, u.hist)));
+        MCHK(h, gemm(st, p.edges(conv(b.r1[bi], r1.c_out, L, r2, xj.row0(), C).elu().residual(u.row0(), C).seg({R, R, xj.seg(), u.seg(), 2 | 4, 0, p.tab, true}),
+                                 c, EncPass::OWN, j, j, 1, L, 0)));
+        // ELU -> strided conv k = 2r: out[t] = sum_k W_k x[t*r + k - r]; zero padding on both sides.  Frame-aligned rows divide exactly
+        // (frames * R, r divides R); one clip's last row rounds up, the partial window the right padding completes.
+        const int r = dn.taps / 2;
+        const long Lo = (p.rag || p.tab) ? L / r : ceil_div(L, r);
+        MCHK(h, gemm(st, p.edges(conv(xj.row0(), C, Lo, dn, nxt.row0(), dn.c_out).taps_at(-r, 1).stride(r).elu().seg({R / r, xj.seg(), nxt.seg(), 0, 1 | 2, 0, p.tab, true}),
+                                 c, EncPass::FORWARD, j, j + 1, 1, L, xj.hist)));
+        L = Lo; R /= r; C = dn.c_out;
+    }
+    MCHK(h, gemm(st, p.edges(conv(b.s0.row0(), C, L, w.enc_conv_out, b.tok, c.hidden).elu().seg({R, b.s0.seg(), R, 0, 1, 0, p.tab, true}),
+                             c, EncPass::BACK, S, S, 1, L, b.s0.hist)));
+    *tok_rows = L;
+    return 0;
+}
+
+// stride-2 downsample, taps at rows 2t - 2 .. 2t + 1, replicate padding, no bias: a0 -> the latent, dense in the rvq buffer [frames][d]
+template <class H>
+static int encode_downsample(H* h, const MimiConfig& c, const MimiWeights& w, Ladder& b, const EncPass& p, long tok_rows, hipStream_t st) {
+    const int d = c.hidden, S = c.n_stages;
+    const MimiConv down = {w.downsample, nullptr, d, d, 4, 1};
+    MCHK(h, gemm(st, p.edges(conv(b.a0.row0(), d, p.frames, down, b.rvq.row0(), d).taps_at(-2, 1).stride(2).seg({1, b.a0.seg(), 1, 0, 1, 0, p.tab, true}),
+                             c, EncPass::FORWARD, S, S + 1, 2, tok_rows, b.a0.hist)));
+    return 0;
+}
+
+// split RVQ of the latent's `rows` rows: semantic level on in_proj_first(z), acoustic levels on in_proj_rest(z); per codebook the scores
+// against the residual (into ffn), then nearest centroid and residual update -> codes [codebook][rows]
+template <class H>
+static int quantize(H* h, const MimiConfig& c, const MimiWeights& w, Ladder& b, long rows, int32_t* codes, hipStream_t st) {
+    const int d = c.hidden, cd = c.codebook_dim;
+    float *res_first = b.ln, *res_rest = b.q;       // [rows][cd]
+    MCHK(h, gemm(st, linear(b.rvq.row0(), d, rows, w.in_proj_first, d, cd, res_first, cd)));
+    MCHK(h, gemm(st, linear(b.rvq.row0(), d, rows, w.in_proj_rest, d, cd, res_rest, cd)));
+    for (int k = 0; k < c.n_codebooks; ++k) {
+        float* res = k < c.n_semantic ? res_first : res_rest;
+        const float* book = w.codebooks + (long)k * c.codebook_size * cd;
+        MCHK(h, gemm(st, linear(res, cd, rows, book, cd, c.codebook_size, b.ffn, c.codebook_size)));
+        hipLaunchKernelGGL(k_rvq_pick, dim3((unsigned)rows), dim3(256), 0, st, b.ffn, c.codebook_size,
+                           w.codebook_sqnorm + (long)k * c.codebook_size, book, cd, res, codes + (long)k * rows, 1L);
+        MCHK(h, hipGetLastError());
+    }
+    return 0;
+}
+
+// every buffer with history slides by its stream's chunk, for the call's n listed streams in one launch: `per` frames each, or -- PRG, a
+// ragged call -- per = 1 and each stream's own frame count from the table
+template <bool PRG, class H>
+static int pool_slide(H* h, const Ladder& b, int per, int n, const int* tab, hipStream_t st) {
+    const PoolRegions z = hist_regions(b, per);
+    int maxC = 0;
+    for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
+    hipLaunchKernelGGL(k_pool_slide<PRG>, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
+    MCHK(h, hipGetLastError());
     return 0;
 }
 
@@ -1159,82 +1283,36 @@ static int slide_all(MimiDecoder* m, int T, hipStream_t st) {
     return 0;
 }
 
-static long ceil_div(long a, long b) { return (a + b - 1) / b; }
-
 // One clip of n samples (T frames), or -- rag: the table of a ragged encode -- the clips of the table in their frame-aligned slots: T = the
 // call's frames in all, every level runs over all of its rate * T rows, and the products that reach beyond their own row take the edge
-// bounds of the row's clip from the table (the RAG instantiation) in place of [0, L).
+// bounds of the row's clip from the table (the RAG instantiation) in place of [0, L).  No left context here: the input is zero-padded.
 static int encode_one(MimiDecoder* m, const float* wav, long n, int32_t* codes, long T, hipStream_t st, const RagArgs* rag = nullptr) {
     const MimiConfig& c = m->cfg;
     const MimiWeights& w = m->w;
     Ladder& b = m->b;
-    const int d = c.hidden, S = c.n_stages;
-    // SEANet encoder; stage j lives in the decoder's stage buffers of index S-1-j (same time scale and width).  There is no left context
-    // here: the products read their input zero-padded over [0, L)
-    const long hop = enc_level_rate(c.ratios, S, 0);
-    long L = rag ? hop * T : n;
-    int C = c.n_filters;
-    {
-        const long tot = L * C;
-        if (rag) hipLaunchKernelGGL(k_enc_conv_in_many, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, L, (int)hop, c.kernel, C,
-                                    w.enc_conv_in_w, w.enc_conv_in_b, rag->clips, rag->frame_clip, b.u(S - 1).row0());
-        else hipLaunchKernelGGL(k_enc_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, L, c.kernel, C,
-                           w.enc_conv_in_w, w.enc_conv_in_b, b.u(S - 1).row0());
-    }
-    for (int j = 0; j < S; ++j) {
-        const int bi = S - 1 - j;
-        const MimiConv &r1 = w.enc_res1[j], &r2 = w.enc_res2[j], &dn = w.enc_down[j];
-        float* x = b.u(bi).row0();
-        MCHK(m, gemm(st, conv(x, C, L, r1, b.r1[bi], r1.c_out).elu().zero_padded(0, L).rag(rag, j, j, c)));
-        MCHK(m, gemm(st, conv(b.r1[bi], r1.c_out, L, r2, b.xj(bi).row0(), C).elu().residual(x, C).zero_padded(0, L)));
-        // ELU -> strided conv k = 2r: out[t] = sum_k W_k x[t*r + k - r]; zero padding on both sides
-        const int r = dn.taps / 2;
-        const long Lo = rag ? L / r : ceil_div(L, r);
-        float* out = (j + 1 < S) ? b.u(bi - 1).row0() : b.s0.row0();
-        MCHK(m, gemm(st, conv(b.xj(bi).row0(), C, Lo, dn, out, dn.c_out).taps_at(-r, 1).stride(r).elu().zero_padded(0, L).rag(rag, j, j + 1, c)));
-        L = Lo; C = dn.c_out;
-    }
-    MCHK(m, gemm(st, conv(b.s0.row0(), C, L, w.enc_conv_out, b.tok, d).elu().zero_padded(0, L).rag(rag, S, S, c)));
-    // encoder transformer (stateless) -> a0
-    TrPass tp{w.enc_tr, L};
-    tp.lin2_ksplit = false;
-    tp.rag = rag;
-    if (transformer(m, c, w, b, tp, st)) return -2;
-    // stride-2 downsample, taps at rows 2t - 2 .. 2t + 1, replicate padding, no bias -> rvq buffer [T][d]
-    const MimiConv down = {w.downsample, nullptr, d, d, 4, 1};
-    MCHK(m, gemm(st, conv(b.a0.row0(), d, T, down, b.rvq.row0(), d).taps_at(-2, 1).stride(2).replicate_padded(0, L).rag(rag, S, S + 1, c)));
-    // split RVQ: semantic level on in_proj_first(z), acoustic levels on in_proj_rest(z)
-    const int cd = c.codebook_dim;
-    float* res_first = b.ln;                    // [T][cd]
-    float* res_rest = b.q;                      // [T][cd]
-    MCHK(m, gemm(st, linear(b.rvq.row0(), d, T, w.in_proj_first, d, cd, res_first, cd)));
-    MCHK(m, gemm(st, linear(b.rvq.row0(), d, T, w.in_proj_rest, d, cd, res_rest, cd)));
-    for (int k = 0; k < c.n_codebooks; ++k) {
-        float* res = k < c.n_semantic ? res_first : res_rest;
-        const float* book = w.codebooks + (long)k * c.codebook_size * cd;
-        MCHK(m, gemm(st, linear(res, cd, T, book, cd, c.codebook_size, b.ffn, c.codebook_size)));
-        hipLaunchKernelGGL(k_rvq_pick, dim3((unsigned)T), dim3(256), 0, st, b.ffn, c.codebook_size,
-                           w.codebook_sqnorm + (long)k * c.codebook_size, book, cd, res, codes + (long)k * T, 1L);
-        MCHK(m, hipGetLastError());
-    }
-    return 0;
-}
-
-static long hop_of(const MimiConfig& c) {
-    long hop = 2;
-    for (int j = 0; j < c.n_stages; ++j) hop *= c.ratios[j];
-    return hop;
+    const long hop = samples_per_frame(c);
+    EncPass p{rag ? hop * T : n, T}; p.rag = rag;
+    // front: the first convolution (1 channel in) -> u[S-1]
+    const int C = c.n_filters; const long tot = p.rows0 * C;
+    if (rag) hipLaunchKernelGGL(k_enc_conv_in_many, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, p.rows0, (int)hop, c.kernel, C,
+                                w.enc_conv_in_w, w.enc_conv_in_b, rag->clips, rag->frame_clip, b.u(c.n_stages - 1).row0());
+    else hipLaunchKernelGGL(k_enc_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, p.rows0, c.kernel, C,
+                            w.enc_conv_in_w, w.enc_conv_in_b, b.u(c.n_stages - 1).row0());
+    long L;
+    if (int rc = seanet_encoder(m, c, w, b, p, st, &L)) return rc;
+    if (int rc = transformer(m, c, w, b, p.tr(w, L), st)) return rc;
+    if (int rc = encode_downsample(m, c, w, b, p, L, st)) return rc;
+    return quantize(m, c, w, b, T, codes, st);
 }
 
 extern "C" int mimi_encode(mimi_handle m, const float* wav, long n_samples, long stride_b, int B, int32_t* codes, void* stream) {
     if (!m || !wav || !codes || B < 1 || n_samples < 1) return fail(m, "mimi_encode: bad argument");
     if (!m->w.has_encoder) return fail(m, "mimi_encode: this codec was created without encoder weights");
-    const long T = ceil_div(n_samples, hop_of(m->cfg));
+    const long T = ceil_div(n_samples, samples_per_frame(m->cfg));
     if (T > m->max_frames) return fail(m, "mimi_encode: audio longer than hop * max_frames");
     hipStream_t st = (hipStream_t)stream;
     for (int b = 0; b < B; ++b) {
-        int rc = encode_one(m, wav + (long)b * stride_b, n_samples, codes + (long)b * m->cfg.n_codebooks * T, T, st);
-        if (rc) return rc;
+        if (int rc = encode_one(m, wav + (long)b * stride_b, n_samples, codes + (long)b * m->cfg.n_codebooks * T, T, st)) return rc;
     }
     m->enc_rows = T;
     return mimi_reset_stream(m, stream);      // the work buffers were reused: start any later stream from scratch
@@ -1244,10 +1322,8 @@ extern "C" int mimi_encode_many(mimi_handle m, const float* wav, const long* wav
     if (!m) return fail(m, "mimi_encode_many: null handle");
     EncHeader hdr;
     EncSegs sg;
-    if (const char* bad = enc_segs_build(wav, wav_off, n_samples, n, codes, m->w.has_encoder, m->cfg.ratios, m->cfg.n_stages, m->max_frames, &hdr, &sg)) {
-        m->err = std::string("mimi_encode_many: ") + bad;
-        return -1;
-    }
+    if (const char* bad = enc_segs_build(wav, wav_off, n_samples, n, codes, m->w.has_encoder, m->cfg.ratios, m->cfg.n_stages, m->max_frames, &hdr, &sg))
+        return fail(m, "mimi_encode_many", bad);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_enc_plan, dim3(1), dim3(256), 0, st, hdr, m->enc_clips, m->enc_frame_clip);
     MCHK(m, hipGetLastError());
@@ -1283,7 +1359,7 @@ extern "C" int mimi_decode_strided(mimi_handle m, const int32_t* codes, int B, i
     if (stateful && B != 1) return fail(m, "mimi_decode: stateful streaming needs B == 1");
     m->enc_rows = 0;                           // the code lookup writes the rvq buffer: the last encode's latent is gone
     hipStream_t st = (hipStream_t)stream;
-    const long hop = hop_of(m->cfg);
+    const long hop = samples_per_frame(m->cfg);
     for (int b = 0; b < B; ++b) {
         if (!stateful) { int rc = mimi_reset_stream(m, stream); if (rc) return rc; }
         if (m->offset + 2L * T > m->cap_tokens) return fail(m, "mimi_decode: stream longer than max_frames; call mimi_reset_stream");
@@ -1299,60 +1375,73 @@ extern "C" int mimi_decode(mimi_handle m, const int32_t* codes, int B, int T, lo
     return mimi_decode_strided(m, codes, B, T, stride_b, stride_k, 1, pcm, stateful, stream);
 }
 
-// ---- stream pool -----------------------------------------------------------------------------------------------------------------------
-extern "C" int mimi_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_pool* out) {
+// ---- the skeleton of both kinds of pool ---------------------------------------------------------------------------------------------------
+// What both create functions check and fill before they allocate anything: 0 and the new pool in *pp, or -1 and the thread's error under
+// the caller's name `who` (max_name: its n_streams limit, as the header spells it)
+template <class P>
+static int pool_new(const char* who, const char* max_name, bool need_encoder, const MimiConfig* cfg, const MimiWeights* w, const void* out,
+                    int n_streams, int max_chunk_frames, P** pp) {
     csm_warn_unknown_switches();
-    if (!cfg || !w || !out) return fail(nullptr, "mimi_pool_create: null argument");
-    if (n_streams < 1 || n_streams > MIMI_POOL_MAX_STREAMS) return fail(nullptr, "mimi_pool_create: n_streams must be 1 .. MIMI_POOL_MAX_STREAMS (64)");
-    if (max_chunk_frames < 1 || max_chunk_frames > 64) return fail(nullptr, "mimi_pool_create: max_chunk_frames must be 1 .. 64");
+    const std::string f = std::string(who) + ": ";
+    if (!cfg || !w || !out) return fail(nullptr, (f + "null argument").c_str());
+    if (need_encoder && !w->has_encoder) return fail(nullptr, (f + "these weights have no encoder").c_str());
+    if (n_streams < 1 || n_streams > POOL_SEG_MAX_STREAMS) return fail(nullptr, (f + "n_streams must be 1 .. " + max_name + " (64)").c_str());
+    if (max_chunk_frames < 1 || max_chunk_frames > POOL_SEG_MAX_CHUNK) return fail(nullptr, (f + "max_chunk_frames must be 1 .. 64").c_str());
     if (const char* bad = config_error(cfg)) return fail(nullptr, bad);
-    MimiStreamPool* p = new MimiStreamPool();
+    P* p = *pp = new P();
     p->cfg = *cfg; p->w = *w; p->n_streams = n_streams; p->max_chunk = max_chunk_frames;
     p->ring = cfg->tr_context + 2 * max_chunk_frames;        // a call's oldest key (offset - context + 1) and newest (offset + 2T - 1) never share a row
     p->offset.assign(n_streams, 0);
-    auto alloc = [&]() {
-        MCHK(p, hipMalloc((void**)&p->tab, (size_t)pool_tab_words(n_streams, max_chunk_frames) * 4));
-        return ladder_alloc(p, p->b, *cfg, n_streams, max_chunk_frames, p->ring, cfg->tr_ffn);
-    };
-    const int rc = alloc();
-    if (rc) { g_mimi_err = p->err; mimi_pool_destroy(p); return rc; }
-    *out = p;
     return 0;
 }
 
-extern "C" void mimi_pool_destroy(mimi_pool p) {
-    if (!p) return;
-    ladder_free(p->b);
-    (void)hipFree(p->tab);
-    delete p;
-}
-
-extern "C" const char* mimi_pool_last_error(mimi_pool p) { return p ? p->err.c_str() : g_mimi_err.c_str(); }
-
-// distinct ids in range -> PoolIds (offsets filled by the caller); nullptr or the reason
-static const char* pool_ids(const MimiStreamPool* p, const int32_t* streams, int n, PoolIds* ids) {
-    if (!streams || n < 1 || n > p->n_streams) return "stream list: need 1 .. n_streams ids";
+// distinct ids in range -> PoolIds (offsets filled by the caller): 0, or -1 and the pool's error under the caller's name
+static int pool_ids(PoolBase* p, const char* who, const int32_t* streams, int n, PoolIds* ids) {
+    if (!streams || n < 1 || n > p->n_streams) return fail(p, who, "stream list: need 1 .. n_streams ids");
     bool seen[MIMI_POOL_MAX_STREAMS] = {};
     for (int i = 0; i < n; ++i) {
-        if (streams[i] < 0 || streams[i] >= p->n_streams) return "stream id outside [0, n_streams)";
-        if (seen[streams[i]]) return "duplicate stream id in one call";
+        if (streams[i] < 0 || streams[i] >= p->n_streams) return fail(p, who, "stream id outside [0, n_streams)");
+        if (seen[streams[i]]) return fail(p, who, "duplicate stream id in one call");
         seen[streams[i]] = true;
         ids->sid[i] = streams[i]; ids->off[i] = 0;
     }
     ids->n = n;
-    return nullptr;
+    return 0;
 }
+
+// The listed streams start afresh: their history rows -- and `tail`, an encode pool's [stream][tail_n] samples -- to zero in one launch, their
+// token offsets to 0.  (The rings need no clearing: a window never starts before position 0, and every position is written before it is read.)
+static int pool_reset(PoolBase* p, const char* who, const int32_t* streams, int n, float* tail, int tail_n, void* stream) {
+    PoolIds ids;
+    if (int rc = pool_ids(p, who, streams, n, &ids)) return rc;
+    PoolRegions z = hist_regions(p->b, 0);
+    if (tail) { z.base[z.count] = tail; z.hist[z.count] = tail_n; z.C[z.count] = 1; z.seg[z.count] = tail_n; z.T[z.count] = 0; ++z.count; }
+    hipLaunchKernelGGL(k_pool_zero_hist, dim3(8, n, z.count), dim3(256), 0, (hipStream_t)stream, z, ids);
+    MCHK(p, hipGetLastError());
+    for (int i = 0; i < n; ++i) p->offset[streams[i]] = 0;
+    return 0;
+}
+
+// ---- stream pool -----------------------------------------------------------------------------------------------------------------------
+extern "C" int mimi_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_pool* out) {
+    MimiStreamPool* p = nullptr;
+    if (int rc = pool_new("mimi_pool_create", "MIMI_POOL_MAX_STREAMS", false, cfg, w, out, n_streams, max_chunk_frames, &p)) return rc;
+    auto alloc = [&]() {
+        MCHK(p, hipMalloc((void**)&p->tab, (size_t)pool_tab_words(n_streams, max_chunk_frames) * 4));
+        return ladder_alloc(p, p->b, *cfg, n_streams, max_chunk_frames, p->ring, cfg->tr_ffn);
+    };
+    if (const int rc = alloc()) { g_mimi_err = p->err; delete p; return rc; }
+    *out = p;
+    return 0;
+}
+
+extern "C" void mimi_pool_destroy(mimi_pool p) { delete p; }
+
+extern "C" const char* mimi_pool_last_error(mimi_pool p) { return p ? p->err.c_str() : g_mimi_err.c_str(); }
 
 extern "C" int mimi_pool_reset(mimi_pool p, const int32_t* streams, int n, void* stream) {
     if (!p) return fail(p, "mimi_pool_reset: null pool");
-    PoolIds ids;
-    if (const char* bad = pool_ids(p, streams, n, &ids)) { p->err = std::string("mimi_pool_reset: ") + bad; return -1; }
-    const PoolRegions z = hist_regions(p->b, 0);
-    // (the rings need no clearing: a window never starts before position 0, and every position is written before it is read)
-    hipLaunchKernelGGL(k_pool_zero_hist, dim3(8, n, z.count), dim3(256), 0, (hipStream_t)stream, z, ids);
-    MCHK(p, hipGetLastError());
-    for (int i = 0; i < n; ++i) p->offset[ids.sid[i]] = 0;
-    return 0;
+    return pool_reset(p, "mimi_pool_reset", streams, n, nullptr, 0, stream);
 }
 
 // The launch chain behind the call's first kernel, for both kinds of call.  The kernels take a UNIT and rows per unit: in a uniform call
@@ -1386,12 +1475,7 @@ static int pool_chain(MimiStreamPool* p, const int32_t* codes, long stride_s, lo
     const MimiConv& co = p->w.conv_out;
     hipLaunchKernelGGL(k_pool_conv_out<PRG>, dim3((unsigned)((units * Tj + 255) / 256)), dim3(256), 0, st, last.row0(), last.seg(), tab, Tj, units, co.c_in,
                        co.taps, co.w, co.bias, pcm);
-    const PoolRegions z = hist_regions(b, per);
-    int maxC = 0;
-    for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
-    hipLaunchKernelGGL(k_pool_slide<PRG>, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
-    MCHK(p, hipGetLastError());
-    return 0;
+    return pool_slide<PRG>(p, b, per, n, tab, st);
 }
 
 extern "C" int mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, const int32_t* codes, int T, long stride_s, long stride_k,
@@ -1400,7 +1484,7 @@ extern "C" int mimi_pool_decode(mimi_pool p, const int32_t* streams, int n, cons
     if (!codes || !pcm_out) return fail(p, "mimi_pool_decode: null codes or pcm");
     if (T < 1 || T > p->max_chunk) return fail(p, "mimi_pool_decode: T must be 1 .. max_chunk_frames given to mimi_pool_create");
     PoolIds ids;
-    if (const char* bad = pool_ids(p, streams, n, &ids)) { p->err = std::string("mimi_pool_decode: ") + bad; return -1; }
+    if (int rc = pool_ids(p, "mimi_pool_decode", streams, n, &ids)) return rc;
     for (int i = 0; i < n; ++i) {
         if (p->offset[ids.sid[i]] + 2L * T > 0x7fffffffL) return fail(p, "mimi_pool_decode: a stream passed 2^31 tokens; reset it");
         ids.off[i] = (int)p->offset[ids.sid[i]];
@@ -1417,10 +1501,8 @@ extern "C" int mimi_pool_decode_ragged(mimi_pool p, const int32_t* streams, cons
     if (!p) return fail(p, "mimi_pool_decode_ragged: null pool");
     PoolSegHeader hdr;
     PoolSegs sg;
-    if (const char* bad = pool_segs_build(streams, frames, n, codes, pcm_out, p->n_streams, p->max_chunk, p->offset.data(), &hdr, &sg)) {
-        p->err = std::string("mimi_pool_decode_ragged: ") + bad;
-        return -1;
-    }
+    if (const char* bad = pool_segs_build(streams, frames, n, codes, pcm_out, p->n_streams, p->max_chunk, p->offset.data(), &hdr, &sg))
+        return fail(p, "mimi_pool_decode_ragged", bad);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_pool_begin_ragged, dim3(1), dim3(256), 0, st, hdr, p->tab, p->b.ksw.ticket, p->b.ksw.ticket ? p->b.ksw.n_tickets : 0);
     if (int rc = pool_chain<true>(p, codes, stride_s, stride_k, stride_t, (float*)pcm_out, n, sg.F, 1, st)) return rc;
@@ -1428,40 +1510,15 @@ extern "C" int mimi_pool_decode_ragged(mimi_pool p, const int32_t* streams, cons
     return 0;
 }
 
-// ---- encode stream pool ------------------------------------------------------------------------------------------------------------------
-// The encoder on the pool's ladder: stage j lives in the stage buffers of index S-1-j, as in encode_one, but every buffer that feeds a
-// convolution with taps keeps each stream's rows IN PLACE behind its history, so the left padding of the whole-clip encode (zeros; row 0
-// replicated for the downsample) becomes the rows the stream's previous call left there.
-struct MimiEncStreamPool {
-    MimiConfig cfg;
-    MimiWeights w;
-    int n_streams = 0, max_chunk = 0, ring = 0;
-    std::vector<long> offset;                       // tokens each stream has encoded so far
-    std::vector<unsigned char> ended;               // the stream took a partial last frame: refused until reset
-    Ladder b;
-    int* tab = nullptr;                             // device table of the running call (enc_stream_segs.h): ENC_STREAM_TAB_WORDS words ...
-    long* ltab = nullptr;                           // ... and ENC_STREAM_LTAB_LONGS longs behind them (same allocation)
-    float* wav_tail = nullptr;                      // [stream][kernel - 1]: the samples in front of the next chunk's first
-    long enc_rows = 0;                              // frames of the last encode call: its latent lies dense in b.rvq
-    std::string err;
-};
-
+// ---- encode stream pool (struct MimiEncStreamPool above) -----------------------------------------------------------------------------------
 extern "C" int mimi_enc_pool_create(const MimiConfig* cfg, const MimiWeights* w, int n_streams, int max_chunk_frames, mimi_enc_pool* out) {
-    csm_warn_unknown_switches();
-    if (!cfg || !w || !out) return fail(nullptr, "mimi_enc_pool_create: null argument");
-    if (!w->has_encoder) return fail(nullptr, "mimi_enc_pool_create: these weights have no encoder");
-    if (n_streams < 1 || n_streams > MIMI_ENC_POOL_MAX_STREAMS) return fail(nullptr, "mimi_enc_pool_create: n_streams must be 1 .. MIMI_ENC_POOL_MAX_STREAMS (64)");
-    if (max_chunk_frames < 1 || max_chunk_frames > ENC_STREAM_MAX_CHUNK) return fail(nullptr, "mimi_enc_pool_create: max_chunk_frames must be 1 .. 64");
-    if (const char* bad = config_error(cfg)) return fail(nullptr, bad);
+    MimiEncStreamPool* p = nullptr;
+    if (int rc = pool_new("mimi_enc_pool_create", "MIMI_ENC_POOL_MAX_STREAMS", true, cfg, w, out, n_streams, max_chunk_frames, &p)) return rc;
     // the histories below are sized from the configuration: the weights must have its taps
     bool taps_ok = cfg->kernel >= 2 && cfg->codebook_dim % 32 == 0 && cfg->codebook_dim <= 2 * cfg->hidden && w->enc_conv_out.taps == cfg->last_kernel;
     for (int j = 0; j < cfg->n_stages; ++j)
         taps_ok = taps_ok && w->enc_res1[j].taps == cfg->res_kernel && w->enc_res2[j].taps == 1 && w->enc_down[j].taps == 2 * cfg->ratios[cfg->n_stages - 1 - j];
-    if (!taps_ok) return fail(nullptr, "mimi_enc_pool_create: encoder weights whose taps are not the configuration's (or codebook_dim % 32)");
-    MimiEncStreamPool* p = new MimiEncStreamPool();
-    p->cfg = *cfg; p->w = *w; p->n_streams = n_streams; p->max_chunk = max_chunk_frames;
-    p->ring = cfg->tr_context + 2 * max_chunk_frames;        // as a decode pool's: a call's oldest key and its newest never share a row
-    p->offset.assign(n_streams, 0);
+    if (!taps_ok) { delete p; return fail(nullptr, "mimi_enc_pool_create: encoder weights whose taps are not the configuration's (or codebook_dim % 32)"); }
     p->ended.assign(n_streams, 0);
     auto alloc = [&]() {
         MCHK(p, hipMalloc((void**)&p->tab, (size_t)ENC_STREAM_TAB_WORDS * 4 + (size_t)ENC_STREAM_LTAB_LONGS * 8));
@@ -1470,43 +1527,22 @@ extern "C" int mimi_enc_pool_create(const MimiConfig* cfg, const MimiWeights* w,
         const size_t tail_bytes = (size_t)n_streams * (cfg->kernel - 1) * 4;
         MCHK(p, hipMalloc((void**)&p->wav_tail, tail_bytes));
         MCHK(p, hipMemset(p->wav_tail, 0, tail_bytes));
-        // (ffn is also the RVQ score buffer, as in mimi_create)
-        return ladder_alloc(p, p->b, *cfg, n_streams, max_chunk_frames, p->ring, cfg->tr_ffn > cfg->codebook_size ? cfg->tr_ffn : cfg->codebook_size, true);
+        return ladder_alloc(p, p->b, *cfg, n_streams, max_chunk_frames, p->ring, enc_ffn_cols(*cfg), true);
     };
-    const int rc = alloc();
-    if (rc) { g_mimi_err = p->err; mimi_enc_pool_destroy(p); return rc; }
+    if (const int rc = alloc()) { g_mimi_err = p->err; delete p; return rc; }
     *out = p;
     return 0;
 }
 
-extern "C" void mimi_enc_pool_destroy(mimi_enc_pool p) {
-    if (!p) return;
-    ladder_free(p->b);
-    (void)hipFree(p->tab);
-    (void)hipFree(p->wav_tail);
-    delete p;
-}
+extern "C" void mimi_enc_pool_destroy(mimi_enc_pool p) { delete p; }
 
 extern "C" const char* mimi_enc_pool_last_error(mimi_enc_pool p) { return p ? p->err.c_str() : g_mimi_err.c_str(); }
 
 extern "C" int mimi_enc_pool_reset(mimi_enc_pool p, const int32_t* streams, int n, void* stream) {
     if (!p) return fail(p, "mimi_enc_pool_reset: null pool");
-    PoolIds ids;
-    if (!streams || n < 1 || n > p->n_streams) return fail(p, "mimi_enc_pool_reset: stream list: need 1 .. n_streams ids");
-    bool seen[MIMI_ENC_POOL_MAX_STREAMS] = {};
-    for (int i = 0; i < n; ++i) {
-        if (streams[i] < 0 || streams[i] >= p->n_streams) return fail(p, "mimi_enc_pool_reset: stream id outside [0, n_streams)");
-        if (seen[streams[i]]) return fail(p, "mimi_enc_pool_reset: duplicate stream id in one call");
-        seen[streams[i]] = true;
-        ids.sid[i] = streams[i]; ids.off[i] = 0;
-    }
-    ids.n = n;
-    // every history row and the sample tail to zero: the whole-clip encode's left padding.  (The rings need no clearing, as in a decode pool.)
-    PoolRegions z = hist_regions(p->b, 0);
-    z.base[z.count] = p->wav_tail; z.hist[z.count] = p->cfg.kernel - 1; z.C[z.count] = 1; z.seg[z.count] = p->cfg.kernel - 1; z.T[z.count] = 0; ++z.count;
-    hipLaunchKernelGGL(k_pool_zero_hist, dim3(8, n, z.count), dim3(256), 0, (hipStream_t)stream, z, ids);
-    MCHK(p, hipGetLastError());
-    for (int i = 0; i < n; ++i) { p->offset[ids.sid[i]] = 0; p->ended[ids.sid[i]] = 0; }
+    // every history row and the sample tail to zero: the whole-clip encode's left padding
+    if (int rc = pool_reset(p, "mimi_enc_pool_reset", streams, n, p->wav_tail, p->cfg.kernel - 1, stream)) return rc;
+    for (int i = 0; i < n; ++i) p->ended[streams[i]] = 0;
     return 0;
 }
 
@@ -1518,70 +1554,29 @@ extern "C" int mimi_enc_pool_encode(mimi_enc_pool p, const int32_t* streams, con
     EncStreamHeader hdr;
     EncStreamSegs sg;
     if (const char* bad = enc_stream_segs_build(streams, wav_off, n_samples, n, wav, codes, p->n_streams, p->max_chunk, p->offset.data(), p->ended.data(),
-                                                c.ratios, c.n_stages, &hdr, &sg)) {
-        p->err = std::string("mimi_enc_pool_encode: ") + bad;
-        return -1;
-    }
+                                                c.ratios, c.n_stages, &hdr, &sg))
+        return fail(p, "mimi_enc_pool_encode", bad);
     hipStream_t st = (hipStream_t)stream;
     Ladder& b = p->b;
-    const int d = c.hidden, S = c.n_stages, F = sg.F;
-    const int* tab = p->tab;
+    const int hop = (int)samples_per_frame(c), C = c.n_filters;
+    EncPass ep{(long)sg.F * hop, sg.F}; ep.tab = p->tab; ep.ring = p->ring;
     hipLaunchKernelGGL(k_enc_stream_plan, dim3(1), dim3(256), 0, st, hdr, p->tab, p->ltab);
-    // first convolution into the streams' level-0 segments, then the sample tails move on
-    int R = (int)enc_level_rate(c.ratios, S, 0), C = c.n_filters;          // rows per frame and channels at the current level
-    {
-        const SegBuf& x0 = b.u(S - 1);
-        const long tot = (long)F * R * C;
-        hipLaunchKernelGGL(k_enc_stream_conv_in, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, wav, (long)F * R, R, c.kernel, C, w.enc_conv_in_w,
-                           w.enc_conv_in_b, tab, p->ltab, p->wav_tail, x0.row0(), x0.seg());
-        hipLaunchKernelGGL(k_enc_stream_tail, dim3(1), dim3(256), 0, st, wav, n, c.kernel - 1, tab, p->ltab, p->wav_tail);
-        MCHK(p, hipGetLastError());
-    }
-    // Every product below runs over ALL the call's rows at its level, frame-aligned (R rows per frame).  Those whose taps stay inside
-    // [-hist, own row] are a decode pool's ragged products; the strided convolutions and the downsample also reach FORWARD, up to the end of
-    // the segment's rows, where the last partial frame of a stream has the whole-clip encode's right padding (seg_edges).
-    for (int j = 0; j < S; ++j) {
-        const int bi = S - 1 - j;
-        const MimiConv &r1 = w.enc_res1[j], &r2 = w.enc_res2[j], &dn = w.enc_down[j];
-        const SegBuf &u = b.u(bi), &xj = b.xj(bi), &nxt = (j + 1 < S) ? b.u(bi - 1) : b.s0;
-        MCHK(p, gemm(st, conv(u.row0(), C, (long)F * R, r1, b.r1[bi], r1.c_out).elu().seg({R, u.seg(), R, 0, 1, 0, tab, true})));
-        MCHK(p, gemm(st, conv(b.r1[bi], r1.c_out, (long)F * R, r2, xj.row0(), C).elu().residual(u.row0(), C).seg({R, R, xj.seg(), u.seg(), 2 | 4, 0, tab, true})));
-        const int r = dn.taps / 2;
-        const int Rn = R / r;
-        MCHK(p, gemm(st, conv(xj.row0(), C, (long)F * Rn, dn, nxt.row0(), dn.c_out).taps_at(-r, 1).stride(r).elu().seg_edges(1, xj.hist, j)
-                             .seg({Rn, xj.seg(), nxt.seg(), 0, 1 | 2, 0, tab, true})));
-        R = Rn; C = dn.c_out;
-    }
-    MCHK(p, gemm(st, conv(b.s0.row0(), C, 2L * F, w.enc_conv_out, b.tok, d).elu().seg({2, b.s0.seg(), 2, 0, 1, 0, tab, true})));
-    // encoder transformer on the streams' K/V rings -> a0 segments.  No K split, as in mimi_encode.
-    TrPass tp{w.enc_tr, 2L * F};
-    tp.lin2_ksplit = false;
-    tp.tab = tab; tp.T2 = 2; tp.ring = p->ring; tp.ragged = true;
-    if (int rc = transformer(p, c, w, b, tp, st)) return rc;
-    // stride-2 downsample, taps at rows 2t - 2 .. 2t + 1 -> rvq [F][d] (dense)
-    const MimiConv down = {w.downsample, nullptr, d, d, 4, 1};
-    MCHK(p, gemm(st, conv(b.a0.row0(), d, F, down, b.rvq.row0(), d).taps_at(-2, 1).stride(2).seg_edges(2, b.a0.hist, S).seg({1, b.a0.seg(), 1, 0, 1, 0, tab, true})));
-    // split RVQ, per row over the call's F frames
-    const int cd = c.codebook_dim;
-    float *res_first = b.ln, *res_rest = b.q;       // [F][cd]
-    MCHK(p, gemm(st, linear(b.rvq.row0(), d, F, w.in_proj_first, d, cd, res_first, cd)));
-    MCHK(p, gemm(st, linear(b.rvq.row0(), d, F, w.in_proj_rest, d, cd, res_rest, cd)));
-    for (int k = 0; k < c.n_codebooks; ++k) {
-        float* res = k < c.n_semantic ? res_first : res_rest;
-        const float* book = w.codebooks + (long)k * c.codebook_size * cd;
-        MCHK(p, gemm(st, linear(res, cd, F, book, cd, c.codebook_size, b.ffn, c.codebook_size)));
-        hipLaunchKernelGGL(k_rvq_pick, dim3((unsigned)F), dim3(256), 0, st, b.ffn, c.codebook_size, w.codebook_sqnorm + (long)k * c.codebook_size, book, cd,
-                           res, codes + (long)k * F, 1L);
-        MCHK(p, hipGetLastError());
-    }
-    // every buffer's history slides by its stream's chunk.  (A stream that ended slides rows nobody reads: its reset zeroes them.)
-    const PoolRegions z = hist_regions(b, 1);
-    int maxC = 0;
-    for (int r = 0; r < z.count; ++r) maxC = z.C[r] > maxC ? z.C[r] : maxC;
-    hipLaunchKernelGGL(k_pool_slide<true>, dim3((maxC + 255) / 256, n, z.count), dim3(256), 0, st, z, tab);
+    // front: the first convolution into the streams' level-0 segments, then the sample tails move on
+    const SegBuf& x0 = b.u(c.n_stages - 1);
+    hipLaunchKernelGGL(k_enc_stream_conv_in, dim3((unsigned)((ep.rows0 * C + 255) / 256)), dim3(256), 0, st, wav, ep.rows0, hop, c.kernel, C, w.enc_conv_in_w,
+                       w.enc_conv_in_b, p->tab, p->ltab, p->wav_tail, x0.row0(), x0.seg());
+    hipLaunchKernelGGL(k_enc_stream_tail, dim3(1), dim3(256), 0, st, wav, n, c.kernel - 1, p->tab, p->ltab, p->wav_tail);
     MCHK(p, hipGetLastError());
+    // every product runs over ALL the call's rows at its level, frame-aligned; the transformer on the streams' K/V rings -> a0 segments
+    long L;
+    if (int rc = seanet_encoder(p, c, w, b, ep, st, &L)) return rc;
+    if (int rc = transformer(p, c, w, b, ep.tr(w, L), st)) return rc;
+    if (int rc = encode_downsample(p, c, w, b, ep, L, st)) return rc;
+    if (int rc = quantize(p, c, w, b, sg.F, codes, st)) return rc;
+    // every buffer's history slides by its stream's chunk.  (A stream that ended slides rows nobody reads: its reset zeroes them.)
+    if (int rc = pool_slide<true>(p, b, 1, n, p->tab, st)) return rc;
     for (int i = 0; i < n; ++i) { p->offset[hdr.sid[i]] += 2 * sg.T[i]; p->ended[hdr.sid[i]] = sg.ends[i]; }
-    p->enc_rows = F;
+    p->enc_rows = sg.F;
     return 0;
 }
 

@@ -249,6 +249,25 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _pack_clips(wavs: Sequence[torch.Tensor], device: torch.device):
+    """Clips (or chunks), each (n_i,), CPU or device -> one fp32 device buffer, clip after clip, and their offsets and lengths in it.  An
+    empty call still hands the library real memory -- a 1-element zero buffer, 1-element arrays -- so that ITS check refuses the call."""
+    lens = [int(w.shape[0]) for w in wavs]
+    offs = [sum(lens[:k]) for k in range(len(lens))]
+    packed = torch.cat([w.to(device=device, dtype=torch.float32) for w in wavs]) if wavs else torch.zeros(1, device=device)
+    if packed.numel() == 0:
+        packed = torch.zeros(1, device=device)
+    m = max(len(lens), 1)
+    return packed, (C.c_long * m)(*offs), (C.c_long * m)(*lens)
+
+
+def _latent(lib_fn, handle, frames: int, check_rc, codec: "MimiCodec") -> torch.Tensor:
+    """(frames, hidden) fp32: the pre-quantisation latent of the last encode call on ``handle``, or the library's refusal."""
+    out = torch.empty(int(frames), codec.args.hidden, dtype=torch.float32, device=codec.device)
+    check_rc(lib_fn(handle, out.data_ptr(), int(frames), _stream()))
+    return out
+
+
 class MimiCodec:
     def __init__(self, args: MimiArgs, state_dict: Optional[Dict[str, torch.Tensor]] = None, device: str = "cuda",
                  max_frames: int = 1125):
@@ -394,13 +413,9 @@ class MimiCodec:
         return out
 
     def _encode_call(self, wavs: Sequence[torch.Tensor], frames: List[int], F: int) -> List[torch.Tensor]:
-        n = len(wavs)
-        packed = torch.cat([w.to(device=self.device, dtype=torch.float32) for w in wavs])       # one device buffer, clip after clip
-        lens = [int(w.shape[0]) for w in wavs]
-        offs = [sum(lens[:k]) for k in range(n)]
+        packed, offs, lens = _pack_clips(wavs, self.device)
         codes = torch.empty(self.args.num_codebooks, F, dtype=torch.int32, device=self.device)
-        check(lib.mimi_encode_many(self._h, packed.data_ptr(), (C.c_long * n)(*offs), (C.c_long * n)(*lens), n, codes.data_ptr(), _stream()),
-              self._h, mimi=True)
+        check(lib.mimi_encode_many(self._h, packed.data_ptr(), offs, lens, len(wavs), codes.data_ptr(), _stream()), self._h, mimi=True)
         codes = codes.long()
         return list(codes.split(frames, dim=1))
 
@@ -410,9 +425,7 @@ class MimiCodec:
         RVQ input projections read (mimi_debug_encode_latent, include/mimi_hip.h).  ``frames`` is that call's frame count: T of ``encode``
         (for B > 1 the rows are the last clip's), the sum of the clips' frames of one ``encode_many`` call, clip i in rows [F_i, F_i + T_i).
         A count that disagrees with the call is refused."""
-        out = torch.empty(int(frames), self.args.hidden, dtype=torch.float32, device=self.device)
-        check(lib.mimi_debug_encode_latent(self._h, out.data_ptr(), int(frames), _stream()), self._h, mimi=True)
-        return out
+        return _latent(lib.mimi_debug_encode_latent, self._h, frames, lambda rc: check(rc, self._h, mimi=True), self)
 
     def _run(self, codes: torch.Tensor, stateful: bool) -> torch.Tensor:
         assert codes.dim() == 3 and codes.shape[1] == self.args.num_codebooks, "codes must be (B, 32, T)"
@@ -457,12 +470,10 @@ class MimiCodec:
             pass
 
 
-class MimiStreamPool:
-    """``n`` independent stateful Mimi decode streams (include/mimi_hip.h, mimi_pool_*): stream ``i`` keeps its own conv left
-    contexts, K/V ring and token offset, and runs for any number of frames.  ``decode(ids, codes)`` continues the listed
-    streams by the same ``T <= max_chunk_frames`` frames each; a stream's PCM does not depend on which other streams share the
-    call, and its chunks, concatenated, are ``MimiCodec.decode`` of its concatenated codes.  ``decode_ragged`` does the same for streams
-    with a different number of frames each, still in one launch chain.  Streams start reset."""
+class _StreamPool:
+    """What the two pools share: a handle of the library's ``<_prefix>_*`` family made from the codec's device weights, its error text, id
+    marshalling, ``reset`` and destruction."""
+    _prefix = ""
 
     def __init__(self, codec: MimiCodec, n: int, max_chunk_frames: int = 10):
         self.codec = codec                        # keeps the device weights alive
@@ -470,23 +481,42 @@ class MimiStreamPool:
         self._h = C.c_void_p(None)
         cfg, w = codec._cfg_w
         with torch.cuda.device(codec.device):
-            rc = lib.mimi_pool_create(C.byref(cfg), C.byref(w), self.n_streams, self.max_chunk_frames, C.byref(self._h))
+            rc = self._fn("create")(C.byref(cfg), C.byref(w), self.n_streams, self.max_chunk_frames, C.byref(self._h))
         if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_pool_last_error(None) or b"").decode())
+            raise _abi.CsmError(rc, (self._fn("last_error")(None) or b"").decode())
+
+    def _fn(self, name: str):
+        return getattr(lib, f"{self._prefix}_{name}")
 
     def _check(self, rc: int) -> None:
         if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_pool_last_error(self._h) or b"").decode())
+            raise _abi.CsmError(rc, (self._fn("last_error")(self._h) or b"").decode())
 
     @staticmethod
     def _ids(ids: Sequence[int]):
         ids = [int(i) for i in ids]
-        return (C.c_int32 * len(ids))(*ids), len(ids)
+        return (C.c_int32 * max(len(ids), 1))(*ids), len(ids)
 
     def reset(self, ids: Optional[Sequence[int]] = None) -> None:
         """Start the listed streams (default: all) afresh."""
         arr, n = self._ids(range(self.n_streams) if ids is None else ids)
-        self._check(lib.mimi_pool_reset(self._h, arr, n, _stream()))
+        self._check(self._fn("reset")(self._h, arr, n, _stream()))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._fn("destroy")(self._h)
+        except Exception:
+            pass
+
+
+class MimiStreamPool(_StreamPool):
+    """``n`` independent stateful Mimi decode streams (include/mimi_hip.h, mimi_pool_*): stream ``i`` keeps its own conv left
+    contexts, K/V ring and token offset, and runs for any number of frames.  ``decode(ids, codes)`` continues the listed
+    streams by the same ``T <= max_chunk_frames`` frames each; a stream's PCM does not depend on which other streams share the
+    call, and its chunks, concatenated, are ``MimiCodec.decode`` of its concatenated codes.  ``decode_ragged`` does the same for streams
+    with a different number of frames each, still in one launch chain.  Streams start reset."""
+    _prefix = "mimi_pool"
 
     @torch.inference_mode()
     def decode(self, ids: Sequence[int], codes: torch.Tensor) -> torch.Tensor:
@@ -530,15 +560,8 @@ class MimiStreamPool:
             out.append(pcm[:, hop * at:hop * (at + t)]); at += t
         return out
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib.mimi_pool_destroy(self._h)
-        except Exception:
-            pass
 
-
-class MimiEncodeStreamPool:
+class MimiEncodeStreamPool(_StreamPool):
     """``n`` independent stateful Mimi ENCODE streams (include/mimi_hip.h, mimi_enc_pool_*): stream ``i`` keeps the left context of every
     convolution of the encoder, its K/V ring and its token offset, and runs for any number of frames.  ``encode(ids, wavs)`` feeds the
     listed streams their new samples, a different number each, in ONE launch chain.  A stream's codes, concatenated over its calls, are
@@ -546,25 +569,16 @@ class MimiEncodeStreamPool:
     list.  A chunk that is no whole number of frames ENDS its stream: the partial last frame is encoded as the whole-clip encode does, and
     the stream is refused until ``reset``.  Streams start reset."""
 
-    def __init__(self, codec: MimiCodec, n: int, max_chunk_frames: int = 10):
-        self.codec = codec                        # keeps the device weights alive
-        self.n_streams, self.max_chunk_frames = int(n), int(max_chunk_frames)
-        self._ended = [False] * self.n_streams
-        self._h = C.c_void_p(None)
-        cfg, w = codec._cfg_w
-        with torch.cuda.device(codec.device):
-            rc = lib.mimi_enc_pool_create(C.byref(cfg), C.byref(w), self.n_streams, self.max_chunk_frames, C.byref(self._h))
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_enc_pool_last_error(None) or b"").decode())
+    _prefix = "mimi_enc_pool"
 
-    def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_enc_pool_last_error(self._h) or b"").decode())
+    def __init__(self, codec: MimiCodec, n: int, max_chunk_frames: int = 10):
+        super().__init__(codec, n, max_chunk_frames)
+        self._ended = [False] * self.n_streams
 
     def reset(self, ids: Optional[Sequence[int]] = None) -> None:
         """Start the listed streams (default: all) afresh."""
         ids = [int(i) for i in (range(self.n_streams) if ids is None else ids)]
-        self._check(lib.mimi_enc_pool_reset(self._h, (C.c_int32 * len(ids))(*ids), len(ids), _stream()))
+        super().reset(ids)
         for i in ids:
             self._ended[i] = False
 
@@ -577,21 +591,14 @@ class MimiEncodeStreamPool:
         """ids: n distinct stream ids; wavs[i]: (n_i,) fp32 @ 24 kHz, CPU or device, the new samples of stream ids[i] (at most
         ``max_chunk_frames`` frames) -> one (32, ceil(n_i / hop)) int64 tensor per stream."""
         ids = [int(i) for i in ids]
-        n = len(ids)
+        arr, n = self._ids(ids)
         assert len(wavs) == n, "one chunk per id"
         assert all(w.dim() == 1 for w in wavs), "every chunk must be (n,)"
         dev, hop = self.codec.device, self.codec.args.hop
-        lens = [int(w.shape[0]) for w in wavs]
-        frames = [-(-x // hop) for x in lens]
-        offs = [sum(lens[:k]) for k in range(n)]
-        packed = torch.cat([w.to(device=dev, dtype=torch.float32) for w in wavs]) if n else torch.zeros(1, device=dev)    # one device buffer, as _encode_call
-        if packed.numel() == 0:
-            packed = torch.zeros(1, device=dev)
-        F = max(sum(f for f in frames if f > 0), 1)
-        codes = torch.empty(self.codec.args.num_codebooks, F, dtype=torch.int32, device=dev)
-        m = max(n, 1)
-        self._check(lib.mimi_enc_pool_encode(self._h, (C.c_int32 * m)(*ids), (C.c_long * m)(*offs), (C.c_long * m)(*lens), n, packed.data_ptr(),
-                                             codes.data_ptr(), _stream()))
+        packed, offs, lens = _pack_clips(wavs, dev)
+        frames = [-(-x // hop) for x in lens[:n]]
+        codes = torch.empty(self.codec.args.num_codebooks, max(sum(f for f in frames if f > 0), 1), dtype=torch.int32, device=dev)
+        self._check(lib.mimi_enc_pool_encode(self._h, arr, offs, lens, n, packed.data_ptr(), codes.data_ptr(), _stream()))
         for i, x in zip(ids, lens):
             self._ended[i] = x % hop != 0
         return list(codes.long().split(frames, dim=1))
@@ -600,13 +607,4 @@ class MimiEncodeStreamPool:
     def encode_latent(self, frames: int) -> torch.Tensor:
         """For tests: the pre-quantisation latent of the pool's LAST ``encode`` call, (frames, hidden) fp32, ``frames`` = the sum of that
         call's chunk frames; chunk i owns rows [F_i, F_i + T_i) (mimi_enc_pool_debug_latent).  A count that disagrees is refused."""
-        out = torch.empty(int(frames), self.codec.args.hidden, dtype=torch.float32, device=self.codec.device)
-        self._check(lib.mimi_enc_pool_debug_latent(self._h, out.data_ptr(), int(frames), _stream()))
-        return out
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib.mimi_enc_pool_destroy(self._h)
-        except Exception:
-            pass
+        return _latent(lib.mimi_enc_pool_debug_latent, self._h, frames, self._check, self.codec)

@@ -245,3 +245,36 @@ def test_generator_builds_the_prompt_from_turns_encoded_while_they_were_spoken(t
     want = gen._build_prompt([11, 12], 0, [Segment(0, [5, 6], audio=a), Segment(1, [7], audio=b)])
     assert got[0].is_cuda and torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
     assert got[0].shape[0] == 2 + 5 + 1 + 17 + 2
+
+
+def test_every_encode_entry_point_interleaved_on_one_codec_equals_fresh_objects():
+    """``encode``, a pool call, ``encode_many``, the pool call that ends the stream and a stateless ``decode``, interleaved on ONE codec: all
+    of them run the one encoder chain on buffers and state that the calls before them used (the handle's work buffers and their reset after
+    an encode, the pool's histories and rings, the latent's row count).  Each result is ``torch.equal`` to the same call on a freshly built
+    codec or pool that did nothing else, and the stream's joined codes to ``encode`` of its clip."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    a, b, c = _clip(401, 3 * HOP + 1), _clip(402, 3 * HOP + 777), _clip(403, HOP + 961)
+    cut = 2 * HOP                                                       # stream 0: two frames, then hop + 777 samples, which ends it
+    codes = torch.randint(0, 2048, (1, 32, 4), generator=torch.Generator().manual_seed(404))
+    want_a, want_b = _single(_new_tiny(), a), _single(_new_tiny(), b)
+    want_many = _new_tiny().encode_many([a, c])
+    fresh_pool = _new_tiny().open_encode_streams(2, max_chunk_frames=3)
+    want_b0, want_b1 = fresh_pool.encode([0], [b[:cut]])[0], fresh_pool.encode([0], [b[cut:]])[0]
+    want_pcm = _new_tiny().decode(codes)
+    assert want_a.shape == (32, 4) and want_b0.shape == (32, 2) and want_b1.shape == (32, 2) and [m.shape[1] for m in want_many] == [4, 2]
+
+    codec = _new_tiny()
+    pool = codec.open_encode_streams(2, max_chunk_frames=3)
+    got_a = _single(codec, a)
+    got_b0 = pool.encode([0], [b[:cut]])[0]
+    got_many = codec.encode_many([a, c])
+    got_b1 = pool.encode([0], [b[cut:]])[0]
+    got_pcm = codec.decode(codes)
+    assert torch.equal(got_a, want_a), "encode after nothing"
+    assert torch.equal(got_b0, want_b0), "the pool's first call, after an encode on the codec"
+    assert len(got_many) == 2 and all(torch.equal(g, w) for g, w in zip(got_many, want_many)), "encode_many between two pool calls"
+    assert torch.equal(got_many[0], want_a), "clip A in a list and alone"
+    assert torch.equal(got_b1, want_b1) and pool.ended(0), "the pool's second call, which ends the stream"
+    assert torch.equal(torch.cat([got_b0, got_b1], dim=1), want_b), "stream 0's joined codes against encode of B alone"
+    assert got_pcm.shape == (1, 1, 4 * HOP) and torch.isfinite(got_pcm).all() and torch.equal(got_pcm, want_pcm), "a stateless decode after the encodes"
