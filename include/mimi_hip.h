@@ -212,6 +212,44 @@ int  mimi_enc_pool_encode(mimi_enc_pool p, const int32_t* streams, const long* w
 /* As mimi_debug_encode_latent, for the pool's last mimi_enc_pool_encode call: rows = its F, stream i of the call owns rows [F_i, F_i + T_i). */
 int  mimi_enc_pool_debug_latent(mimi_enc_pool p, float* out, long rows, void* stream);
 
+/* ---- A pool of stateful RESAMPLER streams (audio at any sample rate in front of the encoder and behind the decoder) ----
+ * The filter is scipy.signal.resample_poly's default: g = gcd(src, dst), up = dst / g, down = src / g, half = 10 * max(up, down),
+ * h = firwin(2 * half + 1, 1 / max(up, down), window = ('kaiser', 5.0)) * up, made once at create in float64 on the host, rounded once to fp32
+ * and kept on the device.  A clip x[0 .. N) gives M = ceil(N * up / down) outputs
+ *     y[n] = sum_k h[n * down + half - k * up] * x[k]     over the k with 0 <= n * down + half - k * up <= 2 * half and 0 <= k < N;
+ * samples outside the clip are zero.  A pool holds n_streams independent streams.  After N samples in all a stream has emitted
+ * floor((N * up - 1 - half) / down) + 1 outputs (0 while N * up - 1 - half < 0) while its clip is open, and ceil(N * up / down) once the clip is
+ * ended (`final`); per stream the pool keeps the last 2 * half / up + 1 samples (two banks, flipped per call: a call's outputs read one, its
+ * history update writes the other) and two running totals, reduced by whole periods (up outputs <-> down inputs) after every call -- a stream
+ * runs for ever, and the kernel sees small numbers for ever.
+ * mimi_rs_pool_feed: stream streams[i] gets n_in[i] >= 0 samples at in + in_off[i] ELEMENTS; final[i] != 0 ends its clip (the tail comes out
+ * and the stream is left fresh; n_in[i] == 0 with final emits the tail alone).  in_fmt / out_fmt: 0 = fp32, 1 = int16 (in: x = s * 2^-15,
+ * exact; out: clamp(y, -1, 1) * 32767 rounded to nearest even, NaN gives 0).  in, out: device memory; streams, in_off, n_in, final: host
+ * arrays read before the call returns; n_out: a host array WRITTEN before the call returns.  Outputs are packed back to back: with
+ * O_i = n_out[0] + .. + n_out[i - 1], stream i owns out[O_i .. O_i + n_out[i]); mimi_rs_pool_out_count says beforehand (host arithmetic only)
+ * what a feed of n_in samples would give stream sid now.  A feed that emits nothing for a stream is legal.  ONE launch per call whatever n
+ * and the lengths are; the plan (at most MIMI_RS_MAX_STREAMS entries) travels in the kernel arguments: no host-to-device copy, no
+ * synchronisation.
+ * NUMERICAL RULE: one output is one thread's sequential fp32 fmaf chain over its in-clip k in ascending order; nothing about it depends on
+ * tiling, on the chunk schedule, on which other streams share the call or on list order -- a stream's outputs, concatenated over its calls,
+ * are BIT FOR BIT the one-shot (single final feed) result of its concatenated samples.  In front of the clip's first sample the kernel
+ * reads 0.0f by index rule, whatever the history memory holds: mimi_rs_pool_reset is host arithmetic, no launch.  A non-finite sample
+ * reaches exactly the outputs whose tap range covers it: nothing in other streams, nothing after a reset or a `final`.
+ * Returns -1 with a message in mimi_rs_pool_last_error, nothing enqueued and no state moved, for: src == dst, a rate <= 0, a reduced up or
+ * down above 320 (create); n outside [1, n_streams], a duplicate or out-of-range id, a negative n_in or in_off, a null pointer, an unknown
+ * format, a chunk that takes or gives more than 2^30 samples (feed).  -2: a HIP error.  Drive ONE HIP stream per pool at a time.          */
+#define MIMI_RS_MAX_STREAMS 64
+typedef struct MimiResamplePool* mimi_rs_pool;
+int  mimi_rs_pool_create(int src_rate, int dst_rate, int n_streams, mimi_rs_pool* out);
+void mimi_rs_pool_destroy(mimi_rs_pool p);
+const char* mimi_rs_pool_last_error(mimi_rs_pool p);           /* p == NULL: why mimi_rs_pool_create failed (this thread) */
+/* For tests: the fp32 taps the device holds (host_out: 2 * half + 1 floats, host memory, may be NULL) and the reduced factors. */
+int  mimi_rs_pool_taps(mimi_rs_pool p, float* host_out, int* up, int* down, int* half);
+long mimi_rs_pool_out_count(mimi_rs_pool p, int sid, long n_in, int final);
+int  mimi_rs_pool_reset(mimi_rs_pool p, const int32_t* streams, int n);
+int  mimi_rs_pool_feed(mimi_rs_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                       const void* in, int in_fmt, void* out, int out_fmt, long* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,13 @@ MIMI_SIGNATURES = {
     "mimi_enc_pool_reset": (_i, [_vp, _vp, _i, _vp]),
     "mimi_enc_pool_encode": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _i, _vp, _vp, _vp]),
     "mimi_enc_pool_debug_latent": (_i, [_vp, _vp, _l, _vp]),
+    "mimi_rs_pool_create": (_i, [_i, _i, _i, C.POINTER(_vp)]),
+    "mimi_rs_pool_destroy": (None, [_vp]),
+    "mimi_rs_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_rs_pool_taps": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "mimi_rs_pool_out_count": (_l, [_vp, _i, _l, _i]),
+    "mimi_rs_pool_reset": (_i, [_vp, _vp, _i]),
+    "mimi_rs_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _i, _vp, _i, C.POINTER(_l), _vp]),
 }
 
 for _name, (_res, _args) in list(SIGNATURES.items()) + list(MIMI_SIGNATURES.items()):

@@ -39,11 +39,14 @@ ENCODE_MANY_MIN_CLIPS = 2
 class Segment:
     """reference: sesameai/generator.py:16-21.  ``audio`` is (num_samples,) @ 24 kHz.
     Extension: ``audio_codes`` (32, T) may carry pre-computed Mimi codes, and ``text`` may be
-    a list of token ids, so prompts can be built without the gated tokenizer / Mimi encoder."""
+    a list of token ids, so prompts can be built without the gated tokenizer / Mimi encoder; ``sample_rate`` (None: 24 kHz) is the rate
+    ``audio`` comes at, fp32 or int16 -- a foreign rate is resampled on the device before Mimi sees it (the reference's callers do it with
+    torchaudio first, tts_service.py:161-166)."""
     speaker: int
     text: Union[str, Sequence[int]]
     audio: Optional[torch.Tensor] = None
     audio_codes: Optional[torch.Tensor] = None
+    sample_rate: Optional[int] = None
 
 
 def load_llama3_tokenizer(path: Optional[str] = None):
@@ -144,12 +147,13 @@ class Generator:
         mask[:, -1] = True
         return frame.to(self.device), mask.to(self.device)
 
-    def _tokenize_audio(self, audio: Optional[torch.Tensor], codes: Optional[torch.Tensor] = None):
+    def _tokenize_audio(self, audio: Optional[torch.Tensor], codes: Optional[torch.Tensor] = None, sample_rate: Optional[int] = None):
         if codes is None:
             assert audio is not None and audio.ndim == 1, "Audio must be single channel"
             if self._audio_tokenizer is None or not hasattr(self._audio_tokenizer, "encode"):
                 raise RuntimeError("no Mimi encoder available: pass Segment.audio_codes")
-            codes = self._audio_tokenizer.encode(audio.to(self.device).unsqueeze(0).unsqueeze(0))[0]
+            kw = {} if sample_rate is None else {"sample_rate": sample_rate}
+            codes = self._audio_tokenizer.encode(audio.to(self.device).unsqueeze(0).unsqueeze(0), **kw)[0]
         codes = codes.to(self.device).long()
         eos = torch.zeros(codes.size(0), 1, dtype=torch.long, device=self.device)     # all-zero EOS frame
         codes = torch.cat([codes, eos], dim=1)
@@ -164,7 +168,7 @@ class Generator:
         codes = segment.audio_codes
         if codes is None and encoded:
             codes = encoded.get(id(segment.audio))          # (the Segment itself is left as it came)
-        a, am = self._tokenize_audio(segment.audio, codes)
+        a, am = self._tokenize_audio(segment.audio, codes, **({} if segment.sample_rate is None else {"sample_rate": segment.sample_rate}))
         return torch.cat([t, a], dim=0), torch.cat([tm, am], dim=0)
 
     def _encode_contexts(self, contexts: Sequence[List[Segment]]) -> dict:
@@ -172,19 +176,22 @@ class Generator:
         calls (``MimiCodec.encode_many``: all clips, whatever their lengths, in one launch chain; the codes are bit for bit those of
         the per-segment ``encode``).  A tensor that several segments or requests share (the same object) is encoded once.  Empty --
         the segments then go through today's per-segment ``encode`` calls -- for a codec without ``encode_many`` and for fewer than
-        ENCODE_MANY_MIN_CLIPS distinct clips."""
+        ENCODE_MANY_MIN_CLIPS distinct clips.  A segment's ``sample_rate`` goes with its clip (``encode_many(.., sample_rates=..)``)."""
         tok = self._audio_tokenizer
         if tok is None or not hasattr(tok, "encode_many"):
             return {}
         clips: dict = {}
+        rates: dict = {}
         for ctx in contexts:
             for seg in ctx:
                 if seg.audio is not None and seg.audio_codes is None and id(seg.audio) not in clips:
                     assert seg.audio.ndim == 1, "Audio must be single channel"
                     clips[id(seg.audio)] = seg.audio
+                    rates[id(seg.audio)] = seg.sample_rate
         if len(clips) < max(2, ENCODE_MANY_MIN_CLIPS):
             return {}
-        return dict(zip(clips.keys(), tok.encode_many(list(clips.values()))))
+        kw = {} if all(r is None for r in rates.values()) else {"sample_rates": list(rates.values())}
+        return dict(zip(clips.keys(), tok.encode_many(list(clips.values()), **kw)))
 
     def _build_prompts(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]]):
         """The prompts of several requests; their unencoded context audio goes through the Mimi encoder together (_encode_contexts)."""
@@ -202,14 +209,20 @@ class Generator:
         toks.append(t); masks.append(m)
         return torch.cat(toks, 0).long().to(self.device), torch.cat(masks, 0).bool().to(self.device)
 
-    def open_turn_streams(self, n: int, chunk_frames: int = 10):
+    def open_turn_streams(self, n: int, chunk_frames: int = 10, sample_rate: Optional[int] = None):
         """``n`` spoken turns encoded while they are spoken (sesameai/turns.py): ``feed`` / ``pump`` as the microphones deliver, then
-        ``finish(sid, speaker, text)`` gives the ``Segment`` of the turn, its codes bit for bit those of ``Segment(audio=the turn)``."""
+        ``finish(sid, speaker, text)`` gives the ``Segment`` of the turn, its codes bit for bit those of ``Segment(audio=the turn)``.
+        ``sample_rate`` (None: 24 kHz, today's calls exactly): the microphones' rate; ``feed`` then takes fp32 or int16 at that rate and a
+        pool of ``n`` resampler streams (sesameai/resample.py) follows the turns in front of the encoder."""
         from .turns import TurnStreams
         tok = self._audio_tokenizer
         if tok is None or not hasattr(tok, "open_encode_streams"):
             raise RuntimeError("no Mimi encoder with encode streams available: pass Segment.audio_codes")
-        return TurnStreams(tok.open_encode_streams(n, max_chunk_frames=chunk_frames), tok.args.hop, chunk_frames)
+        pool = tok.open_encode_streams(n, max_chunk_frames=chunk_frames)
+        if sample_rate is None or int(sample_rate) == self.sample_rate:
+            return TurnStreams(pool, tok.args.hop, chunk_frames)
+        from .resample import ResamplerPool
+        return TurnStreams(pool, tok.args.hop, chunk_frames, resampler=ResamplerPool(int(sample_rate), self.sample_rate, n, device=self.device))
 
     # -- prefix store: a voice prompt's K/V computed once, copied into any slot ----------------------
     def _store(self) -> list:
@@ -467,7 +480,8 @@ class Generator:
     def generate_many_stream(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                              temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None,
-                             sessions: Optional[Sequence[Optional[Conversation]]] = None
+                             sessions: Optional[Sequence[Optional[Conversation]]] = None,
+                             out_sample_rate: Optional[int] = None, out_dtype: Optional[torch.dtype] = None
                              ) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
@@ -489,7 +503,13 @@ class Generator:
         whole-clip decode, bit for bit what the uniform calls give.  The Philox key of a sampled frame holds the global frame index, so --
         as with ``refill_group`` -- the sampled codes of requests WITHOUT a seed of their own may differ between None and k (the shorter
         blocks see the retirements at other steps); requests with their own seed, and greedy runs, give the same codes for every k.
-        ``sessions``: as for ``generate_many``."""
+        ``sessions``: as for ``generate_many``.
+        ``out_sample_rate`` / ``out_dtype`` (None, None: fp32 at 24 kHz, the calls described above exactly): the rate and the format
+        (torch.float32 or torch.int16) the caller's device wants.  Each slot is then also one stream of a ``ResamplerPool``
+        (sesameai/resample.py), reset when a new request takes the slot, and each pool call's PCM goes through ONE resampler call on the
+        side stream.  A request's chunks, concatenated, are bit for bit ``resample`` of its concatenated 24 kHz chunks; the filter's tail
+        comes with the request's last chunk -- also with the closing chunk that is empty at 24 kHz -- so a chunk's length is no longer
+        1920 samples a frame.  ``out_dtype`` other than fp32 needs a foreign ``out_sample_rate`` (the conversion is the resampler's)."""
         size = self._stream_buffer_size
         if first_chunk_frames is not None and not 1 <= int(first_chunk_frames) < size:
             raise ValueError(f"first_chunk_frames must be None or 1 .. {size - 1}")
@@ -507,7 +527,16 @@ class Generator:
             self._stream_pools = {}
         if (B, size) not in self._stream_pools:
             self._stream_pools[(B, size)] = codec.open_streams(B, max_chunk_frames=size)
-        streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device, **({} if first is None else {"first": first}))
+        kw = {} if first is None else {"first": first}
+        if out_sample_rate is not None and int(out_sample_rate) != self.sample_rate:
+            from .resample import ResamplerPool
+            key = ("resampler", B, int(out_sample_rate), out_dtype or torch.float32)
+            if key not in self._stream_pools:
+                self._stream_pools[key] = ResamplerPool(self.sample_rate, int(out_sample_rate), B, device=self.device, out_dtype=out_dtype or torch.float32)
+            kw["resampler"] = self._stream_pools[key]
+        elif out_dtype is not None and out_dtype != torch.float32:
+            raise ValueError("out_dtype without out_sample_rate: convert the 24 kHz chunks yourself")
+        streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device, **kw)
         backlog: List[list] = []                                    # polled blocks whose audio is still to be decoded
         for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed, refill_group=refill_group,
                                                   **({} if first is None else {"first_chunk_frames": first}),

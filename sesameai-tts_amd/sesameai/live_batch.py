@@ -333,14 +333,17 @@ class SlotStreams:
     """The stream state of ``generate_many_stream``: each batch slot is one stream of a ``MimiStreamPool``; ``owner[slot]`` is the request
     whose audio the slot's stream carries, ``held[slot]`` its frames not decoded yet.  Decodes run on ``side`` (a HIP stream, or None).
     ``first`` = k (None: off, today's calls exactly): a request's first chunk goes out as soon as its slot holds k frames, and everything
-    that is ready after a block -- full chunks, first chunks, the endings' remainders -- goes into ONE ragged pool call (``_ragged_calls``)."""
+    that is ready after a block -- full chunks, first chunks, the endings' remainders -- goes into ONE ragged pool call (``_ragged_calls``).
+    ``resampler`` (None: 24 kHz fp32, today's calls exactly): a pool of at least ``slots`` resampler streams (``ResamplerPool``), slot = stream;
+    every pool call's PCM goes through ONE ``resampler.feed`` on ``side``, ``final`` for the slots whose request it closes -- a request's last
+    chunk carries the filter's tail, also when it is empty at 24 kHz."""
 
-    def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None):
-        self.pool, self.size, self.side, self.first = pool, size, side, first
+    def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None, resampler=None):
+        self.pool, self.size, self.side, self.first, self.resampler = pool, size, side, first, resampler
         self.started: List[bool] = [False] * slots                  # whether the slot's request has had a chunk (``first`` only)
         self.owner: List[Optional[int]] = [None] * slots
         self.held: List[List[torch.Tensor]] = [[] for _ in range(slots)]
-        self.no_pcm = torch.empty(0, dtype=torch.float32, device=device)
+        self.no_pcm = torch.empty(0, dtype=getattr(resampler, "out_dtype", torch.float32), device=device)
 
     def chunks(self, block: list) -> List[Tuple[int, torch.Tensor, torch.Tensor, bool]]:
         """One polled block (a slot carries at most one utterance in it) -> its chunks: a stream is reset when a new request takes its slot, all slots that
@@ -366,23 +369,32 @@ class SlotStreams:
                 del held[s_][:T]
             calls.append((slots, frames, pool.decode(slots, frames.permute(0, 2, 1))))
 
+        tails: dict = {}                                            # (resampler) slot -> the tail of a request whose closing chunk is empty at 24 kHz
         with torch.inference_mode(), (torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext()):
             if fresh:
                 pool.reset(fresh)
+                if self.resampler is not None:
+                    self.resampler.reset(fresh)
             if self.first is not None:
                 self._ragged_calls(ending, calls)
             while self.first is None and (full := [s_ for s_, h in enumerate(held) if len(h) >= self.size]):
                 decode(full, self.size)
             for T in sorted({len(held[s_]) for s_ in ending} - {0}):
                 decode([s_ for s_ in ending if len(held[s_]) == T], T)
+            final = {s_: k for k, (slots, _, _) in enumerate(calls) for s_ in slots}   # the call that holds a slot's newest chunk
+            if self.resampler is not None:                          # ONE resampler call per pool call, and one for the empty closing chunks
+                for k, (slots, frames, pcm) in enumerate(calls):
+                    rs = self.resampler.feed(slots, [pcm[j][0] for j in range(len(slots))], [s_ in ending and final[s_] == k for s_ in slots])
+                    calls[k] = (slots, frames, [y.unsqueeze(0) for y in rs])
+                if bare := [s_ for s_ in ending if s_ not in final]:
+                    tails = dict(zip(bare, self.resampler.feed(bare, [self.no_pcm.float()] * len(bare), True)))
         if self.side is not None:
             self.side.synchronize()
-        final = {s_: k for k, (slots, _, _) in enumerate(calls) for s_ in slots}       # the call that holds a slot's newest chunk
         for k, (slots, frames, pcm) in enumerate(calls):
             out.extend((owner[s_], pcm[j][0], frames[j], s_ in ending and final[s_] == k) for j, s_ in enumerate(slots))
         for s_ in ending:
-            if s_ not in final:                                     # nothing was left to decode: the closing chunk is empty
-                out.append((owner[s_], self.no_pcm, _NO_FRAMES, True))
+            if s_ not in final:                                     # nothing was left to decode: the closing chunk is empty (at 24 kHz)
+                out.append((owner[s_], tails.get(s_, self.no_pcm), _NO_FRAMES, True))
             owner[s_] = None
         return out
 

@@ -376,11 +376,14 @@ class MimiCodec:
             raise ValueError(f"this codec is built for {self.args.num_codebooks} codebooks")
 
     @torch.inference_mode()
-    def encode(self, wav: torch.Tensor) -> torch.Tensor:
-        """wav (B,1,n) fp32 @ 24 kHz -> codes (B,32,ceil(n/1920)) int64 (generator.py:86)."""
+    def encode(self, wav: torch.Tensor, sample_rate: Optional[int] = None) -> torch.Tensor:
+        """wav (B,1,n) fp32 @ 24 kHz -> codes (B,32,ceil(n/1920)) int64 (generator.py:86).  ``sample_rate`` (None: 24 kHz, today's calls
+        exactly): the rate ``wav`` comes at, fp32 or int16; a foreign rate goes through ONE resampler launch (sesameai/resample.py) first."""
         if not self.has_encoder:
             raise RuntimeError("this MimiCodec was built without encoder weights; pass Segment.audio_codes instead")
         assert wav.dim() == 3 and wav.shape[1] == 1, "wav must be (B, 1, n)"
+        if sample_rate is not None and int(sample_rate) != self.sample_rate:
+            wav = torch.stack(self._to_codec_rate([wav[b, 0] for b in range(wav.shape[0])], int(sample_rate))).unsqueeze(1)
         B, _, n = wav.shape
         T = -(-n // self.args.hop)
         x = wav.to(device=self.device, dtype=torch.float32).contiguous()
@@ -389,12 +392,22 @@ class MimiCodec:
         return codes.long()
 
     @torch.inference_mode()
-    def encode_many(self, wavs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    def encode_many(self, wavs: Sequence[torch.Tensor], sample_rates=None) -> List[torch.Tensor]:
         """Clips of different lengths, each (n_i,) fp32 @ 24 kHz -> their codes, each (32, ceil(n_i/1920)) int64: bit for bit what
         ``encode`` gives for the clip alone, from ONE launch chain per call of ``mimi_encode_many`` (include/mimi_hip.h).  The list is
-        split greedily, in input order, into calls of at most ``max_frames`` frames and MAX_ENCODE_CLIPS clips."""
+        split greedily, in input order, into calls of at most ``max_frames`` frames and MAX_ENCODE_CLIPS clips.
+        ``sample_rates`` (None: all at 24 kHz, today's calls exactly): one rate, or one per clip (None or 24000: as it is); the clips of
+        each distinct foreign rate, fp32 or int16, go through ONE resampler launch (per 64 clips), then all through the chain above."""
         if not self.has_encoder:
             raise RuntimeError("this MimiCodec was built without encoder weights; pass Segment.audio_codes instead")
+        if sample_rates is not None:
+            rates = [sample_rates] * len(wavs) if isinstance(sample_rates, int) else list(sample_rates)
+            assert len(rates) == len(wavs), "one sample rate per clip"
+            wavs = list(wavs)
+            for rate in sorted({int(r) for r in rates if r is not None and int(r) != self.sample_rate}):
+                idx = [k for k, r in enumerate(rates) if r is not None and int(r) == rate]
+                for k, w in zip(idx, self._to_codec_rate([wavs[k] for k in idx], rate)):
+                    wavs[k] = w
         hop = self.args.hop
         frames = []
         for w in wavs:
@@ -410,6 +423,14 @@ class MimiCodec:
                 F += frames[j]; j += 1
             out += self._encode_call(wavs[i:j], frames[i:j], F)
             i = j
+        return out
+
+    def _to_codec_rate(self, wavs: Sequence[torch.Tensor], rate: int) -> List[torch.Tensor]:
+        """Clips at ``rate`` -> the same at the codec's rate: one resampler launch per MAX_STREAMS clips."""
+        from .resample import MAX_STREAMS, resample
+        out: List[torch.Tensor] = []
+        for a in range(0, len(wavs), MAX_STREAMS):
+            out += resample(wavs[a:a + MAX_STREAMS], rate, self.sample_rate, device=self.device)
         return out
 
     def _encode_call(self, wavs: Sequence[torch.Tensor], frames: List[int], F: int) -> List[torch.Tensor]:
