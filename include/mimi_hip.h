@@ -250,6 +250,38 @@ int  mimi_rs_pool_reset(mimi_rs_pool p, const int32_t* streams, int n);
 int  mimi_rs_pool_feed(mimi_rs_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
                        const void* in, int in_fmt, void* out, int out_fmt, long* n_out, void* stream);
 
+/* ---- The segment finisher: decoded fp32 clips -> the int16 segments a WAV holds, every clip that is ready in ONE launch chain ----
+ * What tts_service.TTS.generate_audio_segment does on the host per clip (peak-normalise, int16, lead and tail silence, fade in and out), as
+ * the rule below.  One clip x[0 .. N), N >= 0, with lead L, tail T and fade F (samples, >= 0):
+ *   1. peak = max(max |x_i| over the FINITE x_i, 1e-6f); an empty clip has the floor as its peak.
+ *   2. q_i = trunc_toward_zero((x_i / peak) * 32767.0f), every operation rounded to fp32, `/` the correctly rounded IEEE division (not a
+ *      multiply by a reciprocal).  A non-finite x_i (NaN, +-Inf) gives q_i = 0 and does not enter the peak.
+ *   3. y = L zeros ++ q ++ T zeros; M = L + N + T.
+ *   4. n = min(F, M / 2).  For n > 0 the ramp is made in float64: r_j = float(j * (1.0 / (n - 1))), r_(n-1) = 1, and r_0 = 0 when n == 1
+ *      (numpy.linspace(0, 1, n, dtype=float32) bit for bit); y[j] = trunc(float(y[j]) * r_j) and y[M-n+j] = trunc(float(y[M-n+j]) * r_(n-1-j)).
+ * mimi_fin_segments: segment i = n_in[i] fp32 samples at in[i] (in: a HOST array of DEVICE pointers, one per segment, so clips of separate
+ * decode calls need no concatenation; in[i] may be NULL where n_in[i] == 0) with lead[i], tail[i], fade[i].  in, n_in, lead, tail, fade: host
+ * arrays read before the call returns; out_off, n_out: host arrays WRITTEN before the call returns.  Outputs are packed back to back in `out`
+ * (device, int16): with O_i = n_out[0] + .. + n_out[i-1] = out_off[i], segment i owns out[O_i .. O_i + n_out[i]), n_out[i] = M_i;
+ * mimi_fin_out_count says beforehand (host arithmetic only) what a segment gives, or -1 for one the call would refuse.  A call is TWO launches
+ * on `stream` whatever n and the lengths are (a partial peak per tile; then every output tile reduces its segment's partials and writes);
+ * the plan (at most MIMI_FIN_MAX_SEGMENTS entries) travels in the kernel arguments: no memset, no atomics, no allocation, no host copy, no
+ * synchronisation.  The handle's scratch for the partials (64 segments x 256 tiles, 64 KiB) is made ONCE at create and holds any legal call:
+ * a segment's peak tile grows with its length so that it never has more than 256.
+ * NUMERICAL RULE: an output depends on its own sample, its segment's peak and its index in the segment -- not on the tiling, not on which
+ * segments share the call, not on list order: bit for bit the rule above.  A non-finite sample reaches nothing but its own output.
+ * Returns -1 with a message in mimi_fin_last_error and nothing enqueued for: n outside [1, MIMI_FIN_MAX_SEGMENTS], a negative length, lead,
+ * tail or fade, an M_i above 2^30, a null pointer (in[i] where n_in[i] > 0 included), a misaligned buffer.  -2: a HIP error.  Drive ONE HIP
+ * stream per handle at a time.                                                                                                           */
+#define MIMI_FIN_MAX_SEGMENTS 64
+typedef struct MimiFinisher* mimi_finisher;
+int  mimi_fin_create(mimi_finisher* out);
+void mimi_fin_destroy(mimi_finisher p);
+const char* mimi_fin_last_error(mimi_finisher p);              /* p == NULL: why mimi_fin_create failed (this thread) */
+long mimi_fin_out_count(long n_in, long lead, long tail);
+int  mimi_fin_segments(mimi_finisher p, const float* const* in, const long* n_in, const int32_t* lead, const int32_t* tail,
+                       const int32_t* fade, int n, int16_t* out, long* out_off, long* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

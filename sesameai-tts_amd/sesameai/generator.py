@@ -7,6 +7,7 @@ EOS flag every few frames instead of synchronising on every frame (generator.py:
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import queue
 import struct
@@ -91,6 +92,7 @@ class Generator:
     refill_row_layers = 600                    # ... about this many prompt-row x layer units per step
     _stream_pools: Optional[dict] = None       # {(slots, chunk frames): MimiStreamPool} of generate_many_stream, made on first use and kept
     _conversations: Optional[ConversationSet] = None   # the sessions opened on this Generator (open_session), made on first use
+    _finisher = None                           # generate_segments' SegmentFinisher (sesameai/finish.py), made on first use and kept
 
     def __init__(self, model: Model, audio_tokenizer=None, text_tokenizer=None, max_batch_size: int = 1):
         self._model = model
@@ -430,14 +432,16 @@ class Generator:
     def _iter_blocks_continuous(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                                 temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], poll: Optional[int] = None,
                                 seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
-                                first_chunk_frames: Optional[int] = None, sessions: Optional[Sequence[Optional[Conversation]]] = None):
+                                first_chunk_frames: Optional[int] = None, sessions: Optional[Sequence[Optional[Conversation]]] = None,
+                                slots: Optional[int] = None):
         """The incremental form of ``iter_codes_continuous`` (same loop, same model calls in the same order): per polled block it
         yields a list of ``(index of the prompt, batch slot, that utterance's NEW frames [k][32] int32 CPU, last)`` -- ``last`` with
         the frames that complete the utterance (possibly none); an utterance that is empty before it ever holds a slot has slot -1.
         In between it yields ``None`` each time a block's frame steps have just been queued and before it waits for them: the
         moment for a consumer to start work that should run beside those steps (generate_many_stream's Mimi decode).
         The scheduler is sesameai/live_batch.py; ``refill_beside_the_loop`` / ``refill_row_layers`` choose and tune how slots are refilled;
-        ``first_chunk_frames``: its short blocks while a request waits for its first chunk (None: every block is ``poll`` steps)."""
+        ``first_chunk_frames``: its short blocks while a request waits for its first chunk (None: every block is ``poll`` steps);
+        ``slots``: use no more than this many of the batch's slots (None: all ``max_batch_size``)."""
         per_prompt_sampling(len(prompts), temperature, topk, seed)          # (a wrong length or a bad value raises before the model is touched)
         kw = {}
         if sessions is not None:                                            # the sessions' prompts become their full prompts
@@ -446,7 +450,8 @@ class Generator:
             if len(limits) == len(prompts):                                 # (a wrong length is live_batch's ValueError) on_full="forget": make room first
                 make_room(sessions, [t.shape[0] for t, _ in prompts], limits, MAX_SEQ_LEN)
             prompts = [(t, mk) if c is None else c.full_prompt(t, mk) for (t, mk), c in zip(prompts, sessions)]
-        yield from live_batch(self._model, prompts, max_generation_len, temperature, topk, poll or self._eos_poll, self._max_batch,
+        yield from live_batch(self._model, prompts, max_generation_len, temperature, topk, poll or self._eos_poll,
+                              self._max_batch if slots is None else min(self._max_batch, int(slots)),
                               self._store(), self.refill_beside_the_loop, self.refill_row_layers, MAX_SEQ_LEN, seed=seed, refill_group=refill_group,
                               first_chunk_frames=first_chunk_frames, **kw)
 
@@ -464,18 +469,87 @@ class Generator:
     def generate_many(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                       temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
                       seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
-                      sessions: Optional[Sequence[Optional[Conversation]]] = None) -> List[torch.Tensor]:
+                      sessions: Optional[Sequence[Optional[Conversation]]] = None, finish=None,
+                      on_result: Optional[Callable[[int, torch.Tensor], None]] = None) -> List[torch.Tensor]:
         """``generate`` for a list of requests through the continuously refilled batch: one audio tensor per request
         (``max_audio_length_ms``, ``temperature``, ``topk``: one value, or one per request; ``seed``: one optional int per request;
-        ``sessions``: one ``Conversation`` or None per request -- the context of a request with a session lists only the NEW segments)."""
+        ``sessions``: one ``Conversation`` or None per request -- the context of a request with a session lists only the NEW segments).
+        ``finish`` (None: the calls described above, exactly): a ``SegmentFinish``, or one per request -- the result is then what
+        ``generate_segments`` returns for these prompts, finished int16 segments on the device, and ``on_result(i, pcm)`` fires as each
+        request completes."""
         max_generation_len = _frames_for(max_audio_length_ms)
         prompts = self._build_prompts(texts, speakers, contexts)
+        if finish is not None:
+            if sessions is not None:
+                raise ValueError("finish= with sessions=: not supported")
+            return self.generate_segments(prompts, max_generation_len, temperature, topk, finish, seed=seed, refill_group=refill_group,
+                                          on_result=on_result)
+        if on_result is not None:
+            raise ValueError("on_result= needs finish=")
         out: List[torch.Tensor] = [torch.tensor([]) for _ in prompts]
         for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group,
                                                     **({} if sessions is None else {"sessions": sessions})):
             if frames.shape[0]:                                       # decoded as each utterance finishes, not at the end
                 out[i] = self._decode_frames(frames.unsqueeze(1))
         return out
+
+    def generate_segments(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
+                          temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], finish,
+                          seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
+                          post: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
+                          on_result: Optional[Callable[[int, torch.Tensor], None]] = None, slots: Optional[int] = None) -> List[torch.Tensor]:
+        """Prompts [(tokens (S_i,33), mask (S_i,33)), ...] through the continuously refilled batch, each result a FINISHED segment: int16 on
+        the device, peak-normalised, with lead and tail silence and fades (``finish``: a ``SegmentFinish`` for all prompts, or one per
+        prompt; sesameai/finish.py) -- what ``tts_service.TTS.generate_audio_segment`` makes of a sentence, bit for bit, without the float32
+        copy to the host.  After each polled block the utterances that ended in it are decoded, and ALL their clips are finished by ONE
+        ``SegmentFinisher.finish`` call; decode and finish run on the Mimi side stream and are submitted right after the next block's frame
+        steps have been queued (``generate_many_stream``'s backlog pattern), so the language model never waits for them.
+        ``post(audio) -> audio`` runs on each non-empty decoded clip before it is finished (the watermark hook); ``on_result(i, pcm)``
+        fires as each request completes; an utterance with no frames still yields its lead and tail silence.  ``max_generation_len``,
+        ``temperature``, ``topk``, ``seed``, ``refill_group``: as for ``iter_codes_continuous``; ``slots``: use no more than this
+        many of the batch's slots (None: all of them).  Returns the segments in the order of ``prompts``."""
+        from .finish import SegmentFinisher, per_clip
+        how = per_clip(finish, len(prompts))
+        if self._finisher is None:
+            self._finisher = SegmentFinisher(self.device)
+        side = self._side_stream()
+        results: List[Optional[torch.Tensor]] = [None] * len(prompts)
+        parts: dict = {}
+        no_audio = torch.empty(0, dtype=torch.float32, device=self.device)
+
+        def finish_block(block: list) -> None:
+            done = []                                               # (request, its frames) of the utterances that end in this block
+            for i, _slot, frames, last in block:
+                parts.setdefault(i, []).append(frames)
+                if last:
+                    got = parts.pop(i)
+                    done.append((i, got[0] if len(got) == 1 else torch.cat(got)))
+            if not done:
+                return
+            with torch.inference_mode(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+                clips = []
+                for _i, frames in done:
+                    audio = self._decode_frames(frames.unsqueeze(1)) if frames.shape[0] else no_audio
+                    clips.append(post(audio) if post is not None and audio.numel() else audio)
+                pcm = self._finisher.finish(clips, [how[i] for i, _ in done], self.sample_rate)
+            if side is not None:
+                side.synchronize()
+            for (i, _), seg in zip(done, pcm):
+                results[i] = seg
+                if on_result is not None:
+                    on_result(i, seg)
+
+        backlog: List[list] = []                                    # polled blocks whose utterances are still to be decoded and finished
+        for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group,
+                                                  **({} if slots is None else {"slots": slots})):
+            if block is not None:
+                backlog.append(block)
+                continue
+            while backlog:                                          # the next block's steps are queued: decode and finish beside them
+                finish_block(backlog.pop(0))
+        while backlog:
+            finish_block(backlog.pop(0))
+        return results
 
     def generate_many_stream(self, texts: Sequence, speakers: Sequence[int], contexts: Sequence[List[Segment]], max_audio_length_ms=90_000,
                              temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,

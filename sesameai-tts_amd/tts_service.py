@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """CLI with the reference's surface (reference: tts_service.py): class ``TTS`` with
 ``load_model / list_voices / load_voice / generate_with_context / generate_audio_segment /
-export_wav / say`` and the flags ``-d/--device  -v/--voice  text  --output  --temp  --topk`` (no text: interactive mode).
+export_wav / say`` and the flags ``-d/--device  -v/--voice  text  --output  --temp  --topk`` (no text: interactive mode), plus
+``--batch N  --seed S``: the sentences of a text as N concurrent requests of the live batch.
 
 Only the hot path is re-implemented: generation runs on the MI355X kernels through
 ``sesameai.generator``.  Host-side audio post-processing that the reference does with pydub
 (peak-normalise -> int16, 500 ms lead / 100 ms tail silence, 50 ms fades, tts_service.py:288-306)
-is done with NumPy and the stdlib ``wave`` module; playback, watermarking and the WAV/resample
+is done with NumPy and the stdlib ``wave`` module -- or, with ``batch=``, on the device for all sentences of a text that finish together
+(sesameai/finish.py), the sentences running through the continuously refilled batch; playback, watermarking and the WAV/resample
 are out of scope.  Voice prompts come from a ``samples.py``-style registry of
 WAV files (loaded with ``wave`` + polyphase resampling, encoded by the GPU Mimi encoder) or from
 pre-tokenised ``<voice>.pt`` files holding ``[(text | token ids, codes[32,T]), ...]``.
@@ -80,9 +82,12 @@ class TTS:
 
     voice_name = None
     voice_data = None
+    max_batch_size = 1
+    _voice_prefix = None            # the prefix-store handle of the loaded voice's context rows (batch= only), made on first use
 
-    def __init__(self, device: str = "cuda", model_repo: str = "sesame/csm-1b", voice_dir: Optional[str] = None) -> None:
+    def __init__(self, device: str = "cuda", model_repo: str = "sesame/csm-1b", voice_dir: Optional[str] = None, max_batch_size: int = 1) -> None:
         self.device = device
+        self.max_batch_size = int(max_batch_size)       # slots of the live batch say / export_wav may use with batch= (1: none)
         self.model_repo = model_repo
         self.generator = None
         self.cached_context_tokens: List[torch.Tensor] = []
@@ -91,7 +96,7 @@ class TTS:
 
     def load_model(self) -> None:
         print("Open Sesame...")
-        self.generator = load_csm_1b(self.device)
+        self.generator = load_csm_1b(self.device) if self.max_batch_size == 1 else load_csm_1b(self.device, max_batch_size=self.max_batch_size)
         # reference tts_service.py load_model: the watermarker is loaded next to the model (a pass-through hook
         # that says so once when silentcipher is not installed)
         self.watermarker = load_watermarker(self.device)
@@ -104,6 +109,9 @@ class TTS:
         if voice_name not in self.voices:
             raise ValueError(f"Voice '{voice_name}' not found. Available voices: {list(self.voices.keys())}")
         self.cached_context_tokens, self.cached_context_masks = [], []
+        if self._voice_prefix is not None:               # the other voice's rows leave the prefix store
+            self.generator.drop_prefix(self._voice_prefix)
+            self._voice_prefix = None
         self.voice_name = voice_name
         src = self.voices[voice_name]
         self.voice_data = src if isinstance(src, dict) else torch.load(src)      # {wav path: transcript} | [(text, codes[32,T]), ...]
@@ -173,15 +181,86 @@ class TTS:
         """reference: tts_service.py:310-311."""
         return self.generate_audio_segment(sentence, fade_duration, start_silence_duration, end_silence_duration, temperature, topk)
 
+    def _segments_batched(self, sentences: List[str], batch: int, seed: Optional[int], fallback_duration: int, fade_duration: int,
+                          start_silence_duration: int, end_silence_duration: int, temperature: float, topk: int, on_segment=None) -> List[np.ndarray]:
+        """The sentences of one text as independent requests of the continuously refilled batch (``batch`` of its slots), each against the
+        cached voice context: the context rows are registered once per loaded voice with the prefix store, every sentence is one prompt
+        (context + sentence) with the 30 s limit of ``generate_audio_segment``, sentence i gets seed ``seed + i``, and every segment is
+        finished on the device (``Generator.generate_segments``).  A sentence whose prompt cannot be built gets ``fallback_duration`` ms of
+        silence and the others still run; an error of the batch run itself propagates.  Requests complete in any order: a reorder buffer
+        hands ``on_segment`` and the ``> sentence ...`` lines out strictly in sentence order, each as soon as all earlier ones are out."""
+        from sesameai.finish import SegmentFinish
+        g = self.generator
+        slots = getattr(g, "_max_batch", 1)
+        if isinstance(batch, bool) or not isinstance(batch, int) or not 2 <= batch <= slots:
+            raise ValueError(f"batch must be None or 2 .. {slots} (the generator's max_batch_size)")
+        sr = g.sample_rate
+        if self._voice_prefix is None and self.cached_context_tokens:
+            self._voice_prefix = g.cache_prefix(torch.cat(self.cached_context_tokens, dim=0), torch.cat(self.cached_context_masks, dim=0))
+        max_audio_frames = int(30_000 / 80)
+        max_seq_len = 2048 - max_audio_frames
+        prompts, owner = [], []                              # the prompts that could be built, and the sentence each belongs to
+        segments: List[Optional[np.ndarray]] = [None] * len(sentences)
+        failed = set()
+        for i, sentence in enumerate(sentences):
+            try:
+                gen_tokens, gen_masks = g._tokenize_text_segment(sentence, 1)
+                tokens = torch.cat(self.cached_context_tokens + [gen_tokens], dim=0).long().to(g.device)
+                mask = torch.cat(self.cached_context_masks + [gen_masks], dim=0).bool().to(g.device)
+                if tokens.size(0) >= max_seq_len:
+                    raise ValueError(f"Input too long ({tokens.size(0)} tokens). Maximum is {max_seq_len} tokens.")
+            except Exception as e:  # noqa: BLE001 -- as the unbatched path: the text goes on with silence
+                print(f"Error generating audio for sentence: {sentence}: {e}")
+                segments[i] = np.zeros(sr * fallback_duration // 1000, np.int16)
+                failed.add(i)
+                continue
+            prompts.append((tokens, mask))
+            owner.append(i)
+        t0 = time.time()
+        state = {"next": 0}
+
+        def drain() -> None:                                 # everything that is ready and has nothing missing in front of it
+            while state["next"] < len(sentences) and segments[state["next"]] is not None:
+                i = state["next"]
+                seg = segments[i]
+                took, secs = time.time() - t0, len(seg) / sr
+                if i not in failed:
+                    print(f"> {sentences[i]} ... [Audio: {secs:.2f}s in {took:.2f}s, RTF: {secs / max(took, 1e-9):.2f}x]")
+                if on_segment is not None:
+                    on_segment(seg, sr)
+                state["next"] = i + 1
+
+        def on_result(k: int, pcm: torch.Tensor) -> None:
+            segments[owner[k]] = pcm.cpu().numpy()
+            drain()
+
+        drain()
+        if prompts:
+            kw = {}
+            wm = getattr(self, "watermarker", None)
+            if wm is not None:                               # every generated clip carries the public CSM watermark (generate_with_context)
+                kw["post"] = lambda audio: resample_to(*watermark(wm, audio, sr, CSM_1B_GH_WATERMARK), sr)
+            g.generate_segments(prompts, max_audio_frames, temperature, topk,
+                                SegmentFinish(lead_ms=start_silence_duration, tail_ms=end_silence_duration, fade_ms=fade_duration),
+                                seed=None if seed is None else [int(seed) + i for i in owner], on_result=on_result, slots=batch, **kw)
+        drain()
+        took, secs = time.time() - t0, sum(len(x) for x in segments) / sr
+        print(f"Batch of {len(sentences)} sentences: {secs:.2f}s of audio in {took:.2f}s, RTF: {secs / max(took, 1e-9):.2f}x")
+        return segments
+
     def say(self, text: str, output_filename: Optional[str] = "combined_output.wav", fallback_duration: int = 1000,
             fade_duration: int = 50, start_silence_duration: int = 500, end_silence_duration: int = 100,
-            temperature: float = 0.8, topk: int = 40, on_segment=None) -> None:
+            temperature: float = 0.8, topk: int = 40, on_segment=None, batch: Optional[int] = None, seed: Optional[int] = None) -> None:
         """reference: tts_service.py:313-470 -- the generation half: the text is split into sentences, each sentence is
         generated against the cached voice context (the shared prompt prefix is prefilled once: Model.prefill_prompt) and
         reported with the reference's line ``> sentence ... [Audio: 1.84s in 0.09s, RTF: 20.44x]``; a sentence that fails is
         replaced by ``fallback_duration`` ms of faded silence; the segments are written to ``output_filename`` if given.
         Playback (the reference's pydub/ffplay player thread) is out of scope: ``on_segment(pcm_int16, sample_rate)``, if
-        given, receives every segment the moment it exists -- that is where a player thread's queue would be fed."""
+        given, receives every segment the moment it exists -- that is where a player thread's queue would be fed.
+        ``batch`` = k, 2 <= k <= the generator's ``max_batch_size`` (None, the default: the calls described above, exactly): the sentences
+        run as concurrent requests in k slots of the continuously refilled batch and are finished on the device
+        (``_segments_batched``); ``on_segment`` and the lines still come in sentence order.  ``seed`` (with ``batch``): sentence i is
+        sampled with seed ``seed + i``, whatever slot it takes."""
         import textwrap
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", textwrap.dedent(text).strip()) if s.strip()]
         if not sentences:
@@ -189,6 +268,12 @@ class TTS:
             return
         sr = self.generator.sample_rate
         segments: List[np.ndarray] = []
+        if batch is not None:
+            segments = self._segments_batched(sentences, batch, seed, fallback_duration, fade_duration, start_silence_duration,
+                                              end_silence_duration, temperature, topk, on_segment)
+            sentences = []
+        elif seed is not None:
+            raise ValueError("seed= needs batch=")
         for sentence in sentences:
             print(f"> {sentence} ... ", end="", flush=True)
             t0 = time.time()
@@ -218,12 +303,20 @@ class TTS:
         print(f"Export complete: {len(combined) / sr:.2f} seconds of audio")
 
     def export_wav(self, text: str, output_filename: str, fallback_duration: int = 1000, max_retries: int = 2,
-                   temperature: float = 0.8, topk: int = 40) -> None:
-        """reference: tts_service.py:472-525."""
+                   temperature: float = 0.8, topk: int = 40, batch: Optional[int] = None, seed: Optional[int] = None) -> None:
+        """reference: tts_service.py:472-525.  ``batch`` / ``seed``: as for ``say`` (None: the calls of the reference's loop, exactly).
+        ``max_retries`` applies only to the unbatched path: with ``batch`` a sentence whose prompt cannot be built gets the fallback
+        silence at once, and an error of the batch run itself propagates."""
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", text) if s.strip()]
         sr = self.generator.sample_rate
         segments = []
         t0 = time.time()
+        if batch is not None:
+            if sentences:
+                segments = self._segments_batched(sentences, batch, seed, fallback_duration, 50, 500, 100, temperature, topk)
+            sentences = []
+        elif seed is not None:
+            raise ValueError("seed= needs batch=")
         for sentence in sentences:
             seg, retries = None, 0
             while retries <= max_retries:
@@ -257,15 +350,23 @@ def main():
     parser.add_argument("--output", type=str, default="output.wav", help="Output filename")
     parser.add_argument("--temp", "--temperature", type=float, default=0.8, dest="temp")
     parser.add_argument("--topk", type=int, default=40)
+    parser.add_argument("--batch", type=int, default=None, metavar="N",
+                        help="run the sentences of a text as N concurrent requests of the live batch (default: one sentence after the other)")
+    parser.add_argument("--seed", type=int, default=None, metavar="S", help="with --batch: sentence i is sampled with seed S + i")
     args = parser.parse_args()
     if args.device == "cpu":
         parser.error("this build runs the hot path on MI355X only; there is no -d cpu path (use the reference)")
-    tts = TTS(device=args.device)
+    if args.batch is not None and args.batch < 2:
+        parser.error("--batch needs N >= 2")
+    if args.seed is not None and args.batch is None:
+        parser.error("--seed needs --batch")
+    tts = TTS(device=args.device) if args.batch is None else TTS(device=args.device, max_batch_size=args.batch)
+    more = {} if args.batch is None else {"batch": args.batch, "seed": args.seed}
     tts.load_model()
     if args.voice:
         tts.load_voice(args.voice)
     if args.text:
-        tts.export_wav(args.text, args.output, temperature=args.temp, topk=args.topk)
+        tts.export_wav(args.text, args.output, temperature=args.temp, topk=args.topk, **more)
         return
     # reference: tts_service.py:560-572 -- no text: interactive mode.  The reference plays every line; playback is out of
     # scope here, so each line is written to <output stem>_<n>.wav instead.
@@ -281,7 +382,7 @@ def main():
             break
         if line.strip():
             n += 1
-            tts.say(line, output_filename=f"{stem}_{n}{ext or '.wav'}", temperature=args.temp, topk=args.topk)
+            tts.say(line, output_filename=f"{stem}_{n}{ext or '.wav'}", temperature=args.temp, topk=args.topk, **more)
     print("\nExiting interactive mode.")
 
 
