@@ -29,162 +29,15 @@
 #include "bb_block.cuh"
 #include "switches.h"
 #include "stack_plan.h"
-#include "dev_pool.h"
-#include "session_pages.h"
-
-#define CSM_FRAME_GRAPHS 4    // captured frame steps kept per handle
-#define CSM_REFILL_SALT 0x9E3779B97F4A7C15ull      /* Philox key domain of slot refills (csm_seed) */
+#include "csm_model.h"               /* the handle: Stack, CsmModel, HIPCHK, dev_get (shared with csm_kv_store.hip) */
 
 static thread_local std::string g_create_err;
-
-struct Stack {
-    CsmLlamaDims d;
-    const CsmLayerWeights* lw;
-    const bf16_t* final_norm;
-    const bf16_t* rope;
-    int hd, nq, nkv, cache_len;
-    bf16_t *kc, *vc;            // [L][B][KV][cache_len][hd]
-    long layer_stride;          // elements per layer
-    long slot_off = 0;          // elements: batch slot the rows of the current call belong to (csm_prefill_slot), else 0
-    int nt_attn, nt_mlp;        // cache policy of the q/k/v/o and of the gate/up/down weight streams
-    const CsmLayerWeights *w8 = nullptr, *w8s = nullptr;      // fp8 weight stream + scales (nullptr = bf16)
-    CsmLayerWeights pk[CSM_MAX_LAYERS];   // matrix-core operand-order copies of wq..w3 (k_pack_w) for the wide-M path
-    CsmLayerWeights pk8[CSM_MAX_LAYERS];  // the same for the e4m3 weight stream (k_pack_w8); valid when has_pk8
-    bool has_pk8 = false;
-};
 
 // THE binding of the handle's device-memory owner (dev_pool.h) to HIP.  One rule for this file: after a failed allocation or fill, HIP's
 // last-error word is read and discarded before returning, so the next launch check of the process does not trip over it.
 static const DevBackend HIP_BACKEND = {[](void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }, [](void* p) { return (int)hipFree(p); },
                                        [](void* p, int byte, size_t bytes) { return (int)hipMemset(p, byte, bytes); }};
-
-// Initial values are stated HERE, once (members without an initialiser start as zero: new CsmModel() value-initialises); csm_create assigns
-// only what it computes from its arguments or reads from a switch.
-struct CsmModel {
-    DevPool pool{&HIP_BACKEND};         // owns every device allocation of the handle: csm_destroy and a failed csm_create release it, nothing else frees
-    CsmConfig cfg;
-    CsmWeights w;
-    int max_batch, max_rows, max_frames, ldl;
-    Stack bb, dec;
-    // workspaces (bf16 unless noted)
-    bf16_t *h, *q, *att, *act;          // backbone rows [max_rows][..]
-    float* part;                        // [max(PART_ROWS, max_batch)][H][NSPLIT][ATTN_PS(hd)] split-K attention partials
-    int part_rows;
-    int* attn_ctr = nullptr;            // [part_rows][KV heads] arrival counters of the split-K attention's in-kernel merge (attn.cuh); nullptr: CSM_ATTN_MERGE=0
-    bf16_t *dec_in;                     // [B][2][d_bb]   row0 = last_h, row1 = c0 embedding
-    float* slab;                        // [8][max_rows][max(d_bb, d_dec)] fp32 split-K partials of the wide path
-    bf16_t *pk_projection, *pk_c0_head, *pk_audio_head;   // packed copies for the wide-M path
-    uint8_t *pk8_c0_head = nullptr, *pk8_audio_head = nullptr;    // e4m3 heads in operand order (fp8 mode)
-    long pk_head_stride;                // elements between packed audio heads
-    bf16_t *qkv0_tab = nullptr;         // [(n_codebooks-2)*audio_vocab][nq + 2 nkv]: layer-0 q | k | v of the depth decoder for every
-                                        // (codebook c in 1..ncb-2, token) at its fixed position c+1 (env CSM_QKV0_TABLE=0 disables)
-    bf16_t *proj_emb;                   // [n_codebooks*audio_vocab][d_dec] = projection(audio_embeddings), built once at create:
-                                        // the decoder input of steps >= 2 is a 2 KB row gather instead of a 4.2 MB GEMV
-    bf16_t *hdec, *qd, *attd, *actd;    // decoder rows [2B][..]
-    bf16_t* logits;                     // [B][ldl]
-    int *frame, *cur_tokens, *cur_pos, *history, *n_frames, *eos_at, *dec_pos, *slot_scratch;
-    uint8_t* cur_mask;
-    uint64_t* rng;                      // [0..1] {seed, frame-step counter}; [2..3] the refill domain {seed ^ REFILL_SALT, refill counter} (rng_slot)
-    uint64_t* rng_slot;
-    // per-slot sampling table (csm_slot_sampling_set): one entry per batch slot, read by every sampler of the slot's row.  The
-    // launches get the pointer only once the handle has set an entry (slot_tab_used); until then they get nullptr and every captured
-    // frame step is node for node what it is without the table -- the rule of the inject node
-    SlotSampling* slot_tab;             // [max_batch]
-    bool slot_tab_used = false;
-    std::vector<unsigned char> slot_tab_host;   // [max_batch] host mirror for csm_describe: bit 0 = has an entry, bit 1 = own seed
-    int* frame_save;                    // [ncb] slot 0's newest frame while a slot refill's depth pass uses scratch row 0
-    // refill beside the frame loop (csm_refill_begin / csm_refill_advance): a prompt runs a few backbone layers per call between frame
-    // steps; its residual stream and the next layer's normalised input live in buffers of their own, everything else is transient
-    int* fresh;                         // [max_batch] device flags: the slot's next frame step yields its frame 0 from rf_last
-    bf16_t *rf_h = nullptr, *rf_xn = nullptr, *rf_last = nullptr;     // [max_rows][d_bb] x 2, [max_batch][2 d_bb] final-normed last prompt row per slot (dec_in
-                                        // layout).  Made together by the handle's first begin call (refill_buffers): all three or none
-    std::vector<char> rf_fresh_host;    // [max_batch] host mirror of `fresh` == 1: slots whose completed refill waits for a frame step to sample its
-    int rf_fresh_count = 0;             // frame 0 -- several can wait at once (a generator fills B slots before the first step: ADVICE r5)
-    RefillRec rf = {};                  // (nothing pending) the pending refill, one slot (csm_refill_begin) or a group in one ragged prefill (csm_refill_group_begin): rag_segs.h
-    int* rg_row_slot = nullptr;         // [max_rows] batch slot of each of the group's rows        } written by k_rag_plan at begin; made together
-    int4* rg_tiles = nullptr;           // [max_rows / 32 + 32] {slot, first row, rows, -} by walk  } by the handle's first group begin: both or none
-    int device = 0;                     // the GPU this handle lives on (csm_generate_frame_s1 makes it current itself)
-    int host_frames = 0;                // frames launched since reset (host mirror); the history is a ring of max_frames rows
-    int wide_path;                      // MFMA path for M >= wide_min (env CSM_WIDE=0 disables)
-    int wide_min;                       // WIDE_MIN_ROWS unless env CSM_WIDE_MIN overrides (tuning knob)
-    int xpack;                          // batched decode steps keep activations in operand order (env CSM_XPACK=0 disables)
-    int xpack_prompt;                   // prompts below the LDS-tiled kernels' row count too (env CSM_XPACK_PROMPT=0 disables)
-    int fp8_wide;                       // fp8 mode: batched decode steps stream e4m3 on the matrix-core path too (env CSM_FP8_WIDE=0 disables)
-    int fuse_dec_attn;                  // depth-decoder attention fused into the O-projection (env CSM_FUSE_DEC_ATTN=0 disables)
-    // persistent depth decoder (dec_persist.cuh): steps 2..ncb-1 of a batch-1 frame as one launch (env CSM_PERSIST=0 disables)
-    bool persist = false;
-    dp_u64 *pg_q, *pg_h1, *pg_h2, *pg_l, *pg_p;
-    uint32_t* p_state;                  // [0] tag epoch, [1] give-up code of the last launch (0 = ok), [2] tag epoch of the first-step launch
-    // the first decoder step (codebook 1: positions 0, 1) of a batch-1 frame as one launch (dec_first.cuh; env CSM_DEC_FIRST=0 disables)
-    bool dec_first = false;
-    dp_u64 *fg_q, *fg_h1, *fg_h2, *fg_p;
-    // backbone attention block of a batch-1 decode step as one launch per layer (bb_block.cuh)
-    bool bb_block = false;
-    dp_u64 *bg_q, *bg_a, *bg_s;
-    bool bb_layer = false;              // ... and the MLP in the same launch (k_bb_layer)
-    dp_u64 *bg_h, *bg_p;
-    uint4* b_w2t;                       // [layers] W2 re-tiled, 256 * 4 * 2048 pieces each
-    uint4* b_w2t8 = nullptr;            // fp8 mode: [layers] e4m3 W2 re-tiled, 256 * 2 * 2048 pieces each
-    bool bb_layer8 = false;             // fp8 mode: the one-launch layer streams the e4m3 bytes (k_bb_layer<true>)
-    uint32_t* b_state;                  // [0] tag epoch, [1] give-up code
-    uint4 *p_w2s, *p_w13p;              // [4 layers] re-tiled W2 / packed W1|W3, constant layer stride
-    bf16_t *p_wsm, *p_norms;            // [4][2560][1024] q|k|v|o rows, [4][2][1024] norm scales
-    int p_trickle, p_poll;
-    // the same for 2..32 batched utterances (dec_persist_m.cuh; env CSM_PERSIST_M=0 disables)
-    bool persist_m = false;
-    uint4 *pm_w13, *pm_w2;              // [4 layers] A-operand packed W1 | W3 / W2
-    char* pm_xchg;                      // exchange buffers (DM_XCHG_BYTES), 0xFF-filled in front of every launch
-    int pm_max_rows;                    // rows up to which the launch is used (env CSM_PERSIST_M_MAX, default 32)
-    int pm_trickle;                     // its weight-trickle nap (env CSM_PERSIST_M_TRICKLE; swept 2..16 x poll 0..4 at B = 4 and 32: 4)
-    dp_u64* p_stamps = nullptr;         // debug timeline (csm_debug_persist_stamps), else nullptr
-    char* xslab = nullptr; size_t xslab_used = 0, xslab_align = 4096;     // the small exchange buffers of the B = 1 all-CU launches live in one 2 MB-aligned slab (placement under our control)
-    bool persist_disabled = false, bb_disabled = false;     // a launch gave up once: the chain runs from then on (the buffers stay: error words are still read)
-    bool have_last = false;             // prefill or a frame step has produced h for csm_depth
-    int last_S = 1;                     // rows per sequence of the h buffer feeding csm_depth
-    // captured frame steps: a small LRU keyed on (batch, top-k, temperature, carries the per-slot sampling table) -- a service whose requests alternate sampling parameters or
-    // batch sizes (the reference's callers use 0.7/30, 0.8/40 and 0.9/50: tts_service.py:175,266) replays, it does not re-capture
-    struct FrameGraph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; int B = -1, topk = 0; float temp = 0.f; bool tab = false; uint64_t used = 0; };     // tab: carries the per-slot sampling table
-    FrameGraph graphs[CSM_FRAME_GRAPHS];
-    uint64_t graph_clock = 0;
-    int graph_captures = 0;             // hipGraphInstantiate calls since csm_create (csm_debug_graph_captures)
-    hipStream_t cap_stream = nullptr;   // capture happens on an internal stream: the caller's may be the legacy NULL stream
-    std::vector<struct CsmPrefix*> prefixes;     // live K/V snapshots captured from this handle (csm_prefix_capture); orphaned by csm_destroy
-    // session store (csm_session_store_create): conversations' backbone K/V in fixed-size pages of ONE pool allocation
-    SessionPages* sess = nullptr;       // the bookkeeping (session_pages.h); nullptr: no store
-    bf16_t* sess_pool = nullptr;        // [n_pages][layer][K|V][kv head][page_rows][hd]
-    int* sess_tab = nullptr;            // [max sessions][sess_tab_stride] device page table: row = session id, entry k = the session's logical page k
-    int sess_tab_stride = 0;            //   (written by k_session_save from its kernel arguments, read by k_session_load: no host-to-device copy);
-                                        //   one row more than sessions can be open: csm_session_forget's staging row (the new page list while the kernel reads the old)
-    int sess_forgets = 0;               // csm_session_forget calls that dropped rows, and the rows they moved down (csm_describe)
-    long sess_forget_moved = 0;
-    std::vector<struct CsmSession*> sessions;    // open session objects of this handle; orphaned by csm_destroy
-    std::string err;
-};
-
-// One conversation's place in the handle's session store: all state is in m->sess under `id`.
-struct CsmSession {
-    CsmModel* owner;                    // nullptr once the handle is destroyed: the pages are gone with it
-    int id;
-};
-
-// A voice prompt's backbone K/V rows [0, rows) of every layer, dense: [layer][K|V][kv head][rows][hd] bf16 (csm_prefix_capture).
-struct CsmPrefix {
-    CsmModel* owner;                    // the handle it was captured from (nullptr once that handle is destroyed: the snapshot is gone with it)
-    int n_layers, kv_heads, hd, rows, device;
-    bf16_t* data;
-    size_t bytes;
-};
-
-#define HIPCHK(h, x)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) {                                                              \
-            char buf_[256];                                                                  \
-            snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            if (h) (h)->err = buf_; else g_create_err = buf_;                                \
-            return CSM_E_HIP;                                                                \
-        }                                                                                    \
-    } while (0)
+const DevBackend* hip_backend() { return &HIP_BACKEND; }
 
 // every captured frame step is dropped (the next csm_frame_step of each key captures again): the step's node list changed
 static void drop_frame_graphs(CsmModel* m) {
@@ -195,16 +48,9 @@ static void drop_frame_graphs(CsmModel* m) {
     }
 }
 
-static int fail(CsmModel* h, int code, const char* msg) {
+int fail(CsmModel* h, int code, const char* msg) {
     if (h) h->err = msg; else g_create_err = msg;
     return code;
-}
-
-// a device allocation the handle owns, optionally with every byte set to `fill`; *p stays null on failure (and the last-error word is clean)
-template <class T> static hipError_t dev_get(CsmModel* m, T** p, size_t bytes, int fill = DevPool::NO_FILL) {
-    const hipError_t e = (hipError_t)m->pool.get(p, bytes, fill);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return e;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -890,9 +736,7 @@ static inline void fresh_clear(CsmModel* m, int slot) {
     if (slot >= 0 && slot < (int)m->rf_fresh_host.size() && m->rf_fresh_host[(size_t)slot]) { m->rf_fresh_host[(size_t)slot] = 0; m->rf_fresh_count -= 1; }
 }
 static inline void fresh_clear_all(CsmModel* m) { m->rf_fresh_host.assign(m->rf_fresh_host.size(), 0); m->rf_fresh_count = 0; }
-// a refill beside the loop, or a group of them, has begun and not completed / `slot` is (one of) its slot(s)
-static inline bool refill_pending(const CsmModel* m) { return refill_pending(m->rf); }
-static inline bool slot_refilling(const CsmModel* m, int slot) { return refill_has_slot(m->rf, slot); }
+// (refill_pending(m) and slot_refilling(m, slot) are csm_model.h's: the K/V stores ask them too)
 static inline bool refill_beside_ok(const CsmModel* m, int B) { return m->wide_path && B >= m->wide_min && B <= m->max_batch; }
 static inline bool frame_injects(const CsmModel* m, int B) { return m->rf_last != nullptr && refill_beside_ok(m, B); }
 
@@ -1324,9 +1168,7 @@ extern "C" void csm_destroy(csm_handle m) {
     if (!m) return;
     drop_frame_graphs(m);
     if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
-    for (CsmPrefix* p : m->prefixes) { (void)hipFree(p->data); p->data = nullptr; p->owner = nullptr; }      // (the caller still destroys the objects)
-    for (CsmSession* s : m->sessions) s->owner = nullptr;                                                     // (likewise: they can only be closed now)
-    delete m->sess;
+    kv_stores_release(m);               // live prefixes freed and orphaned, open sessions orphaned (csm_kv_store.hip)
     m->pool.release_all();
     delete m;
 }
@@ -1873,400 +1715,6 @@ extern "C" int csm_refill_group_advance(csm_handle m, int max_layers, void* stre
 
 extern "C" int csm_refill_supported(csm_handle m, int B) { return m && B >= 1 && refill_beside_ok(m, B) ? 1 : 0; }
 
-// ---------------------------------------------------------------------------------------
-// prefix store: K/V snapshots of prompt prefixes (the reference re-runs the whole 900-1,550-row voice prompt for every sentence,
-// tts_service.py:191-207).  The backbone cache is [L][B][KV][cache_len][hd], so rows [0, rows) of one slot are L * 2 * KV runs of
-// rows * hd contiguous elements; a snapshot keeps the runs back to back.  One launch moves every run of every listed slot: grid =
-// (pieces of a run, run, slot), 16 B per lane, four independent loads in flight per lane before the first store.  The slot list
-// travels in the kernel arguments (max_batch <= 256), so an apply needs neither a host-to-device copy nor a synchronisation.
-// ---------------------------------------------------------------------------------------
-#define PREFIX_VECS_PER_BLOCK (256 * 4)
-struct PrefixSlots { unsigned short s[256]; };
-
-template <bool APPLY>
-__global__ __launch_bounds__(256) void k_prefix_copy(bf16_t* kc, bf16_t* vc, bf16_t* snap, long run_vecs, int kv_heads, long layer_stride,
-                                                     long slot_stride, long head_stride, PrefixSlots sl) {
-    const int run = blockIdx.y, kvh = run % kv_heads, which = (run / kv_heads) & 1, l = run / (2 * kv_heads);
-    const long slot = sl.s[blockIdx.z];
-    uint4* c = (uint4*)((which ? vc : kc) + (long)l * layer_stride + slot * slot_stride + (long)kvh * head_stride);
-    uint4* s = (uint4*)snap + (long)run * run_vecs;
-    const long i0 = (long)blockIdx.x * PREFIX_VECS_PER_BLOCK + threadIdx.x;
-    uint4 v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long i = i0 + j * 256;
-        if (i < run_vecs) v[j] = APPLY ? s[i] : c[i];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long i = i0 + j * 256;
-        if (i < run_vecs) { if (APPLY) c[i] = v[j]; else s[i] = v[j]; }
-    }
-}
-
-static hipError_t launch_prefix_copy(CsmModel* m, const CsmPrefix* p, const PrefixSlots& sl, int n, bool apply, hipStream_t st) {
-    const Stack& S = m->bb;
-    const long run_vecs = (long)p->rows * p->hd / 8;
-    const long head_stride = (long)S.cache_len * S.hd, slot_stride = (long)S.d.n_kv_heads * head_stride;
-    const dim3 grid((unsigned)((run_vecs + PREFIX_VECS_PER_BLOCK - 1) / PREFIX_VECS_PER_BLOCK), (unsigned)(p->n_layers * 2 * p->kv_heads), (unsigned)n);
-    if (apply) hipLaunchKernelGGL(k_prefix_copy<true>, grid, dim3(256), 0, st, S.kc, S.vc, p->data, run_vecs, p->kv_heads, S.layer_stride, slot_stride, head_stride, sl);
-    else hipLaunchKernelGGL(k_prefix_copy<false>, grid, dim3(256), 0, st, S.kc, S.vc, p->data, run_vecs, p->kv_heads, S.layer_stride, slot_stride, head_stride, sl);
-    return hipGetLastError();
-}
-
-extern "C" int csm_prefix_capture(csm_handle m, int slot, int rows, csm_prefix* out, void* stream) {
-    if (!m || !out) return fail(m, CSM_E_INVALID, "csm_prefix_capture: null argument");
-    if (slot < 0 || slot >= m->max_batch || rows < 1 || rows >= m->cfg.backbone.max_seq) return fail(m, CSM_E_INVALID, "csm_prefix_capture: slot outside the batch or rows outside [1, max_seq)");
-    if (slot_refilling(m, slot)) return fail(m, CSM_E_STATE, "csm_prefix_capture: the slot's refill beside the frame loop is still running (csm_refill_advance)");
-    hipStream_t st = (hipStream_t)stream;
-    int pos = 0;
-    HIPCHK(m, hipMemcpyAsync(&pos, m->cur_pos + slot, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(m, hipStreamSynchronize(st));
-    if (rows > pos) return fail(m, CSM_E_INVALID, "csm_prefix_capture: rows beyond the slot's position (those rows have not been written)");
-    CsmPrefix* p = new CsmPrefix();
-    p->owner = m; p->n_layers = m->cfg.backbone.n_layers; p->kv_heads = m->cfg.backbone.n_kv_heads; p->hd = m->bb.hd; p->rows = rows; p->device = m->device;
-    p->bytes = (size_t)p->n_layers * 2 * p->kv_heads * rows * p->hd * 2;
-    hipError_t e = hipMalloc((void**)&p->data, p->bytes);
-    if (e == hipSuccess) {
-        PrefixSlots sl; sl.s[0] = (unsigned short)slot;
-        e = launch_prefix_copy(m, p, sl, 1, false, st);
-        if (e != hipSuccess) (void)hipFree(p->data);
-    }
-    if (e != hipSuccess) { delete p; HIPCHK(m, e); }
-    m->prefixes.push_back(p);
-    *out = p;
-    return CSM_OK;
-}
-
-extern "C" int csm_prefix_apply(csm_handle m, csm_prefix p, const int32_t* slots, int n, void* stream) {
-    if (!m || !p || !slots || n < 0 || n > m->max_batch) return fail(m, CSM_E_INVALID, "csm_prefix_apply: bad argument");
-    if (!p->data) return fail(m, CSM_E_INVALID, "csm_prefix_apply: the handle this prefix was captured from has been destroyed");
-    if (p->n_layers != m->cfg.backbone.n_layers || p->kv_heads != m->cfg.backbone.n_kv_heads || p->hd != m->bb.hd || p->device != m->device)
-        return fail(m, CSM_E_INVALID, "csm_prefix_apply: the prefix comes from a handle of another shape (layers / kv heads / head_dim) or another GPU");
-    if (p->rows >= m->cfg.backbone.max_seq) return fail(m, CSM_E_INVALID, "csm_prefix_apply: the prefix has max_seq rows or more");
-    PrefixSlots sl;
-    for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_prefix_apply: slot outside the batch");
-        if (slot_refilling(m, slots[i])) return fail(m, CSM_E_STATE, "csm_prefix_apply: the slot's refill beside the frame loop is still running (csm_refill_advance)");
-        sl.s[i] = (unsigned short)slots[i];
-    }
-    if (n == 0) return CSM_OK;
-    HIPCHK(m, launch_prefix_copy(m, p, sl, n, true, (hipStream_t)stream));
-    return CSM_OK;
-}
-
-extern "C" int csm_prefix_rows(csm_prefix p) { return p ? p->rows : 0; }
-extern "C" size_t csm_prefix_bytes(csm_prefix p) { return p ? p->bytes : 0; }
-
-extern "C" int csm_prefix_read(csm_prefix p, void* host_buf, size_t bytes, void* stream) {
-    if (!p || !host_buf || bytes != p->bytes) return fail(p ? p->owner : nullptr, CSM_E_INVALID, "csm_prefix_read: null argument or bytes != csm_prefix_bytes");
-    if (!p->data) return fail(nullptr, CSM_E_INVALID, "csm_prefix_read: the handle this prefix was captured from has been destroyed");
-    HIPCHK(p->owner, hipMemcpyAsync(host_buf, p->data, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(p->owner, hipStreamSynchronize((hipStream_t)stream));
-    return CSM_OK;
-}
-
-extern "C" void csm_prefix_destroy(csm_prefix p) {
-    if (!p) return;
-    if (p->owner) {
-        auto& v = p->owner->prefixes;
-        v.erase(std::remove(v.begin(), v.end(), p), v.end());
-    }
-    if (p->data) (void)hipFree(p->data);
-    delete p;
-}
-
-// ---------------------------------------------------------------------------------------
-// session store: a conversation's backbone K/V carried from turn to turn.  The prefix store snapshots a slot into a dense
-// allocation of its own -- right once per voice, wrong once per turn between two frame steps (an allocation, a synchronisation, every row
-// copied again).  Here the rows live in fixed-size pages of ONE pool allocated at csm_session_store_create: a page holds page_rows rows
-// of each of the L * 2 * KV runs of a slot's cache, [run][page_rows][hd] -- at CSM-1B with 64 rows 8 KB per run, 2 MB per page.  A save
-// appends only the rows the session does not hold; a load gathers the pages of up to 32 sessions into as many slots in one launch.
-// The page lists reach the kernels through a device table [session id][logical page] that the SAVE writes from its kernel arguments
-// (k_session_tab, <= 256 entries per launch) ahead of the copy; the load passes (session id, slot, rows) per pair in its arguments and
-// reads the table.  So save, load and truncate allocate nothing, copy nothing from the host and never synchronise, and a page that a
-// truncate or close gives back may go to the next save at once: everything that still reads it was enqueued earlier on the one stream.
-// Both copies are k_prefix_copy's: 16 B per lane, four independent loads in flight per lane before the first store, indexed by the
-// position in the slot's run (each lane finds its own page: neighbouring lanes share it, the table entry comes from the cache).
-// ---------------------------------------------------------------------------------------
-#define SESS_VECS_PER_BLOCK (256 * 4)
-#define SESS_TAB_PER_LAUNCH 256
-#define SESS_MAX_LOAD 32
-struct SessTabEntries { int page[SESS_TAB_PER_LAUNCH]; };
-struct SessLoadPairs { int id[SESS_MAX_LOAD], slot[SESS_MAX_LOAD], rows[SESS_MAX_LOAD]; };
-struct SessGeom { long layer_stride, slot_stride, head_stride; int kv_heads, n_runs, page_rows, hv; };     // hv: 16-byte pieces per row (hd / 8)
-
-__global__ __launch_bounds__(SESS_TAB_PER_LAUNCH) void k_session_tab(int* tab_row, int first, int n, SessTabEntries e) {
-    if ((int)threadIdx.x < n) tab_row[first + threadIdx.x] = e.page[threadIdx.x];
-}
-
-// pieces [i0 + j * 256 (j < 4)) below `end` of run `run` of one slot <-> the session's pages; i counts 16-byte pieces from the run's row 0
-template <bool LOAD>
-__device__ __forceinline__ void session_copy(uint4* c, uint4* pool, const int* tab_row, const SessGeom& g, int run, long i0, long end) {
-    const long page_vecs = (long)g.page_rows * g.hv;
-    uint4* pp[4];
-    uint4 v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long i = i0 + j * 256;
-        if (i < end) {
-            const long lp = i / page_vecs;
-            pp[j] = pool + ((long)tab_row[lp] * g.n_runs + run) * page_vecs + (i - lp * page_vecs);
-            v[j] = LOAD ? *pp[j] : c[i];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long i = i0 + j * 256;
-        if (i < end) { if (LOAD) c[i] = v[j]; else *pp[j] = v[j]; }
-    }
-}
-
-__device__ __forceinline__ uint4* session_run(bf16_t* kc, bf16_t* vc, const SessGeom& g, int run, long slot) {
-    const int kvh = run % g.kv_heads, which = (run / g.kv_heads) & 1, l = run / (2 * g.kv_heads);
-    return (uint4*)((which ? vc : kc) + (long)l * g.layer_stride + slot * g.slot_stride + (long)kvh * g.head_stride);
-}
-
-// slot rows [from, to) -> the session's pages.  grid = (pieces of the range, run)
-__global__ __launch_bounds__(256) void k_session_save(bf16_t* kc, bf16_t* vc, bf16_t* pool, const int* tab_row, SessGeom g, int slot, int from, int to) {
-    const int run = blockIdx.y;
-    session_copy<false>(session_run(kc, vc, g, run, slot), (uint4*)pool, tab_row, g, run,
-                        (long)from * g.hv + (long)blockIdx.x * SESS_VECS_PER_BLOCK + threadIdx.x, (long)to * g.hv);
-}
-
-// the pages of pair z's session -> rows [0, rows[z]) of slot[z], all pairs in one launch.  grid = (pieces of the longest, run, pair)
-__global__ __launch_bounds__(256) void k_session_load(bf16_t* kc, bf16_t* vc, bf16_t* pool, const int* tab, int tab_stride, SessGeom g, SessLoadPairs a) {
-    const int run = blockIdx.y, z = blockIdx.z;
-    const long end = (long)a.rows[z] * g.hv, b0 = (long)blockIdx.x * SESS_VECS_PER_BLOCK;
-    if (b0 >= end) return;                                      // (a shorter session of the group)
-    session_copy<true>(session_run(kc, vc, g, run, a.slot[z]), (uint4*)pool, tab + (long)a.id[z] * tab_stride, g, run, b0 + threadIdx.x, end);
-}
-
-// csm_session_forget: the session's rows [first, rows) rewritten into fresh pages without its old rows [from, from + d).  New row r < from is
-// old row r; new row r >= from is old row r + d, verbatim in V runs and with its keys rotated BACK by d positions in K runs (K is stored
-// rotated; rot[j] = (cos, sin)(d * theta_j), so a pair (x0, x1) becomes (x0 c + x1 s, x1 c - x0 s)): fp32 on the bf16 values, multiplies and
-// adds kept apart as in dp_rope_pair so that they equal torch's bit for bit, one rounding to bf16.  old_row: the session's table row (still
-// the old page list: it is rewritten after this launch), new_row: the staging row.  k_session_load's shape: 16 B per lane, four
-// independent loads in flight per lane before the first store; grid = (pieces of the rewritten range, run).  rot is staged into LDS
-// while the loads fly (a lane-varying index into kernel arguments would go to scratch).
-#define SESS_ROT_MAX 64                 // head_dim / 2 at head_dim 128
-struct SessRot { float cs[SESS_ROT_MAX][2]; };
-__device__ __forceinline__ uint32_t session_unrope_pair(uint32_t w, float2 cs) {
-#pragma clang fp contract(off)
-    const float x0 = lo2f(w), x1 = hi2f(w);
-    const float o0 = x0 * cs.x + x1 * cs.y;
-    const float o1 = x1 * cs.x - x0 * cs.y;
-    return pack_bf(o0, o1);
-}
-__global__ __launch_bounds__(256) void k_session_forget(bf16_t* pool_, const int* old_row, const int* new_row, SessGeom g, int first, int from, int d, int rows, int n_rot, SessRot rot) {
-    __shared__ float2 lrot[SESS_ROT_MAX];
-    uint4* pool = (uint4*)pool_;
-    const int run = blockIdx.y;
-    const bool is_k = ((run / g.kv_heads) & 1) == 0;
-    const long page_vecs = (long)g.page_rows * g.hv, end = (long)rows * g.hv, moved_from = (long)from * g.hv;
-    const long i0 = (long)first * g.hv + (long)blockIdx.x * SESS_VECS_PER_BLOCK + threadIdx.x;
-    uint4* pp[4];
-    uint4 v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long i = i0 + j * 256;
-        if (i < end) {
-            const long si = i >= moved_from ? i + (long)d * g.hv : i, sp = si / page_vecs, lp = i / page_vecs;
-            v[j] = pool[((long)old_row[sp] * g.n_runs + run) * page_vecs + (si - sp * page_vecs)];
-            pp[j] = pool + ((long)new_row[lp] * g.n_runs + run) * page_vecs + (i - lp * page_vecs);
-        }
-    }
-    if (is_k) {                                                 // (uniform over the block)
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int j = 0; j < SESS_ROT_MAX; ++j)
-                if (j < n_rot) lrot[j] = make_float2(rot.cs[j][0], rot.cs[j][1]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long i = i0 + j * 256;
-            if (i < end && i >= moved_from) {
-                const int p = (int)(i % g.hv) * 4;              // the row's pair index of this piece's first pair
-                v[j].x = session_unrope_pair(v[j].x, lrot[p]);     v[j].y = session_unrope_pair(v[j].y, lrot[p + 1]);
-                v[j].z = session_unrope_pair(v[j].z, lrot[p + 2]); v[j].w = session_unrope_pair(v[j].w, lrot[p + 3]);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (i0 + j * 256 < end) *pp[j] = v[j];
-}
-
-static SessGeom session_geom(const CsmModel* m) {
-    const Stack& S = m->bb;
-    SessGeom g;
-    g.head_stride = (long)S.cache_len * S.hd; g.slot_stride = (long)S.d.n_kv_heads * g.head_stride; g.layer_stride = S.layer_stride;
-    g.kv_heads = S.d.n_kv_heads; g.n_runs = S.d.n_layers * 2 * S.d.n_kv_heads; g.page_rows = m->sess->page_rows(); g.hv = S.hd / 8;
-    return g;
-}
-
-static bool session_live(const CsmModel* m, const CsmSession* s) {     // by address: a closed session's object is gone and is never read
-    return s && std::find(m->sessions.begin(), m->sessions.end(), s) != m->sessions.end();
-}
-
-extern "C" int csm_session_store_create(csm_handle m, int n_pages, int page_rows) {
-    if (!m) return fail(m, CSM_E_INVALID, "csm_session_store_create: null handle");
-    if (m->sess) return fail(m, CSM_E_STATE, "csm_session_store_create: this handle has a session store already");
-    const Stack& S = m->bb;
-    if (n_pages < 1 || page_rows < 1 || page_rows > S.cache_len || S.hd % 8 != 0) return fail(m, CSM_E_INVALID, "csm_session_store_create: n_pages >= 1, 1 <= page_rows <= max_seq, head_dim % 8 == 0 required");
-    const size_t page_bytes = (size_t)S.d.n_layers * 2 * S.d.n_kv_heads * page_rows * S.hd * 2;
-    const int stride = (S.cache_len + page_rows - 1) / page_rows, max_sessions = n_pages + 32;
-    const size_t mark = m->pool.mark();
-    hipError_t e = dev_get(m, &m->sess_pool, page_bytes * (size_t)n_pages);
-    if (e == hipSuccess) e = dev_get(m, &m->sess_tab, (size_t)(max_sessions + 1) * stride * sizeof(int), 0);     // (+ 1: csm_session_forget's staging row)
-    if (e != hipSuccess) { m->pool.release_to(mark); m->sess_pool = nullptr; m->sess_tab = nullptr; HIPCHK(m, e); }
-    m->sess_tab_stride = stride;
-    m->sess = new SessionPages(n_pages, page_rows, max_sessions);
-    return CSM_OK;
-}
-
-extern "C" int csm_session_open(csm_handle m, csm_session* out) {
-    if (!m || !out) return fail(m, CSM_E_INVALID, "csm_session_open: null argument");
-    if (!m->sess) return fail(m, CSM_E_STATE, "csm_session_open: no session store (csm_session_store_create)");
-    const int id = m->sess->open();
-    if (id < 0) return fail(m, CSM_E_STATE, "csm_session_open: too many open sessions (pages + 32)");
-    CsmSession* s = new CsmSession{m, id};
-    m->sessions.push_back(s);
-    *out = s;
-    return CSM_OK;
-}
-
-// entries [first, end) of a table row from the session's page list, <= 256 per launch
-static hipError_t session_tab_write(CsmModel* m, int id, int* tab_row, int first, int end, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    for (; first < end && e == hipSuccess; first += SESS_TAB_PER_LAUNCH) {
-        SessTabEntries te;
-        const int n = std::min(end - first, SESS_TAB_PER_LAUNCH);
-        for (int k = 0; k < n; ++k) te.page[k] = m->sess->page_at(id, first + k);
-        hipLaunchKernelGGL(k_session_tab, dim3(1), dim3(SESS_TAB_PER_LAUNCH), 0, st, tab_row, first, n, te);
-        e = hipGetLastError();
-    }
-    return e;
-}
-
-extern "C" int csm_session_save(csm_handle m, csm_session s, int slot, int rows, void* stream) {
-    if (!m || !m->sess) return fail(m, m ? CSM_E_STATE : CSM_E_INVALID, "csm_session_save: null handle or no session store");
-    if (!session_live(m, s)) return fail(m, CSM_E_INVALID, "csm_session_save: not an open session of this handle");
-    const int from = m->sess->rows(s->id);
-    if (slot < 0 || slot >= m->max_batch || rows < from || rows >= m->cfg.backbone.max_seq)
-        return fail(m, CSM_E_INVALID, "csm_session_save: slot outside the batch, rows below the session's row count, or rows >= max_seq");
-    if (slot_refilling(m, slot)) return fail(m, CSM_E_STATE, "csm_session_save: the slot's refill beside the frame loop is still running (csm_refill_advance)");
-    if (rows == from) return CSM_OK;
-    const int had_pages = m->sess->pages(s->id);
-    if (!m->sess->grow_to(s->id, rows)) return fail(m, CSM_E_NO_PAGES, "csm_session_save: the pool has too few free pages (truncate or close a session and call again)");
-    hipStream_t st = (hipStream_t)stream;
-    int* tab_row = m->sess_tab + (long)s->id * m->sess_tab_stride;
-    hipError_t e = session_tab_write(m, s->id, tab_row, had_pages, m->sess->pages(s->id), st);     // the new pages' table entries, ahead of the copy
-    if (e == hipSuccess) {
-        const SessGeom g = session_geom(m);
-        const long vecs = (long)(rows - from) * g.hv;
-        hipLaunchKernelGGL(k_session_save, dim3((unsigned)((vecs + SESS_VECS_PER_BLOCK - 1) / SESS_VECS_PER_BLOCK), (unsigned)g.n_runs), dim3(256), 0, st,
-                           m->bb.kc, m->bb.vc, m->sess_pool, (const int*)tab_row, g, slot, from, rows);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { (void)m->sess->truncate(s->id, from); HIPCHK(m, e); }
-    return CSM_OK;
-}
-
-extern "C" int csm_session_load(csm_handle m, const csm_session* ss, const int32_t* slots, int n, void* stream) {
-    if (!m || !m->sess) return fail(m, m ? CSM_E_STATE : CSM_E_INVALID, "csm_session_load: null handle or no session store");
-    if (!ss || !slots || n < 0 || n > SESS_MAX_LOAD) return fail(m, CSM_E_INVALID, "csm_session_load: null argument or n outside [0, 32]");
-    SessLoadPairs a;
-    int longest = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!session_live(m, ss[i])) return fail(m, CSM_E_INVALID, "csm_session_load: not an open session of this handle");
-        if (slots[i] < 0 || slots[i] >= m->max_batch) return fail(m, CSM_E_INVALID, "csm_session_load: slot outside the batch");
-        for (int j = 0; j < i; ++j)
-            if (slots[j] == slots[i]) return fail(m, CSM_E_INVALID, "csm_session_load: a slot is listed twice");
-        if (slot_refilling(m, slots[i])) return fail(m, CSM_E_STATE, "csm_session_load: the slot's refill beside the frame loop is still running (csm_refill_advance)");
-        a.id[i] = ss[i]->id; a.slot[i] = slots[i]; a.rows[i] = m->sess->rows(ss[i]->id);
-        longest = std::max(longest, a.rows[i]);
-    }
-    if (longest == 0) return CSM_OK;
-    const SessGeom g = session_geom(m);
-    const long vecs = (long)longest * g.hv;
-    hipLaunchKernelGGL(k_session_load, dim3((unsigned)((vecs + SESS_VECS_PER_BLOCK - 1) / SESS_VECS_PER_BLOCK), (unsigned)g.n_runs, (unsigned)n), dim3(256), 0,
-                       (hipStream_t)stream, m->bb.kc, m->bb.vc, m->sess_pool, (const int*)m->sess_tab, m->sess_tab_stride, g, a);
-    HIPCHK(m, hipGetLastError());
-    return CSM_OK;
-}
-
-extern "C" int csm_session_forget(csm_handle m, csm_session s, int from, int to, const float* rot, void* stream) {
-    if (!m || !m->sess) return fail(m, m ? CSM_E_STATE : CSM_E_INVALID, "csm_session_forget: null handle or no session store");
-    if (!session_live(m, s)) return fail(m, CSM_E_INVALID, "csm_session_forget: not an open session of this handle");
-    const int had = m->sess->rows(s->id), hd = m->bb.hd;
-    if (from < 0 || to < from || to > had) return fail(m, CSM_E_INVALID, "csm_session_forget: 0 <= from <= to <= the session's row count required");
-    if (from == to) return CSM_OK;
-    if (!rot || (hd != 64 && hd != 128)) return fail(m, CSM_E_INVALID, "csm_session_forget: null rotation table, or a head_dim other than 64 or 128");
-    SessRot r;
-    for (int j = 0; j < hd / 2; ++j) { r.cs[j][0] = rot[2 * j]; r.cs[j][1] = rot[2 * j + 1]; }
-    for (int j = hd / 2; j < SESS_ROT_MAX; ++j) { r.cs[j][0] = 1.f; r.cs[j][1] = 0.f; }
-    const int rc = m->sess->forget(s->id, from, to);
-    if (rc == SessionPages::FORGET_NO_PAGES) return fail(m, CSM_E_NO_PAGES, "csm_session_forget: the pool has too few free pages for the rewritten rows (truncate or close a session and call again)");
-    if (rc != SessionPages::FORGET_OK) return fail(m, CSM_E_INVALID, "csm_session_forget: refused by the page bookkeeping");
-    const SessGeom g = session_geom(m);
-    const int k0 = from / g.page_rows, first = k0 * g.page_rows, rows = m->sess->rows(s->id), pages = m->sess->pages(s->id);
-    hipStream_t st = (hipStream_t)stream;
-    int* tab_row = m->sess_tab + (long)s->id * m->sess_tab_stride;
-    int* stage_row = m->sess_tab + (long)m->sess->max_sessions() * m->sess_tab_stride;
-    hipError_t e = hipSuccess;
-    if (rows > first) {                                         // the new page list into the staging row, the copy (it reads the old list in the session's row), then the session's row
-        e = session_tab_write(m, s->id, stage_row, k0, pages, st);
-        if (e == hipSuccess) {
-            const long vecs = (long)(rows - first) * g.hv;
-            hipLaunchKernelGGL(k_session_forget, dim3((unsigned)((vecs + SESS_VECS_PER_BLOCK - 1) / SESS_VECS_PER_BLOCK), (unsigned)g.n_runs), dim3(256), 0, st,
-                               m->sess_pool, (const int*)tab_row, (const int*)stage_row, g, first, from, to - from, rows, hd / 2, r);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = session_tab_write(m, s->id, tab_row, k0, pages, st);
-    }
-    if (e != hipSuccess) { (void)m->sess->truncate(s->id, first); HIPCHK(m, e); }       // (the kept pages below `first` are whole and untouched)
-    m->sess_forgets += 1; m->sess_forget_moved += rows - from;
-    return CSM_OK;
-}
-
-extern "C" int csm_session_truncate(csm_session s, int rows) {
-    if (!s || !s->owner) return fail(nullptr, CSM_E_INVALID, "csm_session_truncate: null session, or its handle has been destroyed");
-    if (!s->owner->sess->truncate(s->id, rows)) return fail(s->owner, CSM_E_INVALID, "csm_session_truncate: rows outside [0, the session's row count]");
-    return CSM_OK;
-}
-
-extern "C" int csm_session_rows(csm_session s) { return s && s->owner ? s->owner->sess->rows(s->id) : 0; }
-extern "C" int csm_session_pages(csm_session s) { return s && s->owner ? s->owner->sess->pages(s->id) : 0; }
-
-extern "C" int csm_session_read(csm_session s, void* host_buf, size_t bytes, void* stream) {
-    if (!s || !s->owner) return fail(nullptr, CSM_E_INVALID, "csm_session_read: null session, or its handle has been destroyed");
-    CsmModel* m = s->owner;
-    const SessGeom g = session_geom(m);
-    const int rows = m->sess->rows(s->id);
-    const size_t row_bytes = (size_t)g.hv * 16, page_run_bytes = row_bytes * g.page_rows;
-    if (bytes != row_bytes * rows * g.n_runs || (!host_buf && bytes)) return fail(m, CSM_E_INVALID, "csm_session_read: bytes != layers * 2 * kv heads * rows * head_dim * 2, or a null buffer");
-    std::vector<SessionCopy> plan;
-    (void)m->sess->plan(s->id, 0, rows, &plan);
-    for (const SessionCopy& c : plan)                       // one strided copy per page: the page's piece of every run
-        HIPCHK(m, hipMemcpy2DAsync((char*)host_buf + c.slot_row * row_bytes, row_bytes * rows,
-                                   (const char*)m->sess_pool + (size_t)c.page * g.n_runs * page_run_bytes + c.page_row * row_bytes, page_run_bytes,
-                                   c.rows * row_bytes, (size_t)g.n_runs, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(m, hipStreamSynchronize((hipStream_t)stream));
-    return CSM_OK;
-}
-
-extern "C" void csm_session_close(csm_session s) {
-    if (!s) return;
-    if (s->owner) {
-        s->owner->sess->close(s->id);
-        auto& v = s->owner->sessions;
-        v.erase(std::remove(v.begin(), v.end(), s), v.end());
-    }
-    delete s;
-}
-
 extern "C" int csm_num_frames(csm_handle m) { return m ? m->host_frames : 0; }
 
 extern "C" int csm_read_frames(csm_handle m, int B, int first, int n, int32_t* host_frames, int32_t* host_eos_at, void* stream) {
@@ -2380,12 +1828,7 @@ extern "C" int csm_describe(csm_handle m, char* buf, int n) {
     snprintf(tmp, sizeof tmp, "; layer0_qkv_table=%d; attn_merge_in_kernel=%d; frame_graphs=LRU of %d (%d captured)", m->qkv0_tab != nullptr, m->attn_ctr != nullptr,
              CSM_FRAME_GRAPHS, m->graph_captures);
     t += tmp;
-    { size_t pb = 0; for (const CsmPrefix* p : m->prefixes) pb += p->bytes;
-      snprintf(tmp, sizeof tmp, "; prefix_store=%d prefixes, %zu bytes", (int)m->prefixes.size(), pb); t += tmp; }
-    snprintf(tmp, sizeof tmp, "; session_store=%d sessions, %d/%d pages", m->sess ? m->sess->sessions() : 0, m->sess ? m->sess->pages_used() : 0, m->sess ? m->sess->pages_total() : 0);
-    t += tmp;
-    snprintf(tmp, sizeof tmp, "; session_forgets=%d (%ld rows moved)", m->sess_forgets, m->sess_forget_moved);
-    t += tmp;
+    kv_stores_describe(m, &t);          // "; prefix_store=...; session_store=...; session_forgets=..."
     { int ne = 0, ns = 0; for (unsigned char f : m->slot_tab_host) { ne += f & 1; ns += (f >> 1) & 1; }
       snprintf(tmp, sizeof tmp, "; slot_sampling=%d entries (%d with own seed)%s", ne, ns, m->slot_tab_used ? ", frame steps carry the table" : ""); t += tmp; }
     const std::string sw = set_switches(true);

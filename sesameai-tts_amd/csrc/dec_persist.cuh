@@ -33,7 +33,6 @@
 #include "gemv.cuh"
 #include "sampler.cuh"
 
-typedef unsigned long long dp_u64;
 #define DP_NB 256                     // workgroups = CUs of an MI355X
 #ifndef DP_NREP
 #define DP_NREP 8                     // granule copies (one per XCD under round-robin placement: the 32 workgroups of an XCD poll the same lines;

@@ -68,20 +68,6 @@ static __global__ __launch_bounds__(256) void k_embed_sum(const int* tokens /*[M
 // ---------------------------------------------------------------------------------------
 #define SAMPLE_MAX_ITERS 8   // supports V <= 8*512
 
-// One entry of the per-slot sampling table (csm_slot_sampling_set), 32 bytes.  topk == 0: no entry -- the slot is
-// sampled with the launch's scalars and the handle's stream.  own_rng: the slot draws Philox at key `seed` and counter (vocabulary
-// index, 0, codebook, `counter`), `counter` being the utterance's own frame index (k_advance).  {seed, counter} sit where a launch's
-// {seed, step} words sit, so a persistent kernel stages either pair with the same four dword loads.
-struct SlotSampling {
-    float temperature;
-    int topk;
-    int own_rng;
-    int pad_;
-    uint64_t seed;
-    uint64_t counter;
-};
-static_assert(sizeof(SlotSampling) == 32, "SlotSampling is addressed as 8 dwords");
-
 struct SampleArgs {
     const bf16_t* logits;     // [B][ldl]
     int ldl, V;

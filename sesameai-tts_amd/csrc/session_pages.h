@@ -1,6 +1,6 @@
 // Page bookkeeping of the session store (include/csm_hip.h csm_session_*): a pool of n_pages pages of page_rows K/V rows each with a free
 // list, and per session an ordered page list and a row count -- logical page k of a session holds its rows [k * page_rows, (k + 1) *
-// page_rows).  No HIP here: csm_engine.hip owns the device memory the page numbers index and enqueues the copies this header plans;
+// page_rows).  No HIP here: csm_kv_store.hip owns the device memory the page numbers index and enqueues the copies this header plans;
 // tools/session_pages_check.cpp and tools/session_forget_check.cpp drive it on the CPU.  Session ids are small integers handed out again
 // after close (the engine uses them as rows of its device page table); every operation on an id that is not open is refused and changes
 // nothing.
