@@ -282,6 +282,46 @@ long mimi_fin_out_count(long n_in, long lead, long tail);
 int  mimi_fin_segments(mimi_finisher p, const float* const* in, const long* n_in, const int32_t* lead, const int32_t* tail,
                        const int32_t* fade, int n, int16_t* out, long* out_off, long* n_out, void* stream);
 
+/* ---- A pool of stateful TIME-STRETCH streams (speech rate without a change of pitch, behind the decoder) ----
+ * WSOLA: overlap-add of 512-sample blocks, each joint placed where the waveforms agree.  Every decision is exact integer arithmetic, so the
+ * device computes THE RULE below bit for bit.  Constants in samples: H = 512 (block and hop, 21.3 ms at 24 kHz), D = 256 (search radius).
+ * Speed is an integer in permille, pm in [500, 2000] (1200 = 1.2 x faster).  For a clip x[0 .. N) of fp32:
+ *   - x^[i] = x[i] for 0 <= i < N, else 0.0f (zero extension); q^ likewise.
+ *   - search samples q[i] = clamp(rint(x[i] * 2048.0f), -2047, 2047), rint to nearest even, a non-finite x[i] gives 0.  12 bits on purpose:
+ *     512 * 2047^2 = 2,145,387,008 < 2^31, so a whole score fits a signed 32-bit accumulator in any summation order.
+ *   - M = (N * 1000 + pm - 1) / pm outputs y[0 .. M) in K = ceil(M / H) blocks, the last one cut at M.
+ *   - block 0: c_0 = 0, y[j] = x^[j].
+ *   - block k >= 1: a_k = (k * H * pm) / 1000 (64-bit integers), b_k = c_(k-1) + H (the natural continuation of what was last played),
+ *     S_k(d) = sum over j < H of q^[a_k + d + j] * q^[b_k + j] for d = -D .. D, d_k = the SMALLEST d with the largest S_k, c_k = a_k + d_k,
+ *     y[k H + j] = fl(fl(x^[c_k + j] * r_j) + fl(x^[b_k + j] * (1 - r_j))) with r_j = j / 512: two fp32 multiplies and one fp32 add, NOT fused.
+ *   - a non-finite sample enters no decision (its q is 0) and appears in exactly the outputs mixed from it.
+ * STREAMING: block k comes out once the stream has received R >= a_k + D + 2 H samples in all, or at `final`, when all remaining blocks up
+ * to K come out and the stream is left fresh -- a function of k alone, so mimi_ts_pool_out_count is host arithmetic (latency: 1,280 samples).
+ * A stream's outputs, concatenated over ANY chunk schedule, are bit for bit the one-shot result; they do not depend on which streams share
+ * the call, on list order or on the stream id.  Per stream the device keeps the samples from a_(k'-1) - D on (k' the next block; fewer than
+ * 2,560 floats, two banks flipped per call: a call reads one and writes the other) and c of the last block; the host keeps {pm, R, k, bank}.
+ * A fresh stream reads neither, so mimi_ts_pool_reset (which also sets each listed stream's speed) is host arithmetic, no launch.  Streams of
+ * a new pool are fresh at pm = 1000.
+ * mimi_ts_pool_feed: stream streams[i] gets n_in[i] >= 0 fp32 samples at in + in_off[i] ELEMENTS; final[i] != 0 ends its clip.  in, out, d_out:
+ * device memory; streams, in_off, n_in, final: host arrays read before the call returns; n_out: a host array WRITTEN before the call returns.
+ * Outputs are packed back to back: stream i owns out[O_i .. O_i + n_out[i]), O_i = n_out[0] + .. + n_out[i-1].  d_out (may be NULL): d_k of
+ * every emitted block (0 for block 0), packed the same way by blocks: stream i owns ceil(n_out[i] / H) entries after those of the streams
+ * listed before it.  ONE launch per call, one workgroup per listed stream; the plan travels in the kernel arguments: no host-to-device copy,
+ * no allocation, no synchronisation.
+ * Returns -1 with a message in mimi_ts_pool_last_error, nothing enqueued and no state moved, for: n_streams outside [1, 64] (create); n
+ * outside [1, n_streams], a duplicate or out-of-range id, a speed outside [500, 2000] (reset); a negative n_in or in_off, a null pointer, a
+ * chunk that takes or gives more than 2^30 samples, a stream of more than 2^48 samples since its reset (feed).  -2: a HIP error.  Drive ONE
+ * HIP stream per pool at a time.                                                                                                          */
+#define MIMI_TS_MAX_STREAMS 64
+typedef struct MimiStretchPool* mimi_ts_pool;
+int  mimi_ts_pool_create(int n_streams, mimi_ts_pool* out);
+void mimi_ts_pool_destroy(mimi_ts_pool p);
+const char* mimi_ts_pool_last_error(mimi_ts_pool p);           /* p == NULL: why mimi_ts_pool_create failed (this thread) */
+int  mimi_ts_pool_reset(mimi_ts_pool p, const int32_t* streams, const int32_t* speed_pm, int n);
+long mimi_ts_pool_out_count(mimi_ts_pool p, int sid, long n_in, int final);
+int  mimi_ts_pool_feed(mimi_ts_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                       const float* in, float* out, long* n_out, int32_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,12 @@ MIMI_SIGNATURES = {
     "mimi_fin_last_error": (C.c_char_p, [_vp]),
     "mimi_fin_out_count": (_l, [_l, _l, _l]),
     "mimi_fin_segments": (_i, [_vp, C.POINTER(_vp), C.POINTER(_l), _vp, _vp, _vp, _i, _vp, C.POINTER(_l), C.POINTER(_l), _vp]),
+    "mimi_ts_pool_create": (_i, [_i, C.POINTER(_vp)]),
+    "mimi_ts_pool_destroy": (None, [_vp]),
+    "mimi_ts_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_ts_pool_reset": (_i, [_vp, _vp, _vp, _i]),
+    "mimi_ts_pool_out_count": (_l, [_vp, _i, _l, _i]),
+    "mimi_ts_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _vp, C.POINTER(_l), _vp, _vp]),
 }
 
 for _name, (_res, _args) in list(SIGNATURES.items()) + list(MIMI_SIGNATURES.items()):

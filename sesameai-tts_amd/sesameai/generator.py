@@ -470,34 +470,55 @@ class Generator:
                       temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
                       seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
                       sessions: Optional[Sequence[Optional[Conversation]]] = None, finish=None,
-                      on_result: Optional[Callable[[int, torch.Tensor], None]] = None) -> List[torch.Tensor]:
+                      on_result: Optional[Callable[[int, torch.Tensor], None]] = None, speed=None) -> List[torch.Tensor]:
         """``generate`` for a list of requests through the continuously refilled batch: one audio tensor per request
         (``max_audio_length_ms``, ``temperature``, ``topk``: one value, or one per request; ``seed``: one optional int per request;
         ``sessions``: one ``Conversation`` or None per request -- the context of a request with a session lists only the NEW segments).
         ``finish`` (None: the calls described above, exactly): a ``SegmentFinish``, or one per request -- the result is then what
         ``generate_segments`` returns for these prompts, finished int16 segments on the device, and ``on_result(i, pcm)`` fires as each
-        request completes."""
+        request completes.
+        ``speed`` (None: the calls described above, exactly): a speech-rate factor in 0.5 .. 2.0, or one (or None) per request -- each decoded
+        clip goes through the device time stretch (sesameai/stretch.py) before anything else sees it; with ``finish`` all clips that end in
+        a block share ONE stretch call."""
         max_generation_len = _frames_for(max_audio_length_ms)
         prompts = self._build_prompts(texts, speakers, contexts)
         if finish is not None:
             if sessions is not None:
                 raise ValueError("finish= with sessions=: not supported")
             return self.generate_segments(prompts, max_generation_len, temperature, topk, finish, seed=seed, refill_group=refill_group,
-                                          on_result=on_result)
+                                          on_result=on_result, **({} if speed is None else {"speed": speed}))
         if on_result is not None:
             raise ValueError("on_result= needs finish=")
+        speeds = self._speeds(speed, len(prompts))
         out: List[torch.Tensor] = [torch.tensor([]) for _ in prompts]
         for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group,
                                                     **({} if sessions is None else {"sessions": sessions})):
             if frames.shape[0]:                                       # decoded as each utterance finishes, not at the end
                 out[i] = self._decode_frames(frames.unsqueeze(1))
+                if speeds[i] is not None:
+                    out[i] = self._stretch_clip(out[i], speeds[i])
         return out
+
+    @staticmethod
+    def _speeds(speed, n: int) -> List[Optional[float]]:
+        """``speed=`` as one checked factor or None per request (None for all without importing anything: today's calls exactly)."""
+        if speed is None:
+            return [None] * n
+        from .stretch import per_request
+        return per_request(speed, n)
+
+    @staticmethod
+    def _stretch_clip(audio: torch.Tensor, speed: float) -> torch.Tensor:
+        """One decoded clip through a one-shot device time stretch (sesameai/stretch.py)."""
+        from .stretch import stretch
+        return stretch([audio], speed)[0] if audio.numel() else audio
 
     def generate_segments(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                           temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], finish,
                           seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
                           post: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
-                          on_result: Optional[Callable[[int, torch.Tensor], None]] = None, slots: Optional[int] = None) -> List[torch.Tensor]:
+                          on_result: Optional[Callable[[int, torch.Tensor], None]] = None, slots: Optional[int] = None,
+                          speed=None) -> List[torch.Tensor]:
         """Prompts [(tokens (S_i,33), mask (S_i,33)), ...] through the continuously refilled batch, each result a FINISHED segment: int16 on
         the device, peak-normalised, with lead and tail silence and fades (``finish``: a ``SegmentFinish`` for all prompts, or one per
         prompt; sesameai/finish.py) -- what ``tts_service.TTS.generate_audio_segment`` makes of a sentence, bit for bit, without the float32
@@ -507,9 +528,13 @@ class Generator:
         ``post(audio) -> audio`` runs on each non-empty decoded clip before it is finished (the watermark hook); ``on_result(i, pcm)``
         fires as each request completes; an utterance with no frames still yields its lead and tail silence.  ``max_generation_len``,
         ``temperature``, ``topk``, ``seed``, ``refill_group``: as for ``iter_codes_continuous``; ``slots``: use no more than this
-        many of the batch's slots (None: all of them).  Returns the segments in the order of ``prompts``."""
+        many of the batch's slots (None: all of them).  Returns the segments in the order of ``prompts``.
+        ``speed`` (None: the calls described above, exactly): a speech-rate factor in 0.5 .. 2.0, or one (or None) per prompt: the decoded
+        clips that end in a block go through ONE ``stretch`` call (sesameai/stretch.py), then ``post``, then the ONE finish call -- the
+        stretch acts on the decoded fp32 clip, so lead and tail silence keep their lengths."""
         from .finish import SegmentFinisher, per_clip
         how = per_clip(finish, len(prompts))
+        speeds = self._speeds(speed, len(prompts))
         if self._finisher is None:
             self._finisher = SegmentFinisher(self.device)
         side = self._side_stream()
@@ -528,9 +553,13 @@ class Generator:
                 return
             with torch.inference_mode(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
                 clips = []
-                for _i, frames in done:
+                for i, frames in done:
                     audio = self._decode_frames(frames.unsqueeze(1)) if frames.shape[0] else no_audio
-                    clips.append(post(audio) if post is not None and audio.numel() else audio)
+                    clips.append(post(audio) if post is not None and audio.numel() and speeds[i] is None else audio)
+                if quick := [j for j, (i, _) in enumerate(done) if speeds[i] is not None and clips[j].numel()]:
+                    from .stretch import stretch                    # ONE stretch call for the block's clips, then post, then the finish
+                    for j, y in zip(quick, stretch([clips[j] for j in quick], [speeds[done[j][0]] for j in quick])):
+                        clips[j] = post(y) if post is not None else y
                 pcm = self._finisher.finish(clips, [how[i] for i, _ in done], self.sample_rate)
             if side is not None:
                 side.synchronize()
@@ -555,7 +584,7 @@ class Generator:
                              temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None,
                              sessions: Optional[Sequence[Optional[Conversation]]] = None,
-                             out_sample_rate: Optional[int] = None, out_dtype: Optional[torch.dtype] = None
+                             out_sample_rate: Optional[int] = None, out_dtype: Optional[torch.dtype] = None, speed=None
                              ) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
@@ -583,7 +612,13 @@ class Generator:
         (sesameai/resample.py), reset when a new request takes the slot, and each pool call's PCM goes through ONE resampler call on the
         side stream.  A request's chunks, concatenated, are bit for bit ``resample`` of its concatenated 24 kHz chunks; the filter's tail
         comes with the request's last chunk -- also with the closing chunk that is empty at 24 kHz -- so a chunk's length is no longer
-        1920 samples a frame.  ``out_dtype`` other than fp32 needs a foreign ``out_sample_rate`` (the conversion is the resampler's)."""
+        1920 samples a frame.  ``out_dtype`` other than fp32 needs a foreign ``out_sample_rate`` (the conversion is the resampler's).
+        ``speed`` (None: the calls described above exactly): a speech-rate factor in 0.5 .. 2.0, or one (or None) per request.  Each slot is
+        then also one stream of a ``TimeStretchPool`` (sesameai/stretch.py), reset with the request's speed when the request takes the slot,
+        and each pool call's PCM goes through ONE stretch call on the side stream, BEFORE the resampler.  A request's chunks, concatenated,
+        are bit for bit ``stretch`` of its concatenated ``speed=None`` chunks (with ``out_sample_rate``: ``resample`` of that); the stretch
+        holds back up to 1,280 samples, which come with the request's last chunk -- also with a closing chunk that is empty at 24 kHz.  A
+        request whose speed is None or 1.0 never touches the stretcher: its chunks are those of a run without ``speed``."""
         size = self._stream_buffer_size
         if first_chunk_frames is not None and not 1 <= int(first_chunk_frames) < size:
             raise ValueError(f"first_chunk_frames must be None or 1 .. {size - 1}")
@@ -610,6 +645,12 @@ class Generator:
             kw["resampler"] = self._stream_pools[key]
         elif out_dtype is not None and out_dtype != torch.float32:
             raise ValueError("out_dtype without out_sample_rate: convert the 24 kHz chunks yourself")
+        speeds = self._speeds(speed, len(prompts))
+        if any(v is not None for v in speeds):
+            from .stretch import TimeStretchPool
+            if ("stretcher", B) not in self._stream_pools:
+                self._stream_pools[("stretcher", B)] = TimeStretchPool(B, device=self.device)
+            kw["stretcher"], kw["speeds"] = self._stream_pools[("stretcher", B)], speeds
         streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device, **kw)
         backlog: List[list] = []                                    # polled blocks whose audio is still to be decoded
         for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed, refill_group=refill_group,
@@ -646,7 +687,8 @@ class Generator:
                         session: Optional[Conversation] = None) -> PyGenerator[torch.Tensor, None, None]:
         """reference: generator.py:119-210 -- yields audio every ``_stream_buffer_size`` frames as soon as it exists,
         each buffer decoded statelessly like the reference.  Mimi runs on its own HIP stream while the frame steps
-        of the next buffer (already enqueued) run on the caller's stream.
+        of the next buffer (already enqueued) run on the caller's stream.  There is no ``speed=`` here: the chunks are the reference's
+        stateless ones, and a stretch needs a stream's state (``generate_many_stream`` has it; ``generate(.., speed=)`` stretches the clip).
         ``session``: ``context`` lists only the segments that are NEW since the session's last turn (``open_session``)."""
         max_generation_len = int(max_audio_length_ms / FRAME_MS)
         with torch.inference_mode():
@@ -693,18 +735,23 @@ class Generator:
 
     @torch.inference_mode()
     def generate(self, text, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
-                 temperature: float = 0.7, topk: int = 30, stream: bool = False, session: Optional[Conversation] = None) -> torch.Tensor:
+                 temperature: float = 0.7, topk: int = 30, stream: bool = False, session: Optional[Conversation] = None,
+                 speed=None) -> torch.Tensor:
         """reference: generator.py:212-300.  ``session``: ``context`` lists only the segments that are NEW since the session's last turn
-        (``open_session``)."""
+        (``open_session``).  ``speed`` (None: the calls above exactly): a speech-rate factor in 0.5 .. 2.0 -- the decoded clip goes through a
+        one-shot device time stretch (sesameai/stretch.py); the pitch stays."""
+        (how_fast,) = self._speeds(speed, 1)
         if stream:
             chunks = list(self.generate_stream(text, speaker, context, max_audio_length_ms, temperature, topk, session=session))
-            return torch.cat(chunks) if chunks else torch.tensor([])
+            audio = torch.cat(chunks) if chunks else torch.tensor([])
+            return audio if how_fast is None else self._stretch_clip(audio, how_fast)
         max_generation_len = int(max_audio_length_ms / FRAME_MS)
         tokens, mask = self._build_prompt(text, speaker, context)
         frames = self.generate_codes(tokens, mask, max_generation_len, temperature, topk, session=session)
         if frames.shape[0] == 0:
             return torch.tensor([])
-        return self._decode_frames(frames)
+        audio = self._decode_frames(frames)
+        return audio if how_fast is None else self._stretch_clip(audio, how_fast)
 
 
 def _wav_float32_header(sample_rate: int, data_bytes: int) -> bytes:

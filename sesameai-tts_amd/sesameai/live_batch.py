@@ -4,7 +4,7 @@ turns its polled blocks into streamed audio (``SlotStreams``).  Host code only; 
 import contextlib
 from collections import deque
 from dataclasses import dataclass
-from typing import Iterator, List, Optional, Tuple
+from typing import Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -336,10 +336,18 @@ class SlotStreams:
     that is ready after a block -- full chunks, first chunks, the endings' remainders -- goes into ONE ragged pool call (``_ragged_calls``).
     ``resampler`` (None: 24 kHz fp32, today's calls exactly): a pool of at least ``slots`` resampler streams (``ResamplerPool``), slot = stream;
     every pool call's PCM goes through ONE ``resampler.feed`` on ``side``, ``final`` for the slots whose request it closes -- a request's last
-    chunk carries the filter's tail, also when it is empty at 24 kHz."""
+    chunk carries the filter's tail, also when it is empty at 24 kHz.
+    ``stretcher`` with ``speeds`` (None: no speed change, today's calls exactly): a pool of at least ``slots`` time-stretch streams
+    (``TimeStretchPool``), slot = stream, and one speed factor or None per REQUEST; a slot is reset with its request's speed when the request
+    takes it, and every pool call's PCM of the requests that have a speed goes through ONE ``stretcher.feed`` on ``side`` BEFORE the resampler,
+    ``final`` for the slots whose request it closes -- the stretch's tail comes with the request's last chunk, also when that chunk is empty at
+    24 kHz.  A request whose speed is None (or 1.0) never touches the stretcher."""
 
-    def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None, resampler=None):
+    def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None, resampler=None, stretcher=None,
+                 speeds: Optional[Sequence[Optional[float]]] = None):
         self.pool, self.size, self.side, self.first, self.resampler = pool, size, side, first, resampler
+        self.stretcher, self.speeds = stretcher, speeds
+        self.speed: List[Optional[float]] = [None] * slots          # (stretcher) the speed of the request that holds the slot
         self.started: List[bool] = [False] * slots                  # whether the slot's request has had a chunk (``first`` only)
         self.owner: List[Optional[int]] = [None] * slots
         self.held: List[List[torch.Tensor]] = [[] for _ in range(slots)]
@@ -375,6 +383,11 @@ class SlotStreams:
                 pool.reset(fresh)
                 if self.resampler is not None:
                     self.resampler.reset(fresh)
+                if self.stretcher is not None:
+                    for s_ in fresh:
+                        self.speed[s_] = self.speeds[owner[s_]]
+                    if quick := [s_ for s_ in fresh if self.speed[s_] is not None]:
+                        self.stretcher.reset(quick, [self.speed[s_] for s_ in quick])
             if self.first is not None:
                 self._ragged_calls(ending, calls)
             while self.first is None and (full := [s_ for s_, h in enumerate(held) if len(h) >= self.size]):
@@ -382,12 +395,23 @@ class SlotStreams:
             for T in sorted({len(held[s_]) for s_ in ending} - {0}):
                 decode([s_ for s_ in ending if len(held[s_]) == T], T)
             final = {s_: k for k, (slots, _, _) in enumerate(calls) for s_ in slots}   # the call that holds a slot's newest chunk
+            if self.stretcher is not None:                          # ONE stretch call per pool call, and one for the empty closing chunks
+                for k, (slots, frames, pcm) in enumerate(calls):
+                    if quick := [j for j, s_ in enumerate(slots) if self.speed[s_] is not None]:
+                        ys = self.stretcher.feed([slots[j] for j in quick], [pcm[j][0] for j in quick],
+                                                 [slots[j] in ending and final[slots[j]] == k for j in quick])
+                        pcm = [pcm[j] for j in range(len(slots))]
+                        for j, y in zip(quick, ys):
+                            pcm[j] = y.unsqueeze(0)
+                        calls[k] = (slots, frames, pcm)
+                if bare := [s_ for s_ in ending if s_ not in final and self.speed[s_] is not None]:
+                    tails = dict(zip(bare, self.stretcher.feed(bare, [self.no_pcm.float()] * len(bare), True)))
             if self.resampler is not None:                          # ONE resampler call per pool call, and one for the empty closing chunks
                 for k, (slots, frames, pcm) in enumerate(calls):
                     rs = self.resampler.feed(slots, [pcm[j][0] for j in range(len(slots))], [s_ in ending and final[s_] == k for s_ in slots])
                     calls[k] = (slots, frames, [y.unsqueeze(0) for y in rs])
                 if bare := [s_ for s_ in ending if s_ not in final]:
-                    tails = dict(zip(bare, self.resampler.feed(bare, [self.no_pcm.float()] * len(bare), True)))
+                    tails = dict(zip(bare, self.resampler.feed(bare, [tails.get(s_, self.no_pcm.float()) for s_ in bare], True)))
         if self.side is not None:
             self.side.synchronize()
         for k, (slots, frames, pcm) in enumerate(calls):

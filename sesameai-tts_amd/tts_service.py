@@ -141,8 +141,9 @@ class TTS:
 
     @torch.inference_mode()
     def generate_with_context(self, prompt, speaker: int = 1, max_audio_length_ms: float = 60_000,
-                              temperature: float = 0.9, topk: int = 50) -> torch.Tensor:
-        """reference: tts_service.py:170-258, watermark included (:249-256)."""
+                              temperature: float = 0.9, topk: int = 50, speed: Optional[float] = None) -> torch.Tensor:
+        """reference: tts_service.py:170-258, watermark included (:249-256).  ``speed`` (None: the calls above exactly): the decoded clip
+        goes through the device time stretch (sesameai/stretch.py) before the watermark."""
         g = self.generator
         gen_tokens, gen_masks = g._tokenize_text_segment(prompt, speaker)
         prompt_tokens = torch.cat(self.cached_context_tokens + [gen_tokens], dim=0).long().to(g.device)
@@ -155,15 +156,24 @@ class TTS:
         audio = g._decode_frames(frames)
         if audio.numel() == 0:
             return audio
+        if speed is not None:
+            from sesameai.stretch import per_request, stretch
+            (how_fast,) = per_request(speed, 1)
+            if how_fast is not None:
+                audio = stretch([audio], how_fast)[0]
         # every generated clip carries the public CSM watermark, then goes back to the generator's rate
         audio, wm_rate = watermark(getattr(self, "watermarker", None), audio, g.sample_rate, CSM_1B_GH_WATERMARK)
         return resample_to(audio, wm_rate, g.sample_rate)
 
     def generate_audio_segment(self, prompt, fade_duration: int = 50, start_silence_duration: int = 500,
-                               end_silence_duration: int = 100, temperature: float = 0.8, topk: int = 40) -> np.ndarray:
+                               end_silence_duration: int = 100, temperature: float = 0.8, topk: int = 40,
+                               speed: Optional[float] = None) -> np.ndarray:
         """-> int16 mono PCM @ generator.sample_rate (the reference returns a pydub AudioSegment
-        holding the same samples, tts_service.py:260-308)."""
-        audio = self.generate_with_context(prompt, speaker=1, max_audio_length_ms=30_000, temperature=temperature, topk=topk)
+        holding the same samples, tts_service.py:260-308).  ``speed`` (None: the calls above exactly): a speech-rate factor in 0.5 .. 2.0,
+        applied to the decoded clip on the device BEFORE the finish below, so the lead and tail silences keep their lengths (the
+        reference's web chat speeds up the finished segment: utils/tts_base.py)."""
+        audio = self.generate_with_context(prompt, speaker=1, max_audio_length_ms=30_000, temperature=temperature, topk=topk,
+                                           **({} if speed is None else {"speed": speed}))
         audio = audio.to(torch.float32).reshape(-1)
         audio = audio / max(float(audio.abs().max()) if audio.numel() else 0.0, 1e-6)
         pcm = (audio.cpu().numpy() * 32767).astype("int16")
@@ -182,7 +192,8 @@ class TTS:
         return self.generate_audio_segment(sentence, fade_duration, start_silence_duration, end_silence_duration, temperature, topk)
 
     def _segments_batched(self, sentences: List[str], batch: int, seed: Optional[int], fallback_duration: int, fade_duration: int,
-                          start_silence_duration: int, end_silence_duration: int, temperature: float, topk: int, on_segment=None) -> List[np.ndarray]:
+                          start_silence_duration: int, end_silence_duration: int, temperature: float, topk: int, on_segment=None,
+                          speed: Optional[float] = None) -> List[np.ndarray]:
         """The sentences of one text as independent requests of the continuously refilled batch (``batch`` of its slots), each against the
         cached voice context: the context rows are registered once per loaded voice with the prefix store, every sentence is one prompt
         (context + sentence) with the 30 s limit of ``generate_audio_segment``, sentence i gets seed ``seed + i``, and every segment is
@@ -240,6 +251,8 @@ class TTS:
             wm = getattr(self, "watermarker", None)
             if wm is not None:                               # every generated clip carries the public CSM watermark (generate_with_context)
                 kw["post"] = lambda audio: resample_to(*watermark(wm, audio, sr, CSM_1B_GH_WATERMARK), sr)
+            if speed is not None:                            # each block's clips: ONE stretch call, then the watermark, then the finish
+                kw["speed"] = speed
             g.generate_segments(prompts, max_audio_frames, temperature, topk,
                                 SegmentFinish(lead_ms=start_silence_duration, tail_ms=end_silence_duration, fade_ms=fade_duration),
                                 seed=None if seed is None else [int(seed) + i for i in owner], on_result=on_result, slots=batch, **kw)
@@ -250,7 +263,8 @@ class TTS:
 
     def say(self, text: str, output_filename: Optional[str] = "combined_output.wav", fallback_duration: int = 1000,
             fade_duration: int = 50, start_silence_duration: int = 500, end_silence_duration: int = 100,
-            temperature: float = 0.8, topk: int = 40, on_segment=None, batch: Optional[int] = None, seed: Optional[int] = None) -> None:
+            temperature: float = 0.8, topk: int = 40, on_segment=None, batch: Optional[int] = None, seed: Optional[int] = None,
+            speed: Optional[float] = None) -> None:
         """reference: tts_service.py:313-470 -- the generation half: the text is split into sentences, each sentence is
         generated against the cached voice context (the shared prompt prefix is prefilled once: Model.prefill_prompt) and
         reported with the reference's line ``> sentence ... [Audio: 1.84s in 0.09s, RTF: 20.44x]``; a sentence that fails is
@@ -260,8 +274,11 @@ class TTS:
         ``batch`` = k, 2 <= k <= the generator's ``max_batch_size`` (None, the default: the calls described above, exactly): the sentences
         run as concurrent requests in k slots of the continuously refilled batch and are finished on the device
         (``_segments_batched``); ``on_segment`` and the lines still come in sentence order.  ``seed`` (with ``batch``): sentence i is
-        sampled with seed ``seed + i``, whatever slot it takes."""
+        sampled with seed ``seed + i``, whatever slot it takes.
+        ``speed`` (None: the calls described above, exactly): a speech-rate factor in 0.5 .. 2.0 for every sentence, on either path
+        (``generate_audio_segment``)."""
         import textwrap
+        more = {} if speed is None else {"speed": speed}
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", textwrap.dedent(text).strip()) if s.strip()]
         if not sentences:
             print("No valid text to process")
@@ -270,7 +287,7 @@ class TTS:
         segments: List[np.ndarray] = []
         if batch is not None:
             segments = self._segments_batched(sentences, batch, seed, fallback_duration, fade_duration, start_silence_duration,
-                                              end_silence_duration, temperature, topk, on_segment)
+                                              end_silence_duration, temperature, topk, on_segment, **more)
             sentences = []
         elif seed is not None:
             raise ValueError("seed= needs batch=")
@@ -279,7 +296,7 @@ class TTS:
             t0 = time.time()
             try:
                 seg = self.generate_audio_segment(sentence, fade_duration=fade_duration, start_silence_duration=start_silence_duration,
-                                                  end_silence_duration=end_silence_duration, temperature=temperature, topk=topk)
+                                                  end_silence_duration=end_silence_duration, temperature=temperature, topk=topk, **more)
                 took, secs = time.time() - t0, len(seg) / sr
                 print(f"[Audio: {secs:.2f}s in {took:.2f}s, RTF: {secs / max(took, 1e-9):.2f}x]")
             except KeyboardInterrupt:
@@ -303,17 +320,19 @@ class TTS:
         print(f"Export complete: {len(combined) / sr:.2f} seconds of audio")
 
     def export_wav(self, text: str, output_filename: str, fallback_duration: int = 1000, max_retries: int = 2,
-                   temperature: float = 0.8, topk: int = 40, batch: Optional[int] = None, seed: Optional[int] = None) -> None:
+                   temperature: float = 0.8, topk: int = 40, batch: Optional[int] = None, seed: Optional[int] = None,
+                   speed: Optional[float] = None) -> None:
         """reference: tts_service.py:472-525.  ``batch`` / ``seed``: as for ``say`` (None: the calls of the reference's loop, exactly).
         ``max_retries`` applies only to the unbatched path: with ``batch`` a sentence whose prompt cannot be built gets the fallback
-        silence at once, and an error of the batch run itself propagates."""
+        silence at once, and an error of the batch run itself propagates.  ``speed``: as for ``say``."""
+        more = {} if speed is None else {"speed": speed}
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", text) if s.strip()]
         sr = self.generator.sample_rate
         segments = []
         t0 = time.time()
         if batch is not None:
             if sentences:
-                segments = self._segments_batched(sentences, batch, seed, fallback_duration, 50, 500, 100, temperature, topk)
+                segments = self._segments_batched(sentences, batch, seed, fallback_duration, 50, 500, 100, temperature, topk, **more)
             sentences = []
         elif seed is not None:
             raise ValueError("seed= needs batch=")
@@ -322,7 +341,7 @@ class TTS:
             while retries <= max_retries:
                 try:
                     print(f"Export: Generating audio for sentence: {sentence} (Attempt {retries + 1})")
-                    seg = self.generate_audio_segment(sentence, temperature=temperature, topk=topk)
+                    seg = self.generate_audio_segment(sentence, temperature=temperature, topk=topk, **more)
                     break
                 except Exception as e:  # noqa: BLE001 -- same retry policy as the reference
                     retries += 1
@@ -342,7 +361,7 @@ class TTS:
         print(f"Export complete: {secs:.2f} seconds of audio, RTF {secs / max(time.time() - t0, 1e-9):.2f}x")
 
 
-def main():
+def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="SesameAI CSM-1B Text-to-Speech (MI355X build)")
     parser.add_argument("-d", "--device", type=str, default="cuda", help="Device to run on (cuda)")
     parser.add_argument("-v", "--voice", type=str, default=None, help="Voice to use (a <voice>.pt prompt file in the voice dir)")
@@ -353,15 +372,26 @@ def main():
     parser.add_argument("--batch", type=int, default=None, metavar="N",
                         help="run the sentences of a text as N concurrent requests of the live batch (default: one sentence after the other)")
     parser.add_argument("--seed", type=int, default=None, metavar="S", help="with --batch: sentence i is sampled with seed S + i")
-    args = parser.parse_args()
+    parser.add_argument("--speed", type=float, default=None, metavar="X",
+                        help="speech rate, 0.5 .. 2.0 (the pitch stays; default: as generated)")
+    args = parser.parse_args(argv)
     if args.device == "cpu":
         parser.error("this build runs the hot path on MI355X only; there is no -d cpu path (use the reference)")
     if args.batch is not None and args.batch < 2:
         parser.error("--batch needs N >= 2")
     if args.seed is not None and args.batch is None:
         parser.error("--seed needs --batch")
+    if args.speed is not None and not 0.5 <= args.speed <= 2.0:
+        parser.error("--speed needs 0.5 <= X <= 2.0")
+    return args
+
+
+def main():
+    args = parse_args()
     tts = TTS(device=args.device) if args.batch is None else TTS(device=args.device, max_batch_size=args.batch)
     more = {} if args.batch is None else {"batch": args.batch, "seed": args.seed}
+    if args.speed is not None:
+        more["speed"] = args.speed
     tts.load_model()
     if args.voice:
         tts.load_voice(args.voice)
