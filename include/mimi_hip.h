@@ -322,6 +322,66 @@ long mimi_ts_pool_out_count(mimi_ts_pool p, int sid, long n_in, int final);
 int  mimi_ts_pool_feed(mimi_ts_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
                        const float* in, float* out, long* n_out, int32_t* d_out, void* stream);
 
+/* ---- A pool of stateful VOICE-ACTIVITY streams (when a speaker starts and when they have stopped: reply on pause, barge-in) ----
+ * Every decision is exact integer arithmetic, so the device computes THE RULE below bit for bit (tests/vad_ref.py states it in NumPy).
+ * 24 kHz.  Constants in samples: F = 240 (frame, 10 ms), W = 480 (analysis window), lags TMIN = 60 .. TMAX = 400 (400 Hz .. 60 Hz).
+ *   - samples: fp32 input s[i] = clamp(rint(x[i] * 32768.0f), -32768, 32767), rint to nearest even, a non-finite x[i] gives 0; int16 input
+ *     s[i] = x[i]; s[i] = 0 for i < 0.  A clip of N samples has K = N / F frames; a trailing partial frame is never judged.
+ * Frame k covers samples [k F, (k + 1) F).  Steps 1 to 5 depend on no other frame's result:
+ *   1. power, DC-free: P_k = F * sum(s^2) - (sum s)^2 over the frame; 0 <= P_k < 2^46.
+ *   2. search samples: m = max |s[i]| over the 880 samples [(k + 1) F - W - TMAX, (k + 1) F), sh = max(0, bitlen(m) - 10), q[i] = s[i] >> sh
+ *      (arithmetic): |q| <= 1024, so a 480-term dot product fits a signed 32-bit accumulator in any order.
+ *   3. for tau in TMIN .. TMAX, over i in [(k + 1) F - W, (k + 1) F): R(tau) = sum q[i] q[i - tau], E(tau) = sum q[i - tau]^2, E0 = sum q[i]^2.
+ *   4. lag_k = the SMALLEST tau with R(tau) > 0 and 2 R(tau)^2 > E0 E(tau) (a normalised correlation above 0.707; both sides below 2^59),
+ *      0 if none.  It is the FIRST lag that crosses the threshold: not the best lag, not a pitch estimate (a 220 Hz voice gives 103 .. 107
+ *      where the best lag is 109).
+ *   5. voiced_k = lag_k != 0 (silence is unvoiced: the inequality is strict).
+ * The scan, per stream with parameters {on_q4, off_q4, min_on, hang, hold, n_min}, all in 64-bit integers:
+ *   6. frame 0 first sets N = max(P_0, n_min) and has loud_0 = false; for k >= 1 loud_k = (16 P_k > N r), N the floor BEFORE this frame's
+ *      update, r = off_q4 while in speech and on_q4 otherwise.
+ *   7. since_voiced = 0 if voiced, else since_voiced + 1 (saturating at 2^20; a fresh stream starts saturated);
+ *      active_k = loud_k and since_voiced <= hold.
+ *   8. in silence: run = active ? run + 1 : 0; at run == min_on the state becomes speech, START is stamped at frame k - min_on + 1,
+ *      run = quiet = 0.  In speech: quiet = active ? 0 : quiet + 1; at quiet == hang the state becomes silence, END is stamped at frame
+ *      k - hang + 1, quiet = 0.
+ *   9. after the test: if P_k < N then N -= (N - P_k) >> 2, else N += (N >> 9) + 1; then N = max(N, n_min).
+ * Per frame the call writes flags (bit 0 loud, bit 1 voiced, bit 2 active, bit 3 in speech AFTER the frame), lag, power and floor (N after
+ * the update).  Per stream the pool holds a summary of MIMI_VAD_SUMMARY int64, rewritten at the end of every call: in speech, frames
+ * judged, frame of the last START (-1: none), frame of the last END (-1), the current quiet run, the numbers of STARTs and of ENDs, 0 --
+ * counted since the stream was last fresh.  mimi_vad_pool_summary enqueues the copy of all n_streams rows to `out` (device memory, or
+ * pinned host memory that the device can write); a stream that was reset and not fed since reads as the fresh summary.
+ * STREAMING: a stream's per-frame outputs, concatenated over ANY chunk schedule, are bit for bit the one-shot result; they do not depend
+ * on which streams share the call, on list order or on the stream id.  Per stream the device keeps the samples from k F - 640 on (k the
+ * next unjudged frame; at most 879 int16, two banks flipped per call: a call reads one and writes the other) and {N, state, run, quiet,
+ * since_voiced}; the host keeps the parameters, the counts {R, k} and the bank.  final[i] != 0 ends the stream's clip: a partial frame is
+ * discarded and the stream is left fresh with the same parameters (its summary still describes the clip that ended, until the next call).
+ * A fresh stream reads neither carry nor state, so mimi_vad_pool_reset (which also sets each listed stream's parameters) is host
+ * arithmetic, no launch.  Streams of a new pool are fresh with the defaults {128, 48, 8, 70, 30, 3686400}.
+ * mimi_vad_pool_feed: stream streams[i] gets n_in[i] >= 0 samples at in + in_off[i] ELEMENTS (in_is_i16: 0 = fp32, 1 = int16).  in, flags,
+ * lag, power, floor: device memory; streams, in_off, n_in, final: host arrays read before the call returns; n_frames: a host array
+ * WRITTEN before the call returns.  Per-frame outputs are packed back to back by frames: stream i owns entries [O_i, O_i + n_frames[i]),
+ * O_i = n_frames[0] + .. + n_frames[i-1]; mimi_vad_pool_frame_count says beforehand (host arithmetic only) what a feed of n_in samples
+ * would give stream sid now.  A feed that judges nothing for a stream is legal.  At most TWO launches per call whatever n and the lengths
+ * are: one workgroup per (stream, frame) for steps 1 to 5, which writes power and lag, then one wave per stream for steps 6 to 9 and the
+ * carry.  The plan travels in the kernel arguments: no host-to-device copy, no allocation, no synchronisation.
+ * Returns -1 with a message in mimi_vad_pool_last_error, nothing enqueued and no state moved, for: n_streams outside [1, 64] (create); n
+ * outside [1, n_streams], a duplicate or out-of-range id, a parameter outside 16 <= off_q4 <= on_q4 <= 4095, min_on 1 .. 1000, hang
+ * 1 .. 10000, hold 0 .. 10000, n_min 1 .. 2^40 (reset); a negative n_in or in_off, a null pointer, a misaligned buffer, an unknown format,
+ * a chunk of more than 2^30 samples, a stream of more than 2^48 samples since it was fresh (feed).  -2: a HIP error.  Drive ONE HIP stream
+ * per pool at a time.                                                                                                                    */
+#define MIMI_VAD_MAX_STREAMS 64
+#define MIMI_VAD_SUMMARY 8
+typedef struct MimiVadPool* mimi_vad_pool;
+typedef struct { int32_t on_q4, off_q4, min_on, hang, hold, reserved; int64_t n_min; } mimi_vad_params;
+int  mimi_vad_pool_create(int n_streams, mimi_vad_pool* out);
+void mimi_vad_pool_destroy(mimi_vad_pool p);
+const char* mimi_vad_pool_last_error(mimi_vad_pool p);         /* p == NULL: why mimi_vad_pool_create failed (this thread) */
+int  mimi_vad_pool_reset(mimi_vad_pool p, const int32_t* streams, const mimi_vad_params* params, int n);
+long mimi_vad_pool_frame_count(mimi_vad_pool p, int sid, long n_in, int final);
+int  mimi_vad_pool_feed(mimi_vad_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                        const void* in, int in_is_i16, uint8_t* flags, int16_t* lag, long* power, long* floor, long* n_frames, void* stream);
+int  mimi_vad_pool_summary(mimi_vad_pool p, long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

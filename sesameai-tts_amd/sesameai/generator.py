@@ -211,20 +211,30 @@ class Generator:
         toks.append(t); masks.append(m)
         return torch.cat(toks, 0).long().to(self.device), torch.cat(masks, 0).bool().to(self.device)
 
-    def open_turn_streams(self, n: int, chunk_frames: int = 10, sample_rate: Optional[int] = None):
+    def open_turn_streams(self, n: int, chunk_frames: int = 10, sample_rate: Optional[int] = None, vad=None, pre_roll_ms: int = 200,
+                          post_roll_ms: int = 200):
         """``n`` spoken turns encoded while they are spoken (sesameai/turns.py): ``feed`` / ``pump`` as the microphones deliver, then
         ``finish(sid, speaker, text)`` gives the ``Segment`` of the turn, its codes bit for bit those of ``Segment(audio=the turn)``.
         ``sample_rate`` (None: 24 kHz, today's calls exactly): the microphones' rate; ``feed`` then takes fp32 or int16 at that rate and a
-        pool of ``n`` resampler streams (sesameai/resample.py) follows the turns in front of the encoder."""
+        pool of ``n`` resampler streams (sesameai/resample.py) follows the turns in front of the encoder.
+        ``vad`` (None: today's calls exactly): ``True`` for a pool of ``n`` voice-activity streams (sesameai/vad.py), or such a pool; the
+        streams then listen all the time, a turn starts ``pre_roll_ms`` before the detected START and ends ``post_roll_ms`` after the
+        detected END, and ``poll_events`` says when."""
         from .turns import TurnStreams
         tok = self._audio_tokenizer
         if tok is None or not hasattr(tok, "open_encode_streams"):
             raise RuntimeError("no Mimi encoder with encode streams available: pass Segment.audio_codes")
         pool = tok.open_encode_streams(n, max_chunk_frames=chunk_frames)
+        kw = {}
+        if vad is not None and vad is not False:
+            if vad is True:
+                from .vad import VadPool
+                vad = VadPool(n, device=self.device)
+            kw = {"vad": vad, "pre_roll": int(pre_roll_ms) * self.sample_rate // 1000, "post_roll": int(post_roll_ms) * self.sample_rate // 1000}
         if sample_rate is None or int(sample_rate) == self.sample_rate:
-            return TurnStreams(pool, tok.args.hop, chunk_frames)
+            return TurnStreams(pool, tok.args.hop, chunk_frames, **kw)
         from .resample import ResamplerPool
-        return TurnStreams(pool, tok.args.hop, chunk_frames, resampler=ResamplerPool(int(sample_rate), self.sample_rate, n, device=self.device))
+        return TurnStreams(pool, tok.args.hop, chunk_frames, resampler=ResamplerPool(int(sample_rate), self.sample_rate, n, device=self.device), **kw)
 
     # -- prefix store: a voice prompt's K/V computed once, copied into any slot ----------------------
     def _store(self) -> list:
