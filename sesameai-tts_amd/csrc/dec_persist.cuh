@@ -10,7 +10,10 @@
 //   wave 7      "gather": sweeps the granules of the previous op (relaxed agent-scope loads, 8 copies so that only 32
 //               CUs poll a line), applies the RMSNorm the consumer needs, writes LDS, raises an LDS flag; it also owns
 //               rows 4cu..4cu+3 of the residual stream: sums the 256 down-projection partials of those rows in a fixed
-//               order, adds the residual and publishes them; after sampling it fetches the next step's table rows.
+//               order, adds the residual and publishes them; it samples the step's code from the logits its sweep leaves in its
+//               registers (sample_wave_front: keys, bound, candidate list and the softmax race on this wave alone, 3.9 us a step
+//               against 6.2 us for the 4-wave form behind an LDS copy of the logits and five barriers: docs/experiments/
+//               sampler_on_gather.md), then fetches the next step's table rows.
 //   waves 0..6  "compute": fixed weight rows per wave; the loads of a wave's next use are issued ONE 1 KB wave load at
 //               a time between polls of the LDS flag the wave waits on anyway (static order -> exact vmcnt(N) waits).
 //               waves 0-3: one 16-row tile of the gate/up projection (8 (gate, up) pairs on v_mfma_f32_16x16x32_bf16,
@@ -18,7 +21,8 @@
 //               waves 4-6: 3 / 3 / 2 row blocks of the split down projection
 //               waves 2-4: + one q|k|v unit (2 rows, RoPE) + one head unit
 //               waves 5,6: + one o-proj unit (2 rows, + residual) + head unit (5) / tail rows (6)
-//               all 8 waves: one attention head each over the LDS-resident K/V;  waves 4-7 ("quad"): the sampler.
+//               all 8 waves: one attention head each over the LDS-resident K/V;  waves 4-6: the Exp(1) draws of the sampler's
+//               candidates; with the gather wave ("quad") the 4-wave sample_body of the steps the one-wave form does not take.
 //               Every wave of an instantiation issues the same load sequence (dp_compute_wave); the per-layer weights are
 //               four buffers with a constant layer stride (DecPersistArgs), addressed by arithmetic.
 //
@@ -133,13 +137,14 @@ static_assert(DP_OFF_CANDI + DP_CAND_SLOTS * 4 <= DP_OFF_LOGITS, "sampler candid
 #define DP_M_FXA 20      // flags
 #define DP_M_FQ 21
 #define DP_M_FXC 22
-#define DP_M_FLG 23
 #define DP_M_FTOK 24
 #define DP_M_ATTN 25     // counters
 #define DP_M_CD 26
 #define DP_M_BAR 27
 #define DP_M_ABORT 28
 #define DP_M_TOK 29
+#define DP_M_SGO 30      // sampler: the gather wave's word to waves 4..6, 4 (step + 1) + DP_SGO_*
+#define DP_M_SARR 31     // sampler: arrivals of waves 4..6 after their Exp(1) draws (3 per step that published a list)
 #define DP_M_SBV 32      // sampler: 4 floats, 4 ints, n, tok, 4 wave totals
 #define DP_M_SBI 36
 #define DP_M_SN 40
@@ -150,6 +155,8 @@ static_assert(DP_OFF_CANDI + DP_CAND_SLOTS * 4 <= DP_OFF_LOGITS, "sampler candid
 #define DP_M_SARG 116    // 4 words: V, temperature (bits), top-k, 1 if a noise tensor was given -- the sampler's scalars, staged once
                          // (both groups resolved against the slot's entry of the per-slot sampling table, if the launch carries one: the
                          // step loop reads these LDS words only)
+#define DP_M_SDBG 120    // 1 word: 1 if the launch returns its logits (logits_out) -- staged like the scalars above: a kernel-argument read at
+                         // sampling time is a scalar-cache miss between the logit sweep and the sampler, on every CU
 #define DP_M_TILE 48     // 4 tiles x 16 floats: the gate | up sums of a tile on their way to the SwiGLU lanes
 
 enum { DP_E_Q = 0, DP_E_H1 = 1, DP_E_P = 2, DP_E_H2 = 3, DP_E_L = 4 };
@@ -360,7 +367,7 @@ __device__ __forceinline__ void dp_attention_wave(char* lds, int wave, int l, in
     if (lane == 0) __hip_atomic_fetch_add(misc + DP_M_ATTN, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// 4-wave barrier of the quad (waves 2..5) on an LDS counter: phase-numbered, bounded
+// 4-wave barrier of the quad (waves 4..7) on an LDS counter: phase-numbered, bounded
 struct DpQuadSync {
     dp_lvu32* ctr; dp_lvu32* ab; uint32_t* err; int lane; uint32_t* phase; dp_u64* stamp;
     __device__ __forceinline__ void mark(int i) const { if (stamp != nullptr && lane == 0) stamp[i] = __builtin_amdgcn_s_memrealtime(); }
@@ -377,12 +384,47 @@ struct DpQuadSync {
     }
 };
 
+__device__ __forceinline__ SampleScratch dp_sample_scratch(char* lds) {
+    dp_lu32* misc = (dp_lu32*)(lds + DP_OFF_MISC);
+    SampleScratch sc;
+    sc.cand_t = (lds_f32_t*)(lds + DP_OFF_CANDT); sc.cand_i = (lds_i32_t*)(lds + DP_OFF_CANDI); sc.s_max = (lds_u32_t*)(lds + DP_OFF_SMAX); sc.cand_q = (lds_f32_t*)(lds + DP_OFF_SMAX);
+    sc.s_bv = (lds_f32_t*)(misc + DP_M_SBV); sc.s_bi = (lds_i32_t*)(misc + DP_M_SBI); sc.s_n = (lds_i32_t*)(misc + DP_M_SN);
+    sc.s_tok = (lds_i32_t*)(misc + DP_M_STOK); sc.s_wtot = (lds_i32_t*)(misc + DP_M_SWTOT);
+    return sc;
+}
+
+// The sampler's hand-off inside a CU.  The gather wave comes out of the logit sweep with every logit of the step in its registers and runs
+// sample_wave_front on them alone: no LDS copy of the logits, no barrier in front of the candidate list.  Waves 4..6 wait on ONE LDS word,
+// DP_M_SGO = 4 (step + 1) + state (monotonic over the launch; zeroed with the misc words at kernel start):
+//   DP_SGO_LIST  the candidate list and its length are in LDS: draw the candidates' Exp(1) variates into cand_q, arrive on DP_M_SARR,
+//                then wait for one of the next two;
+//   DP_SGO_FAST  the one-wave form goes through: nothing more to do in this step;
+//   DP_SGO_QUAD  the step takes the 4-wave form (top-k 1 or beyond 128, more than 128 candidates, more than 64 survivors): the logits are
+//                in LDS, run dp_sample_step.  After DP_SGO_LIST it is raised only once all three waves have arrived.
+// The decision is a function of the logits and the sampling parameters alone, so every CU takes the same branch in the same step.
+enum { DP_SGO_LIST = 1, DP_SGO_FAST = 2, DP_SGO_QUAD = 3 };
+struct DpFrontHand {
+    dp_lvu32* go; dp_lvu32* arr; dp_lvu32* ab; uint32_t* err; int lane; uint32_t w0; uint32_t* arr_want; dp_u64* stamp;
+    __device__ __forceinline__ void mark(int i) const { if (stamp != nullptr && lane == 0) stamp[i] = __builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ void publish_list() const { *arr_want += 3u; dp_flag(go, w0 + DP_SGO_LIST); }
+    __device__ __forceinline__ void publish_fast() const { dp_flag(go, w0 + DP_SGO_FAST); }
+    __device__ __forceinline__ bool wait_draws() const {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const uint32_t want = *arr_want;
+        const dp_u64 t0 = __builtin_amdgcn_s_memrealtime();
+        for (uint32_t spins = 1; (int32_t)(*arr - want) < 0; ++spins)
+            if ((spins & 255u) == 0 && dp_give_up(t0, ab, err, 0xB10u, lane)) return false;
+        asm volatile("" ::: "memory");
+        return true;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------------------
-// compute wave.  Roles: X = waves 0,1;  A = waves 2,3,4 (q|k|v unit; 2,3,4 are in the quad);  B = waves 5,6 (o-proj
-// unit; 5 is in the quad).
+// compute wave.  Roles: X = waves 0,1;  A = waves 2,3,4 (q|k|v unit);  B = waves 5,6 (o-proj unit).  Waves 4, 5, 6 are
+// the sampler's helpers and, with the gather wave, the quad.
 // ---------------------------------------------------------------------------------------------------------------
-// one sampling step by the 4 waves of the quad (qw = 0..3): sample_body on the logits in LDS; returns the code
-template <bool DEBUG_OUT>
+// one sampling step by the 4 waves of the quad (qw = 0..3): sample_body on the logits in LDS; returns the code.  (The form for the
+// steps sample_wave_front does not take: see DP_SGO_QUAD.)
 __device__ __forceinline__ int dp_sample_step(const DecPersistArgs& a, char* lds, int qw, int lane, int cu, int cb, int s, uint32_t* quad_phase) {
     dp_lu32* misc = (dp_lu32*)(lds + DP_OFF_MISC);
     dp_lvu32* ab = (dp_lvu32*)(misc + DP_M_ABORT);
@@ -396,13 +438,7 @@ __device__ __forceinline__ int dp_sample_step(const DecPersistArgs& a, char* lds
         const uint4 v1 = tid < 64 ? dp_ldq(lg + 256 + tid) : make_uint4(0, 0, 0, 0);
         w[1][0] = v1.x; w[1][1] = v1.y; w[1][2] = v1.z; w[1][3] = v1.w;
     }
-    if (DEBUG_OUT && a.logits_out != nullptr && cu == 0) {       // (gather wave only: its stores would put a vmcnt(0) in a compute wave's path)
-        for (int i = lane; i < a.V; i += 64) a.logits_out[(long)cb * a.V + i] = ((const dp_lu16*)lg)[i];
-    }
-    SampleScratch sc;
-    sc.cand_t = (lds_f32_t*)(lds + DP_OFF_CANDT); sc.cand_i = (lds_i32_t*)(lds + DP_OFF_CANDI); sc.s_max = (lds_u32_t*)(lds + DP_OFF_SMAX); sc.cand_q = (lds_f32_t*)(lds + DP_OFF_SMAX);
-    sc.s_bv = (lds_f32_t*)(misc + DP_M_SBV); sc.s_bi = (lds_i32_t*)(misc + DP_M_SBI); sc.s_n = (lds_i32_t*)(misc + DP_M_SN);
-    sc.s_tok = (lds_i32_t*)(misc + DP_M_STOK); sc.s_wtot = (lds_i32_t*)(misc + DP_M_SWTOT);
+    const SampleScratch sc = dp_sample_scratch(lds);
     DpQuadSync sync{(dp_lvu32*)(misc + DP_M_BAR), ab, a.err, lane, quad_phase, DP_STAMPS(a) != nullptr && cu == 100 && qw == 0 ? DP_STAMPS(a) + 4352 + s * 16 : nullptr};
     const uint64_t seed = (uint64_t)misc[DP_M_RNG] | ((uint64_t)misc[DP_M_RNG + 1] << 32), step = (uint64_t)misc[DP_M_RNG + 2] | ((uint64_t)misc[DP_M_RNG + 3] << 32);
     // (the sampler's scalars from LDS: as kernel arguments they are re-read from the kernarg segment here, a scalar-cache miss per step)
@@ -634,9 +670,28 @@ __device__ __forceinline__ void dp_compute_wave(const DecPersistArgs& a, char* l
         }
         // ---- the sampler (waves 4, 5, 6 and the gather wave), on every CU alike: each CU needs the code for its table rows
         if (!HAS_TILE) {
-            if (!dp_wait<1, false>((dp_lvu32*)(misc + DP_M_FLG), dp_tag(base, s, DP_NL - 1, DP_E_L), ab, a.err, 0x970u, lane, ts, [&](int) {})) return;
-            (void)dp_sample_step<false>(a, lds, wave - 4, (int)lane, cu, cb, s, &quad_phase);
-            if (*ab) return;
+            dp_lvu32* go = (dp_lvu32*)(misc + DP_M_SGO);
+            const uint32_t w0 = 4u * (uint32_t)(s + 1);
+            if (!dp_wait<1, true>(go, w0 + DP_SGO_LIST, ab, a.err, 0x970u, lane, ts, [&](int) {})) return;
+            const bool st4 = DP_STAMPS(a) != nullptr && cu == 100 && lane == 0 && wave == 4;
+            if (st4) DP_STAMPS(a)[s * 32 + 28] = __builtin_amdgcn_s_memrealtime();      // (22, 23: the 4-wave form's entry and exit)
+            uint32_t state = *go - w0;
+            if (state != DP_SGO_QUAD) {
+                // the Exp(1) draws of the listed candidates (a pure function of the index; Philox is ~150 instructions each, off the
+                // gather wave's path), then the verdict
+                const bool sN = misc[DP_M_SARG + 3] != 0u;
+                const uint64_t seed = (uint64_t)misc[DP_M_RNG] | ((uint64_t)misc[DP_M_RNG + 1] << 32), step = (uint64_t)misc[DP_M_RNG + 2] | ((uint64_t)misc[DP_M_RNG + 3] << 32);
+                sample_wave_draws(dp_sample_scratch(lds), wave - 4, 3, (int)lane, sN ? a.noise + (long)cb * (int)misc[DP_M_SARG] : nullptr, seed, step, 0, cb);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (lane == 0) __hip_atomic_fetch_add(misc + DP_M_SARR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (st4) DP_STAMPS(a)[s * 32 + 29] = __builtin_amdgcn_s_memrealtime();
+                if (!dp_wait<1, true>(go, w0 + DP_SGO_FAST, ab, a.err, 0x980u, lane, ts, [&](int) {})) return;
+                state = *go - w0;
+            }
+            if (state == DP_SGO_QUAD) {
+                (void)dp_sample_step(a, lds, wave - 4, (int)lane, cu, cb, s, &quad_phase);
+                if (*ab) return;
+            }
         }
     }
 }
@@ -680,7 +735,7 @@ static __global__ __launch_bounds__(512) void k_dec_persist(const DecPersistArgs
         const uint32_t* se = a.slot_tab != nullptr ? reinterpret_cast<const uint32_t*>(a.slot_tab + a.slot_row0) : nullptr;
         const bool has = se != nullptr && se[1] != 0u, own = has && se[2] != 0u;
         if (threadIdx.x >= 64 && threadIdx.x < 68) misc[DP_M_RNG + threadIdx.x - 64] = own ? se[4 + threadIdx.x - 64] : (a.rng ? reinterpret_cast<const uint32_t*>(a.rng)[threadIdx.x - 64] : 0u);
-        if (threadIdx.x == 128) { misc[DP_M_SARG] = (uint32_t)a.V; misc[DP_M_SARG + 1] = has ? se[0] : __float_as_uint(a.temperature); misc[DP_M_SARG + 2] = has ? se[1] : (uint32_t)a.topk; misc[DP_M_SARG + 3] = a.noise != nullptr; }
+        if (threadIdx.x == 128) { misc[DP_M_SARG] = (uint32_t)a.V; misc[DP_M_SARG + 1] = has ? se[0] : __float_as_uint(a.temperature); misc[DP_M_SARG + 2] = has ? se[1] : (uint32_t)a.topk; misc[DP_M_SARG + 3] = a.noise != nullptr; misc[DP_M_SDBG] = a.logits_out != nullptr; }
     }
     __syncthreads();
     const uint32_t base = dp_sload32(a.epoch);
@@ -691,7 +746,7 @@ static __global__ __launch_bounds__(512) void k_dec_persist(const DecPersistArgs
         const dp_u64 *rgQ = a.gQ + rep * 768, *rgH1 = a.gH1 + rep * 512, *rgH2 = a.gH2 + rep * 512, *rgL = a.gL + rep * DP_LSLOTS;
         const dp_u64* rgP = a.gP + (long)cu * 1024;
         const int n_steps = a.cb_last - a.cb_first + 1;
-        uint32_t quad_phase = 0;
+        uint32_t quad_phase = 0, arr_want = 0;
         dp_flag((dp_lvu32*)(misc + DP_M_FQ), dp_tag(base, 0, 0, DP_E_Q));          // layer 0's q / k / v of the first step are in place
         const bool st = DP_STAMPS(a) != nullptr && cu == 100 && lane == 0;
 #define DP_STAMP(s_, i_) do { if (st) DP_STAMPS(a)[(s_) * 32 + (i_)] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -764,25 +819,57 @@ static __global__ __launch_bounds__(512) void k_dec_persist(const DecPersistArgs
                 DP_STAMP(s, 16);
                 if (DP_STAMPS(a) != nullptr && s == 5 && lane == 0) DP_STAMPS(a)[1024 + 2048 + 256 + cu] = __builtin_amdgcn_s_memrealtime();
             }
-            {   // logits -> LDS
+            int tok;
+            bool own_code;
+            {   // logits -> registers -> the code: sample_wave_front on this wave, the draws on waves 4..6 (DpFrontHand)
                 uint32_t v[18];
                 const int ng = (a.V + 1) / 2;
+                // the sampler's scalars from LDS, asked for before the sweep (as kernel arguments they are re-read from the kernarg segment
+                // here, a scalar-cache miss per step -- and between the sweep and the sampler it is on every CU's critical path)
+                const int sV = (int)misc[DP_M_SARG], sK = (int)misc[DP_M_SARG + 2];
+                const float sT = __uint_as_float(misc[DP_M_SARG + 1]);
+                const bool dbg = misc[DP_M_SDBG] != 0u && cu == 0;
+                const bool quad0 = !(sK > 1 && min(sK, sV) <= 128);        // known before the logits: the 4-wave form
                 if (!dp_sweep<9>(rgL, ng, dp_tag(base, s, DP_NL - 1, DP_E_L), v, ln, ab, a.err, 0x600u, a.poll_sleep, st ? DP_STAMPS(a) + s * 32 + 24 : nullptr)) return;
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    const int g0 = 2 * (j * 64 + ln);
-                    if (g0 < ng) ((dp_lu32*)(lds + DP_OFF_LOGITS))[g0] = v[2 * j];
-                    if (g0 + 1 < ng) ((dp_lu32*)(lds + DP_OFF_LOGITS))[g0 + 1] = v[2 * j + 1];
-                }
-                if ((a.V & 1) && ln == 0) ((dp_lu16*)(lds + DP_OFF_LOGITS))[a.V] = 0;       // the tail unit's second half is not a logit
-                dp_flag((dp_lvu32*)(misc + DP_M_FLG), dp_tag(base, s, DP_NL - 1, DP_E_L));
                 DP_STAMP(s, 17);
                 if (DP_STAMPS(a) != nullptr && s == 5 && lane == 0) DP_STAMPS(a)[1024 + 2048 + cu] = __builtin_amdgcn_s_memrealtime();
+                auto logits_to_lds = [&]() {
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) {
+                        const int g0 = 2 * (j * 64 + ln);
+                        if (g0 < ng) ((dp_lu32*)(lds + DP_OFF_LOGITS))[g0] = v[2 * j];
+                        if (g0 + 1 < ng) ((dp_lu32*)(lds + DP_OFF_LOGITS))[g0 + 1] = v[2 * j + 1];
+                    }
+                    if ((sV & 1) && ln == 0) ((dp_lu16*)(lds + DP_OFF_LOGITS))[sV] = 0;       // the tail unit's second half is not a logit
+                };
+                const uint32_t w0 = 4u * (uint32_t)(s + 1);
+                // the LDS copy of the logits: for the 4-wave form and for the debug copy only; straight after the sweep, like the word that
+                // sends waves 4..6 into the 4-wave form when that is known beforehand
+                if (quad0 || dbg) logits_to_lds();
+                if (quad0) dp_flag((dp_lvu32*)(misc + DP_M_SGO), w0 + DP_SGO_QUAD);
+                if (dbg) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    for (int i = ln; i < sV; i += 64) a.logits_out[(long)cb * sV + i] = ((const dp_lu16*)(lds + DP_OFF_LOGITS))[i];
+                }
+                tok = SAMPLE_WAVE_FALLBACK;
+                if (!quad0) {
+                    const DpFrontHand hand{(dp_lvu32*)(misc + DP_M_SGO), (dp_lvu32*)(misc + DP_M_SARR), ab, a.err, ln, w0, &arr_want,
+                                           st ? DP_STAMPS(a) + 4352 + s * 16 + 8 : nullptr};
+                    tok = sample_wave_front<9>(v, sV, sT, min(sK, sV), dp_sample_scratch(lds), ln, hand);
+                    if (tok == SAMPLE_WAVE_ABORT) return;
+                    if (tok == SAMPLE_WAVE_FALLBACK) {       // decided on the logits: the 4-wave form after all
+                        if (!dbg) logits_to_lds();
+                        dp_flag((dp_lvu32*)(misc + DP_M_SGO), w0 + DP_SGO_QUAD);
+                    }
+                }
+                own_code = tok != SAMPLE_WAVE_FALLBACK;
+                if (!own_code) {
+                    // the 4-wave form with waves 4..6 (this wave is the quad's fourth), on the logits in LDS; its wave 4 writes frame[]
+                    tok = dp_sample_step(a, lds, 3, ln, cu, cb, s, &quad_phase);
+                    if (*ab) return;
+                }
             }
-            {   // sample with waves 4..6 (this wave is the quad's fourth), then the code -> the next step's input row and layer-0
-                // q / k / v (table rows), like k_sample's tail
-                const int tok = dp_sample_step<true>(a, lds, 3, ln, cu, cb, s, &quad_phase);
-                if (*ab) return;
+            {   // the code -> the next step's input row and layer-0 q / k / v (table rows), like k_sample's tail
                 DP_STAMP(s, 18);
                 if (cb + 1 < a.ncb) {
                     int fed = a.forced ? a.forced[cb] : tok;
@@ -802,6 +889,7 @@ static __global__ __launch_bounds__(512) void k_dec_persist(const DecPersistArgs
                     dp_flag((dp_lvu32*)(misc + DP_M_FQ), dp_tag(base, s + 1, 0, DP_E_Q));
                     DP_STAMP(s, 19);
                 }
+                if (own_code && cu == 0 && ln == 0) a.frame[cb] = tok;      // (after the hand-off: its kernel-argument read is off the path)
             }
         }
         if (cu == 0 && lane == 0) __hip_atomic_store(a.epoch, base + (uint32_t)(n_steps * DP_NL * 5 + 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -363,6 +363,149 @@ __device__ __forceinline__ int sample_body(const uint32_t (&w)[ITERS][4], int V,
     return *sc.s_tok;
 }
 
+// ONE wave samples one sequence from logits it already holds in registers (the persistent depth decoder's gather wave, straight out of
+// its sweep of the logit granules): v[2j], v[2j+1] of lane l = packed logits 4 (64 j + l) .. + 3.  Same arithmetic and rounding points as
+// sample_body's fast form, and the same survivors in the same lanes, so the same bits; what differs is who builds the candidate list.
+// One wave issues one vector instruction per ~4 cycles, so the front works on the PACKED pairs (v_pk_*_i16), two logits per instruction:
+//  1. order values of the lane's 4 NL logits (pk_order: +-magnitude as a signed 16-bit integer, -0 == +0; + 32768 = an unsigned key that
+//     is dense in the bf16 values, 0 = not an element); the maxima of two groups per lane (the even and the odd elements: 2 NL logits
+//     each, like the thread pairs of sample_body); the kth largest of the 128 group maxima is the lower bound L (k <= 128 distinct
+//     elements >= it);
+//  2. candidates (key >= L - margin; the keys being dense, the margin covers at least the neighbours it has to) in ascending index order
+//     without a barrier: index order is (load, lane, sub-element), so one ballot per (load, sub-element) chained through mbcnt gives
+//     every lane its slot; ONE word per candidate, raw logit << 16 | index, into cand_i (non-candidates write a dump slot);
+//  3. the list and *s_n in LDS -> hand.publish_list(): the helper waves draw the candidates' Exp(1) variates into cand_q meanwhile;
+//  4. sample_body's fast back half; hand.wait_draws() stands where its barrier stood.
+// The caller guarantees 2 <= k <= 128 and V <= 4096.  Returns the code, or SAMPLE_WAVE_FALLBACK when the form does not apply -- a NaN
+// logit or more than 128 candidates (nothing published yet), or more than 64 survivors (the helpers have drawn and arrived) -- a pure
+// function of the logits and the parameters; or SAMPLE_WAVE_ABORT when wait_draws gave up.
+#define SAMPLE_WAVE_FALLBACK (-1)
+#define SAMPLE_WAVE_ABORT (-2)
+#define SAMPLE_WAVE_DUMP 255     // list slot of the non-candidates' writes (beyond the 128 list slots and the 64 survivor slots)
+typedef short s16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ s16x2_t pk_order(uint32_t w) {
+    const s16x2_t x = __builtin_bit_cast(s16x2_t, w);
+    const s16x2_t sg = x >> 15;                                     // 0 / -1
+    return (x ^ (sg & (short)0x7fff)) - sg;
+}
+template <int NL, class Hand>
+__device__ __forceinline__ int sample_wave_front(const uint32_t (&v)[2 * NL], int V, float temperature, int k, const SampleScratch& sc, int lane, Hand hand) {
+    // o: order values, slots that are not elements at -32768 (key 0);  z: the same with those slots at 0, for the NaN test.  Slots at
+    // or beyond V (the pad half of the last granule, the sweep's clamped re-reads of the last pair) are no elements.
+    s16x2_t o[2 * NL], z[2 * NL];
+#pragma unroll
+    for (int r = 0; r < 2 * NL; ++r) o[r] = z[r] = pk_order(v[r]);
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+        if (256 * (j + 1) > V) {                                    // (wave-uniform; V = 2051: the last load only)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int idx0 = 4 * (j * 64 + lane) + 2 * h;
+                const uint32_t bits = __builtin_bit_cast(uint32_t, o[2 * j + h]);
+                const uint32_t in = (idx0 < V ? bits & 0xffffu : 0u) | (idx0 + 1 < V ? bits & 0xffff0000u : 0u);
+                z[2 * j + h] = __builtin_bit_cast(s16x2_t, in);
+                o[2 * j + h] = __builtin_bit_cast(s16x2_t, in | (idx0 < V ? 0u : 0x8000u) | (idx0 + 1 < V ? 0u : 0x80000000u));
+            }
+        }
+    s16x2_t gmx = o[0], zmax = z[0], zmin = z[0];
+#pragma unroll
+    for (int r = 1; r < 2 * NL; ++r) {
+        gmx = __builtin_elementwise_max(gmx, o[r]);
+        zmax = __builtin_elementwise_max(zmax, z[r]);
+        zmin = __builtin_elementwise_min(zmin, z[r]);
+    }
+    // a NaN element (|order value| beyond infinity's) is not an element either: left to the 4-wave form
+    if (__ballot(max(zmax.x, zmax.y) > 0x7f80 || min(zmin.x, zmin.y) < -0x7f80) != 0ull) return SAMPLE_WAVE_FALLBACK;
+    const uint32_t gm[2] = {(uint32_t)((int)gmx.x + 32768), (uint32_t)((int)gmx.y + 32768)};
+    const uint32_t L = kth_largest_key<2>(gm, k);
+    hand.mark(0);
+    const uint32_t margin = 2u * (uint32_t)ceilf(fmaxf(temperature, 1.0f)) + 2u;
+    const uint32_t Lm = L > margin ? L - margin : 1u;             // >= 1: key 0 is "not an element"
+    const short lms = (short)((int)Lm - 32768);
+    const s16x2_t lm2 = {lms, lms};
+    const int idx_lane = 4 * lane;
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        // saturating o - Lm: the sign bit of each half says "below the bound"
+        const uint32_t d0 = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(o[2 * j], lm2));
+        const uint32_t d1 = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(o[2 * j + 1], lm2));
+        const bool f[4] = {(int)(d0 << 16) >= 0, (int)d0 >= 0, (int)(d1 << 16) >= 0, (int)d1 >= 0};
+        uint32_t p = (uint32_t)n;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned long long m = __ballot(f[e]);
+            p = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, p));
+            n += __popcll(m);
+        }
+        // p = candidates of earlier loads + of lower lanes of this load (p < n <= V <= the slots of cand_i: every slot written exists)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t w = v[2 * j + (e >> 1)];
+            const uint32_t idx = (uint32_t)(idx_lane | (256 * j + e));
+            sc.cand_i[f[e] ? (int)p : SAMPLE_WAVE_DUMP] = (int)((e & 1) ? ((w & 0xffff0000u) | idx) : ((w << 16) | idx));
+            p += f[e] ? 1u : 0u;
+        }
+    }
+    if (n > 128) return SAMPLE_WAVE_FALLBACK;
+    if (lane == 0) *sc.s_n = n;
+    hand.publish_list();
+    hand.mark(1);
+    // ---- sample_body's fast form from here on: two list slots per lane, t = bf16(logit / T), exact kth-largest t (ties kept) ----
+    float tv[2]; int ix[2]; uint32_t ck[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int c = u * 64 + lane;
+        const bool live = c < n;
+        const uint32_t w = (uint32_t)sc.cand_i[live ? c : 0];
+        tv[u] = round_bf(__uint_as_float(w & 0xffff0000u) / temperature);
+        ix[u] = (int)(w & 0xffffu) | (c << 16);
+        ck[u] = live ? order_key(tv[u]) : 0u;
+    }
+    const uint32_t kth = n > k ? kth_largest_key<2>(ck, k) : 0u;
+    const bool keep0 = ck[0] != 0u && ck[0] >= kth, keep1 = ck[1] != 0u && ck[1] >= kth;
+    const unsigned long long m0 = __ballot(keep0), m1 = __ballot(keep1);
+    const int kept0 = __popcll(m0), kept = kept0 + __popcll(m1);
+    hand.mark(2);
+    if (kept > 64) {                           // many ties: the 4-wave form, once the helpers have left cand_q (it aliases s_max)
+        if (!hand.wait_draws()) return SAMPLE_WAVE_ABORT;
+        return SAMPLE_WAVE_FALLBACK;
+    }
+    hand.publish_fast();                       // the helpers need not stay for the 4-wave form
+    const int p0 = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m0, 0u));
+    const int p1 = kept0 + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, 0u));
+    if (keep0) { sc.cand_t[128 + p0] = tv[0]; sc.cand_i[128 + p0] = ix[0]; }      // (slots 0..127 are still being read by the helpers)
+    if (keep1) { sc.cand_t[128 + p1] = tv[1]; sc.cand_i[128 + p1] = ix[1]; }
+    const bool live = lane < kept;
+    const float x = sc.cand_t[128 + (live ? lane : 0)];
+    const int pk = sc.cand_i[128 + (live ? lane : 0)];
+    // log_softmax / softmax with torch-CPU's bf16 rounding points
+    const float mx = wave_max(live ? x : -INFINITY);
+    const float sum = wave_sum(live ? expf(x - mx) : 0.f);
+    const float logsum = round_bf(logf(round_bf(sum)));
+    const float mx2 = round_bf(0.f - logsum);      // log-prob of the max element
+    const float e3 = live ? expf(round_bf((x - mx) - logsum) - mx2) : 0.f;
+    const float s2 = wave_sum(e3);
+    hand.mark(3);
+    if (!hand.wait_draws()) return SAMPLE_WAVE_ABORT;      // the Exp(1) draws of the helpers are in cand_q
+    hand.mark(4);
+    // argmax(p / q), q ~ Exp(1); first index wins ties
+    int best_idx = 0x7fffffff;
+    float best = -INFINITY;
+    const float p = round_bf(e3 / s2);
+    if (live && p > 0.f) { best = round_bf(p / sc.cand_q[pk >> 16]); best_idx = pk & 0xffff; }
+    const float wb = wave_max(best);
+    best_idx = wave_min_i(best == wb ? best_idx : 0x7fffffff);
+    return best_idx == 0x7fffffff ? 0 : best_idx;
+}
+// a helper wave's share of step 3: the Exp(1) draws of list slots hw * 64 + lane, + 64 nh, .. (hw = 0 .. nh-1)
+__device__ __forceinline__ void sample_wave_draws(const SampleScratch& sc, int hw, int nh, int lane, const bf16_t* noise_row, uint64_t seed, uint64_t step,
+                                                  int b, int codebook) {
+    const int n = min(*sc.s_n, 256);
+    for (int c = hw * 64 + lane; c < n; c += 64 * nh)
+        sc.cand_q[c] = exp1_draw(sc.cand_i[c] & 0xffff, noise_row, seed, step, b, codebook);
+}
+
 struct SyncThreads {
     __device__ __forceinline__ void operator()() const { __syncthreads(); }
     __device__ __forceinline__ void mark(int) const {}      // (the persistent decoder's barrier records a debug timeline here)

@@ -26,10 +26,11 @@ def main():
     tok, msk = bench.synthetic_prompt(args, 1, margs.text_vocab_size)
     S = tok.shape[1]
     m.prefill(tok, msk, torch.arange(S).unsqueeze(0))
-    m.depth(1, 0.9, 50, commit=True)
+    T, K = (float(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (0.9, 50)      # optional: temperature, top-k
+    m.depth(1, T, K, commit=True)
     assert _abi.lib.csm_debug_persist_stamps(m._h, None, 0) == 0, "this handle does not run the persistent launch"
     for _ in range(6):
-        m.step(1, 0.9, 50)
+        m.step(1, T, K)
     buf = (C.c_uint64 * (32 * 32 + 4096 + 256))()
     assert _abi.lib.csm_debug_persist_stamps(m._h, buf, 32 * 32 + 4096 + 256) == 0
     allw = torch.tensor(list(buf), dtype=torch.float64)
@@ -46,13 +47,11 @@ def main():
     seq.append(("rows published(L3) -> x of head ready (edge + final norm)", 15, 16))
     seq.append(("  x of head ready -> head wave 2 saw it", 16, 20))
     seq.append(("  head wave 2: rows computed and published", 20, 21))
-    seq.append(("  published -> logits in LDS (edge)", 21, 17))
-    seq.append(("  logits in LDS -> sampler waves saw them", 17, 22))
-    seq.append(("  sampler body", 22, 23))
-    seq.append(("  code written -> gather wave saw it", 23, 18))
+    seq.append(("  published -> logits swept into the gather wave's registers (edge)", 21, 17))
+    seq.append(("  logits swept -> code (the sampler: front and back on the gather wave, draws on waves 4..6)", 17, 18))
     seq.append(("code -> next step's table rows in LDS", 18, 19))
     tot = 0.0
-    print("persistent depth decoder, workgroup 100, mean over steps 3..28 (us):")
+    print(f"persistent depth decoder, T = {T}, top-k {K}, workgroup 100, mean over steps 3..28 (us):")
     for label, a, b in seq:
         vals = []
         for s in range(3, n_steps - 1):
@@ -88,18 +87,35 @@ def main():
     print(f"      wave 0: 3 row blocks of the down partial, published    {mean_d(4, 5):6.2f}")
     print(f"      partials published -> rows published (edge + sum)      {float(sum(float(t[s_, 2 * 4 + 3] - ex[s_, 5]) for s_ in range(3, 29)) / 26):6.2f}")
     sm = allw[4352:4352 + 512].view(32, 16) * 0.01
-    names = ["flag seen -> per-thread maxima stored", "barrier + kth bound of the 128 pair maxima", "count, scan, barrier, candidate list, barrier",
-             "t = logit / T, exact kth, survivors re-packed (wave 0)", "log-softmax, softmax", "barrier (Exp(1) draws ready) + race"]
-    print("   sampler detail (thread 0 of the quad):")
-    prev = t[:, 22]
-    for i, nm in enumerate(names):
-        vals = [float(sm[s_, i] - prev[s_]) for s_ in range(3, 29) if sm[s_, i] > 0]
-        print(f"      {nm:58s} {sum(vals) / max(len(vals), 1):6.2f}")
-        prev = sm[:, i]
-    vals = [float(t[s_, 23] - sm[s_, 5]) for s_ in range(3, 29) if sm[s_, 5] > 0]
-    print(f"      {'argmax over the wave, last barrier':58s} {sum(vals) / max(len(vals), 1):6.2f}")
-    vals = [float(sm[s_, 7] - sm[s_, 6]) for s_ in range(3, 29) if sm[s_, 7] > 0]
-    print(f"      {'sampler body alone, last pass (CSM_PERSIST_TRICKLE=134 runs it twice: warm instruction cache)':58s} {sum(vals) / max(len(vals), 1):6.2f}")
+    def detail(title, names, first, prev, last_name, last):
+        print(title)
+        for i, nm in enumerate(names):
+            vals = [float(sm[s_, first + i] - prev[s_]) for s_ in range(3, 29) if sm[s_, first + i] > 0 and prev[s_] > 0]
+            print(f"      {nm:58s} {sum(vals) / max(len(vals), 1):6.2f}   ({len(vals)} steps)")
+            prev = sm[:, first + i]
+        vals = [float(last[s_] - prev[s_]) for s_ in range(3, 29) if prev[s_] > 0 and last[s_] > 0]
+        print(f"      {last_name:58s} {sum(vals) / max(len(vals), 1):6.2f}   ({len(vals)} steps)")
+    # steps in the one-wave form (sample_wave_front): stamps 8.. of the step's row, by the gather wave
+    detail("   sampler detail, one-wave form (gather wave), from 'logits swept':",
+           ["keys, group maxima, kth bound of the 128 group maxima", "ballot compaction, candidate list, list word raised",
+            "t = logit / T, exact kth (survivors counted)", "survivors re-packed, log-softmax, softmax", "Exp(1) draws of waves 4..6 arrived"],
+           8, t[:, 17], "race, argmax over the wave -> code", t[:, 18])
+    vals = [float(t[s_, 28] - t[s_, 17]) for s_ in range(3, 29) if t[s_, 28] > 0]
+    print(f"      {'(wave 4: logits swept -> saw the list word)':58s} {sum(vals) / max(len(vals), 1):6.2f}")
+    vals = [float(t[s_, 29] - t[s_, 28]) for s_ in range(3, 29) if t[s_, 29] > 0]
+    print(f"      {'(wave 4: its draws, arrival)':58s} {sum(vals) / max(len(vals), 1):6.2f}")
+    # steps in the 4-wave form (sample_body; every step of a build from before the one-wave form): stamps 0..7, by wave 4
+    if float(sm[3:29, 0].max()) > 0:
+        vals = [float(t[s_, 22] - t[s_, 17]) for s_ in range(3, 29) if t[s_, 22] > 0]
+        print(f"   4-wave form: logits swept (older builds: in LDS) -> wave 4 enters   {sum(vals) / max(len(vals), 1):6.2f}   ({len(vals)} steps)")
+        vals = [float(t[s_, 23] - t[s_, 22]) for s_ in range(3, 29) if t[s_, 23] > 0]
+        print(f"   4-wave form: wave 4 enters -> leaves                               {sum(vals) / max(len(vals), 1):6.2f}")
+        vals = [float(t[s_, 18] - t[s_, 23]) for s_ in range(3, 29) if t[s_, 23] > 0]
+        print(f"   4-wave form: wave 4 leaves -> gather wave has the code             {sum(vals) / max(len(vals), 1):6.2f}")
+        detail("   sampler detail, 4-wave form (thread 0 of the quad), from its entry:",
+               ["flag seen -> per-thread maxima stored", "barrier + kth bound of the 128 pair maxima", "count, scan, barrier, candidate list, barrier",
+                "t = logit / T, exact kth, survivors re-packed (wave 0)", "log-softmax, softmax", "barrier (Exp(1) draws ready) + race"],
+               0, sm[:, 6], "argmax over the wave, last barrier", sm[:, 7])
     bl = allw[5312:5312 + 16] * 0.01
     if float(bl[12]) > 0:
         nm = ["entry (wave 0)", "q|k|v pair published (wave 0)", "attention vector in LDS (gather wave)", "o-proj rows published (wave 0)", "h1 in LDS (gather wave)",
