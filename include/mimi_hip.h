@@ -382,6 +382,65 @@ int  mimi_vad_pool_feed(mimi_vad_pool p, const int32_t* streams, const long* in_
                         const void* in, int in_is_i16, uint8_t* flags, int16_t* lag, long* power, long* floor, long* n_frames, void* stream);
 int  mimi_vad_pool_summary(mimi_vad_pool p, long* out, void* stream);
 
+/* ---- A keyed pool of WATERMARK streams (every clip marked on the device; the mark found again in a cut, padded, scaled clip) ----
+ * This project's own keyed spread-spectrum mark with host-interference cancellation -- not silentcipher's, and not compatible with it.
+ * Every decision is exact integer arithmetic, so the device computes THE RULE below bit for bit (tests/watermark_ref.py states it in NumPy).
+ * 24 kHz.  Constants: S = 1920 samples per symbol (one Mimi frame, 80 ms), K = 56 symbols per period, P = S K = 107,520 samples (4.48 s).
+ *   - samples: fp32 input q = clamp(rint(x * 32768.0f), -32768, 32767), rint to nearest even, a non-finite x gives q = 0; int16 input q = x.
+ *   - symbols: a one bit is b = +1, a zero bit b = -1.  k = 0 .. 7: the sync byte 0xB2; k = 8 .. 47: the five payload bytes; k = 48 .. 55: the
+ *     CRC-8 of the five bytes (polynomial 0x07, initial value 0); every byte MSB first.  As a word, bit k (LSB = symbol 0) holds symbol k.
+ *   - chips from the pool's 64-bit secret: w = philox4x32_10(counter (p >> 7, 0, 0, 0x574D), key (secret_lo, secret_hi))[(p >> 5) & 3],
+ *     c[p] = 1 - 2 * ((w >> (p & 31)) & 1) for p in [0, P).
+ * EMBED, per stream: sample n (counted from the reset) lies in block J = n / S, which carries symbol k = J % K; its chip is c[n % P].  For
+ * each COMPLETE block, sums over its S samples:
+ *   1. E = sum q^2, r = sum q c, T = (isqrt(E) * t_q4) >> 4, u = b_k r.            (|r| <= 1920 * 32768 < 2^26; E <= 1920 * 2^30 < 2^41)
+ *   2. u >= T: D = 0, the block already says its bit with margin and is untouched; otherwise D = b_k (T - u).
+ *   3. a = |D| / S, rem = |D| % S; d[m] = sgn(D) c[m] (a + (m < rem)) for the block's sample m, so that sum d c == D exactly.
+ *   4. fp32: y = x + float(d) * 2^-15 (one rounding) where d != 0 and x is finite, else y = x bit for bit; int16: y = clamp(q + d).
+ * t_q4 in 1 .. 64 per stream (default 8: the block says its bit at no less than half a standard deviation of the host's own correlation; at
+ * 0 a cancelled block would sum to exactly 0 and say nothing).  Digital silence stays digital silence; a NaN or Inf stays what it was.
+ * STREAMING: a block comes out once it is complete, so a stream's output lags its input by fewer than S samples; final[i] != 0 writes the
+ * open block through unchanged and leaves the stream fresh (same payload and t_q4).  A stream's outputs, concatenated over ANY chunk
+ * schedule, are bit for bit the one-shot result; they do not depend on which streams share the call, on list order or on the stream id.
+ * Per stream the device keeps the open block's samples (fewer than 1920 raw words, two banks flipped per call: a call reads one and writes
+ * the other); the host keeps {samples taken, samples given, t_q4, the symbol bits, the format, the bank}.  mimi_wm_pool_reset (payloads: 5
+ * bytes per listed stream) is host arithmetic, no launch.  Streams of a new pool are fresh with the payload {212, 211, 146, 56, 201}, t_q4 8.
+ * mimi_wm_pool_feed: stream streams[i] gets n_in[i] >= 0 samples at in + in_off[i] ELEMENTS (in_is_i16: 0 = fp32, 1 = int16; out has the
+ * format of in; a stream keeps one format between resets).  in, out: device memory; streams, in_off, n_in, final: host arrays read before
+ * the call returns; n_out: a host array WRITTEN before the call returns.  Outputs are packed back to back: stream i owns
+ * out[O_i .. O_i + n_out[i]), O_i = n_out[0] + .. + n_out[i-1]; mimi_wm_pool_out_count says beforehand what a feed would give.  ONE launch.
+ * DETECT, per clip: candidate offset o in [0, P) says "clip sample 0 is stream position o".  With first = (-o) mod S the clip's complete
+ * blocks start at first + i S; block i carries symbol k_i = ((o + first) / S + i) % K; r_i = sum_m q[first + i S + m] c[(o + first + i S + m) % P];
+ * R_k = sum of the r_i with k_i = k (int64), cov_k their number.  With the caller's K-bit words expect and mask (bit k = symbol k):
+ * score(o) = the number of k with the mask bit set, cov_k > 0 and sign(R_k) == b_k (R_k == 0 matches nothing); covered(o) = the number of k
+ * with the mask bit set and cov_k > 0.  The candidates are (o0 + i) % P for i < n_off; the best is the highest score, on ties the smallest i.
+ * All K mask bits: "verify this payload"; the 8 sync bits alone: "find any payload".  Per clip the call writes MIMI_WM_ROW int64: the best i,
+ * its offset, its score, its covered count, the number of complete blocks, the decoded payload (bit = R_k > 0) as one 40-bit integer,
+ * whether its CRC-8 holds (every symbol 8 .. 55 has cov_k > 0 and R_k != 0, and the decoded sixth byte is the CRC-8 of the five), 0,
+ * R_0 .. R_55 of the best offset.  scores: device scratch of sum n_off int32 (every candidate's score, clip after clip).  TWO launches: one
+ * workgroup per (clip, 256 consecutive candidates), then one per clip.
+ * feed and detect allocate nothing, copy nothing from the host beyond the kernel arguments and never synchronise.
+ * Returns -1 with a message in mimi_wm_pool_last_error, nothing enqueued and no state moved, for: n_streams outside [1, 64] (create); n
+ * outside [1, n_streams], a duplicate or out-of-range id, t_q4 outside 1 .. 64 (reset); a negative n_in or in_off, a null pointer, a
+ * misaligned buffer, an unknown format, a chunk of more than 2^30 samples, a stream of more than 2^48 samples since it was fresh, a stream
+ * that changes format between resets (feed); more than 64 clips, a clip of more than 2^24 samples, a negative o0, n_off < 1, more than 2^21
+ * candidates in a call, expect or mask bits beyond the 56 symbols (detect).  -2: a HIP error.  Drive ONE HIP stream per pool at a time.     */
+#define MIMI_WM_MAX_STREAMS 64
+#define MIMI_WM_MAX_CLIPS 64
+#define MIMI_WM_S 1920
+#define MIMI_WM_K 56
+#define MIMI_WM_ROW 64
+typedef struct MimiWmPool* mimi_wm_pool;
+int  mimi_wm_pool_create(int n_streams, uint64_t secret, mimi_wm_pool* out);
+void mimi_wm_pool_destroy(mimi_wm_pool p);
+const char* mimi_wm_pool_last_error(mimi_wm_pool p);           /* p == NULL: why mimi_wm_pool_create failed (this thread) */
+int  mimi_wm_pool_reset(mimi_wm_pool p, const int32_t* streams, const uint8_t* payloads, const int32_t* t_q4, int n);
+long mimi_wm_pool_out_count(mimi_wm_pool p, int sid, long n_in, int final);
+int  mimi_wm_pool_feed(mimi_wm_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                       const void* in, int in_is_i16, void* out, long* n_out, void* stream);
+int  mimi_wm_pool_detect(mimi_wm_pool p, const long* in_off, const long* n_in, const long* o0, const long* n_off, const uint64_t* expect,
+                         const uint64_t* mask, int n, const void* in, int in_is_i16, int32_t* scores, long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

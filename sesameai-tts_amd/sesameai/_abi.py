@@ -168,6 +168,13 @@ MIMI_SIGNATURES = {
     "mimi_vad_pool_frame_count": (_l, [_vp, _i, _l, _i]),
     "mimi_vad_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_l), _vp]),
     "mimi_vad_pool_summary": (_i, [_vp, _vp, _vp]),
+    "mimi_wm_pool_create": (_i, [_i, C.c_uint64, C.POINTER(_vp)]),
+    "mimi_wm_pool_destroy": (None, [_vp]),
+    "mimi_wm_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_wm_pool_reset": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "mimi_wm_pool_out_count": (_l, [_vp, _i, _l, _i]),
+    "mimi_wm_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _i, _vp, C.POINTER(_l), _vp]),
+    "mimi_wm_pool_detect": (_i, [_vp, C.POINTER(_l), C.POINTER(_l), C.POINTER(_l), C.POINTER(_l), _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in list(SIGNATURES.items()) + list(MIMI_SIGNATURES.items()):

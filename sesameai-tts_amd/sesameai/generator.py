@@ -480,7 +480,7 @@ class Generator:
                       temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
                       seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
                       sessions: Optional[Sequence[Optional[Conversation]]] = None, finish=None,
-                      on_result: Optional[Callable[[int, torch.Tensor], None]] = None, speed=None) -> List[torch.Tensor]:
+                      on_result: Optional[Callable[[int, torch.Tensor], None]] = None, speed=None, watermark=None) -> List[torch.Tensor]:
         """``generate`` for a list of requests through the continuously refilled batch: one audio tensor per request
         (``max_audio_length_ms``, ``temperature``, ``topk``: one value, or one per request; ``seed``: one optional int per request;
         ``sessions``: one ``Conversation`` or None per request -- the context of a request with a session lists only the NEW segments).
@@ -489,17 +489,22 @@ class Generator:
         request completes.
         ``speed`` (None: the calls described above, exactly): a speech-rate factor in 0.5 .. 2.0, or one (or None) per request -- each decoded
         clip goes through the device time stretch (sesameai/stretch.py) before anything else sees it; with ``finish`` all clips that end in
-        a block share ONE stretch call."""
+        a block share ONE stretch call.
+        ``watermark`` (None: the calls described above, exactly): True or "device" for the public CSM key, or a five-byte key -- each clip
+        carries the device watermark (sesameai/watermarking.py) after the stretch; with ``finish`` all clips that end in a block share ONE
+        embed call in front of the finish."""
         max_generation_len = _frames_for(max_audio_length_ms)
         prompts = self._build_prompts(texts, speakers, contexts)
         if finish is not None:
             if sessions is not None:
                 raise ValueError("finish= with sessions=: not supported")
             return self.generate_segments(prompts, max_generation_len, temperature, topk, finish, seed=seed, refill_group=refill_group,
-                                          on_result=on_result, **({} if speed is None else {"speed": speed}))
+                                          on_result=on_result, **({} if speed is None else {"speed": speed}),
+                                          **({} if watermark is None else {"watermark": watermark}))
         if on_result is not None:
             raise ValueError("on_result= needs finish=")
         speeds = self._speeds(speed, len(prompts))
+        key = self._mark_key(watermark)
         out: List[torch.Tensor] = [torch.tensor([]) for _ in prompts]
         for i, frames in self.iter_codes_continuous(prompts, max_generation_len, temperature, topk, seed=seed, refill_group=refill_group,
                                                     **({} if sessions is None else {"sessions": sessions})):
@@ -507,6 +512,8 @@ class Generator:
                 out[i] = self._decode_frames(frames.unsqueeze(1))
                 if speeds[i] is not None:
                     out[i] = self._stretch_clip(out[i], speeds[i])
+                if key is not None:
+                    out[i] = self._mark_clip(out[i], key)
         return out
 
     @staticmethod
@@ -523,12 +530,26 @@ class Generator:
         from .stretch import stretch
         return stretch([audio], speed)[0] if audio.numel() else audio
 
+    @staticmethod
+    def _mark_key(watermark) -> Optional[List[int]]:
+        """``watermark=`` as a checked five-byte key, or None (None without importing anything: today's calls exactly)."""
+        if watermark is None:
+            return None
+        from .watermarking import key_of
+        return key_of(watermark)
+
+    @staticmethod
+    def _mark_clip(audio: torch.Tensor, key: List[int]) -> torch.Tensor:
+        """One clip through a one-shot device watermark embed (sesameai/watermarking.py)."""
+        from .watermarking import embed
+        return embed([audio], key)[0] if audio.numel() else audio
+
     def generate_segments(self, prompts: Sequence[Tuple[torch.Tensor, torch.Tensor]], max_generation_len: Union[int, Sequence[int]],
                           temperature: Union[float, Sequence[float]], topk: Union[int, Sequence[int]], finish,
                           seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1,
                           post: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
                           on_result: Optional[Callable[[int, torch.Tensor], None]] = None, slots: Optional[int] = None,
-                          speed=None) -> List[torch.Tensor]:
+                          speed=None, watermark=None) -> List[torch.Tensor]:
         """Prompts [(tokens (S_i,33), mask (S_i,33)), ...] through the continuously refilled batch, each result a FINISHED segment: int16 on
         the device, peak-normalised, with lead and tail silence and fades (``finish``: a ``SegmentFinish`` for all prompts, or one per
         prompt; sesameai/finish.py) -- what ``tts_service.TTS.generate_audio_segment`` makes of a sentence, bit for bit, without the float32
@@ -541,10 +562,14 @@ class Generator:
         many of the batch's slots (None: all of them).  Returns the segments in the order of ``prompts``.
         ``speed`` (None: the calls described above, exactly): a speech-rate factor in 0.5 .. 2.0, or one (or None) per prompt: the decoded
         clips that end in a block go through ONE ``stretch`` call (sesameai/stretch.py), then ``post``, then the ONE finish call -- the
-        stretch acts on the decoded fp32 clip, so lead and tail silence keep their lengths."""
+        stretch acts on the decoded fp32 clip, so lead and tail silence keep their lengths.
+        ``watermark`` (None: the calls described above, exactly): True, "device" or a five-byte key -- the block's non-empty clips go through
+        ONE device embed call (sesameai/watermarking.py) after the stretch and ``post``, in front of the finish: the mark that replaces the
+        host ``post`` hook, so a segment stays on the device between decode and finish."""
         from .finish import SegmentFinisher, per_clip
         how = per_clip(finish, len(prompts))
         speeds = self._speeds(speed, len(prompts))
+        key = self._mark_key(watermark)
         if self._finisher is None:
             self._finisher = SegmentFinisher(self.device)
         side = self._side_stream()
@@ -570,6 +595,10 @@ class Generator:
                     from .stretch import stretch                    # ONE stretch call for the block's clips, then post, then the finish
                     for j, y in zip(quick, stretch([clips[j] for j in quick], [speeds[done[j][0]] for j in quick])):
                         clips[j] = post(y) if post is not None else y
+                if key is not None and (heard := [j for j, c in enumerate(clips) if c.numel()]):
+                    from .watermarking import embed                 # ONE embed call for the block's clips, then the finish
+                    for j, y in zip(heard, embed([clips[j] for j in heard], key)):
+                        clips[j] = y
                 pcm = self._finisher.finish(clips, [how[i] for i, _ in done], self.sample_rate)
             if side is not None:
                 side.synchronize()
@@ -594,8 +623,8 @@ class Generator:
                              temperature: Union[float, Sequence[float]] = 0.7, topk: Union[int, Sequence[int]] = 30,
                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None,
                              sessions: Optional[Sequence[Optional[Conversation]]] = None,
-                             out_sample_rate: Optional[int] = None, out_dtype: Optional[torch.dtype] = None, speed=None
-                             ) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
+                             out_sample_rate: Optional[int] = None, out_dtype: Optional[torch.dtype] = None, speed=None,
+                             watermark=None) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
         Each batch slot is one stream of a ``MimiStreamPool`` (reset when a new utterance takes the slot); after every polled block
@@ -628,7 +657,12 @@ class Generator:
         and each pool call's PCM goes through ONE stretch call on the side stream, BEFORE the resampler.  A request's chunks, concatenated,
         are bit for bit ``stretch`` of its concatenated ``speed=None`` chunks (with ``out_sample_rate``: ``resample`` of that); the stretch
         holds back up to 1,280 samples, which come with the request's last chunk -- also with a closing chunk that is empty at 24 kHz.  A
-        request whose speed is None or 1.0 never touches the stretcher: its chunks are those of a run without ``speed``."""
+        request whose speed is None or 1.0 never touches the stretcher: its chunks are those of a run without ``speed``.
+        ``watermark`` (None: the calls described above exactly): True or "device" for the public CSM key, or a five-byte key.  Each slot is
+        then also one stream of a ``WatermarkPool`` (sesameai/watermarking.py), reset with the key when a request takes the slot, and each
+        pool call's PCM goes through ONE embed call on the side stream, AFTER the stretch and BEFORE the resampler.  A request's chunks,
+        concatenated, are bit for bit ``embed`` of its concatenated ``watermark=None`` chunks; a chunk of whole frames is whole blocks and
+        lags by nothing, behind a stretch the mark holds back fewer than 1920 samples, which come with the request's last chunk."""
         size = self._stream_buffer_size
         if first_chunk_frames is not None and not 1 <= int(first_chunk_frames) < size:
             raise ValueError(f"first_chunk_frames must be None or 1 .. {size - 1}")
@@ -661,6 +695,12 @@ class Generator:
             if ("stretcher", B) not in self._stream_pools:
                 self._stream_pools[("stretcher", B)] = TimeStretchPool(B, device=self.device)
             kw["stretcher"], kw["speeds"] = self._stream_pools[("stretcher", B)], speeds
+        if (key := self._mark_key(watermark)) is not None:
+            from .watermarking import WatermarkPool, default_secret
+            at = ("marker", B, default_secret(key))
+            if at not in self._stream_pools:
+                self._stream_pools[at] = WatermarkPool(B, at[2], device=self.device)
+            kw["marker"], kw["marks"] = self._stream_pools[at], [key] * len(prompts)
         streams = SlotStreams(self._stream_pools[(B, size)], B, size, self._side_stream(), self.device, **kw)
         backlog: List[list] = []                                    # polled blocks whose audio is still to be decoded
         for block in self._iter_blocks_continuous(prompts, max_generation_len, temperature, topk, size, seed=seed, refill_group=refill_group,
@@ -746,11 +786,16 @@ class Generator:
     @torch.inference_mode()
     def generate(self, text, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                  temperature: float = 0.7, topk: int = 30, stream: bool = False, session: Optional[Conversation] = None,
-                 speed=None) -> torch.Tensor:
+                 speed=None, watermark=None) -> torch.Tensor:
         """reference: generator.py:212-300.  ``session``: ``context`` lists only the segments that are NEW since the session's last turn
         (``open_session``).  ``speed`` (None: the calls above exactly): a speech-rate factor in 0.5 .. 2.0 -- the decoded clip goes through a
-        one-shot device time stretch (sesameai/stretch.py); the pitch stays."""
+        one-shot device time stretch (sesameai/stretch.py); the pitch stays.  ``watermark`` (None: the calls above exactly): True, "device"
+        or a five-byte key -- the clip then carries the device watermark (sesameai/watermarking.py), embedded after the stretch."""
         (how_fast,) = self._speeds(speed, 1)
+        if (key := self._mark_key(watermark)) is not None:
+            audio = self.generate(text, speaker, context, max_audio_length_ms, temperature, topk, stream=stream, session=session,
+                                  **({} if speed is None else {"speed": speed}))
+            return self._mark_clip(audio, key)
         if stream:
             chunks = list(self.generate_stream(text, speaker, context, max_audio_length_ms, temperature, topk, session=session))
             audio = torch.cat(chunks) if chunks else torch.tensor([])

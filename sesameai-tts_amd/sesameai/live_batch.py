@@ -341,12 +341,19 @@ class SlotStreams:
     (``TimeStretchPool``), slot = stream, and one speed factor or None per REQUEST; a slot is reset with its request's speed when the request
     takes it, and every pool call's PCM of the requests that have a speed goes through ONE ``stretcher.feed`` on ``side`` BEFORE the resampler,
     ``final`` for the slots whose request it closes -- the stretch's tail comes with the request's last chunk, also when that chunk is empty at
-    24 kHz.  A request whose speed is None (or 1.0) never touches the stretcher."""
+    24 kHz.  A request whose speed is None (or 1.0) never touches the stretcher.
+    ``marker`` with ``marks`` (None: no watermark, today's calls exactly): a pool of at least ``slots`` watermark streams (``WatermarkPool``),
+    slot = stream, and one five-byte key or None per REQUEST; a slot is reset with its request's key when the request takes it, and every pool
+    call's PCM of the requests that have a key goes through ONE ``marker.feed`` on ``side`` AFTER the stretch and BEFORE the resampler,
+    ``final`` for the slots whose request it closes -- an open block (only a stretch leaves one: a chunk of whole frames is whole blocks) comes
+    through with the request's last chunk, also when that chunk is empty at 24 kHz."""
 
     def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None, resampler=None, stretcher=None,
-                 speeds: Optional[Sequence[Optional[float]]] = None):
+                 speeds: Optional[Sequence[Optional[float]]] = None, marker=None, marks: Optional[Sequence] = None):
         self.pool, self.size, self.side, self.first, self.resampler = pool, size, side, first, resampler
         self.stretcher, self.speeds = stretcher, speeds
+        self.marker, self.marks = marker, marks
+        self.mark: List[Optional[Sequence[int]]] = [None] * slots    # (marker) the key of the request that holds the slot
         self.speed: List[Optional[float]] = [None] * slots          # (stretcher) the speed of the request that holds the slot
         self.started: List[bool] = [False] * slots                  # whether the slot's request has had a chunk (``first`` only)
         self.owner: List[Optional[int]] = [None] * slots
@@ -388,6 +395,11 @@ class SlotStreams:
                         self.speed[s_] = self.speeds[owner[s_]]
                     if quick := [s_ for s_ in fresh if self.speed[s_] is not None]:
                         self.stretcher.reset(quick, [self.speed[s_] for s_ in quick])
+                if self.marker is not None:
+                    for s_ in fresh:
+                        self.mark[s_] = self.marks[owner[s_]]
+                    if keyed := [s_ for s_ in fresh if self.mark[s_] is not None]:
+                        self.marker.reset(keyed, [list(self.mark[s_]) for s_ in keyed])
             if self.first is not None:
                 self._ragged_calls(ending, calls)
             while self.first is None and (full := [s_ for s_, h in enumerate(held) if len(h) >= self.size]):
@@ -406,6 +418,17 @@ class SlotStreams:
                         calls[k] = (slots, frames, pcm)
                 if bare := [s_ for s_ in ending if s_ not in final and self.speed[s_] is not None]:
                     tails = dict(zip(bare, self.stretcher.feed(bare, [self.no_pcm.float()] * len(bare), True)))
+            if self.marker is not None:                             # ONE watermark call per pool call, and one for the empty closing chunks
+                for k, (slots, frames, pcm) in enumerate(calls):
+                    if keyed := [j for j, s_ in enumerate(slots) if self.mark[s_] is not None]:
+                        ys = self.marker.feed([slots[j] for j in keyed], [pcm[j][0] for j in keyed],
+                                              [slots[j] in ending and final[slots[j]] == k for j in keyed])
+                        pcm = [pcm[j] for j in range(len(slots))]
+                        for j, y in zip(keyed, ys):
+                            pcm[j] = y.unsqueeze(0)
+                        calls[k] = (slots, frames, pcm)
+                if bare := [s_ for s_ in ending if s_ not in final and self.mark[s_] is not None]:
+                    tails.update(zip(bare, self.marker.feed(bare, [tails.get(s_, self.no_pcm.float()) for s_ in bare], True)))
             if self.resampler is not None:                          # ONE resampler call per pool call, and one for the empty closing chunks
                 for k, (slots, frames, pcm) in enumerate(calls):
                     rs = self.resampler.feed(slots, [pcm[j][0] for j in range(len(slots))], [s_ in ending and final[s_] == k for s_ in slots])

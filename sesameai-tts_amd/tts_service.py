@@ -85,7 +85,13 @@ class TTS:
     max_batch_size = 1
     _voice_prefix = None            # the prefix-store handle of the loaded voice's context rows (batch= only), made on first use
 
-    def __init__(self, device: str = "cuda", model_repo: str = "sesame/csm-1b", voice_dir: Optional[str] = None, max_batch_size: int = 1) -> None:
+    watermark_kind = None           # None: silentcipher when it is importable, else the pass-through; "device": this build's own mark
+
+    def __init__(self, device: str = "cuda", model_repo: str = "sesame/csm-1b", voice_dir: Optional[str] = None, max_batch_size: int = 1,
+                 watermark: Optional[str] = None) -> None:
+        if watermark not in (None, "device"):
+            raise ValueError("watermark must be None or 'device'")
+        self.watermark_kind = watermark
         self.device = device
         self.max_batch_size = int(max_batch_size)       # slots of the live batch say / export_wav may use with batch= (1: none)
         self.model_repo = model_repo
@@ -99,7 +105,7 @@ class TTS:
         self.generator = load_csm_1b(self.device) if self.max_batch_size == 1 else load_csm_1b(self.device, max_batch_size=self.max_batch_size)
         # reference tts_service.py load_model: the watermarker is loaded next to the model (a pass-through hook
         # that says so once when silentcipher is not installed)
-        self.watermarker = load_watermarker(self.device)
+        self.watermarker = load_watermarker(self.device) if self.watermark_kind is None else load_watermarker(self.device, kind=self.watermark_kind)
 
     def list_voices(self) -> list:
         return list(self.voices.keys())
@@ -249,7 +255,9 @@ class TTS:
         if prompts:
             kw = {}
             wm = getattr(self, "watermarker", None)
-            if wm is not None:                               # every generated clip carries the public CSM watermark (generate_with_context)
+            if self.watermark_kind == "device":              # the device mark: ONE embed call per block, the clips never leave the device
+                kw["watermark"] = CSM_1B_GH_WATERMARK
+            elif wm is not None:                             # every generated clip carries the public CSM watermark (generate_with_context)
                 kw["post"] = lambda audio: resample_to(*watermark(wm, audio, sr, CSM_1B_GH_WATERMARK), sr)
             if speed is not None:                            # each block's clips: ONE stretch call, then the watermark, then the finish
                 kw["speed"] = speed
@@ -374,6 +382,8 @@ def parse_args(argv=None):
     parser.add_argument("--seed", type=int, default=None, metavar="S", help="with --batch: sentence i is sampled with seed S + i")
     parser.add_argument("--speed", type=float, default=None, metavar="X",
                         help="speech rate, 0.5 .. 2.0 (the pitch stays; default: as generated)")
+    parser.add_argument("--watermark", type=str, default=None, choices=["device"],
+                        help="device: mark every clip with this build's own keyed mark, on the GPU (default: silentcipher if it is installed)")
     args = parser.parse_args(argv)
     if args.device == "cpu":
         parser.error("this build runs the hot path on MI355X only; there is no -d cpu path (use the reference)")
@@ -388,7 +398,8 @@ def parse_args(argv=None):
 
 def main():
     args = parse_args()
-    tts = TTS(device=args.device) if args.batch is None else TTS(device=args.device, max_batch_size=args.batch)
+    made = {} if args.watermark is None else {"watermark": args.watermark}
+    tts = TTS(device=args.device, **made) if args.batch is None else TTS(device=args.device, max_batch_size=args.batch, **made)
     more = {} if args.batch is None else {"batch": args.batch, "seed": args.seed}
     if args.speed is not None:
         more["speed"] = args.speed

@@ -1,0 +1,271 @@
+// The host plan of a keyed pool of watermark streams (sesameai-tts_amd/csrc/watermark_plan.h: no HIP) as a stand-alone host program, built
+// with the host sanitizers by tests/test_watermark_plan_host.py.  The output counts against the definition (a block comes out once its S
+// samples are in; `final` lets the open block through); every refusal of include/mimi_hip.h's mimi_wm_pool_reset / mimi_wm_pool_feed /
+// mimi_wm_pool_detect at both sides of both ends of its range, made with nothing planned and no state moved; the packed output places and
+// workgroup offsets; that the carry never reaches S; a stream walked past 2^40 samples in large steps, whose kernel-visible numbers stay
+// small; the symbol word of the default payload and its CRC-8; and the detect plan's packed places.  Prints "ok".
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "watermark_plan.h"
+
+static int g_checks = 0;
+#define REQUIRE(cond)                                                              \
+    do {                                                                           \
+        ++g_checks;                                                                \
+        if (!(cond)) { printf("FAILED %s (%s:%d)\n", #cond, __FILE__, __LINE__); exit(1); } \
+    } while (0)
+
+static float g_in[4], g_out[4];
+static int32_t g_scores[4];
+static long g_rows[4];
+static const uint8_t kPayload[5] = {212, 211, 146, 56, 201};
+
+struct Walk {                        // one stream, fed through wm_plan_build, beside its totals
+    WmStream st[WM_MAX_STREAMS] = {};
+    long R = 0, given = 0;
+    int t_q4 = 8;
+    void reset(int sid, int t) {
+        const int32_t ids[1] = {sid}, tq[1] = {t};
+        REQUIRE(wm_reset(4, st, ids, kPayload, tq, 1) == nullptr);
+        REQUIRE(st[sid].R == 0 && st[sid].given == 0 && st[sid].fmt == -1 && st[sid].t_q4 == t && st[sid].bits == wm_symbol_bits(kPayload));
+        R = 0; given = 0; t_q4 = t;
+    }
+    void feed(int sid, long n, bool final, int i16 = 0, WmSeg* seg_out = nullptr) {
+        const int32_t ids[1] = {sid}, fin[1] = {final ? 1 : 0};
+        const long off[1] = {5}, len[1] = {n};
+        long n_out[1] = {-1};
+        WmPlan plan; WmStream next[WM_MAX_STREAMS];
+        const char* bad = wm_plan_build(4, st, ids, off, len, fin, 1, g_in, i16, g_out, n_out, &plan, next);
+        REQUIRE(bad == nullptr && plan.n == 1);
+        const WmSeg& g = plan.seg[0];
+        const long R1 = R + n, blocks = R1 / WM_S - R / WM_S;                                     // blocks completed by this call
+        const long want = final ? R1 - given : R1 / WM_S * WM_S - given;
+        REQUIRE(n_out[0] == want && wm_out_len(st[sid], n, final) == want);
+        REQUIRE(g.nb == blocks && plan.groups == blocks + 1 && g.g_off == 0 && g.out_off == 0 && g.in_off == 5 && g.n_in == n);
+        REQUIRE(WM_SID(g) == sid && WM_PARITY(g) == st[sid].parity && WM_FINAL(g) == (final ? 1 : 0) && g.t_q4 == t_q4);
+        REQUIRE(g.Lc == R % WM_S && g.Lc >= 0 && g.Lc < WM_S && given == R - g.Lc);              // the carry is the open block, never S
+        REQUIRE(g.k0 == (R / WM_S) % WM_K && g.k0 >= 0 && g.k0 < WM_K);
+        REQUIRE((long)g.Lc + g.n_in - (long)g.nb * WM_S >= 0 && (long)g.Lc + g.n_in - (long)g.nb * WM_S < WM_S);   // the tail fits a bank
+        REQUIRE(next[0].parity == (st[sid].parity ^ 1) && next[0].t_q4 == t_q4 && next[0].bits == st[sid].bits);
+        if (final) {
+            REQUIRE(next[0].R == 0 && next[0].given == 0 && next[0].fmt == -1);
+            R = 0; given = 0;
+        } else {
+            REQUIRE(next[0].R == R1 && next[0].given == given + want && next[0].fmt == i16 && wm_carry_len(R1) < WM_S);
+            R = R1; given += want;
+        }
+        st[sid] = next[0];
+        if (seg_out) *seg_out = g;
+    }
+};
+
+static void check_counts() {
+    const long chunks[9] = {0, 1, 7, 1919, 1920, 1921, 3839, 4000, 19200};
+    for (int a = 0; a < 9; ++a)
+        for (int b = 0; b < 9; ++b)
+            for (int c = 0; c < 9; c += 2)
+                for (int fin = 0; fin < 2; ++fin) {
+                    Walk w; w.reset(1, 8);
+                    w.feed(1, chunks[a], false); w.feed(1, chunks[b], false); w.feed(1, chunks[c], fin != 0);
+                    if (fin) w.feed(1, chunks[a], true);                  // the stream is fresh again
+                }
+    Walk w; w.reset(2, 1);
+    w.feed(2, 1919, false); REQUIRE(w.given == 0);                         // 1919 samples give nothing, the 1920th completes block 0
+    w.feed(2, 1, false); REQUIRE(w.given == 1920);
+    w.feed(2, 10 * 1920, false); REQUIRE(w.given == 11 * 1920);            // ten whole blocks in, ten whole blocks out: no lag
+    // the period wraps after 56 blocks
+    Walk p; p.reset(0, 64);
+    WmSeg g;
+    p.feed(0, 55L * WM_S + 3, false);
+    p.feed(0, 2L * WM_S, false, 0, &g); REQUIRE(g.k0 == 55 && g.nb == 2 && g.Lc == 3);
+    p.feed(0, 0, false, 0, &g); REQUIRE(g.k0 == 1 && g.nb == 0);
+}
+
+static void check_long_walk() {
+    Walk w; w.reset(3, 8);
+    long big = 0;
+    while (w.R < (1L << 40) + 12345) {
+        WmSeg g;
+        w.feed(3, WM_MAX_CHUNK - 7 * (big % 5), false, 0, &g); ++big;
+        REQUIRE(g.Lc < WM_S && g.k0 < WM_K && g.n_in <= WM_MAX_CHUNK && g.nb <= WM_MAX_CHUNK / WM_S + 1 && g.g_off == 0);
+        w.feed(3, 1917, false, 0, &g);
+        REQUIRE(g.Lc < WM_S && g.nb <= 1);
+    }
+    REQUIRE(w.R > (1L << 40));
+    w.feed(3, 5, true);
+}
+
+static void check_feed_refusals() {
+    WmStream st[WM_MAX_STREAMS] = {};
+    const int32_t ids2[2] = {0, 1}, tq2[2] = {8, 8};
+    const uint8_t pay2[10] = {212, 211, 146, 56, 201, 1, 2, 3, 4, 5};
+    REQUIRE(wm_reset(4, st, ids2, pay2, tq2, 2) == nullptr);
+    REQUIRE(st[1].bits == wm_symbol_bits(pay2 + 5) && st[1].bits != st[0].bits);
+    st[0].R = 777; st[0].given = 0; st[0].fmt = 0;
+    WmStream before[WM_MAX_STREAMS]; memcpy(before, st, sizeof(st));
+    WmPlan plan; WmStream next[WM_MAX_STREAMS];
+    long n_out[2];
+    const int32_t fin[2] = {0, 0};
+    const long off[2] = {0, 4}, len[2] = {4, 0};
+#define REFUSED(expr)                                                              \
+    do {                                                                           \
+        plan.n = 99;                                                               \
+        REQUIRE((expr) != nullptr);                                                \
+        REQUIRE(plan.n == 0 && plan.groups == 0 && memcmp(before, st, sizeof(st)) == 0); \
+    } while (0)
+#define ACCEPTED(expr) REQUIRE((expr) == nullptr && plan.n > 0 && memcmp(before, st, sizeof(st)) == 0)
+    ACCEPTED(wm_plan_build(4, st, ids2, off, len, fin, 2, g_in, 0, g_out, n_out, &plan, next));
+    REQUIRE(plan.seg[1].g_off == 1 && plan.groups == 2 && plan.seg[1].out_off == 0 && n_out[0] == 0);
+    // null pointers
+    REFUSED(wm_plan_build(4, nullptr, ids2, off, len, fin, 2, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, nullptr, off, len, fin, 2, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, nullptr, len, fin, 2, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, nullptr, fin, 2, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, nullptr, 2, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, nullptr, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, g_in, 0, nullptr, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, g_in, 0, g_out, nullptr, &plan, next));
+    // the format flag, and a stream that changes its format
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, g_in, -1, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, g_in, 2, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, g_in, 1, g_out, n_out, &plan, next));      // stream 0 has taken fp32
+    ACCEPTED(wm_plan_build(4, st, ids2 + 1, off, len, fin, 1, g_in, 1, g_out, n_out, &plan, next)); // stream 1 is fresh: either format
+    ACCEPTED(wm_plan_build(4, st, ids2 + 1, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    // misaligned buffers
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, (const char*)g_in + 2, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 2, g_in, 0, (char*)g_out + 2, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2 + 1, off, len, fin, 1, (const char*)g_in + 1, 1, g_out, n_out, &plan, next));
+    ACCEPTED(wm_plan_build(4, st, ids2 + 1, off, len, fin, 1, (const char*)g_in + 2, 1, (char*)g_out + 2, n_out, &plan, next));
+    // the id list
+    const int32_t dup[2] = {1, 1}, low[1] = {-1}, high[1] = {4}, last[1] = {3}, zero[1] = {0};
+    REFUSED(wm_plan_build(4, st, dup, off, len, fin, 2, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, low, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, high, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, ids2, off, len, fin, 0, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(1, st, ids2, off, len, fin, 2, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(0, st, zero, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(65, st, zero, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    st[3].t_q4 = 8; st[3].fmt = -1; memcpy(before, st, sizeof(st));
+    ACCEPTED(wm_plan_build(4, st, last, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    ACCEPTED(wm_plan_build(4, st, zero, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    // lengths and offsets
+    long l1[1] = {-1}, o1[1] = {-1}, z[1] = {0};
+    REFUSED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    REFUSED(wm_plan_build(4, st, zero, o1, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    ACCEPTED(wm_plan_build(4, st, zero, z, z, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    l1[0] = WM_MAX_CHUNK + 1;
+    REFUSED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    l1[0] = WM_MAX_CHUNK;
+    ACCEPTED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    REQUIRE(plan.seg[0].nb == (777 + WM_MAX_CHUNK) / WM_S && plan.groups == plan.seg[0].nb + 1);
+    st[0].R = WM_MAX_TOTAL - 4; st[0].given = st[0].R / WM_S * WM_S; memcpy(before, st, sizeof(st));
+    l1[0] = 5;
+    REFUSED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    l1[0] = 4;
+    ACCEPTED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+    // reset: t_q4 at 0 / 1 / 64 / 65, null pointers, ids
+    int32_t t[1] = {0};
+#define RESET_REFUSED(expr) REQUIRE((expr) != nullptr && memcmp(before, st, sizeof(st)) == 0)
+    RESET_REFUSED(wm_reset(4, st, zero, kPayload, t, 1));
+    t[0] = 65; RESET_REFUSED(wm_reset(4, st, zero, kPayload, t, 1));
+    t[0] = -3; RESET_REFUSED(wm_reset(4, st, zero, kPayload, t, 1));
+    t[0] = 8;
+    RESET_REFUSED(wm_reset(4, nullptr, zero, kPayload, t, 1));
+    RESET_REFUSED(wm_reset(4, st, nullptr, kPayload, t, 1));
+    RESET_REFUSED(wm_reset(4, st, zero, nullptr, t, 1));
+    RESET_REFUSED(wm_reset(4, st, zero, kPayload, nullptr, 1));
+    RESET_REFUSED(wm_reset(4, st, high, kPayload, t, 1));
+    RESET_REFUSED(wm_reset(4, st, low, kPayload, t, 1));
+    RESET_REFUSED(wm_reset(4, st, dup, pay2, tq2, 2));
+    RESET_REFUSED(wm_reset(4, st, zero, kPayload, t, 0));
+    const int32_t bad2[2] = {8, 65};                                       // the second of two is bad: the first does not move either
+    RESET_REFUSED(wm_reset(4, st, ids2, pay2, bad2, 2));
+    t[0] = 1; REQUIRE(wm_reset(4, st, zero, kPayload, t, 1) == nullptr && st[0].t_q4 == 1 && st[0].R == 0 && st[0].fmt == -1);
+    t[0] = 64; REQUIRE(wm_reset(4, st, zero, kPayload, t, 1) == nullptr && st[0].t_q4 == 64);
+    // a stream whose t_q4 was never set is not planned
+    st[2].t_q4 = 0; memcpy(before, st, sizeof(st));
+    const int32_t two[1] = {2};
+    REFUSED(wm_plan_build(4, st, two, off, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
+}
+
+static void check_detect_plan() {
+    WmDetectPlan plan;
+    long off[64], len[64], o0[64], n_off[64];
+    uint64_t ex[64], mk[64];
+    for (int i = 0; i < 64; ++i) { off[i] = 10 * i; len[i] = 10; o0[i] = i; n_off[i] = 255 + i % 3; ex[i] = wm_symbol_bits(kPayload); mk[i] = WM_ALL; }
+#define D_REFUSED(expr)                                                            \
+    do {                                                                           \
+        plan.n = 99;                                                               \
+        REQUIRE((expr) != nullptr && plan.n == 0 && plan.tiles == 0);              \
+    } while (0)
+#define D_ACCEPTED(expr) REQUIRE((expr) == nullptr && plan.n > 0)
+    D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 64, g_in, 0, g_scores, g_rows, &plan));
+    int s = 0, t = 0;
+    for (int i = 0; i < 64; ++i) {
+        REQUIRE(plan.clip[i].s_off == s && plan.clip[i].t_off == t && plan.clip[i].o0 == i && plan.clip[i].n_in == 10 && plan.clip[i].in_off == 10 * i);
+        s += (int)n_off[i]; t += n_off[i] <= 256 ? 1 : 2;
+    }
+    REQUIRE(plan.tiles == t && plan.n == 64);
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 65, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 0, g_in, 0, g_scores, g_rows, &plan));
+    D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(nullptr, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, nullptr, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, nullptr, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, nullptr, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, nullptr, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, nullptr, 1, g_in, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, nullptr, 0, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, nullptr, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, nullptr, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 2, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, (const char*)g_in + 2, 0, g_scores, g_rows, &plan));
+    D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, (const char*)g_in + 2, 1, g_scores, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, (const char*)g_scores + 2, g_rows, &plan));
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, (const char*)g_rows + 4, &plan));
+    len[0] = -1; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    len[0] = 0; D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    len[0] = WM_MAX_CLIP + 1; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    len[0] = WM_MAX_CLIP; D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    len[0] = 10;
+    off[0] = -1; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    off[0] = 0;
+    o0[0] = -1; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    o0[0] = WM_P + 7; D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    REQUIRE(plan.clip[0].o0 == 7);                                         // o0 is not restricted: it is taken modulo the period
+    o0[0] = 0;
+    n_off[0] = 0; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    n_off[0] = 1; D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    n_off[0] = WM_MAX_OFFSETS; D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    REQUIRE(plan.tiles == WM_MAX_OFFSETS / WM_TILE);
+    n_off[0] = WM_MAX_OFFSETS + 1; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    n_off[0] = WM_MAX_OFFSETS; n_off[1] = 1;                               // the sum counts
+    D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 2, g_in, 0, g_scores, g_rows, &plan));
+    n_off[0] = WM_MAX_OFFSETS - 1; D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 2, g_in, 0, g_scores, g_rows, &plan));
+    n_off[0] = 4;
+    mk[0] = WM_ALL + 1; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    mk[0] = 0xFF; ex[0] = 1ULL << 56; D_REFUSED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+    ex[0] = WM_ALL; D_ACCEPTED(wm_detect_plan(off, len, o0, n_off, ex, mk, 1, g_in, 0, g_scores, g_rows, &plan));
+}
+
+static void check_symbols() {
+    REQUIRE(wm_crc8(kPayload, 5) == 74);
+    const uint64_t w = wm_symbol_bits(kPayload);
+    REQUIRE((w & ~WM_ALL) == 0);
+    const uint8_t want[7] = {0xB2, 212, 211, 146, 56, 201, 74};
+    for (int j = 0; j < 7; ++j)
+        for (int i = 0; i < 8; ++i) REQUIRE(((w >> (8 * j + i)) & 1) == (uint64_t)((want[j] >> (7 - i)) & 1));
+}
+
+int main() {
+    check_counts();
+    check_long_walk();
+    check_feed_refusals();
+    check_detect_plan();
+    check_symbols();
+    if (g_checks < 1000) { printf("only %d checks ran\n", g_checks); return 1; }
+    printf("ok\n");
+    return 0;
+}
