@@ -1,6 +1,7 @@
 // Shared device helpers for the gfx950 kernels (wave64, bf16 storage, fp32 math).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 #include "rag_segs.h"                                                 // RagSegs: the segment table of a ragged group prefill
 
@@ -117,6 +118,31 @@ __device__ __forceinline__ int wave_max_i(int v) {
     v = max(v, dpp_i<0x143, 0xC>(v, v));
     return __builtin_amdgcn_readlane(v, 63);
 }
+// integer sum over the wave (exact in any order while it fits 32 bits)
+__device__ __forceinline__ int wave_sum_i(int v) {
+    v += dpp_i<0xB1, 0xF>(0, v);
+    v += dpp_i<0x4E, 0xF>(0, v);
+    v += dpp_i<0x141, 0xF>(0, v);
+    v += dpp_i<0x140, 0xF>(0, v);
+    v += dpp_i<0x142, 0xA>(0, v);
+    v += dpp_i<0x143, 0xC>(0, v);
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+// acc + a.lo * b.lo + a.hi * b.hi on two packed int16 pairs (v_dot2_i32_i16)
+typedef short short2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int dot2_i16(uint32_t a, uint32_t b, int acc) {
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, a), __builtin_bit_cast(short2_t, b), acc, false);
+}
+
+// clamp(rint(x * scale), lo, hi) for integer bounds (clamp and rint commute then); a non-finite sample gives 0
+__device__ __forceinline__ int quant_i16(float x, float scale, float lo, float hi) {
+    if (!(fabsf(x) <= FLT_MAX)) return 0;
+    return (int)rintf(fminf(fmaxf(x * scale, lo), hi));
+}
+// an fp32 sample as the int16 it stands for: clamp(rint(x * 32768), -32768, 32767)
+__device__ __forceinline__ int pcm_i16(float x) { return quant_i16(x, 32768.0f, -32768.0f, 32767.0f); }
+
 // exclusive prefix sum over the wave of a small non-negative count (< 2^BITS per lane), bit-sliced: one ballot and one
 // mbcnt per bit, no LDS round trips (a __shfl_up scan is six ds_bpermute)
 template <int BITS>

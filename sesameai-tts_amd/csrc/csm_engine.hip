@@ -33,11 +33,8 @@
 
 static thread_local std::string g_create_err;
 
-// THE binding of the handle's device-memory owner (dev_pool.h) to HIP.  One rule for this file: after a failed allocation or fill, HIP's
-// last-error word is read and discarded before returning, so the next launch check of the process does not trip over it.
-static const DevBackend HIP_BACKEND = {[](void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }, [](void* p) { return (int)hipFree(p); },
-                                       [](void* p, int byte, size_t bytes) { return (int)hipMemset(p, byte, bytes); }};
-const DevBackend* hip_backend() { return &HIP_BACKEND; }
+// The handle's device-memory owner (dev_pool.h) is bound to HIP in hip_backend.h.  One rule for this file: after a failed allocation or
+// fill, HIP's last-error word is read and discarded before returning, so the next launch check of the process does not trip over it.
 
 // every captured frame step is dropped (the next csm_frame_step of each key captures again): the step's node list changed
 static void drop_frame_graphs(CsmModel* m) {

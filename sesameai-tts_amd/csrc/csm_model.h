@@ -10,7 +10,7 @@
 
 #include "../../include/csm_hip.h"
 #include "common.cuh"
-#include "dev_pool.h"
+#include "hip_backend.h"            /* dev_pool.h and its binding to HIP */
 
 #define CSM_LOCAL __attribute__((visibility("hidden")))       /* crosses translation units, stays out of the library's dynamic symbol table */
 
@@ -32,8 +32,6 @@ struct Stack {
     CsmLayerWeights pk8[CSM_MAX_LAYERS];  // the same for the e4m3 weight stream (k_pack_w8); valid when has_pk8
     bool has_pk8 = false;
 };
-
-CSM_LOCAL const DevBackend* hip_backend();         // the binding of the handle's device-memory owner (dev_pool.h) to HIP: csm_engine.hip
 
 // The two K/V stores' state in the handle (csm_kv_store.hip owns it: nothing else reads inside)
 class SessionPages;

@@ -1,5 +1,5 @@
 // The device allocations of ONE owner, each freed exactly once.  No HIP here: the allocate / free / fill functions are the user's
-// (csm_engine.hip binds them to hipMalloc / hipFree / hipMemset in one place; tools/dev_pool_check.cpp drives the pool on the CPU with a
+// (hip_backend.h binds them to hipMalloc / hipFree / hipMemset in one place; tools/dev_pool_check.cpp drives the pool on the CPU with a
 // counting fake).  Status 0 = success.  An optional block is abandoned as a unit: mark(), then release_to(mark).
 #pragma once
 #include <stddef.h>

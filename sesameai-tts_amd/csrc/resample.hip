@@ -10,26 +10,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
 #include <vector>
 
 #include "../../include/mimi_hip.h"
 #include "resample_plan.h"
+#include "stream_pool.cuh"
 
 static_assert(MIMI_RS_MAX_STREAMS == RS_MAX_STREAMS, "header and plan disagree");
 static_assert(sizeof(RsPlan) <= 3200, "the plan must fit the kernel arguments");
 
-struct MimiResamplePool {
+struct MimiResamplePool : SpPool<RsStream> {
     RsRates r{};
-    int n_streams = 0;
-    RsStream st[RS_MAX_STREAMS] = {};
     std::vector<float> taps;         // float32(h), as the device holds them
     float* taps_dev = nullptr;       // [2 * half + 1]
     float* hist_dev = nullptr;       // [n_streams][2 banks][hist]
-    std::string err;
 };
-
-static thread_local std::string g_rs_err;
 
 __device__ __forceinline__ long rs_fdiv(long a, int b) { long q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; }     // b > 0
 
@@ -80,45 +75,25 @@ __global__ void __launch_bounds__(RS_BLOCK) k_rs_feed(const RsPlan plan, const f
     rs_store<OFMT>(out, g.out_off + j, acc);
 }
 
-#define RS_HIP(p, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) { (p)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } \
-    } while (0)
-
 extern "C" int mimi_rs_pool_create(int src_rate, int dst_rate, int n_streams, mimi_rs_pool* out) {
-    if (!out) { g_rs_err = "null pointer"; return -1; }
-    *out = nullptr;
     RsRates r;
-    if (const char* bad = rs_rates(src_rate, dst_rate, &r)) { g_rs_err = bad; return -1; }
-    if (n_streams < 1 || n_streams > RS_MAX_STREAMS) { g_rs_err = "pool outside 1 .. 64 streams"; return -1; }
-    MimiResamplePool* p = new MimiResamplePool();
-    p->r = r; p->n_streams = n_streams;
-    const std::vector<double> h = rs_taps(r);
-    p->taps.resize(h.size());
-    for (size_t i = 0; i < h.size(); ++i) p->taps[i] = (float)h[i];                   // rounded once
-    const size_t hist_bytes = sizeof(float) * 2 * (size_t)r.hist * n_streams;
-    hipError_t e = hipMalloc((void**)&p->taps_dev, sizeof(float) * p->taps.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&p->hist_dev, hist_bytes);
-    if (e == hipSuccess) e = hipMemcpy(p->taps_dev, p->taps.data(), sizeof(float) * p->taps.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(p->hist_dev, 0, hist_bytes);
-    if (e != hipSuccess) {
-        g_rs_err = std::string("mimi_rs_pool_create: ") + hipGetErrorString(e);
-        mimi_rs_pool_destroy(p);
-        return -2;
-    }
-    *out = p;
-    return 0;
+    const char* bad = rs_rates(src_rate, dst_rate, &r);
+    return sp_create("mimi_rs_pool_create", n_streams, out, bad, [&](MimiResamplePool* p) {
+        p->r = r;
+        const std::vector<double> h = rs_taps(r);
+        p->taps.resize(h.size());
+        for (size_t i = 0; i < h.size(); ++i) p->taps[i] = (float)h[i];               // rounded once
+        const size_t taps_bytes = sizeof(float) * p->taps.size();
+        hipError_t e = p->get(&p->taps_dev, taps_bytes);
+        if (e == hipSuccess) e = p->get(&p->hist_dev, sizeof(float) * 2 * (size_t)r.hist * n_streams, 0);
+        if (e == hipSuccess) e = hipMemcpy(p->taps_dev, p->taps.data(), taps_bytes, hipMemcpyHostToDevice);
+        return e;
+    });
 }
 
-extern "C" void mimi_rs_pool_destroy(mimi_rs_pool p) {
-    if (!p) return;
-    if (p->taps_dev) (void)hipFree(p->taps_dev);
-    if (p->hist_dev) (void)hipFree(p->hist_dev);
-    delete p;
-}
+extern "C" void mimi_rs_pool_destroy(mimi_rs_pool p) { delete p; }
 
-extern "C" const char* mimi_rs_pool_last_error(mimi_rs_pool p) { return p ? p->err.c_str() : g_rs_err.c_str(); }
+extern "C" const char* mimi_rs_pool_last_error(mimi_rs_pool p) { return sp_last_error(p); }
 
 extern "C" int mimi_rs_pool_taps(mimi_rs_pool p, float* host_out, int* up, int* down, int* half) {
     if (!p) return -1;
@@ -130,31 +105,20 @@ extern "C" int mimi_rs_pool_taps(mimi_rs_pool p, float* host_out, int* up, int* 
 }
 
 extern "C" long mimi_rs_pool_out_count(mimi_rs_pool p, int sid, long n_in, int final) {
-    if (!p) return -1;
-    if (sid < 0 || sid >= p->n_streams) { p->err = "stream id outside [0, n_streams)"; return -1; }
-    if (n_in < 0 || n_in > RS_MAX_CHUNK) { p->err = "a chunk of negative length or of more than 2^30 samples"; return -1; }
-    return rs_emitted(p->r, p->st[sid].n_in, p->st[sid].n_out, n_in, final != 0) - p->st[sid].n_out;
+    return sp_count_ok(p, sid, n_in) ? rs_emitted(p->r, p->st[sid].n_in, p->st[sid].n_out, n_in, final != 0) - p->st[sid].n_out : -1;
 }
 
 extern "C" int mimi_rs_pool_reset(mimi_rs_pool p, const int32_t* streams, int n) {
-    if (!p) return -1;
-    if (!streams) { p->err = "null pointer"; return -1; }
-    if (n < 1 || n > p->n_streams) { p->err = "stream list: need 1 .. n_streams ids"; return -1; }
-    for (int i = 0; i < n; ++i)
-        if (streams[i] < 0 || streams[i] >= p->n_streams) { p->err = "stream id outside [0, n_streams)"; return -1; }
-    for (int i = 0; i < n; ++i) { RsStream& s = p->st[streams[i]]; s.n_in = s.n_out = s.k0 = 0; }      // (the bank stays: nothing of it is read)
-    return 0;
+    return p ? sp_status(p, rs_reset(p->n_streams, p->st, streams, n)) : -1;
 }
 
 extern "C" int mimi_rs_pool_feed(mimi_rs_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
                                  const void* in, int in_fmt, void* out, int out_fmt, long* n_out, void* stream) {
     if (!p) return -1;
     RsPlan plan;
-    RsStream next[RS_MAX_STREAMS];
-    if (const char* bad = rs_plan_build(p->r, p->n_streams, p->st, streams, in_off, n_in, final, n, in, in_fmt, out, out_fmt, n_out, &plan, next)) {
-        p->err = bad;
-        return -1;
-    }
+    RsStream next[SP_MAX_STREAMS];
+    if (int rc = sp_status(p, rs_plan_build(p->r, p->n_streams, p->st, streams, in_off, n_in, final, n, in, in_fmt, out, out_fmt, n_out, &plan, next)))
+        return rc;
     const dim3 grid((unsigned)(plan.blocks + plan.n)), block(RS_BLOCK);
     hipStream_t s = (hipStream_t)stream;
     const RsRates& r = p->r;
@@ -163,7 +127,7 @@ extern "C" int mimi_rs_pool_feed(mimi_rs_pool p, const int32_t* streams, const l
     else if (in_fmt == 0) k_rs_feed<0, 1><<<grid, block, 0, s>>>(plan, p->taps_dev, p->hist_dev, in, out, r.up, r.down, r.half, r.hist);
     else if (out_fmt == 0) k_rs_feed<1, 0><<<grid, block, 0, s>>>(plan, p->taps_dev, p->hist_dev, in, out, r.up, r.down, r.half, r.hist);
     else k_rs_feed<1, 1><<<grid, block, 0, s>>>(plan, p->taps_dev, p->hist_dev, in, out, r.up, r.down, r.half, r.hist);
-    RS_HIP(p, hipGetLastError());
-    for (int i = 0; i < n; ++i) p->st[streams[i]] = next[i];
+    SP_HIP(p, hipGetLastError());
+    sp_commit(p->st, streams, next, n);
     return 0;
 }

@@ -15,9 +15,11 @@
 #include <cmath>
 #include <vector>
 
+#include "stream_pool.h"
+
 #define RS_MAX_STREAMS 64           // = MIMI_RS_MAX_STREAMS
+static_assert(RS_MAX_STREAMS == SP_MAX_STREAMS, "the pools share one spine");
 #define RS_MAX_FACTOR 320           // the largest reduced up or down mimi_rs_pool_create takes
-#define RS_MAX_CHUNK (1L << 30)     // samples one stream takes, or gives, in one call (grid and index arithmetic stay inside 32 bits)
 #define RS_BLOCK 256                // outputs per block
 
 struct RsRates { int up, down, half, hist; };      // hist = 2 * half / up + 1: the samples in front of a call's first that its outputs can reach
@@ -80,6 +82,14 @@ static inline long rs_emitted(const RsRates& r, long n_in, long n_out, long more
     return e > n_out ? e : n_out;
 }
 
+// nullptr, or why the reset is refused (then no state has moved).  An id may come twice: resetting a stream twice is resetting it.
+static inline const char* rs_reset(int n_streams, RsStream* st, const int32_t* streams, int n) {
+    if (!st || !streams) return "null pointer";
+    if (const char* bad = sp_ids_bad(n_streams, streams, n, true)) return bad;
+    for (int i = 0; i < n; ++i) { RsStream& s = st[streams[i]]; s.n_in = s.n_out = s.k0 = 0; }      // (the bank stays: nothing of it is read)
+    return nullptr;
+}
+
 // Fills `plan` and `next` (the listed streams' states after the call; commit them once the launch is made) from the caller's host arrays.
 // Returns nullptr, or what is wrong (plan->n == 0 then: nothing may be launched, no state may move).
 static inline const char* rs_plan_build(const RsRates& r, int n_streams, const RsStream* st, const int32_t* streams, const long* in_off, const long* n_in,
@@ -89,18 +99,11 @@ static inline const char* rs_plan_build(const RsRates& r, int n_streams, const R
     if (!st || !streams || !in_off || !n_in || !final || !in || !out || !n_out) return "null pointer";
     if (in_fmt != 0 && in_fmt != 1) return "unknown input format (0 = fp32, 1 = int16)";
     if (out_fmt != 0 && out_fmt != 1) return "unknown output format (0 = fp32, 1 = int16)";
-    if (n_streams < 1 || n_streams > RS_MAX_STREAMS) return "pool outside 1 .. 64 streams";
-    if (n < 1 || n > n_streams) return "stream list: need 1 .. n_streams ids";
-    bool seen[RS_MAX_STREAMS] = {};
+    if (const char* bad = sp_ids_bad(n_streams, streams, n)) return bad;
     for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= n_streams) return "stream id outside [0, n_streams)";
-        if (seen[s]) return "duplicate stream id in one call";
-        seen[s] = true;
-        if (n_in[i] < 0) return "a chunk of negative length";
-        if (in_off[i] < 0) return "a chunk at a negative offset";
-        if (n_in[i] > RS_MAX_CHUNK) return "a chunk of more than 2^30 samples";
-        if (rs_emitted(r, st[s].n_in, st[s].n_out, n_in[i], final[i] != 0) - st[s].n_out > RS_MAX_CHUNK) return "a chunk that gives more than 2^30 samples";
+        const RsStream& s = st[streams[i]];
+        if (const char* bad = sp_chunk_bad(n_in[i], in_off[i], 0)) return bad;        // (the totals are reduced: they never reach 2^48)
+        if (rs_emitted(r, s.n_in, s.n_out, n_in[i], final[i] != 0) - s.n_out > SP_MAX_CHUNK) return "a chunk that gives more than 2^30 samples";
     }
     long O = 0;
     int blocks = 0;
@@ -126,7 +129,7 @@ static inline const char* rs_plan_build(const RsRates& r, int n_streams, const R
         }
         t.bank = s.bank ^ 1;                                            // the call wrote the other bank
     }
-    for (int i = n; i < RS_MAX_STREAMS; ++i) plan->seg[i] = RsSeg{};
+    sp_zero_tail(plan->seg, n);
     plan->n = n; plan->blocks = blocks;
     return nullptr;
 }

@@ -10,13 +10,10 @@
 // candidate is one dot2 per thread and a sum.  A score is an exact integer below 2^31 in any order, so the argmax -- score descending,
 // candidate ascending -- is the rule's, bit for bit.  The crossfade is two fp32 multiplies and an fp32 add, never fused.
 #include <hip/hip_runtime.h>
-#include <float.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/mimi_hip.h"
-#include "common.cuh"
+#include "stream_pool.cuh"
 #include "stretch_plan.h"
 
 #pragma clang fp contract(off)
@@ -27,37 +24,13 @@ static_assert(TS_H == 512 && TS_D == 256, "k_ts_feed: 256 threads, two candidate
 
 #define TS_THREADS 256
 
-struct MimiStretchPool {
-    int n_streams = 0;
-    TsStream st[TS_MAX_STREAMS] = {};
+struct MimiStretchPool : SpPool<TsStream> {
     float* carry_dev = nullptr;      // [n_streams][2 banks][TS_CARRY]
     int* c_dev = nullptr;            // [n_streams]: c of the stream's last block, relative to the base of its next call
-    std::string err;
 };
 
-static thread_local std::string g_ts_err;
-
-typedef short ts_short2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int ts_dot2(uint32_t a, uint32_t b, int acc) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(ts_short2, a), __builtin_bit_cast(ts_short2, b), acc, false);
-}
-
-__device__ __forceinline__ int ts_wave_sum_i(int v) {
-    v += dpp_i<0xB1, 0xF>(0, v);
-    v += dpp_i<0x4E, 0xF>(0, v);
-    v += dpp_i<0x141, 0xF>(0, v);
-    v += dpp_i<0x140, 0xF>(0, v);
-    v += dpp_i<0x142, 0xA>(0, v);
-    v += dpp_i<0x143, 0xC>(0, v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// q = clamp(rint(x * 2048), -2047, 2047); a non-finite sample gives 0
-__device__ __forceinline__ int ts_quant(float x) {
-    if (!(fabsf(x) <= FLT_MAX)) return 0;
-    return (int)rintf(fminf(fmaxf(x * 2048.0f, -2047.0f), 2047.0f));                  // (the bounds are integers: clamp and rint commute)
-}
+// the 12-bit search samples: q = clamp(rint(x * 2048), -2047, 2047)
+__device__ __forceinline__ int ts_quant(float x) { return quant_i16(x, 2048.0f, -2047.0f, 2047.0f); }
 __device__ __forceinline__ uint32_t ts_pack(float x0, float x1) {
     return (uint32_t)(ts_quant(x0) & 0xFFFF) | ((uint32_t)ts_quant(x1) << 16);
 }
@@ -86,8 +59,8 @@ __global__ void __launch_bounds__(TS_THREADS) k_ts_feed(const TsPlan plan, float
     __shared__ int red_s[4], red_e[4], red_x[4];
     const TsSeg& g = plan.seg[blockIdx.x];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int sid = TS_SID(g), L = g.L < TS_CARRY ? g.L : TS_CARRY, n_in = g.n_in, n_out = g.n_out, pm = TS_PM(g);
-    const float* old = carry + ((long)sid * 2 + TS_PARITY(g)) * TS_CARRY;
+    const int sid = SP_SID(g), L = g.L < TS_CARRY ? g.L : TS_CARRY, n_in = g.n_in, n_out = g.n_out, pm = TS_PM(g);
+    const float* old = carry + ((long)sid * 2 + SP_PARITY(g)) * TS_CARRY;
     const float* in = in_all + g.in_off;
     float* out = out_all + g.out_off;
     const int nb = (n_out + TS_H - 1) / TS_H;
@@ -124,15 +97,15 @@ __global__ void __launch_bounds__(TS_THREADS) k_ts_feed(const TsPlan plan, float
         for (int m = 0; m < TS_H / 2; ++m) {
             const uint32_t nxt = qr[t + m + 1 < TS_H ? t + m + 1 : TS_H - 1];         // (t + m + 1 <= 511 always; the clamp keeps the read provably inside)
             const uint32_t tq = qt[m];
-            s0 = ts_dot2(cur, tq, s0);
-            s1 = ts_dot2(__builtin_amdgcn_alignbit(nxt, cur, 16), tq, s1);
+            s0 = dot2_i16(cur, tq, s0);
+            s1 = dot2_i16(__builtin_amdgcn_alignbit(nxt, cur, 16), tq, s1);
             cur = nxt;
         }
         int s = s0, e = 2 * t;
         if (s1 > s0) { s = s1; e = 2 * t + 1; }
         const int wm = wave_max_i(s);
         const int we = wave_min_i(s == wm ? e : 0x7FFFFFFF);
-        const int px = ts_wave_sum_i(ts_dot2(qr[TS_H / 2 + t], qt[t], 0));            // candidate 512, a 256th of it per thread
+        const int px = wave_sum_i(dot2_i16(qr[TS_H / 2 + t], qt[t], 0));            // candidate 512, a 256th of it per thread
         if (lane == 0) { red_s[w] = wm; red_e[w] = we; red_x[w] = px; }
         __syncthreads();
         int best = red_s[0], be = red_e[0];
@@ -149,76 +122,45 @@ __global__ void __launch_bounds__(TS_THREADS) k_ts_feed(const TsPlan plan, float
         if (o + j0 < n_out) out[o + j0] = y0;
         if (o + j1 < n_out) out[o + j1] = y1;
     }
-    if (TS_FINAL(g)) return;                                                          // the stream is fresh: it reads neither carry nor c
+    if (SP_FINAL(g)) return;                                                          // the stream is fresh: it reads neither carry nor c
     // the samples from the next call's base on, into the bank this call did not read
-    float* nw = carry + ((long)sid * 2 + (TS_PARITY(g) ^ 1)) * TS_CARRY;
+    float* nw = carry + ((long)sid * 2 + (SP_PARITY(g) ^ 1)) * TS_CARRY;
     int Ln = L + n_in - g.shift;
     Ln = Ln < TS_CARRY ? Ln : TS_CARRY;
     for (int p = t; p < Ln; p += TS_THREADS) nw[p] = ts_x(old, L, in, n_in, g.shift + p);
     if (t == 0) cpos[sid] = c - g.shift;
 }
 
-#define TS_HIP(p, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) { (p)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } \
-    } while (0)
-
 extern "C" int mimi_ts_pool_create(int n_streams, mimi_ts_pool* out) {
-    if (!out) { g_ts_err = "null pointer"; return -1; }
-    *out = nullptr;
-    if (n_streams < 1 || n_streams > TS_MAX_STREAMS) { g_ts_err = "pool outside 1 .. 64 streams"; return -1; }
-    MimiStretchPool* p = new MimiStretchPool();
-    p->n_streams = n_streams;
-    for (int i = 0; i < n_streams; ++i) p->st[i].pm = 1000;
-    const size_t carry_bytes = sizeof(float) * 2 * TS_CARRY * (size_t)n_streams;
-    hipError_t e = hipMalloc((void**)&p->carry_dev, carry_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->c_dev, sizeof(int) * n_streams);
-    if (e == hipSuccess) e = hipMemset(p->carry_dev, 0, carry_bytes);
-    if (e == hipSuccess) e = hipMemset(p->c_dev, 0, sizeof(int) * n_streams);
-    if (e != hipSuccess) {
-        g_ts_err = std::string("mimi_ts_pool_create: ") + hipGetErrorString(e);
-        mimi_ts_pool_destroy(p);
-        return -2;
-    }
-    *out = p;
-    return 0;
+    return sp_create("mimi_ts_pool_create", n_streams, out, nullptr, [&](MimiStretchPool* p) {
+        for (int i = 0; i < n_streams; ++i) p->st[i].pm = 1000;
+        hipError_t e = p->get(&p->carry_dev, sizeof(float) * 2 * TS_CARRY * (size_t)n_streams, 0);
+        if (e == hipSuccess) e = p->get(&p->c_dev, sizeof(int) * n_streams, 0);
+        return e;
+    });
 }
 
-extern "C" void mimi_ts_pool_destroy(mimi_ts_pool p) {
-    if (!p) return;
-    if (p->carry_dev) (void)hipFree(p->carry_dev);
-    if (p->c_dev) (void)hipFree(p->c_dev);
-    delete p;
-}
+extern "C" void mimi_ts_pool_destroy(mimi_ts_pool p) { delete p; }
 
-extern "C" const char* mimi_ts_pool_last_error(mimi_ts_pool p) { return p ? p->err.c_str() : g_ts_err.c_str(); }
+extern "C" const char* mimi_ts_pool_last_error(mimi_ts_pool p) { return sp_last_error(p); }
 
 extern "C" int mimi_ts_pool_reset(mimi_ts_pool p, const int32_t* streams, const int32_t* speed_pm, int n) {
-    if (!p) return -1;
-    if (const char* bad = ts_reset(p->n_streams, p->st, streams, speed_pm, n)) { p->err = bad; return -1; }
-    return 0;
+    return p ? sp_status(p, ts_reset(p->n_streams, p->st, streams, speed_pm, n)) : -1;
 }
 
 extern "C" long mimi_ts_pool_out_count(mimi_ts_pool p, int sid, long n_in, int final) {
-    if (!p) return -1;
-    if (sid < 0 || sid >= p->n_streams) { p->err = "stream id outside [0, n_streams)"; return -1; }
-    if (n_in < 0 || n_in > TS_MAX_CHUNK) { p->err = "a chunk of negative length or of more than 2^30 samples"; return -1; }
-    return ts_out_count(p->st[sid], n_in, final != 0);
+    return sp_count_ok(p, sid, n_in) ? ts_out_count(p->st[sid], n_in, final != 0) : -1;
 }
 
 extern "C" int mimi_ts_pool_feed(mimi_ts_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
                                  const float* in, float* out, long* n_out, int32_t* d_out, void* stream) {
     if (!p) return -1;
     TsPlan plan;
-    TsStream next[TS_MAX_STREAMS];
-    if (const char* bad = ts_plan_build(p->n_streams, p->st, streams, in_off, n_in, final, n, in, out, n_out, &plan, next)) {
-        p->err = bad;
-        return -1;
-    }
+    TsStream next[SP_MAX_STREAMS];
+    if (int rc = sp_status(p, ts_plan_build(p->n_streams, p->st, streams, in_off, n_in, final, n, in, out, n_out, &plan, next))) return rc;
     (void)hipGetLastError();
     k_ts_feed<<<dim3((unsigned)plan.n), dim3(TS_THREADS), 0, (hipStream_t)stream>>>(plan, p->carry_dev, p->c_dev, in, out, d_out);
-    TS_HIP(p, hipGetLastError());
-    for (int i = 0; i < n; ++i) p->st[streams[i]] = next[i];
+    SP_HIP(p, hipGetLastError());
+    sp_commit(p->st, streams, next, n);
     return 0;
 }

@@ -9,28 +9,26 @@
 #pragma once
 #include <stdint.h>
 
+#include "stream_pool.h"
+
 #define TS_MAX_STREAMS 64           // = MIMI_TS_MAX_STREAMS
+static_assert(TS_MAX_STREAMS == SP_MAX_STREAMS, "the pools share one spine");
 #define TS_H 512                    // block and hop
 #define TS_D 256                    // search radius
 #define TS_LOOK (TS_D + 2 * TS_H)   // block k comes out once a_k + TS_LOOK samples are in
 #define TS_CARRY 2560               // floats a stream keeps between calls (the most it needs is 2,559)
 #define TS_PM_MIN 500
 #define TS_PM_MAX 2000
-#define TS_MAX_CHUNK (1L << 30)     // samples one stream takes, or gives, in one call
-#define TS_MAX_TOTAL (1L << 48)     // samples one stream takes between two resets (k H pm stays inside 63 bits)
 
 // One listed stream of one call, as the kernel gets it: 48 bytes.
 struct TsSeg {
     long in_off, out_off;           // elements: its new samples in `in`, its outputs in `out`
-    int sid;                        // | parity << 8 (the carry bank the call READS; it writes the other) | final << 9 | fresh << 10 (k0 == 0)
+    int sid;                        // sp_sid_word | fresh << 10 (k0 == 0)
     int L, n_in, n_out;             // carry samples; new samples; outputs (ceil(n_out / H) blocks, only a final's last one cut)
     int a0, rem;                    // a_k0 - base and (k0 H pm) % 1000: a_(k0+i) - base = a0 + (rem + i H pm) / 1000;  rem | pm << 10
     int shift;                      // base of the stream's next call - base of this one: the new carry is positions [shift, L + n_in)
     int blk_off;                    // its blocks' place in d_out
 };
-#define TS_SID(g) ((g).sid & 0xFF)
-#define TS_PARITY(g) (((g).sid >> 8) & 1)
-#define TS_FINAL(g) (((g).sid >> 9) & 1)
 #define TS_FRESH(g) (((g).sid >> 10) & 1)
 #define TS_REM(g) ((g).rem & 0x3FF)
 #define TS_PM(g) ((g).rem >> 10)
@@ -42,7 +40,7 @@ struct TsPlan {
 
 struct TsStream { long R, k; int pm, parity; };     // samples taken and blocks emitted since the reset; speed; the bank that holds the carry
 
-static inline long ts_a(long k, int pm) { return k * TS_H * pm / 1000; }                                  // k <= 2^41: inside 63 bits
+static inline long ts_a(long k, int pm) { return k * TS_H * pm / 1000; }                                  // k <= 2^41 (SP_MAX_TOTAL samples): inside 63 bits
 static inline long ts_base(long k, int pm) { const long b = k >= 1 ? ts_a(k - 1, pm) - TS_D : 0; return b > 0 ? b : 0; }
 static inline long ts_out_len(long N, int pm) { return (N * 1000 + pm - 1) / pm; }
 
@@ -62,16 +60,9 @@ static inline long ts_out_count(const TsStream& s, long more, int final) {
 // nullptr, or why the reset is refused (then no state has moved)
 static inline const char* ts_reset(int n_streams, TsStream* st, const int32_t* streams, const int32_t* speed_pm, int n) {
     if (!st || !streams || !speed_pm) return "null pointer";
-    if (n_streams < 1 || n_streams > TS_MAX_STREAMS) return "pool outside 1 .. 64 streams";
-    if (n < 1 || n > n_streams) return "stream list: need 1 .. n_streams ids";
-    bool seen[TS_MAX_STREAMS] = {};
-    for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= n_streams) return "stream id outside [0, n_streams)";
-        if (seen[s]) return "duplicate stream id in one call";
-        seen[s] = true;
+    if (const char* bad = sp_ids_bad(n_streams, streams, n)) return bad;
+    for (int i = 0; i < n; ++i)
         if (speed_pm[i] < TS_PM_MIN || speed_pm[i] > TS_PM_MAX) return "speed outside 500 .. 2000 permille";
-    }
     for (int i = 0; i < n; ++i) { TsStream& s = st[streams[i]]; s.R = 0; s.k = 0; s.pm = speed_pm[i]; }      // (the parity stays: a fresh stream reads no carry)
     return nullptr;
 }
@@ -82,20 +73,12 @@ static inline const char* ts_plan_build(int n_streams, const TsStream* st, const
                                         const int32_t* final, int n, const void* in, const void* out, long* n_out, TsPlan* plan, TsStream* next) {
     plan->n = 0; plan->blocks = 0;
     if (!st || !streams || !in_off || !n_in || !final || !in || !out || !n_out) return "null pointer";
-    if (n_streams < 1 || n_streams > TS_MAX_STREAMS) return "pool outside 1 .. 64 streams";
-    if (n < 1 || n > n_streams) return "stream list: need 1 .. n_streams ids";
-    bool seen[TS_MAX_STREAMS] = {};
+    if (const char* bad = sp_ids_bad(n_streams, streams, n)) return bad;
     for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= n_streams) return "stream id outside [0, n_streams)";
-        if (seen[s]) return "duplicate stream id in one call";
-        seen[s] = true;
-        if (st[s].pm < TS_PM_MIN || st[s].pm > TS_PM_MAX) return "speed outside 500 .. 2000 permille";
-        if (n_in[i] < 0) return "a chunk of negative length";
-        if (in_off[i] < 0) return "a chunk at a negative offset";
-        if (n_in[i] > TS_MAX_CHUNK) return "a chunk of more than 2^30 samples";
-        if (st[s].R + n_in[i] > TS_MAX_TOTAL) return "a stream of more than 2^48 samples";
-        if (ts_out_count(st[s], n_in[i], final[i] != 0) > TS_MAX_CHUNK) return "a chunk that gives more than 2^30 samples";
+        const TsStream& s = st[streams[i]];
+        if (s.pm < TS_PM_MIN || s.pm > TS_PM_MAX) return "speed outside 500 .. 2000 permille";
+        if (const char* bad = sp_chunk_bad(n_in[i], in_off[i], s.R)) return bad;
+        if (ts_out_count(s, n_in[i], final[i] != 0) > SP_MAX_CHUNK) return "a chunk that gives more than 2^30 samples";
     }
     long O = 0;
     int blocks = 0;
@@ -106,7 +89,7 @@ static inline const char* ts_plan_build(int n_streams, const TsStream* st, const
         const long R1 = s.R + n_in[i], k1 = ts_emitted(R1, s.pm, fin), base = ts_base(s.k, s.pm);
         const long cnt = ts_out_count(s, n_in[i], fin);
         g.in_off = in_off[i]; g.out_off = O;
-        g.sid = streams[i] | s.parity << 8 | fin << 9 | (s.k == 0) << 10;
+        g.sid = sp_sid_word(streams[i], s.parity, fin) | (s.k == 0) << 10;
         g.L = (int)(s.R - base); g.n_in = (int)n_in[i]; g.n_out = (int)cnt;
         g.a0 = (int)(ts_a(s.k, s.pm) - base);
         g.rem = (int)(s.k * TS_H * s.pm % 1000) | s.pm << 10;
@@ -120,7 +103,7 @@ static inline const char* ts_plan_build(int n_streams, const TsStream* st, const
         if (fin) { t.R = 0; t.k = 0; }                                // the next sample starts a new clip
         else { t.R = R1; t.k = k1; }
     }
-    for (int i = n; i < TS_MAX_STREAMS; ++i) plan->seg[i] = TsSeg{};
+    sp_zero_tail(plan->seg, n);
     plan->n = n; plan->blocks = blocks;
     return nullptr;
 }

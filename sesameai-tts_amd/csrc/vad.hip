@@ -15,13 +15,10 @@
 // exact like a prefix sum, and it rides in the shadow of the LDS reads.  Every sum is an exact integer below 2^29 in any order; the
 // threshold is compared in 64 bits; "smallest qualifying tau" is a max-reduction over e.
 #include <hip/hip_runtime.h>
-#include <float.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/mimi_hip.h"
-#include "common.cuh"
+#include "stream_pool.cuh"
 #include "vad_plan.h"
 
 static_assert(MIMI_VAD_MAX_STREAMS == VAD_MAX_STREAMS && MIMI_VAD_SUMMARY == VAD_SUMMARY, "header and plan disagree");
@@ -35,38 +32,11 @@ static_assert(VAD_SPAN == 880 && VAD_F == 240 && VAD_TMAX - VAD_TMIN == 340, "k_
 
 struct VadState { long N; int run, since; };      // (in speech and quiet live in the summary)
 
-struct MimiVadPool {
-    int n_streams = 0;
-    VadStream st[VAD_MAX_STREAMS] = {};
+struct MimiVadPool : SpPool<VadStream> {
     int16_t* carry_dev = nullptr;    // [n_streams][2 banks][VAD_CARRY]
     VadState* state_dev = nullptr;   // [n_streams]
     long* summary_dev = nullptr;     // [n_streams][VAD_SUMMARY]
-    std::string err;
 };
-
-static thread_local std::string g_vad_err;
-
-typedef short vad_short2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int vad_dot2(uint32_t a, uint32_t b, int acc) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(vad_short2, a), __builtin_bit_cast(vad_short2, b), acc, false);
-}
-
-__device__ __forceinline__ int vad_wave_sum_i(int v) {
-    v += dpp_i<0xB1, 0xF>(0, v);
-    v += dpp_i<0x4E, 0xF>(0, v);
-    v += dpp_i<0x141, 0xF>(0, v);
-    v += dpp_i<0x140, 0xF>(0, v);
-    v += dpp_i<0x142, 0xA>(0, v);
-    v += dpp_i<0x143, 0xC>(0, v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// s = clamp(rint(x * 32768), -32768, 32767); a non-finite sample gives 0
-__device__ __forceinline__ int vad_quant(float x) {
-    if (!(fabsf(x) <= FLT_MAX)) return 0;
-    return (int)rintf(fminf(fmaxf(x * 32768.0f, -32768.0f), 32767.0f));               // (the bounds are integers: clamp and rint commute)
-}
 
 // integer sample at position p relative to the call's base: `lead` rule zeros, the carry, the new chunk; zero outside
 __device__ __forceinline__ int vad_s(const int16_t* __restrict__ carry, int lead, int Lc, const void* __restrict__ in, long in_off, int n_in,
@@ -76,7 +46,7 @@ __device__ __forceinline__ int vad_s(const int16_t* __restrict__ carry, int lead
     if (p < Lc) return carry[p];
     p -= Lc;
     if (p >= n_in) return 0;
-    return i16 ? (int)((const int16_t*)in)[in_off + p] : vad_quant(((const float*)in)[in_off + p]);
+    return i16 ? (int)((const int16_t*)in)[in_off + p] : pcm_i16(((const float*)in)[in_off + p]);
 }
 
 __global__ void __launch_bounds__(VAD_THREADS) k_vad_features(const VadPlan plan, const int16_t* __restrict__ carry, const void* __restrict__ in,
@@ -85,15 +55,10 @@ __global__ void __launch_bounds__(VAD_THREADS) k_vad_features(const VadPlan plan
     __shared__ int red[4][4];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     // the segment that owns this frame: the last one whose f_off <= blockIdx.x among those with frames
-    int lo = 0, hi = plan.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (plan.seg[mid].f_off <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const VadSeg& g = plan.seg[lo];
+    const VadSeg& g = plan.seg[sp_owner(plan.seg, plan.n, &VadSeg::f_off)];
     const int i = (int)blockIdx.x - g.f_off;
     if (i >= g.nf) return;                                                            // (never: every block below plan.frames lies in a segment)
-    const int16_t* old = carry + ((long)VAD_SID(g) * 2 + VAD_PARITY(g)) * VAD_CARRY;
+    const int16_t* old = carry + ((long)SP_SID(g) * 2 + SP_PARITY(g)) * VAD_CARRY;
     const int lead = VAD_LEAD(g), Lc = g.Lc, n_in = g.n_in, p0 = i * VAD_F;
     // the 880 samples that end with the frame: pairs m = t and t + 256 (m < 440)
     int s[4] = {0, 0, 0, 0};
@@ -115,7 +80,7 @@ __global__ void __launch_bounds__(VAD_THREADS) k_vad_features(const VadPlan plan
         sq_lo = (int)((a & 0x7FFF) + (b & 0x7FFF));
         sq_hi = (int)((a >> 15) + (b >> 15));
     }
-    const int wm = wave_max_i(m_abs), ws1 = vad_wave_sum_i(s1), wlo = vad_wave_sum_i(sq_lo), whi = vad_wave_sum_i(sq_hi);
+    const int wm = wave_max_i(m_abs), ws1 = wave_sum_i(s1), wlo = wave_sum_i(sq_lo), whi = wave_sum_i(sq_hi);
     if (lane == 0) { red[w][0] = wm; red[w][1] = ws1; red[w][2] = wlo; red[w][3] = whi; }
     __syncthreads();
     const int mx = max(max(red[0][0], red[1][0]), max(red[2][0], red[3][0]));
@@ -133,7 +98,7 @@ __global__ void __launch_bounds__(VAD_THREADS) k_vad_features(const VadPlan plan
     __syncthreads();
     // E0 over the window's 240 pairs
     const uint32_t wq = t < VAD_W / 2 ? q[VAD_WIN0 + t] : 0u;
-    const int we0 = vad_wave_sum_i(vad_dot2(wq, wq, 0));
+    const int we0 = wave_sum_i(dot2_i16(wq, wq, 0));
     if (lane == 0) red[w][0] = we0;                                                   // (the maxima there were read before the last barrier)
     // offsets e = 2t and 2t + 1, e <= 340: R_e = sum_j w[j] B[e + j], E_e = sum_j B[e + j]^2
     const bool mine = t <= (VAD_TMAX - VAD_TMIN) / 2;
@@ -145,10 +110,10 @@ __global__ void __launch_bounds__(VAD_THREADS) k_vad_features(const VadPlan plan
             const uint32_t nxt = q[t + m + 1];                                        // t + m + 1 <= 170 + 240 < 440
             const uint32_t wv = q[VAD_WIN0 + m];
             const uint32_t odd = __builtin_amdgcn_alignbit(nxt, cur, 16);
-            r0 = vad_dot2(cur, wv, r0);
-            e0 = vad_dot2(cur, cur, e0);
-            r1 = vad_dot2(odd, wv, r1);
-            e1 = vad_dot2(odd, odd, e1);
+            r0 = dot2_i16(cur, wv, r0);
+            e0 = dot2_i16(cur, cur, e0);
+            r1 = dot2_i16(odd, wv, r1);
+            e1 = dot2_i16(odd, odd, e1);
             cur = nxt;
         }
     }
@@ -173,7 +138,7 @@ __global__ void __launch_bounds__(64) k_vad_scan(const VadPlan plan, int16_t* __
     __shared__ long sp[64];
     __shared__ int sl[64];
     const VadSeg& g = plan.seg[blockIdx.x];
-    const int lane = threadIdx.x, sid = VAD_SID(g), nf = g.nf;
+    const int lane = threadIdx.x, sid = SP_SID(g), nf = g.nf;
     const int on = VAD_ON(g), off = VAD_OFF(g), min_on = VAD_MIN_ON(g), hang = VAD_HANG(g), hold = g.hold;
     const long n_min = g.n_min;
     long* sm = summary + (long)sid * VAD_SUMMARY;
@@ -217,10 +182,10 @@ __global__ void __launch_bounds__(64) k_vad_scan(const VadPlan plan, int16_t* __
         sm[0] = speech; sm[1] = k; sm[2] = last_start; sm[3] = last_end; sm[4] = quiet; sm[5] = n_start; sm[6] = n_end; sm[7] = 0;
         state[sid].N = N; state[sid].run = run; state[sid].since = since;
     }
-    if (VAD_FINAL(g)) return;                                                         // the stream is fresh: it reads no carry
+    if (SP_FINAL(g)) return;                                                         // the stream is fresh: it reads no carry
     // the samples from the next call's base on, into the bank this call did not read
-    const int16_t* old = carry + ((long)sid * 2 + VAD_PARITY(g)) * VAD_CARRY;
-    int16_t* nw = carry + ((long)sid * 2 + (VAD_PARITY(g) ^ 1)) * VAD_CARRY;
+    const int16_t* old = carry + ((long)sid * 2 + SP_PARITY(g)) * VAD_CARRY;
+    int16_t* nw = carry + ((long)sid * 2 + (SP_PARITY(g) ^ 1)) * VAD_CARRY;
     const int lead = VAD_LEAD(g), Lc = g.Lc, n_in = g.n_in;
     const long k1 = g.k0 + nf;
     const int lead1 = k1 < 3 ? VAD_HIST - (int)k1 * VAD_F : 0;
@@ -239,57 +204,27 @@ __global__ void __launch_bounds__(64) k_vad_summary(unsigned long long fresh, in
     for (int j = 0; j < VAD_SUMMARY; ++j) out[s * VAD_SUMMARY + j] = f ? (j == 2 || j == 3 ? -1 : 0) : summary[s * VAD_SUMMARY + j];
 }
 
-#define VAD_HIP(p, call)                                                                             \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) { (p)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } \
-    } while (0)
-
 extern "C" int mimi_vad_pool_create(int n_streams, mimi_vad_pool* out) {
-    if (!out) { g_vad_err = "null pointer"; return -1; }
-    *out = nullptr;
-    if (n_streams < 1 || n_streams > VAD_MAX_STREAMS) { g_vad_err = "pool outside 1 .. 64 streams"; return -1; }
-    MimiVadPool* p = new MimiVadPool();
-    p->n_streams = n_streams;
-    for (int i = 0; i < n_streams; ++i) p->st[i].prm = VAD_DEFAULT_PARAMS;
-    const size_t carry_bytes = sizeof(int16_t) * 2 * VAD_CARRY * (size_t)n_streams;
-    hipError_t e = hipMalloc((void**)&p->carry_dev, carry_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->state_dev, sizeof(VadState) * n_streams);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->summary_dev, sizeof(long) * VAD_SUMMARY * n_streams);
-    if (e == hipSuccess) e = hipMemset(p->carry_dev, 0, carry_bytes);
-    if (e == hipSuccess) e = hipMemset(p->state_dev, 0, sizeof(VadState) * n_streams);
-    if (e == hipSuccess) e = hipMemset(p->summary_dev, 0, sizeof(long) * VAD_SUMMARY * n_streams);
-    if (e != hipSuccess) {
-        g_vad_err = std::string("mimi_vad_pool_create: ") + hipGetErrorString(e);
-        mimi_vad_pool_destroy(p);
-        return -2;
-    }
-    *out = p;
-    return 0;
+    return sp_create("mimi_vad_pool_create", n_streams, out, nullptr, [&](MimiVadPool* p) {
+        for (int i = 0; i < n_streams; ++i) p->st[i].prm = VAD_DEFAULT_PARAMS;
+        hipError_t e = p->get(&p->carry_dev, sizeof(int16_t) * 2 * VAD_CARRY * (size_t)n_streams, 0);
+        if (e == hipSuccess) e = p->get(&p->state_dev, sizeof(VadState) * n_streams, 0);
+        if (e == hipSuccess) e = p->get(&p->summary_dev, sizeof(long) * VAD_SUMMARY * n_streams, 0);
+        return e;
+    });
 }
 
-extern "C" void mimi_vad_pool_destroy(mimi_vad_pool p) {
-    if (!p) return;
-    if (p->carry_dev) (void)hipFree(p->carry_dev);
-    if (p->state_dev) (void)hipFree(p->state_dev);
-    if (p->summary_dev) (void)hipFree(p->summary_dev);
-    delete p;
-}
+extern "C" void mimi_vad_pool_destroy(mimi_vad_pool p) { delete p; }
 
-extern "C" const char* mimi_vad_pool_last_error(mimi_vad_pool p) { return p ? p->err.c_str() : g_vad_err.c_str(); }
+extern "C" const char* mimi_vad_pool_last_error(mimi_vad_pool p) { return sp_last_error(p); }
 
 extern "C" int mimi_vad_pool_reset(mimi_vad_pool p, const int32_t* streams, const mimi_vad_params* params, int n) {
-    if (!p) return -1;
-    if (const char* bad = vad_reset(p->n_streams, p->st, streams, (const VadParams*)params, n)) { p->err = bad; return -1; }
-    return 0;
+    return p ? sp_status(p, vad_reset(p->n_streams, p->st, streams, (const VadParams*)params, n)) : -1;
 }
 
 extern "C" long mimi_vad_pool_frame_count(mimi_vad_pool p, int sid, long n_in, int final) {
     (void)final;                                                                      // a partial frame is never judged, final or not
-    if (!p) return -1;
-    if (sid < 0 || sid >= p->n_streams) { p->err = "stream id outside [0, n_streams)"; return -1; }
-    if (n_in < 0 || n_in > VAD_MAX_CHUNK) { p->err = "a chunk of negative length or of more than 2^30 samples"; return -1; }
-    return vad_frame_count(p->st[sid], n_in);
+    return sp_count_ok(p, sid, n_in) ? vad_frame_count(p->st[sid], n_in) : -1;
 }
 
 extern "C" int mimi_vad_pool_feed(mimi_vad_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
@@ -297,21 +232,19 @@ extern "C" int mimi_vad_pool_feed(mimi_vad_pool p, const int32_t* streams, const
                                   void* stream) {
     if (!p) return -1;
     VadPlan plan;
-    VadStream next[VAD_MAX_STREAMS];
-    if (const char* bad = vad_plan_build(p->n_streams, p->st, streams, in_off, n_in, final, n, in, in_is_i16, flags, lag, power, floor,
-                                         n_frames, &plan, next)) {
-        p->err = bad;
-        return -1;
-    }
+    VadStream next[SP_MAX_STREAMS];
+    if (int rc = sp_status(p, vad_plan_build(p->n_streams, p->st, streams, in_off, n_in, final, n, in, in_is_i16, flags, lag, power, floor,
+                                             n_frames, &plan, next)))
+        return rc;
     (void)hipGetLastError();
     if (plan.frames > 0) {
         k_vad_features<<<dim3((unsigned)plan.frames), dim3(VAD_THREADS), 0, (hipStream_t)stream>>>(plan, p->carry_dev, in, in_is_i16, lag, power);
-        VAD_HIP(p, hipGetLastError());
+        SP_HIP(p, hipGetLastError());
     }
     k_vad_scan<<<dim3((unsigned)plan.n), dim3(64), 0, (hipStream_t)stream>>>(plan, p->carry_dev, p->state_dev, p->summary_dev, in, in_is_i16,
                                                                             lag, power, flags, floor);
-    VAD_HIP(p, hipGetLastError());
-    for (int i = 0; i < n; ++i) p->st[streams[i]] = next[i];
+    SP_HIP(p, hipGetLastError());
+    sp_commit(p->st, streams, next, n);
     return 0;
 }
 
@@ -324,6 +257,6 @@ extern "C" int mimi_vad_pool_summary(mimi_vad_pool p, long* out, void* stream) {
         if (!p->st[i].touched) fresh |= 1ull << i;
     (void)hipGetLastError();
     k_vad_summary<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(fresh, p->n_streams, p->summary_dev, out);
-    VAD_HIP(p, hipGetLastError());
+    SP_HIP(p, hipGetLastError());
     return 0;
 }

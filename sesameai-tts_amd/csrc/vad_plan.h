@@ -10,7 +10,10 @@
 #pragma once
 #include <stdint.h>
 
+#include "stream_pool.h"
+
 #define VAD_MAX_STREAMS 64           // = MIMI_VAD_MAX_STREAMS
+static_assert(VAD_MAX_STREAMS == SP_MAX_STREAMS, "the pools share one spine");
 #define VAD_F 240                    // frame
 #define VAD_W 480                    // analysis window
 #define VAD_TMIN 60
@@ -19,8 +22,6 @@
 #define VAD_HIST (VAD_SPAN - VAD_F)  // samples in front of its next frame that a stream keeps: 640
 #define VAD_CARRY VAD_SPAN           // int16 values per bank (the most a stream keeps is 879)
 #define VAD_SAT (1 << 20)            // since_voiced saturates here
-#define VAD_MAX_CHUNK (1L << 30)     // samples one stream takes in one call
-#define VAD_MAX_TOTAL (1L << 48)     // samples one stream takes between two resets
 #define VAD_SUMMARY 8                // int64 per stream: in speech, frames, last START, last END, quiet, STARTs, ENDs, 0
 
 struct VadParams { int32_t on_q4, off_q4, min_on, hang, hold, pad; int64_t n_min; };      // = mimi_vad_params
@@ -31,16 +32,13 @@ struct VadSeg {
     long in_off;                     // elements: its new samples in `in`
     long n_min;
     long k0;                         // frames judged since the stream was fresh (k0 == 0: the scan starts from the fresh state)
-    int sid;                         // | parity << 8 (the carry bank the call READS; it writes the other) | final << 9
+    int sid;                         // sp_sid_word
     int Lc, n_in;                    // carry samples; new samples
     int nf, f_off;                   // frames judged in this call; their place in the per-frame outputs
     int onoff;                       // on_q4 | off_q4 << 12
     int mh;                          // min_on | hang << 10
     int hold;
 };
-#define VAD_SID(g) ((g).sid & 0xFF)
-#define VAD_PARITY(g) (((g).sid >> 8) & 1)
-#define VAD_FINAL(g) (((g).sid >> 9) & 1)
 #define VAD_LEAD(g) ((g).k0 < 3 ? VAD_HIST - (int)(g).k0 * VAD_F : 0)      // rule zeros in front of the carry
 #define VAD_ON(g) ((g).onoff & 0xFFF)
 #define VAD_OFF(g) ((g).onoff >> 12)
@@ -66,23 +64,10 @@ static inline const char* vad_params_bad(const VadParams& p) {
     return nullptr;
 }
 
-static inline const char* vad_ids_bad(int n_streams, const int32_t* streams, int n) {
-    if (n_streams < 1 || n_streams > VAD_MAX_STREAMS) return "pool outside 1 .. 64 streams";
-    if (n < 1 || n > n_streams) return "stream list: need 1 .. n_streams ids";
-    bool seen[VAD_MAX_STREAMS] = {};
-    for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= n_streams) return "stream id outside [0, n_streams)";
-        if (seen[s]) return "duplicate stream id in one call";
-        seen[s] = true;
-    }
-    return nullptr;
-}
-
 // nullptr, or why the reset is refused (then no state has moved)
 static inline const char* vad_reset(int n_streams, VadStream* st, const int32_t* streams, const VadParams* params, int n) {
     if (!st || !streams || !params) return "null pointer";
-    if (const char* bad = vad_ids_bad(n_streams, streams, n)) return bad;
+    if (const char* bad = sp_ids_bad(n_streams, streams, n)) return bad;
     for (int i = 0; i < n; ++i)
         if (const char* bad = vad_params_bad(params[i])) return bad;
     for (int i = 0; i < n; ++i) {                                                      // (the parity stays: a fresh stream reads no carry)
@@ -101,15 +86,12 @@ static inline const char* vad_plan_build(int n_streams, const VadStream* st, con
     if (!st || !streams || !in_off || !n_in || !final || !in || !flags || !lag || !power || !floor || !n_frames) return "null pointer";
     if (in_is_i16 != 0 && in_is_i16 != 1) return "unknown input format";
     if ((uintptr_t)in % (in_is_i16 ? 2 : 4) || (uintptr_t)lag % 2 || (uintptr_t)power % 8 || (uintptr_t)floor % 8) return "a misaligned buffer";
-    if (const char* bad = vad_ids_bad(n_streams, streams, n)) return bad;
+    if (const char* bad = sp_ids_bad(n_streams, streams, n)) return bad;
     long total = 0;
     for (int i = 0; i < n; ++i) {
         const VadStream& s = st[streams[i]];
         if (const char* bad = vad_params_bad(s.prm)) return bad;
-        if (n_in[i] < 0) return "a chunk of negative length";
-        if (in_off[i] < 0) return "a chunk at a negative offset";
-        if (n_in[i] > VAD_MAX_CHUNK) return "a chunk of more than 2^30 samples";
-        if (s.R + n_in[i] > VAD_MAX_TOTAL) return "a stream of more than 2^48 samples";
+        if (const char* bad = sp_chunk_bad(n_in[i], in_off[i], s.R)) return bad;
         total += vad_frame_count(s, n_in[i]);
     }
     if (total > (1L << 30)) return "a call of more than 2^30 frames";
@@ -120,7 +102,7 @@ static inline const char* vad_plan_build(int n_streams, const VadStream* st, con
         const int fin = final[i] != 0;
         const long nf = vad_frame_count(s, n_in[i]);
         g.in_off = in_off[i]; g.n_min = s.prm.n_min; g.k0 = s.k;
-        g.sid = streams[i] | s.parity << 8 | fin << 9;
+        g.sid = sp_sid_word(streams[i], s.parity, fin);
         g.Lc = (int)vad_carry_len(s.R); g.n_in = (int)n_in[i];
         g.nf = (int)nf; g.f_off = frames;
         g.onoff = s.prm.on_q4 | s.prm.off_q4 << 12;
@@ -133,7 +115,7 @@ static inline const char* vad_plan_build(int n_streams, const VadStream* st, con
         if (fin) { t.R = 0; t.k = 0; }                                // the next sample starts a new clip
         else { t.R = s.R + n_in[i]; t.k = s.k + nf; }
     }
-    for (int i = n; i < VAD_MAX_STREAMS; ++i) plan->seg[i] = VadSeg{};
+    sp_zero_tail(plan->seg, n);
     plan->n = n; plan->frames = frames;
     return nullptr;
 }

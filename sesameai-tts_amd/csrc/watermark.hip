@@ -23,10 +23,8 @@
 #include <float.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/mimi_hip.h"
-#include "common.cuh"
+#include "stream_pool.cuh"
 #include "watermark_plan.h"
 
 static_assert(MIMI_WM_MAX_STREAMS == WM_MAX_STREAMS && MIMI_WM_MAX_CLIPS == WM_MAX_CLIPS && MIMI_WM_ROW == WM_ROW, "header and plan disagree");
@@ -40,43 +38,16 @@ static_assert(WM_P % 128 == 0 && WM_S % 2 == 0 && WM_TILE == 256, "k_wm_chips: 1
 #define WM_WIN (WM_S + WM_TILE)          // samples staged per block: 2176 (the last one is read by nobody)
 #define WM_WORDS (WM_WIN / 2)            // 1088 int16 pairs
 
-struct MimiWmPool {
-    int n_streams = 0;
+struct MimiWmPool : SpPool<WmStream> {
     uint64_t secret = 0;
-    WmStream st[WM_MAX_STREAMS] = {};
     int16_t* chips_dev = nullptr;    // [WM_P] +-1
     uint32_t* carry_dev = nullptr;   // [n_streams][2 banks][WM_S] raw words: fp32 bits, or a sign-extended int16
-    std::string err;
 };
-
-static thread_local std::string g_wm_err;
-
-typedef short wm_short2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int wm_dot2(uint32_t a, uint32_t b, int acc) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(wm_short2, a), __builtin_bit_cast(wm_short2, b), acc, false);
-}
-
-__device__ __forceinline__ int wm_wave_sum_i(int v) {
-    v += dpp_i<0xB1, 0xF>(0, v);
-    v += dpp_i<0x4E, 0xF>(0, v);
-    v += dpp_i<0x141, 0xF>(0, v);
-    v += dpp_i<0x140, 0xF>(0, v);
-    v += dpp_i<0x142, 0xA>(0, v);
-    v += dpp_i<0x143, 0xC>(0, v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// q = clamp(rint(x * 32768), -32768, 32767); a non-finite sample gives 0
-__device__ __forceinline__ int wm_quant(float x) {
-    if (!(fabsf(x) <= FLT_MAX)) return 0;
-    return (int)rintf(fminf(fmaxf(x * 32768.0f, -32768.0f), 32767.0f));                // (the bounds are integers: clamp and rint commute)
-}
 
 // the clip's integer sample at position p, zero outside [0, N)
 __device__ __forceinline__ int wm_q_at(const void* __restrict__ in, long in_off, int N, int i16, int p) {
     if (p < 0 || p >= N) return 0;
-    return i16 ? (int)((const int16_t*)in)[in_off + p] : wm_quant(((const float*)in)[in_off + p]);
+    return i16 ? (int)((const int16_t*)in)[in_off + p] : pcm_i16(((const float*)in)[in_off + p]);
 }
 
 __global__ void __launch_bounds__(64) k_wm_chips(uint2 key, int16_t* __restrict__ chips) {
@@ -94,15 +65,10 @@ __global__ void __launch_bounds__(WM_THREADS) k_wm_embed(const WmPlan plan, cons
     __shared__ int red[4][3];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     // the segment that owns this workgroup: the last one whose g_off <= blockIdx.x (every segment owns at least its tail group)
-    int lo = 0, hi = plan.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (plan.seg[mid].g_off <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const WmSeg& g = plan.seg[lo];
-    const int j = (int)blockIdx.x - g.g_off, sid = WM_SID(g), Lc = g.Lc, n_in = g.n_in, nb = g.nb;
+    const WmSeg& g = plan.seg[sp_owner(plan.seg, plan.n, &WmSeg::g_off)];
+    const int j = (int)blockIdx.x - g.g_off, sid = SP_SID(g), Lc = g.Lc, n_in = g.n_in, nb = g.nb;
     if (j > nb) return;                                                               // (never: every group below plan.groups lies in a segment)
-    const uint32_t* old = carry + ((long)sid * 2 + WM_PARITY(g)) * WM_S;
+    const uint32_t* old = carry + ((long)sid * 2 + SP_PARITY(g)) * WM_S;
     // raw word at position p of carry + chunk (p < Lc + n_in by construction of every use below)
     auto raw = [&](int p) -> uint32_t {
         if (p < Lc) return old[p];
@@ -111,10 +77,10 @@ __global__ void __launch_bounds__(WM_THREADS) k_wm_embed(const WmPlan plan, cons
     };
     if (j == nb) {                                                                    // the open block: fewer than S samples
         const int base = nb * WM_S, tl = Lc + n_in - base;
-        uint32_t* nw = carry + ((long)sid * 2 + (WM_PARITY(g) ^ 1)) * WM_S;
+        uint32_t* nw = carry + ((long)sid * 2 + (SP_PARITY(g) ^ 1)) * WM_S;
         for (int p = t; p < tl; p += WM_THREADS) {
             const uint32_t v = raw(base + p);
-            if (!WM_FINAL(g)) nw[p] = v;
+            if (!SP_FINAL(g)) nw[p] = v;
             else if (i16) ((int16_t*)out)[g.out_off + base + p] = (int16_t)(int)v;
             else ((uint32_t*)out)[g.out_off + base + p] = v;
         }
@@ -133,14 +99,14 @@ __global__ void __launch_bounds__(WM_THREADS) k_wm_embed(const WmPlan plan, cons
         x[i] = 0; q[i] = 0; c[i] = 0;
         if (m < WM_S) {
             x[i] = raw(base + m);
-            q[i] = i16 ? (int)x[i] : wm_quant(__uint_as_float(x[i]));
+            q[i] = i16 ? (int)x[i] : pcm_i16(__uint_as_float(x[i]));
             c[i] = cp[m];
             e += (unsigned long)(q[i] * q[i]);                                        // q^2 <= 2^30
             r += q[i] * c[i];
         }
     }
     // e <= 2^33 per thread: its low 15 bits and the rest are summed apart, each sum below 2^31 over the 256 threads
-    const int wr = wm_wave_sum_i(r), wlo = wm_wave_sum_i((int)(e & 0x7FFF)), whi = wm_wave_sum_i((int)(e >> 15));
+    const int wr = wave_sum_i(r), wlo = wave_sum_i((int)(e & 0x7FFF)), whi = wave_sum_i((int)(e >> 15));
     if (lane == 0) { red[w][0] = wr; red[w][1] = wlo; red[w][2] = whi; }
     __syncthreads();
     const long R = (long)red[0][0] + red[1][0] + red[2][0] + red[3][0];
@@ -208,8 +174,8 @@ __global__ void __launch_bounds__(WM_ST) k_wm_search(const WmDetectPlan plan, co
                 const uint32_t nxt = L[t + m + 1];                                    // t + m + 1 <= 127 + 960 < 1088
                 const uint32_t cw = cp[m];
                 const uint32_t odd = __builtin_amdgcn_alignbit(nxt, cur, 16);
-                ra = wm_dot2(cur, cw, ra);
-                rb = wm_dot2(odd, cw, rb);
+                ra = dot2_i16(cur, cw, ra);
+                rb = dot2_i16(odd, cw, rb);
                 cur = nxt;
             }
             // a candidate owns the block if it lies in the clip whole
@@ -248,7 +214,7 @@ __global__ void __launch_bounds__(WM_THREADS) k_wm_pick(const WmDetectPlan plan,
         const int k = (kb + b) % WM_K;
         int r = 0;
         for (int m = lane; m < WM_S; m += 64) r += wm_q_at(in, c.in_off, N, i16, first + b * WM_S + m) * chips[k * WM_S + m];
-        r = wm_wave_sum_i(r);
+        r = wave_sum_i(r);
         if (lane == 0) { atomicAdd(&R[k], (unsigned long long)(long)r); atomicAdd(&cov[k], 1); }
     }
     __syncthreads();
@@ -281,73 +247,44 @@ __global__ void __launch_bounds__(WM_THREADS) k_wm_pick(const WmDetectPlan plan,
     }
 }
 
-#define WM_HIP(p, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) { (p)->err = std::string(#call) + ": " + hipGetErrorString(e_); return -2; } \
-    } while (0)
-
 extern "C" int mimi_wm_pool_create(int n_streams, uint64_t secret, mimi_wm_pool* out) {
-    if (!out) { g_wm_err = "null pointer"; return -1; }
-    *out = nullptr;
-    if (n_streams < 1 || n_streams > WM_MAX_STREAMS) { g_wm_err = "pool outside 1 .. 64 streams"; return -1; }
-    MimiWmPool* p = new MimiWmPool();
-    p->n_streams = n_streams; p->secret = secret;
-    const uint8_t dflt[5] = {212, 211, 146, 56, 201};
-    for (int i = 0; i < n_streams; ++i) { wm_fresh(p->st[i]); p->st[i].t_q4 = 8; p->st[i].bits = wm_symbol_bits(dflt); }
-    const size_t carry_bytes = sizeof(uint32_t) * 2 * WM_S * (size_t)n_streams;
-    hipError_t e = hipMalloc((void**)&p->chips_dev, sizeof(int16_t) * WM_P);
-    if (e == hipSuccess) e = hipMalloc((void**)&p->carry_dev, carry_bytes);
-    if (e == hipSuccess) e = hipMemset(p->carry_dev, 0, carry_bytes);
-    if (e == hipSuccess) {
-        k_wm_chips<<<dim3((WM_P / 128 + 63) / 64), dim3(64), 0, 0>>>(make_uint2((uint32_t)secret, (uint32_t)(secret >> 32)), p->chips_dev);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(0);                                  // the table is there before any stream uses it
-    if (e != hipSuccess) {
-        g_wm_err = std::string("mimi_wm_pool_create: ") + hipGetErrorString(e);
-        mimi_wm_pool_destroy(p);
-        return -2;
-    }
-    *out = p;
-    return 0;
+    return sp_create("mimi_wm_pool_create", n_streams, out, nullptr, [&](MimiWmPool* p) {
+        p->secret = secret;
+        const uint8_t dflt[5] = {212, 211, 146, 56, 201};
+        for (int i = 0; i < n_streams; ++i) { wm_fresh(p->st[i]); p->st[i].t_q4 = 8; p->st[i].bits = wm_symbol_bits(dflt); }
+        hipError_t e = p->get(&p->chips_dev, sizeof(int16_t) * WM_P);
+        if (e == hipSuccess) e = p->get(&p->carry_dev, sizeof(uint32_t) * 2 * WM_S * (size_t)n_streams, 0);
+        if (e == hipSuccess) {
+            k_wm_chips<<<dim3((WM_P / 128 + 63) / 64), dim3(64), 0, 0>>>(make_uint2((uint32_t)secret, (uint32_t)(secret >> 32)), p->chips_dev);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(0);                              // the table is there before any stream uses it
+        return e;
+    });
 }
 
-extern "C" void mimi_wm_pool_destroy(mimi_wm_pool p) {
-    if (!p) return;
-    if (p->chips_dev) (void)hipFree(p->chips_dev);
-    if (p->carry_dev) (void)hipFree(p->carry_dev);
-    delete p;
-}
+extern "C" void mimi_wm_pool_destroy(mimi_wm_pool p) { delete p; }
 
-extern "C" const char* mimi_wm_pool_last_error(mimi_wm_pool p) { return p ? p->err.c_str() : g_wm_err.c_str(); }
+extern "C" const char* mimi_wm_pool_last_error(mimi_wm_pool p) { return sp_last_error(p); }
 
 extern "C" int mimi_wm_pool_reset(mimi_wm_pool p, const int32_t* streams, const uint8_t* payloads, const int32_t* t_q4, int n) {
-    if (!p) return -1;
-    if (const char* bad = wm_reset(p->n_streams, p->st, streams, payloads, t_q4, n)) { p->err = bad; return -1; }
-    return 0;
+    return p ? sp_status(p, wm_reset(p->n_streams, p->st, streams, payloads, t_q4, n)) : -1;
 }
 
 extern "C" long mimi_wm_pool_out_count(mimi_wm_pool p, int sid, long n_in, int final) {
-    if (!p) return -1;
-    if (sid < 0 || sid >= p->n_streams) { p->err = "stream id outside [0, n_streams)"; return -1; }
-    if (n_in < 0 || n_in > WM_MAX_CHUNK) { p->err = "a chunk of negative length or of more than 2^30 samples"; return -1; }
-    return wm_out_len(p->st[sid], n_in, final != 0);
+    return sp_count_ok(p, sid, n_in) ? wm_out_len(p->st[sid], n_in, final != 0) : -1;
 }
 
 extern "C" int mimi_wm_pool_feed(mimi_wm_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
                                  const void* in, int in_is_i16, void* out, long* n_out, void* stream) {
     if (!p) return -1;
     WmPlan plan;
-    WmStream next[WM_MAX_STREAMS];
-    if (const char* bad = wm_plan_build(p->n_streams, p->st, streams, in_off, n_in, final, n, in, in_is_i16, out, n_out, &plan, next)) {
-        p->err = bad;
-        return -1;
-    }
+    WmStream next[SP_MAX_STREAMS];
+    if (int rc = sp_status(p, wm_plan_build(p->n_streams, p->st, streams, in_off, n_in, final, n, in, in_is_i16, out, n_out, &plan, next))) return rc;
     (void)hipGetLastError();
     k_wm_embed<<<dim3((unsigned)plan.groups), dim3(WM_THREADS), 0, (hipStream_t)stream>>>(plan, p->chips_dev, p->carry_dev, in, in_is_i16, out);
-    WM_HIP(p, hipGetLastError());
-    for (int i = 0; i < n; ++i) p->st[streams[i]] = next[i];
+    SP_HIP(p, hipGetLastError());
+    sp_commit(p->st, streams, next, n);
     return 0;
 }
 
@@ -356,11 +293,11 @@ extern "C" int mimi_wm_pool_detect(mimi_wm_pool p, const long* in_off, const lon
                                    long* out, void* stream) {
     if (!p) return -1;
     WmDetectPlan plan;
-    if (const char* bad = wm_detect_plan(in_off, n_in, o0, n_off, expect, mask, n, in, in_is_i16, scores, out, &plan)) { p->err = bad; return -1; }
+    if (int rc = sp_status(p, wm_detect_plan(in_off, n_in, o0, n_off, expect, mask, n, in, in_is_i16, scores, out, &plan))) return rc;
     (void)hipGetLastError();
     k_wm_search<<<dim3((unsigned)plan.tiles), dim3(WM_ST), 0, (hipStream_t)stream>>>(plan, (const uint32_t*)p->chips_dev, in, in_is_i16, scores);
-    WM_HIP(p, hipGetLastError());
+    SP_HIP(p, hipGetLastError());
     k_wm_pick<<<dim3((unsigned)plan.n), dim3(WM_THREADS), 0, (hipStream_t)stream>>>(plan, p->chips_dev, in, in_is_i16, scores, out);
-    WM_HIP(p, hipGetLastError());
+    SP_HIP(p, hipGetLastError());
     return 0;
 }

@@ -10,7 +10,10 @@
 #pragma once
 #include <stdint.h>
 
+#include "stream_pool.h"
+
 #define WM_MAX_STREAMS 64            // = MIMI_WM_MAX_STREAMS
+static_assert(WM_MAX_STREAMS == SP_MAX_STREAMS, "the pools share one spine");
 #define WM_MAX_CLIPS 64              // = MIMI_WM_MAX_CLIPS
 #define WM_S 1920                    // samples per symbol: one Mimi frame
 #define WM_K 56                      // symbols per period
@@ -18,8 +21,6 @@
 #define WM_ROW 64                    // int64 per detected clip (= MIMI_WM_ROW)
 #define WM_TILE 256                  // candidates per search workgroup
 #define WM_SYNC 0xB2
-#define WM_MAX_CHUNK (1L << 30)      // samples one stream takes in one call
-#define WM_MAX_TOTAL (1L << 48)      // samples one stream takes between two resets
 #define WM_MAX_CLIP (1L << 24)       // samples of one detected clip
 #define WM_MAX_OFFSETS (1L << 21)    // candidates of one detect call, all clips together
 #define WM_ALL ((1ULL << WM_K) - 1)
@@ -49,16 +50,13 @@ static inline uint64_t wm_symbol_bits(const uint8_t* payload) {
 struct WmSeg {
     long in_off, out_off;            // elements: its new samples in `in`, its place in the packed `out`
     uint64_t bits;                   // the 56 symbol bits
-    int sid;                         // | parity << 8 (the carry bank the call READS; it writes the other) | final << 9
+    int sid;                         // sp_sid_word
     int Lc, n_in;                    // carry samples (< S); new samples
     int nb, g_off;                   // complete blocks; its first workgroup (a stream owns nb + 1: its blocks, then its tail)
     int k0;                          // symbol of its first block
     int t_q4;
     int pad;
 };
-#define WM_SID(g) ((g).sid & 0xFF)
-#define WM_PARITY(g) (((g).sid >> 8) & 1)
-#define WM_FINAL(g) (((g).sid >> 9) & 1)
 
 struct WmPlan {
     int n, groups;                   // segments; workgroups in all
@@ -73,25 +71,12 @@ static inline long wm_out_len(const WmStream& s, long more, int final) {
     return final ? have : have / WM_S * WM_S;
 }
 
-static inline const char* wm_ids_bad(int n_streams, const int32_t* streams, int n) {
-    if (n_streams < 1 || n_streams > WM_MAX_STREAMS) return "pool outside 1 .. 64 streams";
-    if (n < 1 || n > n_streams) return "stream list: need 1 .. n_streams ids";
-    bool seen[WM_MAX_STREAMS] = {};
-    for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= n_streams) return "stream id outside [0, n_streams)";
-        if (seen[s]) return "duplicate stream id in one call";
-        seen[s] = true;
-    }
-    return nullptr;
-}
-
 static inline void wm_fresh(WmStream& s) { s.R = 0; s.given = 0; s.fmt = -1; }
 
 // nullptr, or why the reset is refused (then no state has moved).  payloads: 5 bytes per listed stream.
 static inline const char* wm_reset(int n_streams, WmStream* st, const int32_t* streams, const uint8_t* payloads, const int32_t* t_q4, int n) {
     if (!st || !streams || !payloads || !t_q4) return "null pointer";
-    if (const char* bad = wm_ids_bad(n_streams, streams, n)) return bad;
+    if (const char* bad = sp_ids_bad(n_streams, streams, n)) return bad;
     for (int i = 0; i < n; ++i)
         if (t_q4[i] < 1 || t_q4[i] > 64) return "t_q4 outside 1 .. 64";
     for (int i = 0; i < n; ++i) {                                                      // (the parity stays: a fresh stream reads no carry)
@@ -111,15 +96,12 @@ static inline const char* wm_plan_build(int n_streams, const WmStream* st, const
     if (!st || !streams || !in_off || !n_in || !final || !in || !out || !n_out) return "null pointer";
     if (in_is_i16 != 0 && in_is_i16 != 1) return "unknown sample format";
     if ((uintptr_t)in % (in_is_i16 ? 2 : 4) || (uintptr_t)out % (in_is_i16 ? 2 : 4)) return "a misaligned buffer";
-    if (const char* bad = wm_ids_bad(n_streams, streams, n)) return bad;
+    if (const char* bad = sp_ids_bad(n_streams, streams, n)) return bad;
     long groups = 0;
     for (int i = 0; i < n; ++i) {
         const WmStream& s = st[streams[i]];
         if (s.t_q4 < 1 || s.t_q4 > 64) return "t_q4 outside 1 .. 64";
-        if (n_in[i] < 0) return "a chunk of negative length";
-        if (in_off[i] < 0) return "a chunk at a negative offset";
-        if (n_in[i] > WM_MAX_CHUNK) return "a chunk of more than 2^30 samples";
-        if (s.R + n_in[i] > WM_MAX_TOTAL) return "a stream of more than 2^48 samples";
+        if (const char* bad = sp_chunk_bad(n_in[i], in_off[i], s.R)) return bad;
         if (s.fmt >= 0 && s.fmt != in_is_i16) return "a stream that changes its sample format between resets";
         groups += (wm_carry_len(s.R) + n_in[i]) / WM_S + 1;
     }
@@ -132,7 +114,7 @@ static inline const char* wm_plan_build(int n_streams, const WmStream* st, const
         const int fin = final[i] != 0;
         const long Lc = wm_carry_len(s.R), nb = (Lc + n_in[i]) / WM_S;
         g.in_off = in_off[i]; g.out_off = out_off; g.bits = s.bits;
-        g.sid = streams[i] | s.parity << 8 | fin << 9;
+        g.sid = sp_sid_word(streams[i], s.parity, fin);
         g.Lc = (int)Lc; g.n_in = (int)n_in[i];
         g.nb = (int)nb; g.g_off = g_off;
         g.k0 = (int)(s.R / WM_S % WM_K);
@@ -145,7 +127,7 @@ static inline const char* wm_plan_build(int n_streams, const WmStream* st, const
         if (fin) wm_fresh(t);                                           // the next sample starts a new clip (same payload and t_q4)
         else { t.R = s.R + n_in[i]; t.given = s.given + n_out[i]; t.fmt = in_is_i16; }
     }
-    for (int i = n; i < WM_MAX_STREAMS; ++i) plan->seg[i] = WmSeg{};
+    sp_zero_tail(plan->seg, n);
     plan->n = n; plan->groups = g_off;
     return nullptr;
 }
@@ -193,7 +175,7 @@ static inline const char* wm_detect_plan(const long* in_off, const long* n_in, c
         s_off += (int)n_off[i];
         t_off += (int)((n_off[i] + WM_TILE - 1) / WM_TILE);
     }
-    for (int i = n; i < WM_MAX_CLIPS; ++i) plan->clip[i] = WmClip{};
+    sp_zero_tail(plan->clip, n);
     plan->n = n; plan->tiles = t_off;
     return nullptr;
 }

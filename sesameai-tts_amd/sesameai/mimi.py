@@ -18,6 +18,7 @@ import torch
 
 from . import _abi
 from ._abi import check, lib
+from ._stream_pool import _stream, fp32_unscaled, pack
 
 MAX_TR, MAX_ST = 16, 8
 MAX_ENCODE_CLIPS = 64           # MIMI_ENCODE_MAX_CLIPS: clips one mimi_encode_many call takes
@@ -245,22 +246,6 @@ def from_moshi_state_dict(sd: Dict[str, torch.Tensor], s: MimiArgs) -> Dict[str,
     return out
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _pack_clips(wavs: Sequence[torch.Tensor], device: torch.device):
-    """Clips (or chunks), each (n_i,), CPU or device -> one fp32 device buffer, clip after clip, and their offsets and lengths in it.  An
-    empty call still hands the library real memory -- a 1-element zero buffer, 1-element arrays -- so that ITS check refuses the call."""
-    lens = [int(w.shape[0]) for w in wavs]
-    offs = [sum(lens[:k]) for k in range(len(lens))]
-    packed = torch.cat([w.to(device=device, dtype=torch.float32) for w in wavs]) if wavs else torch.zeros(1, device=device)
-    if packed.numel() == 0:
-        packed = torch.zeros(1, device=device)
-    m = max(len(lens), 1)
-    return packed, (C.c_long * m)(*offs), (C.c_long * m)(*lens)
-
-
 def _latent(lib_fn, handle, frames: int, check_rc, codec: "MimiCodec") -> torch.Tensor:
     """(frames, hidden) fp32: the pre-quantisation latent of the last encode call on ``handle``, or the library's refusal."""
     out = torch.empty(int(frames), codec.args.hidden, dtype=torch.float32, device=codec.device)
@@ -434,9 +419,9 @@ class MimiCodec:
         return out
 
     def _encode_call(self, wavs: Sequence[torch.Tensor], frames: List[int], F: int) -> List[torch.Tensor]:
-        packed, offs, lens = _pack_clips(wavs, self.device)
+        p = pack(wavs, self.device, fp32_unscaled, noun="clip")
         codes = torch.empty(self.args.num_codebooks, F, dtype=torch.int32, device=self.device)
-        check(lib.mimi_encode_many(self._h, packed.data_ptr(), offs, lens, len(wavs), codes.data_ptr(), _stream()), self._h, mimi=True)
+        check(lib.mimi_encode_many(self._h, p.packed.data_ptr(), p.c_offs, p.c_lens, len(wavs), codes.data_ptr(), _stream()), self._h, mimi=True)
         codes = codes.long()
         return list(codes.split(frames, dim=1))
 
@@ -616,11 +601,11 @@ class MimiEncodeStreamPool(_StreamPool):
         assert len(wavs) == n, "one chunk per id"
         assert all(w.dim() == 1 for w in wavs), "every chunk must be (n,)"
         dev, hop = self.codec.device, self.codec.args.hop
-        packed, offs, lens = _pack_clips(wavs, dev)
-        frames = [-(-x // hop) for x in lens[:n]]
+        p = pack(wavs, dev, fp32_unscaled)
+        frames = [-(-x // hop) for x in p.lens]
         codes = torch.empty(self.codec.args.num_codebooks, max(sum(f for f in frames if f > 0), 1), dtype=torch.int32, device=dev)
-        self._check(lib.mimi_enc_pool_encode(self._h, arr, offs, lens, n, packed.data_ptr(), codes.data_ptr(), _stream()))
-        for i, x in zip(ids, lens):
+        self._check(lib.mimi_enc_pool_encode(self._h, arr, p.c_offs, p.c_lens, n, p.packed.data_ptr(), codes.data_ptr(), _stream()))
+        for i, x in zip(ids, p.lens):
             self._ended[i] = x % hop != 0
         return list(codes.long().split(frames, dim=1))
 

@@ -12,18 +12,13 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _abi
-from ._abi import lib
+from ._stream_pool import StreamPool, _stream, int16_if_all, pack, shared_pool, split
 
 MAX_STREAMS = 64                 # MIMI_RS_MAX_STREAMS
 _FMT = {torch.float32: 0, torch.int16: 1}
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-class ResamplerPool:
+class ResamplerPool(StreamPool):
     """``n`` independent resampler streams ``src_rate`` -> ``dst_rate``.  ``feed(ids, chunks, final)`` gives every listed stream its new
     samples -- fp32, or int16 (``s / 32768``) -- and returns what each may emit now, as ``out_dtype`` (fp32, or int16:
     ``round(clamp(y, -1, 1) * 32767)``): ONE launch, no host-to-device copy of a plan, no synchronisation.  ``final`` ends a stream's clip:
@@ -32,73 +27,36 @@ class ResamplerPool:
     def __init__(self, src_rate: int, dst_rate: int, n: int, device: Union[str, torch.device] = "cuda", out_dtype: torch.dtype = torch.float32):
         if out_dtype not in _FMT:
             raise ValueError("out_dtype must be torch.float32 or torch.int16")
-        self.src_rate, self.dst_rate, self.n_streams = int(src_rate), int(dst_rate), int(n)
-        self.device, self.out_dtype = torch.device(device), out_dtype
-        self._h = C.c_void_p(None)
-        with torch.cuda.device(self.device):
-            rc = lib.mimi_rs_pool_create(self.src_rate, self.dst_rate, self.n_streams, C.byref(self._h))
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_rs_pool_last_error(None) or b"").decode())
+        self.src_rate, self.dst_rate, self.out_dtype = int(src_rate), int(dst_rate), out_dtype
+        super().__init__("mimi_rs_pool", n, device, self.src_rate, self.dst_rate, int(n))
         up, down, half = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._check(lib.mimi_rs_pool_taps(self._h, None, C.byref(up), C.byref(down), C.byref(half)))
+        self._check(self._lib.mimi_rs_pool_taps(self._h, None, C.byref(up), C.byref(down), C.byref(half)))
         self.up, self.down, self.half = up.value, down.value, half.value
-
-    def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_rs_pool_last_error(self._h) or b"").decode())
 
     def taps(self) -> torch.Tensor:
         """For tests: the fp32 taps the device holds, h[0 .. 2 * half]."""
         out = torch.empty(2 * self.half + 1, dtype=torch.float32)
-        self._check(lib.mimi_rs_pool_taps(self._h, out.data_ptr(), None, None, None))
+        self._check(self._lib.mimi_rs_pool_taps(self._h, out.data_ptr(), None, None, None))
         return out
 
     def out_count(self, sid: int, n_in: int, final: bool = False) -> int:
         """Samples a feed of ``n_in`` samples would give stream ``sid`` now (host arithmetic)."""
-        n = int(lib.mimi_rs_pool_out_count(self._h, int(sid), int(n_in), int(bool(final))))
-        if n < 0:
-            self._check(-1)
-        return n
+        return self._count("out_count", sid, n_in, final)
 
     def reset(self, ids: Optional[Sequence[int]] = None) -> None:
         """Start the listed streams (default: all) afresh.  No launch."""
         ids = [int(i) for i in (range(self.n_streams) if ids is None else ids)]
-        self._check(lib.mimi_rs_pool_reset(self._h, (C.c_int32 * max(len(ids), 1))(*ids), len(ids)))
+        self._check(self._lib.mimi_rs_pool_reset(self._h, (C.c_int32 * max(len(ids), 1))(*ids), len(ids)))
 
     @torch.inference_mode()
     def feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False) -> List[torch.Tensor]:
         """ids: n distinct stream ids; chunks[i]: (n_i,) fp32 or int16, n_i >= 0, CPU or device, the new samples of stream ids[i];
         final: one flag, or one per stream -> one (m_i,) ``out_dtype`` tensor per stream (views into one buffer), m_i >= 0."""
-        ids = [int(i) for i in ids]
-        n = len(ids)
-        assert len(chunks) == n, "one chunk per id"
-        assert all(c.dim() == 1 for c in chunks), "every chunk must be (n,)"
-        fin = [bool(final)] * n if isinstance(final, (bool, int)) else [bool(f) for f in final]
-        assert len(fin) == n, "one final flag per id"
-        in_dtype = torch.int16 if n and all(c.dtype == torch.int16 for c in chunks) else torch.float32
-        parts = [c.to(self.device) if c.dtype == in_dtype else self._as_float(c.to(self.device)) for c in chunks]
-        lens = [int(c.shape[0]) for c in parts]
-        offs = [sum(lens[:k]) for k in range(n)]
-        packed = torch.cat(parts) if sum(lens) else torch.zeros(1, dtype=in_dtype, device=self.device)
-        m = max(n, 1)
-        # (an id the library will refuse counts as 0 here: the call below is what refuses it)
-        total = sum(max(int(lib.mimi_rs_pool_out_count(self._h, i, k, int(f))), 0) for i, k, f in zip(ids, lens, fin))
-        out = torch.empty(max(total, 1), dtype=self.out_dtype, device=self.device)
-        n_out = (C.c_long * m)()
-        self._check(lib.mimi_rs_pool_feed(self._h, (C.c_int32 * m)(*ids), (C.c_long * m)(*offs), (C.c_long * m)(*lens), (C.c_int32 * m)(*[int(f) for f in fin]),
-                                          n, packed.data_ptr(), _FMT[in_dtype], out.data_ptr(), _FMT[self.out_dtype], n_out, _stream()))
-        return list(out[:sum(n_out[:n])].split([int(x) for x in n_out[:n]]))
-
-    @staticmethod
-    def _as_float(c: torch.Tensor) -> torch.Tensor:
-        return c.float() / 32768.0 if c.dtype == torch.int16 else c.to(torch.float32)
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib.mimi_rs_pool_destroy(self._h)
-        except Exception:
-            pass
+        p = pack(chunks, self.device, int16_if_all, ids, final)
+        out = torch.empty(max(sum(self._counts("out_count", p)), 1), dtype=self.out_dtype, device=self.device)
+        n_out = (C.c_long * p.m)()
+        self._check(self._lib.mimi_rs_pool_feed(self._h, *p.head, _FMT[p.dtype], out.data_ptr(), _FMT[self.out_dtype], n_out, _stream()))
+        return split(out, n_out[:len(p.ids)])
 
 
 _POOLS: Dict[Tuple[int, int, str, torch.dtype], ResamplerPool] = {}       # resample()'s pools, made on first use and kept
@@ -111,15 +69,8 @@ def resample(wavs: Sequence[torch.Tensor], src_rate: int, dst_rate: int, device:
     launch on fresh streams with ``final``: per clip what ``scipy.signal.resample_poly(clip, up, down)`` computes, in fp32."""
     if not 1 <= len(wavs) <= MAX_STREAMS:
         raise ValueError(f"resample takes 1 .. {MAX_STREAMS} clips a call")
-    if device is None:
-        device = wavs[0].device if wavs[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(src_rate), int(dst_rate), str(device), out_dtype)
-    if key not in _POOLS:
-        _POOLS[key] = ResamplerPool(src_rate, dst_rate, MAX_STREAMS, device=device, out_dtype=out_dtype)
-    pool = _POOLS[key]
+    pool = shared_pool(_POOLS, device, wavs[0], lambda dev: (int(src_rate), int(dst_rate), str(dev), out_dtype),
+                       lambda dev: ResamplerPool(src_rate, dst_rate, MAX_STREAMS, device=dev, out_dtype=out_dtype))
     ids = list(range(len(wavs)))
     pool.reset(ids)                    # (host arithmetic: covers a stream that an earlier call, interrupted, left open)
     return pool.feed(ids, wavs, final=True)

@@ -12,8 +12,7 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
-from . import _abi
-from ._abi import lib
+from ._stream_pool import StreamPool, _stream, fp32_unscaled, pack, shared_pool, split
 
 MAX_STREAMS = 64                 # MIMI_TS_MAX_STREAMS
 BLOCK = 512                      # H: samples per block, one d per block
@@ -42,34 +41,18 @@ def per_request(speed, n: int) -> List[Optional[float]]:
     return [None if pm is None else pm / 1000.0 for pm in pms]
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-class TimeStretchPool:
+class TimeStretchPool(StreamPool):
     """``n`` independent time-stretch streams.  ``reset(ids, speeds)`` starts the listed streams afresh at their speeds (host arithmetic, no
     launch); ``feed(ids, chunks, final)`` gives every listed stream its new fp32 samples and returns what each may emit now: ONE launch, no
     host-to-device copy of a plan, no synchronisation.  ``final`` ends a stream's clip: the tail comes out and the stream is fresh (at the
     same speed).  Streams start fresh at speed 1.0."""
 
     def __init__(self, n: int, device: Union[str, torch.device] = "cuda"):
-        self.n_streams, self.device = int(n), torch.device(device)
-        self._h = C.c_void_p(None)
-        with torch.cuda.device(self.device):
-            rc = lib.mimi_ts_pool_create(self.n_streams, C.byref(self._h))
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_ts_pool_last_error(None) or b"").decode())
-
-    def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_ts_pool_last_error(self._h) or b"").decode())
+        super().__init__("mimi_ts_pool", n, device, int(n))
 
     def out_count(self, sid: int, n_in: int, final: bool = False) -> int:
         """Samples a feed of ``n_in`` samples would give stream ``sid`` now (host arithmetic)."""
-        n = int(lib.mimi_ts_pool_out_count(self._h, int(sid), int(n_in), int(bool(final))))
-        if n < 0:
-            self._check(-1)
-        return n
+        return self._count("out_count", sid, n_in, final)
 
     def reset(self, ids: Sequence[int], speeds: Union[float, int, Sequence[Union[float, int]]]) -> None:
         """Start the listed streams afresh; ``speeds``: one factor for all, or one per id (0.5 .. 2.0; 1.0 is a legal stream speed)."""
@@ -78,44 +61,23 @@ class TimeStretchPool:
         assert len(sp) == len(ids), "one speed per id"
         pm = [int(round(float(s) * 1000)) for s in sp]
         m = max(len(ids), 1)
-        self._check(lib.mimi_ts_pool_reset(self._h, (C.c_int32 * m)(*ids), (C.c_int32 * m)(*pm), len(ids)))
+        self._check(self._lib.mimi_ts_pool_reset(self._h, (C.c_int32 * m)(*ids), (C.c_int32 * m)(*pm), len(ids)))
 
     @torch.inference_mode()
     def feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False, want_offsets: bool = False):
         """ids: n distinct stream ids; chunks[i]: (n_i,) fp32, n_i >= 0, CPU or device, the new samples of stream ids[i]; final: one flag, or
         one per stream -> one (m_i,) fp32 tensor per stream (views into one buffer), m_i >= 0.  want_offsets: also, per stream, the int32
         offsets d_k of its ceil(m_i / 512) emitted blocks (device; 0 for a clip's first block)."""
-        ids = [int(i) for i in ids]
-        n = len(ids)
-        assert len(chunks) == n, "one chunk per id"
-        assert all(c.dim() == 1 for c in chunks), "every chunk must be (n,)"
-        fin = [bool(final)] * n if isinstance(final, (bool, int)) else [bool(f) for f in final]
-        assert len(fin) == n, "one final flag per id"
-        parts = [c.to(self.device, torch.float32) for c in chunks]
-        lens = [int(c.shape[0]) for c in parts]
-        offs = [sum(lens[:k]) for k in range(n)]
-        packed = torch.cat(parts) if sum(lens) else torch.zeros(1, dtype=torch.float32, device=self.device)
-        m = max(n, 1)
-        # (an id the library will refuse counts as 0 here: the call below is what refuses it)
-        counts = [max(int(lib.mimi_ts_pool_out_count(self._h, i, k, int(f))), 0) for i, k, f in zip(ids, lens, fin)]
+        p = pack(chunks, self.device, fp32_unscaled, ids, final)
+        counts = self._counts("out_count", p)
         out = torch.empty(max(sum(counts), 1), dtype=torch.float32, device=self.device)
         d = torch.empty(max(sum(-(-c // BLOCK) for c in counts), 1), dtype=torch.int32, device=self.device) if want_offsets else None
-        n_out = (C.c_long * m)()
-        self._check(lib.mimi_ts_pool_feed(self._h, (C.c_int32 * m)(*ids), (C.c_long * m)(*offs), (C.c_long * m)(*lens), (C.c_int32 * m)(*[int(f) for f in fin]),
-                                          n, packed.data_ptr(), out.data_ptr(), n_out, d.data_ptr() if want_offsets else None, _stream()))
-        got = [int(x) for x in n_out[:n]]
-        ys = list(out[:sum(got)].split(got))
+        n_out = (C.c_long * p.m)()
+        self._check(self._lib.mimi_ts_pool_feed(self._h, *p.head, out.data_ptr(), n_out, d.data_ptr() if want_offsets else None, _stream()))
+        got = [int(x) for x in n_out[:len(p.ids)]]
         if not want_offsets:
-            return ys
-        nb = [-(-g // BLOCK) for g in got]
-        return ys, list(d[:sum(nb)].split(nb))
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib.mimi_ts_pool_destroy(self._h)
-        except Exception:
-            pass
+            return split(out, got)
+        return split(out, got), split(d, [-(-g // BLOCK) for g in got])
 
 
 _POOLS: Dict[str, TimeStretchPool] = {}       # stretch()'s pools, made on first use and kept
@@ -128,15 +90,7 @@ def stretch(wavs: Sequence[torch.Tensor], speed: Union[float, int, Sequence[Unio
     (ceil(n_i / speed_i),) fp32, in ONE launch on fresh streams with ``final``."""
     if not 1 <= len(wavs) <= MAX_STREAMS:
         raise ValueError(f"stretch takes 1 .. {MAX_STREAMS} clips a call")
-    if device is None:
-        device = wavs[0].device if wavs[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = str(device)
-    if key not in _POOLS:
-        _POOLS[key] = TimeStretchPool(MAX_STREAMS, device=device)
-    pool = _POOLS[key]
+    pool = shared_pool(_POOLS, device, wavs[0], str, lambda dev: TimeStretchPool(MAX_STREAMS, device=dev))
     ids = list(range(len(wavs)))
     pool.reset(ids, speed)             # (host arithmetic: also covers a stream that an earlier call, interrupted, left open)
     return pool.feed(ids, wavs, final=True, want_offsets=want_offsets)

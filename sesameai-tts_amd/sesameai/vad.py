@@ -13,8 +13,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _abi
-from ._abi import lib
+from ._stream_pool import StreamPool, _stream, int16_if_all, pack, shared_pool, split
 
 MAX_STREAMS = 64                 # MIMI_VAD_MAX_STREAMS
 FRAME = 240                      # F: samples per frame at 24 kHz
@@ -78,11 +77,7 @@ def events(frames: Union[VadFrames, Sequence[int], torch.Tensor], params: VadPar
     return out
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-class VadPool:
+class VadPool(StreamPool):
     """``n`` independent voice-activity streams.  ``reset(ids, params)`` starts the listed streams afresh with their parameters (host
     arithmetic, no launch); ``feed(ids, chunks, final)`` gives every listed stream its new samples at 24 kHz, fp32 or int16, and returns
     the frames each completed: at most two launches, no host-to-device copy of a plan, no synchronisation.  ``final`` ends a stream's clip:
@@ -90,28 +85,16 @@ class VadPool:
     call's only synchronisation)."""
 
     def __init__(self, n: int, device: Union[str, torch.device] = "cuda"):
-        self.n_streams, self.device = int(n), torch.device(device)
-        self._h = C.c_void_p(None)
-        with torch.cuda.device(self.device):
-            rc = lib.mimi_vad_pool_create(self.n_streams, C.byref(self._h))
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_vad_pool_last_error(None) or b"").decode())
+        super().__init__("mimi_vad_pool", n, device, int(n))
         self.params: Dict[int, VadParams] = {s: VadParams() for s in range(self.n_streams)}
         self._k: Dict[int, int] = {s: 0 for s in range(self.n_streams)}          # frames judged since the stream was fresh
         self._summary = torch.zeros(self.n_streams * SUMMARY, dtype=torch.int64, device=self.device)
 
     events = staticmethod(events)
 
-    def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise _abi.CsmError(rc, (lib.mimi_vad_pool_last_error(self._h) or b"").decode())
-
     def frame_count(self, sid: int, n_in: int, final: bool = False) -> int:
         """Frames a feed of ``n_in`` samples would complete for stream ``sid`` now (host arithmetic)."""
-        n = int(lib.mimi_vad_pool_frame_count(self._h, int(sid), int(n_in), int(bool(final))))
-        if n < 0:
-            self._check(-1)
-        return n
+        return self._count("frame_count", sid, n_in, final)
 
     def reset(self, ids: Sequence[int], params: Union[None, VadParams, Sequence[VadParams]] = None) -> None:
         """Start the listed streams afresh; ``params``: None (the defaults), one set for all, or one per id."""
@@ -120,7 +103,7 @@ class VadPool:
         assert len(ps) == len(ids), "one parameter set per id"
         m = max(len(ids), 1)
         arr = (_CParams * m)(*[_CParams(p.on_q4, p.off_q4, p.min_on, p.hang, p.hold, 0, p.n_min) for p in ps])
-        self._check(lib.mimi_vad_pool_reset(self._h, (C.c_int32 * m)(*ids), arr, len(ids)))
+        self._check(self._lib.mimi_vad_pool_reset(self._h, (C.c_int32 * m)(*ids), arr, len(ids)))
         for i, p in zip(ids, ps):
             self.params[i], self._k[i] = p, 0
 
@@ -129,36 +112,19 @@ class VadPool:
         """ids: n distinct stream ids; chunks[i]: (n_i,) fp32 or int16 at 24 kHz, n_i >= 0, CPU or device, the new samples of stream
         ids[i] (int16 only if every chunk is); final: one flag, or one per stream -> one ``VadFrames`` per stream (views into four
         buffers), K_i >= 0 frames each."""
-        ids = [int(i) for i in ids]
-        n = len(ids)
-        assert len(chunks) == n, "one chunk per id"
-        assert all(c.dim() == 1 for c in chunks), "every chunk must be (n,)"
-        fin = [bool(final)] * n if isinstance(final, (bool, int)) else [bool(f) for f in final]
-        assert len(fin) == n, "one final flag per id"
-        i16 = n > 0 and all(c.dtype == torch.int16 for c in chunks)
-        dt = torch.int16 if i16 else torch.float32
-        parts = [c.to(self.device) if c.dtype == dt else (c.to(self.device).float() / 32768.0 if c.dtype == torch.int16 else c.to(self.device, dt))
-                 for c in chunks]
-        lens = [int(c.shape[0]) for c in parts]
-        offs = [sum(lens[:k]) for k in range(n)]
-        packed = torch.cat(parts) if sum(lens) else torch.zeros(1, dtype=dt, device=self.device)
-        m = max(n, 1)
-        # (an id the library will refuse counts as 0 here: the call below is what refuses it)
-        counts = [max(int(lib.mimi_vad_pool_frame_count(self._h, i, k, int(f))), 0) for i, k, f in zip(ids, lens, fin)]
-        K = max(sum(counts), 1)
+        p = pack(chunks, self.device, int16_if_all, ids, final)
+        K = max(sum(self._counts("frame_count", p)), 1)
         flags = torch.empty(K, dtype=torch.uint8, device=self.device)
         lag = torch.empty(K, dtype=torch.int16, device=self.device)
         power = torch.empty(K, dtype=torch.int64, device=self.device)
         floor = torch.empty(K, dtype=torch.int64, device=self.device)
-        n_frames = (C.c_long * m)()
-        self._check(lib.mimi_vad_pool_feed(self._h, (C.c_int32 * m)(*ids), (C.c_long * m)(*offs), (C.c_long * m)(*lens),
-                                           (C.c_int32 * m)(*[int(f) for f in fin]), n, packed.data_ptr(), int(i16), flags.data_ptr(),
-                                           lag.data_ptr(), power.data_ptr(), floor.data_ptr(), n_frames, _stream()))
-        got = [int(x) for x in n_frames[:n]]
-        tot = sum(got)
-        cols = [list(t[:tot].split(got)) for t in (flags, lag, power, floor)]
+        n_frames = (C.c_long * p.m)()
+        self._check(self._lib.mimi_vad_pool_feed(self._h, *p.head, int(p.dtype == torch.int16), flags.data_ptr(), lag.data_ptr(),
+                                                 power.data_ptr(), floor.data_ptr(), n_frames, _stream()))
+        got = [int(x) for x in n_frames[:len(p.ids)]]
+        cols = [split(t, got) for t in (flags, lag, power, floor)]
         out = []
-        for j, (i, g, f) in enumerate(zip(ids, got, fin)):
+        for j, (i, g, f) in enumerate(zip(p.ids, got, p.fin)):
             out.append(VadFrames(cols[0][j], cols[1][j], cols[2][j], cols[3][j], self._k[i]))
             self._k[i] = 0 if f else self._k[i] + g
         return out
@@ -166,16 +132,9 @@ class VadPool:
     @torch.inference_mode()
     def poll(self) -> List[VadSummary]:
         """Every stream's summary as of its last call (counts since the stream was last fresh)."""
-        self._check(lib.mimi_vad_pool_summary(self._h, self._summary.data_ptr(), _stream()))
+        self._check(self._lib.mimi_vad_pool_summary(self._h, self._summary.data_ptr(), _stream()))
         rows = self._summary.view(self.n_streams, SUMMARY).cpu().tolist()
         return [VadSummary(bool(r[0]), *r[1:7]) for r in rows]
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib.mimi_vad_pool_destroy(self._h)
-        except Exception:
-            pass
 
 
 _POOLS: Dict[str, VadPool] = {}       # detect()'s pools, made on first use and kept
@@ -188,15 +147,7 @@ def detect(wavs: Sequence[torch.Tensor], params: Union[None, VadParams, Sequence
     fresh streams with ``final``.  want_summary: also every clip's ``VadSummary``."""
     if not 1 <= len(wavs) <= MAX_STREAMS:
         raise ValueError(f"detect takes 1 .. {MAX_STREAMS} clips a call")
-    if device is None:
-        device = wavs[0].device if wavs[0].is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = str(device)
-    if key not in _POOLS:
-        _POOLS[key] = VadPool(MAX_STREAMS, device=device)
-    pool = _POOLS[key]
+    pool = shared_pool(_POOLS, device, wavs[0], str, lambda dev: VadPool(MAX_STREAMS, device=dev))
     ids = list(range(len(wavs)))
     pool.reset(ids, params)            # (host arithmetic: also covers a stream that an earlier call, interrupted, left open)
     frames = pool.feed(ids, wavs, final=True)

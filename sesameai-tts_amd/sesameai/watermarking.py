@@ -18,6 +18,8 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
+from ._stream_pool import StreamPool, _stream, int16_if_all, one_format, pack, shared_pool, split
+
 # Same public (hence not secret) key as the reference; use a private one in another application.
 CSM_1B_GH_WATERMARK = [212, 211, 146, 56, 201]
 
@@ -93,11 +95,7 @@ class DetectRow:
         return f"DetectRow(offset={self.offset}, score={self.score}/{self.covered}, blocks={self.blocks}, payload={self.payload}, crc_ok={self.crc_ok})"
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-class WatermarkPool:
+class WatermarkPool(StreamPool):
     """``n`` independent watermark streams under one ``secret`` (None: the default payload's 40-bit value).  ``reset(ids, payloads, t_q4)``
     starts the listed streams afresh (host arithmetic, no launch); ``feed(ids, chunks, final)`` gives every listed stream its new samples at
     24 kHz, fp32 or int16, and returns each stream's finished blocks in that format: ONE launch, no host-to-device copy of a plan, no
@@ -105,26 +103,12 @@ class WatermarkPool:
     leaves the stream fresh.  ``embed`` marks whole clips, ``detect`` searches clips for the mark."""
 
     def __init__(self, n: int, secret: Optional[int] = None, device: Union[str, torch.device] = "cuda"):
-        from . import _abi
-        self._abi, self._lib = _abi, _abi.lib
-        self.n_streams, self.device = int(n), torch.device(device)
         self.secret = default_secret() if secret is None else int(secret) & (2 ** 64 - 1)
-        self._h = C.c_void_p(None)
-        with torch.cuda.device(self.device):
-            rc = self._lib.mimi_wm_pool_create(self.n_streams, self.secret, C.byref(self._h))
-        if rc != 0:
-            raise _abi.CsmError(rc, (self._lib.mimi_wm_pool_last_error(None) or b"").decode())
-
-    def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise self._abi.CsmError(rc, (self._lib.mimi_wm_pool_last_error(self._h) or b"").decode())
+        super().__init__("mimi_wm_pool", n, device, int(n), self.secret)           # (resolves the library: importing this module does not)
 
     def out_count(self, sid: int, n_in: int, final: bool = False) -> int:
         """Samples a feed of ``n_in`` samples would give stream ``sid`` now (host arithmetic)."""
-        n = int(self._lib.mimi_wm_pool_out_count(self._h, int(sid), int(n_in), int(bool(final))))
-        if n < 0:
-            self._check(-1)
-        return n
+        return self._count("out_count", sid, n_in, final)
 
     def reset(self, ids: Sequence[int], payloads=CSM_1B_GH_WATERMARK, t_q4: Union[int, Sequence[int]] = 8) -> None:
         """Start the listed streams afresh; ``payloads``: five bytes for all, or one such list per id; ``t_q4``: 1 .. 64, one or one per id."""
@@ -140,29 +124,11 @@ class WatermarkPool:
     def feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False) -> List[torch.Tensor]:
         """ids: n distinct stream ids; chunks[i]: (n_i,) fp32 or int16 at 24 kHz, n_i >= 0, CPU or device, the new samples of stream
         ids[i] (all chunks of a call in one format); final: one flag, or one per stream -> one tensor per stream (views into one buffer)."""
-        ids = [int(i) for i in ids]
-        n = len(ids)
-        assert len(chunks) == n, "one chunk per id"
-        assert all(c.dim() == 1 for c in chunks), "every chunk must be (n,)"
-        fin = [bool(final)] * n if isinstance(final, (bool, int)) else [bool(f) for f in final]
-        assert len(fin) == n, "one final flag per id"
-        i16 = n > 0 and all(c.dtype == torch.int16 for c in chunks)
-        assert i16 or all(c.dtype != torch.int16 for c in chunks), "fp32 and int16 chunks in one call"
-        dt = torch.int16 if i16 else torch.float32
-        parts = [c.to(self.device, dt) for c in chunks]
-        lens = [int(c.shape[0]) for c in parts]
-        offs = [sum(lens[:k]) for k in range(n)]
-        packed = torch.cat(parts) if sum(lens) else torch.zeros(1, dtype=dt, device=self.device)
-        m = max(n, 1)
-        # (an id the library will refuse counts as 0 here: the call below is what refuses it)
-        counts = [max(int(self._lib.mimi_wm_pool_out_count(self._h, i, k, int(f))), 0) for i, k, f in zip(ids, lens, fin)]
-        out = torch.empty(max(sum(counts), 1), dtype=dt, device=self.device)
-        n_out = (C.c_long * m)()
-        self._check(self._lib.mimi_wm_pool_feed(self._h, (C.c_int32 * m)(*ids), (C.c_long * m)(*offs), (C.c_long * m)(*lens),
-                                                (C.c_int32 * m)(*[int(f) for f in fin]), n, packed.data_ptr(), int(i16), out.data_ptr(),
-                                                n_out, _stream()))
-        got = [int(x) for x in n_out[:n]]
-        return list(out[:sum(got)].split(got))
+        p = pack(chunks, self.device, one_format, ids, final)
+        out = torch.empty(max(sum(self._counts("out_count", p)), 1), dtype=p.dtype, device=self.device)
+        n_out = (C.c_long * p.m)()
+        self._check(self._lib.mimi_wm_pool_feed(self._h, *p.head, int(p.dtype == torch.int16), out.data_ptr(), n_out, _stream()))
+        return split(out, n_out[:len(p.ids)])
 
     def embed(self, wavs: Sequence[torch.Tensor], payload=CSM_1B_GH_WATERMARK, t_q4: Union[int, Sequence[int]] = 8) -> List[torch.Tensor]:
         """Up to ``n_streams`` whole clips in ONE launch, on fresh streams with ``final``: each clip comes back marked, same length and format."""
@@ -190,29 +156,16 @@ class WatermarkPool:
             expect, mask = [symbol_bits(p) for p in payload], [ALL_MASK] * n
         pairs = [search] * n if isinstance(search[0], int) else list(search)
         assert len(pairs) == n, "one (o0, n_off) per clip"
-        i16 = all(c.dtype == torch.int16 for c in wavs)
-        dt = torch.int16 if i16 else torch.float32
-        parts = [c.to(self.device).float() / 32768.0 if c.dtype == torch.int16 and not i16 else c.to(self.device, dt) for c in wavs]
-        assert all(c.dim() == 1 for c in parts), "every clip must be (n,)"
-        lens = [int(c.shape[0]) for c in parts]
-        offs = [sum(lens[:k]) for k in range(n)]
-        packed = torch.cat(parts) if sum(lens) else torch.zeros(1, dtype=dt, device=self.device)
-        scores = torch.empty(max(sum(max(int(p[1]), 0) for p in pairs), 1), dtype=torch.int32, device=self.device)
+        p = pack(wavs, self.device, int16_if_all, noun="clip")
+        scores = torch.empty(max(sum(max(int(q[1]), 0) for q in pairs), 1), dtype=torch.int32, device=self.device)
         rows = torch.empty(n, ROW, dtype=torch.int64, device=self.device)
         L, U = C.c_long * n, C.c_uint64 * n
-        self._check(self._lib.mimi_wm_pool_detect(self._h, L(*offs), L(*lens), L(*[int(p[0]) for p in pairs]), L(*[int(p[1]) for p in pairs]),
-                                                  U(*expect), U(*mask), n, packed.data_ptr(), int(i16), scores.data_ptr(), rows.data_ptr(),
-                                                  _stream()))
+        self._check(self._lib.mimi_wm_pool_detect(self._h, p.c_offs, p.c_lens, L(*[int(q[0]) for q in pairs]), L(*[int(q[1]) for q in pairs]),
+                                                  U(*expect), U(*mask), n, p.packed.data_ptr(), int(p.dtype == torch.int16), scores.data_ptr(),
+                                                  rows.data_ptr(), _stream()))
         if want_rows:
             return rows
         return [DetectRow(r) for r in rows.cpu().tolist()]
-
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.mimi_wm_pool_destroy(self._h)
-        except Exception:
-            pass
 
 
 def key_of(watermark) -> Optional[List[int]]:
@@ -231,15 +184,8 @@ _POOLS: Dict[Tuple[str, int], WatermarkPool] = {}       # embed()'s and detect()
 
 
 def _shared_pool(key: Sequence[int], device: Union[str, torch.device, None], like: Optional[torch.Tensor] = None) -> WatermarkPool:
-    if device is None:
-        device = like.device if like is not None and like.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    at = (str(device), default_secret(key))
-    if at not in _POOLS:
-        _POOLS[at] = WatermarkPool(MAX_STREAMS, at[1], device=device)
-    return _POOLS[at]
+    secret = default_secret(key)
+    return shared_pool(_POOLS, device, like, lambda dev: (str(dev), secret), lambda dev: WatermarkPool(MAX_STREAMS, secret, device=dev))
 
 
 def embed(wavs: Sequence[torch.Tensor], key: Sequence[int] = CSM_1B_GH_WATERMARK, device: Union[str, torch.device, None] = None,

@@ -1,18 +1,8 @@
 """The clip plan of a ragged Mimi encode (sesameai-tts_amd/csrc/enc_segs.h: no HIP) as a stand-alone host program under the host
 sanitizers: for every list of up to four clips around the seams (1, hop / 2, hop +- 1, 2 hop +- 1 samples) the slots do not overlap, the
 rows fit them, every level's row count is the single encode's, and every refusal of mimi_encode_many is made (tools/enc_segs_check.cpp)."""
-import os
-import shutil
-import subprocess
+from host_check import build_and_run
 
 
 def test_enc_segs_under_the_host_sanitizers(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    exe = str(tmp_path / "enc_segs_check")
-    r = subprocess.run([hipcc, "-std=c++17", "-O1", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                        "-I", os.path.join(root, "sesameai-tts_amd", "csrc"), os.path.join(root, "tools", "enc_segs_check.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok" and r.stderr == "", r.stdout + r.stderr
+    build_and_run("enc_segs_check", tmp_path, "-O1")

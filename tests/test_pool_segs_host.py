@@ -1,18 +1,8 @@
 """The segment plan of a ragged stream-pool decode (sesameai-tts_amd/csrc/pool_segs.h: no HIP) as a stand-alone host program under the host
 sanitizers: for every list of up to four segments with T_i in {1, 2, max - 1, max} the dense slots tile [0, R * F) at every level without
 gap or overlap, frame_seg is right at every frame, and every refusal of mimi_pool_decode_ragged is made (tools/pool_segs_check.cpp)."""
-import os
-import shutil
-import subprocess
+from host_check import build_and_run
 
 
 def test_pool_segs_under_the_host_sanitizers(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    exe = str(tmp_path / "pool_segs_check")
-    r = subprocess.run([hipcc, "-std=c++17", "-O1", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                        "-I", os.path.join(root, "sesameai-tts_amd", "csrc"), os.path.join(root, "tools", "pool_segs_check.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok" and r.stderr == "", r.stdout + r.stderr
+    build_and_run("pool_segs_check", tmp_path, "-O1")

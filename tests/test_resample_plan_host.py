@@ -2,18 +2,8 @@
 sanitizers: every refusal of mimi_rs_pool_create / mimi_rs_pool_feed, the packed output offsets, the emitted counts against the formula for
 the ten rate pairs, and a stream walked past 2^40 samples whose kernel-visible numbers stay those of its totals reduced by whole periods
 (tools/resample_plan_check.cpp)."""
-import os
-import shutil
-import subprocess
+from host_check import build_and_run
 
 
 def test_resample_plan_under_the_host_sanitizers(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    exe = str(tmp_path / "resample_plan_check")
-    r = subprocess.run([hipcc, "-std=c++17", "-O1", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                        "-I", os.path.join(root, "sesameai-tts_amd", "csrc"), os.path.join(root, "tools", "resample_plan_check.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok" and r.stderr == "", r.stdout + r.stderr
+    build_and_run("resample_plan_check", tmp_path, "-O1")

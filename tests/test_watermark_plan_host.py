@@ -2,18 +2,8 @@
 sanitizers: every refusal of mimi_wm_pool_reset / mimi_wm_pool_feed / mimi_wm_pool_detect at both sides of both ends of its range with
 nothing planned and no state moved, the output counts against the definition, the carry that never reaches 1920 samples, the packed
 places, and a stream walked past 2^40 samples whose kernel-visible numbers stay small (tools/wm_plan_check.cpp)."""
-import os
-import shutil
-import subprocess
+from host_check import build_and_run
 
 
 def test_watermark_plan_under_the_host_sanitizers(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hipcc = shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    exe = str(tmp_path / "wm_plan_check")
-    r = subprocess.run([hipcc, "-std=c++17", "-O1", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                        "-I", os.path.join(root, "sesameai-tts_amd", "csrc"), os.path.join(root, "tools", "wm_plan_check.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok" and r.stderr == "", r.stdout + r.stderr
+    build_and_run("wm_plan_check", tmp_path, "-O1")

@@ -156,13 +156,13 @@ static void check_offsets_and_refusals() {
     REFUSED(r, 4, st, dup, o2, l2, f2, 2, &x, 0, &y, 0);
     REFUSED(r, 4, st, far, o0, l1, fin0, 1, &x, 0, &y, 0);
     REFUSED(r, 4, st, neg, o0, l1, fin0, 1, &x, 0, &y, 0);
-    const long lneg[1] = {-1}, oneg[1] = {-1}, lbig[1] = {RS_MAX_CHUNK + 1};
+    const long lneg[1] = {-1}, oneg[1] = {-1}, lbig[1] = {SP_MAX_CHUNK + 1};
     REFUSED(r, 4, st, one, o0, lneg, fin0, 1, &x, 0, &y, 0);
     REFUSED(r, 4, st, one, oneg, l1, fin0, 1, &x, 0, &y, 0);
     REFUSED(r, 4, st, one, o0, lbig, fin0, 1, &x, 0, &y, 0);
     RsRates u;
     REQUIRE(rs_rates(24000, 48000, &u) == nullptr);
-    const long lmax[1] = {RS_MAX_CHUNK};
+    const long lmax[1] = {SP_MAX_CHUNK};
     REFUSED(u, 4, st, one, o0, lmax, fin0, 1, &x, 0, &y, 0);          // 2^30 in would give 2^31 out
     REFUSED(r, 0, st, one, o0, l1, fin0, 1, &x, 0, &y, 0);
     REFUSED(r, RS_MAX_STREAMS + 1, st, one, o0, l1, fin0, 1, &x, 0, &y, 0);

@@ -55,7 +55,7 @@ struct Walk {                        // one stream, fed through ts_plan_build, b
         const long cnt = final ? M - k * TS_H : (k1 - k) * TS_H;
         REQUIRE(cnt >= 0 && n_out[0] == cnt && g.n_out == cnt && g.n_in == n && g.in_off == 5 && g.out_off == 0 && g.blk_off == 0);
         REQUIRE(plan.blocks == (cnt + TS_H - 1) / TS_H && plan.blocks == k1 - k);
-        REQUIRE(TS_SID(g) == sid && TS_PARITY(g) == st[sid].parity && TS_FINAL(g) == (final ? 1 : 0) && TS_FRESH(g) == (k == 0 ? 1 : 0) && TS_PM(g) == pm);
+        REQUIRE(SP_SID(g) == sid && SP_PARITY(g) == st[sid].parity && SP_FINAL(g) == (final ? 1 : 0) && TS_FRESH(g) == (k == 0 ? 1 : 0) && TS_PM(g) == pm);
         REQUIRE(next[0].parity == (st[sid].parity ^ 1) && next[0].pm == pm);
         // what the kernel sees: positions relative to the carry's base
         const long base = k >= 1 ? (want_a(k - 1, pm) - TS_D > 0 ? want_a(k - 1, pm) - TS_D : 0) : 0;
@@ -125,7 +125,7 @@ static void check_offsets_and_refusals() {
     REQUIRE(n_out[0] == 0 && n_out[1] == 1000 && n_out[2] == 0 && n_out[3] == 600);
     REQUIRE(plan.seg[0].out_off == 0 && plan.seg[1].out_off == 0 && plan.seg[2].out_off == 1000 && plan.seg[3].out_off == 1000);
     REQUIRE(plan.seg[0].blk_off == 0 && plan.seg[1].blk_off == 0 && plan.seg[2].blk_off == 2 && plan.seg[3].blk_off == 2 && plan.blocks == 4);
-    for (int i = 0; i < 4; ++i) REQUIRE(plan.seg[i].in_off == off[i] && TS_SID(plan.seg[i]) == ids[i] && TS_PM(plan.seg[i]) == sp[ids[i]]);
+    for (int i = 0; i < 4; ++i) REQUIRE(plan.seg[i].in_off == off[i] && SP_SID(plan.seg[i]) == ids[i] && TS_PM(plan.seg[i]) == sp[ids[i]]);
     REQUIRE(next[0].R == 5 && next[0].k == 0 && next[1].R == 0 && next[2].R == 0 && next[3].R == 0);
     for (int i = 4; i < TS_MAX_STREAMS; ++i) REQUIRE(plan.seg[i].n_in == 0 && plan.seg[i].n_out == 0);
 
@@ -154,7 +154,7 @@ static void check_offsets_and_refusals() {
     REFUSED(4, st, dup, o2, l2, f2, 2, &x, &y);
     REFUSED(4, st, far, o0, l1, fin0, 1, &x, &y);
     REFUSED(4, st, neg, o0, l1, fin0, 1, &x, &y);
-    const long lneg[1] = {-1}, oneg[1] = {-1}, lbig[1] = {TS_MAX_CHUNK + 1}, lmax[1] = {TS_MAX_CHUNK};
+    const long lneg[1] = {-1}, oneg[1] = {-1}, lbig[1] = {SP_MAX_CHUNK + 1}, lmax[1] = {SP_MAX_CHUNK};
     REFUSED(4, st, one, o0, lneg, fin0, 1, &x, &y);
     REFUSED(4, st, one, oneg, l1, fin0, 1, &x, &y);
     REFUSED(4, st, one, o0, lbig, fin0, 1, &x, &y);
@@ -162,7 +162,7 @@ static void check_offsets_and_refusals() {
     REFUSED(4, st, slow, o0, lmax, fin1, 1, &x, &y);                     // 2^30 in at half speed would give 2^31 out
     REQUIRE(ts_plan_build(4, st, one, o0, lmax, fin0, 1, &x, &y, no, &plan, next) == nullptr);       // ... at 1.2 x it is legal
     TsStream big[TS_MAX_STREAMS] = {};
-    big[0].pm = 1000; big[0].R = TS_MAX_TOTAL - 5; big[0].k = ts_emitted(big[0].R, 1000, 0);
+    big[0].pm = 1000; big[0].R = SP_MAX_TOTAL - 5; big[0].k = ts_emitted(big[0].R, 1000, 0);
     REFUSED(4, big, one, o0, l1, fin0, 1, &x, &y);                       // a stream past 2^48 samples
     big[0].pm = 499;  big[0].R = 0; big[0].k = 0;
     REFUSED(4, big, one, o0, l1, fin0, 1, &x, &y);

@@ -43,7 +43,7 @@ struct Walk {                        // one stream, fed through vad_plan_build, 
         const long R1 = R + n, k1 = R1 / VAD_F, nf = k1 - k;
         REQUIRE(nf >= 0 && nfr[0] == nf && g.nf == nf && plan.frames == nf && g.f_off == 0 && g.n_in == n && g.in_off == 5);
         REQUIRE(vad_frame_count(st[sid], n) == nf);
-        REQUIRE(VAD_SID(g) == sid && VAD_PARITY(g) == st[sid].parity && VAD_FINAL(g) == (final ? 1 : 0) && g.k0 == k);
+        REQUIRE(SP_SID(g) == sid && SP_PARITY(g) == st[sid].parity && SP_FINAL(g) == (final ? 1 : 0) && g.k0 == k);
         REQUIRE(VAD_ON(g) == prm.on_q4 && VAD_OFF(g) == prm.off_q4 && VAD_MIN_ON(g) == prm.min_on && VAD_HANG(g) == prm.hang && g.hold == prm.hold && g.n_min == prm.n_min);
         REQUIRE(next[0].parity == (st[sid].parity ^ 1) && next[0].touched == 1 && next[0].prm.hang == prm.hang);
         // what the kernels see: positions relative to base = k F - 640; `lead` rule zeros, the carry, the chunk
@@ -108,7 +108,7 @@ static void check_offsets_and_refusals() {
     REQUIRE(vad_plan_build(4, st, ids, off, len, fin, 4, g_in, 1, g_flags, g_lag, g_power, g_floor, nfr, &plan, next) == nullptr && plan.n == 4);
     REQUIRE(nfr[0] == 0 && nfr[1] == 5 && nfr[2] == 0 && nfr[3] == 2 && plan.frames == 7);
     REQUIRE(plan.seg[0].f_off == 0 && plan.seg[1].f_off == 0 && plan.seg[2].f_off == 5 && plan.seg[3].f_off == 5);
-    for (int i = 0; i < 4; ++i) REQUIRE(plan.seg[i].in_off == off[i] && VAD_SID(plan.seg[i]) == ids[i] && VAD_HANG(plan.seg[i]) == four[ids[i]].hang);
+    for (int i = 0; i < 4; ++i) REQUIRE(plan.seg[i].in_off == off[i] && SP_SID(plan.seg[i]) == ids[i] && VAD_HANG(plan.seg[i]) == four[ids[i]].hang);
     REQUIRE(plan.seg[0].n_min == 1 && next[0].R == 5 && next[0].k == 0 && next[1].R == 0 && next[2].R == 0 && next[3].R == 0);
     for (int i = 4; i < VAD_MAX_STREAMS; ++i) REQUIRE(plan.seg[i].n_in == 0 && plan.seg[i].nf == 0);
 
@@ -149,16 +149,16 @@ static void check_offsets_and_refusals() {
     REFUSED(4, st, dup, o2, l2, f2, 2, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
     REFUSED(4, st, far, o0, l1, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
     REFUSED(4, st, neg, o0, l1, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
-    const long lneg[1] = {-1}, oneg[1] = {-1}, lbig[1] = {VAD_MAX_CHUNK + 1}, lmax[1] = {VAD_MAX_CHUNK};
+    const long lneg[1] = {-1}, oneg[1] = {-1}, lbig[1] = {SP_MAX_CHUNK + 1}, lmax[1] = {SP_MAX_CHUNK};
     REFUSED(4, st, one, o0, lneg, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
     REFUSED(4, st, one, oneg, l1, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
     REFUSED(4, st, one, o0, lbig, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
-    REQUIRE(vad_plan_build(4, st, one, o0, lmax, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no, &plan, next) == nullptr && no[0] == (77 + VAD_MAX_CHUNK) / VAD_F);
+    REQUIRE(vad_plan_build(4, st, one, o0, lmax, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no, &plan, next) == nullptr && no[0] == (77 + SP_MAX_CHUNK) / VAD_F);
     REFUSED(0, st, one, o0, l1, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
     REFUSED(VAD_MAX_STREAMS + 1, st, one, o0, l1, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no);
     {
         VadStream big[VAD_MAX_STREAMS] = {};
-        big[0].prm = VAD_DEFAULT_PARAMS; big[0].R = VAD_MAX_TOTAL - 5; big[0].k = big[0].R / VAD_F;
+        big[0].prm = VAD_DEFAULT_PARAMS; big[0].R = SP_MAX_TOTAL - 5; big[0].k = big[0].R / VAD_F;
         plan.n = 7;
         REQUIRE(vad_plan_build(4, big, one, o0, l1, fin0, 1, g_in, 0, g_flags, g_lag, g_power, g_floor, no, &plan, next) != nullptr && plan.n == 0);      // past 2^48 samples
         big[0].R = 0; big[0].k = 0; big[0].prm.hang = 0;

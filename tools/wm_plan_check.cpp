@@ -44,7 +44,7 @@ struct Walk {                        // one stream, fed through wm_plan_build, b
         const long want = final ? R1 - given : R1 / WM_S * WM_S - given;
         REQUIRE(n_out[0] == want && wm_out_len(st[sid], n, final) == want);
         REQUIRE(g.nb == blocks && plan.groups == blocks + 1 && g.g_off == 0 && g.out_off == 0 && g.in_off == 5 && g.n_in == n);
-        REQUIRE(WM_SID(g) == sid && WM_PARITY(g) == st[sid].parity && WM_FINAL(g) == (final ? 1 : 0) && g.t_q4 == t_q4);
+        REQUIRE(SP_SID(g) == sid && SP_PARITY(g) == st[sid].parity && SP_FINAL(g) == (final ? 1 : 0) && g.t_q4 == t_q4);
         REQUIRE(g.Lc == R % WM_S && g.Lc >= 0 && g.Lc < WM_S && given == R - g.Lc);              // the carry is the open block, never S
         REQUIRE(g.k0 == (R / WM_S) % WM_K && g.k0 >= 0 && g.k0 < WM_K);
         REQUIRE((long)g.Lc + g.n_in - (long)g.nb * WM_S >= 0 && (long)g.Lc + g.n_in - (long)g.nb * WM_S < WM_S);   // the tail fits a bank
@@ -88,8 +88,8 @@ static void check_long_walk() {
     long big = 0;
     while (w.R < (1L << 40) + 12345) {
         WmSeg g;
-        w.feed(3, WM_MAX_CHUNK - 7 * (big % 5), false, 0, &g); ++big;
-        REQUIRE(g.Lc < WM_S && g.k0 < WM_K && g.n_in <= WM_MAX_CHUNK && g.nb <= WM_MAX_CHUNK / WM_S + 1 && g.g_off == 0);
+        w.feed(3, SP_MAX_CHUNK - 7 * (big % 5), false, 0, &g); ++big;
+        REQUIRE(g.Lc < WM_S && g.k0 < WM_K && g.n_in <= SP_MAX_CHUNK && g.nb <= SP_MAX_CHUNK / WM_S + 1 && g.g_off == 0);
         w.feed(3, 1917, false, 0, &g);
         REQUIRE(g.Lc < WM_S && g.nb <= 1);
     }
@@ -155,12 +155,12 @@ static void check_feed_refusals() {
     REFUSED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
     REFUSED(wm_plan_build(4, st, zero, o1, len, fin, 1, g_in, 0, g_out, n_out, &plan, next));
     ACCEPTED(wm_plan_build(4, st, zero, z, z, fin, 1, g_in, 0, g_out, n_out, &plan, next));
-    l1[0] = WM_MAX_CHUNK + 1;
+    l1[0] = SP_MAX_CHUNK + 1;
     REFUSED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
-    l1[0] = WM_MAX_CHUNK;
+    l1[0] = SP_MAX_CHUNK;
     ACCEPTED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
-    REQUIRE(plan.seg[0].nb == (777 + WM_MAX_CHUNK) / WM_S && plan.groups == plan.seg[0].nb + 1);
-    st[0].R = WM_MAX_TOTAL - 4; st[0].given = st[0].R / WM_S * WM_S; memcpy(before, st, sizeof(st));
+    REQUIRE(plan.seg[0].nb == (777 + SP_MAX_CHUNK) / WM_S && plan.groups == plan.seg[0].nb + 1);
+    st[0].R = SP_MAX_TOTAL - 4; st[0].given = st[0].R / WM_S * WM_S; memcpy(before, st, sizeof(st));
     l1[0] = 5;
     REFUSED(wm_plan_build(4, st, zero, off, l1, fin, 1, g_in, 0, g_out, n_out, &plan, next));
     l1[0] = 4;
