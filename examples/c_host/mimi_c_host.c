@@ -1,12 +1,14 @@
 /*
  * The codec half of the boundary from plain C: libcsm_hip.so's include/mimi_hip.h with gcc, the HIP runtime and nothing else.
  *
- *     mimi_c_host <codec.blob> <out.pcm>
+ *     mimi_c_host <codec.blob> <out.pcm> [<finished.i16>]
  *
  * The blob (tests/test_c_host_gpu.py) holds MimiConfig, an image of the MimiWeights the Python shim hands to mimi_create -- its
  * pointers are the shim's device addresses -- the tensors behind those addresses, and codes [32][T].  Every pointer field is looked
  * up in the tensor table and replaced by this process's copy (decode side only), then: mimi_create -> mimi_decode (stateless, what
  * generator.py:299 does) twice -- the launch chain, then the chunk's middle from the hipGraph -- and the PCM is written to <out.pcm>.
+ * Then the decoded clip is metered (mimi_ld_pool_feed, mimi_ld_pool_integrate) and finished at -19 LUFS (mimi_fin_segments_ld), all on
+ * the same stream with no synchronisation between them; the int16 segment is written to <finished.i16> if it is named.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -107,6 +109,39 @@ int main(int argc, char** argv) {
     if (!o || fwrite(pcm, sizeof(float), (size_t)(hop * T), o) != (size_t)(hop * T)) DIE("cannot write %s", argv[2]);
     fclose(o);
     printf("decoded %d frames -> %ld samples\n", T, hop * T);
+
+    /* the decoded clip through the loudness meter (mimi_ld_pool_*), then finished at -19 LUFS with a ceiling of -1 dBFS
+     * (mimi_fin_segments_ld): P_T = rint(2^30 10^((-19 + 0.691) / 10)), C = floor(32767 10^(-1 / 20)); no lead, tail or fade */
+    mimi_ld_pool ld = NULL;
+    mimi_finisher fin = NULL;
+    if (mimi_ld_pool_create(1, 0, &ld) != 0) DIE("mimi_ld_pool_create: %s", mimi_ld_pool_last_error(NULL));
+    if (mimi_fin_create(&fin) != 0) DIE("mimi_fin_create: %s", mimi_fin_last_error(NULL));
+    const int32_t sid = 0, last = 1, none = 0, ceiling = 29203;
+    const long at = 0, n_smp = hop * T, pt = 15848927;
+    long n_hops = 0, seg_off = 0, seg_n = 0, row[MIMI_LD_ROW];
+    long *d_energy, *d_row;
+    int16_t* d_seg;
+    HIP(hipMalloc((void**)&d_energy, sizeof(long) * (size_t)(n_smp / MIMI_LD_HOP + 1)));
+    HIP(hipMalloc((void**)&d_row, sizeof(long) * MIMI_LD_ROW));
+    HIP(hipMalloc((void**)&d_seg, sizeof(int16_t) * (size_t)(n_smp + 1)));
+    if (mimi_ld_pool_feed(ld, &sid, &at, &n_smp, &last, 1, d_pcm, 0, d_energy, &n_hops, st) != 0) DIE("mimi_ld_pool_feed: %s", mimi_ld_pool_last_error(ld));
+    if (mimi_ld_pool_integrate(ld, &sid, 1, d_row, st) != 0) DIE("mimi_ld_pool_integrate: %s", mimi_ld_pool_last_error(ld));
+    const float* clips[1] = {d_pcm};
+    if (mimi_fin_segments_ld(fin, clips, &n_smp, &none, &none, &none, &pt, &ceiling, d_row, 1, d_seg, &seg_off, &seg_n, st) != 0)
+        DIE("mimi_fin_segments_ld: %s", mimi_fin_last_error(fin));
+    int16_t* seg = (int16_t*)malloc(sizeof(int16_t) * (size_t)(n_smp + 1));
+    HIP(hipMemcpyAsync(row, d_row, sizeof row, hipMemcpyDeviceToHost, st));
+    HIP(hipMemcpyAsync(seg, d_seg, sizeof(int16_t) * (size_t)n_smp, hipMemcpyDeviceToHost, st));
+    HIP(hipStreamSynchronize(st));
+    if (n_hops != n_smp / MIMI_LD_HOP || row[3] != n_hops || seg_off != 0 || seg_n != n_smp) DIE("the meter or the finisher miscounted");
+    printf("loudness: S %ld n %ld peak %ld hops %ld; finished %ld samples at -19 LUFS\n", row[0], row[1], row[2], row[3], seg_n);
+    if (argc > 3) {
+        FILE* q = fopen(argv[3], "wb");
+        if (!q || fwrite(seg, sizeof(int16_t), (size_t)seg_n, q) != (size_t)seg_n) DIE("cannot write %s", argv[3]);
+        fclose(q);
+    }
+    mimi_ld_pool_destroy(ld);
+    mimi_fin_destroy(fin);
     mimi_destroy(h);
     return 0;
 }

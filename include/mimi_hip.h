@@ -441,6 +441,71 @@ int  mimi_wm_pool_feed(mimi_wm_pool p, const int32_t* streams, const long* in_of
 int  mimi_wm_pool_detect(mimi_wm_pool p, const long* in_off, const long* n_in, const long* o0, const long* n_off, const uint64_t* expect,
                          const uint64_t* mask, int n, const void* in, int in_is_i16, int32_t* scores, long* out, void* stream);
 
+/* ---- A pool of LOUDNESS-METER streams, and the finisher that brings a clip to a stated loudness ----
+ * ITU-R BS.1770-4 / EBU R 128 for one channel, made integer, so the device computes THE RULE below bit for bit (tests/loudness_ref.py
+ * states it in NumPy).  24 kHz.  Constants in samples: T = 512 (taps), Q = 14, H = 2400 (hop, 100 ms).
+ *   - samples: fp32 input s[i] = clamp(rint(x[i] * 32768.0f), -32768, 32767), rint to nearest even, a non-finite x[i] gives 0; int16 input
+ *     s[i] = x[i]; s[i] = 0 for i < 0.
+ *   1. K-weighting as an integer FIR: the two BS.1770 biquads (high shelf, RLB high-pass) re-derived for 24 kHz, their cascaded impulse
+ *      response h cut at T taps, hq[j] = rint(h[j] * 2^Q) as int16 (tools/loudness_taps.py makes the table the library holds);
+ *      z[i] = (sum over j < T of hq[j] s[i - j] + 2^(Q-1)) >> Q, an arithmetic shift.  sum |hq| * 32768 = 0.806 * 2^31: the sum fits a signed
+ *      32-bit accumulator in any order, and |z| < 2^17.
+ *   2. hop h covers samples [h H, (h + 1) H): e[h] = sum z^2 < 2^45.3, an exact integer.  A clip of N samples has N / H hops; a trailing
+ *      partial hop has no energy, at `final` or ever.
+ *   3. gating blocks of 400 ms with 75 % overlap: E[j] = e[j] + e[j+1] + e[j+2] + e[j+3] for every j whose four hops are HELD.  A stream
+ *      holds its last `ring` hops (4096 unless create says otherwise: 409.6 s); the integrated value is the exact two-pass gating over what
+ *      the ring holds, not an approximation of a longer programme.  Absolute gate: E[j] > 1208568 = floor(4 H 2^30 10^((-70 + 0.691) / 10)),
+ *      which is -70 LUFS; S_abs, n_abs = sum and count of those blocks.  Relative gate, 10 LU under their mean, compared as integers:
+ *      10 n_abs E[j] > S_abs (below 10 * 4096 * 2^47.3 < 2^63: this is why a ring holds at most 4096 hops).  S, n = sum and count of the
+ *      blocks behind BOTH gates.  peak = max |s[i]| over every sample taken, a partial hop's included (0 .. 32768).
+ *      The integrated loudness, for display, is -0.691 + 10 log10(S / (n * 4 H * 32768^2)) LUFS; n == 0 has none.
+ * mimi_ld_pool_integrate writes MIMI_LD_ROW int64 per LISTED stream to `out` (device memory, row i for streams[i]): S, n, peak, hops, as of
+ * the stream's last feed (a `final` feed included: the row still describes the clip that ended, until the stream is fed again); a stream
+ * that was reset and not fed since gives zeros.  ONE launch, one wave per listed stream, no synchronisation: whatever reads `out` on the
+ * same HIP stream -- mimi_fin_segments_ld -- sees it.
+ * STREAMING: a stream's hop energies, concatenated over ANY chunk schedule, are bit for bit the one-shot result, and so is what integrate
+ * gives; they do not depend on which streams share the call, on list order or on the stream id.  Per stream the device keeps the samples
+ * from k H - 511 on (k the next unmeasured hop; at most 2910 int16, two banks flipped per call: a call reads one and writes the other),
+ * the ring and {hops, peak}; the host keeps the counts {R, k} and the bank.  final[i] != 0 ends the stream's clip: a partial hop is
+ * discarded and the stream is left fresh.  A fresh stream reads neither carry nor state, so mimi_ld_pool_reset is host arithmetic, no launch.
+ * mimi_ld_pool_feed: stream streams[i] gets n_in[i] >= 0 samples at in + in_off[i] ELEMENTS (in_is_i16: 0 = fp32, 1 = int16).  in, energy:
+ * device memory; streams, in_off, n_in, final: host arrays read before the call returns; n_hops: a host array WRITTEN before the call
+ * returns.  The hop energies are packed back to back: stream i owns energy[O_i .. O_i + n_hops[i]), O_i = n_hops[0] + .. + n_hops[i-1];
+ * mimi_ld_pool_hop_count says beforehand (host arithmetic only) what a feed of n_in samples would give stream sid now.  A feed that
+ * completes no hop is legal.  At most TWO launches per call whatever n and the lengths are: one workgroup per (stream, hop) for steps 1 and
+ * 2, then one wave per stream for the ring, the peak and the carry.  The plan travels in the kernel arguments: no host-to-device copy, no
+ * allocation, no synchronisation.  (This pool meters; it does not change a stream's samples.)
+ *
+ * mimi_fin_segments_ld is mimi_fin_segments with a per-segment target: pt[i] (host) is P_T, the K-weighted mean square of the target in
+ * int16 units, rint(2^30 10^((L + 0.691) / 10)) for L LUFS, or 0 for a segment that keeps the peak rule; ceiling[i] (host) is the sample
+ * ceiling C in 1 .. 32767; meter: DEVICE memory, MIMI_LD_ROW int64 per segment, row i = what mimi_ld_pool_integrate gave for clip i.  For
+ * a segment with pt[i] > 0 whose row has n > 0, steps 1 and 2 of the finishing rule become
+ *     g = float(min(sqrt((double(P_T * 4 H) * double(n)) / double(S)), double(C) / double(peak))), every conversion and operation IEEE
+ *     round-to-nearest in float64, then ONE rounding to fp32;  q_i = clamp(trunc(fl(fl(x_i * g) * 32767.0f)), -32767, 32767), 0 for a
+ *     non-finite x_i;
+ * lead, tail and fades as in mimi_fin_segments.  A segment with pt[i] == 0, or whose row has n == 0 (shorter than 400 ms, or nothing above
+ * -70 LUFS), is bit for bit what mimi_fin_segments gives.  Same two launches, same refusals, and -1 also for: a null pt, ceiling or meter, a
+ * misaligned meter, pt outside 0 .. 2^31, a ceiling outside 1 .. 32767.
+ * Returns -1 with a message in mimi_ld_pool_last_error, nothing enqueued and no state moved, for: n_streams outside [1, 64], a ring
+ * outside 4 .. 4096 and not 0 (create); n outside [1, n_streams], a duplicate or out-of-range id (reset, feed, integrate); a negative n_in
+ * or in_off, a null pointer, a misaligned buffer, an unknown format, a chunk of more than 2^30 samples, a stream of more than 2^48 samples
+ * since it was fresh (feed).  -2: a HIP error.  Drive ONE HIP stream per pool at a time.                                                  */
+#define MIMI_LD_MAX_STREAMS 64
+#define MIMI_LD_ROW 4
+#define MIMI_LD_HOP 2400
+typedef struct MimiLdPool* mimi_ld_pool;
+int  mimi_ld_pool_create(int n_streams, int ring_hops, mimi_ld_pool* out);       /* ring_hops == 0: 4096 */
+void mimi_ld_pool_destroy(mimi_ld_pool p);
+const char* mimi_ld_pool_last_error(mimi_ld_pool p);           /* p == NULL: why mimi_ld_pool_create failed (this thread) */
+int  mimi_ld_pool_reset(mimi_ld_pool p, const int32_t* streams, int n);
+long mimi_ld_pool_hop_count(mimi_ld_pool p, int sid, long n_in, int final);
+int  mimi_ld_pool_feed(mimi_ld_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                       const void* in, int in_is_i16, long* energy, long* n_hops, void* stream);
+int  mimi_ld_pool_integrate(mimi_ld_pool p, const int32_t* streams, int n, long* out, void* stream);
+int  mimi_fin_segments_ld(mimi_finisher p, const float* const* in, const long* n_in, const int32_t* lead, const int32_t* tail,
+                          const int32_t* fade, const long* pt, const int32_t* ceiling, const long* meter, int n, int16_t* out, long* out_off,
+                          long* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

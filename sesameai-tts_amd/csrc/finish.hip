@@ -16,6 +16,7 @@
 #include "../../include/mimi_hip.h"
 #include "common.cuh"
 #include "finish_plan.h"
+#include "loudness_plan.h"
 
 static_assert(MIMI_FIN_MAX_SEGMENTS == FIN_MAX_SEGMENTS, "header and plan disagree");
 static_assert(sizeof(FinPlan) <= 3200, "the plan must fit the kernel arguments");
@@ -97,6 +98,85 @@ __global__ void __launch_bounds__(FIN_BLOCK) k_fin_write(const FinPlan plan, con
         else if (has0) o[j0] = (int16_t)v0;                                          // the segment's last output, its pair half a neighbour's
         else if (has1) o[j0 + 1] = (int16_t)v1;                                      // its first output at an odd address
     }
+}
+
+// ---- mimi_fin_segments_ld: the same chain with a clip gain from the loudness meter's rows in the place of the peak rule ----
+// A segment's gain, or 0 where it keeps the peak rule: float64 from integers, rounded once to fp32 (include/mimi_hip.h spells it out).
+__device__ __forceinline__ float fin_ld_gain(long pt, int ceiling, const long* __restrict__ row) {
+    const long S = row[0], nb = row[1], pk = row[2];
+    if (pt <= 0 || nb <= 0 || S <= 0 || pk <= 0) return 0.0f;
+    const double g1 = sqrt(((double)(pt * (4 * LD_H)) * (double)nb) / (double)S);
+    const double g2 = (double)ceiling / (double)pk;
+    return (float)(g1 < g2 ? g1 : g2);
+}
+
+// output j of segment g under the gain `gain` (> 0), 0 <= j < g.m
+__device__ __forceinline__ int fin_sample_ld(const FinSeg& g, float gain, int j) {
+    int v = 0;
+    const int d = j - g.lead;
+    if (d >= 0 && d < g.n_in) {
+        const float x = g.in[d];
+        if (fabsf(x) <= FLT_MAX) {
+            const float u = fminf(fmaxf((x * gain) * 32767.0f, -32767.0f), 32767.0f);  // the bounds are integers: clamp and trunc commute
+            v = (int)u;                                                               // the cast truncates
+        }
+    }
+    const int n = g.nfade;
+    const int r = j < n ? j : (j >= g.m - n ? g.m - 1 - j : -1);
+    if (r >= 0) {
+        const float ramp = r == n - 1 ? (n == 1 ? 0.0f : 1.0f) : (float)((double)r * (1.0 / (double)(n - 1)));
+        v = (int)((float)v * ramp);
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(FIN_BLOCK) k_fin_write_ld(const FinPlan plan, const FinLd ld, const long* __restrict__ meter,
+                                                            const float* __restrict__ partials, int16_t* __restrict__ out) {
+    __shared__ float sh[FIN_BLOCK / 64];
+    const int b = blockIdx.x;
+    int i = 0;
+    while (i + 1 < plan.n && plan.seg[i + 1].wblk0 <= b) ++i;                        // (segment, output tile) of this block
+    const FinSeg& g = plan.seg[i];
+    const int n_pt = g.n_in == 0 ? 0 : (int)(((long)g.n_in + g.ptile - 1) / g.ptile);
+    const float part = (int)threadIdx.x < n_pt ? partials[i * FIN_MAX_PTILES + threadIdx.x] : 0.0f;
+    const float peak = fmaxf(fin_block_max(part, sh), FIN_PEAK_FLOOR);
+    const float gain = fin_ld_gain(ld.pt[i], ld.ceil[i], meter + (long)i * LD_ROW);  // uniform over the block
+    int16_t* o = out + g.out_off;
+    const int p0 = (b - g.wblk0) * (FIN_OUT_TILE / 2);
+#pragma unroll
+    for (int k = 0; k < FIN_OUT_TILE / 2 / FIN_BLOCK; ++k) {
+        const int j0 = 2 * (p0 + k * FIN_BLOCK + (int)threadIdx.x) - g.par;          // the aligned pair (j0, j0 + 1); j0 >= -1
+        if (j0 >= g.m) continue;
+        const bool has0 = j0 >= 0, has1 = j0 + 1 < g.m;
+        int v0 = 0, v1 = 0;
+        if (gain > 0.0f) {
+            v0 = has0 ? fin_sample_ld(g, gain, j0) : 0;
+            v1 = has1 ? fin_sample_ld(g, gain, j0 + 1) : 0;
+        } else {
+            v0 = has0 ? fin_sample(g, peak, j0) : 0;
+            v1 = has1 ? fin_sample(g, peak, j0 + 1) : 0;
+        }
+        if (has0 && has1) *(uint32_t*)(o + j0) = (uint32_t)(v0 & 0xFFFF) | ((uint32_t)v1 << 16);
+        else if (has0) o[j0] = (int16_t)v0;
+        else if (has1) o[j0 + 1] = (int16_t)v1;
+    }
+}
+
+extern "C" int mimi_fin_segments_ld(mimi_finisher p, const float* const* in, const long* n_in, const int32_t* lead, const int32_t* tail,
+                                    const int32_t* fade, const long* pt, const int32_t* ceiling, const long* meter, int n, int16_t* out,
+                                    long* out_off, long* n_out, void* stream) {
+    if (!p) return -1;
+    FinPlan plan;
+    FinLd ld;
+    if (const char* bad = fin_plan_build(in, n_in, lead, tail, fade, n, out, out_off, n_out, &plan)) { p->err = bad; return -1; }
+    if (const char* bad = fin_ld_build(pt, ceiling, n, meter, &ld)) { p->err = bad; return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    if (plan.pblocks > 0) k_fin_peak<<<dim3((unsigned)plan.pblocks), dim3(FIN_BLOCK), 0, s>>>(plan, p->partials);
+    if (plan.wblocks > 0) k_fin_write_ld<<<dim3((unsigned)plan.wblocks), dim3(FIN_BLOCK), 0, s>>>(plan, ld, meter, p->partials, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { p->err = std::string("mimi_fin_segments_ld: ") + hipGetErrorString(e); return -2; }
+    return 0;
 }
 
 extern "C" int mimi_fin_create(mimi_finisher* out) {

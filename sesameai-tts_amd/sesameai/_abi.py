@@ -155,6 +155,15 @@ MIMI_SIGNATURES = {
     "mimi_fin_last_error": (C.c_char_p, [_vp]),
     "mimi_fin_out_count": (_l, [_l, _l, _l]),
     "mimi_fin_segments": (_i, [_vp, C.POINTER(_vp), C.POINTER(_l), _vp, _vp, _vp, _i, _vp, C.POINTER(_l), C.POINTER(_l), _vp]),
+    "mimi_fin_segments_ld": (_i, [_vp, C.POINTER(_vp), C.POINTER(_l), _vp, _vp, _vp, C.POINTER(_l), _vp, _vp, _i, _vp, C.POINTER(_l),
+                                  C.POINTER(_l), _vp]),
+    "mimi_ld_pool_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "mimi_ld_pool_destroy": (None, [_vp]),
+    "mimi_ld_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_ld_pool_reset": (_i, [_vp, _vp, _i]),
+    "mimi_ld_pool_hop_count": (_l, [_vp, _i, _l, _i]),
+    "mimi_ld_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _i, _vp, C.POINTER(_l), _vp]),
+    "mimi_ld_pool_integrate": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mimi_ts_pool_create": (_i, [_i, C.POINTER(_vp)]),
     "mimi_ts_pool_destroy": (None, [_vp]),
     "mimi_ts_pool_last_error": (C.c_char_p, [_vp]),

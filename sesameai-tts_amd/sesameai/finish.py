@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Sequence, Union
+from typing import List, Optional, Sequence, Union
 
 import torch
 
@@ -25,11 +25,20 @@ class SegmentFinish:
     lead_ms: int = 500
     tail_ms: int = 100
     fade_ms: int = 50
+    loudness: Optional[float] = None     # LUFS: the clip is brought to this integrated loudness (BS.1770) instead of to its own peak
+    ceiling_db: float = -1.0             # ... but no sample above this, dB relative to full scale (only read with ``loudness``)
 
     def samples(self, sample_rate: int):
         if min(self.lead_ms, self.tail_ms, self.fade_ms) < 0:
             raise ValueError("lead_ms, tail_ms and fade_ms must be >= 0")
         return tuple(int(sample_rate) * int(ms) // 1000 for ms in (self.lead_ms, self.tail_ms, self.fade_ms))
+
+    def level(self):
+        """(P_T, C) of mimi_fin_segments_ld; P_T == 0: the peak rule"""
+        if self.loudness is None:
+            return 0, 32767
+        from .loudness import ceiling_i16, target_ms
+        return target_ms(self.loudness), ceiling_i16(self.ceiling_db)
 
 
 def per_clip(finish: Union[SegmentFinish, Sequence[SegmentFinish]], n: int) -> List[SegmentFinish]:
@@ -44,11 +53,14 @@ def per_clip(finish: Union[SegmentFinish, Sequence[SegmentFinish]], n: int) -> L
 
 class SegmentFinisher:
     """``finish(clips, finish)``: every clip (n_i,) fp32, n_i >= 0 -> its segment (lead + n_i + tail,) int16 on the device, views of one packed
-    buffer.  Up to 64 clips are one library call (two launches on the current torch stream, no synchronisation); more run in several."""
+    buffer.  Up to 64 clips are one library call (two launches on the current torch stream, no synchronisation); more run in several.
+    Where a clip's ``SegmentFinish`` names a ``loudness``, the call's clips are metered first (sesameai/loudness.py, three more launches)
+    and the call is mimi_fin_segments_ld; where none does, the calls are exactly those made without the keyword."""
 
     def __init__(self, device: Union[str, torch.device] = "cuda"):
         self.device = torch.device(device)
         self._h = C.c_void_p(None)
+        self.last_meter = None       # (m, 4) int64 on the device: {S, n, peak, hops} of the last call's clips that went through the meter
         with torch.cuda.device(self.device):
             rc = lib.mimi_fin_create(C.byref(self._h))
         if rc != 0:
@@ -62,7 +74,9 @@ class SegmentFinisher:
     def finish(self, clips: Sequence[torch.Tensor], finish: Union[SegmentFinish, Sequence[SegmentFinish]] = SegmentFinish(),
                sample_rate: int = 24000) -> List[torch.Tensor]:
         n = len(clips)
-        params = [f.samples(sample_rate) for f in per_clip(finish, n)]
+        each = per_clip(finish, n)
+        params = [f.samples(sample_rate) for f in each]
+        levels = [f.level() for f in each]
         if n == 0:
             return []
         # (kept alive until the launches are made; the stream orders their release behind the kernels)
@@ -75,14 +89,20 @@ class SegmentFinisher:
         res: List[torch.Tensor] = []
         base = 0
         for lo in range(0, n, MAX_SEGMENTS):
-            sub, par = parts[lo:lo + MAX_SEGMENTS], params[lo:lo + MAX_SEGMENTS]
+            sub, par, lev = parts[lo:lo + MAX_SEGMENTS], params[lo:lo + MAX_SEGMENTS], levels[lo:lo + MAX_SEGMENTS]
             m = len(sub)
             ptrs = (C.c_void_p * m)(*[c.data_ptr() if c.shape[0] else None for c in sub])
             off, n_out = (C.c_long * m)(), (C.c_long * m)()
+            head = (self._h, ptrs, (C.c_long * m)(*[int(c.shape[0]) for c in sub]), (C.c_int32 * m)(*[p[0] for p in par]),
+                    (C.c_int32 * m)(*[p[1] for p in par]), (C.c_int32 * m)(*[p[2] for p in par]))
             with torch.cuda.device(self.device):
-                self._check(lib.mimi_fin_segments(self._h, ptrs, (C.c_long * m)(*[int(c.shape[0]) for c in sub]),
-                                                  (C.c_int32 * m)(*[p[0] for p in par]), (C.c_int32 * m)(*[p[1] for p in par]),
-                                                  (C.c_int32 * m)(*[p[2] for p in par]), m, out.data_ptr() + 2 * base, off, n_out, stream))
+                if any(pt for pt, _ in lev):       # a clip of the call asks for a loudness: meter them all (three launches), then finish
+                    from .loudness import measure_rows
+                    self.last_meter = meter = measure_rows(sub, self.device)
+                    self._check(lib.mimi_fin_segments_ld(*head, (C.c_long * m)(*[pt for pt, _ in lev]), (C.c_int32 * m)(*[c for _, c in lev]),
+                                                         meter.data_ptr(), m, out.data_ptr() + 2 * base, off, n_out, stream))
+                else:
+                    self._check(lib.mimi_fin_segments(*head, m, out.data_ptr() + 2 * base, off, n_out, stream))
             res.extend(out[base + off[k]:base + off[k] + n_out[k]] for k in range(m))
             base += sum(n_out[:m])
         return res

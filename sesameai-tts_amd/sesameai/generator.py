@@ -92,6 +92,7 @@ class Generator:
     refill_row_layers = 600                    # ... about this many prompt-row x layer units per step
     _stream_pools: Optional[dict] = None       # {(slots, chunk frames): MimiStreamPool} of generate_many_stream, made on first use and kept
     _conversations: Optional[ConversationSet] = None   # the sessions opened on this Generator (open_session), made on first use
+    segment_meters: dict = {}                  # request -> (4,) int64 {S, n, peak, hops} on the device, of the last run that levelled
     _finisher = None                           # generate_segments' SegmentFinisher (sesameai/finish.py), made on first use and kept
 
     def __init__(self, model: Model, audio_tokenizer=None, text_tokenizer=None, max_batch_size: int = 1):
@@ -565,9 +566,13 @@ class Generator:
         stretch acts on the decoded fp32 clip, so lead and tail silence keep their lengths.
         ``watermark`` (None: the calls described above, exactly): True, "device" or a five-byte key -- the block's non-empty clips go through
         ONE device embed call (sesameai/watermarking.py) after the stretch and ``post``, in front of the finish: the mark that replaces the
-        host ``post`` hook, so a segment stays on the device between decode and finish."""
+        host ``post`` hook, so a segment stays on the device between decode and finish.
+        A ``SegmentFinish`` with ``loudness=`` (LUFS) brings its clip to that integrated loudness instead of to its own peak: the block's
+        clips are metered on the device (sesameai/loudness.py) in front of the ONE finish call, and ``segment_meters[i]`` keeps what the
+        meter said of request i, on the device.  Without it the calls are those described above, exactly."""
         from .finish import SegmentFinisher, per_clip
         how = per_clip(finish, len(prompts))
+        self.segment_meters = {}
         speeds = self._speeds(speed, len(prompts))
         key = self._mark_key(watermark)
         if self._finisher is None:
@@ -600,6 +605,9 @@ class Generator:
                     for j, y in zip(heard, embed([clips[j] for j in heard], key)):
                         clips[j] = y
                 pcm = self._finisher.finish(clips, [how[i] for i, _ in done], self.sample_rate)
+                if len(done) <= 64 and any(how[i].loudness is not None for i, _ in done):   # what the meter said of each clip, kept on the device
+                    for j, (i, _) in enumerate(done):
+                        self.segment_meters[i] = self._finisher.last_meter[j]
             if side is not None:
                 side.synchronize()
             for (i, _), seg in zip(done, pcm):

@@ -1,0 +1,128 @@
+"""Loudness on the device: a pool of stateful meter streams (include/mimi_hip.h, mimi_ld_pool_*), and the numbers the finisher needs to
+bring a clip to a stated loudness (mimi_fin_segments_ld).
+
+A served TTS is expected to hit a stated loudness (podcast and telephony targets are given in LUFS); dividing a clip by its own peak, as
+the reference does (tts_service.py:291), does not give one.  Here the measurement is ITU-R BS.1770-4 / EBU R 128 for one channel in exact
+integers -- K-weighting as a 512-tap integer FIR, 100 ms hop energies, 400 ms gating blocks behind the absolute and the relative gate --
+for up to 64 clips or streams with two launches per call, with state: a stream's hop energies, concatenated over any chunk schedule, are
+bit for bit the one-shot result.  All arithmetic is the library's; this file marshals, and ``lufs`` turns the integers into the number a
+person reads."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, List, NamedTuple, Optional, Sequence, Union
+
+import torch
+
+from ._stream_pool import StreamPool, _stream, int16_if_all, pack, shared_pool, split
+
+MAX_STREAMS = 64                 # MIMI_LD_MAX_STREAMS
+HOP = 2400                       # MIMI_LD_HOP: samples per hop at 24 kHz
+SAMPLE_RATE = 24000
+ROW = 4                          # MIMI_LD_ROW
+
+
+def lufs(S: int, n: int) -> float:
+    """The integrated loudness of {S, n}: -0.691 + 10 log10(S / (n 4 H 32768^2)); -inf where no block passed the gates."""
+    return -0.691 + 10.0 * math.log10(S / (n * 4.0 * HOP * 32768.0 ** 2)) if n > 0 and S > 0 else float("-inf")
+
+
+def target_ms(loudness: float) -> int:
+    """P_T of mimi_fin_segments_ld: the K-weighted mean square, in int16 units, of a signal at ``loudness`` LUFS."""
+    loudness = float(loudness)
+    if not -70.0 <= loudness <= 0.0:
+        raise ValueError("loudness: a target in LUFS, -70 .. 0")
+    return int(round(2.0 ** 30 * 10.0 ** ((loudness + 0.691) / 10.0)))
+
+
+def ceiling_i16(ceiling_db: float) -> int:
+    """C of mimi_fin_segments_ld: the sample ceiling in int16 units, from dB relative to full scale."""
+    ceiling_db = float(ceiling_db)
+    if ceiling_db > 0.0:
+        raise ValueError("ceiling_db: dB relative to full scale, <= 0")
+    return max(1, min(32767, int(math.floor(32767.0 * 10.0 ** (ceiling_db / 20.0)))))
+
+
+class Loudness(NamedTuple):
+    """What the meter says of one clip or stream: S and n, the sum and the count of the gating blocks behind both gates; the sample peak in
+    int16 units; the hops measured."""
+    S: int
+    n: int
+    peak: int
+    hops: int
+
+    @property
+    def lufs(self) -> float:
+        return lufs(self.S, self.n)
+
+
+class LoudnessPool(StreamPool):
+    """``n`` independent meter streams.  ``reset(ids)`` starts the listed streams afresh (host arithmetic, no launch); ``feed(ids, chunks,
+    final)`` gives every listed stream its new samples at 24 kHz, fp32 or int16, and returns the hop energies each completed: at most two
+    launches, no host-to-device copy of a plan, no synchronisation.  ``final`` ends a stream's clip: a partial hop is discarded and the
+    stream is fresh.  ``integrate(ids)`` gates what the streams' rings hold: one launch, a (len(ids), 4) int64 tensor {S, n, peak, hops}
+    that stays on the device; ``poll()`` reads every stream's (one small copy, the call's only synchronisation).  ring: hop energies a
+    stream holds, 4 .. 4096 (0: 4096)."""
+
+    def __init__(self, n: int, device: Union[str, torch.device] = "cuda", ring: int = 0):
+        super().__init__("mimi_ld_pool", n, device, int(n), int(ring))
+
+    def hop_count(self, sid: int, n_in: int, final: bool = False) -> int:
+        """Hops a feed of ``n_in`` samples would complete for stream ``sid`` now (host arithmetic)."""
+        return self._count("hop_count", sid, n_in, final)
+
+    def reset(self, ids: Sequence[int]) -> None:
+        ids = [int(i) for i in ids]
+        self._check(self._lib.mimi_ld_pool_reset(self._h, (C.c_int32 * max(len(ids), 1))(*ids), len(ids)))
+
+    @torch.inference_mode()
+    def feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False) -> List[torch.Tensor]:
+        """ids: n distinct stream ids; chunks[i]: (n_i,) fp32 or int16 at 24 kHz, n_i >= 0, CPU or device (int16 only if every chunk is);
+        final: one flag, or one per stream -> per stream the (K_i,) int64 energies of the hops it completed, views of one buffer."""
+        p = pack(chunks, self.device, int16_if_all, ids, final)
+        energy = torch.empty(max(sum(self._counts("hop_count", p)), 1), dtype=torch.int64, device=self.device)
+        n_hops = (C.c_long * p.m)()
+        self._check(self._lib.mimi_ld_pool_feed(self._h, *p.head, int(p.dtype == torch.int16), energy.data_ptr(), n_hops, _stream()))
+        return split(energy, n_hops[:len(p.ids)])
+
+    @torch.inference_mode()
+    def integrate(self, ids: Sequence[int]) -> torch.Tensor:
+        ids = [int(i) for i in ids]
+        out = torch.empty((max(len(ids), 1), ROW), dtype=torch.int64, device=self.device)
+        self._check(self._lib.mimi_ld_pool_integrate(self._h, (C.c_int32 * max(len(ids), 1))(*ids), len(ids), out.data_ptr(), _stream()))
+        return out[:len(ids)]
+
+    def poll(self) -> List[Loudness]:
+        return [Loudness(*r) for r in self.integrate(range(self.n_streams)).cpu().tolist()]
+
+
+_POOLS: Dict[str, LoudnessPool] = {}       # measure()'s pools, made on first use and kept
+
+
+@torch.inference_mode()
+def measure_rows(wavs: Sequence[torch.Tensor], device: Union[str, torch.device, None] = None) -> torch.Tensor:
+    """Up to 64 clips of different lengths, each (n_i,) fp32 or int16 at 24 kHz -> (len(wavs), 4) int64 {S, n, peak, hops} ON THE DEVICE,
+    on fresh streams with ``final``: three launches, no synchronisation.  What ``SegmentFinisher`` hands to mimi_fin_segments_ld."""
+    if not 1 <= len(wavs) <= MAX_STREAMS:
+        raise ValueError(f"measure takes 1 .. {MAX_STREAMS} clips a call")
+    pool = shared_pool(_POOLS, device, wavs[0], str, lambda dev: LoudnessPool(MAX_STREAMS, device=dev))
+    ids = list(range(len(wavs)))
+    pool.reset(ids)                    # (host arithmetic: also covers a stream that an earlier call, interrupted, left open)
+    pool.feed(ids, wavs, final=True)
+    return pool.integrate(ids)
+
+
+def measure(wavs: Sequence[torch.Tensor], device: Union[str, torch.device, None] = None) -> List[Loudness]:
+    """``measure_rows`` read back: one ``Loudness`` per clip (one small copy, the call's only synchronisation)."""
+    return [Loudness(*r) for r in measure_rows(wavs, device).cpu().tolist()]
+
+
+def per_request(loudness, n: int) -> List[Optional[float]]:
+    """None, one target for all n, or one per request (None among them) -> one per request."""
+    if loudness is None or isinstance(loudness, (int, float)):
+        return [None if loudness is None else float(loudness)] * n
+    loudness = [None if v is None else float(v) for v in loudness]
+    if len(loudness) != n:
+        raise ValueError(f"loudness: one target, or one per request ({n})")
+    return loudness

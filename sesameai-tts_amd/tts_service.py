@@ -14,6 +14,7 @@ WAV files (loaded with ``wave`` + polyphase resampling, encoded by the GPU Mimi 
 pre-tokenised ``<voice>.pt`` files holding ``[(text | token ids, codes[32,T]), ...]``.
 """
 import argparse
+import logging
 import os
 import re
 import sys
@@ -88,10 +89,11 @@ class TTS:
     watermark_kind = None           # None: silentcipher when it is importable, else the pass-through; "device": this build's own mark
 
     def __init__(self, device: str = "cuda", model_repo: str = "sesame/csm-1b", voice_dir: Optional[str] = None, max_batch_size: int = 1,
-                 watermark: Optional[str] = None) -> None:
+                 watermark: Optional[str] = None, loudness: Optional[float] = None, ceiling_db: float = -1.0) -> None:
         if watermark not in (None, "device"):
             raise ValueError("watermark must be None or 'device'")
         self.watermark_kind = watermark
+        self.loudness, self.ceiling_db = loudness, ceiling_db      # say / export_wav(.., batch=) bring every sentence to this LUFS (None: peak)
         self.device = device
         self.max_batch_size = int(max_batch_size)       # slots of the live batch say / export_wav may use with batch= (1: none)
         self.model_repo = model_repo
@@ -199,14 +201,18 @@ class TTS:
 
     def _segments_batched(self, sentences: List[str], batch: int, seed: Optional[int], fallback_duration: int, fade_duration: int,
                           start_silence_duration: int, end_silence_duration: int, temperature: float, topk: int, on_segment=None,
-                          speed: Optional[float] = None) -> List[np.ndarray]:
+                          speed: Optional[float] = None, loudness: Optional[float] = None) -> List[np.ndarray]:
         """The sentences of one text as independent requests of the continuously refilled batch (``batch`` of its slots), each against the
         cached voice context: the context rows are registered once per loaded voice with the prefix store, every sentence is one prompt
         (context + sentence) with the 30 s limit of ``generate_audio_segment``, sentence i gets seed ``seed + i``, and every segment is
         finished on the device (``Generator.generate_segments``).  A sentence whose prompt cannot be built gets ``fallback_duration`` ms of
         silence and the others still run; an error of the batch run itself propagates.  Requests complete in any order: a reorder buffer
-        hands ``on_segment`` and the ``> sentence ...`` lines out strictly in sentence order, each as soon as all earlier ones are out."""
+        hands ``on_segment`` and the ``> sentence ...`` lines out strictly in sentence order, each as soon as all earlier ones are out.
+        ``loudness`` (None: the service's own, and with that None the calls above exactly): every sentence is brought to this integrated
+        loudness in LUFS by the device finisher (sesameai/loudness.py) instead of to its own peak, no sample above ``ceiling_db``."""
         from sesameai.finish import SegmentFinish
+        loudness = self.loudness if loudness is None else loudness
+        level = {} if loudness is None else {"loudness": float(loudness), "ceiling_db": self.ceiling_db}
         g = self.generator
         slots = getattr(g, "_max_batch", 1)
         if isinstance(batch, bool) or not isinstance(batch, int) or not 2 <= batch <= slots:
@@ -249,6 +255,12 @@ class TTS:
 
         def on_result(k: int, pcm: torch.Tensor) -> None:
             segments[owner[k]] = pcm.cpu().numpy()
+            if level and logging.getLogger(__name__).isEnabledFor(logging.DEBUG):
+                from sesameai.loudness import lufs            # from the meter's integers; the copy above has already waited for them
+                row = self._segment_meter(k)
+                if row is not None:
+                    logging.getLogger(__name__).debug("sentence %d: %.2f LUFS before levelling (peak %d), target %.1f", owner[k],
+                                                      lufs(row[0], row[1]), row[2], level["loudness"])
             drain()
 
         drain()
@@ -262,17 +274,22 @@ class TTS:
             if speed is not None:                            # each block's clips: ONE stretch call, then the watermark, then the finish
                 kw["speed"] = speed
             g.generate_segments(prompts, max_audio_frames, temperature, topk,
-                                SegmentFinish(lead_ms=start_silence_duration, tail_ms=end_silence_duration, fade_ms=fade_duration),
+                                SegmentFinish(lead_ms=start_silence_duration, tail_ms=end_silence_duration, fade_ms=fade_duration, **level),
                                 seed=None if seed is None else [int(seed) + i for i in owner], on_result=on_result, slots=batch, **kw)
         drain()
         took, secs = time.time() - t0, sum(len(x) for x in segments) / sr
         print(f"Batch of {len(sentences)} sentences: {secs:.2f}s of audio in {took:.2f}s, RTF: {secs / max(took, 1e-9):.2f}x")
         return segments
 
+    def _segment_meter(self, k: int):
+        """[S, n, peak, hops] the device meter gave request k of the last batched run, or None (sesameai/loudness.py)"""
+        row = getattr(self.generator, "segment_meters", {}).get(k)
+        return None if row is None else row.cpu().tolist()
+
     def say(self, text: str, output_filename: Optional[str] = "combined_output.wav", fallback_duration: int = 1000,
             fade_duration: int = 50, start_silence_duration: int = 500, end_silence_duration: int = 100,
             temperature: float = 0.8, topk: int = 40, on_segment=None, batch: Optional[int] = None, seed: Optional[int] = None,
-            speed: Optional[float] = None) -> None:
+            speed: Optional[float] = None, loudness: Optional[float] = None) -> None:
         """reference: tts_service.py:313-470 -- the generation half: the text is split into sentences, each sentence is
         generated against the cached voice context (the shared prompt prefix is prefilled once: Model.prefill_prompt) and
         reported with the reference's line ``> sentence ... [Audio: 1.84s in 0.09s, RTF: 20.44x]``; a sentence that fails is
@@ -284,9 +301,14 @@ class TTS:
         (``_segments_batched``); ``on_segment`` and the lines still come in sentence order.  ``seed`` (with ``batch``): sentence i is
         sampled with seed ``seed + i``, whatever slot it takes.
         ``speed`` (None: the calls described above, exactly): a speech-rate factor in 0.5 .. 2.0 for every sentence, on either path
-        (``generate_audio_segment``)."""
+        (``generate_audio_segment``).  ``loudness`` (with ``batch``; None: the service's own, and with that None the calls described
+        above, exactly): every sentence comes out at this integrated loudness in LUFS instead of at its own peak."""
         import textwrap
         more = {} if speed is None else {"speed": speed}
+        if (loudness is not None or self.loudness is not None) and batch is None:
+            raise ValueError("loudness= needs batch=")
+        if loudness is not None:
+            more["loudness"] = loudness
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", textwrap.dedent(text).strip()) if s.strip()]
         if not sentences:
             print("No valid text to process")
@@ -329,11 +351,15 @@ class TTS:
 
     def export_wav(self, text: str, output_filename: str, fallback_duration: int = 1000, max_retries: int = 2,
                    temperature: float = 0.8, topk: int = 40, batch: Optional[int] = None, seed: Optional[int] = None,
-                   speed: Optional[float] = None) -> None:
+                   speed: Optional[float] = None, loudness: Optional[float] = None) -> None:
         """reference: tts_service.py:472-525.  ``batch`` / ``seed``: as for ``say`` (None: the calls of the reference's loop, exactly).
         ``max_retries`` applies only to the unbatched path: with ``batch`` a sentence whose prompt cannot be built gets the fallback
-        silence at once, and an error of the batch run itself propagates.  ``speed``: as for ``say``."""
+        silence at once, and an error of the batch run itself propagates.  ``speed``, ``loudness``: as for ``say``."""
         more = {} if speed is None else {"speed": speed}
+        if (loudness is not None or self.loudness is not None) and batch is None:
+            raise ValueError("loudness= needs batch=")
+        if loudness is not None:
+            more["loudness"] = loudness
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", text) if s.strip()]
         sr = self.generator.sample_rate
         segments = []
@@ -384,7 +410,13 @@ def parse_args(argv=None):
                         help="speech rate, 0.5 .. 2.0 (the pitch stays; default: as generated)")
     parser.add_argument("--watermark", type=str, default=None, choices=["device"],
                         help="device: mark every clip with this build's own keyed mark, on the GPU (default: silentcipher if it is installed)")
+    parser.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                        help="with --batch: bring every sentence to this integrated loudness, e.g. -19 (default: each to its own peak)")
     args = parser.parse_args(argv)
+    if args.loudness is not None and args.batch is None:
+        parser.error("--loudness needs --batch")
+    if args.loudness is not None and not -70.0 <= args.loudness <= 0.0:
+        parser.error("--loudness needs -70 <= LUFS <= 0")
     if args.device == "cpu":
         parser.error("this build runs the hot path on MI355X only; there is no -d cpu path (use the reference)")
     if args.batch is not None and args.batch < 2:
@@ -399,6 +431,8 @@ def parse_args(argv=None):
 def main():
     args = parse_args()
     made = {} if args.watermark is None else {"watermark": args.watermark}
+    if args.loudness is not None:
+        made["loudness"] = args.loudness
     tts = TTS(device=args.device, **made) if args.batch is None else TTS(device=args.device, max_batch_size=args.batch, **made)
     more = {} if args.batch is None else {"batch": args.batch, "seed": args.seed}
     if args.speed is not None:
