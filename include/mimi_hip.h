@@ -474,7 +474,7 @@ int  mimi_wm_pool_detect(mimi_wm_pool p, const long* in_off, const long* n_in, c
  * mimi_ld_pool_hop_count says beforehand (host arithmetic only) what a feed of n_in samples would give stream sid now.  A feed that
  * completes no hop is legal.  At most TWO launches per call whatever n and the lengths are: one workgroup per (stream, hop) for steps 1 and
  * 2, then one wave per stream for the ring, the peak and the carry.  The plan travels in the kernel arguments: no host-to-device copy, no
- * allocation, no synchronisation.  (This pool meters; it does not change a stream's samples.)
+ * allocation, no synchronisation.  (This feed meters and does not change a stream's samples; the leveler's feed is stated further down.)
  *
  * mimi_fin_segments_ld is mimi_fin_segments with a per-segment target: pt[i] (host) is P_T, the K-weighted mean square of the target in
  * int16 units, rint(2^30 10^((L + 0.691) / 10)) for L LUFS, or 0 for a segment that keeps the peak rule; ceiling[i] (host) is the sample
@@ -505,6 +505,50 @@ int  mimi_ld_pool_integrate(mimi_ld_pool p, const int32_t* streams, int n, long*
 int  mimi_fin_segments_ld(mimi_finisher p, const float* const* in, const long* n_in, const int32_t* lead, const int32_t* tail,
                           const int32_t* fade, const long* pt, const int32_t* ceiling, const long* meter, int n, int16_t* out, long* out_off,
                           long* n_out, void* stream);
+
+/* ---- The pool's streams as LIVE LEVELERS: a causal gain that follows the gated loudness measured so far ----
+ * n_out == n_in on every call and no sample is held back; exact integers plus a few spelled-out IEEE operations, so the device computes THE
+ * RULE below bit for bit (tests/leveler_ref.py states it in NumPy).  Samples s, hop energies e[h] (H = 2400) and the gating are the meter's.
+ * Per stream, set when the stream is made fresh: P_T, the target mean square (1 .. 2^31, as pt above); C, the ceiling (1 .. 32767);
+ * g0, the start gain, Q16 (1 .. gmax); gmax, the largest gain, Q16 (1 .. 2^22); sh, the slew shift (1 .. 16: at most 1 / 2^sh per hop).
+ *   1. pk[h] = max |s| over hop h; P[h] = max(pk[0 .. h]) since the stream was fresh (the ring does not limit it).
+ *   2. boundary gains A[j], the gain at the start of hop j, Q16: A[0] = A[1] = g0, and for j >= 1, from hops <= j - 1 only -- so A[j + 1] is
+ *      known before hop j's first sample arrives:  (S, n) = the two-pass gating over e[max(0, j - ring) .. j - 1];
+ *      T = A[j] if n == 0, else int(min(double(gmax), trunc(sqrt((double(P_T * 4 H) * double(n)) / double(S)) * 65536.0))), every operation
+ *      IEEE round-to-nearest in float64;  d = max(1, A[j] >> sh);  B = min(max(T, A[j] - d), A[j] + d);
+ *      cap = (C << 16) / max(P[j - 1], 1), an integer division;  A[j + 1] = max(1, min(B, cap, gmax)).
+ *   3. the sample at stream position r, j = r / H, i = r % H: gi = (A[j] (H - i) + A[j + 1] i) / H, an integer division in 64 bits.
+ *   4. the output has the input's format.  int16: v = (s gi + 2^15) >> 16, y = clamp(v, -C, C).  fp32: y = fl(x * gf) with
+ *      gf = float(gi) * 2^-16 (exact), then y > Cf -> Cf and y < -Cf -> -Cf with Cf = float(C) * 2^-15: a NaN stays a NaN, an infinite
+ *      sample becomes +-Cf.  `clipped` counts the samples the clamp changed.
+ *   5. final[i] != 0 ends the clip: a trailing partial hop is levelled like any other sample (its gains were known); the stream is then
+ *      fresh with the same parameters.
+ * A stream's outputs, gains and counters, concatenated over ANY chunk schedule, are the one-shot result, whatever the company in the call,
+ * the list order and the stream id.  Known limits: there is no look-ahead (a sudden onset is clamped at C, not anticipated), and the cap
+ * follows the all-time peak (one plosive holds the gain down for the rest of the clip).
+ * mimi_ld_pool_level_reset: host arithmetic, no launch.  The listed streams are fresh, in LEVELER mode, with pt[i], ceiling[i], g0_q16[i],
+ * gmax_q16[i], slew_shift[i] (host arrays).  A stream keeps one mode between resets: mimi_ld_pool_feed refuses a stream in leveler mode,
+ * mimi_ld_pool_level_feed a metering one; mimi_ld_pool_reset returns a stream to metering.  mimi_ld_pool_hop_count and
+ * mimi_ld_pool_integrate work on a leveler stream as on any other (they see its INPUT).
+ * mimi_ld_pool_level_feed: arguments as mimi_ld_pool_feed, and: out, DEVICE memory in the format of `in` -- stream i's samples go to
+ * out + in_off[i]; out == in is allowed, any other overlap is not; gain, int32 DEVICE memory: stream i owns n_hops[i] + 2 values, packed
+ * back to back, A[k0] .. A[k0 + n_hops[i] + 1] for k0 hops measured before the call: the boundaries of every hop the call touches, the open
+ * hop included.  At most THREE launches per call whatever n and the lengths are: the energies (and hop peaks), one wave per stream for
+ * steps 1 and 2 with the meter's ring, state and carry, then the samples in 16 KiB tiles spread over the chip.  The plan travels in the
+ * kernel arguments: no host-to-device copy, no allocation, no synchronisation.
+ * mimi_ld_pool_level_state writes MIMI_LD_LEVEL_ROW int64 per LISTED stream to `out` (device memory): the gain the open hop ends on
+ * (A[k + 1] for k measured hops), k, `clipped` since the stream was fresh, P[k - 1] (0 while k == 0).  ONE launch.  After `final` the row
+ * still describes the clip that ended, until the stream is fed again; a stream reset and not fed since gives {g0, 0, 0, 0}.
+ * Returns -1 with a message in mimi_ld_pool_last_error, nothing enqueued and no state moved, for everything mimi_ld_pool_reset / feed /
+ * integrate refuse, and for: pt outside 1 .. 2^31, a ceiling outside 1 .. 32767, gmax outside 1 .. 2^22, g0 outside 1 .. gmax, a slew
+ * shift outside 1 .. 16 (level_reset); a null or misaligned out or gain (level_feed); a stream in the wrong mode (feed, level_feed,
+ * level_state).  -2: a HIP error.                                                                                                        */
+#define MIMI_LD_LEVEL_ROW 4
+int  mimi_ld_pool_level_reset(mimi_ld_pool p, const int32_t* streams, const long* pt, const int32_t* ceiling, const int32_t* g0_q16,
+                              const int32_t* gmax_q16, const int32_t* slew_shift, int n);
+int  mimi_ld_pool_level_feed(mimi_ld_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                             const void* in, int in_is_i16, void* out, long* energy, int32_t* gain, long* n_hops, void* stream);
+int  mimi_ld_pool_level_state(mimi_ld_pool p, const int32_t* streams, int n, long* out, void* stream);
 
 #ifdef __cplusplus
 }

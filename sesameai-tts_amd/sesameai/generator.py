@@ -632,7 +632,7 @@ class Generator:
                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None,
                              sessions: Optional[Sequence[Optional[Conversation]]] = None,
                              out_sample_rate: Optional[int] = None, out_dtype: Optional[torch.dtype] = None, speed=None,
-                             watermark=None) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
+                             watermark=None, loudness=None) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
         Each batch slot is one stream of a ``MimiStreamPool`` (reset when a new utterance takes the slot); after every polled block
@@ -670,7 +670,14 @@ class Generator:
         then also one stream of a ``WatermarkPool`` (sesameai/watermarking.py), reset with the key when a request takes the slot, and each
         pool call's PCM goes through ONE embed call on the side stream, AFTER the stretch and BEFORE the resampler.  A request's chunks,
         concatenated, are bit for bit ``embed`` of its concatenated ``watermark=None`` chunks; a chunk of whole frames is whole blocks and
-        lags by nothing, behind a stretch the mark holds back fewer than 1920 samples, which come with the request's last chunk."""
+        lags by nothing, behind a stretch the mark holds back fewer than 1920 samples, which come with the request's last chunk.
+        ``loudness`` (None: the calls described above exactly, nothing imported): a target in LUFS or a ``Level`` (sesameai/loudness.py), or
+        one (or None) per request.  Each slot is then also one leveler stream of a ``LoudnessPool``, reset with the request's ``Level`` when
+        the request takes the slot, and each pool call's PCM goes through ONE ``level_feed`` on the side stream, AFTER the stretch and BEFORE
+        the watermark.  The leveler is causal and holds nothing back: chunk lengths stay what they were, and a request's chunks,
+        concatenated, are bit for bit ``level`` of its concatenated ``loudness=None`` chunks.  The gain starts at ``Level.start_gain`` and
+        follows the gated loudness measured so far by at most 1 / 2^slew_shift per 100 ms, under the ceiling.  A request whose level is None
+        never touches the pool: its chunks are those of a run without ``loudness``."""
         size = self._stream_buffer_size
         if first_chunk_frames is not None and not 1 <= int(first_chunk_frames) < size:
             raise ValueError(f"first_chunk_frames must be None or 1 .. {size - 1}")
@@ -703,6 +710,13 @@ class Generator:
             if ("stretcher", B) not in self._stream_pools:
                 self._stream_pools[("stretcher", B)] = TimeStretchPool(B, device=self.device)
             kw["stretcher"], kw["speeds"] = self._stream_pools[("stretcher", B)], speeds
+        if loudness is not None:
+            from .loudness import LoudnessPool, per_request_levels
+            levels = per_request_levels(loudness, len(prompts))
+            if any(v is not None for v in levels):
+                if ("leveler", B) not in self._stream_pools:
+                    self._stream_pools[("leveler", B)] = LoudnessPool(B, device=self.device)
+                kw["leveler"], kw["levels"] = self._stream_pools[("leveler", B)], levels
         if (key := self._mark_key(watermark)) is not None:
             from .watermarking import WatermarkPool, default_secret
             at = ("marker", B, default_secret(key))

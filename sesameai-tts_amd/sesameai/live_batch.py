@@ -346,13 +346,21 @@ class SlotStreams:
     slot = stream, and one five-byte key or None per REQUEST; a slot is reset with its request's key when the request takes it, and every pool
     call's PCM of the requests that have a key goes through ONE ``marker.feed`` on ``side`` AFTER the stretch and BEFORE the resampler,
     ``final`` for the slots whose request it closes -- an open block (only a stretch leaves one: a chunk of whole frames is whole blocks) comes
-    through with the request's last chunk, also when that chunk is empty at 24 kHz."""
+    through with the request's last chunk, also when that chunk is empty at 24 kHz.
+    ``leveler`` with ``levels`` (None: no levelling, today's calls exactly): a pool of at least ``slots`` loudness streams (``LoudnessPool``),
+    slot = stream, and one ``Level`` or None per REQUEST; a slot is reset with its request's ``Level`` when the request takes it, and every pool
+    call's PCM of the requests that have one goes through ONE ``leveler.level_feed`` on ``side`` AFTER the stretch and BEFORE the watermark --
+    the mark goes into the samples that leave -- ``final`` for the slots whose request it closes.  The leveler holds nothing back: a bare
+    ending hands it the stretch's tail, as the marker's does.  A request whose level is None never touches the pool."""
 
     def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None, resampler=None, stretcher=None,
-                 speeds: Optional[Sequence[Optional[float]]] = None, marker=None, marks: Optional[Sequence] = None):
+                 speeds: Optional[Sequence[Optional[float]]] = None, marker=None, marks: Optional[Sequence] = None, leveler=None,
+                 levels: Optional[Sequence] = None):
         self.pool, self.size, self.side, self.first, self.resampler = pool, size, side, first, resampler
         self.stretcher, self.speeds = stretcher, speeds
         self.marker, self.marks = marker, marks
+        self.leveler, self.levels = leveler, levels
+        self.level: list = [None] * slots                           # (leveler) the Level of the request that holds the slot
         self.mark: List[Optional[Sequence[int]]] = [None] * slots    # (marker) the key of the request that holds the slot
         self.speed: List[Optional[float]] = [None] * slots          # (stretcher) the speed of the request that holds the slot
         self.started: List[bool] = [False] * slots                  # whether the slot's request has had a chunk (``first`` only)
@@ -395,6 +403,11 @@ class SlotStreams:
                         self.speed[s_] = self.speeds[owner[s_]]
                     if quick := [s_ for s_ in fresh if self.speed[s_] is not None]:
                         self.stretcher.reset(quick, [self.speed[s_] for s_ in quick])
+                if self.leveler is not None:
+                    for s_ in fresh:
+                        self.level[s_] = self.levels[owner[s_]]
+                    if even := [s_ for s_ in fresh if self.level[s_] is not None]:
+                        self.leveler.level_reset(even, [self.level[s_] for s_ in even])
                 if self.marker is not None:
                     for s_ in fresh:
                         self.mark[s_] = self.marks[owner[s_]]
@@ -418,6 +431,17 @@ class SlotStreams:
                         calls[k] = (slots, frames, pcm)
                 if bare := [s_ for s_ in ending if s_ not in final and self.speed[s_] is not None]:
                     tails = dict(zip(bare, self.stretcher.feed(bare, [self.no_pcm.float()] * len(bare), True)))
+            if self.leveler is not None:                            # ONE leveler call per pool call, and one for the empty closing chunks
+                for k, (slots, frames, pcm) in enumerate(calls):
+                    if even := [j for j, s_ in enumerate(slots) if self.level[s_] is not None]:
+                        ys = self.leveler.level_feed([slots[j] for j in even], [pcm[j][0] for j in even],
+                                                     [slots[j] in ending and final[slots[j]] == k for j in even])
+                        pcm = [pcm[j] for j in range(len(slots))]
+                        for j, y in zip(even, ys):
+                            pcm[j] = y.unsqueeze(0)
+                        calls[k] = (slots, frames, pcm)
+                if bare := [s_ for s_ in ending if s_ not in final and self.level[s_] is not None]:
+                    tails.update(zip(bare, self.leveler.level_feed(bare, [tails.get(s_, self.no_pcm.float()) for s_ in bare], True)))
             if self.marker is not None:                             # ONE watermark call per pool call, and one for the empty closing chunks
                 for k, (slots, frames, pcm) in enumerate(calls):
                     if keyed := [j for j, s_ in enumerate(slots) if self.mark[s_] is not None]:

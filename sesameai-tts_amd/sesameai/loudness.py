@@ -5,8 +5,10 @@ A served TTS is expected to hit a stated loudness (podcast and telephony targets
 the reference does (tts_service.py:291), does not give one.  Here the measurement is ITU-R BS.1770-4 / EBU R 128 for one channel in exact
 integers -- K-weighting as a 512-tap integer FIR, 100 ms hop energies, 400 ms gating blocks behind the absolute and the relative gate --
 for up to 64 clips or streams with two launches per call, with state: a stream's hop energies, concatenated over any chunk schedule, are
-bit for bit the one-shot result.  All arithmetic is the library's; this file marshals, and ``lufs`` turns the integers into the number a
-person reads."""
+bit for bit the one-shot result.  A stream of the same pool can also LEVEL what it is fed (mimi_ld_pool_level_*: ``Level``,
+``LoudnessPool.level_reset / level_feed / level_state``, ``level``): a causal gain that follows the gated loudness measured so far, hop by
+hop, with as many samples out as in on every call -- what ``generate_many_stream(loudness=)`` puts behind each slot.  All arithmetic is the
+library's; this file marshals, and ``lufs`` turns the integers into the number a person reads."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,7 +17,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
-from ._stream_pool import StreamPool, _stream, int16_if_all, pack, shared_pool, split
+from ._stream_pool import StreamPool, _stream, int16_if_all, one_format, pack, shared_pool, split
 
 MAX_STREAMS = 64                 # MIMI_LD_MAX_STREAMS
 HOP = 2400                       # MIMI_LD_HOP: samples per hop at 24 kHz
@@ -96,6 +98,93 @@ class LoudnessPool(StreamPool):
     def poll(self) -> List[Loudness]:
         return [Loudness(*r) for r in self.integrate(range(self.n_streams)).cpu().tolist()]
 
+    # -- the streams as live levelers (mimi_ld_pool_level_*): a stream levels from ``level_reset`` until ``reset`` returns it to metering
+
+    def level_reset(self, ids: Sequence[int], levels: Union["Level", Sequence["Level"]]) -> None:
+        """The listed streams are fresh, in leveler mode, each with its ``Level`` (one for all, or one per id): host arithmetic, no launch."""
+        ids = [int(i) for i in ids]
+        levels = [levels] * len(ids) if isinstance(levels, Level) else list(levels)
+        assert len(levels) == len(ids), "one Level per id"
+        q = [lv.params() for lv in levels]
+        m = max(len(ids), 1)
+        cols = [(C.c_long * m)(*[v[0] for v in q])] + [(C.c_int32 * m)(*[v[k] for v in q]) for k in range(1, 5)]
+        self._check(self._lib.mimi_ld_pool_level_reset(self._h, (C.c_int32 * m)(*ids), *cols, len(ids)))
+
+    @torch.inference_mode()
+    def level_feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False,
+                   in_place: bool = False) -> List[torch.Tensor]:
+        """ids: n distinct leveler streams; chunks[i]: (n_i,) fp32 or int16 at 24 kHz, n_i >= 0 (one format a call: the output keeps it);
+        final: one flag, or one per stream -> per stream its n_i levelled samples, views of one buffer: nothing is held back.  At most
+        three launches, no host-to-device copy of a plan, no synchronisation.  ``last_energies[i]`` are the hop energies stream i
+        completed, ``last_gains[i]`` its n_hops + 2 boundary gains (Q16, int32) from the first hop the call touched to the end of the
+        open one: device views.  in_place: the packed input buffer is also the output."""
+        p = pack(chunks, self.device, one_format, ids, final)
+        counts = self._counts("hop_count", p)
+        energy = torch.empty(max(sum(counts), 1), dtype=torch.int64, device=self.device)
+        gain = torch.empty(sum(counts) + 2 * p.m, dtype=torch.int32, device=self.device)
+        out = p.packed if in_place else torch.empty_like(p.packed)
+        n_hops = (C.c_long * p.m)()
+        self._check(self._lib.mimi_ld_pool_level_feed(self._h, *p.head, int(p.dtype == torch.int16), out.data_ptr(), energy.data_ptr(),
+                                                      gain.data_ptr(), n_hops, _stream()))
+        hops = [int(v) for v in n_hops[:len(p.ids)]]
+        self.last_energies, self.last_gains = split(energy, hops), split(gain, [h + 2 for h in hops])
+        return split(out, p.lens)
+
+    @torch.inference_mode()
+    def level_state(self, ids: Sequence[int]) -> torch.Tensor:
+        """(len(ids), 4) int64 ON THE DEVICE: {the gain the open hop ends on (Q16), hops, samples clamped since fresh, the running peak of
+        the complete hops}, as of each stream's last feed: one launch."""
+        ids = [int(i) for i in ids]
+        out = torch.empty((max(len(ids), 1), LEVEL_ROW), dtype=torch.int64, device=self.device)
+        self._check(self._lib.mimi_ld_pool_level_state(self._h, (C.c_int32 * max(len(ids), 1))(*ids), len(ids), out.data_ptr(), _stream()))
+        return out[:len(ids)]
+
+    def poll_level(self, ids: Optional[Sequence[int]] = None) -> List["LevelState"]:
+        """``level_state`` read back (one small copy, the call's only synchronisation); ids None: every stream -- all must be levelers."""
+        return [LevelState(*r) for r in self.level_state(range(self.n_streams) if ids is None else ids).cpu().tolist()]
+
+
+LEVEL_ROW = 4                    # MIMI_LD_LEVEL_ROW
+GAIN_ONE = 65536                 # a gain of 1 in Q16
+GAIN_LIMIT = 1 << 22             # the largest gmax: 64 x
+
+
+class Level(NamedTuple):
+    """How one live stream is levelled (include/mimi_hip.h, mimi_ld_pool_level_reset): ``loudness`` the target in LUFS; ``ceiling_db`` the
+    sample ceiling in dB relative to full scale; ``start_gain`` the linear gain the stream starts on, before anything is measured;
+    ``max_gain_db`` the largest gain, 6 dB a doubling (24 -> 16 x); ``slew_shift`` = sh: the gain moves by at most 1 / 2^sh of itself per
+    100 ms hop (4: about 0.53 dB)."""
+    loudness: float
+    ceiling_db: float = -1.0
+    start_gain: float = 1.0
+    max_gain_db: float = 24.0
+    slew_shift: int = 4
+
+    def params(self) -> tuple:
+        """(P_T, C, g0, gmax, sh): the integers the library takes, checked against its ranges."""
+        gmax = int(round(GAIN_ONE * 2.0 ** (float(self.max_gain_db) / 6.0)))
+        g0 = int(round(float(self.start_gain) * GAIN_ONE))
+        if not 1 <= gmax <= GAIN_LIMIT:
+            raise ValueError("max_gain_db: -96 .. 36 dB (a Q16 gain of 1 .. 2^22)")
+        if not 1 <= g0 <= gmax:
+            raise ValueError("start_gain: above 0 and at most the largest gain")
+        if int(self.slew_shift) != self.slew_shift or not 1 <= int(self.slew_shift) <= 16:
+            raise ValueError("slew_shift: an integer, 1 .. 16")
+        return target_ms(self.loudness), ceiling_i16(self.ceiling_db), g0, gmax, int(self.slew_shift)
+
+
+class LevelState(NamedTuple):
+    """What ``level_state`` says of one stream: ``gain_q16`` the gain its open hop ends on; the hops measured; the samples the ceiling
+    clamped; the running sample peak of the complete hops, in int16 units."""
+    gain_q16: int
+    hops: int
+    clipped: int
+    peak: int
+
+    @property
+    def gain(self) -> float:
+        return self.gain_q16 / GAIN_ONE
+
 
 _POOLS: Dict[str, LoudnessPool] = {}       # measure()'s pools, made on first use and kept
 
@@ -116,6 +205,38 @@ def measure_rows(wavs: Sequence[torch.Tensor], device: Union[str, torch.device, 
 def measure(wavs: Sequence[torch.Tensor], device: Union[str, torch.device, None] = None) -> List[Loudness]:
     """``measure_rows`` read back: one ``Loudness`` per clip (one small copy, the call's only synchronisation)."""
     return [Loudness(*r) for r in measure_rows(wavs, device).cpu().tolist()]
+
+
+@torch.inference_mode()
+def level(wavs: Sequence[torch.Tensor], loudness: Union[float, "Level", Sequence[Union[float, "Level"]]],
+          device: Union[str, torch.device, None] = None) -> List[torch.Tensor]:
+    """Up to 64 clips of different lengths, each (n_i,) fp32 or int16 at 24 kHz (one format a call), levelled the way a live stream is:
+    on fresh streams with ``final``, in ONE ``level_feed`` -- three launches, no synchronisation.  ``loudness``: a target in LUFS or a
+    ``Level``, for all clips or one per clip.  What ``generate_many_stream(loudness=)`` hands out, chunk by chunk, concatenated."""
+    if not 1 <= len(wavs) <= MAX_STREAMS:
+        raise ValueError(f"level takes 1 .. {MAX_STREAMS} clips a call")
+    levels = per_request_levels(loudness, len(wavs))
+    if any(v is None for v in levels):
+        raise ValueError("level: every clip needs a target")
+    pool = shared_pool(_POOLS, device, wavs[0], lambda dev: ("level", str(dev)), lambda dev: LoudnessPool(MAX_STREAMS, device=dev))
+    ids = list(range(len(wavs)))
+    pool.level_reset(ids, levels)
+    return pool.level_feed(ids, wavs, final=True)
+
+
+def per_request_levels(loudness, n: int) -> List[Optional[Level]]:
+    """None, one LUFS value or ``Level`` for all n, or one per request (None among them) -> one ``Level`` or None per request, checked."""
+    def one(v):
+        lv = None if v is None else v if isinstance(v, Level) else Level(float(v))
+        if lv is not None:
+            lv.params()
+        return lv
+    if loudness is None or isinstance(loudness, (int, float, Level)):
+        return [one(loudness)] * n
+    loudness = [one(v) for v in loudness]
+    if len(loudness) != n:
+        raise ValueError(f"loudness: one target, or one per request ({n})")
+    return loudness
 
 
 def per_request(loudness, n: int) -> List[Optional[float]]:
