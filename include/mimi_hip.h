@@ -550,6 +550,64 @@ int  mimi_ld_pool_level_feed(mimi_ld_pool p, const int32_t* streams, const long*
                              const void* in, int in_is_i16, void* out, long* energy, int32_t* gain, long* n_hops, void* stream);
 int  mimi_ld_pool_level_state(mimi_ld_pool p, const int32_t* streams, int n, long* out, void* stream);
 
+/* ---- A pool of LOOK-AHEAD PEAK-LIMITER streams (nothing above a ceiling, and no clipped waveform: behind the leveler, or alone) ----
+ * A gain that starts to fall L samples AHEAD of a peak, is what the peak requires exactly on it, and recovers at a fixed step per sample.
+ * Exact integers plus a few spelled-out IEEE operations, so the device computes THE RULE below bit for bit (tests/limiter_ref.py states it
+ * in NumPy).  Sample peaks only: no oversampled (true-peak) detection, one channel, one band.  ONE = 65536 is a gain of 1 in Q16.
+ * Per stream, set when the stream is made fresh: C, the ceiling (1 .. 32767); L, the look-ahead in samples (1 .. 480); rho, the release
+ * step in Q16 per sample (8 .. 65536; K = ceil(ONE / rho) <= 8192 samples from silence of gain back to 1); hr, the drive shift (0 .. 4):
+ * the input is multiplied by exactly 2^hr in front of the limiter.  A stream is preceded and followed by silence: m[r] = ONE for r < 0 and
+ * for r >= the clip's length.
+ *   1. magnitude, an integer.  int16: a = |s 2^hr|.  fp32: t = fl(|x| * 2^(15 + hr)), an exact scaling; a = 0 for a NaN, a = 2^30 if
+ *      t >= 2^30 (an infinite sample too), else a = int(ceil(t)).
+ *   2. required gain, Q16: m[r] = ONE if a[r] <= C, else (C << 16) / a[r], an integer division.
+ *   3. look-ahead minimum: w[r] = min(m[r .. r + L]), for r >= -L.
+ *   4. release: e[r] = min(w[r], e[r - 1] + rho), e = ONE before r = -L; equivalently, and exactly,
+ *      e[r] = min over j in [r - K, r] of (w[j] + (r - j) rho): terms further back cannot win because w <= ONE.
+ *   5. attack smoothing: g[r] = (e[r - L] + .. + e[r]) / (L + 1), an integer division.  Every e[r - k] <= w[r - k] <= m[r], so g[r] <= m[r].
+ *   6. the output has the input's format.  int16: y = (s 2^hr g + 2^15) >> 16, which cannot leave [-C, C].  fp32: y = fl(fl(x * 2^hr) * gf)
+ *      with gf = float(g) * 2^-16 (exact), two multiplies, NOT fused; then y > Cf -> Cf and y < -Cf -> -Cf with Cf = float(C) * 2^-15.
+ *      The clamp fires only where a = 2^30, an infinite or absurd sample; a NaN stays a NaN and moves no other sample.  (Where such a
+ *      sample's own g is 0 -- only possible with C < 16384 -- inf * 0 is a NaN, by IEEE.)
+ *   7. STREAMING: sample r comes out once the stream has received r + L + 1 samples, or at `final`: the latency is L samples.  With R
+ *      received and E emitted after the call's n_in are counted, a call emits max(0, R - L) - E, or R - E at `final`, which then leaves the
+ *      stream fresh with the same parameters; mimi_lim_pool_out_count is host arithmetic.  A stream's outputs, concatenated over ANY chunk
+ *      schedule, are bit for bit the one-shot result; they do not depend on which streams share the call, on list order or on the stream id.
+ *   8. the state row, MIMI_LIM_ROW int64 since the stream was fresh: the smallest g emitted (ONE while none), samples emitted, samples
+ *      with g < ONE, samples the clamp changed.
+ * Per stream the device keeps the required gains of its last K + 2 L positions and the at most L samples it holds (two banks flipped per
+ * call: a call reads one and writes the other) and the row; the host keeps {R, E, bank, parameters}.  A fresh stream reads neither, so
+ * mimi_lim_pool_reset is host arithmetic, no launch.  A stream must be reset once before it is fed: a new pool's streams have no parameters.
+ * mimi_lim_pool_feed: stream streams[i] gets n_in[i] >= 0 samples at in + in_off[i] ELEMENTS; fmt: 0 = fp32, 1 = int16, one per call; a
+ * stream that HOLDS samples takes only their format.  in, out: device memory in that format, which must not overlap; streams, in_off, n_in,
+ * final: host arrays read before the call returns; n_out: a host array WRITTEN before the call returns.  Outputs are packed back to back:
+ * stream i owns out[O_i .. O_i + n_out[i]), O_i = n_out[0] + .. + n_out[i-1].  At most TWO launches per call whatever n and the lengths
+ * are: one workgroup per stream for the carry, then one per (stream, tile of 4096 outputs), which stages the tile's required gains with
+ * their halo (L ahead, K + L behind) in LDS and runs steps 3 to 5 there as a doubling minimum and two workgroup scans -- no walk over a
+ * clip; samples move as 16-byte vectors wherever a line lies wholly inside the chunk.  The plan travels in the kernel arguments: no
+ * host-to-device copy, no allocation, no synchronisation.
+ * mimi_lim_pool_state writes the row of every LISTED stream to `out` (device memory), as of the stream's last feed (a `final` feed
+ * included: the row still describes the clip that ended, until the stream is fed again); a stream reset and not fed since gives
+ * {ONE, 0, 0, 0}.  ONE launch.
+ * Returns -1 with a message in mimi_lim_pool_last_error, nothing enqueued and no state moved, for: n_streams outside [1, 64] (create); n
+ * outside [1, n_streams], a duplicate or out-of-range id (reset, feed, state); a ceiling outside 1 .. 32767, a look-ahead outside 1 .. 480,
+ * a release step outside 8 .. 65536, a drive shift outside 0 .. 4 (reset); a negative n_in or in_off, a null pointer, a misaligned buffer,
+ * an unknown format, a chunk that takes or gives more than 2^30 samples, a stream of more than 2^48 samples since it was fresh, a stream
+ * without parameters, a stream that holds samples of the other format, in and out that overlap (feed).  -2: a HIP error.  Drive ONE HIP
+ * stream per pool at a time.                                                                                                              */
+#define MIMI_LIM_MAX_STREAMS 64
+#define MIMI_LIM_ROW 4
+typedef struct MimiLimPool* mimi_lim_pool;
+int  mimi_lim_pool_create(int n_streams, mimi_lim_pool* out);
+void mimi_lim_pool_destroy(mimi_lim_pool p);
+const char* mimi_lim_pool_last_error(mimi_lim_pool p);         /* p == NULL: why mimi_lim_pool_create failed (this thread) */
+int  mimi_lim_pool_reset(mimi_lim_pool p, const int32_t* streams, const int32_t* ceiling, const int32_t* lookahead, const int32_t* rho,
+                         const int32_t* drive_shift, int n);
+long mimi_lim_pool_out_count(mimi_lim_pool p, int sid, long n_in, int final);
+int  mimi_lim_pool_feed(mimi_lim_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                        const void* in, void* out, long* n_out, int fmt, void* stream);
+int  mimi_lim_pool_state(mimi_lim_pool p, const int32_t* streams, int n, long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,13 @@ MIMI_SIGNATURES = {
     "mimi_ld_pool_level_reset": (_i, [_vp, _vp, C.POINTER(_l), _vp, _vp, _vp, _vp, _i]),
     "mimi_ld_pool_level_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(_l), _vp]),
     "mimi_ld_pool_level_state": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mimi_lim_pool_create": (_i, [_i, C.POINTER(_vp)]),
+    "mimi_lim_pool_destroy": (None, [_vp]),
+    "mimi_lim_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_lim_pool_reset": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "mimi_lim_pool_out_count": (_l, [_vp, _i, _l, _i]),
+    "mimi_lim_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _vp, C.POINTER(_l), _i, _vp]),
+    "mimi_lim_pool_state": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mimi_ts_pool_create": (_i, [_i, C.POINTER(_vp)]),
     "mimi_ts_pool_destroy": (None, [_vp]),
     "mimi_ts_pool_last_error": (C.c_char_p, [_vp]),

@@ -632,7 +632,7 @@ class Generator:
                              seed: Optional[Sequence[Optional[int]]] = None, refill_group: int = 1, first_chunk_frames: Optional[int] = None,
                              sessions: Optional[Sequence[Optional[Conversation]]] = None,
                              out_sample_rate: Optional[int] = None, out_dtype: Optional[torch.dtype] = None, speed=None,
-                             watermark=None, loudness=None) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
+                             watermark=None, loudness=None, limiter=None) -> PyGenerator[Tuple[int, torch.Tensor, torch.Tensor, bool], None, None]:
         """``generate_many`` that hands out audio as it comes into existence: yields ``(request index, pcm chunk (samples,) fp32,
         the chunk's frames [t][32] int32 CPU, last)`` for every request while the continuously refilled batch keeps generating.
         Each batch slot is one stream of a ``MimiStreamPool`` (reset when a new utterance takes the slot); after every polled block
@@ -677,7 +677,16 @@ class Generator:
         the watermark.  The leveler is causal and holds nothing back: chunk lengths stay what they were, and a request's chunks,
         concatenated, are bit for bit ``level`` of its concatenated ``loudness=None`` chunks.  The gain starts at ``Level.start_gain`` and
         follows the gated loudness measured so far by at most 1 / 2^slew_shift per 100 ms, under the ceiling.  A request whose level is None
-        never touches the pool: its chunks are those of a run without ``loudness``."""
+        never touches the pool: its chunks are those of a run without ``loudness``.
+        ``limiter`` (None: the calls described above exactly, nothing imported): True for the default ``Limit`` (sesameai/limiter.py), a
+        ``Limit``, or one of these (or None) per request.  Each slot is then also one stream of a ``LimiterPool``, reset with the request's
+        ``Limit`` when the request takes the slot, and each pool call's PCM goes through ONE limiter ``feed`` on the side stream, AFTER the
+        leveler and BEFORE the watermark: stretch, level, limit, mark, resample.  The limiter holds back ``Limit.lookahead`` samples, which
+        come with the request's last chunk -- also with a closing chunk that is empty at 24 kHz; a request's chunks, concatenated, are bit
+        for bit ``limit`` of its concatenated ``limiter=None`` chunks.  With ``loudness`` given too, a request that has both gets the pair
+        of ``sesameai.limiter.paired``: its leveler runs ``Limit.headroom_shift`` doublings lower under a 0 dB ceiling and the limiter is
+        driven by as many, so an onset that the leveler alone would clamp is brought down ahead of its peak.  A request whose limit is None
+        never touches the pool."""
         size = self._stream_buffer_size
         if first_chunk_frames is not None and not 1 <= int(first_chunk_frames) < size:
             raise ValueError(f"first_chunk_frames must be None or 1 .. {size - 1}")
@@ -710,13 +719,24 @@ class Generator:
             if ("stretcher", B) not in self._stream_pools:
                 self._stream_pools[("stretcher", B)] = TimeStretchPool(B, device=self.device)
             kw["stretcher"], kw["speeds"] = self._stream_pools[("stretcher", B)], speeds
+        limits = None
+        if limiter is not None:
+            from .limiter import LimiterPool, paired, per_request_limits
+            limits = per_request_limits(limiter, len(prompts))
         if loudness is not None:
             from .loudness import LoudnessPool, per_request_levels
             levels = per_request_levels(loudness, len(prompts))
+            if limits is not None:                                  # a request with both: the leveler lower by the headroom, the limiter driven by it
+                both = [paired(lv, lm) if lv is not None and lm is not None else (lv, lm) for lv, lm in zip(levels, limits)]
+                levels, limits = [lv for lv, _ in both], [lm for _, lm in both]
             if any(v is not None for v in levels):
                 if ("leveler", B) not in self._stream_pools:
                     self._stream_pools[("leveler", B)] = LoudnessPool(B, device=self.device)
                 kw["leveler"], kw["levels"] = self._stream_pools[("leveler", B)], levels
+        if limits is not None and any(v is not None for v in limits):
+            if ("limiter", B) not in self._stream_pools:
+                self._stream_pools[("limiter", B)] = LimiterPool(B, device=self.device)
+            kw["limiter"], kw["limits"] = self._stream_pools[("limiter", B)], limits
         if (key := self._mark_key(watermark)) is not None:
             from .watermarking import WatermarkPool, default_secret
             at = ("marker", B, default_secret(key))

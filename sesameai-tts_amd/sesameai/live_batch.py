@@ -351,15 +351,22 @@ class SlotStreams:
     slot = stream, and one ``Level`` or None per REQUEST; a slot is reset with its request's ``Level`` when the request takes it, and every pool
     call's PCM of the requests that have one goes through ONE ``leveler.level_feed`` on ``side`` AFTER the stretch and BEFORE the watermark --
     the mark goes into the samples that leave -- ``final`` for the slots whose request it closes.  The leveler holds nothing back: a bare
-    ending hands it the stretch's tail, as the marker's does.  A request whose level is None never touches the pool."""
+    ending hands it the stretch's tail, as the marker's does.  A request whose level is None never touches the pool.
+    ``limiter`` with ``limits`` (None: no limiting, today's calls exactly): a pool of at least ``slots`` limiter streams (``LimiterPool``),
+    slot = stream, and one ``Limit`` or None per REQUEST; a slot is reset with its request's ``Limit`` when the request takes it, and every pool
+    call's PCM of the requests that have one goes through ONE ``limiter.feed`` on ``side`` AFTER the leveler and BEFORE the watermark -- stretch,
+    level, limit, mark, resample -- ``final`` for the slots whose request it closes.  The limiter holds its look-ahead back: those samples come
+    with the request's last chunk, also when that chunk is empty at 24 kHz."""
 
     def __init__(self, pool, slots: int, size: int, side, device, first: Optional[int] = None, resampler=None, stretcher=None,
                  speeds: Optional[Sequence[Optional[float]]] = None, marker=None, marks: Optional[Sequence] = None, leveler=None,
-                 levels: Optional[Sequence] = None):
+                 levels: Optional[Sequence] = None, limiter=None, limits: Optional[Sequence] = None):
         self.pool, self.size, self.side, self.first, self.resampler = pool, size, side, first, resampler
         self.stretcher, self.speeds = stretcher, speeds
         self.marker, self.marks = marker, marks
         self.leveler, self.levels = leveler, levels
+        self.limiter, self.limits = limiter, limits
+        self.limit: list = [None] * slots                           # (limiter) the Limit of the request that holds the slot
         self.level: list = [None] * slots                           # (leveler) the Level of the request that holds the slot
         self.mark: List[Optional[Sequence[int]]] = [None] * slots    # (marker) the key of the request that holds the slot
         self.speed: List[Optional[float]] = [None] * slots          # (stretcher) the speed of the request that holds the slot
@@ -408,6 +415,11 @@ class SlotStreams:
                         self.level[s_] = self.levels[owner[s_]]
                     if even := [s_ for s_ in fresh if self.level[s_] is not None]:
                         self.leveler.level_reset(even, [self.level[s_] for s_ in even])
+                if self.limiter is not None:
+                    for s_ in fresh:
+                        self.limit[s_] = self.limits[owner[s_]]
+                    if peaks := [s_ for s_ in fresh if self.limit[s_] is not None]:
+                        self.limiter.reset(peaks, [self.limit[s_] for s_ in peaks])
                 if self.marker is not None:
                     for s_ in fresh:
                         self.mark[s_] = self.marks[owner[s_]]
@@ -442,7 +454,18 @@ class SlotStreams:
                         calls[k] = (slots, frames, pcm)
                 if bare := [s_ for s_ in ending if s_ not in final and self.level[s_] is not None]:
                     tails.update(zip(bare, self.leveler.level_feed(bare, [tails.get(s_, self.no_pcm.float()) for s_ in bare], True)))
-            if self.marker is not None:                             # ONE watermark call per pool call, and one for the empty closing chunks
+            if self.limiter is not None:                            # ONE limiter call per pool call, and one for the empty closing chunks
+                for k, (slots, frames, pcm) in enumerate(calls):
+                    if peaks := [j for j, s_ in enumerate(slots) if self.limit[s_] is not None]:
+                        ys = self.limiter.feed([slots[j] for j in peaks], [pcm[j][0] for j in peaks],
+                                               [slots[j] in ending and final[slots[j]] == k for j in peaks])
+                        pcm = [pcm[j] for j in range(len(slots))]
+                        for j, y in zip(peaks, ys):
+                            pcm[j] = y.unsqueeze(0)
+                        calls[k] = (slots, frames, pcm)
+                if bare := [s_ for s_ in ending if s_ not in final and self.limit[s_] is not None]:
+                    tails.update(zip(bare, self.limiter.feed(bare, [tails.get(s_, self.no_pcm.float()) for s_ in bare], True)))
+            if self.marker is not None:                            # ONE watermark call per pool call, and one for the empty closing chunks
                 for k, (slots, frames, pcm) in enumerate(calls):
                     if keyed := [j for j, s_ in enumerate(slots) if self.mark[s_] is not None]:
                         ys = self.marker.feed([slots[j] for j in keyed], [pcm[j][0] for j in keyed],
