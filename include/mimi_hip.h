@@ -553,7 +553,8 @@ int  mimi_ld_pool_level_state(mimi_ld_pool p, const int32_t* streams, int n, lon
 /* ---- A pool of LOOK-AHEAD PEAK-LIMITER streams (nothing above a ceiling, and no clipped waveform: behind the leveler, or alone) ----
  * A gain that starts to fall L samples AHEAD of a peak, is what the peak requires exactly on it, and recovers at a fixed step per sample.
  * Exact integers plus a few spelled-out IEEE operations, so the device computes THE RULE below bit for bit (tests/limiter_ref.py states it
- * in NumPy).  Sample peaks only: no oversampled (true-peak) detection, one channel, one band.  ONE = 65536 is a gain of 1 in Q16.
+ * in NumPy).  Sample peaks by default; a stream made fresh by mimi_lim_pool_reset_tp with its flag set detects TRUE PEAKS, 4x oversampled
+ * (below).  One channel, one band.  ONE = 65536 is a gain of 1 in Q16.
  * Per stream, set when the stream is made fresh: C, the ceiling (1 .. 32767); L, the look-ahead in samples (1 .. 480); rho, the release
  * step in Q16 per sample (8 .. 65536; K = ceil(ONE / rho) <= 8192 samples from silence of gain back to 1); hr, the drive shift (0 .. 4):
  * the input is multiplied by exactly 2^hr in front of the limiter.  A stream is preceded and followed by silence: m[r] = ONE for r < 0 and
@@ -607,6 +608,38 @@ long mimi_lim_pool_out_count(mimi_lim_pool p, int sid, long n_in, int final);
 int  mimi_lim_pool_feed(mimi_lim_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
                         const void* in, void* out, long* n_out, int fmt, void* stream);
 int  mimi_lim_pool_state(mimi_lim_pool p, const int32_t* streams, int n, long* out, void* stream);
+
+/* ---- TRUE PEAKS: 4x oversampled detection for the limiter, and a stateless meter (tests/truepeak_ref.py states the rule in NumPy) ----
+ * A 24 kHz waveform whose samples all lie under a ceiling can pass it between them, and a resampler behind the limiter makes those
+ * inter-sample peaks real samples.  T = 8.  Three fractional phases p = 1, 2, 3 of 16 taps in Q14, H[p][k + 7] for k = -7 .. 8
+ * (csrc/truepeak_taps.h; tools/truepeak_taps.py makes them: a 63-tap Kaiser windowed sinc); phase 0 is the sample itself.  Exact integers:
+ *   a. signed sample v[r].  int16: s 2^hr.  fp32: sign(x) a[r] with a of step 1 above (a NaN: 0; |v| <= 2^30).  v = 0 outside the clip.
+ *   b. interval i lies between samples i - 1 and i (i = 0 .. N): acc = sum over k of H[p][k + 7] v[i - 1 + k], in 64 bits
+ *      (|acc| < 2^45); U[i][p] = (|acc| + 2^13) >> 14.
+ *   c. a_tp[r] = max(a[r], U[r][1 .. 3], U[r + 1][1 .. 3]) < 2^31, for the samples of the clip.
+ *   d. step 2 above reads a_tp in the place of a.  a_tp >= a, so the gain is never above the sample-peak gain and |y| <= C still holds
+ *      exactly; the OUTPUT's own true peak can pass C by a little, because the gain moves between samples (docs/experiments/true_peak.md
+ *      has the measured worst).  Steps 3 to 6 and the state row are unchanged.
+ *   e. m[r] needs v up to r + T, so the latency is L + T: a call emits max(0, R - L - T) - E, or R - E at `final`.
+ * mimi_lim_pool_reset_tp is mimi_lim_pool_reset with true_peak[i] = 0 or 1 per listed stream (all 0: the same call); every other entry
+ * point keeps its signature.  A true-peak stream keeps, beside the required gains (of the K + 2 L positions in front of its last T), the
+ * signed samples of its last 2 T positions and the at most L + T samples it holds.  A call may list streams of both modes: each mode
+ * present takes its own two launches, outputs packed in list order as before.  Where every |v| a workgroup stages is below 2^15 the taps
+ * run as int16 pairs into an int32 accumulator (it stays below 2^30), else in 64 bits: the integer is the rule's either way.
+ * Additionally refused (-1): a flag that is neither 0 nor 1, a null true_peak.
+ * mimi_tp_measure: a stateless meter with hr = 0.  Clip i is n_in[i] >= 0 samples at in + in_off[i] ELEMENTS (device memory; fmt as
+ * above); in_off, n_in: host arrays of n <= MIMI_TP_MAX_CLIPS entries, read before the call returns.  out: device memory, MIMI_TP_ROW
+ * int64 per clip: {sample peak max a, true peak max a_tp, the first r with a_tp[r] == true peak, n_in[i]}; an empty clip gives four
+ * zeros.  One memset of the rows and ONE launch over (clip, tile of 4096 positions) workgroups; the maximum and its first position go
+ * through one packed 64-bit atomicMax, so the row is exact in any order.  No host-to-device copy, no allocation, no synchronisation.
+ * Returns -1 with a message in mimi_tp_last_error (this thread), nothing enqueued, for: a null pointer, an unknown format, a misaligned
+ * buffer (out: 8 bytes), n outside [1, 64], a negative n_in or in_off, a clip of more than 2^30 samples.  -2: a HIP error.              */
+#define MIMI_TP_MAX_CLIPS 64
+#define MIMI_TP_ROW 4
+int  mimi_lim_pool_reset_tp(mimi_lim_pool p, const int32_t* streams, const int32_t* ceiling, const int32_t* lookahead, const int32_t* rho,
+                            const int32_t* drive_shift, const int32_t* true_peak, int n);
+int  mimi_tp_measure(const void* in, const long* in_off, const long* n_in, int n, int fmt, long* out, void* stream);
+const char* mimi_tp_last_error(void);
 
 #ifdef __cplusplus
 }

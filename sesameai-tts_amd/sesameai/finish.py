@@ -7,6 +7,7 @@ same samples.  All arithmetic is the library's; this file marshals."""
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Union
 
@@ -27,6 +28,7 @@ class SegmentFinish:
     fade_ms: int = 50
     loudness: Optional[float] = None     # LUFS: the clip is brought to this integrated loudness (BS.1770) instead of to its own peak
     ceiling_db: float = -1.0             # ... but no sample above this, dB relative to full scale (only read with ``loudness``)
+    true_peak: bool = False              # ... the ceiling holds for the 4x oversampled waveform, dBTP (only read with ``loudness``)
 
     def samples(self, sample_rate: int):
         if min(self.lead_ms, self.tail_ms, self.fade_ms) < 0:
@@ -55,7 +57,11 @@ class SegmentFinisher:
     """``finish(clips, finish)``: every clip (n_i,) fp32, n_i >= 0 -> its segment (lead + n_i + tail,) int16 on the device, views of one packed
     buffer.  Up to 64 clips are one library call (two launches on the current torch stream, no synchronisation); more run in several.
     Where a clip's ``SegmentFinish`` names a ``loudness``, the call's clips are metered first (sesameai/loudness.py, three more launches)
-    and the call is mimi_fin_segments_ld; where none does, the calls are exactly those made without the keyword."""
+    and the call is mimi_fin_segments_ld; where none does, the calls are exactly those made without the keyword.  Where such a clip also
+    asks for ``true_peak``, the buffer the clips were packed into for the loudness meter also goes through mimi_tp_measure
+    (sesameai/truepeak.py: a memset of 32 bytes a clip and one launch), and one small device copy per run of clips that ask puts their
+    true peaks in the place of the sample peaks in the meter rows: one gain per clip is linear, so the finished clip's true peak is the
+    input's times the gain.  No synchronisation."""
 
     def __init__(self, device: Union[str, torch.device] = "cuda"):
         self.device = torch.device(device)
@@ -98,7 +104,22 @@ class SegmentFinisher:
             with torch.cuda.device(self.device):
                 if any(pt for pt, _ in lev):       # a clip of the call asks for a loudness: meter them all (three launches), then finish
                     from .loudness import measure_rows
-                    self.last_meter = meter = measure_rows(sub, self.device)
+                    want = [f.true_peak and f.loudness is not None for f in each[lo:lo + MAX_SEGMENTS]]
+                    if any(want):                  # one packed buffer for both meters; the true peaks into the peak column of the clips that ask
+                        from .loudness import pack_clips
+                        from .truepeak import ROW, measure_packed
+                        p = pack_clips(sub, self.device)
+                        self.last_meter = meter = measure_rows(sub, self.device, packed=p)
+                        peaks = torch.empty((m, ROW), dtype=torch.int64, device=self.device)
+                        measure_packed(_abi.lib, p.packed, p.c_offs, p.c_lens, m, peaks)
+                        at = 0
+                        for asks, run in itertools.groupby(want):
+                            k = len(list(run))
+                            if asks:
+                                meter[at:at + k, 2] = peaks[at:at + k, 1]
+                            at += k
+                    else:
+                        self.last_meter = meter = measure_rows(sub, self.device)
                     self._check(lib.mimi_fin_segments_ld(*head, (C.c_long * m)(*[pt for pt, _ in lev]), (C.c_int32 * m)(*[c for _, c in lev]),
                                                          meter.data_ptr(), m, out.data_ptr() + 2 * base, off, n_out, stream))
                 else:

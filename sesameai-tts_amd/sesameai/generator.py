@@ -681,8 +681,8 @@ class Generator:
         ``limiter`` (None: the calls described above exactly, nothing imported): True for the default ``Limit`` (sesameai/limiter.py), a
         ``Limit``, or one of these (or None) per request.  Each slot is then also one stream of a ``LimiterPool``, reset with the request's
         ``Limit`` when the request takes the slot, and each pool call's PCM goes through ONE limiter ``feed`` on the side stream, AFTER the
-        leveler and BEFORE the watermark: stretch, level, limit, mark, resample.  The limiter holds back ``Limit.lookahead`` samples, which
-        come with the request's last chunk -- also with a closing chunk that is empty at 24 kHz; a request's chunks, concatenated, are bit
+        leveler and BEFORE the watermark: stretch, level, limit, mark, resample.  The limiter holds back ``Limit.lookahead`` samples
+        (``Limit(true_peak=True)``, which makes the ceiling hold for the 4x oversampled waveform too: 8 more), which come with the request's last chunk -- also with a closing chunk that is empty at 24 kHz; a request's chunks, concatenated, are bit
         for bit ``limit`` of its concatenated ``limiter=None`` chunks.  With ``loudness`` given too, a request that has both gets the pair
         of ``sesameai.limiter.paired``: its leveler runs ``Limit.headroom_shift`` doublings lower under a 0 dB ceiling and the limiter is
         driven by as many, so an onset that the leveler alone would clamp is brought down ahead of its peak.  A request whose limit is None

@@ -5,7 +5,9 @@ by ``lookahead`` samples and brings its gain down smoothly AHEAD of every peak: 
 recovers at a fixed step per sample.  Exact integers (tests/limiter_ref.py states the rule), for up to 64 streams with two launches per
 call, with state: a stream's outputs, concatenated over any chunk schedule, are bit for bit the one-shot result.  Behind the live leveler
 (``paired``) it lets the leveler overshoot by a known headroom instead of clamping: what ``generate_many_stream(loudness=, limiter=)``
-puts behind each slot.  Sample peaks only -- no oversampled (true-peak) detection.  All arithmetic is the library's; this file marshals."""
+puts behind each slot.  Sample peaks by default; ``Limit(true_peak=True)`` detects the peaks of the 4x oversampled signal
+(tests/truepeak_ref.py; ``sesameai.truepeak`` is the meter) at ``TRUE_PEAK_TAPS`` more samples of latency.  All arithmetic is the library's;
+this file marshals."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,6 +25,7 @@ GAIN_ONE = 65536                 # a gain of 1 in Q16
 LOOKAHEAD_MAX = 480
 RHO_MIN, RHO_MAX = 8, 65536
 SHIFT_MAX = 4
+TRUE_PEAK_TAPS = 8               # TP_T: a true-peak stream's latency is lookahead + 8
 
 
 def ceiling_i16(ceiling_db: float) -> int:
@@ -37,12 +40,19 @@ class Limit(NamedTuple):
     """How one stream is limited (include/mimi_hip.h, mimi_lim_pool_reset): ``ceiling_db`` the sample ceiling in dB relative to full scale;
     ``lookahead`` = L in samples, the stream's latency (120: 5 ms); ``release_ms`` the time from silence of gain back to 1 (the step is
     rho = max(8, rint(65536 / (release_ms * 24))) in Q16 per sample); ``drive_shift`` = hr: the input is multiplied by exactly 2^hr in
-    front of the limiter; ``headroom_shift`` = h, read by ``paired`` alone: how many doublings a leveler in front may overshoot."""
+    front of the limiter; ``headroom_shift`` = h, read by ``paired`` alone: how many doublings a leveler in front may overshoot;
+    ``true_peak``: the stream detects true peaks, 4x oversampled, and its latency is ``lookahead`` + 8 (mimi_lim_pool_reset_tp)."""
     ceiling_db: float = -1.0
     lookahead: int = 120
     release_ms: float = 100.0
     drive_shift: int = 0
     headroom_shift: int = 2
+    true_peak: bool = False
+
+    @property
+    def latency(self) -> int:
+        """Samples the stream holds back until more arrive."""
+        return int(self.lookahead) + (TRUE_PEAK_TAPS if self.true_peak else 0)
 
     def params(self) -> tuple:
         """(C, L, rho, hr): the integers the library takes, checked against its ranges."""
@@ -76,7 +86,8 @@ class LimiterPool(StreamPool):
     """``n`` independent limiter streams.  ``reset(ids, limits)`` makes the listed streams fresh, each with its ``Limit`` (host
     arithmetic, no launch; a stream must be reset once before it is fed); ``feed(ids, chunks, final)`` gives every listed stream its new
     samples at 24 kHz, fp32 or int16 (one format a call), and returns what each emits: at most two launches, no host-to-device copy of a
-    plan, no synchronisation.  A stream holds its last ``lookahead`` samples back until more arrive or ``final`` ends its clip, which
+    plan, no synchronisation (a call that lists sample-peak and true-peak streams: two launches for each kind).  A stream holds its last
+    ``Limit.latency`` samples back until more arrive or ``final`` ends its clip, which
     leaves it fresh with the same parameters.  ``state(ids)``: one launch, a (len(ids), 4) int64 tensor that stays on the device;
     ``poll()`` reads it (one small copy, the call's only synchronisation)."""
 
@@ -93,8 +104,11 @@ class LimiterPool(StreamPool):
         assert len(limits) == len(ids), "one Limit per id"
         q = [lm.params() for lm in limits]
         m = max(len(ids), 1)
-        self._check(self._lib.mimi_lim_pool_reset(self._h, (C.c_int32 * m)(*ids), *[(C.c_int32 * m)(*[v[k] for v in q]) for k in range(4)],
-                                                  len(ids)))
+        head = (self._h, (C.c_int32 * m)(*ids), *[(C.c_int32 * m)(*[v[k] for v in q]) for k in range(4)])
+        if any(lm.true_peak for lm in limits):
+            self._check(self._lib.mimi_lim_pool_reset_tp(*head, (C.c_int32 * m)(*[int(bool(lm.true_peak)) for lm in limits]), len(ids)))
+        else:
+            self._check(self._lib.mimi_lim_pool_reset(*head, len(ids)))
 
     @torch.inference_mode()
     def feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False) -> List[torch.Tensor]:

@@ -79,10 +79,12 @@ class LoudnessPool(StreamPool):
         self._check(self._lib.mimi_ld_pool_reset(self._h, (C.c_int32 * max(len(ids), 1))(*ids), len(ids)))
 
     @torch.inference_mode()
-    def feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False) -> List[torch.Tensor]:
+    def feed(self, ids: Sequence[int], chunks: Sequence[torch.Tensor], final: Union[bool, Sequence[bool]] = False,
+             packed=None) -> List[torch.Tensor]:
         """ids: n distinct stream ids; chunks[i]: (n_i,) fp32 or int16 at 24 kHz, n_i >= 0, CPU or device (int16 only if every chunk is);
-        final: one flag, or one per stream -> per stream the (K_i,) int64 energies of the hops it completed, views of one buffer."""
-        p = pack(chunks, self.device, int16_if_all, ids, final)
+        final: one flag, or one per stream -> per stream the (K_i,) int64 energies of the hops it completed, views of one buffer.
+        ``packed``: the call's chunks already packed by ``pack_clips`` (then ids, chunks and final are its own)."""
+        p = pack(chunks, self.device, int16_if_all, ids, final) if packed is None else packed
         energy = torch.empty(max(sum(self._counts("hop_count", p)), 1), dtype=torch.int64, device=self.device)
         n_hops = (C.c_long * p.m)()
         self._check(self._lib.mimi_ld_pool_feed(self._h, *p.head, int(p.dtype == torch.int16), energy.data_ptr(), n_hops, _stream()))
@@ -190,15 +192,25 @@ _POOLS: Dict[str, LoudnessPool] = {}       # measure()'s pools, made on first us
 
 
 @torch.inference_mode()
-def measure_rows(wavs: Sequence[torch.Tensor], device: Union[str, torch.device, None] = None) -> torch.Tensor:
+def pack_clips(wavs: Sequence[torch.Tensor], device: torch.device):
+    """The clips of one ``measure_rows`` call as it packs them -- one device buffer, streams 0 .. n - 1, ``final`` -- for a caller that
+    wants the same buffer for something else too (``SegmentFinisher`` hands it to the true-peak meter)."""
+    return pack(wavs, device, int16_if_all, list(range(len(wavs))), True)
+
+
+def measure_rows(wavs: Sequence[torch.Tensor], device: Union[str, torch.device, None] = None, packed=None) -> torch.Tensor:
     """Up to 64 clips of different lengths, each (n_i,) fp32 or int16 at 24 kHz -> (len(wavs), 4) int64 {S, n, peak, hops} ON THE DEVICE,
-    on fresh streams with ``final``: three launches, no synchronisation.  What ``SegmentFinisher`` hands to mimi_fin_segments_ld."""
+    on fresh streams with ``final``: three launches, no synchronisation.  What ``SegmentFinisher`` hands to mimi_fin_segments_ld.
+    ``packed``: ``pack_clips(wavs, device)``, if the caller has made it already."""
     if not 1 <= len(wavs) <= MAX_STREAMS:
         raise ValueError(f"measure takes 1 .. {MAX_STREAMS} clips a call")
     pool = shared_pool(_POOLS, device, wavs[0], str, lambda dev: LoudnessPool(MAX_STREAMS, device=dev))
     ids = list(range(len(wavs)))
     pool.reset(ids)                    # (host arithmetic: also covers a stream that an earlier call, interrupted, left open)
-    pool.feed(ids, wavs, final=True)
+    if packed is None:
+        pool.feed(ids, wavs, final=True)
+    else:
+        pool.feed(ids, wavs, final=True, packed=packed)
     return pool.integrate(ids)
 
 

@@ -89,11 +89,13 @@ class TTS:
     watermark_kind = None           # None: silentcipher when it is importable, else the pass-through; "device": this build's own mark
 
     def __init__(self, device: str = "cuda", model_repo: str = "sesame/csm-1b", voice_dir: Optional[str] = None, max_batch_size: int = 1,
-                 watermark: Optional[str] = None, loudness: Optional[float] = None, ceiling_db: float = -1.0) -> None:
+                 watermark: Optional[str] = None, loudness: Optional[float] = None, ceiling_db: float = -1.0,
+                 true_peak: bool = False) -> None:
         if watermark not in (None, "device"):
             raise ValueError("watermark must be None or 'device'")
         self.watermark_kind = watermark
         self.loudness, self.ceiling_db = loudness, ceiling_db      # say / export_wav(.., batch=) bring every sentence to this LUFS (None: peak)
+        self.true_peak = bool(true_peak)                           # ... with ``ceiling_db`` a true-peak ceiling, dBTP (read with loudness only)
         self.device = device
         self.max_batch_size = int(max_batch_size)       # slots of the live batch say / export_wav may use with batch= (1: none)
         self.model_repo = model_repo
@@ -201,7 +203,8 @@ class TTS:
 
     def _segments_batched(self, sentences: List[str], batch: int, seed: Optional[int], fallback_duration: int, fade_duration: int,
                           start_silence_duration: int, end_silence_duration: int, temperature: float, topk: int, on_segment=None,
-                          speed: Optional[float] = None, loudness: Optional[float] = None) -> List[np.ndarray]:
+                          speed: Optional[float] = None, loudness: Optional[float] = None,
+                          true_peak: Optional[bool] = None) -> List[np.ndarray]:
         """The sentences of one text as independent requests of the continuously refilled batch (``batch`` of its slots), each against the
         cached voice context: the context rows are registered once per loaded voice with the prefix store, every sentence is one prompt
         (context + sentence) with the 30 s limit of ``generate_audio_segment``, sentence i gets seed ``seed + i``, and every segment is
@@ -209,10 +212,14 @@ class TTS:
         silence and the others still run; an error of the batch run itself propagates.  Requests complete in any order: a reorder buffer
         hands ``on_segment`` and the ``> sentence ...`` lines out strictly in sentence order, each as soon as all earlier ones are out.
         ``loudness`` (None: the service's own, and with that None the calls above exactly): every sentence is brought to this integrated
-        loudness in LUFS by the device finisher (sesameai/loudness.py) instead of to its own peak, no sample above ``ceiling_db``."""
+        loudness in LUFS by the device finisher (sesameai/loudness.py) instead of to its own peak, no sample above ``ceiling_db``.
+        ``true_peak`` (None: the service's own; read with a loudness only, and False makes the calls above exactly): ``ceiling_db`` holds
+        for the 4x oversampled waveform (sesameai/truepeak.py), the EBU R 128 -1 dBTP."""
         from sesameai.finish import SegmentFinish
         loudness = self.loudness if loudness is None else loudness
         level = {} if loudness is None else {"loudness": float(loudness), "ceiling_db": self.ceiling_db}
+        if level and (self.true_peak if true_peak is None else true_peak):
+            level["true_peak"] = True
         g = self.generator
         slots = getattr(g, "_max_batch", 1)
         if isinstance(batch, bool) or not isinstance(batch, int) or not 2 <= batch <= slots:
@@ -289,7 +296,7 @@ class TTS:
     def say(self, text: str, output_filename: Optional[str] = "combined_output.wav", fallback_duration: int = 1000,
             fade_duration: int = 50, start_silence_duration: int = 500, end_silence_duration: int = 100,
             temperature: float = 0.8, topk: int = 40, on_segment=None, batch: Optional[int] = None, seed: Optional[int] = None,
-            speed: Optional[float] = None, loudness: Optional[float] = None) -> None:
+            speed: Optional[float] = None, loudness: Optional[float] = None, true_peak: Optional[bool] = None) -> None:
         """reference: tts_service.py:313-470 -- the generation half: the text is split into sentences, each sentence is
         generated against the cached voice context (the shared prompt prefix is prefilled once: Model.prefill_prompt) and
         reported with the reference's line ``> sentence ... [Audio: 1.84s in 0.09s, RTF: 20.44x]``; a sentence that fails is
@@ -302,13 +309,18 @@ class TTS:
         sampled with seed ``seed + i``, whatever slot it takes.
         ``speed`` (None: the calls described above, exactly): a speech-rate factor in 0.5 .. 2.0 for every sentence, on either path
         (``generate_audio_segment``).  ``loudness`` (with ``batch``; None: the service's own, and with that None the calls described
-        above, exactly): every sentence comes out at this integrated loudness in LUFS instead of at its own peak."""
+        above, exactly): every sentence comes out at this integrated loudness in LUFS instead of at its own peak.  ``true_peak`` (with
+        ``batch``, read with a loudness; None: the service's own): the ceiling is a true-peak ceiling."""
         import textwrap
         more = {} if speed is None else {"speed": speed}
         if (loudness is not None or self.loudness is not None) and batch is None:
             raise ValueError("loudness= needs batch=")
         if loudness is not None:
             more["loudness"] = loudness
+        if true_peak and batch is None:
+            raise ValueError("true_peak= needs batch=")
+        if true_peak is not None and batch is not None:
+            more["true_peak"] = true_peak
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", textwrap.dedent(text).strip()) if s.strip()]
         if not sentences:
             print("No valid text to process")
@@ -351,15 +363,19 @@ class TTS:
 
     def export_wav(self, text: str, output_filename: str, fallback_duration: int = 1000, max_retries: int = 2,
                    temperature: float = 0.8, topk: int = 40, batch: Optional[int] = None, seed: Optional[int] = None,
-                   speed: Optional[float] = None, loudness: Optional[float] = None) -> None:
+                   speed: Optional[float] = None, loudness: Optional[float] = None, true_peak: Optional[bool] = None) -> None:
         """reference: tts_service.py:472-525.  ``batch`` / ``seed``: as for ``say`` (None: the calls of the reference's loop, exactly).
         ``max_retries`` applies only to the unbatched path: with ``batch`` a sentence whose prompt cannot be built gets the fallback
-        silence at once, and an error of the batch run itself propagates.  ``speed``, ``loudness``: as for ``say``."""
+        silence at once, and an error of the batch run itself propagates.  ``speed``, ``loudness``, ``true_peak``: as for ``say``."""
         more = {} if speed is None else {"speed": speed}
         if (loudness is not None or self.loudness is not None) and batch is None:
             raise ValueError("loudness= needs batch=")
         if loudness is not None:
             more["loudness"] = loudness
+        if true_peak and batch is None:
+            raise ValueError("true_peak= needs batch=")
+        if true_peak is not None and batch is not None:
+            more["true_peak"] = true_peak
         sentences = [s for s in re.split(r"(?<=[.!?])\s+", text) if s.strip()]
         sr = self.generator.sample_rate
         segments = []
@@ -412,7 +428,11 @@ def parse_args(argv=None):
                         help="device: mark every clip with this build's own keyed mark, on the GPU (default: silentcipher if it is installed)")
     parser.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                         help="with --batch: bring every sentence to this integrated loudness, e.g. -19 (default: each to its own peak)")
+    parser.add_argument("--true-peak", action="store_true",
+                        help="with --loudness: the -1 dB ceiling holds for the 4x oversampled waveform (-1 dBTP), not only for the samples")
     args = parser.parse_args(argv)
+    if args.true_peak and args.loudness is None:
+        parser.error("--true-peak needs --loudness")
     if args.loudness is not None and args.batch is None:
         parser.error("--loudness needs --batch")
     if args.loudness is not None and not -70.0 <= args.loudness <= 0.0:
@@ -433,6 +453,8 @@ def main():
     made = {} if args.watermark is None else {"watermark": args.watermark}
     if args.loudness is not None:
         made["loudness"] = args.loudness
+    if args.true_peak:
+        made["true_peak"] = True
     tts = TTS(device=args.device, **made) if args.batch is None else TTS(device=args.device, max_batch_size=args.batch, **made)
     more = {} if args.batch is None else {"batch": args.batch, "seed": args.seed}
     if args.speed is not None:

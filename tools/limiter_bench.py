@@ -12,6 +12,11 @@ served live batch.
             alternating: what the halo and the minimum's passes cost.
   live      ``generate_many_stream`` for 96 requests over 32 slots (full-size model and codec, synthetic weights, seeded limits of
             25 .. 125 frames) with and without ``limiter=True``, alternating: frames per second on the host clock up to a synchronise.
+  true_peak the "feed" and "clips" shapes once more, sample-peak streams against true-peak streams (``Limit(true_peak=True)``) of two
+            pools on the same packed buffer, alternating; the yardstick is the sample-peak feed of the same run.  At drive_shift 2, as
+            the legs above (samples of 2^15 and more: the taps in 64 bits), and at drive_shift 0 ("narrow": int16 pairs).  For the clips also
+            mimi_tp_measure (one memset, one kernel) against mimi_ld_pool_feed (the loudness meter's energies) on the same clips.
+            --only-true-peak runs these two alone.
 Kernel times proper come from a kernel trace of this tool with --skip-live, in a run of its own (docs/experiments/limiter.md).
 
     python tools/limiter_bench.py --out profiles/limiter/limiter.json
@@ -144,6 +149,65 @@ def shapes_leg(rounds, warmup):
     return res
 
 
+def true_peak_leg(N, n, final, drive_shift, rounds, warmup, meter):
+    """sample-peak against true-peak limiting of N streams x n samples, alternating; with ``meter`` also the stateless true-peak meter
+    against the loudness meter's feed on the same clips"""
+    from sesameai import _abi
+    from sesameai.limiter import Limit, LimiterPool
+    from sesameai.loudness import LoudnessPool
+    lib = _abi.lib
+    pools = {"sample": LimiterPool(N), "true_peak": LimiterPool(N)}
+    pools["sample"].reset(range(N), Limit(drive_shift=drive_shift))
+    pools["true_peak"].reset(range(N), Limit(drive_shift=drive_shift, true_peak=True))
+    ld = LoudnessPool(N)
+    packed = torch.from_numpy(np.concatenate([speechlike(n, 40 + i) for i in range(N)])).cuda()
+    out = torch.empty(N * n + 16, dtype=packed.dtype, device="cuda")
+    ids = (C.c_int32 * N)(*range(N))
+    offs, lens = (C.c_long * N)(*[i * n for i in range(N)]), (C.c_long * N)(*[n] * N)
+    fin, ones, n_out, n_h = (C.c_int32 * N)(*[int(final)] * N), (C.c_int32 * N)(*[1] * N), (C.c_long * N)(), (C.c_long * N)()
+    energy = torch.empty(N * (n // H + 1), dtype=torch.int64, device="cuda")
+    rows = torch.empty((N, 4), dtype=torch.int64, device="cuda")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    if not final:                             # open streams: the latency is held from here on
+        for pool in pools.values():
+            assert lib.mimi_lim_pool_feed(pool._h, ids, offs, lens, fin, N, packed.data_ptr(), out.data_ptr(), n_out, 0,
+                                          torch.cuda.current_stream().cuda_stream) == 0
+
+    def run(leg):
+        s = torch.cuda.current_stream().cuda_stream
+        if leg == "ld_feed":
+            assert lib.mimi_ld_pool_reset(ld._h, ids, N) == 0          # (host arithmetic, outside the clock)
+        e0.record()
+        if leg in pools:
+            rc = lib.mimi_lim_pool_feed(pools[leg]._h, ids, offs, lens, fin, N, packed.data_ptr(), out.data_ptr(), n_out, 0, s)
+        elif leg == "tp_measure":
+            rc = lib.mimi_tp_measure(packed.data_ptr(), offs, lens, N, 0, rows.data_ptr(), s)
+        else:
+            rc = lib.mimi_ld_pool_feed(ld._h, ids, offs, lens, ones, N, packed.data_ptr(), 0, energy.data_ptr(), n_h, s)
+        e1.record()
+        assert rc == 0
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    legs = ["sample", "true_peak"] + (["ld_feed", "tp_measure"] if meter else [])
+    t = {k: [] for k in legs}
+    for r in range(warmup + rounds):
+        for k in legs:
+            ms = run(k)
+            if r >= warmup:
+                t[k].append(ms)
+    limited = {k: [int(v) for v in pool.state(range(N)).cpu()[:, 2].tolist()] for k, pool in pools.items()}
+    res = {"streams": N, "samples_per_stream": n, "final": bool(final), "drive_shift": drive_shift,
+           "samples_limited_per_stream_since_fresh": {k: [min(v), max(v)] for k, v in limited.items()},
+           "sample_gpu_ms": stats(t["sample"]), "true_peak_gpu_ms": stats(t["true_peak"]),
+           "true_peak_over_sample": statistics.median(t["true_peak"]) / statistics.median(t["sample"])}
+    if meter:
+        res.update({"ld_feed_gpu_ms": stats(t["ld_feed"]), "tp_measure_gpu_ms": stats(t["tp_measure"]),
+                    "tp_measure_over_ld_feed": statistics.median(t["tp_measure"]) / statistics.median(t["ld_feed"]),
+                    "true_peak_over_sample_peak_db": [float(20 * np.log10(max(r[1], 1) / max(r[0], 1))) for r in rows.cpu().tolist()][:4]})
+    return res
+
+
 def live_leg(rounds, warmup):
     """the leveler tool's own live leg with ``limiter=True`` in the place of its loudness target"""
     import time
@@ -193,19 +257,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--live-rounds", type=int, default=3)
     ap.add_argument("--skip-live", action="store_true")
+    ap.add_argument("--only-true-peak", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("limiter_bench: needs a GPU (there is nothing to measure without one)")
     res = {"command": "python tools/limiter_bench.py " + " ".join(sys.argv[1:]), "device": torch.cuda.get_device_name(0),
            "what": "gpu_ms: between HIP events, medians over alternating rounds after warm-up; frames_per_s: host clock up to a synchronise",
            "rounds": args.rounds, "warmup": args.warmup}
-    res["feed"] = pair_leg(32, 19200, False, 2, args.rounds, args.warmup)
-    print(json.dumps({"feed": res["feed"]}), flush=True)
-    res["clips"] = pair_leg(64, 240000, True, 2, args.rounds, args.warmup)
-    print(json.dumps({"clips": res["clips"]}), flush=True)
-    res["shapes"] = shapes_leg(args.rounds, args.warmup)
-    print(json.dumps({"shapes": res["shapes"]}), flush=True)
-    if not args.skip_live:
+    if not args.only_true_peak:
+        res["feed"] = pair_leg(32, 19200, False, 2, args.rounds, args.warmup)
+        print(json.dumps({"feed": res["feed"]}), flush=True)
+        res["clips"] = pair_leg(64, 240000, True, 2, args.rounds, args.warmup)
+        print(json.dumps({"clips": res["clips"]}), flush=True)
+        res["shapes"] = shapes_leg(args.rounds, args.warmup)
+        print(json.dumps({"shapes": res["shapes"]}), flush=True)
+    # drive_shift 2, as the legs above: samples of 2^15 and more, the 64-bit taps; drive_shift 0: int16 pairs
+    res["true_peak"] = {"feed": true_peak_leg(32, 19200, False, 2, args.rounds, args.warmup, False),
+                        "clips": true_peak_leg(64, 240000, True, 2, args.rounds, args.warmup, True),
+                        "feed_narrow": true_peak_leg(32, 19200, False, 0, args.rounds, args.warmup, False),
+                        "clips_narrow": true_peak_leg(64, 240000, True, 0, args.rounds, args.warmup, False)}
+    print(json.dumps({"true_peak": res["true_peak"]}), flush=True)
+    if not args.skip_live and not args.only_true_peak:
         res["live"] = live_leg(args.live_rounds, 1)
     print(json.dumps(res))
     if args.out:
