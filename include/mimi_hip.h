@@ -641,6 +641,63 @@ int  mimi_lim_pool_reset_tp(mimi_lim_pool p, const int32_t* streams, const int32
 int  mimi_tp_measure(const void* in, const long* in_off, const long* n_in, int n, int fmt, long* out, void* stream);
 const char* mimi_tp_last_error(void);
 
+/* ---- WHISPER LOG-MEL STREAMS: the speech-to-text front end (tests/mel_ref.py states the rule in NumPy, float64) ----
+ * Every Whisper-family recogniser takes a log-mel spectrogram of 30 s at 16 kHz, n_mels = 80 or 128 bands by 3000 frames.  It is a pure
+ * function of the samples and causal but for a final clamp, so a stream computes it WHILE the turn is spoken.
+ *   1. s: 480,000 samples, the clip's first min(L, 480000) and zeros behind them; int16 is x 2^-15, exact.  Samples past the cap are
+ *      counted (the dropped count) and dropped, not refused.
+ *   2. p: s reflected by 200 samples at both ends, p[j] = s[|j - 200|] on the left, mirrored about s[479999] on the right.
+ *   3. frame t = 0 .. 2999 reads p[160 t .. 160 t + 399], times the PERIODIC Hann window w[n] = 0.5 - 0.5 cos(2 pi n / 400);
+ *      P[k] = |DFT_400|^2, k = 0 .. 200; mel[m] = sum over k of F[k][m] P[k], F the Slaney-scale, Slaney-normalised triangular bank over
+ *      0 .. 8000 Hz; raw[t][m] = log10(max(mel, 1e-10)).  A frame that reads only zeros is exactly -10.
+ *   4. features[m][t] = (max(raw[t][m], M - 8) + 4) / 4 with M the largest raw value of all 3000 frames: the finisher's part.
+ *   5. streaming: a frame is emitted once every sample it reads has been received or is known to be zero or reflected: with R samples in,
+ *      frame 0 needs 201 and frame t >= 1 needs 160 t + 200; `final` or the cap settle the rest.  At `final` a clip of L samples has
+ *      emitted min(3000, ceil((L + 200) / 160)) frames in all; the frames behind them are the constant -10 and are not written.
+ * NUMERICAL RULE.  The DFT and the bank are fp32 matrix products on v_mfma_f32_32x32x2_f32 (exact fp32; no reduced-precision form exists
+ * on gfx950 and bf16 would lose the bins 80 dB under a frame's strongest): every output is a k-ordered fp32 fmaf chain over the frame's own
+ * 400 windowed samples, whichever frames share its tile.  So a stream's raw rows, concatenated over ANY chunk schedule, company, stream
+ * id or list order, are bit for bit its one-shot rows.  A non-finite sample may make its own clip's features anything; it gives nothing
+ * to other streams, to other clips of the call, or to the stream's next clip after `final` or a reset.
+ * The pool builds its tables on the host in double and keeps them as fp32: window[400]; basis[400][MIMI_MEL_BASIS_COLS], the cos of bins
+ * 0 .. 223 and then their -sin, zero from bin 201 on; bank[MIMI_MEL_BINS_PAD][MIMI_MEL_MAX_MELS], zero outside [201][n_mels].  The
+ * call named ..._tables reads them back into host memory (it synchronises; for tests).
+ * The feed: stream streams[i] gets n_in[i] >= 0 samples at 16 kHz at in + in_off[i] ELEMENTS; fmt: 0 = fp32, 1 = int16, one per
+ * call (the carry is fp32: a stream may change format between calls).  The frames it completes come out as rows of n_mels fp32 in `raw`
+ * (device memory, room for the sum of the frame counts), packed back to back in list order; n_frames[i] is written before the call
+ * returns.  The host arrays are read before the call returns.  Per stream the device keeps the samples from the next unemitted frame's
+ * first sample on, fewer than 400 fp32, in two banks flipped per call; the host keeps {R, frames, bank, dropped}.  `final` ends the clip
+ * and leaves the stream fresh; the reset is host arithmetic with no launch, and a fresh stream reads no carry.  TWO launches per
+ * call whatever n and the lengths are; no host-to-device copy, no allocation, no synchronisation.  The frame count and the dropped count
+ * (samples past the cap since the stream was fresh) are host arithmetic; -1: ask the last error.
+ * The finisher is stateless: clip i has n_frames[i] <= 3000 raw rows at raw + off[i] ELEMENTS (off, n_frames: host arrays of
+ * n <= MIMI_MEL_MAX_CLIPS entries); out[i] is (n_mels, 3000) fp32, device memory.  M is taken over the clip's rows, and -10 if frames are
+ * missing; the missing frames get the constant.  Two launches: a clip's M travels in the last two elements of its own output, which the
+ * workgroup that finishes the clip last overwrites with their values; no workgroup waits for another.
+ * Returns -1 with a message in the pool's last error (the finisher: mimi_mel_last_error, this thread), nothing enqueued and no state
+ * moved, for: n_mels not 80 or 128, n_streams outside [1, 64] (create); n outside [1, n_streams], a stream id outside [0, n_streams) or
+ * listed twice, a null pointer, an unknown format, a misaligned buffer, a negative n_in or in_off, a chunk of more than 2^30 samples;
+ * the finisher: n outside [1, 64], n_frames outside [0, 3000], a negative off.  -2: a HIP error.                                       */
+#define MIMI_MEL_MAX_STREAMS 64
+#define MIMI_MEL_MAX_CLIPS 64
+#define MIMI_MEL_CAP 480000
+#define MIMI_MEL_FRAMES 3000
+#define MIMI_MEL_BINS_PAD 224
+#define MIMI_MEL_BASIS_COLS 448
+#define MIMI_MEL_MAX_MELS 128
+typedef struct MimiMelPool* mimi_mel_pool;
+int  mimi_mel_pool_create(int n_mels, int n_streams, mimi_mel_pool* out);
+void mimi_mel_pool_destroy(mimi_mel_pool p);
+const char* mimi_mel_pool_last_error(mimi_mel_pool p);         /* p == NULL: why mimi_mel_pool_create failed (this thread) */
+int  mimi_mel_pool_reset(mimi_mel_pool p, const int32_t* streams, int n);
+int  mimi_mel_pool_tables(mimi_mel_pool p, float* window, float* basis, float* bank);
+long mimi_mel_pool_frame_count(mimi_mel_pool p, int sid, long n_in, int final);
+long mimi_mel_pool_dropped(mimi_mel_pool p, int sid);
+int  mimi_mel_pool_feed(mimi_mel_pool p, const int32_t* streams, const long* in_off, const long* n_in, const int32_t* final, int n,
+                        const void* in, int fmt, float* raw, long* n_frames, void* stream);
+int  mimi_mel_finish(const float* raw, const long* off, const long* n_frames, int n, int n_mels, float* out, void* stream);
+const char* mimi_mel_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

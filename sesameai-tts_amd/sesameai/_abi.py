@@ -177,6 +177,16 @@ MIMI_SIGNATURES = {
     "mimi_lim_pool_reset_tp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "mimi_tp_measure": (_i, [_vp, C.POINTER(_l), C.POINTER(_l), _i, _i, _vp, _vp]),
     "mimi_tp_last_error": (C.c_char_p, []),
+    "mimi_mel_pool_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "mimi_mel_pool_destroy": (None, [_vp]),
+    "mimi_mel_pool_last_error": (C.c_char_p, [_vp]),
+    "mimi_mel_pool_reset": (_i, [_vp, _vp, _i]),
+    "mimi_mel_pool_tables": (_i, [_vp, _vp, _vp, _vp]),
+    "mimi_mel_pool_frame_count": (_l, [_vp, _i, _l, _i]),
+    "mimi_mel_pool_dropped": (_l, [_vp, _i]),
+    "mimi_mel_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _i, _vp, C.POINTER(_l), _vp]),
+    "mimi_mel_finish": (_i, [_vp, C.POINTER(_l), C.POINTER(_l), _i, _i, _vp, _vp]),
+    "mimi_mel_last_error": (C.c_char_p, []),
     "mimi_ts_pool_create": (_i, [_i, C.POINTER(_vp)]),
     "mimi_ts_pool_destroy": (None, [_vp]),
     "mimi_ts_pool_last_error": (C.c_char_p, [_vp]),

@@ -213,25 +213,32 @@ class Generator:
         return torch.cat(toks, 0).long().to(self.device), torch.cat(masks, 0).bool().to(self.device)
 
     def open_turn_streams(self, n: int, chunk_frames: int = 10, sample_rate: Optional[int] = None, vad=None, pre_roll_ms: int = 200,
-                          post_roll_ms: int = 200):
+                          post_roll_ms: int = 200, features=None):
         """``n`` spoken turns encoded while they are spoken (sesameai/turns.py): ``feed`` / ``pump`` as the microphones deliver, then
         ``finish(sid, speaker, text)`` gives the ``Segment`` of the turn, its codes bit for bit those of ``Segment(audio=the turn)``.
         ``sample_rate`` (None: 24 kHz, today's calls exactly): the microphones' rate; ``feed`` then takes fp32 or int16 at that rate and a
         pool of ``n`` resampler streams (sesameai/resample.py) follows the turns in front of the encoder.
         ``vad`` (None: today's calls exactly): ``True`` for a pool of ``n`` voice-activity streams (sesameai/vad.py), or such a pool; the
         streams then listen all the time, a turn starts ``pre_roll_ms`` before the detected START and ends ``post_roll_ms`` after the
-        detected END, and ``poll_events`` says when."""
+        detected END, and ``poll_events`` says when.
+        ``features`` (None: today's calls exactly, nothing imported): ``True`` or 80 for a ``TurnFeatures`` of ``n`` streams with 80 mel
+        bands (sesameai/mel.py), 128 for 128 bands, or such an object; ``take_features(sid)`` then has each ended turn's Whisper input."""
         from .turns import TurnStreams
         tok = self._audio_tokenizer
         if tok is None or not hasattr(tok, "open_encode_streams"):
             raise RuntimeError("no Mimi encoder with encode streams available: pass Segment.audio_codes")
         pool = tok.open_encode_streams(n, max_chunk_frames=chunk_frames)
         kw = {}
+        if features is not None and features is not False:
+            if features is True or (isinstance(features, int) and features in (80, 128)):
+                from .mel import TurnFeatures
+                features = TurnFeatures(n, src_rate=self.sample_rate, n_mels=80 if features is True else int(features), device=self.device)
+            kw["features"] = features
         if vad is not None and vad is not False:
             if vad is True:
                 from .vad import VadPool
                 vad = VadPool(n, device=self.device)
-            kw = {"vad": vad, "pre_roll": int(pre_roll_ms) * self.sample_rate // 1000, "post_roll": int(post_roll_ms) * self.sample_rate // 1000}
+            kw.update({"vad": vad, "pre_roll": int(pre_roll_ms) * self.sample_rate // 1000, "post_roll": int(post_roll_ms) * self.sample_rate // 1000})
         if sample_rate is None or int(sample_rate) == self.sample_rate:
             return TurnStreams(pool, tok.args.hop, chunk_frames, **kw)
         from .resample import ResamplerPool

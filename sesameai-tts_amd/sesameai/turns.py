@@ -7,7 +7,9 @@ frame included -- and hands back a ``Segment`` with ``audio_codes``: bit for bit
 the turn ends, all of it but the last call's frames is already on the device.  With a ``resampler`` (a ``ResamplerPool`` from the
 microphones' rate to the codec's, sesameai/resample.py) the samples come at the microphones' rate, fp32 or int16: the codes are then those
 of ``encode(resample(the whole turn))``.  With a ``vad`` (a ``VadPool``, sesameai/vad.py) the streams listen all the time and the
-detector says where a turn starts and ends; ``ReplyOnPause`` turns its events into calls.  Host logic only; the arithmetic is the pools'."""
+detector says where a turn starts and ends; ``ReplyOnPause`` turns its events into calls.  With ``features`` (a ``TurnFeatures``,
+sesameai/mel.py) the turn's speech-to-text input -- Whisper's log-mel features of exactly the samples the segment's codes encode -- is
+computed while the turn is spoken too, and ``take_features`` has it when the turn ends.  Host logic only; the arithmetic is the pools'."""
 from __future__ import annotations
 
 from collections import deque
@@ -19,7 +21,8 @@ import torch
 class TurnStreams:
     VAD_FRAME = 240                  # the detector's frame at 24 kHz: events are stamped in frames
 
-    def __init__(self, pool, hop: int, chunk_frames: int = 10, resampler=None, vad=None, pre_roll: int = 4800, post_roll: int = 4800):
+    def __init__(self, pool, hop: int, chunk_frames: int = 10, resampler=None, vad=None, pre_roll: int = 4800, post_roll: int = 4800,
+                 features=None):
         """pool: anything with ``n_streams``, ``encode(ids, wavs) -> [(32, T_i)]`` and ``reset(ids)`` (``MimiEncodeStreamPool``);
         chunk_frames: the most frames one stream gives one call (at most the pool's ``max_chunk_frames``);
         resampler: None (samples come at 24 kHz: today's calls exactly), or anything with ``feed(ids, chunks, final) -> [(m_i,)]`` and
@@ -33,7 +36,14 @@ class TurnStreams:
         start_frame * 240 - pre_roll)`` and is encoded as it comes; at END its audio ends at ``end = end_frame * 240 + post_roll`` (never
         past what has been received), the codes of frames past ``T = ceil((end - a) / hop)`` are dropped -- the encoder is causal, so the
         segment is bit for bit ``encode(samples[a : a + T * hop])`` -- and the stream goes on listening.  ``poll_events`` hands out
-        ``(sid, "start" | "end", sample)``; after an "end", ``finish`` returns that turn's segment."""
+        ``(sid, "start" | "end", sample)``; after an "end", ``finish`` returns that turn's segment.
+        features: None (today's calls exactly), or anything with ``feed(ids, chunks, final)``, ``reset(ids)`` and ``take(sid) ->
+        (features, n_frames)`` over at least ``pool.n_streams`` streams that takes samples at the codec's rate (``TurnFeatures``).  Without
+        a vad every sample range handed to ``pool.encode`` is handed to ``features.feed`` too, one call per pump over the same ids, and
+        the turn's last range goes with ``final``.  With a vad the codes of an ended turn are cut where the detector says, up to ``hang``
+        frames behind what was already encoded, and features cannot be cut afterwards: so ``features.feed`` follows the encoder only up to
+        where a coming END may still cut (one call per pump), and the rest, up to the last sample the segment's codes encode, goes with
+        ``final`` when the turn is closed.  Either way the features are those of EXACTLY the samples ``[a, b)`` that the codes encode."""
         assert chunk_frames >= 1 and hop >= 1
         self.pool, self.hop, self.chunk_frames, self.resampler = pool, int(hop), int(chunk_frames), resampler
         self._buf: Dict[int, Optional[torch.Tensor]] = {s: None for s in range(pool.n_streams)}     # samples not yet encoded
@@ -41,6 +51,8 @@ class TurnStreams:
         self._raw: Dict[int, List[torch.Tensor]] = {s: [] for s in range(pool.n_streams)}           # (resampler) samples not yet resampled
         self._fed: Dict[int, bool] = {s: False for s in range(pool.n_streams)}                      # (resampler) the turn has had samples
         self.vad, self.pre_roll, self.post_roll = vad, int(pre_roll), int(post_roll)
+        self.features = features
+        self._fsent: Dict[int, int] = {s: 0 for s in range(pool.n_streams)}       # (features, vad) the next sample of the turn they lack
         if vad is not None:
             assert pre_roll >= 0 and post_roll >= 0
             ids = range(pool.n_streams)
@@ -118,6 +130,8 @@ class TurnStreams:
         if not ids:
             return 0
         wavs = [self._take(s, min(self.chunk_frames, self.buffered(s) // self.hop) * self.hop) for s in ids]
+        if self.features is not None:
+            self.features.feed(ids, wavs, False)
         total = 0
         for s, c in zip(ids, self.pool.encode(ids, wavs)):
             self._codes[s].append(c)
@@ -141,14 +155,26 @@ class TurnStreams:
             self._append(sid, y)
             self._fed[sid] = False
         full = self.chunk_frames * self.hop
+        ended = False                                                    # (features) the turn's last range has gone with final
         while self.buffered(sid) > 0:
-            (c,) = self.pool.encode([sid], [self._take(sid, min(full, self.buffered(sid)))])
+            wav = self._take(sid, min(full, self.buffered(sid)))
+            (c,) = self.pool.encode([sid], [wav])
             self._codes[sid].append(c)
+            if self.features is not None:
+                ended = self.buffered(sid) == 0
+                self.features.feed([sid], [wav], ended)
         codes, self._codes[sid] = self._codes[sid], []
         if not codes:
             raise ValueError(f"stream {sid}: a turn without samples")
+        if self.features is not None and not ended:                      # every sample was encoded by a pump: an empty last range
+            self.features.feed([sid], [torch.empty(0, dtype=torch.float32)], True)
         self.pool.reset([sid])
         return Segment(speaker=speaker, text=text, audio=None, audio_codes=torch.cat(codes, dim=1))
+
+    def take_features(self, sid: int):
+        """The oldest ended turn of stream ``sid`` whose features have not been taken: ``(features (n_mels, 3000), n_frames)``."""
+        assert self.features is not None, "TurnStreams without features"
+        return self.features.take(int(sid))
 
     # -- with a voice-activity detector ---------------------------------------------------------------
     def poll_events(self) -> List[Tuple[int, str, int]]:
@@ -175,6 +201,8 @@ class TurnStreams:
             sent += n
         codes, self._codes[sid] = self._codes[sid], []
         self.pool.reset([sid])
+        if self.features is not None:                                    # what the turn's features lack of [a, b), and the end of the clip
+            self.features.feed([sid], [self._samples(sid, self._fsent[sid], b)], True)
         self._ready[sid].append(torch.cat(codes, dim=1)[:, :T])
         self._turn[sid], self._cut[sid] = None, end
         self._events.append((sid, "end", end))
@@ -203,6 +231,7 @@ class TurnStreams:
                     if kind == "start" and self._turn[s] is None:
                         a = max(self._cut[s], f * F - self.pre_roll, self._h0[s], 0)
                         self._turn[s] = [a, a]
+                        self._fsent[s] = a
                         self._events.append((s, "start", a))
                     elif kind == "end" and self._turn[s] is not None:        # (None: finish has ended the turn by hand)
                         self._close(s, f * F + self.post_roll)
@@ -212,6 +241,8 @@ class TurnStreams:
                 t = self._turn[s]
                 if t is not None:
                     keep = min(t[1], max((self._judged[s] - prm.hang + 1) * F + self.post_roll, 0))
+                    if self.features is not None:
+                        keep = min(keep, self._fsent[s])
                 else:
                     keep = max(self._cut[s], (self._judged[s] - prm.min_on + 1) * F - self.pre_roll, 0)
                 keep = min(max(keep, self._h0[s]), self._recv[s])
@@ -219,6 +250,8 @@ class TurnStreams:
         ids = [s for s in sorted(self._turn) if self._turn[s] is not None and self.buffered(s) >= self.hop]
         if not ids:
             return 0
+        if self.features is not None:
+            self._feed_features_vad(ids)
         wavs = []
         for s in ids:
             t = self._turn[s]
@@ -232,15 +265,34 @@ class TurnStreams:
         return total
 
 
+    def _feed_features_vad(self, ids: List[int]) -> None:
+        """ONE ``features.feed`` over the streams about to be encoded: each turn's samples up to where this pump's encode call will stand,
+        but no further than a coming END may still cut -- END frame f >= judged - hang + 1 ends the audio at f * 240 + post_roll."""
+        F, fids, chunks = self.VAD_FRAME, [], []
+        for s in ids:
+            t = self._turn[s]
+            upto = t[1] + min(self.chunk_frames, self.buffered(s) // self.hop) * self.hop
+            safe = min(upto, max((self._judged[s] - self.vad.params[s].hang + 1) * F + self.post_roll, 0))
+            if safe > self._fsent[s]:
+                fids.append(s)
+                chunks.append(self._samples(s, self._fsent[s], safe))
+                self._fsent[s] = safe
+        if fids:
+            self.features.feed(fids, chunks, False)
+
+
 class ReplyOnPause:
     """The reference's ``ReplyOnPause(respond, can_interrupt=True)`` over a ``TurnStreams`` with a vad: ``receive(sid, samples)`` feeds a
     microphone and pumps; at every END ``respond(sid, segment)`` is called, where ``segment(speaker, text)`` gives the turn's ``Segment``
     (``TurnStreams.finish``), and the stream's reply counts as in flight until ``reply_done(sid)``; a START that arrives meanwhile calls
-    ``on_interrupt(sid)`` once (barge-in) and ends the flight.  Host logic only."""
+    ``on_interrupt(sid)`` once (barge-in) and ends the flight.  With ``stt`` (a callable ``(features, n_frames) -> str``, such as
+    ``sesameai.stt.WhisperSTT``, over ``TurnStreams(features=)``) an END calls ``respond(sid, segment, text)`` with the transcribed
+    text, and ``segment(speaker, text=None)`` puts it into the ``Segment`` unless another is given.  Host logic only."""
 
-    def __init__(self, turns: TurnStreams, respond: Callable, on_interrupt: Optional[Callable] = None):
+    def __init__(self, turns: TurnStreams, respond: Callable, on_interrupt: Optional[Callable] = None, stt: Optional[Callable] = None):
         assert turns.vad is not None, "ReplyOnPause needs TurnStreams with a vad"
-        self.turns, self.respond, self.on_interrupt = turns, respond, on_interrupt
+        assert stt is None or turns.features is not None, "stt needs TurnStreams with features"
+        self.turns, self.respond, self.on_interrupt, self.stt = turns, respond, on_interrupt, stt
         self.in_flight: Dict[int, bool] = {}
 
     def reply_done(self, sid: int) -> None:
@@ -259,5 +311,9 @@ class ReplyOnPause:
                 self.in_flight[s] = False
             else:
                 self.in_flight[s] = True
-                self.respond(s, lambda speaker, text, s=s: self.turns.finish(s, speaker, text))
+                if self.stt is None:
+                    self.respond(s, lambda speaker, text, s=s: self.turns.finish(s, speaker, text))
+                else:
+                    said = self.stt(*self.turns.take_features(s))
+                    self.respond(s, lambda speaker, text=None, s=s, said=said: self.turns.finish(s, speaker, said if text is None else text), said)
         return len(events)
