@@ -698,6 +698,55 @@ int  mimi_mel_pool_feed(mimi_mel_pool p, const int32_t* streams, const long* in_
 int  mimi_mel_finish(const float* raw, const long* off, const long* n_frames, int n, int n_mels, float* out, void* stream);
 const char* mimi_mel_last_error(void);
 
+/* ---- THE WHISPER ENCODER: the recogniser's hot path (tests/whisper_enc_ref.py states the rule in float64 torch) ----
+ * What stands between the log-mel features above and the text is a Whisper-family model; its encoder runs all n_ctx positions of every
+ * turn, however short, and distil-whisper keeps the whole of it.  This is that encoder, the forward of transformers' WhisperEncoder:
+ *   1. conv1 (k = 3, pad 1) + GELU over the (n_mels, 2 n_ctx) features; conv2 (k = 3, stride 2, pad 1: output t reads inputs 2t - 1, 2t,
+ *      2t + 1, zero outside) + GELU; transposed to (n_ctx, d); + embed_positions.
+ *   2. L pre-LN layers: x += out_proj(attention(LN(x))); x += fc2(GELU(fc1(LN(x)))).  Self-attention has a bias on q, v and out and NONE
+ *      on k; q is scaled by head_dim^-0.5 = 0.125; there is NO mask.  GELU is the erf form.
+ *   3. a final LayerNorm.
+ * Head dim is 64, as in every Whisper size: create refuses d_model != 64 n_heads.
+ * NUMERICAL RULE.  fp16 operands on v_mfma_f32_32x32x16_f16, fp32 everything else (Whisper checkpoints are published in fp16: the weights
+ * stay exact).  The residual stream is fp32 in device memory from conv2 + positions to the final LayerNorm.  Rounded to fp16 exactly
+ * here and nowhere else: the input features; every weight matrix, once at create; conv1's GELU output; each LayerNorm output but the
+ * last; q (after bias and the exact x 0.125), k and v; the softmax numerators P (the running sum takes them unrounded); the attention
+ * output; fc1's GELU output.  Kept in fp32: biases, LayerNorm parameters, positions, accumulators, scores, the softmax with its running
+ * maximum and sum, erff, the LayerNorm statistics (two passes).  Every output element's K chain has ONE fixed order (k ascending, one
+ * accumulator), whatever the batch size, the clip's place in the batch or the tile shape a launch picked; no split-K, no atomics.  So a
+ * clip's output has the same bits alone, at any position in a batch of any size, and on a repeated call; a non-finite feature stays
+ * inside its own clip.  A key tile's missing keys (n_ctx is no multiple of 32) give nothing to the maximum and exactly 0 to the sum.
+ * Weights: fp32 pointers named after model.get_encoder().state_dict(), all in host memory (host = 1) or all in device memory (host = 0);
+ * matrices are (out, in) row-major, the convolutions (out, in, 3).  They are converted once at create, which synchronises; a matrix value
+ * that does not fit fp16, or any value that is not finite, fails create with the tensor's name (host weights: before any device call).
+ * encode: features (batch, n_mels, 2 n_ctx) fp32 as mimi_mel_finish writes them, out (batch, n_ctx, d_model) in out_fmt (0 = fp32,
+ * 1 = fp16, 2 = bf16: the fp32 value rounded to nearest even), both device memory; 2 + 7 n_layers + 1 launches on `stream`, no host
+ * synchronisation, no allocation, no host-to-device copy.  One encode at a time per handle: the handle owns the activations.
+ * describe: the launch plan of an encode of `batch` clips as text; returns the bytes the whole text takes, writes at most cap.
+ * Returns -1 with a message (mimi_wenc_last_error; h == NULL: this thread's create error) and NO device call for: a null pointer, n_mels
+ * not 80 or 128, n_heads outside [1, 20], d_model != 64 n_heads, n_layers outside [1, 32], n_ctx outside [1, 1500], ffn_dim no multiple
+ * of 64 in [64, 8192], ln_eps outside (0, 1), max_batch outside [1, 64]; encode: batch outside [1, max_batch], an unknown format, a
+ * misaligned buffer.  -2: a HIP error; a create that fails frees everything it took.                                                    */
+#define MIMI_WENC_MAX_LAYERS 32
+#define MIMI_WENC_MAX_CTX 1500
+#define MIMI_WENC_MAX_BATCH 64
+typedef struct MimiWenc* mimi_wenc;
+typedef struct { int32_t n_mels, d_model, n_layers, n_heads, ffn_dim, n_ctx; float ln_eps; } MimiWencConfig;
+typedef struct {
+    const float *self_attn_layer_norm_w, *self_attn_layer_norm_b, *q_w, *q_b, *k_w, *v_w, *v_b, *out_w, *out_b;
+    const float *final_layer_norm_w, *final_layer_norm_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+} MimiWencLayerWeights;
+typedef struct {
+    int32_t host;                                                  /* 1: every pointer is host memory; 0: device memory */
+    const float *conv1_w, *conv1_b, *conv2_w, *conv2_b, *embed_positions, *layer_norm_w, *layer_norm_b;
+    MimiWencLayerWeights layers[MIMI_WENC_MAX_LAYERS];
+} MimiWencWeights;
+int  mimi_wenc_create(const MimiWencConfig* cfg, const MimiWencWeights* w, int max_batch, mimi_wenc* out);
+void mimi_wenc_destroy(mimi_wenc h);
+const char* mimi_wenc_last_error(mimi_wenc h);                 /* h == NULL: why mimi_wenc_create failed (this thread) */
+int  mimi_wenc_encode(mimi_wenc h, const float* features, int batch, void* out, int out_fmt, void* stream);
+int  mimi_wenc_describe(mimi_wenc h, int batch, char* text, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,11 @@ MIMI_SIGNATURES = {
     "mimi_mel_pool_feed": (_i, [_vp, _vp, C.POINTER(_l), C.POINTER(_l), _vp, _i, _vp, _i, _vp, C.POINTER(_l), _vp]),
     "mimi_mel_finish": (_i, [_vp, C.POINTER(_l), C.POINTER(_l), _i, _i, _vp, _vp]),
     "mimi_mel_last_error": (C.c_char_p, []),
+    "mimi_wenc_create": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
+    "mimi_wenc_destroy": (None, [_vp]),
+    "mimi_wenc_last_error": (C.c_char_p, [_vp]),
+    "mimi_wenc_encode": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "mimi_wenc_describe": (_i, [_vp, _i, _vp, _i]),
     "mimi_ts_pool_create": (_i, [_i, C.POINTER(_vp)]),
     "mimi_ts_pool_destroy": (None, [_vp]),
     "mimi_ts_pool_last_error": (C.c_char_p, [_vp]),

@@ -7,8 +7,8 @@ matrix product on the matrix cores), ``finish`` turns a clip's rows into the ``(
 over any chunk schedule, are bit for bit its one-shot rows (tests/mel_ref.py states the rule in float64).  ``TurnFeatures`` puts a
 resampler in front, for ``TurnStreams(features=)``.  All arithmetic is the library's; this file marshals.
 
-Not built: turns longer than 30 s (Whisper's long-form windows: samples past 480,000 are counted and dropped), a recogniser of our own,
-``generate_stream`` at B = 1, a C-host example."""
+Not built: turns longer than 30 s (Whisper's long-form windows: samples past 480,000 are counted and dropped), the recogniser's decoder
+(its encoder is sesameai/whisper_enc.py), ``generate_stream`` at B = 1, a C-host example."""
 from __future__ import annotations
 
 import ctypes as C
